@@ -64,6 +64,9 @@ def parse():
                         "300 s limit; if they fail or are switched off the committed profiles/pmc_traffic.json is quoted, with its provenance")
     p.add_argument("--configs", default=",".join(EXTRA_CONFIGS),
                    help="extra single-GPU configurations reported under \"configs\" (N=1 only); \"\" or none: skip")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed iterations of the headline run, write what the last one computed (parameters, Adam state, the "
+                        "rollout storage: a fixed seeded sample of envs where it is wide) as DIR/<name>.npy, float32 / float64, rank 0")
     return p.parse_args()
 
 
@@ -214,6 +217,44 @@ def cpu_baseline(num_envs, T=60, full_minibatch=True, allow_reference=True):
 
 
 # ------------------------------------------------------------------------------------------------ GPU runs
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_ENVS_NARROW, DUMP_ENVS_WIDE = 4096, 64      # envs kept of the (T, N) columns / of the wide rows (actions, observations)
+
+
+def dump_outputs(runner, out_dir):
+    """What learn() leaves a caller after its last iteration, as out_dir/<name>.npy: the parameters and the optimizer state after the
+    last update, and that iteration's rollout storage (transitions, returns, advantages, the T + 1 observation slots).  Where the storage
+    is wide the same seeded sample of envs is kept on every run (numpy default_rng(0)), so that the files stay below DUMP_LIMIT_BYTES
+    at any env count.  Everything is written as float32, the optimizer's fp64 state as float64."""
+    import numpy as np
+    net, st = runner.alg.net, runner.alg.storage
+    N = st.num_envs
+    rng = np.random.default_rng(0)
+    narrow = np.sort(rng.choice(N, size=min(N, DUMP_ENVS_NARROW), replace=False))
+    wide = np.sort(rng.choice(narrow, size=min(len(narrow), DUMP_ENVS_WIDE), replace=False))
+
+    def host(t, envs=None, dim=1):
+        t = t.detach()
+        if envs is not None:
+            t = t.index_select(dim, torch.as_tensor(envs, device=t.device))
+        return t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+    arrays = dict(params=host(net.params), adam_m=host(net.adam_m), adam_v=host(net.adam_v), opt_state=host(net.opt_state))
+    for name in ("rewards", "dones", "values", "returns", "advantages", "actions_log_prob"):
+        arrays[name] = host(getattr(st, name), narrow)
+    for name in ("actions", "mu", "sigma"):
+        arrays[name] = host(getattr(st, name), wide)
+    arrays["observations"] = host(st._obs_all, wide)
+    if st._priv_all is not None:
+        arrays["privileged_observations"] = host(st._priv_all, wide)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
+
+
 def collect_pmc_traffic(num_envs=4096):
     """roofline.traffic measured in this run: rocprofv3 --kernel-trace --pmc <counter> (one pass per counter, as
     MI355X_MICROARCH.md's HBM section prescribes) around tools/traffic_run.py -- a 256 MiB streaming kernel for the FETCH_SIZE
@@ -309,9 +350,10 @@ def _roofline(L, runner, elapsed_per_iter_ms, precision, n_profiled_iters, traff
     return ks
 
 
-def run_config(args, task, num_envs, rank, world, local, dist, steps, warmup, log_root=None, want_roofline=True, quiet=False):
+def run_config(args, task, num_envs, rank, world, local, dist, steps, warmup, log_root=None, want_roofline=True, quiet=False, dump_dir=None):
     """Builds env + runner for one configuration, W warm-up iterations, K timed ones (barrier + synchronize on both sides, max
-    over ranks), optionally two more eager iterations under the library's HIP-event hooks for the roofline."""
+    over ranks), optionally two more eager iterations under the library's HIP-event hooks for the roofline.  dump_dir: rank 0 writes
+    what the last timed iteration computed there (dump_outputs), before anything else runs on the runner."""
     from humanoid.envs import task_registry
     from humanoid.utils import get_args
     from hgym import _lib as L
@@ -355,6 +397,8 @@ def run_config(args, task, num_envs, rank, world, local, dist, steps, warmup, lo
         if hasattr(runner, "wait_for_saves"):
             runner.wait_for_saves()
         ckpt_wait_s = time.perf_counter() - t1
+    if dump_dir is not None and rank == 0:
+        dump_outputs(runner, dump_dir)
     tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if dist is not None:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -603,7 +647,7 @@ def main():
                 args.pmc_by_envs[8192] = r8
         del os.environ["HGYM_BENCH_CHILD"]
     head = run_config(args, args.task, args.num_envs, rank, world, local, dist, args.steps, args.warmup,
-                      want_roofline=not args.no_roofline)
+                      want_roofline=not args.no_roofline, dump_dir=args.dump_outputs)
     T, N = head["T"], head["N"]
     extra = []
     want = [c for c in args.configs.split(",") if c and c != "none"]

@@ -118,3 +118,37 @@ def test_rank_placement_partitions_the_allowed_cores(monkeypatch):
         assert b.place_rank_on_host(0, world)["pinned"] is False
     finally:
         torch.set_num_threads(nt)
+
+
+def test_dump_outputs_writes_a_fixed_bounded_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float32 / float64 .npy files of what the last timed iteration left (parameters, Adam state, rollout storage), the
+    same seeded env sample on every call, under 64 MB; a storage wider than the sample is cut to it."""
+    import types
+    import numpy as np
+    import torch
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--dump-outputs", str(tmp_path / "a")])
+    assert b.parse().dump_outputs == str(tmp_path / "a")
+    T, N, A = 3, b.DUMP_ENVS_NARROW + 7, 2
+    g = torch.Generator().manual_seed(0)
+    f = lambda *s: torch.randn(*s, generator=g)
+    st = types.SimpleNamespace(num_envs=N, _obs_all=f(T + 1, N, 5), _priv_all=f(T + 1, N, 4), rewards=f(T, N, 1),
+                               dones=(f(T, N, 1) > 1).to(torch.uint8), values=f(T, N, 1), returns=f(T, N, 1), advantages=f(T, N, 1),
+                               actions_log_prob=f(T, N, 1), actions=f(T, N, A), mu=f(T, N, A), sigma=f(T, N, A))
+    net = types.SimpleNamespace(params=f(11), adam_m=f(11), adam_v=f(11), opt_state=f(16).double())
+    runner = types.SimpleNamespace(alg=types.SimpleNamespace(net=net, storage=st))
+    total = b.dump_outputs(runner, str(tmp_path / "a"))
+    b.dump_outputs(runner, str(tmp_path / "b"))
+    names = sorted(os.listdir(str(tmp_path / "a")))
+    assert names == sorted(os.listdir(str(tmp_path / "b"))) and "params.npy" in names and "observations.npy" in names
+    assert 0 < total <= b.DUMP_LIMIT_BYTES == 64 << 20
+    for n in names:
+        x, y = np.load(str(tmp_path / "a" / n)), np.load(str(tmp_path / "b" / n))
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), n
+    assert np.load(str(tmp_path / "a" / "opt_state.npy")).dtype == np.float64
+    np.testing.assert_array_equal(np.load(str(tmp_path / "a" / "params.npy")), net.params.numpy())
+    rew, obs = np.load(str(tmp_path / "a" / "rewards.npy")), np.load(str(tmp_path / "a" / "observations.npy"))
+    assert rew.shape == (T, b.DUMP_ENVS_NARROW, 1) and obs.shape == (T + 1, b.DUMP_ENVS_WIDE, 5)
+    # the wide sample is a subset of the narrow one: its rows are columns of the full storage
+    full = st._obs_all.numpy()
+    assert all(any(np.array_equal(obs[:, k], full[:, e]) for e in range(N)) for k in range(3))
