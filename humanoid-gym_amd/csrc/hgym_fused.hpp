@@ -954,6 +954,24 @@ constexpr int FB_LIN_ACTOR = 40;      // floats per row
 HG_HD int fb_lds_lin(const FusedNet& n) { return n.layer[3].N == 1 ? 64 * 2 * 4 : (n.layer[3].N <= 12 ? 64 * FB_LIN_ACTOR * 4 : 0); }
 HG_HD int fb_lds_extra(const FusedNet& n) { return 64 * 64 * n.layer[3].NBB + 4 * 32 * 4 + 64 * n.layer[2].N * 2 + 256 + fb_lds_lin(n); }
 
+// Dynamic LDS the update's tiles of a net ask for, and the most a workgroup may have.  A net takes the fused path only if its
+// mlp_fb_kernel tile fits (hgym_net.hip: fused_supported / fused_aux_supported, and the launch itself).  This also covers the forward:
+// mlp_fwd_kernel's 64-row tile needs P + Q + bias of the same sum, and its 32-row tile less.
+constexpr size_t FB_LDS_LIMIT = 160 * 1024;
+HG_HD int fb_lds_bytes(const FusedNet& n) { return fused_lds_p(n, 64) + fused_lds_q(n, 64) + fused_lds_bias(n) + fb_lds_extra(n); }
+// the same from the net's widths (dims[0] = input .. dims[4] = head), before any workspace exists: the fields the sum reads,
+// filled the way the workspace layout fills them (hgym_net.hip: ws_layout)
+inline int fb_lds_bytes(const int32_t* dims) {
+    FusedNet n{};
+    for (int l = 0; l < 4; ++l) {
+        n.layer[l].K = dims[l];
+        n.layer[l].N = dims[l + 1];
+        n.layer[l].NB = (dims[l + 1] + 15) / 16;
+        n.layer[l].NBB = (dims[l + 1] + 31) / 32;
+    }
+    return fb_lds_bytes(n);
+}
+
 template <int G1, bool AUX = false, bool XB16 = false>
 __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const FusedNet& n, bool is_actor, char* smem) {
     constexpr int BM = 64, NW = 16, D = 2, MB = BM / 16;

@@ -75,6 +75,7 @@ static bool fused_supported(const HgymNetConfig* c) {
         if (d[1] % 128 || !(g1 == 2 || g1 == 4 || g1 == 6)) return false;
         if (d[2] % 128 || d[2] > 768 || d[3] % 128 || d[3] > 768) return false;
         if (d[4] > 16) return false;
+        if ((size_t)fb_lds_bytes(d) > FB_LDS_LIMIT) return false;      // the update's tile must fit (hgym_fused.hpp: fb_lds_bytes)
     }
     return true;
 }
@@ -84,7 +85,7 @@ static bool fused_aux_supported(const HgymNetConfig* c) {
     const int32_t* d = c->aux_dims;
     if (d[1] != 512) return false;         // the wide-head instantiation of the forward exists for this first width only
     if (d[2] % 128 || d[2] > 768 || d[3] % 128 || d[3] > 768) return false;
-    return d[4] > 16 && d[4] <= 96;
+    return d[4] > 16 && d[4] <= 96 && (size_t)fb_lds_bytes(d) <= FB_LDS_LIMIT;
 }
 constexpr int MAX_SPLITS = 32;
 
@@ -1031,9 +1032,8 @@ struct NetRunner {
             fl.aux_coef = ppo.aux_coef;
             size_t lds = 0;
             for (int i = 0; i < nets; ++i)
-                lds = std::max(lds, (size_t)fused_lds_p(fa.net[i], 64) + (size_t)fused_lds_q(fa.net[i], 64) + (size_t)fused_lds_bias(fa.net[i]) +
-                                        (size_t)fb_lds_extra(fa.net[i]));
-            HG_REQUIRE(lds <= 160 * 1024, HGYM_E_UNSUPPORTED, "mlp_fb_kernel needs %zu bytes of LDS", lds);
+                lds = std::max(lds, (size_t)fb_lds_bytes(fa.net[i]));       // the nets the kernel receives (fused_supported: same sum)
+            HG_REQUIRE(lds <= FB_LDS_LIMIT, HGYM_E_UNSUPPORTED, "mlp_fb_kernel needs %zu bytes of LDS", lds);
             FwdArgs fb = fa;
             fb.nets = nets;
             fb.dbg = phase_buffer((int64_t)tiles * nets);

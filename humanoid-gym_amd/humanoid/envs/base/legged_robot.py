@@ -443,6 +443,9 @@ class LeggedRobot(BaseTask):
         ok = bool(own_step and not generic and not c.use_ref_actions and c.frame_stack == 15 and c.c_frame_stack == 3 and self.num_envs % 32 == 0
                   and nc.precision == self._L.BF16 and nc.actor_layers == 4 and nc.critic_layers == 4 and nc.actor_dims[1] == 512
                   and nc.critic_dims[1] == 768 and nc.num_actions == 12 and getattr(self.cfg.env, "send_timeouts", False))
+        # ... and only on a net that took the fused kernels: a bf16 net whose update tile does not fit in LDS runs the generic path
+        # (hgym_net_shadow_ld = 0 there), which hgym_rollout_step refuses
+        ok = ok and net.shadow_ld(0) > 0
         if not ok:
             return None
         want = os.environ.get("HGYM_ROLLOUT_CRITIC", "auto").lower()
