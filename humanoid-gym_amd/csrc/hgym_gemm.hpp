@@ -41,7 +41,20 @@ template <> struct ElemTraits<__bf16> {
 };
 template <typename T> constexpr int stage_elems() { return ElemTraits<T>::kFragK * KSTAGE; }
 
-enum { ACT_NONE = 0, ACT_ELU = 1 };
+enum { ACT_NONE = 0, ACT_APPLY = 1 };
+
+// The hidden layers' activation (HgymNetConfig.activation), resolved by the host (act_resolve, hgym_net.hip): defaults filled in,
+// SELU folded into the ELU form.  act_fwd_tile / act_bwd_tile apply it on the generic path with libm (fp32 parity within
+// 1e-5 of torch).  The fused bf16 kernels (hgym_fused.hpp) implement ELU(1) only: a configuration with any other activation
+// takes this path (fused_supported, hgym_net.hip).
+struct Act {
+    int kind;            // HGYM_ACT_ELU (also SELU), HGYM_ACT_LEAKY_RELU, HGYM_ACT_TANH, HGYM_ACT_SIGMOID
+    float alpha, scale;  // ELU: scale * (z > 0 ? z : alpha * (exp(z) - 1)); LeakyReLU: alpha = the negative slope
+    // f'(z) from y = f(z), one branch-free form for every kind: c0 + y * (c1 - dq * y), (c0, c1) = y > 0 ? (d0p, d1p) : (d0n, d1n).
+    // ELU: (scale, 0) / (scale alpha, 1), dq 0 -- for ELU(1) exactly y > 0 ? 1 : y + 1; LeakyReLU: (1, 0) / (alpha, 0), dq 0;
+    // Tanh: (1, 0) both, dq 1 (1 - y^2); Sigmoid: (0, 1) both, dq 1 (y (1 - y)).
+    float d0p, d1p, d0n, d1n, dq;
+};
 
 struct GemmArgs {
     const void* A;     // [rowsA][lda]  K-contiguous
@@ -55,8 +68,9 @@ struct GemmArgs {
     int64_t ldcf;
     int64_t slab_stride;
     const float* bias;  // optional [N]
-    int act;            // ACT_*
-    const void* aux;    // optional [M][ldaux] operand-type matrix y = elu(z): output is multiplied by elu'(z) = y>0 ? 1 : y+1
+    int act;            // ACT_*: ACT_APPLY applies fn to the output
+    Act fn;
+    const void* aux;    // optional [M][ldaux] operand-type matrix y = fn(z): the output is multiplied by fn'(z), taken from y
     int64_t ldaux;
     int k_chunk;        // K range per split (multiple of stage_elems); K itself when not split
 };
@@ -69,6 +83,33 @@ template <> __device__ __forceinline__ float to_f32<__bf16>(__bf16 v) { return (
 template <typename T> __device__ __forceinline__ T from_f32(float v);
 template <> __device__ __forceinline__ float from_f32<float>(float v) { return v; }
 template <> __device__ __forceinline__ __bf16 from_f32<__bf16>(float v) { return (__bf16)v; }
+
+// v = fn(v): one branch on the (uniform) kind, the unrolled element loops inside each case; ELU(1) is elu_f, to the bit.
+// d *= fn'(z), taken from the operand-type y = fn(z) (PK: 4 elements of T per fragment), in Act's parametric form.
+#define HG_ACT_LOOP(BODY)                                       \
+    _Pragma("unroll") for (int i = 0; i < TM; ++i)              \
+        _Pragma("unroll") for (int j = 0; j < TN; ++j)          \
+            _Pragma("unroll") for (int r = 0; r < 4; ++r) { BODY; }
+template <int TM, int TN>
+__device__ __forceinline__ void act_fwd_tile(f32x4 (&v)[TM][TN], const Act& a) {
+    const float al = a.alpha, sc = a.scale;
+    switch (a.kind) {
+        case HGYM_ACT_LEAKY_RELU: HG_ACT_LOOP(const float z = v[i][j][r]; v[i][j][r] = z > 0.0f ? z : al * z) break;
+        case HGYM_ACT_TANH: HG_ACT_LOOP(v[i][j][r] = tanhf(v[i][j][r])) break;
+        case HGYM_ACT_SIGMOID: HG_ACT_LOOP(v[i][j][r] = 1.0f / (1.0f + expf(-v[i][j][r]))) break;
+        default:
+            if (al == 1.0f && sc == 1.0f) HG_ACT_LOOP(v[i][j][r] = elu_f(v[i][j][r]))
+            else HG_ACT_LOOP(const float z = v[i][j][r]; v[i][j][r] = z > 0.0f ? sc * z : sc * (al * (expf(z) - 1.0f)))
+            break;
+    }
+}
+template <typename T, int TM, int TN, class PK>
+__device__ __forceinline__ void act_bwd_tile(f32x4 (&d)[TM][TN], const PK (&y)[TM][TN], const Act& a) {
+    // (no branch on the kind here: with one, the compiler converts every y of the tile ahead of it -- 60 more live registers)
+    HG_ACT_LOOP(const float t = to_f32<T>(y[i][j].e[r]); const bool p = t > 0.0f;
+                d[i][j][r] *= fmaf(t, fmaf(-a.dq, t, p ? a.d1p : a.d1n), p ? a.d0p : a.d0n))
+}
+#undef HG_ACT_LOOP
 
 template <typename T> __device__ __forceinline__ void mma_frag(u32x4 w, u32x4 x, f32x4& acc);
 template <> __device__ __forceinline__ void mma_frag<__bf16>(u32x4 w, u32x4 x, f32x4& acc) {
@@ -200,15 +241,16 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_nt_kernel(const Ge
                 }
             }
         }
+        act_bwd_tile<T, TM, TN>(acc, ax, g.fn);   // fn'(z) from y = fn(z)
+    }
+    if (g.act == ACT_APPLY) {
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
             for (int j = 0; j < TN; ++j)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float y = to_f32<T>(ax[i][j].e[r]);
-                    acc[i][j][r] *= (y > 0.0f) ? 1.0f : (y + 1.0f);   // elu'(z) from y = elu(z)
-                }
+                for (int r = 0; r < 4; ++r) acc[i][j][r] += bias_r[j][r];
+        act_fwd_tile<TM, TN>(acc, g.fn);
     }
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
@@ -220,10 +262,7 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_nt_kernel(const Ge
             if (nb >= g.N) continue;
             float v[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                v[r] = acc[i][j][r] + bias_r[j][r];
-                if (g.act == ACT_ELU) v[r] = elu_f(v[r]);
-            }
+            for (int r = 0; r < 4; ++r) v[r] = g.act == ACT_APPLY ? acc[i][j][r] : acc[i][j][r] + bias_r[j][r];   // (ACT_APPLY: bias and fn applied above)
             const bool full = nb + 3 < g.N;
             if (Cf) {
                 float* p = Cf + (int64_t)m * g.ldcf + nb;

@@ -58,6 +58,7 @@ struct WsLayout {
     int64_t sqn;             // [SQN_BLOCKS] fp64 per-workgroup sums of sqnorm_prologue_kernel + its arrival counter (zero between launches)
     int64_t total_bytes;
     int fused;               // 1: bf16 fast path (three fused kernels) is usable for this configuration
+    Act act;                 // the hidden layers' activation (HgymNetConfig.activation, resolved)
     int64_t Mpad;            // fused path: batch padded to the 64-row tile
     int dw_splits;
 };
@@ -89,6 +90,45 @@ static bool fused_aux_supported(const HgymNetConfig* c) {
 }
 constexpr int MAX_SPLITS = 32;
 
+// HgymNetConfig.activation / act_alpha / act_scale -> struct Act (hgym_gemm.hpp): defaults filled in, SELU as the ELU form.
+// Refuses what the derivative-from-y design cannot carry.
+static int32_t act_resolve(const HgymNetConfig* c, Act* a) {
+    memset(a, 0, sizeof(*a));
+    const int k = c->activation;
+    const float al = c->act_alpha, sc = c->act_scale;
+    HG_REQUIRE(k >= HGYM_ACT_ELU && k <= HGYM_ACT_SIGMOID, HGYM_E_UNSUPPORTED,
+               "activation=%d: not one of HGYM_ACT_ELU, _SELU, _LEAKY_RELU, _TANH, _SIGMOID", k);
+    // (written so that a NaN fails it)
+    HG_REQUIRE(al >= 0.0f && al < INFINITY && sc >= 0.0f && sc < INFINITY, HGYM_E_BADARG,
+               "activation %d: act_alpha=%g, act_scale=%g must be finite and >= 0 (a negative alpha, slope or scale would break "
+               "sign(f(z)) = sign(z), from which the backward takes the derivative)", k, al, sc);
+    a->kind = k;
+    if (k == HGYM_ACT_ELU || k == HGYM_ACT_SELU) {
+        a->kind = HGYM_ACT_ELU;
+        a->alpha = al != 0.0f ? al : (k == HGYM_ACT_SELU ? 1.6732632423543772f : 1.0f);
+        a->scale = sc != 0.0f ? sc : (k == HGYM_ACT_SELU ? 1.0507009873554805f : 1.0f);
+        a->d0p = a->scale;
+        a->d0n = a->scale * a->alpha;
+        a->d1n = 1.0f;
+        return HGYM_OK;
+    }
+    HG_REQUIRE(sc == 0.0f, HGYM_E_BADARG, "activation %d: act_scale=%g is used by ELU / SELU only and must be 0", k, sc);
+    HG_REQUIRE(k == HGYM_ACT_LEAKY_RELU || al == 0.0f, HGYM_E_BADARG, "activation %d: act_alpha=%g is not used by Tanh / Sigmoid and must be 0",
+               k, al);
+    a->alpha = al;
+    if (k == HGYM_ACT_LEAKY_RELU) {
+        a->d0p = 1.0f;
+        a->d0n = al;
+    } else {
+        a->dq = 1.0f;
+        a->d0p = a->d0n = k == HGYM_ACT_TANH ? 1.0f : 0.0f;
+        a->d1p = a->d1n = k == HGYM_ACT_TANH ? 0.0f : 1.0f;
+    }
+    return HGYM_OK;
+}
+// the activation the fused bf16 kernels implement (their epilogues and dZ chain are ELU(1) only)
+static bool act_is_elu1(const Act& a) { return a.kind == HGYM_ACT_ELU && a.alpha == 1.0f && a.scale == 1.0f; }
+
 static int32_t ws_layout(const HgymNetConfig* c, WsLayout* w) {
     HG_REQUIRE(c, HGYM_E_BADARG, "null net config");
     HG_REQUIRE(c->precision == HGYM_F32 || c->precision == HGYM_BF16, HGYM_E_BADARG, "precision=%d", c->precision);
@@ -101,11 +141,13 @@ static int32_t ws_layout(const HgymNetConfig* c, WsLayout* w) {
     HG_REQUIRE(c->num_actions >= 1 && c->num_actions <= 12, HGYM_E_UNSUPPORTED, "num_actions=%d (loss kernel reduces <=12 per-action sums)",
                c->num_actions);
     memset(w, 0, sizeof(*w));
+    const int32_t rc_act = act_resolve(c, &w->act);
+    if (rc_act) return rc_act;
     w->es = c->precision == HGYM_F32 ? 4 : 2;
     w->SE = c->precision == HGYM_F32 ? stage_elems<float>() : stage_elems<__bf16>();
     w->maxM = c->max_batch;
     w->Mp = round_up(c->max_batch, w->SE);
-    w->fused = fused_supported(c) ? 1 : 0;
+    w->fused = fused_supported(c) && act_is_elu1(w->act) ? 1 : 0;
     w->Mpad = round_up(c->max_batch, 64);
     int64_t off = 0, poff = c->num_actions;  // std first (state_dict order)
     auto take = [&](int64_t bytes) {
@@ -1155,7 +1197,8 @@ struct NetRunner {
                 g.Cf = y_out;
                 g.ldcf = ld_out;
             } else {
-                g.act = ACT_ELU;
+                g.act = ACT_APPLY;
+                g.fn = w.act;
                 g.Ct = at<T>(n.layer[l + 1].X);
                 g.ldct = n.layer[l + 1].Kp;
             }
@@ -1195,7 +1238,7 @@ struct NetRunner {
                                    at<T>(y.dYT), w.Mp, net.grads + y.b_off);
                 HG_CHECK_LAUNCH("rowsum_kernel");
             }
-            if (l > 0) {   // dX = (dY * W) .* elu'(X_l)  -> dY of layer l-1
+            if (l > 0) {   // dX = (dY * W) .* f'(z), from X_l = f(z)  -> dY of layer l-1
                 const LayerLayout& p = n.layer[l - 1];
                 GemmArgs g;
                 memset(&g, 0, sizeof(g));
@@ -1210,6 +1253,7 @@ struct NetRunner {
                 g.K = y.Ncp;
                 g.aux = at<T>(y.X);
                 g.ldaux = y.Kp;
+                g.fn = w.act;
                 g.Ct = at<T>(p.dY);
                 g.ldct = p.Ncp;
                 const int32_t rc = launch_gemm<T>(g, 1, s);

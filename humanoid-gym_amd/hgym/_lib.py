@@ -18,6 +18,7 @@ PRIV_FRAME = 73
 MAX_LAYERS = 8
 MAX_CUSTOM_REWARDS = 24
 F32, BF16 = 0, 1
+ACT_ELU, ACT_SELU, ACT_LEAKY_RELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3, 4    # HGYM_ACT_*
 
 c_float_p = C.POINTER(C.c_float)
 c_u8_p = C.POINTER(C.c_uint8)
@@ -106,7 +107,8 @@ class NetConfig(C.Structure):
                 ("actor_layers", C.c_int32), ("critic_layers", C.c_int32),
                 ("actor_dims", C.c_int32 * (MAX_LAYERS + 1)), ("critic_dims", C.c_int32 * (MAX_LAYERS + 1)),
                 ("precision", C.c_int32), ("max_batch", C.c_int32),
-                ("aux_layers", C.c_int32), ("aux_dims", C.c_int32 * (MAX_LAYERS + 1)), ("aux_target_offset", C.c_int32)]
+                ("aux_layers", C.c_int32), ("aux_dims", C.c_int32 * (MAX_LAYERS + 1)), ("aux_target_offset", C.c_int32),
+                ("activation", C.c_int32), ("act_alpha", C.c_float), ("act_scale", C.c_float)]
 
 
 class PPOConfig(C.Structure):

@@ -6,11 +6,40 @@ import torch
 from . import _lib as L
 
 
+SUPPORTED_ACTIVATIONS = "nn.ELU(alpha > 0), nn.SELU(), nn.ReLU(), nn.LeakyReLU(negative_slope >= 0), nn.Tanh(), nn.Sigmoid()"
+
+
+def activation_spec(activation):
+    """(HgymNetConfig.activation, act_alpha, act_scale) of a torch activation module (None: ELU, the reference default).
+    Raises NotImplementedError for anything the kernels do not implement; the exact module types are matched, so a subclass
+    (which may override forward) is refused too."""
+    import torch.nn as nn
+    m = activation
+    if m is None:
+        return L.ACT_ELU, 1.0, 1.0
+    t = type(m)
+    if t is nn.ELU and m.alpha > 0:
+        return L.ACT_ELU, float(m.alpha), 1.0
+    if t is nn.SELU:
+        return L.ACT_SELU, 1.6732632423543772, 1.0507009873554805
+    if t is nn.ReLU:
+        return L.ACT_LEAKY_RELU, 0.0, 0.0
+    if t is nn.LeakyReLU and m.negative_slope >= 0:
+        return L.ACT_LEAKY_RELU, float(m.negative_slope), 0.0
+    if t is nn.Tanh:
+        return L.ACT_TANH, 0.0, 0.0
+    if t is nn.Sigmoid:
+        return L.ACT_SIGMOID, 0.0, 0.0
+    raise NotImplementedError("activation %r is not implemented by the HIP kernels; supported: %s" % (m, SUPPORTED_ACTIVATIONS))
+
+
 def make_net_config(num_obs, num_priv, num_actions, actor_hidden, critic_hidden, precision, max_batch, aux_hidden=None, aux_out=0,
-                    aux_target_offset=0):
+                    aux_target_offset=0, activation=None):
     """aux_hidden / aux_out / aux_target_offset: the optional auxiliary (denoising) head obs -> aux_hidden -> aux_out that regresses
-    columns [aux_target_offset, aux_target_offset + aux_out) of the privileged row (HgymNetConfig.aux_*)."""
+    columns [aux_target_offset, aux_target_offset + aux_out) of the privileged row (HgymNetConfig.aux_*).
+    activation: the torch module between the Linear layers of every MLP (activation_spec; None: ELU)."""
     c = L.NetConfig()
+    c.activation, c.act_alpha, c.act_scale = activation_spec(activation)
     c.num_obs, c.num_priv, c.num_actions = int(num_obs), int(num_priv), int(num_actions)
     ad = [num_obs] + list(actor_hidden) + [num_actions]
     cd = [num_priv] + list(critic_hidden) + [1]

@@ -35,8 +35,9 @@ class ActorCritic(nn.Module):
         if kwargs:
             print("ActorCritic.__init__ got unexpected arguments, which will be ignored: " + str(list(kwargs.keys())))
         super().__init__()
-        if not isinstance(activation, nn.ELU):
-            raise NotImplementedError("the MFMA epilogue implements ELU (the reference default); got %r" % (activation,))
+        from hgym.net import activation_spec
+        activation_spec(activation)          # NotImplementedError (listing what is supported) for anything the kernels lack
+        self.activation = activation
         self.num_actor_obs, self.num_critic_obs, self.num_actions = num_actor_obs, num_critic_obs, num_actions
         self.actor_hidden_dims, self.critic_hidden_dims = list(actor_hidden_dims), list(critic_hidden_dims)
         self.actor = _mlp([num_actor_obs] + self.actor_hidden_dims + [num_actions], activation)

@@ -121,7 +121,8 @@ class PPO:
         aux = getattr(ac, "denoiser_hidden_dims", None)
         cfg = hgym.make_net_config(ac.num_actor_obs, ac.num_critic_obs, ac.num_actions, ac.actor_hidden_dims, ac.critic_hidden_dims,
                                    self.precision, max(mb, num_envs), aux_hidden=aux, aux_out=getattr(ac, "denoiser_targets", 0),
-                                   aux_target_offset=ac.num_critic_obs - getattr(ac, "denoiser_targets", 0))
+                                   aux_target_offset=ac.num_critic_obs - getattr(ac, "denoiser_targets", 0),
+                                   activation=getattr(ac, "activation", None))
         # data-parallel update: the exchange is chosen here, once (HGYM_COMM=auto: the direct kernel over peer mappings is set up,
         # checked and timed against the collective, and used when it is faster; any failure falls back on every rank -- dist_utils).
         # With the direct exchange the gradient vector lives in peer-mapped memory.
@@ -321,7 +322,7 @@ class PPO:
         import ctypes as C
         return (bytes(C.string_at(C.addressof(self._ppo_cfg), C.sizeof(self._ppo_cfg))), self.num_learning_epochs, self.num_mini_batches,
                 float(self.gamma), float(self.lam), self.permutation, self._perm_seed, id(self.storage), id(self.net),
-                bool(dist_utils.active()), bool(self._comm_p2p))
+                bool(dist_utils.active()), bool(self._comm_p2p), bytes(C.string_at(C.addressof(self.net.cfg), C.sizeof(self.net.cfg))))
 
     def after_update_replay(self):
         """Host-side book-keeping of one replayed compute_returns() + update(sync=False): what the Python of those two calls changes on the

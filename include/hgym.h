@@ -43,7 +43,9 @@ extern "C" {
                              * 8: hgym_gae / hgym_gae_bootstrap: `stats` is HGYM_GAE_STATS_DOUBLES(n) doubles (per-workgroup partial sums + arrival
                              *    counter behind the three results), the advantage statistics are summed in a fixed order
                              * 9: hgym_randperm_dev (draw number on the device); hgym_comm_allreduce(seq = 0): the call number kept on the device
-                             *    (status[2]); hgym_comm_sum64 -- what a captured update needs: no launch argument changes between iterations */
+                             *    (status[2]); hgym_comm_sum64 -- what a captured update needs: no launch argument changes between iterations
+                             *    (same version, later: HgymNetConfig.activation / act_alpha / act_scale appended -- ELU, SELU, LeakyReLU / ReLU,
+                             *    Tanh or Sigmoid between the Linear layers; a zero-filled tail is the ELU(1) every earlier layout meant) */
 
 enum {
     HGYM_OK = 0,
@@ -387,6 +389,21 @@ int32_t hgym_gae_bootstrap(int32_t T, int32_t n, float* rewards, const float* va
  * ---------------------------------------------------------------------------------------------- */
 enum { HGYM_F32 = 0, HGYM_BF16 = 1 };
 
+/* Activation between the Linear layers of the actor, the critic and the auxiliary head (the reference's
+ * ActorCritic(activation=...), actor_critic.py:41; one module for every MLP).  HgymNetConfig.act_alpha / act_scale:
+ *   HGYM_ACT_ELU         scale * (z > 0 ? z : alpha * (exp(z) - 1));  alpha 0 -> 1, scale 0 -> 1 (nn.ELU(alpha))
+ *   HGYM_ACT_SELU        the same form; alpha 0 -> 1.6732632423543772, scale 0 -> 1.0507009873554805 (nn.SELU)
+ *   HGYM_ACT_LEAKY_RELU  z > 0 ? z : alpha * z;  alpha = the negative slope >= 0 (0: nn.ReLU), act_scale 0
+ *   HGYM_ACT_TANH, HGYM_ACT_SIGMOID   act_alpha = act_scale = 0
+ * The backward takes the derivative from the stored output y = f(z) (ELU: y > 0 ? scale : y + scale * alpha; LeakyReLU: y > 0 ?
+ * 1 : alpha; Tanh: 1 - y^2; Sigmoid: y (1 - y)), so no kind needs more workspace than another.  Anything else (an unknown kind,
+ * alpha or scale < 0, a parameter a kind does not use set) is refused by hgym_net_param_count / hgym_net_workspace_bytes and
+ * every call taking the configuration.
+ * Supported: every kind at HGYM_F32 and HGYM_BF16 on the layer-by-layer GEMM path; the fused bf16 kernels (hgym_rollout_step, the
+ * update's fused tiles) implement ELU(1) only, so a bf16 configuration with any other activation runs the GEMM path, as a net too
+ * wide for the fused tiles' LDS does. */
+enum { HGYM_ACT_ELU = 0, HGYM_ACT_SELU = 1, HGYM_ACT_LEAKY_RELU = 2, HGYM_ACT_TANH = 3, HGYM_ACT_SIGMOID = 4 };
+
 typedef struct HgymNetConfig {
     int32_t num_obs, num_priv, num_actions;
     int32_t actor_layers, critic_layers;                 /* number of Linear layers (4, 4) */
@@ -395,13 +412,15 @@ typedef struct HgymNetConfig {
     int32_t precision;                                   /* HGYM_F32 (parity) or HGYM_BF16 (MFMA fast path) */
     int32_t max_batch;                                   /* largest M any call will use */
     /* Optional auxiliary head trained jointly with PPO (BASELINE configs[4], SURVEY.md 8f item 4: the denoising world-model
-     * head -- NO reference code exists for it; design: DESIGN.md section 9).  An MLP obs -> aux_dims[1..] (ELU between) that
+     * head -- NO reference code exists for it; design: DESIGN.md section 9).  An MLP obs -> aux_dims[1..] (`activation` between) that
      * regresses columns [aux_target_offset, aux_target_offset + aux_dims[aux_layers]) of the privileged observation row
      * with a mean-squared error weighted by HgymPPOConfig.aux_coef.  aux_layers = 0: absent.  Its parameters follow the
      * critic's in the flat vector ("denoiser.{0,2,..}.{weight,bias}"); hgym_mlp_forward(which = 2) evaluates it. */
     int32_t aux_layers;
     int32_t aux_dims[HGYM_MAX_LAYERS + 1];               /* aux_dims[0] = num_obs */
     int32_t aux_target_offset;
+    int32_t activation;                                  /* HGYM_ACT_* (0: ELU, the reference default) */
+    float act_alpha, act_scale;                          /* its parameters, see HGYM_ACT_* (0, 0: the kind's defaults) */
 } HgymNetConfig;
 
 typedef struct HgymPPOConfig {
@@ -514,7 +533,7 @@ int32_t hgym_policy_act_fin(const HgymNetConfig* cfg, const HgymNet* net, int32_
  * scratch: HGYM_ROLLOUT_SCRATCH_BYTES(num_envs) bytes owned by the caller, 16-byte aligned, zero-filled once (ping-pong step
  * counters, per-parity reset count and episode-sum accumulators; behind that header the env step's draw tables, which the
  * critic workgroups of step t compute for step t + 1).  Supported: the XBot-L default options (none of the generic ones, no use_ref_actions),
- * 15 / 3 history, contiguous [136][N] state, SoA sim tensors, N a multiple of 32, the bf16 fused net path;
+ * 15 / 3 history, contiguous [136][N] state, SoA sim tensors, N a multiple of 32, the bf16 fused net path (so activation ELU(1));
  * HGYM_E_UNSUPPORTED otherwise (callers fall back to hgym_policy_act_fin + hgym_env_step_synth).
  * values = NULL (header v7, deferred values): no critic tiles -- the grid is the N / 32 actor + env workgroups and the finaliser, every
  * workgroup draws its own step's random numbers and copies its own history rows (the critic workgroups' side jobs), and the
