@@ -972,7 +972,8 @@ inline int fb_lds_bytes(const int32_t* dims) {
     return fb_lds_bytes(n);
 }
 
-template <int G1, bool AUX = false, bool XB16 = false>
+// VU: the unclipped value loss (HgymPPOConfig.value_loss_unclipped); a template parameter, so that the clipped kernels stay as they were
+template <int G1, bool AUX = false, bool XB16 = false, bool VU = false>
 __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const FusedNet& n, bool is_actor, char* smem) {
     constexpr int BM = 64, NW = 16, D = 2, MB = BM / 16;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1122,14 +1123,23 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
         } else {
             const float ret = pre ? lin[rl * 2] : L.returns[row], vold = pre ? lin[rl * 2 + 1] : L.values[row];
             const float v = out[0];
-            const float vc = vold + clampf(v - vold, -L.clip, L.clip);
-            const float l1 = (v - ret) * (v - ret), l2 = (vc - ret) * (vc - ret);
-            const float v_in = ((v - vold) >= -L.clip && (v - vold) <= L.clip) ? 1.0f : 0.0f;
-            const float u1 = l1 > l2 ? 1.0f : (l1 == l2 ? 0.5f : 0.0f);
-            if (valid && q == 0) {
-                g[0] = L.value_coef * invB * (u1 * 2.0f * (v - ret) + (1.0f - u1) * 2.0f * (vc - ret) * v_in);
-                part[0] = fmaxf(l1, l2);
-                part[1] = g[0];
+            if constexpr (VU) {         // (R - V)^2: the stored old value plays no part
+                (void)vold;
+                if (valid && q == 0) {
+                    g[0] = L.value_coef * invB * (2.0f * (v - ret));
+                    part[0] = (v - ret) * (v - ret);
+                    part[1] = g[0];
+                }
+            } else {
+                const float vc = vold + clampf(v - vold, -L.clip, L.clip);
+                const float l1 = (v - ret) * (v - ret), l2 = (vc - ret) * (vc - ret);
+                const float v_in = ((v - vold) >= -L.clip && (v - vold) <= L.clip) ? 1.0f : 0.0f;
+                const float u1 = l1 > l2 ? 1.0f : (l1 == l2 ? 0.5f : 0.0f);
+                if (valid && q == 0) {
+                    g[0] = L.value_coef * invB * (u1 * 2.0f * (v - ret) + (1.0f - u1) * 2.0f * (vc - ret) * v_in);
+                    part[0] = fmaxf(l1, l2);
+                    part[1] = g[0];
+                }
             }
         }
         // dZ3 tile, block layout: row block hw, column block 0 holds this lane's 4 columns (block 1 is zero padding)
@@ -1194,19 +1204,32 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
 }
 
 // XB16: every net of the launch gathers its input rows from the bf16 shadow (FusedNet::xb) instead of the fp32 storage rows
-template <bool XB16 = false>
+// VU: the critic tile forms the unclipped value loss (R - V)^2 (HgymPPOConfig.value_loss_unclipped)
+template <bool XB16 = false, bool VU = false>
 __global__ __launch_bounds__(1024) void mlp_fb_kernel(const FwdArgs a, const FbLoss L) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int which = a.net0 + blockIdx.y;
     const FusedNet& n = a.net[which];
     const int g1 = n.layer[0].NB / 16;     // first hidden width 256 / 512 / 768
     if (which == 2) {                      // the auxiliary head (wide head, first hidden width 512 only): MSE instead of the PPO loss
-        if (g1 == 2) fb_body<2, true, XB16>(a, L, n, false, smem);
+        if (g1 == 2) fb_body<2, true, XB16, VU>(a, L, n, false, smem);
         return;
     }
-    if (g1 == 2) fb_body<2, false, XB16>(a, L, n, which == 0, smem);
-    else if (g1 == 3) fb_body<3, false, XB16>(a, L, n, which == 0, smem);
-    else if (g1 == 1) fb_body<1, false, XB16>(a, L, n, which == 0, smem);
+    if (g1 == 2) fb_body<2, false, XB16, VU>(a, L, n, which == 0, smem);
+    else if (g1 == 3) fb_body<3, false, XB16, VU>(a, L, n, which == 0, smem);
+    else if (g1 == 1) fb_body<1, false, XB16, VU>(a, L, n, which == 0, smem);
+}
+
+// One launch of mlp_fb_kernel<shadow, VU>.  Each value-loss form lives in a translation unit of its own (hgym_update.hip: clipped,
+// hgym_update_vu.hip: unclipped), so that neither device code object grows by the other's two 125 KB kernels.
+template <bool VU>
+int32_t launch_mlp_fb_form(const FwdArgs& fb, const FbLoss& fl, bool shadow, int tiles, int nets, size_t lds, hipStream_t s) {
+    const int32_t rc = shadow ? ensure_dynamic_lds(reinterpret_cast<const void*>(&mlp_fb_kernel<true, VU>), lds, "mlp_fb_kernel<shadow>")
+                              : ensure_dynamic_lds(reinterpret_cast<const void*>(&mlp_fb_kernel<false, VU>), lds, "mlp_fb_kernel");
+    if (rc) return rc;
+    if (shadow) hipLaunchKernelGGL((mlp_fb_kernel<true, VU>), dim3(tiles, nets), dim3(1024), lds, s, fb, fl);
+    else hipLaunchKernelGGL((mlp_fb_kernel<false, VU>), dim3(tiles, nets), dim3(1024), lds, s, fb, fl);
+    return HGYM_OK;
 }
 
 // ================================================================================================ per-minibatch loss scalars

@@ -20,7 +20,7 @@
 namespace hgym {
 
 // hgym_update.hip
-int32_t launch_mlp_fb(const FwdArgs& fb, const FbLoss& fl, bool shadow, int tiles, int nets, size_t lds, hipStream_t s);
+int32_t launch_mlp_fb(const FwdArgs& fb, const FbLoss& fl, bool shadow, bool unclipped, int tiles, int nets, size_t lds, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------ layouts
 struct LayerLayout {
@@ -358,7 +358,9 @@ struct LossArgs {
     float* partials;             // [gridDim.x][32]: surrogate, value loss, entropy, kl, dstd[12], sum dmu[12], sum dval, pad
 };
 
-template <typename T>
+// VU: the unclipped value loss (R - V)^2 (HgymPPOConfig.value_loss_unclipped); a template parameter, so that the clipped kernels stay as
+// they were
+template <typename T, bool VU = false>
 __global__ __launch_bounds__(256) void ppo_loss_kernel(const LossArgs a) {
     __shared__ float red[4][LOSS_PARTIALS];
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -427,16 +429,22 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(const LossArgs a) {
         const float s1 = -adv * ratio;
         const float s2 = -adv * clampf(ratio, 1.0f - a.clip, 1.0f + a.clip);
         const float surr = fmaxf(s1, s2);
-        const float vc = vold + clampf(v - vold, -a.clip, a.clip);
-        const float l1 = (v - ret) * (v - ret), l2 = (vc - ret) * (vc - ret);
-        const float vl = fmaxf(l1, l2);
         // backward (torch.max splits ties evenly between its operands; clamp passes gradient on the closed range)
         const float in_range = (ratio >= 1.0f - a.clip && ratio <= 1.0f + a.clip) ? 1.0f : 0.0f;
         const float w1 = s1 > s2 ? 1.0f : (s1 == s2 ? 0.5f : 0.0f);
         const float d_lp = (-adv) * (w1 + (1.0f - w1) * in_range) * invB * ratio;
-        const float v_in = ((v - vold) >= -a.clip && (v - vold) <= a.clip) ? 1.0f : 0.0f;
-        const float u1 = l1 > l2 ? 1.0f : (l1 == l2 ? 0.5f : 0.0f);
-        const float d_v = a.value_coef * invB * (u1 * 2.0f * (v - ret) + (1.0f - u1) * 2.0f * (vc - ret) * v_in);
+        float vl, d_v;
+        if constexpr (VU) {         // (R - V)^2: the stored old value plays no part
+            vl = (v - ret) * (v - ret);
+            d_v = a.value_coef * invB * (2.0f * (v - ret));
+        } else {
+            const float vc = vold + clampf(v - vold, -a.clip, a.clip);
+            const float l1 = (v - ret) * (v - ret), l2 = (vc - ret) * (vc - ret);
+            vl = fmaxf(l1, l2);
+            const float v_in = ((v - vold) >= -a.clip && (v - vold) <= a.clip) ? 1.0f : 0.0f;
+            const float u1 = l1 > l2 ? 1.0f : (l1 == l2 ? 0.5f : 0.0f);
+            d_v = a.value_coef * invB * (u1 * 2.0f * (v - ret) + (1.0f - u1) * 2.0f * (vc - ret) * v_in);
+        }
         float gm[16];
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
@@ -1080,7 +1088,7 @@ struct NetRunner {
             fb.nets = nets;
             fb.dbg = phase_buffer((int64_t)tiles * nets);
             prof_begin(HGYM_PROF_MLP_FWD, s);
-            const int32_t rc_fb = launch_mlp_fb(fb, fl, shadow, tiles, nets, lds, s);      // (hgym_update.hip: the kernel's own code object)
+            const int32_t rc_fb = launch_mlp_fb(fb, fl, shadow, ppo.value_loss_unclipped != 0, tiles, nets, lds, s);      // (hgym_update.hip: the kernel's own code object)
             if (rc_fb) return rc_fb;
             double flops = 0.0;
             for (int i = 0; i < nets; ++i) {
@@ -1324,7 +1332,8 @@ struct NetRunner {
         a.Bp = Bp;
         a.partials = at<float>(w.partials);
         prof_begin(HGYM_PROF_LOSS, s);
-        hipLaunchKernelGGL((ppo_loss_kernel<T>), dim3(nblocks), dim3(256), 0, s, a);
+        if (ppo.value_loss_unclipped) hipLaunchKernelGGL((ppo_loss_kernel<T, true>), dim3(nblocks), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((ppo_loss_kernel<T>), dim3(nblocks), dim3(256), 0, s, a);
         prof_end(HGYM_PROF_LOSS, s, (double)B * (4.0 * (5 * A + 6) + (double)sizeof(T) * (2 * A + 2)));
         HG_CHECK_LAUNCH("ppo_loss_kernel");
         const ScalArgs sc = {nblocks, B, A, 0, at<float>(w.partials), net.grads, nullptr, nullptr, net.grads + w.P, net.opt_state,
@@ -1512,6 +1521,8 @@ int32_t hgym_ppo_grad(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const 
     const int32_t rc = check_net(cfg, net, &w);
     if (rc) return rc;
     HG_REQUIRE(ppo && batch, HGYM_E_BADARG, "null ppo / batch");
+    HG_REQUIRE(ppo->value_loss_unclipped == 0 || ppo->value_loss_unclipped == 1, HGYM_E_BADARG,
+               "HgymPPOConfig.value_loss_unclipped=%d (0: clipped value loss, 1: unclipped)", ppo->value_loss_unclipped);
     HG_REQUIRE(net->grads && net->opt_state, HGYM_E_BADARG, "null grads / opt_state");
     HG_REQUIRE(batch->obs && batch->priv && batch->actions && batch->values && batch->advantages && batch->returns && batch->logp &&
                    batch->mu && batch->sigma && batch->idx, HGYM_E_BADARG, "null batch tensor");
@@ -1524,6 +1535,8 @@ int32_t hgym_ppo_grad_part(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, c
     const int32_t rc = check_net(cfg, net, &w);
     if (rc) return rc;
     HG_REQUIRE(ppo && batch, HGYM_E_BADARG, "null ppo / batch");
+    HG_REQUIRE(ppo->value_loss_unclipped == 0 || ppo->value_loss_unclipped == 1, HGYM_E_BADARG,
+               "HgymPPOConfig.value_loss_unclipped=%d (0: clipped value loss, 1: unclipped)", ppo->value_loss_unclipped);
     HG_REQUIRE(part == 0 || part == 1, HGYM_E_BADARG, "part=%d (0 or 1)", part);
     HG_REQUIRE(net->grads && net->opt_state, HGYM_E_BADARG, "null grads / opt_state");
     HG_REQUIRE(batch->obs && batch->priv && batch->actions && batch->values && batch->advantages && batch->returns && batch->logp &&
@@ -1543,6 +1556,8 @@ int32_t hgym_ppo_apply(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const
     const int32_t rc = check_net(cfg, net, &w);
     if (rc) return rc;
     HG_REQUIRE(ppo, HGYM_E_BADARG, "null ppo");
+    HG_REQUIRE(ppo->value_loss_unclipped == 0 || ppo->value_loss_unclipped == 1, HGYM_E_BADARG,
+               "HgymPPOConfig.value_loss_unclipped=%d (0: clipped value loss, 1: unclipped)", ppo->value_loss_unclipped);
     HG_REQUIRE(net->grads && net->adam_m && net->adam_v && net->opt_state, HGYM_E_BADARG, "null optimiser buffers");
     HG_DISPATCH(cfg, net, w, stream, apply(*ppo));
 }

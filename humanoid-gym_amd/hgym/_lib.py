@@ -116,7 +116,8 @@ class PPOConfig(C.Structure):
                 ("max_grad_norm", C.c_float), ("desired_kl", C.c_float),
                 ("beta1", C.c_float), ("beta2", C.c_float), ("adam_eps", C.c_float),
                 ("lr_min", C.c_double), ("lr_max", C.c_double), ("adaptive_lr", C.c_int32), ("world_size", C.c_int32),
-                ("aux_coef", C.c_float), ("grad_norm_ready", C.c_int32)]
+                ("aux_coef", C.c_float), ("grad_norm_ready", C.c_int32),
+                ("value_loss_unclipped", C.c_int32)]
 
 
 class Net(C.Structure):

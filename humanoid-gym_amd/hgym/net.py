@@ -60,7 +60,8 @@ def make_net_config(num_obs, num_priv, num_actions, actor_hidden, critic_hidden,
 
 
 def make_ppo_config(clip_param=0.2, value_loss_coef=1.0, entropy_coef=0.001, max_grad_norm=1.0, desired_kl=0.01,
-                    adaptive=True, world_size=1, grad_norm_ready=False, aux_coef=0.0):
+                    adaptive=True, world_size=1, grad_norm_ready=False, aux_coef=0.0, clipped_value_loss=True):
+    """clipped_value_loss: the reference's use_clipped_value_loss (False: the value loss (R - V)^2, HgymPPOConfig.value_loss_unclipped)."""
     p = L.PPOConfig()
     p.clip_param, p.value_loss_coef, p.entropy_coef = clip_param, value_loss_coef, entropy_coef
     p.max_grad_norm, p.desired_kl = max_grad_norm, desired_kl
@@ -70,6 +71,7 @@ def make_ppo_config(clip_param=0.2, value_loss_coef=1.0, entropy_coef=0.001, max
     p.world_size = int(world_size)
     p.aux_coef = float(aux_coef)
     p.grad_norm_ready = 1 if (grad_norm_ready and int(world_size) == 1) else 0    # see HgymPPOConfig
+    p.value_loss_unclipped = 0 if clipped_value_loss else 1
     return p
 
 

@@ -74,8 +74,6 @@ class PPO:
                  schedule="fixed", desired_kl=0.01, device="cpu", denoise_coef=0.0):
         if not (str(device).startswith("cuda") and torch.cuda.is_available()):
             raise RuntimeError("PPO runs on the MI355X hot path only (device=%r); there is no CPU training path" % (device,))
-        if not use_clipped_value_loss:
-            raise NotImplementedError("the loss kernel implements the clipped value loss (reference default)")
         self.device = device
         self.desired_kl, self.schedule = desired_kl, schedule
         self._lr0 = learning_rate
@@ -146,7 +144,8 @@ class PPO:
                                              adaptive=(self.desired_kl is not None and self.schedule == "adaptive"),
                                              world_size=self._world,
                                              grad_norm_ready=True,   # update() applies exactly what hgym_ppo_grad produced
-                                             aux_coef=self.denoise_coef if aux else 0.0)
+                                             aux_coef=self.denoise_coef if aux else 0.0,
+                                             clipped_value_loss=self.use_clipped_value_loss)
         self.last_denoise_loss = None
         self._sample_step = torch.zeros(1, dtype=torch.int64, device=self.device)
         self._perm_seed = (torch.initial_seed() * 0x9E3779B97F4A7C15 + 0xABCD + 104729 * self._rank) & 0xFFFFFFFFFFFFFFFF

@@ -45,7 +45,9 @@ extern "C" {
                              * 9: hgym_randperm_dev (draw number on the device); hgym_comm_allreduce(seq = 0): the call number kept on the device
                              *    (status[2]); hgym_comm_sum64 -- what a captured update needs: no launch argument changes between iterations
                              *    (same version, later: HgymNetConfig.activation / act_alpha / act_scale appended -- ELU, SELU, LeakyReLU / ReLU,
-                             *    Tanh or Sigmoid between the Linear layers; a zero-filled tail is the ELU(1) every earlier layout meant) */
+                             *    Tanh or Sigmoid between the Linear layers; a zero-filled tail is the ELU(1) every earlier layout meant)
+                             *    (same version, later still: HgymPPOConfig.value_loss_unclipped appended -- the value loss (R - V)^2 instead of
+                             *    the clipped form; a zero-filled tail is the clipped loss every earlier layout meant) */
 
 enum {
     HGYM_OK = 0,
@@ -440,6 +442,11 @@ typedef struct HgymPPOConfig {
                                        opt_state[13] keeps the two honest: a second hgym_ppo_grad before the apply does not advance the step
                                        again, and an apply under another configuration does not repeat a prologue already taken.  (Not
                                        covered: a gradient call WITHOUT the flag followed by an apply WITH it -- no prologue runs.) */
+    int32_t value_loss_unclipped;   /* the value loss (the reference's use_clipped_value_loss, ppo.py:158-166), in every path:
+                                         0: max((V - R)^2, (V_old + clamp(V - V_old, -clip, clip) - R)^2).mean()  (the reference default)
+                                         1: (R - V)^2.mean()  (use_clipped_value_loss = False)
+                                       opt_state[4] sums the form in use.  Any other value: HGYM_E_BADARG from every call taking the
+                                       configuration.  Appended later within header v9, so a zero-filled tail is the clipped form. */
 } HgymPPOConfig;
 
 /* Sizes (bytes) of the caller-allocated blocks, as functions of the configuration. */
