@@ -956,9 +956,10 @@ HG_HD int fb_lds_extra(const FusedNet& n) { return 64 * 64 * n.layer[3].NBB + 4 
 
 // Dynamic LDS the update's tiles of a net ask for, and the most a workgroup may have.  A net takes the fused path only if its
 // mlp_fb_kernel tile fits (hgym_net.hip: fused_supported / fused_aux_supported, and the launch itself).  This also covers the forward:
-// mlp_fwd_kernel's 64-row tile needs P + Q + bias of the same sum, and its 32-row tile less.
+// mlp_fwd_kernel's BM-row tile needs P + Q + bias (fwd_lds_bytes), which at 64 rows is a part of the same sum, and at 32 rows less.
 constexpr size_t FB_LDS_LIMIT = 160 * 1024;
-HG_HD int fb_lds_bytes(const FusedNet& n) { return fused_lds_p(n, 64) + fused_lds_q(n, 64) + fused_lds_bias(n) + fb_lds_extra(n); }
+HG_HD int fwd_lds_bytes(const FusedNet& n, int BM) { return fused_lds_p(n, BM) + fused_lds_q(n, BM) + fused_lds_bias(n); }
+HG_HD int fb_lds_bytes(const FusedNet& n) { return fwd_lds_bytes(n, 64) + fb_lds_extra(n); }
 // the same from the net's widths (dims[0] = input .. dims[4] = head), before any workspace exists: the fields the sum reads,
 // filled the way the workspace layout fills them (hgym_net.hip: ws_layout)
 inline int fb_lds_bytes(const int32_t* dims) {
@@ -1441,7 +1442,7 @@ __global__ __launch_bounds__(DW_THREADS, 1) void dw_kernel_rs(const DwArgs a) {
     // the page of zeros" is a scalar select on that base, never a branch around a load (a conditional load makes the compiler's
     // vmcnt conservative), and an OFFSET from the operand's own pointer (a pointer rebuilt from an integer becomes a FLAT access).
     //
-    // Gathered X operand (first-layer products on the bf16 shadow, < 4 GiB: fused_grad checks): the lane that holds bytes
+    // Gathered X operand (first-layer products on the bf16 shadow, < 4 GiB: FusedPath::grad checks): the lane that holds bytes
     // [16 l, 16 l + 16) of a piece holds row (l & 31) >> 1 of the row block, block l >> 5 of the pair, half l & 1 -- in the row-major
     // shadow that is 16 bytes of row gidx[m].  The 16 row indices of a stage are one 4-byte load per lane (row l & 15, replicated
     // over the wave) issued TWO stages ahead of the stage's data and in front of the data loads issued with it: a wave's loads

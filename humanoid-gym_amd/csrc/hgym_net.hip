@@ -36,6 +36,7 @@ struct LayerLayout {
 
 struct NetLayout {
     int L;
+    bool fused;              // the fused bf16 layout (fragment-major weights, block-layout activations); else the layer-by-layer one
     LayerLayout layer[HGYM_MAX_LAYERS];
     int64_t out_f32;         // [maxM][N_last] fp32 output of the last layer (update path)
     int64_t X0b, Hb[3], dZb[4];   // fused path: block-layout activations / pre-activation gradients
@@ -47,8 +48,7 @@ struct WsLayout {
     int64_t maxM, Mp;        // max batch and its contraction padding (row stride of every transposed buffer)
     int64_t P;               // total parameters
     int64_t Ps;              // slab stride (P rounded up so every slab starts 256-byte aligned)
-    NetLayout net[3];        // 0 actor, 1 critic, 2 auxiliary head (optional)
-    int fused_aux;           // 1: the auxiliary head also has the fused layout (its own launches of the three fused kernels)
+    NetLayout net[3];        // 0 actor, 1 critic (both fused or neither), 2 auxiliary head (optional; fused only with the other two)
     int nnets;               // 2 or 3
     int64_t aux_p0;          // first parameter of the auxiliary head in the flat vector (= P when absent)
     int splits;
@@ -57,7 +57,6 @@ struct WsLayout {
     int64_t zeros;           // 4 KiB that nothing ever writes (the workspace arrives zero-filled)
     int64_t sqn;             // [SQN_BLOCKS] fp64 per-workgroup sums of sqnorm_prologue_kernel + its arrival counter (zero between launches)
     int64_t total_bytes;
-    int fused;               // 1: bf16 fast path (three fused kernels) is usable for this configuration
     Act act;                 // the hidden layers' activation (HgymNetConfig.activation, resolved)
     int64_t Mpad;            // fused path: batch padded to the 64-row tile
     int dw_splits;
@@ -67,26 +66,23 @@ constexpr int MAX_LOSS_BLOCKS = 8192;   // 256 samples each: minibatches up to 2
 constexpr int SQN_BLOCKS = 256;         // workgroups of sqnorm_prologue_kernel
 constexpr int RSN_X = 96;               // workgroups per segment of reduce_slabs_kernel
 
+// the hidden widths the fused kernels are instantiated for, and the update's tile fits (hgym_fused.hpp: fb_lds_bytes)
+static bool fused_trunk_ok(const int32_t* d) {
+    if (!(d[1] == 256 || d[1] == 512 || d[1] == 768)) return false;
+    if (d[2] % 128 || d[2] > 768 || d[3] % 128 || d[3] > 768) return false;
+    return (size_t)fb_lds_bytes(d) <= FB_LDS_LIMIT;
+}
 static bool fused_supported(const HgymNetConfig* c) {
     if (c->precision != HGYM_BF16 || c->actor_layers != 4 || c->critic_layers != 4) return false;
     if (getenv("HGYM_NO_FUSED")) return false;
-    for (int which = 0; which < 2; ++which) {
-        const int32_t* d = which == 0 ? c->actor_dims : c->critic_dims;
-        const int g1 = d[1] / 128;
-        if (d[1] % 128 || !(g1 == 2 || g1 == 4 || g1 == 6)) return false;
-        if (d[2] % 128 || d[2] > 768 || d[3] % 128 || d[3] > 768) return false;
-        if (d[4] > 16) return false;
-        if ((size_t)fb_lds_bytes(d) > FB_LDS_LIMIT) return false;      // the update's tile must fit (hgym_fused.hpp: fb_lds_bytes)
-    }
-    return true;
+    return fused_trunk_ok(c->actor_dims) && c->actor_dims[4] <= 16 && fused_trunk_ok(c->critic_dims) && c->critic_dims[4] <= 16;
 }
-// the auxiliary head through the fused kernels: same trunk constraints, head up to 96 columns (three 32-wide contraction blocks)
+// the auxiliary head through the fused kernels: head up to 96 columns (three 32-wide contraction blocks), first width 512 (the
+// wide-head instantiation of the forward exists for this first width only)
 static bool fused_aux_supported(const HgymNetConfig* c) {
     if (c->aux_layers != 4 || getenv("HGYM_NO_FUSED_AUX")) return false;
     const int32_t* d = c->aux_dims;
-    if (d[1] != 512) return false;         // the wide-head instantiation of the forward exists for this first width only
-    if (d[2] % 128 || d[2] > 768 || d[3] % 128 || d[3] > 768) return false;
-    return d[4] > 16 && d[4] <= 96 && (size_t)fb_lds_bytes(d) <= FB_LDS_LIMIT;
+    return d[1] == 512 && d[4] > 16 && d[4] <= 96 && fused_trunk_ok(d);
 }
 constexpr int MAX_SPLITS = 32;
 
@@ -147,7 +143,7 @@ static int32_t ws_layout(const HgymNetConfig* c, WsLayout* w) {
     w->SE = c->precision == HGYM_F32 ? stage_elems<float>() : stage_elems<__bf16>();
     w->maxM = c->max_batch;
     w->Mp = round_up(c->max_batch, w->SE);
-    w->fused = fused_supported(c) && act_is_elu1(w->act) ? 1 : 0;
+    const bool fused = fused_supported(c) && act_is_elu1(w->act);
     w->Mpad = round_up(c->max_batch, 64);
     int64_t off = 0, poff = c->num_actions;  // std first (state_dict order)
     auto take = [&](int64_t bytes) {
@@ -161,13 +157,12 @@ static int32_t ws_layout(const HgymNetConfig* c, WsLayout* w) {
                        c->aux_target_offset + c->aux_dims[c->aux_layers] <= c->num_priv && c->actor_layers + c->critic_layers + c->aux_layers <= 16,
                    HGYM_E_SHAPE, "auxiliary head: input must be num_obs, targets must lie inside the privileged row");
     w->nnets = c->aux_layers > 0 ? 3 : 2;
-    w->fused_aux = (w->fused && c->aux_layers > 0 && fused_aux_supported(c)) ? 1 : 0;
     w->aux_p0 = -1;
     for (int which = 0; which < w->nnets; ++which) {
         NetLayout& n = w->net[which];
         n.L = which == 0 ? c->actor_layers : (which == 1 ? c->critic_layers : c->aux_layers);
         const int32_t* dims = which == 0 ? c->actor_dims : (which == 1 ? c->critic_dims : c->aux_dims);
-        const bool fused_net = w->fused && (which < 2 || w->fused_aux);
+        n.fused = fused && (which < 2 || fused_aux_supported(c));
         if (which == 2) w->aux_p0 = poff;
         for (int l = 0; l < n.L; ++l) {
             LayerLayout& y = n.layer[l];
@@ -182,7 +177,7 @@ static int32_t ws_layout(const HgymNetConfig* c, WsLayout* w) {
             poff += (int64_t)y.N * y.K;
             y.b_off = poff;
             poff += y.N;
-            if (fused_net) {
+            if (n.fused) {
                 y.KBf = (int)round_up(y.K, l == 0 ? FUSED_CHUNK : 32) / 32;
                 y.NBf = y.N16 / 16;
                 y.NBBf = (int)round_up(y.N, 32) / 32;
@@ -198,7 +193,7 @@ static int32_t ws_layout(const HgymNetConfig* c, WsLayout* w) {
             }
         }
         n.out_f32 = take(w->maxM * (int64_t)dims[n.L] * 4);
-        if (fused_net) {
+        if (n.fused) {
             n.X0b = take(w->Mpad * (int64_t)n.layer[0].KBf * 32 * 2);
             for (int l = 0; l < 3; ++l) {
                 n.Hb[l] = take(w->Mpad * (int64_t)n.layer[l].N * 2);
@@ -349,7 +344,6 @@ struct LossArgs {
     const float* val;            // [B]    current value
     const float* std_;           // [A]
     float clip, value_coef, entropy_coef;
-    int fused;                   // 1: dmu / dval are block-layout tiles of 32 columns (hgym_fused.hpp); 0: row-major + transposes
     void* dmu;  int64_t ld_dmu;  // [B][Ncp] operand type
     void* dmuT; int64_t ld_t;    // [A16][Mp]
     void* dval; int64_t ld_dval; // [B][Ncp]
@@ -373,9 +367,6 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(const LossArgs a) {
     T* dmuT = (T*)a.dmuT;
     T* dval = (T*)a.dval;
     T* dvalT = (T*)a.dvalT;
-    // fused layout: sample i lives in row block i>>4, row i&15 of a 2-block (32-column) tile; only block 0 is ever non-zero
-    char* fmu = (char*)a.dmu + ((int64_t)(i >> 4) * 2) * 512 + (i & 15) * 32;
-    char* fval = (char*)a.dval + ((int64_t)(i >> 4) * 2) * 512 + (i & 15) * 32;
     if (i < B) {
         const int64_t r = a.b.idx[i];
         const float adv = a.b.advantages[r], ret = a.b.returns[r], vold = a.b.values[r], lpold = a.b.logp[r];
@@ -445,56 +436,29 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(const LossArgs a) {
             const float u1 = l1 > l2 ? 1.0f : (l1 == l2 ? 0.5f : 0.0f);
             d_v = a.value_coef * invB * (u1 * 2.0f * (v - ret) + (1.0f - u1) * 2.0f * (vc - ret) * v_in);
         }
-        float gm[16];
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
-            gm[j] = 0.0f;
             if (j >= A) continue;
             const float s = sg[j], d = diff[j];
             const float g_mu = d_lp * d / (s * s);
             const float g_sg = d_lp * (d * d / (s * s * s) - 1.0f / s) - (a.entropy_coef * invB) / s;
-            gm[j] = g_mu;
             if (j < 12) {
                 acc[4 + j] = g_sg;
                 acc[16 + j] = g_mu;
             }
-            if (!a.fused) {
-                dmu[(int64_t)i * a.ld_dmu + j] = from_f32<T>(g_mu);
-                dmuT[(int64_t)j * a.ld_t + i] = from_f32<T>(g_mu);
-            }
+            dmu[(int64_t)i * a.ld_dmu + j] = from_f32<T>(g_mu);
+            dmuT[(int64_t)j * a.ld_t + i] = from_f32<T>(g_mu);
         }
-        if (a.fused) {
-            if constexpr (sizeof(T) == 2) {
-                u32x4 lo, hi;
-                const u32x2 p0 = pack_bf16x4(gm[0], gm[1], gm[2], gm[3]), p1 = pack_bf16x4(gm[4], gm[5], gm[6], gm[7]);
-                const u32x2 p2 = pack_bf16x4(gm[8], gm[9], gm[10], gm[11]), p3 = pack_bf16x4(gm[12], gm[13], gm[14], gm[15]);
-                lo = (u32x4){p0[0], p0[1], p1[0], p1[1]};
-                hi = (u32x4){p2[0], p2[1], p3[0], p3[1]};
-                reinterpret_cast<u32x4*>(fmu)[0] = lo;
-                reinterpret_cast<u32x4*>(fmu)[1] = hi;
-                const u32x2 pv = pack_bf16x4(d_v, 0.0f, 0.0f, 0.0f);
-                reinterpret_cast<u32x4*>(fval)[0] = (u32x4){pv[0], 0u, 0u, 0u};
-                reinterpret_cast<u32x4*>(fval)[1] = (u32x4){0u, 0u, 0u, 0u};
-            }
-        } else {
-            dval[(int64_t)i * a.ld_dval] = from_f32<T>(d_v);
-            dvalT[i] = from_f32<T>(d_v);
-        }
+        dval[(int64_t)i * a.ld_dval] = from_f32<T>(d_v);
+        dvalT[i] = from_f32<T>(d_v);
         acc[0] = surr;
         acc[1] = vl;
         acc[2] = ent;
         acc[3] = kl;
         acc[28] = d_v;
     } else if (i < a.Bp) {   // zero the contraction padding of the gradients
-        if (a.fused) {
-            reinterpret_cast<u32x4*>(fmu)[0] = (u32x4){0u, 0u, 0u, 0u};
-            reinterpret_cast<u32x4*>(fmu)[1] = (u32x4){0u, 0u, 0u, 0u};
-            reinterpret_cast<u32x4*>(fval)[0] = (u32x4){0u, 0u, 0u, 0u};
-            reinterpret_cast<u32x4*>(fval)[1] = (u32x4){0u, 0u, 0u, 0u};
-        } else {
-            for (int j = 0; j < A; ++j) dmuT[(int64_t)j * a.ld_t + i] = from_f32<T>(0.0f);
-            dvalT[i] = from_f32<T>(0.0f);
-        }
+        for (int j = 0; j < A; ++j) dmuT[(int64_t)j * a.ld_t + i] = from_f32<T>(0.0f);
+        dvalT[i] = from_f32<T>(0.0f);
     }
 #pragma unroll
     for (int k = 0; k < LOSS_PARTIALS; ++k) {
@@ -770,39 +734,80 @@ int32_t launch_gemm(const GemmArgs& g0, int splits, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------------------ orchestration
-template <typename T>
-struct NetRunner {
+// input rows and output of one net in a launch (arrays of three are indexed by net id)
+struct NetIO {
+    const float* x;
+    int64_t ldx;
+    float* out;
+    int64_t ldo;
+};
+
+// bf16 shadow rows of net `which`'s input on the fused layout (hgym_net_shadow_ld): the first layer's padded width
+static int64_t shadow_ld(const WsLayout& w, int which) { return (int64_t)w.net[which].layer[0].KBf * 32; }
+
+static int32_t check_shadow(const WsLayout& w, const HgymObsShadow* sh) {
+    if (!sh) return HGYM_OK;
+    HG_REQUIRE((!sh->obs || (sh->ld_obs >= shadow_ld(w, 0) && sh->ld_obs % 8 == 0 && ((uintptr_t)sh->obs & 15) == 0)) &&
+                   (!sh->priv || (sh->ld_priv >= shadow_ld(w, 1) && sh->ld_priv % 8 == 0 && ((uintptr_t)sh->priv & 15) == 0)),
+               HGYM_E_SHAPE, "observation shadow: leading dimensions %lld / %lld (need >= %lld / %lld, multiples of 8, 16-byte aligned rows)",
+               (long long)sh->ld_obs, (long long)sh->ld_priv, (long long)shadow_ld(w, 0), (long long)shadow_ld(w, 1));
+    return HGYM_OK;
+}
+
+// dynamic LDS of one mlp_fwd_kernel launch with BM-row tiles over a.net[a.net0 .. + nets)
+static size_t fwd_lds(const FwdArgs& a, int nets, int BM) {
+    size_t lds = 0;
+    for (int i = 0; i < nets; ++i) lds = std::max(lds, (size_t)fwd_lds_bytes(a.net[a.net0 + i], BM));
+    return lds;
+}
+
+// What both paths share: the workspace, the segment table of the slab reduction / Adam / the shadow refresh, and those two launches.
+struct NetBase {
     const HgymNetConfig& cfg;
     const HgymNet& net;
-    WsLayout w;
+    const WsLayout& w;
     hipStream_t s;
     char* ws;
 
     template <typename U> U* at(int64_t off) const { return reinterpret_cast<U*>(ws + off); }
 
-    SegTable segments(bool with_slabs) const {
+    // split-K slabs of a weight gradient on the layer-by-layer path, for a minibatch whose contraction padding is Mp
+    int split_count(const LayerLayout& y, int Mp) const {
+        // enough workgroups to fill 256 CUs: tiles(N x K) x splits ~ 512
+        const int tiles = ceil_div(y.N, y.N <= 16 ? 16 : 128) * ceil_div(y.K, 128);
+        int sp = ceil_div(512, tiles);
+        if (sp > w.splits) sp = w.splits;
+        const int stages = Mp / w.SE;
+        if (sp > stages) sp = stages;
+        if (sp < 1) sp = 1;
+        const int per = ceil_div(stages, sp);
+        return ceil_div(stages, per);
+    }
+
+    // Mp > 0: with the slab counts of a gradient over a minibatch of contraction padding Mp; Mp = 0: without (Adam, shadow refresh)
+    SegTable segments(int Mp) const {
         SegTable t;
         memset(&t, 0, sizeof(t));
         Segment& sd = t.s[t.n++];
         sd.off = 0;
         sd.rows = cfg.num_actions;
         sd.cols = 1;
-        for (int which = 0; which < w.nnets; ++which)
-            for (int l = 0; l < w.net[which].L; ++l) {
-                const LayerLayout& y = w.net[which].layer[l];
-                const bool fused_net = w.fused && (which < 2 || w.fused_aux);
+        for (int which = 0; which < w.nnets; ++which) {
+            const NetLayout& n = w.net[which];
+            for (int l = 0; l < n.L; ++l) {
+                const LayerLayout& y = n.layer[l];
                 Segment& a = t.s[t.n++];
                 a.off = y.w_off;
                 a.rows = y.N;
                 a.cols = y.K;
-                if (fused_net) {
-                    a.splits = with_slabs ? w.dw_splits : 0;
+                if (n.fused) {
+                    a.splits = Mp ? w.dw_splits : 0;
                     a.Wf = ws + y.Wf;
                     a.WTf = ws + y.WTf;
                     a.KB = y.KBf;
                     a.NBB = y.NBBf;
                 } else {
-                    a.splits = with_slabs ? split_count(y) : 0;
+                    a.splits = Mp ? split_count(y, Mp) : 0;
                     a.Wp = ws + y.Wp;
                     a.ldw = y.Kp;
                     a.WTp = ws + y.WTp;
@@ -814,365 +819,46 @@ struct NetRunner {
                 b.cols = 1;
                 // bias gradients that come from the slabs: hidden layers (the dW kernel's column sums of dZ); the actor / critic
                 // head biases are written by ppo_scalars_kernel, the auxiliary head's is a column sum like the others
-                if (fused_net && with_slabs && (l < w.net[which].L - 1 || which == 2)) b.splits = w.dw_splits;
+                if (n.fused && Mp && (l < n.L - 1 || which == 2)) b.splits = w.dw_splits;
             }
+        }
         return t;
     }
 
-    int cur_Mp = 0;   // contraction padding of the current batch
-    int split_count(const LayerLayout& y) const {
-        // enough workgroups to fill 256 CUs: tiles(N x K) x splits ~ 512
-        const int tiles = ceil_div(y.N, y.N <= 16 ? 16 : 128) * ceil_div(y.K, 128);
-        int sp = ceil_div(512, tiles);
-        if (sp > w.splits) sp = w.splits;
-        const int stages = cur_Mp / w.SE;
-        if (sp > stages) sp = stages;
-        if (sp < 1) sp = 1;
-        const int per = ceil_div(stages, sp);
-        return ceil_div(stages, per);
-    }
-
-    // ------------------------------------------------------------------ fused bf16 path (hgym_fused.hpp)
-    struct SampleOut {
-        const float* z; uint64_t seed; const int64_t* step; float* actions; float* sigma; float* logp;
-    };
-
-    FusedNet fused_net(int which, const float* x, int64_t ldx, float* out, int64_t ldo) const {
-        FusedNet f;
-        memset(&f, 0, sizeof(f));
-        const NetLayout& n = w.net[which];
-        for (int l = 0; l < 4; ++l) {
-            const LayerLayout& y = n.layer[l];
-            FusedLayer& d = f.layer[l];
-            d.Wf = at<u32x4>(y.Wf);
-            d.WTf = at<u32x4>(y.WTf);
-            d.bias = net.params + y.b_off;
-            d.K = y.K;
-            d.N = y.N;
-            d.KB = y.KBf;
-            d.NB = y.NBf;
-            d.NBB = y.NBBf;
-        }
-        f.x = x;
-        f.ldx = ldx;
-        f.X0 = at<__bf16>(n.X0b);
-        for (int l = 0; l < 3; ++l) f.H[l] = at<__bf16>(n.Hb[l]);
-        for (int l = 0; l < 4; ++l) f.dZ[l] = at<__bf16>(n.dZb[l]);
-        f.out = out;
-        f.ldo = ldo;
-        return f;
-    }
-
-    template <int BM, int NW, int D, bool FIN>
-    int32_t launch_fwd_k(const FwdArgs& a, int nets) {
-        size_t lds = 0;
-        for (int i = 0; i < nets; ++i) {
-            const FusedNet& n = a.net[a.net0 + i];
-            lds = std::max(lds, (size_t)fused_lds_p(n, BM) + (size_t)fused_lds_q(n, BM) + (size_t)fused_lds_bias(n));
-        }
-        const int32_t rc_lds = ensure_dynamic_lds(reinterpret_cast<const void*>(&mlp_fwd_kernel<BM, NW, D, FIN>), lds, "mlp_fwd_kernel");
-        if (rc_lds) return rc_lds;
-        FwdArgs b = a;
-        b.nets = nets;
-        const int rows = nets + (FIN ? 1 : 0);          // + the finaliser's grid row (its workgroup 0 works, the rest exit)
-        b.dbg = phase_buffer((int64_t)ceil_div(a.M, BM) * rows);
-        hipLaunchKernelGGL((mlp_fwd_kernel<BM, NW, D, FIN>), dim3(ceil_div(a.M, BM), rows), dim3(NW * 64), lds, s, b);
-        HG_CHECK_LAUNCH("mlp_fwd_kernel");
-        return HGYM_OK;
-    }
-    template <int BM, int NW, int D>
-    int32_t launch_fwd(const FwdArgs& a, int nets) {
-        return a.fin.N > 0 ? launch_fwd_k<BM, NW, D, true>(a, nets) : launch_fwd_k<BM, NW, D, false>(a, nets);
-    }
-
-    // bf16 shadow rows of net `which`'s input (hgym_net_shadow_ld): the first layer's padded width
-    int64_t shadow_ld(int which) const { return (int64_t)w.net[which].layer[0].KBf * 32; }
-
-    // sh (policy launches, no row gather): net 0 / 1 also store the bf16 of their input rows as rows of sh->obs / sh->priv
-    FwdArgs make_fwd_args(int first, int nets, int M, const float* const xs[3], const int64_t ldxs[3], const int64_t* idx, float* const outs[3],
-                          const int64_t ldos[3], bool train, const SampleOut* smp, const FinArgs* fin, const HgymObsShadow* sh = nullptr) const {
-        FwdArgs a;
-        memset(&a, 0, sizeof(a));
-        for (int i = first; i < first + nets; ++i) a.net[i] = fused_net(i, xs[i], ldxs[i], outs[i], ldos[i]);
-        if (sh && !idx && !train) {
-            if (first == 0 && sh->obs) { a.net[0].xs = (__bf16*)sh->obs; a.net[0].ldxs = sh->ld_obs; }
-            if (first <= 1 && first + nets > 1 && sh->priv) { a.net[1].xs = (__bf16*)sh->priv; a.net[1].ldxs = sh->ld_priv; }
-        }
-        a.net0 = first;
-        a.M = M;
-        a.idx = idx;
-        if (fin) a.fin = *fin;
-        a.train = train ? 3 : 0;
-        a.A = cfg.num_actions;
-        a.std_ = net.params;
-        if (smp) {
-            a.sample = 1;
-            a.z = smp->z;
-            a.k0 = (uint32_t)smp->seed;
-            a.k1 = (uint32_t)(smp->seed >> 32);
-            a.step = smp->step;
-            a.actions = smp->actions;
-            a.sigma = smp->sigma;
-            a.logp = smp->logp;
-        }
-        return a;
-    }
-
-    // forward of `nets` networks starting at `first` in ONE launch; xs/outs indexed by net id
-    int32_t fused_forward(int first, int nets, int M, const float* const xs[3], const int64_t ldxs[3], const int64_t* idx, float* const outs[3],
-                          const int64_t ldos[3], bool train, const SampleOut* smp, const FinArgs* fin = nullptr, const HgymObsShadow* sh = nullptr) {
-        HG_REQUIRE(M > 0 && M <= w.maxM, HGYM_E_SHAPE, "batch %d exceeds max_batch %lld", M, (long long)w.maxM);
-        if (sh) {
-            HG_REQUIRE((!sh->obs || (sh->ld_obs >= shadow_ld(0) && sh->ld_obs % 8 == 0 && ((uintptr_t)sh->obs & 15) == 0)) &&
-                           (!sh->priv || (sh->ld_priv >= shadow_ld(1) && sh->ld_priv % 8 == 0 && ((uintptr_t)sh->priv & 15) == 0)),
-                       HGYM_E_SHAPE, "observation shadow: leading dimensions %lld / %lld (need >= %lld / %lld, multiples of 8, 16-byte aligned rows)",
-                       (long long)sh->ld_obs, (long long)sh->ld_priv, (long long)shadow_ld(0), (long long)shadow_ld(1));
-        }
-        const FwdArgs a = make_fwd_args(first, nets, M, xs, ldxs, idx, outs, ldos, train, smp, fin, sh);
-        const int pcls = train ? HGYM_PROF_MLP_FWD : HGYM_PROF_POLICY;
-        prof_begin(pcls, s);
-        // 32-row tiles x 8 waves (weight ring depth 4) while they fit the chip in one round (one workgroup per CU: 2 * M / 32
-        // <= CUs, i.e. 4096 envs), 64-row tiles x 16 waves (depth 2) for the update and for larger rollouts; measured
-        // alternatives (64 rows x 8 waves, 32-row tiles for the update, other depths) were equal or slower
-        const int cus = device_cus() > 0 ? device_cus() : 256;
-        // (32-row tiles two per CU at 8192 rows: collection 5.32 vs 3.82 ms, profiles/r03_envs8192_policy_tiles_ab.txt)
-        const int32_t rc = (train || nets * ceil_div(M, 32) > cus) ? launch_fwd<64, 16, 2>(a, nets) : launch_fwd<32, 8, 4>(a, nets);
-        double fl = 0.0;
-        for (int i = first; i < first + nets; ++i)
-            for (int l = 0; l < 4; ++l) fl += 2.0 * (double)M * w.net[i].layer[l].N * w.net[i].layer[l].K;   // algorithmic (unpadded) flops
-        prof_end(pcls, s, fl);
-        return rc;
-    }
-
-    // all weight (and hidden bias) gradients of nets [first, first + count): one launch, split-K slabs
-    // (the auxiliary head, net 2, reads the ACTOR's bf16 copy of the gathered observation rows as its first-layer operand -- same
-    // rows, same columns -- and every bias gradient of it is a column sum of dZ: its loss has no per-tile partial sums for them)
-    // gb (mlp_fb_kernel<XB16> ran): the first-layer operands were never copied -- those products gather their rows by gb->idx from the
-    // bf16 shadows
-    int32_t fused_dw(int first, int count, int B, const ScalArgs* sc = nullptr, const HgymBatch* gb = nullptr) {
-        const int Bp = (int)round_up(B, 64);
-        DwArgs d;
-        memset(&d, 0, sizeof(d));
-        d.B = B;
-        int tile = 0;
-        double fl = 0.0;
-        for (int i = first; i < first + count; ++i)
-            for (int l = 0; l < 4; ++l) {
-                const NetLayout& n = w.net[i];
-                const LayerLayout& y = n.layer[l];
-                HG_REQUIRE(d.np < DW_MAX_PRODUCTS, HGYM_E_UNSUPPORTED, "too many weight-gradient products in one launch");
-                DwProduct& p = d.p[d.np++];
-                p.Z = at<__bf16>(n.dZb[l]);
-                p.CBz = l < 3 ? y.N / 16 : 2 * y.NBBf;
-                p.X = l == 0 ? at<__bf16>(w.net[i == 2 ? 0 : i].X0b) : at<__bf16>(n.Hb[l - 1]);
-                p.CBx = l == 0 ? 2 * y.KBf : y.K / 16;
-                if (l == 0 && gb) {
-                    p.X = (const __bf16*)(i == 1 ? gb->priv_bf16 : gb->obs_bf16);
-                    p.gidx = gb->idx;
-                    p.ldg = shadow_ld(i == 1 ? 1 : 0);
-                    p.CBx = (int)(p.ldg / 16);
-                }
-                p.N = y.N;
-                p.K = y.K;
-                p.w_off = y.w_off;
-                p.b_off = (l < 3 || i == 2) ? y.b_off : -1;
-                p.tiles_n = ceil_div(y.N, DW_TILE_N);
-                p.tiles_k = ceil_div(y.K, DW_TILE_K);
-                p.tile0 = tile;
-                tile += p.tiles_n * p.tiles_k;
-                fl += 2.0 * (double)B * y.N * y.K;
-            }
-        d.total_tiles = tile;
-        d.splits = w.dw_splits;
-        d.steps_total = Bp / 32;
-        d.steps_per_split = ceil_div(d.steps_total, w.dw_splits);
-        d.slabs = at<float>(w.slabs);
-        d.slab_stride = w.Ps;
-        d.zeros = at<char>(w.zeros);
-        int blocks = tile * (int)round_up(w.dw_splits, 8);
-        d.scal_bid = -1;
-        if (sc) {
-            d.sc = *sc;
-            d.scal_bid = blocks++;
-        }
-        const int32_t rc_lds = ensure_dynamic_lds(reinterpret_cast<const void*>(&dw_kernel_rs<3>), DW_LDS_STAGES * DW_STAGE_BYTES, "dw_kernel_rs");
-        if (rc_lds != HGYM_OK) return rc_lds;
-        prof_begin(HGYM_PROF_DW, s);
-        hipLaunchKernelGGL(dw_kernel_rs<3>, dim3(blocks), dim3(DW_THREADS), DW_LDS_STAGES * DW_STAGE_BYTES, s, d);
-        prof_end(HGYM_PROF_DW, s, fl);
-        HG_CHECK_LAUNCH("dw_kernel_rs");
+    // prologue_done: the gradient call has already taken the learning-rate decision and Adam's step scalars (FusedPath::prologue_in_grad)
+    template <typename T>
+    int32_t apply(const HgymPPOConfig& ppo, bool prologue_done) {
+        prof_begin(HGYM_PROF_APPLY, s);
+        const float inv_w = ppo.world_size > 1 ? (float)(1.0 / (double)ppo.world_size) : 1.0f;
+        if (ppo.world_size > 1 || !ppo.grad_norm_ready)        // else: reduce_slabs_kernel left the squared norm in opt[9]
+            hipLaunchKernelGGL(sqnorm_prologue_kernel, dim3(SQN_BLOCKS), dim3(256), 0, s, w.P, net.grads, inv_w, ppo, net.grads + w.P, net.opt_state,
+                               at<double>(w.sqn));
+        else if (!prologue_done)
+            hipLaunchKernelGGL(apply_prologue_kernel, dim3(1), dim3(64), 0, s, ppo, net.grads + w.P, inv_w, net.opt_state);
+        const SegTable tab = segments(0);
+        // 256 workgroups per segment: the two first-layer matrices hold 57 % of the parameters, and 64 workgroups (a quarter of
+        // the CUs) walked them in 22 dependent load -> store rounds per lane (30.7 us; 18.1 us with 256, 20.8 us with 512)
+        hipLaunchKernelGGL((adam_kernel<T>), dim3(256, tab.n), dim3(256), 0, s, tab, ppo, net.params, net.grads, net.adam_m, net.adam_v,
+                           inv_w, net.opt_state);
+        prof_end(HGYM_PROF_APPLY, s, (double)w.P * 36.0);
+        HG_CHECK_LAUNCH("adam_kernel");
         return HGYM_OK;
     }
 
-    // slab reduction of the segments whose parameters lie in [lo, hi) of the flat vector
-    int32_t reduce_range(int64_t lo, int64_t hi) {
-        const SegTable all = segments(true);
-        SegTable tab;
-        memset(&tab, 0, sizeof(tab));
-        int64_t elems = 0;
-        for (int i = 0; i < all.n; ++i)
-            if (all.s[i].off >= lo && all.s[i].off < hi) {
-                tab.s[tab.n++] = all.s[i];
-                elems += (int64_t)all.s[i].rows * all.s[i].cols;
-            }
-        if (tab.n == 0) return HGYM_OK;
-        prof_begin(HGYM_PROF_REDUCE, s);
-        hipLaunchKernelGGL(reduce_slabs_kernel, dim3(RSN_X, tab.n), dim3(256), 0, s, tab, w.Ps, at<float>(w.slabs), net.grads, net.opt_state);
-        prof_end(HGYM_PROF_REDUCE, s, (double)elems * 4.0 * (w.dw_splits + 1));
-        HG_CHECK_LAUNCH("reduce_slabs_kernel");
+    template <typename T>
+    int32_t sync_shadow() {
+        const SegTable tab = segments(0);
+        hipLaunchKernelGGL((sync_shadow_kernel<T>), dim3(64, tab.n), dim3(256), 0, s, tab, net.params);
+        HG_CHECK_LAUNCH("sync_shadow_kernel");
         return HGYM_OK;
     }
+};
 
-    // part < 0: the whole minibatch gradient.  part 0 / 1: the two halves of hgym_ppo_grad_part -- 0 leaves std's and the actor's
-    // gradient final, 1 the critic's, the auxiliary head's and the KL slot.
-    int32_t fused_grad(const HgymPPOConfig& ppo, const HgymBatch& b, int part = -1) {
-        const int B = b.B, A = cfg.num_actions;
-        const int64_t critic_off = w.net[1].layer[0].w_off;
-        const bool aux_fb = w.nnets > 2 && w.fused_aux;      // the auxiliary head as a third grid row of the same launches
-        // bf16 shadows of the storage rows (HgymBatch.obs_bf16 / priv_bf16): gather 2 B per element, keep no operand copy
-        static const bool no_shadow = getenv("HGYM_NO_SHADOW") != nullptr;       // A/B experiments only
-        const bool shadow = b.obs_bf16 && b.priv_bf16 && !no_shadow && b.num_rows > 0 &&
-                            b.num_rows * shadow_ld(0) * 2 < ((int64_t)1 << 32) && b.num_rows * shadow_ld(1) * 2 < ((int64_t)1 << 32);
-        const HgymBatch* gb = shadow ? &b : nullptr;
-        // In two parts (hgym_ppo_grad_part): part 0 runs everything up to and including ALL weight-gradient products and sums the
-        // slabs of [std | actor]; part 1 only sums the rest.  (Until round 3 part 1 also launched the critic's products on their own:
-        // two launches of 144 and 112 workgroups on 256 CUs, each as long as the full one -- 2 x 142 us against 178 us.)
-        if (part == 1) return reduce_range(critic_off, w.P);
-        float* mu = at<float>(w.net[0].out_f32);
-        float* val = at<float>(w.net[1].out_f32);
-        const float* xs[3] = {b.obs, b.priv, b.obs};
-        const int64_t ldxs[3] = {cfg.num_obs, cfg.num_priv, cfg.num_obs};
-        float* outs[3] = {mu, val, nullptr};
-        const int64_t ldos[3] = {A, 1, 0};
-        const int Bp = (int)round_up(B, 64);
-        const int nets = aux_fb ? 3 : 2;
-        // (128-row tiles on eight 256-register wavefronts -- round 4's mlp_fb2_kernel -- measured equal to slightly slower:
-        // profiles/r04_fb2_128row_tiles_negative_result.txt; its source is profiles/r04_fb2_128row_kernel.patch; round 6 rebuilt the idea on role-specialised wavefronts at 64 and 128 rows: profiles/r06_fb3_role_specialised_wavefronts.txt.)
-        const int tiles = Bp / 64;
-        HG_REQUIRE(tiles <= MAX_LOSS_BLOCKS, HGYM_E_UNSUPPORTED, "minibatch %d too large for the loss partial buffer", B);
-        HG_REQUIRE(B <= w.maxM, HGYM_E_SHAPE, "minibatch %d exceeds max_batch %lld", B, (long long)w.maxM);
-        int32_t rc = HGYM_OK;
-        {   // forward + PPO loss + dZ chain of both nets: ONE launch (hgym_fused.hpp: mlp_fb_kernel)
-            FwdArgs fa = make_fwd_args(0, nets, B, xs, ldxs, b.idx, outs, ldos, true, nullptr, nullptr);
-            fa.net[2].X0 = nullptr;       // the head's first-layer operand for the weight gradient is the actor's copy (fused_dw)
-            if (shadow) {
-                HG_REQUIRE((((uintptr_t)b.obs_bf16 | (uintptr_t)b.priv_bf16) & 15) == 0, HGYM_E_BADARG, "observation shadows must be 16-byte aligned");
-                for (int i = 0; i < nets; ++i) {
-                    fa.net[i].xb = (const __bf16*)(i == 1 ? b.priv_bf16 : b.obs_bf16);
-                    fa.net[i].ldxb = shadow_ld(i == 1 ? 1 : 0);
-                    fa.net[i].X0 = nullptr;
-                }
-            }
-            FbLoss fl;
-            memset(&fl, 0, sizeof(fl));
-            fl.actions = b.actions;
-            fl.old_mu = b.mu;
-            fl.old_sigma = b.sigma;
-            fl.values = b.values;
-            fl.advantages = b.advantages;
-            fl.returns = b.returns;
-            fl.logp = b.logp;
-            fl.clip = ppo.clip_param;
-            fl.value_coef = ppo.value_loss_coef;
-            fl.entropy_coef = ppo.entropy_coef;
-            fl.partials = at<float>(w.partials);
-            fl.aux_target = b.priv;
-            fl.aux_ldt = cfg.num_priv;
-            fl.aux_off = cfg.aux_target_offset;
-            fl.aux_coef = ppo.aux_coef;
-            size_t lds = 0;
-            for (int i = 0; i < nets; ++i)
-                lds = std::max(lds, (size_t)fb_lds_bytes(fa.net[i]));       // the nets the kernel receives (fused_supported: same sum)
-            HG_REQUIRE(lds <= FB_LDS_LIMIT, HGYM_E_UNSUPPORTED, "mlp_fb_kernel needs %zu bytes of LDS", lds);
-            FwdArgs fb = fa;
-            fb.nets = nets;
-            fb.dbg = phase_buffer((int64_t)tiles * nets);
-            prof_begin(HGYM_PROF_MLP_FWD, s);
-            const int32_t rc_fb = launch_mlp_fb(fb, fl, shadow, ppo.value_loss_unclipped != 0, tiles, nets, lds, s);      // (hgym_update.hip: the kernel's own code object)
-            if (rc_fb) return rc_fb;
-            double flops = 0.0;
-            for (int i = 0; i < nets; ++i) {
-                for (int l = 0; l < 4; ++l) flops += 2.0 * (double)B * w.net[i].layer[l].N * w.net[i].layer[l].K;
-                for (int l = 1; l < 4; ++l) flops += 2.0 * (double)B * w.net[i].layer[l].K * w.net[i].layer[l].N;
-            }
-            prof_end(HGYM_PROF_MLP_FWD, s, flops);
-            HG_CHECK_LAUNCH("mlp_fb_kernel");
-        }
-        // the minibatch's loss scalars (per-tile partials -> opt_state, std / head-bias gradients, KL slot): one extra workgroup of
-        // the weight-gradient launch that follows anyway (it needs nothing but the partials mlp_fb_kernel has just written)
-        const ScalArgs sc = {tiles, B, A, aux_fb ? w.net[2].layer[3].N : 0, at<float>(w.partials), net.grads,
-                             net.grads + w.net[0].layer[3].b_off, net.grads + w.net[1].layer[3].b_off, net.grads + w.P, net.opt_state,
-                             (double)ppo.beta1, (double)ppo.beta2, prologue_in_grad(ppo) ? 1 : 0, ppo.adaptive_lr, ppo.desired_kl, ppo.lr_min,
-                             ppo.lr_max, 1};
-        rc = fused_dw(0, nets, B, &sc, gb);
-        if (rc) return rc;
-        if (w.nnets > 2 && !aux_fb) {
-            const int32_t rca = aux_grad(ppo, b);
-            if (rca) return rca;
-        }
-        return part == 0 ? reduce_range(0, critic_off) : reduce_range(0, w.P);
-    }
-
-    int32_t act(int M, const float* obs, const float* priv, const float* z, uint64_t seed, const int64_t* step, float* actions, float* mu,
-                float* sigma, float* logp, float* values, const FinArgs* fin = nullptr, const HgymObsShadow* sh = nullptr) {
-        if (w.fused) {
-            const float* xs[3] = {obs, priv, nullptr};
-            const int64_t ldxs[3] = {cfg.num_obs, cfg.num_priv, 0};
-            float* outs[3] = {mu, values, nullptr};
-            const int64_t ldos[3] = {cfg.num_actions, 1, 0};
-            const SampleOut smp = {z, seed, step, actions, sigma, logp};
-            return fused_forward(0, 2, M, xs, ldxs, nullptr, outs, ldos, false, &smp, fin, sh);
-        }
-        HG_REQUIRE(!sh || (!sh->obs && !sh->priv), HGYM_E_UNSUPPORTED, "the observation shadow exists on the fused bf16 path only (hgym_net_shadow_ld = 0 here)");
-        if (fin) {     // generic path: the postponed finaliser as its own (tiny) launch
-            hipLaunchKernelGGL(fin_only_kernel, dim3(1), dim3(1024), 0, s, *fin);
-            HG_CHECK_LAUNCH("fin_only_kernel");
-        }
-        int32_t rc = forward(0, M, obs, cfg.num_obs, nullptr, mu, cfg.num_actions, false);
-        if (rc) return rc;
-        rc = forward(1, M, priv, cfg.num_priv, nullptr, values, 1, false);
-        if (rc) return rc;
-        hipLaunchKernelGGL(act_sample_kernel, dim3(ceil_div(M, 256)), dim3(256), 0, s, M, cfg.num_actions, mu, net.params, z, seed, step,
-                           actions, sigma, logp);
-        HG_CHECK_LAUNCH("act_sample_kernel");
-        return HGYM_OK;
-    }
-
-    // the critic over M rows in pieces of at most max_batch (a multiple of 64 rows each: whole tiles); fused path: 64-row tiles, the
-    // shadow's priv rows written by the tiles that read them
-    int32_t critic_values(int64_t M, const float* priv, float* values, const HgymObsShadow* sh) {
-        const int64_t piece = std::max<int64_t>(64, w.maxM / 64 * 64);
-        for (int64_t m0 = 0; m0 < M; m0 += piece) {
-            const int m = (int)std::min<int64_t>(piece, M - m0);
-            const float* x = priv + m0 * cfg.num_priv;
-            int32_t rc;
-            if (w.fused) {
-                const float* xs[3] = {nullptr, x, nullptr};
-                const int64_t ldxs[3] = {0, cfg.num_priv, 0};
-                float* outs[3] = {nullptr, values + m0, nullptr};
-                const int64_t ldos[3] = {0, 1, 0};
-                HgymObsShadow s1 = {nullptr, 0, nullptr, 0};
-                if (sh && sh->priv) {
-                    s1.priv = (char*)sh->priv + m0 * sh->ld_priv * 2;
-                    s1.ld_priv = sh->ld_priv;
-                }
-                rc = fused_forward(1, 1, m, xs, ldxs, nullptr, outs, ldos, false, nullptr, nullptr, (sh && sh->priv) ? &s1 : nullptr);
-            } else {
-                rc = forward(1, m, x, cfg.num_priv, nullptr, values + m0, 1, false);
-            }
-            if (rc) return rc;
-        }
-        return HGYM_OK;
-    }
-
+// The layer-by-layer path: every dense product through gemm_nt_kernel in the operand precision T, plus the packs, transposes and
+// row sums around it.
+template <typename T>
+struct GemmPath : NetBase {
     int32_t forward(int which, int M, const float* x, int64_t ldx, const int64_t* idx, float* y_out, int64_t ld_out, bool train) {
-        if (w.fused && (which < 2 || w.fused_aux)) {
-            const float* xs[3] = {x, x, x};
-            const int64_t ldxs[3] = {ldx, ldx, ldx};
-            float* outs[3] = {y_out, y_out, y_out};
-            const int64_t ldos[3] = {ld_out, ld_out, ld_out};
-            return fused_forward(which, 1, M, xs, ldxs, idx, outs, ldos, train, nullptr);
-        }
         const NetLayout& n = w.net[which];
         HG_REQUIRE(M > 0 && M <= w.maxM, HGYM_E_SHAPE, "batch %d exceeds max_batch %lld", M, (long long)w.maxM);
         const LayerLayout& l0 = n.layer[0];
@@ -1220,7 +906,6 @@ struct NetRunner {
     int32_t backward(int which, int M) {
         const NetLayout& n = w.net[which];
         const int Mp = (int)round_up(M, w.SE);
-        cur_Mp = Mp;
         for (int l = n.L - 1; l >= 0; --l) {
             const LayerLayout& y = n.layer[l];
             {   // dW_l[N][K] = sum_m dY[m][n] * X[m][k]  (contraction over the batch, split-K slabs)
@@ -1238,7 +923,7 @@ struct NetRunner {
                 g.Cf = at<float>(w.slabs) + y.w_off;
                 g.ldcf = y.K;
                 g.slab_stride = w.Ps;
-                const int want = split_count(y);
+                const int want = split_count(y, Mp);
                 const int32_t got = launch_gemm<T>(g, want, s);
                 if (got < 0) return got;
                 HG_REQUIRE(got == want, HGYM_E_LAUNCH, "split-K mismatch %d vs %d", got, want);
@@ -1291,15 +976,14 @@ struct NetRunner {
                            cfg.aux_target_offset, b.idx, ppo.aux_coef, at<T>(last.dY), (int64_t)last.Ncp, at<T>(last.dYT), w.Mp,
                            net.opt_state);
         HG_CHECK_LAUNCH("aux_mse_kernel");
-        cur_Mp = Bp;
         return backward(2, B);
     }
 
-    int32_t grad(const HgymPPOConfig& ppo, const HgymBatch& b, int part = -1) {
+    // part 1 (the second half of hgym_ppo_grad_part) has nothing left to do: part 0 does everything (the caller's first bucket goes out
+    // complete, just later)
+    int32_t grad(const HgymPPOConfig& ppo, const HgymBatch& b, int part) {
+        if (part == 1) return HGYM_OK;
         const int B = b.B, A = cfg.num_actions;
-        HG_REQUIRE(B > 0 && B <= w.maxM, HGYM_E_SHAPE, "minibatch %d exceeds max_batch %lld", B, (long long)w.maxM);
-        if (w.fused) return fused_grad(ppo, b, part);
-        if (part == 1) return HGYM_OK;      // layer-by-layer path: part 0 does everything (the caller's first bucket goes out complete, just later)
         float* mu = at<float>(w.net[0].out_f32);
         float* val = at<float>(w.net[1].out_f32);
         if (hipMemsetAsync(net.grads, 0, (size_t)w.P * sizeof(float), s) != hipSuccess) HG_FAIL(HGYM_E_LAUNCH, "memset of grads failed");
@@ -1340,7 +1024,6 @@ struct NetRunner {
                              (double)ppo.beta1, (double)ppo.beta2, 0, 0, 0.0f, 0.0, 0.0, 1};
         hipLaunchKernelGGL(ppo_scalars_kernel, dim3(1), dim3(512), 0, s, sc);
         HG_CHECK_LAUNCH("ppo_scalars_kernel");
-        cur_Mp = Bp;
         rc = backward(0, B);
         if (rc) return rc;
         rc = backward(1, B);
@@ -1349,40 +1032,348 @@ struct NetRunner {
             rc = aux_grad(ppo, b);
             if (rc) return rc;
         }
-        const SegTable tab = segments(true);
+        const SegTable tab = segments(Bp);
         hipLaunchKernelGGL(reduce_slabs_kernel, dim3(RSN_X, tab.n), dim3(256), 0, s, tab, w.Ps, at<float>(w.slabs), net.grads, net.opt_state);
         HG_CHECK_LAUNCH("reduce_slabs_kernel");
         return HGYM_OK;
     }
 
-    // The fused path on one rank with grad_norm_ready: the loss-scalar workgroup that rides in the weight-gradient launch has already taken
-    // the learning-rate decision and prepared Adam's step scalars (ScalArgs::do_prologue); hgym_ppo_apply then starts with Adam.
-    bool prologue_in_grad(const HgymPPOConfig& ppo) const { return w.fused && ppo.world_size <= 1 && ppo.grad_norm_ready != 0; }
-
-    int32_t apply(const HgymPPOConfig& ppo) {
-        prof_begin(HGYM_PROF_APPLY, s);
-        const float inv_w = ppo.world_size > 1 ? (float)(1.0 / (double)ppo.world_size) : 1.0f;
-        if (ppo.world_size > 1 || !ppo.grad_norm_ready)        // else: reduce_slabs_kernel left the squared norm in opt[9]
-            hipLaunchKernelGGL(sqnorm_prologue_kernel, dim3(SQN_BLOCKS), dim3(256), 0, s, w.P, net.grads, inv_w, ppo, net.grads + w.P, net.opt_state,
-                               at<double>(w.sqn));
-        else if (!prologue_in_grad(ppo))
-            hipLaunchKernelGGL(apply_prologue_kernel, dim3(1), dim3(64), 0, s, ppo, net.grads + w.P, inv_w, net.opt_state);
-        const SegTable tab = segments(false);
-        // 256 workgroups per segment: the two first-layer matrices hold 57 % of the parameters, and 64 workgroups (a quarter of
-        // the CUs) walked them in 22 dependent load -> store rounds per lane (30.7 us; 18.1 us with 256, 20.8 us with 512)
-        hipLaunchKernelGGL((adam_kernel<T>), dim3(256, tab.n), dim3(256), 0, s, tab, ppo, net.params, net.grads, net.adam_m, net.adam_v,
-                           inv_w, net.opt_state);
-        prof_end(HGYM_PROF_APPLY, s, (double)w.P * 36.0);
-        HG_CHECK_LAUNCH("adam_kernel");
+    int32_t act(int M, const float* obs, const float* priv, const float* z, uint64_t seed, const int64_t* step, float* actions, float* mu,
+                float* sigma, float* logp, float* values, const FinArgs* fin, const HgymObsShadow* sh) {
+        HG_REQUIRE(!sh || (!sh->obs && !sh->priv), HGYM_E_UNSUPPORTED, "the observation shadow exists on the fused bf16 path only (hgym_net_shadow_ld = 0 here)");
+        if (fin) {     // the postponed finaliser as its own (tiny) launch
+            hipLaunchKernelGGL(fin_only_kernel, dim3(1), dim3(1024), 0, s, *fin);
+            HG_CHECK_LAUNCH("fin_only_kernel");
+        }
+        int32_t rc = forward(0, M, obs, cfg.num_obs, nullptr, mu, cfg.num_actions, false);
+        if (rc) return rc;
+        rc = forward(1, M, priv, cfg.num_priv, nullptr, values, 1, false);
+        if (rc) return rc;
+        hipLaunchKernelGGL(act_sample_kernel, dim3(ceil_div(M, 256)), dim3(256), 0, s, M, cfg.num_actions, mu, net.params, z, seed, step,
+                           actions, sigma, logp);
+        HG_CHECK_LAUNCH("act_sample_kernel");
         return HGYM_OK;
     }
 
-    int32_t sync_shadow() {
-        const SegTable tab = segments(false);
-        hipLaunchKernelGGL((sync_shadow_kernel<T>), dim3(64, tab.n), dim3(256), 0, s, tab, net.params);
-        HG_CHECK_LAUNCH("sync_shadow_kernel");
+    // the critic over M rows in pieces of at most max_batch (a multiple of 64 rows each)
+    int32_t critic_values(int64_t M, const float* priv, float* values, const HgymObsShadow* sh) {
+        HG_REQUIRE(!sh || !sh->priv, HGYM_E_UNSUPPORTED, "the observation shadow exists on the fused bf16 path only");
+        const int64_t piece = std::max<int64_t>(64, w.maxM / 64 * 64);
+        for (int64_t m0 = 0; m0 < M; m0 += piece) {
+            const int32_t rc = forward(1, (int)std::min<int64_t>(piece, M - m0), priv + m0 * cfg.num_priv, cfg.num_priv, nullptr, values + m0, 1,
+                                       false);
+            if (rc) return rc;
+        }
         return HGYM_OK;
     }
+
+    int32_t apply(const HgymPPOConfig& ppo) { return NetBase::apply<T>(ppo, false); }
+    int32_t sync_shadow() { return NetBase::sync_shadow<T>(); }
+};
+
+// The fused bf16 path (hgym_fused.hpp): the actor and the critic, and the auxiliary head when it has the fused layout too, through
+// mlp_fwd_kernel, mlp_fb_kernel and dw_kernel_rs.  An auxiliary head that does not fit those kernels takes the layer-by-layer path.
+struct FusedPath : NetBase {
+    GemmPath<__bf16> aux;
+
+    explicit FusedPath(const NetBase& b) : NetBase(b), aux{b} {}
+
+    struct SampleOut {
+        const float* z; uint64_t seed; const int64_t* step; float* actions; float* sigma; float* logp;
+    };
+
+    FusedNet fused_net(int which, const NetIO& io) const {
+        FusedNet f;
+        memset(&f, 0, sizeof(f));
+        const NetLayout& n = w.net[which];
+        for (int l = 0; l < 4; ++l) {
+            const LayerLayout& y = n.layer[l];
+            FusedLayer& d = f.layer[l];
+            d.Wf = at<u32x4>(y.Wf);
+            d.WTf = at<u32x4>(y.WTf);
+            d.bias = net.params + y.b_off;
+            d.K = y.K;
+            d.N = y.N;
+            d.KB = y.KBf;
+            d.NB = y.NBf;
+            d.NBB = y.NBBf;
+        }
+        f.x = io.x;
+        f.ldx = io.ldx;
+        f.X0 = at<__bf16>(n.X0b);
+        for (int l = 0; l < 3; ++l) f.H[l] = at<__bf16>(n.Hb[l]);
+        for (int l = 0; l < 4; ++l) f.dZ[l] = at<__bf16>(n.dZb[l]);
+        f.out = io.out;
+        f.ldo = io.ldo;
+        return f;
+    }
+
+    template <int BM, int NW, int D, bool FIN>
+    int32_t launch_fwd_k(const FwdArgs& a, int nets) {
+        const size_t lds = fwd_lds(a, nets, BM);
+        const int32_t rc_lds = ensure_dynamic_lds(reinterpret_cast<const void*>(&mlp_fwd_kernel<BM, NW, D, FIN>), lds, "mlp_fwd_kernel");
+        if (rc_lds) return rc_lds;
+        FwdArgs b = a;
+        b.nets = nets;
+        const int rows = nets + (FIN ? 1 : 0);          // + the finaliser's grid row (its workgroup 0 works, the rest exit)
+        b.dbg = phase_buffer((int64_t)ceil_div(a.M, BM) * rows);
+        hipLaunchKernelGGL((mlp_fwd_kernel<BM, NW, D, FIN>), dim3(ceil_div(a.M, BM), rows), dim3(NW * 64), lds, s, b);
+        HG_CHECK_LAUNCH("mlp_fwd_kernel");
+        return HGYM_OK;
+    }
+    template <int BM, int NW, int D>
+    int32_t launch_fwd(const FwdArgs& a, int nets) {
+        return a.fin.N > 0 ? launch_fwd_k<BM, NW, D, true>(a, nets) : launch_fwd_k<BM, NW, D, false>(a, nets);
+    }
+
+    // sh (policy launches, no row gather): net 0 / 1 also store the bf16 of their input rows as rows of sh->obs / sh->priv
+    FwdArgs make_fwd_args(int first, int nets, int M, const NetIO io[3], const int64_t* idx, bool train, const SampleOut* smp,
+                          const FinArgs* fin, const HgymObsShadow* sh = nullptr) const {
+        FwdArgs a;
+        memset(&a, 0, sizeof(a));
+        for (int i = first; i < first + nets; ++i) a.net[i] = fused_net(i, io[i]);
+        if (sh && !idx && !train) {
+            if (first == 0 && sh->obs) { a.net[0].xs = (__bf16*)sh->obs; a.net[0].ldxs = sh->ld_obs; }
+            if (first <= 1 && first + nets > 1 && sh->priv) { a.net[1].xs = (__bf16*)sh->priv; a.net[1].ldxs = sh->ld_priv; }
+        }
+        a.net0 = first;
+        a.M = M;
+        a.idx = idx;
+        if (fin) a.fin = *fin;
+        a.train = train ? 3 : 0;
+        a.A = cfg.num_actions;
+        a.std_ = net.params;
+        if (smp) {
+            a.sample = 1;
+            a.z = smp->z;
+            a.k0 = (uint32_t)smp->seed;
+            a.k1 = (uint32_t)(smp->seed >> 32);
+            a.step = smp->step;
+            a.actions = smp->actions;
+            a.sigma = smp->sigma;
+            a.logp = smp->logp;
+        }
+        return a;
+    }
+
+    // forward of `nets` networks starting at `first` in ONE launch
+    int32_t forward_nets(int first, int nets, int M, const NetIO io[3], const int64_t* idx, bool train, const SampleOut* smp,
+                         const FinArgs* fin = nullptr, const HgymObsShadow* sh = nullptr) {
+        HG_REQUIRE(M > 0 && M <= w.maxM, HGYM_E_SHAPE, "batch %d exceeds max_batch %lld", M, (long long)w.maxM);
+        const int32_t rc_sh = check_shadow(w, sh);
+        if (rc_sh) return rc_sh;
+        const FwdArgs a = make_fwd_args(first, nets, M, io, idx, train, smp, fin, sh);
+        const int pcls = train ? HGYM_PROF_MLP_FWD : HGYM_PROF_POLICY;
+        prof_begin(pcls, s);
+        // 32-row tiles x 8 waves (weight ring depth 4) while they fit the chip in one round (one workgroup per CU: 2 * M / 32
+        // <= CUs, i.e. 4096 envs), 64-row tiles x 16 waves (depth 2) for the update and for larger rollouts; measured
+        // alternatives (64 rows x 8 waves, 32-row tiles for the update, other depths) were equal or slower
+        const int cus = device_cus() > 0 ? device_cus() : 256;
+        // (32-row tiles two per CU at 8192 rows: collection 5.32 vs 3.82 ms, profiles/r03_envs8192_policy_tiles_ab.txt)
+        const int32_t rc = (train || nets * ceil_div(M, 32) > cus) ? launch_fwd<64, 16, 2>(a, nets) : launch_fwd<32, 8, 4>(a, nets);
+        double fl = 0.0;
+        for (int i = first; i < first + nets; ++i)
+            for (int l = 0; l < 4; ++l) fl += 2.0 * (double)M * w.net[i].layer[l].N * w.net[i].layer[l].K;   // algorithmic (unpadded) flops
+        prof_end(pcls, s, fl);
+        return rc;
+    }
+
+    int32_t forward(int which, int M, const float* x, int64_t ldx, const int64_t* idx, float* y_out, int64_t ld_out, bool train) {
+        if (!w.net[which].fused) return aux.forward(which, M, x, ldx, idx, y_out, ld_out, train);
+        NetIO io[3] = {};
+        io[which] = {x, ldx, y_out, ld_out};
+        return forward_nets(which, 1, M, io, idx, train, nullptr);
+    }
+
+    // all weight (and hidden bias) gradients of nets [0, nets): one launch, split-K slabs, plus the loss-scalar workgroup `sc`
+    // (the auxiliary head, net 2, reads the ACTOR's bf16 copy of the gathered observation rows as its first-layer operand -- same
+    // rows, same columns -- and every bias gradient of it is a column sum of dZ: its loss has no per-tile partial sums for them)
+    // gb (mlp_fb_kernel<XB16> ran): the first-layer operands were never copied -- those products gather their rows by gb->idx from the
+    // bf16 shadows
+    int32_t dw(int nets, int B, const ScalArgs& sc, const HgymBatch* gb) {
+        const int Bp = (int)round_up(B, 64);
+        DwArgs d;
+        memset(&d, 0, sizeof(d));
+        d.B = B;
+        int tile = 0;
+        double fl = 0.0;
+        for (int i = 0; i < nets; ++i)
+            for (int l = 0; l < 4; ++l) {
+                const NetLayout& n = w.net[i];
+                const LayerLayout& y = n.layer[l];
+                HG_REQUIRE(d.np < DW_MAX_PRODUCTS, HGYM_E_UNSUPPORTED, "too many weight-gradient products in one launch");
+                DwProduct& p = d.p[d.np++];
+                p.Z = at<__bf16>(n.dZb[l]);
+                p.CBz = l < 3 ? y.N / 16 : 2 * y.NBBf;
+                p.X = l == 0 ? at<__bf16>(w.net[i == 2 ? 0 : i].X0b) : at<__bf16>(n.Hb[l - 1]);
+                p.CBx = l == 0 ? 2 * y.KBf : y.K / 16;
+                if (l == 0 && gb) {
+                    p.X = (const __bf16*)(i == 1 ? gb->priv_bf16 : gb->obs_bf16);
+                    p.gidx = gb->idx;
+                    p.ldg = shadow_ld(w, i == 1 ? 1 : 0);
+                    p.CBx = (int)(p.ldg / 16);
+                }
+                p.N = y.N;
+                p.K = y.K;
+                p.w_off = y.w_off;
+                p.b_off = (l < 3 || i == 2) ? y.b_off : -1;
+                p.tiles_n = ceil_div(y.N, DW_TILE_N);
+                p.tiles_k = ceil_div(y.K, DW_TILE_K);
+                p.tile0 = tile;
+                tile += p.tiles_n * p.tiles_k;
+                fl += 2.0 * (double)B * y.N * y.K;
+            }
+        d.total_tiles = tile;
+        d.splits = w.dw_splits;
+        d.steps_total = Bp / 32;
+        d.steps_per_split = ceil_div(d.steps_total, w.dw_splits);
+        d.slabs = at<float>(w.slabs);
+        d.slab_stride = w.Ps;
+        d.zeros = at<char>(w.zeros);
+        d.sc = sc;
+        d.scal_bid = tile * (int)round_up(w.dw_splits, 8);
+        const int blocks = d.scal_bid + 1;
+        const int32_t rc_lds = ensure_dynamic_lds(reinterpret_cast<const void*>(&dw_kernel_rs<3>), DW_LDS_STAGES * DW_STAGE_BYTES, "dw_kernel_rs");
+        if (rc_lds != HGYM_OK) return rc_lds;
+        prof_begin(HGYM_PROF_DW, s);
+        hipLaunchKernelGGL(dw_kernel_rs<3>, dim3(blocks), dim3(DW_THREADS), DW_LDS_STAGES * DW_STAGE_BYTES, s, d);
+        prof_end(HGYM_PROF_DW, s, fl);
+        HG_CHECK_LAUNCH("dw_kernel_rs");
+        return HGYM_OK;
+    }
+
+    // slab reduction of the segments whose parameters lie in [lo, hi) of the flat vector (Mp: an auxiliary head on the layer-by-layer
+    // path took its slab counts from the minibatch's contraction padding)
+    int32_t reduce_range(int64_t lo, int64_t hi, int Mp) {
+        const SegTable all = segments(Mp);
+        SegTable tab;
+        memset(&tab, 0, sizeof(tab));
+        int64_t elems = 0;
+        for (int i = 0; i < all.n; ++i)
+            if (all.s[i].off >= lo && all.s[i].off < hi) {
+                tab.s[tab.n++] = all.s[i];
+                elems += (int64_t)all.s[i].rows * all.s[i].cols;
+            }
+        if (tab.n == 0) return HGYM_OK;
+        prof_begin(HGYM_PROF_REDUCE, s);
+        hipLaunchKernelGGL(reduce_slabs_kernel, dim3(RSN_X, tab.n), dim3(256), 0, s, tab, w.Ps, at<float>(w.slabs), net.grads, net.opt_state);
+        prof_end(HGYM_PROF_REDUCE, s, (double)elems * 4.0 * (w.dw_splits + 1));
+        HG_CHECK_LAUNCH("reduce_slabs_kernel");
+        return HGYM_OK;
+    }
+
+    // part < 0: the whole minibatch gradient.  part 0 / 1: the two halves of hgym_ppo_grad_part -- 0 leaves std's and the actor's
+    // gradient final, 1 the critic's, the auxiliary head's and the KL slot.
+    int32_t grad(const HgymPPOConfig& ppo, const HgymBatch& b, int part) {
+        const int B = b.B, A = cfg.num_actions;
+        const int64_t critic_off = w.net[1].layer[0].w_off;
+        const int Mp = (int)round_up(B, w.SE);
+        // In two parts (hgym_ppo_grad_part): part 0 runs everything up to and including ALL weight-gradient products and sums the
+        // slabs of [std | actor]; part 1 only sums the rest.  (Until round 3 part 1 also launched the critic's products on their own:
+        // two launches of 144 and 112 workgroups on 256 CUs, each as long as the full one -- 2 x 142 us against 178 us.)
+        if (part == 1) return reduce_range(critic_off, w.P, Mp);
+        const int nets = w.net[2].fused ? 3 : 2;      // the auxiliary head as a third grid row of the same launches
+        // bf16 shadows of the storage rows (HgymBatch.obs_bf16 / priv_bf16): gather 2 B per element, keep no operand copy
+        const bool shadow = b.obs_bf16 && b.priv_bf16 && b.num_rows > 0 && b.num_rows * shadow_ld(w, 0) * 2 < ((int64_t)1 << 32) &&
+                            b.num_rows * shadow_ld(w, 1) * 2 < ((int64_t)1 << 32);
+        // (128-row tiles on eight 256-register wavefronts -- round 4's mlp_fb2_kernel -- measured equal to slightly slower:
+        // profiles/r04_fb2_128row_tiles_negative_result.txt; its source is profiles/r04_fb2_128row_kernel.patch; round 6 rebuilt the idea on role-specialised wavefronts at 64 and 128 rows: profiles/r06_fb3_role_specialised_wavefronts.txt.)
+        const int tiles = (int)round_up(B, 64) / 64;
+        HG_REQUIRE(tiles <= MAX_LOSS_BLOCKS, HGYM_E_UNSUPPORTED, "minibatch %d too large for the loss partial buffer", B);
+        {   // forward + PPO loss + dZ chain of both nets: ONE launch (hgym_fused.hpp: mlp_fb_kernel)
+            const NetIO io[3] = {{b.obs, cfg.num_obs, at<float>(w.net[0].out_f32), A},
+                                 {b.priv, cfg.num_priv, at<float>(w.net[1].out_f32), 1},
+                                 {b.obs, cfg.num_obs, nullptr, 0}};
+            FwdArgs fb = make_fwd_args(0, nets, B, io, b.idx, true, nullptr, nullptr);
+            fb.net[2].X0 = nullptr;       // the head's first-layer operand for the weight gradient is the actor's copy (dw)
+            if (shadow) {
+                HG_REQUIRE((((uintptr_t)b.obs_bf16 | (uintptr_t)b.priv_bf16) & 15) == 0, HGYM_E_BADARG, "observation shadows must be 16-byte aligned");
+                for (int i = 0; i < nets; ++i) {
+                    fb.net[i].xb = (const __bf16*)(i == 1 ? b.priv_bf16 : b.obs_bf16);
+                    fb.net[i].ldxb = shadow_ld(w, i == 1 ? 1 : 0);
+                    fb.net[i].X0 = nullptr;
+                }
+            }
+            FbLoss fl;
+            memset(&fl, 0, sizeof(fl));
+            fl.actions = b.actions;
+            fl.old_mu = b.mu;
+            fl.old_sigma = b.sigma;
+            fl.values = b.values;
+            fl.advantages = b.advantages;
+            fl.returns = b.returns;
+            fl.logp = b.logp;
+            fl.clip = ppo.clip_param;
+            fl.value_coef = ppo.value_loss_coef;
+            fl.entropy_coef = ppo.entropy_coef;
+            fl.partials = at<float>(w.partials);
+            fl.aux_target = b.priv;
+            fl.aux_ldt = cfg.num_priv;
+            fl.aux_off = cfg.aux_target_offset;
+            fl.aux_coef = ppo.aux_coef;
+            size_t lds = 0;
+            for (int i = 0; i < nets; ++i)
+                lds = std::max(lds, (size_t)fb_lds_bytes(fb.net[i]));       // the nets the kernel receives (fused_supported: same sum)
+            HG_REQUIRE(lds <= FB_LDS_LIMIT, HGYM_E_UNSUPPORTED, "mlp_fb_kernel needs %zu bytes of LDS", lds);
+            fb.nets = nets;
+            fb.dbg = phase_buffer((int64_t)tiles * nets);
+            prof_begin(HGYM_PROF_MLP_FWD, s);
+            const int32_t rc_fb = launch_mlp_fb(fb, fl, shadow, ppo.value_loss_unclipped != 0, tiles, nets, lds, s);      // (hgym_update.hip: the kernel's own code object)
+            if (rc_fb) return rc_fb;
+            double flops = 0.0;
+            for (int i = 0; i < nets; ++i) {
+                for (int l = 0; l < 4; ++l) flops += 2.0 * (double)B * w.net[i].layer[l].N * w.net[i].layer[l].K;
+                for (int l = 1; l < 4; ++l) flops += 2.0 * (double)B * w.net[i].layer[l].K * w.net[i].layer[l].N;
+            }
+            prof_end(HGYM_PROF_MLP_FWD, s, flops);
+            HG_CHECK_LAUNCH("mlp_fb_kernel");
+        }
+        // the minibatch's loss scalars (per-tile partials -> opt_state, std / head-bias gradients, KL slot): one extra workgroup of
+        // the weight-gradient launch that follows anyway (it needs nothing but the partials mlp_fb_kernel has just written)
+        const ScalArgs sc = {tiles, B, A, nets == 3 ? w.net[2].layer[3].N : 0, at<float>(w.partials), net.grads,
+                             net.grads + w.net[0].layer[3].b_off, net.grads + w.net[1].layer[3].b_off, net.grads + w.P, net.opt_state,
+                             (double)ppo.beta1, (double)ppo.beta2, prologue_in_grad(ppo) ? 1 : 0, ppo.adaptive_lr, ppo.desired_kl, ppo.lr_min,
+                             ppo.lr_max, 1};
+        int32_t rc = dw(nets, B, sc, shadow ? &b : nullptr);
+        if (rc) return rc;
+        if (w.nnets > 2 && nets == 2) {
+            rc = aux.aux_grad(ppo, b);
+            if (rc) return rc;
+        }
+        return part == 0 ? reduce_range(0, critic_off, Mp) : reduce_range(0, w.P, Mp);
+    }
+
+    int32_t act(int M, const float* obs, const float* priv, const float* z, uint64_t seed, const int64_t* step, float* actions, float* mu,
+                float* sigma, float* logp, float* values, const FinArgs* fin, const HgymObsShadow* sh) {
+        const NetIO io[3] = {{obs, cfg.num_obs, mu, cfg.num_actions}, {priv, cfg.num_priv, values, 1}, {}};
+        const SampleOut smp = {z, seed, step, actions, sigma, logp};
+        return forward_nets(0, 2, M, io, nullptr, false, &smp, fin, sh);
+    }
+
+    // the critic over M rows in pieces of at most max_batch (a multiple of 64 rows each: whole tiles), the shadow's priv rows written by
+    // the tiles that read them
+    int32_t critic_values(int64_t M, const float* priv, float* values, const HgymObsShadow* sh) {
+        const int64_t piece = std::max<int64_t>(64, w.maxM / 64 * 64);
+        for (int64_t m0 = 0; m0 < M; m0 += piece) {
+            const NetIO io[3] = {{}, {priv + m0 * cfg.num_priv, cfg.num_priv, values + m0, 1}, {}};
+            HgymObsShadow s1 = {nullptr, 0, nullptr, 0};
+            if (sh && sh->priv) {
+                s1.priv = (char*)sh->priv + m0 * sh->ld_priv * 2;
+                s1.ld_priv = sh->ld_priv;
+            }
+            const int32_t rc = forward_nets(1, 1, (int)std::min<int64_t>(piece, M - m0), io, nullptr, false, nullptr, nullptr,
+                                            (sh && sh->priv) ? &s1 : nullptr);
+            if (rc) return rc;
+        }
+        return HGYM_OK;
+    }
+
+    // One rank with grad_norm_ready: the loss-scalar workgroup that rides in the weight-gradient launch has already taken the
+    // learning-rate decision and prepared Adam's step scalars (ScalArgs::do_prologue); hgym_ppo_apply then starts with Adam.
+    bool prologue_in_grad(const HgymPPOConfig& ppo) const { return ppo.world_size <= 1 && ppo.grad_norm_ready != 0; }
+
+    int32_t apply(const HgymPPOConfig& ppo) { return NetBase::apply<__bf16>(ppo, prologue_in_grad(ppo)); }
+    int32_t sync_shadow() { return NetBase::sync_shadow<__bf16>(); }
 };
 
 static int32_t check_net(const HgymNetConfig* cfg, const HgymNet* net, WsLayout* w) {
@@ -1394,6 +1385,41 @@ static int32_t check_net(const HgymNetConfig* cfg, const HgymNet* net, WsLayout*
     return HGYM_OK;
 }
 
+static int32_t check_ppo(const HgymPPOConfig* ppo) {
+    HG_REQUIRE(ppo, HGYM_E_BADARG, "null ppo");
+    HG_REQUIRE(ppo->value_loss_unclipped == 0 || ppo->value_loss_unclipped == 1, HGYM_E_BADARG,
+               "HgymPPOConfig.value_loss_unclipped=%d (0: clipped value loss, 1: unclipped)", ppo->value_loss_unclipped);
+    return HGYM_OK;
+}
+
+static int32_t check_batch(const WsLayout& w, const HgymBatch* b) {
+    HG_REQUIRE(b, HGYM_E_BADARG, "null batch");
+    HG_REQUIRE(b->obs && b->priv && b->actions && b->values && b->advantages && b->returns && b->logp && b->mu && b->sigma && b->idx,
+               HGYM_E_BADARG, "null batch tensor");
+    HG_REQUIRE(b->B > 0 && b->B <= w.maxM, HGYM_E_SHAPE, "minibatch %d exceeds max_batch %lld", b->B, (long long)w.maxM);
+    return HGYM_OK;
+}
+
+// The one place that picks a runner: the fused path when ws_layout gave the actor and the critic the fused layout, else the
+// layer-by-layer path in the configured precision.  `f` receives the runner; check_net's failures return before it runs.
+template <class F>
+static int32_t run(const HgymNetConfig* cfg, const HgymNet* net, void* stream, F&& f) {
+    WsLayout w;
+    const int32_t rc = check_net(cfg, net, &w);
+    if (rc) return rc;
+    const NetBase b{*cfg, *net, w, (hipStream_t)stream, (char*)net->workspace};
+    if (w.net[0].fused) {
+        FusedPath R(b);
+        return f(R);
+    }
+    if (cfg->precision == HGYM_F32) {
+        GemmPath<float> R{b};
+        return f(R);
+    }
+    GemmPath<__bf16> R{b};
+    return f(R);
+}
+
 // For hgym_rollout.hip (the fused policy + env step lives in a translation unit of its own: it also contains the env
 // arithmetic, which is built with -ffp-contract=off): the FwdArgs record of one PPO.act launch over the actor and the critic
 // with 32-row tiles, and the dynamic LDS those tiles need.  Fails unless the fused bf16 path serves this configuration with
@@ -1402,41 +1428,22 @@ int32_t rollout_fwd_args(const HgymNetConfig* cfg, const HgymNet* net, int M, co
                          const int64_t* step, float* actions, float* mu, float* sigma, float* logp, float* values, FwdArgs* out,
                          size_t* lds_bytes, const HgymObsShadow* sh) {
     WsLayout w;
-    const int32_t rc = check_net(cfg, net, &w);
+    int32_t rc = check_net(cfg, net, &w);
     if (rc) return rc;
-    HG_REQUIRE(cfg->precision == HGYM_BF16 && w.fused, HGYM_E_UNSUPPORTED, "the fused rollout step needs the bf16 fused path");
+    HG_REQUIRE(w.net[0].fused, HGYM_E_UNSUPPORTED, "the fused rollout step needs the bf16 fused path");
     HG_REQUIRE(M > 0 && M <= w.maxM, HGYM_E_SHAPE, "batch %d exceeds max_batch %lld", M, (long long)w.maxM);
     HG_REQUIRE(cfg->actor_dims[1] == 512 && cfg->critic_dims[1] == 768, HGYM_E_UNSUPPORTED,
                "fused rollout step: first hidden widths 512 / 768 (XBot-L) only, not %d / %d", cfg->actor_dims[1], cfg->critic_dims[1]);
-    NetRunner<__bf16> R{*cfg, *net, w, nullptr, (char*)net->workspace};
-    const float* xs[3] = {obs, priv, nullptr};
-    const int64_t ldxs[3] = {cfg->num_obs, cfg->num_priv, 0};
-    float* outs[3] = {mu, values, nullptr};
-    const int64_t ldos[3] = {cfg->num_actions, 1, 0};
-    const NetRunner<__bf16>::SampleOut smp = {nullptr, seed, step, actions, sigma, logp};
-    if (sh)
-        HG_REQUIRE((!sh->obs || (sh->ld_obs >= R.shadow_ld(0) && sh->ld_obs % 8 == 0 && ((uintptr_t)sh->obs & 15) == 0)) &&
-                       (!sh->priv || (sh->ld_priv >= R.shadow_ld(1) && sh->ld_priv % 8 == 0 && ((uintptr_t)sh->priv & 15) == 0)),
-                   HGYM_E_SHAPE, "observation shadow: bad leading dimension / alignment");
-    *out = R.make_fwd_args(0, 2, M, xs, ldxs, nullptr, outs, ldos, false, &smp, nullptr, sh);
+    rc = check_shadow(w, sh);
+    if (rc) return rc;
+    const FusedPath R(NetBase{*cfg, *net, w, nullptr, (char*)net->workspace});
+    const NetIO io[3] = {{obs, cfg->num_obs, mu, cfg->num_actions}, {priv, cfg->num_priv, values, 1}, {}};
+    const FusedPath::SampleOut smp = {nullptr, seed, step, actions, sigma, logp};
+    *out = R.make_fwd_args(0, 2, M, io, nullptr, false, &smp, nullptr, sh);
     out->nets = 2;
-    size_t lds = 0;
-    for (int i = 0; i < 2; ++i)
-        lds = std::max(lds, (size_t)fused_lds_p(out->net[i], 32) + (size_t)fused_lds_q(out->net[i], 32) + (size_t)fused_lds_bias(out->net[i]));
-    *lds_bytes = lds;
+    *lds_bytes = fwd_lds(*out, 2, 32);
     return HGYM_OK;
 }
-
-#define HG_DISPATCH(cfg, net, w, stream, expr)                                                     \
-    do {                                                                                           \
-        if ((cfg)->precision == HGYM_F32) {                                                        \
-            NetRunner<float> R{*(cfg), *(net), (w), (hipStream_t)(stream), (char*)(net)->workspace}; \
-            return R.expr;                                                                         \
-        } else {                                                                                   \
-            NetRunner<__bf16> R{*(cfg), *(net), (w), (hipStream_t)(stream), (char*)(net)->workspace}; \
-            return R.expr;                                                                         \
-        }                                                                                          \
-    } while (0)
 
 }  // namespace hgym
 
@@ -1457,91 +1464,77 @@ int64_t hgym_net_workspace_bytes(const HgymNetConfig* cfg) {
 }
 
 int32_t hgym_net_sync_shadow(const HgymNetConfig* cfg, const HgymNet* net, void* stream) {
-    WsLayout w;
-    const int32_t rc = check_net(cfg, net, &w);
-    if (rc) return rc;
-    HG_DISPATCH(cfg, net, w, stream, sync_shadow());
+    return run(cfg, net, stream, [](auto& R) { return R.sync_shadow(); });
 }
 
 int32_t hgym_mlp_forward(const HgymNetConfig* cfg, const HgymNet* net, int32_t which, int32_t M, const float* x, int64_t ldx, float* y,
                          void* stream) {
-    WsLayout w;
-    const int32_t rc = check_net(cfg, net, &w);
-    if (rc) return rc;
-    HG_REQUIRE(which == 0 || which == 1 || (which == 2 && cfg->aux_layers > 0), HGYM_E_BADARG, "which=%d", which);
-    HG_REQUIRE(x && y, HGYM_E_BADARG, "null x / y");
-    const int nout = which == 0 ? cfg->num_actions : (which == 1 ? 1 : cfg->aux_dims[cfg->aux_layers]);
-    HG_DISPATCH(cfg, net, w, stream, forward(which, M, x, ldx, nullptr, y, nout, false));
+    return run(cfg, net, stream, [&](auto& R) -> int32_t {
+        HG_REQUIRE(which == 0 || which == 1 || (which == 2 && cfg->aux_layers > 0), HGYM_E_BADARG, "which=%d", which);
+        HG_REQUIRE(x && y, HGYM_E_BADARG, "null x / y");
+        const int nout = which == 0 ? cfg->num_actions : (which == 1 ? 1 : cfg->aux_dims[cfg->aux_layers]);
+        return R.forward(which, M, x, ldx, nullptr, y, nout, false);
+    });
 }
 
 int32_t hgym_critic_values(const HgymNetConfig* cfg, const HgymNet* net, int64_t M, const float* priv, float* values,
                            const HgymObsShadow* shadow, void* stream) {
-    WsLayout w;
-    const int32_t rc = check_net(cfg, net, &w);
-    if (rc) return rc;
-    HG_REQUIRE(M > 0 && priv && values, HGYM_E_BADARG, "M=%lld, null priv / values", (long long)M);
-    HG_REQUIRE(!shadow || !shadow->priv || w.fused, HGYM_E_UNSUPPORTED, "the observation shadow exists on the fused bf16 path only");
-    HG_DISPATCH(cfg, net, w, stream, critic_values(M, priv, values, shadow));
+    return run(cfg, net, stream, [&](auto& R) -> int32_t {
+        HG_REQUIRE(M > 0 && priv && values, HGYM_E_BADARG, "M=%lld, null priv / values", (long long)M);
+        return R.critic_values(M, priv, values, shadow);
+    });
 }
 
 int64_t hgym_net_shadow_ld(const HgymNetConfig* cfg, int32_t which) {
     WsLayout w;
-    if (ws_layout(cfg, &w) != HGYM_OK || !w.fused || which < 0 || which > 1) return 0;
-    return (int64_t)w.net[which].layer[0].KBf * 32;
+    if (ws_layout(cfg, &w) != HGYM_OK || which < 0 || which > 1 || !w.net[which].fused) return 0;
+    return shadow_ld(w, which);
 }
 
 int32_t hgym_policy_act(const HgymNetConfig* cfg, const HgymNet* net, int32_t M, const float* obs, const float* priv, const float* z,
                         uint64_t seed, const int64_t* step_counter, float* actions, float* mu, float* sigma, float* logp, float* values,
                         const HgymObsShadow* shadow, void* stream) {
-    WsLayout w;
-    int32_t rc = check_net(cfg, net, &w);
-    if (rc) return rc;
-    HG_REQUIRE(obs && priv && actions && mu && sigma && logp && values, HGYM_E_BADARG, "null pointer");
-    HG_DISPATCH(cfg, net, w, stream, act(M, obs, priv, z, seed, step_counter, actions, mu, sigma, logp, values, nullptr, shadow));
+    return run(cfg, net, stream, [&](auto& R) -> int32_t {
+        HG_REQUIRE(obs && priv && actions && mu && sigma && logp && values, HGYM_E_BADARG, "null pointer");
+        return R.act(M, obs, priv, z, seed, step_counter, actions, mu, sigma, logp, values, nullptr, shadow);
+    });
 }
 
 int32_t hgym_policy_act_fin(const HgymNetConfig* cfg, const HgymNet* net, int32_t M, const float* obs, const float* priv, const float* z,
                             uint64_t seed, const int64_t* step_counter, float* actions, float* mu, float* sigma, float* logp,
                             float* values, const HgymEnvConfig* env_cfg, const HgymEnvState* env_st, const HgymEnvOut* env_out,
                             const HgymObsShadow* shadow, void* stream) {
-    WsLayout w;
-    int32_t rc = check_net(cfg, net, &w);
-    if (rc) return rc;
-    HG_REQUIRE(obs && priv && actions && mu && sigma && logp && values, HGYM_E_BADARG, "null pointer");
-    HG_REQUIRE(env_cfg && env_st && env_out, HGYM_E_BADARG, "null env cfg/state/out");
-    HG_REQUIRE(env_st->counters && env_st->episode_acc && env_out->time_out && env_out->extras_time_outs && env_out->extras_episode &&
-                   env_out->rew && env_out->reset, HGYM_E_BADARG, "null finaliser buffer");
-    HG_REQUIRE(env_cfg->num_envs > 0, HGYM_E_SHAPE, "num_envs=%d", env_cfg->num_envs);
-    const FinArgs fin = make_fin_args(*env_cfg, *env_st, *env_out, FIN_MODE_STEP);
-    HG_DISPATCH(cfg, net, w, stream, act(M, obs, priv, z, seed, step_counter, actions, mu, sigma, logp, values, &fin, shadow));
+    return run(cfg, net, stream, [&](auto& R) -> int32_t {
+        HG_REQUIRE(obs && priv && actions && mu && sigma && logp && values, HGYM_E_BADARG, "null pointer");
+        HG_REQUIRE(env_cfg && env_st && env_out, HGYM_E_BADARG, "null env cfg/state/out");
+        HG_REQUIRE(env_st->counters && env_st->episode_acc && env_out->time_out && env_out->extras_time_outs && env_out->extras_episode &&
+                       env_out->rew && env_out->reset, HGYM_E_BADARG, "null finaliser buffer");
+        HG_REQUIRE(env_cfg->num_envs > 0, HGYM_E_SHAPE, "num_envs=%d", env_cfg->num_envs);
+        const FinArgs fin = make_fin_args(*env_cfg, *env_st, *env_out, FIN_MODE_STEP);
+        return R.act(M, obs, priv, z, seed, step_counter, actions, mu, sigma, logp, values, &fin, shadow);
+    });
 }
 
 int32_t hgym_ppo_grad(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const HgymNet* net, const HgymBatch* batch, void* stream) {
-    WsLayout w;
-    const int32_t rc = check_net(cfg, net, &w);
-    if (rc) return rc;
-    HG_REQUIRE(ppo && batch, HGYM_E_BADARG, "null ppo / batch");
-    HG_REQUIRE(ppo->value_loss_unclipped == 0 || ppo->value_loss_unclipped == 1, HGYM_E_BADARG,
-               "HgymPPOConfig.value_loss_unclipped=%d (0: clipped value loss, 1: unclipped)", ppo->value_loss_unclipped);
-    HG_REQUIRE(net->grads && net->opt_state, HGYM_E_BADARG, "null grads / opt_state");
-    HG_REQUIRE(batch->obs && batch->priv && batch->actions && batch->values && batch->advantages && batch->returns && batch->logp &&
-                   batch->mu && batch->sigma && batch->idx, HGYM_E_BADARG, "null batch tensor");
-    HG_DISPATCH(cfg, net, w, stream, grad(*ppo, *batch));
+    return run(cfg, net, stream, [&](auto& R) -> int32_t {
+        int32_t rc = check_ppo(ppo);
+        if (rc) return rc;
+        HG_REQUIRE(net->grads && net->opt_state, HGYM_E_BADARG, "null grads / opt_state");
+        rc = check_batch(R.w, batch);
+        return rc ? rc : R.grad(*ppo, *batch, -1);
+    });
 }
 
 int32_t hgym_ppo_grad_part(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const HgymNet* net, const HgymBatch* batch, int32_t part,
                            void* stream) {
-    WsLayout w;
-    const int32_t rc = check_net(cfg, net, &w);
-    if (rc) return rc;
-    HG_REQUIRE(ppo && batch, HGYM_E_BADARG, "null ppo / batch");
-    HG_REQUIRE(ppo->value_loss_unclipped == 0 || ppo->value_loss_unclipped == 1, HGYM_E_BADARG,
-               "HgymPPOConfig.value_loss_unclipped=%d (0: clipped value loss, 1: unclipped)", ppo->value_loss_unclipped);
-    HG_REQUIRE(part == 0 || part == 1, HGYM_E_BADARG, "part=%d (0 or 1)", part);
-    HG_REQUIRE(net->grads && net->opt_state, HGYM_E_BADARG, "null grads / opt_state");
-    HG_REQUIRE(batch->obs && batch->priv && batch->actions && batch->values && batch->advantages && batch->returns && batch->logp &&
-                   batch->mu && batch->sigma && batch->idx, HGYM_E_BADARG, "null batch tensor");
-    HG_DISPATCH(cfg, net, w, stream, grad(*ppo, *batch, part));
+    return run(cfg, net, stream, [&](auto& R) -> int32_t {
+        int32_t rc = check_ppo(ppo);
+        if (rc) return rc;
+        HG_REQUIRE(part == 0 || part == 1, HGYM_E_BADARG, "part=%d (0 or 1)", part);
+        HG_REQUIRE(net->grads && net->opt_state, HGYM_E_BADARG, "null grads / opt_state");
+        rc = check_batch(R.w, batch);
+        return rc ? rc : R.grad(*ppo, *batch, part);
+    });
 }
 
 int64_t hgym_net_param_offset(const HgymNetConfig* cfg, int32_t which) {
@@ -1552,14 +1545,12 @@ int64_t hgym_net_param_offset(const HgymNetConfig* cfg, int32_t which) {
 }
 
 int32_t hgym_ppo_apply(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const HgymNet* net, void* stream) {
-    WsLayout w;
-    const int32_t rc = check_net(cfg, net, &w);
-    if (rc) return rc;
-    HG_REQUIRE(ppo, HGYM_E_BADARG, "null ppo");
-    HG_REQUIRE(ppo->value_loss_unclipped == 0 || ppo->value_loss_unclipped == 1, HGYM_E_BADARG,
-               "HgymPPOConfig.value_loss_unclipped=%d (0: clipped value loss, 1: unclipped)", ppo->value_loss_unclipped);
-    HG_REQUIRE(net->grads && net->adam_m && net->adam_v && net->opt_state, HGYM_E_BADARG, "null optimiser buffers");
-    HG_DISPATCH(cfg, net, w, stream, apply(*ppo));
+    return run(cfg, net, stream, [&](auto& R) -> int32_t {
+        const int32_t rc = check_ppo(ppo);
+        if (rc) return rc;
+        HG_REQUIRE(net->grads && net->adam_m && net->adam_v && net->opt_state, HGYM_E_BADARG, "null optimiser buffers");
+        return R.apply(*ppo);
+    });
 }
 
 }  // extern "C"

@@ -435,6 +435,34 @@ def test_grad_in_two_parts_is_the_whole_gradient(precision):
     assert torch.equal(net.grads_ext, whole)
 
 
+def test_grad_in_two_parts_with_a_layer_by_layer_aux_head():
+    """A fused bf16 trunk with an auxiliary head too wide for the fused kernels (it takes the layer-by-layer path): part 1 sums that
+    head's split-K slabs with the split counts part 0 wrote them with, and both parts together equal hgym_ppo_grad."""
+    from hgym import NetBuffers, make_net_config, make_ppo_config, make_batch
+    S = B = 777
+    torch.manual_seed(4)
+    cfg = make_net_config(705, 219, 12, [512, 256, 128], [768, 256, 128], "bf16", B, aux_hidden=[512, 768, 768], aux_out=96,
+                          aux_target_offset=219 - 96)
+    net = NetBuffers(cfg, "cuda", learning_rate=1e-3)
+    for k, v in net.views.items():
+        v.copy_(torch.randn(v.shape, device="cuda") * (0.05 if v.dim() > 1 else 0.01))
+    net.views["std"].fill_(0.9)
+    net.sync_shadow()
+    r = lambda *s: torch.randn(*s, device="cuda")
+    cols = (r(S, 705), r(S, 219), r(S, 12), r(S), r(S), r(S), r(S) - 12.0, r(S, 12) * 0.3, torch.ones(S, 12, device="cuda"))
+    idx = torch.randperm(S, device="cuda").contiguous()
+    ppo = make_ppo_config(aux_coef=0.5)
+    net.ppo_grad(ppo, make_batch(*cols, idx))
+    torch.cuda.synchronize()
+    whole = net.grads_ext.clone()
+    assert torch.isfinite(whole).all() and whole[net.bucket_split:].abs().sum() > 0
+    net.grads_ext.fill_(float("nan"))
+    net.ppo_grad_part(ppo, make_batch(*cols, idx), 0)
+    net.ppo_grad_part(ppo, make_batch(*cols, idx), 1)
+    torch.cuda.synchronize()
+    assert torch.equal(net.grads_ext, whole)
+
+
 # ---------------------------------------------------------------------------------------------- full-width reference fixture
 def _full_case():
     import ppo_full_common as F
