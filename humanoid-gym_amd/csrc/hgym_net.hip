@@ -152,10 +152,17 @@ static int32_t ws_layout(const HgymNetConfig* c, WsLayout* w) {
         return o;
     };
     HG_REQUIRE(c->aux_layers >= 0 && c->aux_layers <= HGYM_MAX_LAYERS, HGYM_E_SHAPE, "aux_layers=%d", c->aux_layers);
-    if (c->aux_layers > 0)
-        HG_REQUIRE(c->aux_dims[0] == c->num_obs && c->aux_target_offset >= 0 &&
-                       c->aux_target_offset + c->aux_dims[c->aux_layers] <= c->num_priv && c->actor_layers + c->critic_layers + c->aux_layers <= 16,
-                   HGYM_E_SHAPE, "auxiliary head: input must be num_obs, targets must lie inside the privileged row");
+    if (c->aux_layers > 0) {
+        // (SegTable holds 2 x 16 layer segments + std)
+        HG_REQUIRE(c->actor_layers + c->critic_layers + c->aux_layers <= 16, HGYM_E_SHAPE,
+                   "auxiliary head: %d actor + %d critic + %d auxiliary layers exceed 16 in total", c->actor_layers, c->critic_layers,
+                   c->aux_layers);
+        HG_REQUIRE(c->aux_dims[0] == c->num_obs, HGYM_E_SHAPE, "auxiliary head: input width %d must be num_obs = %d", c->aux_dims[0],
+                   c->num_obs);
+        HG_REQUIRE(c->aux_target_offset >= 0 && c->aux_target_offset + c->aux_dims[c->aux_layers] <= c->num_priv, HGYM_E_SHAPE,
+                   "auxiliary head: targets [%d, %d) must lie inside the privileged row of %d", c->aux_target_offset,
+                   c->aux_target_offset + c->aux_dims[c->aux_layers], c->num_priv);
+    }
     w->nnets = c->aux_layers > 0 ? 3 : 2;
     w->aux_p0 = -1;
     for (int which = 0; which < w->nnets; ++which) {
@@ -168,7 +175,7 @@ static int32_t ws_layout(const HgymNetConfig* c, WsLayout* w) {
             LayerLayout& y = n.layer[l];
             y.K = dims[l];
             y.N = dims[l + 1];
-            HG_REQUIRE(y.K > 0 && y.N > 0, HGYM_E_SHAPE, "non-positive layer dim");
+            HG_REQUIRE(y.K > 0 && y.N > 0, HGYM_E_SHAPE, "%s layer %d: non-positive layer dim %d -> %d", which == 0 ? "actor" : (which == 1 ? "critic" : "auxiliary"), l, y.K, y.N);
             y.Kp = (int)round_up(y.K, w->SE);
             y.Ncp = (int)round_up(y.N, w->SE);
             y.N16 = (int)round_up(y.N, 16);
@@ -248,30 +255,36 @@ __global__ __launch_bounds__(256) void transpose_kernel(int M, int Mp, int C, co
     }
 }
 
-// out[r] += sum_m in[r][m] (bias gradients from dY^T).  grid = (column chunks, rows); every lane issues four
-// independent 16-byte loads, one fp32 atomic per workgroup.  `out` must be zero on entry.
+// Bias gradients from dY^T, in a fixed order: workgroup (x, r) sums in[r][m] over its `per` chunks of 1024 * V columns
+// (V = 16 / sizeof(T)) and stores the sum at out[x * slab_stride + r] -- a split-K slab of the bias segment, summed in
+// ascending x by reduce_slabs_kernel like every other slab.  (Until the slabs carried them, each workgroup added its
+// partial with an fp32 atomic: above one chunk the last bits depended on the arrival order.)  Every lane issues four
+// independent 16-byte loads per chunk.
 template <typename T>
-__global__ __launch_bounds__(256) void rowsum_kernel(int Mp, const T* __restrict__ in, int64_t ld_in, float* __restrict__ out) {
+__global__ __launch_bounds__(256) void rowsum_kernel(int Mp, int per, const T* __restrict__ in, int64_t ld_in, float* __restrict__ out,
+                                                     int64_t slab_stride) {
     constexpr int V = 16 / sizeof(T);
     __shared__ float red[4];
     const T* row = in + (int64_t)blockIdx.y * ld_in;
-    const int base = blockIdx.x * (256 * 4 * V);
     float s = 0.0f;
+    for (int c = 0; c < per; ++c) {
+        const int base = (blockIdx.x * per + c) * (256 * 4 * V);
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const int m = base + (u * 256 + threadIdx.x) * V;
-        if (m < Mp) {   // Mp is a multiple of V and the pad columns are zero
-            const u32x4 raw = *reinterpret_cast<const u32x4*>(row + m);
-            const T* e = reinterpret_cast<const T*>(&raw);
+        for (int u = 0; u < 4; ++u) {
+            const int m = base + (u * 256 + threadIdx.x) * V;
+            if (m < Mp) {   // Mp is a multiple of V and the pad columns are zero
+                const u32x4 raw = *reinterpret_cast<const u32x4*>(row + m);
+                const T* e = reinterpret_cast<const T*>(&raw);
 #pragma unroll
-            for (int k = 0; k < V; ++k) s += to_f32<T>(e[k]);
+                for (int k = 0; k < V; ++k) s += to_f32<T>(e[k]);
+            }
         }
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(&out[blockIdx.y], red[0] + red[1] + red[2] + red[3]);
+    if (threadIdx.x == 0) out[(int64_t)blockIdx.x * slab_stride + blockIdx.y] = red[0] + red[1] + red[2] + red[3];
 }
 
 // Auxiliary head loss: L = coef * mean_b mean_j (y[b][j] - t[b][j])^2 with t = priv[idx[b]][off + j].  Writes
@@ -477,7 +490,7 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(const LossArgs a) {
 // grads_bmu / grads_bv (fused path only): gradients of the two head biases = column sums of the head gradients.
 __global__ __launch_bounds__(512) void ppo_scalars_kernel(const ScalArgs a) { ppo_scalars_block(a, threadIdx.x, blockDim.x); }
 
-// gradient finalise: sum the split-K slabs of every weight matrix into the flat gradient vector
+// gradient finalise: sum the split-K slabs of every weight matrix and bias vector into the flat gradient vector
 struct Segment {
     int64_t off;     // offset in the flat parameter vector
     int rows, cols;  // N, K  (bias / std: rows = count, cols = 1, no shadow)
@@ -723,6 +736,7 @@ int32_t launch_gemm(const GemmArgs& g0, int splits, hipStream_t s) {
     splits = ceil_div(stages, per);
     g.k_chunk = per * SE;
     prof_begin(HGYM_PROF_GEMM, s);
+    // (the tile choice is restated in tests/layer_path_common.py: tile -- keep the two in step)
     const int64_t t128 = (int64_t)ceil_div(g.M, 128) * ceil_div(g.N, 128) * splits;
     if (g.N <= 16) launch_cfg<T, 128, 16, 4, 1>(g, splits, s);
     else if (g.M <= 16) launch_cfg<T, 16, 128, 1, 4>(g, splits, s);
@@ -772,6 +786,7 @@ struct NetBase {
     template <typename U> U* at(int64_t off) const { return reinterpret_cast<U*>(ws + off); }
 
     // split-K slabs of a weight gradient on the layer-by-layer path, for a minibatch whose contraction padding is Mp
+    // (restated in tests/layer_path_common.py: split_count -- keep the two in step)
     int split_count(const LayerLayout& y, int Mp) const {
         // enough workgroups to fill 256 CUs: tiles(N x K) x splits ~ 512
         const int tiles = ceil_div(y.N, y.N <= 16 ? 16 : 128) * ceil_div(y.K, 128);
@@ -782,6 +797,15 @@ struct NetBase {
         if (sp < 1) sp = 1;
         const int per = ceil_div(stages, sp);
         return ceil_div(stages, per);
+    }
+
+    // rowsum_kernel's workgroups per bias row (= its slabs) for a minibatch of contraction padding Mp, and the chunks each one sums
+    // (restated in tests/layer_path_common.py: rowsum_splits)
+    int rowsum_splits(int Mp, int* per_out = nullptr) const {
+        const int chunks = ceil_div(Mp, 1024 * 16 / w.es);
+        const int per = ceil_div(chunks, std::min(chunks, w.splits));
+        if (per_out) *per_out = per;
+        return ceil_div(chunks, per);
     }
 
     // Mp > 0: with the slab counts of a gradient over a minibatch of contraction padding Mp; Mp = 0: without (Adam, shadow refresh)
@@ -817,9 +841,10 @@ struct NetBase {
                 b.off = y.b_off;
                 b.rows = y.N;
                 b.cols = 1;
-                // bias gradients that come from the slabs: hidden layers (the dW kernel's column sums of dZ); the actor / critic
-                // head biases are written by ppo_scalars_kernel, the auxiliary head's is a column sum like the others
+                // bias gradients that come from the slabs: on the fused layout the hidden layers' (the dW kernel's column sums of dZ;
+                // the actor / critic head biases are written by ppo_scalars_kernel, the auxiliary head's is a column sum like the others)
                 if (n.fused && Mp && (l < n.L - 1 || which == 2)) b.splits = w.dw_splits;
+                if (!n.fused && Mp) b.splits = rowsum_splits(Mp);     // every bias of a layer-by-layer net: rowsum_kernel's slabs
             }
         }
         return t;
@@ -927,8 +952,10 @@ struct GemmPath : NetBase {
                 const int32_t got = launch_gemm<T>(g, want, s);
                 if (got < 0) return got;
                 HG_REQUIRE(got == want, HGYM_E_LAUNCH, "split-K mismatch %d vs %d", got, want);
-                hipLaunchKernelGGL((rowsum_kernel<T>), dim3(ceil_div(Mp, 256 * 4 * (16 / (int)sizeof(T))), y.N), dim3(256), 0, s, Mp,
-                                   at<T>(y.dYT), w.Mp, net.grads + y.b_off);
+                int per = 0;
+                const int rs = rowsum_splits(Mp, &per);
+                hipLaunchKernelGGL((rowsum_kernel<T>), dim3(rs, y.N), dim3(256), 0, s, Mp, per, at<T>(y.dYT), w.Mp,
+                                   at<float>(w.slabs) + y.b_off, w.Ps);
                 HG_CHECK_LAUNCH("rowsum_kernel");
             }
             if (l > 0) {   // dX = (dY * W) .* f'(z), from X_l = f(z)  -> dY of layer l-1
@@ -960,15 +987,13 @@ struct GemmPath : NetBase {
     }
 
     // Auxiliary (denoising) head, HgymNetConfig::aux_*: forward on the gathered observation rows, MSE against the target
-    // columns of the gathered privileged rows, backward.  Leaves its weight gradients in the split-K slabs and its bias
-    // gradients in net.grads; the caller's slab reduction finishes them together with everything else.
+    // columns of the gathered privileged rows, backward.  Leaves its weight and bias gradients in the split-K slabs; the
+    // caller's slab reduction finishes them together with everything else.
     int32_t aux_grad(const HgymPPOConfig& ppo, const HgymBatch& b) {
         const NetLayout& n = w.net[2];
         const LayerLayout& last = n.layer[n.L - 1];
         const int B = b.B, No = last.N;
         float* y = at<float>(n.out_f32);
-        if (hipMemsetAsync(net.grads + w.aux_p0, 0, (size_t)(w.P - w.aux_p0) * sizeof(float), s) != hipSuccess)
-            HG_FAIL(HGYM_E_LAUNCH, "memset of the auxiliary gradients failed");
         int32_t rc = forward(2, B, b.obs, cfg.num_obs, b.idx, y, No, true);
         if (rc) return rc;
         const int Bp = (int)round_up(B, w.SE);
@@ -986,7 +1011,7 @@ struct GemmPath : NetBase {
         const int B = b.B, A = cfg.num_actions;
         float* mu = at<float>(w.net[0].out_f32);
         float* val = at<float>(w.net[1].out_f32);
-        if (hipMemsetAsync(net.grads, 0, (size_t)w.P * sizeof(float), s) != hipSuccess) HG_FAIL(HGYM_E_LAUNCH, "memset of grads failed");
+        // (no zeroing of net.grads: ppo_scalars_kernel writes std's gradient, reduce_slabs_kernel every weight and bias segment)
         int32_t rc = forward(0, B, b.obs, cfg.num_obs, b.idx, mu, A, true);
         if (rc) return rc;
         rc = forward(1, B, b.priv, cfg.num_priv, b.idx, val, 1, true);
@@ -1055,10 +1080,10 @@ struct GemmPath : NetBase {
         return HGYM_OK;
     }
 
-    // the critic over M rows in pieces of at most max_batch (a multiple of 64 rows each)
+    // the critic over M rows in pieces of at most max_batch (a multiple of 64 rows each when max_batch is at least 64)
     int32_t critic_values(int64_t M, const float* priv, float* values, const HgymObsShadow* sh) {
         HG_REQUIRE(!sh || !sh->priv, HGYM_E_UNSUPPORTED, "the observation shadow exists on the fused bf16 path only");
-        const int64_t piece = std::max<int64_t>(64, w.maxM / 64 * 64);
+        const int64_t piece = w.maxM < 64 ? w.maxM : w.maxM / 64 * 64;
         for (int64_t m0 = 0; m0 < M; m0 += piece) {
             const int32_t rc = forward(1, (int)std::min<int64_t>(piece, M - m0), priv + m0 * cfg.num_priv, cfg.num_priv, nullptr, values + m0, 1,
                                        false);
@@ -1350,10 +1375,10 @@ struct FusedPath : NetBase {
         return forward_nets(0, 2, M, io, nullptr, false, &smp, fin, sh);
     }
 
-    // the critic over M rows in pieces of at most max_batch (a multiple of 64 rows each: whole tiles), the shadow's priv rows written by
-    // the tiles that read them
+    // the critic over M rows in pieces of at most max_batch (a multiple of 64 rows each: whole tiles; max_batch itself below 64), the
+    // shadow's priv rows written by the tiles that read them
     int32_t critic_values(int64_t M, const float* priv, float* values, const HgymObsShadow* sh) {
-        const int64_t piece = std::max<int64_t>(64, w.maxM / 64 * 64);
+        const int64_t piece = w.maxM < 64 ? w.maxM : w.maxM / 64 * 64;
         for (int64_t m0 = 0; m0 < M; m0 += piece) {
             const NetIO io[3] = {{}, {priv + m0 * cfg.num_priv, cfg.num_priv, values + m0, 1}, {}};
             HgymObsShadow s1 = {nullptr, 0, nullptr, 0};

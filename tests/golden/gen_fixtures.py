@@ -478,16 +478,19 @@ def gen_env_reset_trace(R, N=16, S0=3, seed=15, name="env_reset_trace.npz"):
 
 
 # ------------------------------------------------------------------------------------------------
-def gen_ppo_update(R, N=24, T=8, seed=3):
-    """Drive the reference PPO through one full iteration on a small actor/critic (same 705/219/12 interface)."""
+def gen_ppo_update(R, N=24, T=8, seed=3, num_obs=705, num_priv=219, num_actions=12, actor_hidden=(48, 32, 16), critic_hidden=(40, 32, 16),
+                   name="ppo_update.npz"):
+    """Drive the reference PPO through one full iteration on a small actor/critic (by default the same 705/219/12 interface;
+    gen_arch_fixture.py records another architecture with the same draws)."""
     torch.manual_seed(seed)
     g = torch.Generator().manual_seed(seed)
-    ah, ch = [48, 32, 16], [40, 32, 16]
-    ac = R.ActorCritic(705, 219, 12, actor_hidden_dims=ah, critic_hidden_dims=ch, init_noise_std=1.0)
+    ah, ch = list(actor_hidden), list(critic_hidden)
+    no, npv, A = num_obs, num_priv, num_actions
+    ac = R.ActorCritic(no, npv, A, actor_hidden_dims=ah, critic_hidden_dims=ch, init_noise_std=1.0)
     alg = R.PPO(ac, num_learning_epochs=2, num_mini_batches=4, clip_param=0.2, gamma=0.994, lam=0.9,
                 value_loss_coef=1.0, entropy_coef=0.001, learning_rate=1e-3, max_grad_norm=1.0,
                 use_clipped_value_loss=True, schedule="adaptive", desired_kl=0.01, device="cpu")
-    alg.init_storage(N, T, [705], [219], [12])
+    alg.init_storage(N, T, [no], [npv], [A])
     out = {("p0_" + k.replace(".", "_")): npy(v) for k, v in ac.state_dict().items()}
     out["actor_hidden"] = np.array(ah)
     out["critic_hidden"] = np.array(ch)
@@ -495,9 +498,9 @@ def gen_ppo_update(R, N=24, T=8, seed=3):
     act_l, val_l, logp_l, mu_l, sig_l = [], [], [], [], []
     _orig_normal = torch.normal
     for t in range(T):
-        obs = (torch.randn(N, 705, generator=g) * 1.2).clamp(-18, 18)
-        priv = (torch.randn(N, 219, generator=g) * 1.2).clamp(-18, 18)
-        z = torch.randn(N, 12, generator=g)
+        obs = (torch.randn(N, no, generator=g) * 1.2).clamp(-18, 18)
+        priv = (torch.randn(N, npv, generator=g) * 1.2).clamp(-18, 18)
+        z = torch.randn(N, A, generator=g)
         # Normal.sample() = torch.normal(loc.expand, scale.expand); substitute the recorded standard draw
         torch.normal = lambda mean, std, **k: mean + std * z
         try:
@@ -514,7 +517,7 @@ def gen_ppo_update(R, N=24, T=8, seed=3):
             alg.process_env_step(rew, done, {"time_outs": tout})
         obs_l.append(npy(obs)); priv_l.append(npy(priv)); z_l.append(npy(z)); rew_l.append(npy(rew))
         done_l.append(npy(done)); to_l.append(npy(tout))
-    last_priv = (torch.randn(N, 219, generator=g) * 1.2).clamp(-18, 18)
+    last_priv = (torch.randn(N, npv, generator=g) * 1.2).clamp(-18, 18)
     with torch.inference_mode():
         alg.compute_returns(last_priv)
     st = alg.storage
@@ -557,8 +560,8 @@ def gen_ppo_update(R, N=24, T=8, seed=3):
     out["final_lr"] = np.array(alg.learning_rate)
     for k, v in ac.state_dict().items():
         out["pF_" + k.replace(".", "_")] = npy(v)
-    np.savez_compressed(os.path.join(HERE, "ppo_update.npz"), **out)
-    print("ppo_update.npz lrs", lrs, "losses", mvl, msl)
+    np.savez_compressed(os.path.join(HERE, name), **out)
+    print(name, "lrs", lrs, "losses", mvl, msl)
 
 
 def gen_ppo_update_full(R):

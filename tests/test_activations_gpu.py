@@ -10,9 +10,9 @@ import numpy as np
 import pytest
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
 import bf16_report as BR
+import layer_path_common as LP
 from oracle import ppo_oracle as P
 
 pytestmark = pytest.mark.gpu
@@ -42,60 +42,9 @@ SHAPES = {
 }
 
 
-def _fns(m):
-    """(f(z), f'(z) from y = f(z)) in float64 for the module m."""
-    if isinstance(m, nn.SELU):
-        a, s = 1.6732632423543772, 1.0507009873554805
-    elif isinstance(m, nn.ELU):
-        a, s = float(m.alpha), 1.0
-    else:
-        a = s = None
-    if a is not None:
-        return (lambda z: s * torch.where(z > 0, z, a * (torch.exp(z) - 1.0)),
-                lambda y: torch.where(y > 0, torch.full_like(y, s), y + s * a))
-    if isinstance(m, (nn.ReLU, nn.LeakyReLU)):
-        sl = 0.0 if isinstance(m, nn.ReLU) else float(m.negative_slope)
-        return (lambda z: torch.where(z > 0, z, sl * z), lambda y: torch.where(y > 0, torch.ones_like(y), torch.full_like(y, sl)))
-    if isinstance(m, nn.Tanh):
-        return torch.tanh, lambda y: 1.0 - y * y
-    return torch.sigmoid, lambda y: y * (1.0 - y)
-
-
 def _restated(m):
-    """mlp_forward / mlp_backward of oracle/ppo_oracle.py with the activation m in place of ELU(1)."""
-    f, df = _fns(m)
-
-    def mlp_forward(x, layers, keep=False, quant=None):
-        q = quant if quant is not None else (lambda t: t)
-        h = q(x)
-        acts, pres = [h], []
-        for i, (W, b) in enumerate(layers):
-            z = F.linear(h, q(W), b)
-            if i < len(layers) - 1:
-                pres.append(z)
-                h = q(f(z))
-                acts.append(h)
-            else:
-                h = z
-        return (h, acts, pres) if keep else h
-
-    def mlp_backward(dy, layers, acts, pres, quant=None):
-        q = quant
-        grads = [None] * len(layers)
-        g = dy
-        for i in reversed(range(len(layers))):
-            W, _ = layers[i]
-            if q is None:
-                grads[i] = (g.t() @ acts[i], g.sum(dim=0))
-            else:
-                gb = g.sum(dim=0) if i == len(layers) - 1 else None
-                g = q(g)
-                grads[i] = (g.t() @ acts[i], gb if gb is not None else g.sum(dim=0))
-            if i > 0:
-                g = (g @ (W if q is None else q(W))) * df(acts[i])
-        return grads
-
-    return mlp_forward, mlp_backward
+    """mlp_forward / mlp_backward of oracle/ppo_oracle.py with the activation m in place of ELU(1) (tests/layer_path_common.py)."""
+    return LP.restated(m)
 
 
 def _q64(t):

@@ -19,9 +19,9 @@ NAMES = ["std"] + ["actor.%d.%s" % (i, k) for i in (0, 2, 4, 6) for k in ("weigh
         ["critic.%d.%s" % (i, k) for i in (0, 2, 4, 6) for k in ("weight", "bias")]
 
 
-def _net(num_obs, num_priv, ah, ch, precision, max_batch, lr=1e-3):
+def _net(num_obs, num_priv, ah, ch, precision, max_batch, lr=1e-3, num_actions=12):
     from hgym import NetBuffers, make_net_config
-    cfg = make_net_config(num_obs, num_priv, 12, ah, ch, precision, max_batch)
+    cfg = make_net_config(num_obs, num_priv, num_actions, ah, ch, precision, max_batch)
     return NetBuffers(cfg, "cuda", learning_rate=lr)
 
 
@@ -120,16 +120,18 @@ def test_policy_act_vs_oracle():
 
 
 def _run_iteration(G, precision):
-    """Replays tests/golden/ppo_update.npz (recorded from the reference's PPO) through the HIP path."""
+    """Replays tests/golden/ppo_update.npz (or another recording of gen_fixtures.gen_ppo_update: ppo_update_arch.npz) from the reference's
+    PPO through the HIP path."""
     from hgym import make_ppo_config, make_batch, _lib as L
     import ctypes as C
     Tn, N = G["obs"].shape[:2]
+    A = G["z"].shape[-1]
     ah, ch = [int(x) for x in G["actor_hidden"]], [int(x) for x in G["critic_hidden"]]
-    net = _net(705, 219, ah, ch, precision, Tn * N, lr=1e-3)
-    net.load_state_dict({k: T(G["p0_" + k.replace(".", "_")]) for k in NAMES})
+    net = _net(G["obs"].shape[-1], G["priv"].shape[-1], ah, ch, precision, Tn * N, lr=1e-3, num_actions=A)
+    net.load_state_dict({k: T(G["p0_" + k.replace(".", "_")]) for k in net.views})
     dev = "cuda"
     st = dict(obs=T(G["obs"]).to(dev).contiguous(), priv=T(G["priv"]).to(dev).contiguous())
-    for k, shape in (("actions", (Tn, N, 12)), ("mu", (Tn, N, 12)), ("sigma", (Tn, N, 12)), ("values", (Tn, N, 1)),
+    for k, shape in (("actions", (Tn, N, A)), ("mu", (Tn, N, A)), ("sigma", (Tn, N, A)), ("values", (Tn, N, 1)),
                      ("logp", (Tn, N)), ("rewards", (Tn, N)), ("returns", (Tn, N)), ("advantages", (Tn, N))):
         st[k] = torch.zeros(*shape, device=dev)
     dones = T(G["done"]).to(dev).to(torch.uint8).contiguous()
@@ -171,8 +173,20 @@ def _run_iteration(G, precision):
 
 
 def test_ppo_iteration_matches_reference_f32(golden_dir):
-    G = np.load(os.path.join(golden_dir, "ppo_update.npz"))
+    _check_iteration_f32(np.load(os.path.join(golden_dir, "ppo_update.npz")))
+
+
+def test_ppo_iteration_at_an_odd_architecture_matches_reference_f32(golden_dir):
+    """tests/golden/ppo_update_arch.npz (gen_arch_fixture.py): actor [37, 5], critic [100, 17, 65, 3], 141 / 73 observations, 5 actions --
+    the layer-by-layer path at 3 + 5 layers, ragged widths and a 5-wide head, against the reference's own iteration, at the bars above."""
+    G = np.load(os.path.join(golden_dir, "ppo_update_arch.npz"))
+    assert G["z"].shape[-1] == 5 and list(G["critic_hidden"]) == [100, 17, 65, 3]
+    _check_iteration_f32(G)
+
+
+def _check_iteration_f32(G):
     r = _run_iteration(G, "f32")
+    names = list(r["net"].views)
     st = r["st"]
     for k, ref, tol in (("actions", G["actions"], 1e-5), ("values", G["values"], 1e-5), ("mu", G["mu"], 1e-5),
                         ("rewards", G["st_rewards"].squeeze(-1), 1e-5), ("returns", G["st_returns"].squeeze(-1), 1e-5),
@@ -182,11 +196,11 @@ def test_ppo_iteration_matches_reference_f32(golden_dir):
     # every adaptive-KL learning-rate decision identical to the reference's
     np.testing.assert_allclose(r["lrs"], G["lrs"], rtol=1e-12)
     # clipped gradients of the first minibatch vs the reference's autograd
-    for k in NAMES:
+    for k in names:
         ref = G["g0_" + k.replace(".", "_")]
         assert _rel_err(r["g0"][k].numpy(), ref) <= 5e-5, (k, _rel_err(r["g0"][k].numpy(), ref))
     # parameters after the 8 Adam steps
-    for k in NAMES:
+    for k in names:
         ref = G["pF_" + k.replace(".", "_")]
         np.testing.assert_allclose(r["net"].views[k].cpu().numpy(), ref, rtol=2e-4, atol=5e-6, err_msg=k)
     opt = r["opt"]

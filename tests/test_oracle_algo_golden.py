@@ -54,8 +54,9 @@ def test_policy_example_known_answers(golden_dir):
 
 def _storage(G, p):
     Tn, N = G["obs"].shape[:2]
-    st = dict(obs=T(G["obs"]), priv=T(G["priv"]), actions=torch.zeros(Tn, N, 12), values=torch.zeros(Tn, N, 1),
-              logp=torch.zeros(Tn, N, 1), mu=torch.zeros(Tn, N, 12), sigma=torch.zeros(Tn, N, 12),
+    A = G["z"].shape[-1]
+    st = dict(obs=T(G["obs"]), priv=T(G["priv"]), actions=torch.zeros(Tn, N, A), values=torch.zeros(Tn, N, 1),
+              logp=torch.zeros(Tn, N, 1), mu=torch.zeros(Tn, N, A), sigma=torch.zeros(Tn, N, A),
               rewards=torch.zeros(Tn, N, 1))
     for t in range(Tn):
         a, v, lp, mu, sg = P.policy_act(p, st["obs"][t], st["priv"][t], T(G["z"][t]))
@@ -70,9 +71,32 @@ def _storage(G, p):
     return st
 
 
+def _layer_names(G, net):
+    """actor_0 / actor_2 / ... of the recorded state dict, however many layers the net has."""
+    return ["%s_%d" % (net, i) for i in sorted(int(k.split("_")[2]) for k in G.files if k.startswith("p0_%s_" % net) and k.endswith("_weight"))]
+
+
+def _params(G, prefix):
+    """P.Params of a recorded state dict at any depth (P.Params.from_npz reads XBot-L's four layers)."""
+    mlp = lambda net: [(T(G["%s%s_weight" % (prefix, n)]).clone(), T(G["%s%s_bias" % (prefix, n)]).clone()) for n in _layer_names(G, net)]
+    return P.Params(mlp("actor"), mlp("critic"), T(G["%sstd" % prefix]).clone())
+
+
 def test_ppo_iteration_matches_reference(golden_dir):
-    G = np.load(os.path.join(golden_dir, "ppo_update.npz"))
-    p = P.Params.from_npz(G, "p0_")
+    _check_iteration(np.load(os.path.join(golden_dir, "ppo_update.npz")))
+
+
+def test_ppo_iteration_at_an_odd_architecture_matches_reference(golden_dir):
+    """tests/golden/ppo_update_arch.npz (gen_arch_fixture.py): the same iteration with actor [37, 5], critic [100, 17, 65, 3], 141 / 73
+    observations and 5 actions -- layer counts and widths the oracle's MLP must not assume."""
+    G = np.load(os.path.join(golden_dir, "ppo_update_arch.npz"))
+    assert len(_layer_names(G, "actor")) == 3 and len(_layer_names(G, "critic")) == 5 and G["z"].shape[-1] == 5
+    assert G["obs"].shape[-1] == 141 and G["priv"].shape[-1] == 73
+    _check_iteration(G)
+
+
+def _check_iteration(G):
+    p = _params(G, "p0_")
     st = _storage(G, p)
     last_v = P.mlp_forward(T(G["last_priv"]), p.critic).squeeze(-1)
     ret, adv = P.gae_returns(st["rewards"].squeeze(-1), st["values"].squeeze(-1), T(G["done"]), last_v, 0.994, 0.9)
@@ -88,8 +112,7 @@ def test_ppo_iteration_matches_reference(golden_dir):
     assert abs(lr - float(G["final_lr"])) < 1e-15
     # clipped gradients of the first minibatch vs autograd
     g0 = trace[0]["grads"]
-    names = ["std"] + ["actor_%d_%s" % (i, k) for i in (0, 2, 4, 6) for k in ("weight", "bias")] + \
-            ["critic_%d_%s" % (i, k) for i in (0, 2, 4, 6) for k in ("weight", "bias")]
+    names = ["std"] + ["%s_%s" % (n, k) for net in ("actor", "critic") for n in _layer_names(G, net) for k in ("weight", "bias")]
     for nme, g in zip(names, g0.tensors()):
         ref = G["g0_" + nme]
         scale = max(np.abs(ref).max(), 1e-8)
