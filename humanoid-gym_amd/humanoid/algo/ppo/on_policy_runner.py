@@ -1,9 +1,8 @@
 """OnPolicyRunner with the reference's interface (algo/ppo/on_policy_runner.py:45-307): rollout / learn loop,
 checkpoint save / load (same dict keys), inference-policy getters, console + optional TensorBoard logging.
 
-The rollout loop issues, per vec-step, one policy launch group, one fused env launch and one store launch; the
-env writes its observations straight into the next rollout-storage slot.  Episode book-keeping stays on the
-device and is read back once per iteration (the reference syncs the host every step, :146-152)."""
+The env writes its observations straight into the rollout-storage slots, and episode book-keeping stays on the device,
+read back once per iteration (the reference syncs the host every step, :146-152)."""
 import atexit
 import os
 import sys
@@ -12,7 +11,9 @@ import statistics
 import threading
 import time
 from collections import deque
+from dataclasses import dataclass
 from datetime import datetime
+from typing import Optional
 
 import torch
 
@@ -78,6 +79,79 @@ _WRITER = _CheckpointWriter()
 atexit.register(lambda: _WRITER.q.join())
 
 
+@dataclass(frozen=True)
+class _LoopPlan:
+    """How one learn() call runs its iterations (_plan_loop)."""
+    zero_copy: bool         # the env writes its observations straight into the rollout storage slots (bind_outputs)
+    graph: bool             # the rollout is captured into a HIP graph and replayed (HGYM_GRAPH)
+    env_sink: bool          # the env's step finaliser also stores the transition's scalar columns (bind_transition, HGYM_ENV_SINK)
+    log_sink: bool          # ... and keeps the logging book-keeping on the device, read once per iteration (bind_log_sink, HGYM_LOG_SINK)
+    defer_fin: bool         # ... and rides in the next policy launch: nothing on the host reads the per-step extras (HGYM_DEFER_FIN)
+    fuse: Optional[str]     # one launch per vec-step (HGYM_FUSE_ROLLOUT): None, "inline" or "deferred" (the critic after the rollout)
+    async_mode: Optional[str]   # nothing read back inside an iteration (HGYM_ASYNC): None, "events" (no logging) or "log" (log sink)
+    graph_update: bool      # compute_returns() + update() as a second HIP graph, behind async_mode only (HGYM_GRAPH_UPDATE)
+
+
+def _plan_loop(env, alg, device, log_on):
+    """The loop plan from the native extensions of env and alg and the HGYM_* knobs; no side effects.  Without them: the plain path."""
+    knob = lambda name: os.environ.get(name, "1") != "0"
+    cuda = str(device).startswith("cuda")
+    st = alg.storage
+    zero_copy = bool(getattr(st, "_obs_all", None) is not None and getattr(st, "_priv_all", None) is not None
+                     and hasattr(env, "bind_outputs") and env.get_privileged_observations() is not None)
+    graph = bool(zero_copy and cuda and knob("HGYM_GRAPH") and hasattr(torch.cuda, "CUDAGraph"))
+    env_sink = bool(zero_copy and hasattr(env, "bind_transition") and hasattr(alg, "transition_sink")
+                    and getattr(env.cfg.env, "send_timeouts", False) and knob("HGYM_ENV_SINK"))
+    log_sink = bool(log_on and env_sink and hasattr(env, "bind_log_sink") and knob("HGYM_LOG_SINK") and env.log_sink_supported())
+    defer_fin = bool(env_sink and not (log_on and not log_sink) and hasattr(env, "take_pending_finalize") and isinstance(alg, PPO)
+                     and knob("HGYM_DEFER_FIN"))
+    fuse = (env.rollout_fused_mode(alg.net) if (defer_fin and hasattr(env, "rollout_fused_mode") and hasattr(alg, "fused_rollout_step")
+                                                and knob("HGYM_FUSE_ROLLOUT")) else None)
+    fuse = "inline" if (fuse == "deferred" and not hasattr(alg, "deferred_values")) else fuse
+    async_ok = cuda and isinstance(alg, PPO) and knob("HGYM_ASYNC")
+    async_mode = "events" if (not log_on and async_ok) else "log" if (log_sink and async_ok) else None
+    graph_update = bool(graph and async_mode is not None and hasattr(alg, "update_capturable") and alg.update_capturable()
+                        and knob("HGYM_GRAPH_UPDATE"))
+    return _LoopPlan(zero_copy, graph, env_sink, log_sink, defer_fin, fuse, async_mode, graph_update)
+
+
+class _CapturedGraph:
+    """Launches learn() repeats every iteration, as one HIP graph.  run(): the first call runs eager() (and marks warm), the next captures
+    capture() and replays it once, later ones with the same key replay and call after_replay(held), held = what capture() returned."""
+
+    def __init__(self):
+        self.graph, self.key, self.held, self.warm = None, None, None, False
+
+    def valid(self, key):
+        return self.graph is not None and self.key == key
+
+    def run(self, on, key, eager, capture, after_replay):
+        if on and self.valid(key):
+            self.graph.replay()
+            after_replay(self.held)
+            return self.held
+        if not (on and self.warm):
+            out, self.warm = eager(), True
+            return out
+        graph = torch.cuda.CUDAGraph()
+        torch.cuda.synchronize()
+        # thread-local capture mode: with torch.distributed initialised, the RCCL watchdog thread polls events concurrently.  Inference
+        # mode: capture_begin updates the generator's graph-state tensors in place, and the first capture created them as inference tensors
+        with torch.inference_mode(), torch.cuda.graph(graph, capture_error_mode="thread_local"):
+            held = capture()
+        self.graph, self.key, self.held = graph, key, held
+        graph.replay()
+        return held
+
+
+class _EpisodeLog:
+    """Host logging book-keeping (on: no log sink): per-step extras["episode"], running return / length, finished-episode sums."""
+
+    def __init__(self, on, tensors):
+        self.on, self.ep_infos = on, []
+        self.reward_sum, self.length, self.done = tensors
+
+
 class OnPolicyRunner:
     def __init__(self, env: VecEnv, train_cfg, log_dir=None, device="cpu"):
         self.cfg = train_cfg["runner"]
@@ -103,18 +177,90 @@ class OnPolicyRunner:
         self.tot_time = 0
         self.current_learning_iteration = 0
         self.last_collection_time = self.last_learn_time = 0.0
-        self._graph = None           # captured rollout (HIP graph) and the tensors it owns
-        self._graph_warm = False
-        self._update_graph = None    # captured compute_returns() + update() (second HIP graph)
-        self._update_warm = False
+        self._rollout_capture = _CapturedGraph()     # the rollout as a HIP graph, and the tensors it owns
+        self._update_capture = _CapturedGraph()      # compute_returns() + update() as a second HIP graph
         _, _ = self.env.reset()
 
-    # ------------------------------------------------------------------
-    def _rollout_slots(self):
-        st = self.alg.storage
-        return getattr(st, "_obs_all", None), getattr(st, "_priv_all", None)
+    _graph = property(lambda self: self._rollout_capture.graph)
+    _update_graph = property(lambda self: self._update_capture.graph)
 
+    # ------------------------------------------------------------------
     def learn(self, num_learning_iterations, init_at_random_ep_len=False):
+        self._open_writer()
+        if init_at_random_ep_len:
+            self.env.episode_length_buf = torch.randint_like(self.env.episode_length_buf, high=int(self.env.max_episode_length))
+        env, alg, log_on = self.env, self.alg, self.log_dir is not None
+        plan = _plan_loop(env, alg, self.device, log_on)
+        obs, privileged_obs = env.get_observations(), env.get_privileged_observations()
+        obs, critic_obs = obs.to(self.device), (privileged_obs if privileged_obs is not None else obs).to(self.device)
+        obs_all, priv_all = getattr(alg.storage, "_obs_all", None), getattr(alg.storage, "_priv_all", None)
+        if plan.zero_copy:
+            obs_all[0].copy_(obs)
+            priv_all[0].copy_(critic_obs)
+            obs, critic_obs = obs_all[0], priv_all[0]
+        alg.actor_critic.train()
+        log = _EpisodeLog(log_on and not plan.log_sink, [torch.zeros(n, device=self.device) for n in (env.num_envs, env.num_envs, 3)])
+        rings = (deque(maxlen=100), deque(maxlen=100))          # the reference's rewbuffer / lenbuffer
+        if plan.env_sink:
+            alg.env_stores_transitions = True
+        if plan.log_sink:
+            env.bind_log_sink(True)
+        # the captured launches hold HgymEnvConfig and the sink's gamma BY VALUE: a change between learn() calls (what a curriculum
+        # script does) must re-capture, as the eager reference would simply see it
+        gkey = (id(env), id(alg.storage), log_on, plan.log_sink, plan.env_sink, plan.defer_fin, plan.fuse, getattr(alg, "gamma", None),
+                env.rollout_graph_key() if hasattr(env, "rollout_graph_key") else None, getattr(alg.storage, "_obs_bf16", None) is not None)
+        ukey = (gkey, alg.update_graph_key(), plan.fuse == "deferred") if plan.graph_update else None
+        if not plan.graph_update:
+            self._update_capture.graph = None
+        pending, marks = None, []
+        try:
+            for it in range(self.current_learning_iteration, self.current_learning_iteration + num_learning_iterations):
+                start = time.time()
+                if plan.async_mode:
+                    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+                    ev[0].record()
+                with torch.inference_mode():
+                    obs, critic_obs, log = self._collect(plan, gkey, obs, critic_obs, log)
+                    if plan.async_mode:
+                        ev[1].record()
+                    elif str(self.device).startswith("cuda"):
+                        torch.cuda.synchronize()
+                stop = time.time()
+                collection_time, start = stop - start, stop
+                mean_value_loss, mean_surrogate_loss = self._learn_step(plan, gkey, ukey, critic_obs)
+                if plan.zero_copy:                  # storage.clear() rotated slot T into slot 0
+                    obs, critic_obs = obs_all[0], priv_all[0]
+                if it % self.save_interval == 0:
+                    self._check_replicas("iteration %d" % it)       # (data-parallel runs only; collective: every rank, same iteration)
+                learn_time = time.time() - start
+                if plan.async_mode:
+                    ev[2].record()
+                if plan.async_mode == "events":
+                    marks.append(ev)
+                elif plan.async_mode == "log":
+                    pending = self._finish_async_log(it, ev, pending, num_learning_iterations)
+                else:
+                    self._finish_sync(plan, log, rings, dict(it=it, num_learning_iterations=num_learning_iterations,
+                                                             collection_time=collection_time, learn_time=learn_time,
+                                                             mean_value_loss=mean_value_loss, mean_surrogate_loss=mean_surrogate_loss))
+                if log_on and it % self.save_interval == 0:
+                    self.save(os.path.join(self.log_dir, "model_{}.pt".format(it)), wait=False)
+        finally:
+            # also on an exception inside the loop: the last finished iteration's log block is printed, the env's bindings released
+            if pending is not None:
+                try:
+                    self._log_flush(pending, num_learning_iterations)
+                except Exception:      # the device may be the thing that failed
+                    pass
+            self._unbind(plan)
+        if marks:
+            self._read_event_times(marks)
+        self.current_learning_iteration += num_learning_iterations
+        self._check_replicas("end of learn() at iteration %d" % self.current_learning_iteration)
+        if log_on:      # (the background writer finishes the file; wait_for_saves() / load() / interpreter exit wait for it: save())
+            self.save(os.path.join(self.log_dir, "model_{}.pt".format(self.current_learning_iteration)), wait=False)
+
+    def _open_writer(self):
         if self.log_dir is not None and self.writer is None:
             if wandb is not None and hasattr(wandb, "init"):
                 try:
@@ -124,274 +270,121 @@ class OnPolicyRunner:
             if SummaryWriter is not None:
                 self.writer = SummaryWriter(log_dir=self.log_dir, flush_secs=10)
             os.makedirs(self.log_dir, exist_ok=True)
-        if init_at_random_ep_len:
-            self.env.episode_length_buf = torch.randint_like(self.env.episode_length_buf, high=int(self.env.max_episode_length))
-        env, alg = self.env, self.alg
-        obs = env.get_observations()
-        privileged_obs = env.get_privileged_observations()
-        critic_obs = privileged_obs if privileged_obs is not None else obs
-        obs, critic_obs = obs.to(self.device), critic_obs.to(self.device)
-        obs_all, priv_all = self._rollout_slots()
-        zero_copy = obs_all is not None and priv_all is not None and hasattr(env, "bind_outputs") and privileged_obs is not None
-        if zero_copy:
-            obs_all[0].copy_(obs)
-            priv_all[0].copy_(critic_obs)
-            obs, critic_obs = obs_all[0], priv_all[0]
-        alg.actor_critic.train()
 
-        ep_infos = []
-        rewbuffer, lenbuffer = deque(maxlen=100), deque(maxlen=100)
-        N = env.num_envs
-        cur_reward_sum = torch.zeros(N, dtype=torch.float, device=self.device)
-        cur_episode_length = torch.zeros(N, dtype=torch.float, device=self.device)
-        done_stats = torch.zeros(3, dtype=torch.float, device=self.device)     # sum of returns, sum of lengths, episodes
+    def _unbind(self, plan):
+        if plan.zero_copy:
+            self.env.bind_outputs(None, None)
+        if plan.env_sink:
+            self.env.bind_transition(None)
+            self.alg.env_stores_transitions = False
+        if plan.log_sink:
+            self.env.bind_log_sink(False)
 
-        # One rollout = num_steps_per_env x {act, env.step, process_env_step}: a few hundred small launches whose host
-        # side (Python + ctypes) costs more than the kernels.  Every buffer the step touches has a fixed address (the env
-        # writes into the storage slots, all counters live on the device), so after one eager warm-up iteration the whole
-        # rollout is captured into a HIP graph and replayed with a single launch per iteration (HGYM_GRAPH=0 disables).
-        use_graph = (zero_copy and str(self.device).startswith("cuda") and os.environ.get("HGYM_GRAPH", "1") != "0"
-                     and hasattr(torch.cuda, "CUDAGraph"))
-        log_on = self.log_dir is not None
+    def _collect(self, plan, gkey, obs, critic_obs, log):
+        """One rollout -> (obs, critic_obs, log) after its last step.  Its few hundred launches touch fixed addresses only (storage slots,
+        device-side counters): after one eager iteration they are captured into a HIP graph and replayed as one launch (plan.graph)."""
+        st = self.alg.storage
 
-        # with zero_copy the env's step finaliser also stores the scalar columns of the transition (bind_transition)
-        sink_ok = (zero_copy and hasattr(env, "bind_transition") and hasattr(alg, "transition_sink")
-                   and getattr(env.cfg.env, "send_timeouts", False) and os.environ.get("HGYM_ENV_SINK", "1") != "0")
+        def rollout(obs, critic_obs, log):
+            return self._rollout_fused(plan, obs, critic_obs) if plan.fuse else self._rollout_stepwise(plan, obs, critic_obs, log)
 
-        if sink_ok:
-            alg.env_stores_transitions = True
-        # With logging the reference reads rewards / dones / infos on the host after every vec-step (:143-156).  Here the step
-        # finaliser keeps that book-keeping on the device (LeggedRobot.bind_log_sink: running episode returns / lengths, the
-        # last-100-episodes rings, the per-step sums of extras["episode"]) and the host reads it once per iteration.
-        log_sink = bool(log_on and sink_ok and hasattr(env, "bind_log_sink") and os.environ.get("HGYM_LOG_SINK", "1") != "0"
-                        and env.bind_log_sink(True))
-        host_log = log_on and not log_sink
-        # ... and, when nothing on the host looks at the per-step extras, the finaliser of vec-step t is not
-        # launched by the env at all: it rides as one extra workgroup of the policy launch of step t+1 (2 launches per vec-step)
-        defer_ok = (sink_ok and not host_log and hasattr(env, "take_pending_finalize") and isinstance(alg, PPO)
-                    and os.environ.get("HGYM_DEFER_FIN", "1") != "0")
+        def capture():
+            log_c = _EpisodeLog(log.on, (log.reward_sum, log.length, log.done))       # (the capture refills its own list at every replay)
+            return dict(out=rollout(st._obs_all[0], st._priv_all[0], log_c), log=log_c, shadow_valid=list(getattr(st, "shadow_valid", [])))
 
-        # ... and with the synthetic-physics backend the whole loop body -- act, env.step, process_env_step -- is ONE launch per
-        # vec-step (hgym_rollout_step): the env step of a 32-env slice runs right behind the actor tile of the same slice
-        fuse_mode = (env.rollout_fused_mode(alg.net) if (defer_ok and hasattr(env, "rollout_fused_mode") and hasattr(alg, "fused_rollout_step")
-                                                         and os.environ.get("HGYM_FUSE_ROLLOUT", "1") != "0") else None)
-        fuse_ok = fuse_mode is not None
-        # "deferred": more than half a chip of envs (8192 per MI355X, BASELINE configs[3]) -- the launch has no critic tiles, the critic
-        # runs once over the stored rows behind the last step (nothing inside the rollout needs V(s_t) but the time-out bootstrap,
-        # which compute_returns then applies: ppo.py:107-108)
-        deferred = fuse_mode == "deferred" and hasattr(alg, "deferred_values")
+        r = self._rollout_capture.run(plan.graph, gkey, lambda: dict(out=rollout(obs, critic_obs, log), log=log), capture,
+                                      lambda held: self.alg.after_rollout_replay(held["shadow_valid"], plan.fuse == "deferred"))
+        return r["out"] + (r["log"],)
 
-        def rollout(obs, critic_obs):
-            if fuse_ok:
-                env.rollout_begin(alg._sample_step, self.num_steps_per_env)
-                T = self.num_steps_per_env
-                for i in range(T):
-                    if deferred:
-                        alg.fused_rollout_step(env, i, obs, critic_obs, obs_all[i + 1], priv_all[i + 1], deferred=True)
-                    else:
-                        # (the slot after next: its older frames are written by this launch, off the next one's critical path)
-                        alg.fused_rollout_step(env, i, obs, critic_obs, obs_all[i + 1], priv_all[i + 1],
-                                               (obs_all[i + 2], priv_all[i + 2]) if i + 2 <= T else None)
-                    obs, critic_obs = obs_all[i + 1], priv_all[i + 1]
-                env.rollout_end()
-                if deferred:
-                    alg.deferred_values()       # part of the collection (and of the captured graph): V of all T + 1 slots in one pass
-                return obs, critic_obs
-            fin = None
-            for i in range(self.num_steps_per_env):
-                actions = alg.act(obs, critic_obs, env_fin=fin) if defer_ok else alg.act(obs, critic_obs)
-                if zero_copy:
-                    env.bind_outputs(obs_all[i + 1], priv_all[i + 1])
-                if sink_ok:
-                    env.bind_transition(alg.transition_sink(), defer_finalize=True) if defer_ok else env.bind_transition(alg.transition_sink())
-                obs, privileged_obs, rewards, dones, infos = env.step(actions)
-                if defer_ok:
-                    fin = env.take_pending_finalize()
-                critic_obs = privileged_obs if privileged_obs is not None else obs
-                alg.process_env_step(rewards, dones, infos, **({"stored": True} if sink_ok else {}))
-                if host_log:
-                    if "episode" in infos:
-                        ep_infos.append({k: v.clone() for k, v in infos["episode"].items()})
-                    cur_reward_sum.add_(rewards)
-                    cur_episode_length.add_(1)
-                    d = dones.to(torch.float)
-                    done_stats[0] += (cur_reward_sum * d).sum()
-                    done_stats[1] += (cur_episode_length * d).sum()
-                    done_stats[2] += d.sum()
-                    cur_reward_sum.mul_(1.0 - d)
-                    cur_episode_length.mul_(1.0 - d)
-            if defer_ok:
-                env.run_finalize(fin)           # the last step has no following policy launch
-            return obs, critic_obs
+    def _rollout_fused(self, plan, obs, critic_obs):
+        """act, env.step and process_env_step as ONE launch per vec-step.  "deferred": no critic tiles; the critic runs once over the
+        stored rows behind the last step (only the time-out bootstrap needs V(s_t), and compute_returns applies it: ppo.py:107-108)."""
+        env, alg, T, deferred = self.env, self.alg, self.num_steps_per_env, plan.fuse == "deferred"
+        obs_all, priv_all = alg.storage._obs_all, alg.storage._priv_all
+        env.rollout_begin(alg._sample_step, T)
+        for i in range(T):
+            # ahead: the slot after next, whose older frames this launch writes, off the next one's critical path (inline form only)
+            ahead = (obs_all[i + 2], priv_all[i + 2]) if (i + 2 <= T and not deferred) else None
+            alg.fused_rollout_step(env, i, obs, critic_obs, obs_all[i + 1], priv_all[i + 1], ahead, deferred=deferred)
+            obs, critic_obs = obs_all[i + 1], priv_all[i + 1]
+        env.rollout_end()
+        if deferred:
+            alg.deferred_values()       # part of the collection (and of the captured graph): V of all T + 1 slots in one pass
+        return obs, critic_obs
 
-        # Without logging nothing on the host needs the iteration's results: collection / learn time are then measured with
-        # HIP events on the launch stream and read once at the end of learn(), and the update's loss read-back is skipped,
-        # so the host enqueues iteration k+1 while the device still runs iteration k (no idle gap at the phase
-        # boundaries).  With logging the reference's per-iteration host synchronisation is kept.
-        async_iters = ((not log_on) and str(self.device).startswith("cuda") and isinstance(alg, PPO)
-                       and os.environ.get("HGYM_ASYNC", "1") != "0")
-        # With the device-side log sink the logging run does not synchronise per iteration either: everything log() prints is
-        # copied to pinned host memory behind the update (stream-ordered), and the host formats iteration k's block while the
-        # device runs iteration k + 1 -- the log appears one iteration late, with the same content in the same order.
-        async_log = (log_sink and str(self.device).startswith("cuda") and isinstance(alg, PPO)
-                     and os.environ.get("HGYM_ASYNC", "1") != "0")
-        pending = None
-        marks = []
-        # the captured launches hold HgymEnvConfig and the sink's gamma BY VALUE: a change between learn() calls (reward scales,
-        # command ranges, push / noise settings written into the env's native config, alg.gamma -- what a curriculum script does)
-        # must re-capture, as the eager reference would simply see it
-        gkey = (id(env), id(alg.storage), log_on, log_sink, sink_ok, defer_ok, fuse_mode, getattr(alg, "gamma", None),
-                env.native_config_digest() if hasattr(env, "native_config_digest") else None,
-                getattr(env, "_rows_ahead", None), getattr(env, "_l0_ahead", None), getattr(alg.storage, "_obs_bf16", None) is not None)
-        # the update as a second captured graph (HGYM_GRAPH_UPDATE=0: eager, as until round 5): only where nothing on the host reads the
-        # update's results inside the iteration (the asynchronous loops) and every launch argument is iteration-invariant
-        graph_update = bool(use_graph and (async_iters or async_log) and hasattr(alg, "update_capturable") and alg.update_capturable()
-                            and os.environ.get("HGYM_GRAPH_UPDATE", "1") != "0")
-        ukey = (gkey, alg.update_graph_key(), deferred) if graph_update else None
-        if not graph_update:
-            self._update_graph = None
-        tot_iter = self.current_learning_iteration + num_learning_iterations
-        try:
-            for it in range(self.current_learning_iteration, tot_iter):
-                start = time.time()
-                if async_iters or async_log:
-                    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-                    ev[0].record()
-                with torch.inference_mode():
-                    g = self._graph
-                    if use_graph and g is not None and g["key"] == gkey:
-                        g["graph"].replay()
-                        alg.storage.step = self.num_steps_per_env
-                        if deferred:
-                            alg._deferred_ready = True              # (the captured rollout ends with deferred_values' launches)
-                        alg.storage.shadow_valid = list(g["shadow_valid"])     # the replayed launches wrote the same shadow slots
-                        obs, critic_obs = g["out"]
-                        ep_infos = g["ep_infos"]
-                        cur_reward_sum, cur_episode_length, done_stats = g["stats"]
-                    elif use_graph and self._graph_warm:
-                        graph = torch.cuda.CUDAGraph()
-                        ep_infos = []
-                        torch.cuda.synchronize()
-                        # thread-local capture mode: with torch.distributed initialised, the RCCL watchdog thread polls events
-                        # concurrently; only this thread's launches belong to the capture
-                        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                            out = rollout(obs_all[0], priv_all[0])
-                        self._graph = dict(graph=graph, out=out, ep_infos=ep_infos, key=gkey,
-                                           stats=(cur_reward_sum, cur_episode_length, done_stats),
-                                           shadow_valid=list(getattr(alg.storage, "shadow_valid", [])))
-                        alg.storage.step = 0
-                        graph.replay()                  # capture does not execute: run the captured rollout once
-                        alg.storage.step = self.num_steps_per_env
-                        obs, critic_obs = out
-                    else:
-                        obs, critic_obs = rollout(obs, critic_obs)
-                        self._graph_warm = True
-                    if async_iters or async_log:
-                        ev[1].record()
-                    elif str(self.device).startswith("cuda"):
-                        torch.cuda.synchronize()
-                    stop = time.time()
-                    collection_time = stop - start
-                    start = stop
-                    ug = self._update_graph
-                    replayed_update = False
-                    if graph_update and ug is not None and ug["key"] == ukey and self._graph is not None and self._graph["key"] == gkey:
-                        # steady state: the whole iteration is two graph launches (rollout, update) with the phase event between them
-                        ug["graph"].replay()
-                        alg.after_update_replay()
-                        replayed_update = True
-                    elif not (graph_update and self._update_warm and self._graph is not None and self._graph["key"] == gkey):
-                        alg.compute_returns(critic_obs)
-                if replayed_update:
-                    mean_value_loss = mean_surrogate_loss = None
-                elif graph_update and self._update_warm and self._graph is not None and self._graph["key"] == gkey:
-                    # the rollout has just been captured (or is replayed) and the update has run eagerly at least once: capture
-                    # compute_returns() + update(sync=False) -- ~45 launches per iteration that otherwise come from Python + ctypes on every
-                    # rank -- into a second graph.  Nothing in their arguments changes between iterations: the permutation's draw number,
-                    # Adam's step, the learning rate and the exchange's call number are read on the device (PPO.update_capturable)
-                    ugraph = torch.cuda.CUDAGraph()
-                    torch.cuda.synchronize()
-                    # (inside inference mode like the rollout's capture: capture_begin updates the generator's graph-state tensors in
-                    # place, and the first capture created them as inference tensors)
-                    with torch.inference_mode():
-                        with torch.cuda.graph(ugraph, capture_error_mode="thread_local"):
-                            alg.compute_returns(critic_obs)
-                            alg.update(sync=False)
-                    self._update_graph = dict(graph=ugraph, key=ukey)
-                    ugraph.replay()                 # capture does not execute (update()'s host book-keeping has run once, for this replay)
-                    mean_value_loss = mean_surrogate_loss = None
-                else:
-                    mean_value_loss, mean_surrogate_loss = alg.update(sync=False) if (async_iters or async_log) else alg.update()
-                    self._update_warm = True
-                if zero_copy:                       # storage.clear() rotated slot T into slot 0
-                    obs, critic_obs = obs_all[0], priv_all[0]
-                if it % self.save_interval == 0:
-                    self._check_replicas("iteration %d" % it)       # (data-parallel runs only; collective: every rank, same iteration)
-                stop = time.time()
-                learn_time = stop - start
-                if async_iters:
-                    ev[2].record()
-                    marks.append(ev)
-                elif async_log:
-                    ev[2].record()
-                    snap = self._log_snapshot(env, alg, it & 1)
-                    if pending is not None:
-                        self._log_flush(pending, num_learning_iterations)
-                    pending = dict(it=it, ev=ev, snap=snap)
-                    if it % self.save_interval == 0:
-                        self.save(os.path.join(self.log_dir, "model_{}.pt".format(it)), wait=False)
-                    continue
-                else:
-                    self.last_collection_time, self.last_learn_time = collection_time, learn_time
-                if self.log_dir is not None:
-                    if log_sink:
-                        # one read-back: mean over this iteration's steps of extras["episode"] (what the reference's ep_infos list
-                        # averages to), and the rings that ARE the reference's rewbuffer / lenbuffer (the last 100 finished episodes)
-                        ep_mean, ring_r, ring_l = env.log_sink_read()
-                        ep_infos = [ep_mean]
-                        rewbuffer, lenbuffer = deque(ring_r, maxlen=100), deque(ring_l, maxlen=100)
-                    else:
-                        s = done_stats.cpu()
-                        if float(s[2]) > 0:
-                            rewbuffer.append(float(s[0] / s[2]))
-                            lenbuffer.append(float(s[1] / s[2]))
-                        done_stats.zero_()
-                    self.log(locals())
-                    if it % self.save_interval == 0:
-                        self.save(os.path.join(self.log_dir, "model_{}.pt".format(it)), wait=False)
-                if self._graph is None or ep_infos is not self._graph["ep_infos"]:
-                    ep_infos.clear()
-        finally:
-            # also on an exception / KeyboardInterrupt inside the loop: the last finished iteration's log block is still printed
-            # (async logging runs one iteration behind) and the env's bindings into the rollout storage are released
-            if pending is not None:
-                try:
-                    self._log_flush(pending, num_learning_iterations)
-                except Exception:      # the device may be the thing that failed
-                    pass
-            if zero_copy:
-                env.bind_outputs(None, None)
-            if sink_ok:
-                env.bind_transition(None)
-                alg.env_stores_transitions = False
-            if log_sink:
-                env.bind_log_sink(False)
-        if marks:                               # mean device time per iteration of this call (HIP events, one sync)
-            torch.cuda.synchronize()
-            if hasattr(alg, "check_comm"):
-                alg.check_comm()                # the asynchronous loop read nothing back: the exchange's status word, once per call
-            self.last_collection_time = sum(a.elapsed_time(b) for a, b, _ in marks) * 1e-3 / len(marks)
-            self.last_learn_time = sum(b.elapsed_time(c) for _, b, c in marks) * 1e-3 / len(marks)
-            # per-iteration device times of this call (ms; iteration k's start event to iteration k + 1's, i.e. including whatever idles
-            # between them): bench.py reports their median next to the mean ("median of >= 20")
-            self.last_iteration_ms = [marks[k][0].elapsed_time(marks[k + 1][0]) for k in range(len(marks) - 1)] + [marks[-1][0].elapsed_time(marks[-1][2])]
-        self.current_learning_iteration += num_learning_iterations
-        self._check_replicas("end of learn() at iteration %d" % self.current_learning_iteration)
+    def _rollout_stepwise(self, plan, obs, critic_obs, log):
+        env, alg, fin = self.env, self.alg, None
+        obs_all, priv_all = getattr(alg.storage, "_obs_all", None), getattr(alg.storage, "_priv_all", None)
+        for i in range(self.num_steps_per_env):
+            actions = alg.act(obs, critic_obs, env_fin=fin) if plan.defer_fin else alg.act(obs, critic_obs)
+            if plan.zero_copy:
+                env.bind_outputs(obs_all[i + 1], priv_all[i + 1])
+            if plan.env_sink:
+                env.bind_transition(alg.transition_sink(), defer_finalize=True) if plan.defer_fin else env.bind_transition(alg.transition_sink())
+            obs, privileged_obs, rewards, dones, infos = env.step(actions)
+            if plan.defer_fin:
+                fin = env.take_pending_finalize()
+            critic_obs = privileged_obs if privileged_obs is not None else obs
+            alg.process_env_step(rewards, dones, infos, **({"stored": True} if plan.env_sink else {}))
+            if log.on:
+                if "episode" in infos:
+                    log.ep_infos.append({k: v.clone() for k, v in infos["episode"].items()})
+                log.reward_sum.add_(rewards)
+                log.length.add_(1)
+                d = dones.to(torch.float)
+                log.done[0] += (log.reward_sum * d).sum()
+                log.done[1] += (log.length * d).sum()
+                log.done[2] += d.sum()
+                log.reward_sum.mul_(1.0 - d)
+                log.length.mul_(1.0 - d)
+        if plan.defer_fin:
+            env.run_finalize(fin)           # the last step has no following policy launch
+        return obs, critic_obs
+
+    def _learn_step(self, plan, gkey, ukey, critic_obs):
+        """compute_returns() + update() -> (mean_value_loss, mean_surrogate_loss), None where not read back (PPO.update_capturable)."""
+        def launches(sync=False):
+            with torch.inference_mode():
+                self.alg.compute_returns(critic_obs)
+            return self.alg.update(sync=sync)
+
+        return self._update_capture.run(plan.graph_update and self._rollout_capture.valid(gkey), ukey, lambda: launches(not plan.async_mode),
+                                        launches, lambda held: self.alg.after_update_replay())
+
+    def _finish_async_log(self, it, ev, pending, num_learning_iterations):
+        """Log sink: iteration k's block is printed from pinned-host copies while the device runs k + 1.  -> the new pending block."""
+        snap = self._log_snapshot(self.env, self.alg, it & 1)
+        if pending is not None:
+            self._log_flush(pending, num_learning_iterations)
+        return dict(it=it, ev=ev, snap=snap)
+
+    def _finish_sync(self, plan, log, rings, locs):
+        self.last_collection_time, self.last_learn_time = locs["collection_time"], locs["learn_time"]
         if self.log_dir is not None:
-            self.save(os.path.join(self.log_dir, "model_{}.pt".format(self.current_learning_iteration)), wait=False)
-            if os.environ.get("HGYM_ASYNC_SAVE", "1") == "0":
-                self.wait_for_saves()       # (synchronous path: nothing is pending; kept for symmetry)
-            # else: the background writer finishes the file; wait_for_saves() / load() / interpreter exit wait for it (save()'s docstring)
+            if plan.log_sink:
+                # one read-back: this iteration's mean extras["episode"] and the rings that ARE the reference's rewbuffer / lenbuffer
+                ep_mean, ring_r, ring_l = self.env.log_sink_read()
+                locs.update(ep_infos=[ep_mean], rewbuffer=deque(ring_r, maxlen=100), lenbuffer=deque(ring_l, maxlen=100))
+            else:
+                s = log.done.cpu()
+                if float(s[2]) > 0:
+                    rings[0].append(float(s[0] / s[2]))
+                    rings[1].append(float(s[1] / s[2]))
+                log.done.zero_()
+                locs.update(ep_infos=log.ep_infos, rewbuffer=rings[0], lenbuffer=rings[1])
+            self.log(locs)
+        if self._graph is None or log is not self._rollout_capture.held["log"]:
+            log.ep_infos.clear()
+
+    def _read_event_times(self, marks):
+        """Without logging the iterations' device times come from HIP events, read once here.  last_iteration_ms: iteration k's start
+        event to iteration k + 1's, i.e. including whatever idles between them (bench.py reports their median)."""
+        torch.cuda.synchronize()
+        if hasattr(self.alg, "check_comm"):
+            self.alg.check_comm()           # the asynchronous loop read nothing back: the exchange's status word, once per call
+        self.last_collection_time = sum(a.elapsed_time(b) for a, b, _ in marks) * 1e-3 / len(marks)
+        self.last_learn_time = sum(b.elapsed_time(c) for _, b, c in marks) * 1e-3 / len(marks)
+        self.last_iteration_ms = [marks[k][0].elapsed_time(marks[k + 1][0]) for k in range(len(marks) - 1)] + [marks[-1][0].elapsed_time(marks[-1][2])]
 
     # ------------------------------------------------------------------
     def _check_replicas(self, what):
@@ -505,8 +498,7 @@ class OnPolicyRunner:
 
     def invalidate_graph(self):
         """Drop the captured rollout; the next learn() iteration runs eagerly and the one after re-captures."""
-        self._graph, self._graph_warm = None, False
-        self._update_graph, self._update_warm = None, False
+        self._rollout_capture, self._update_capture = _CapturedGraph(), _CapturedGraph()
 
     def save(self, path, infos=None, wait=True):
         """on_policy_runner.py:274-281 (same dict, same keys).  wait=True (the reference's semantics, and what a direct caller gets): the
@@ -516,10 +508,7 @@ class OnPolicyRunner:
         included (round 6: default; `test_background_checkpoint_equals_the_synchronous_one`): the file of the last iteration is complete a
         few milliseconds AFTER learn() returns -- `wait_for_saves()` (called by load(), by the next save(wait=True), and at interpreter
         exit, which is when scripts/train.py ends) waits for it.  A caller that reads model_<it>.pt from the same process right after
-        learn() calls runner.wait_for_saves() first; HGYM_ASYNC_SAVE=0 restores the reference's blocking torch.save everywhere.
-        (Round 4 kept this opt-in because learn() then WAITED for the final file and the writer thread's wake-up made that wait 5-75 ms
-        instead of a steady 5 ms, profiles/r04_async_checkpoint_ab.txt; with nothing waiting inside learn() that jitter is off the
-        training thread.)"""
+        learn() calls runner.wait_for_saves() first; HGYM_ASYNC_SAVE=0 restores the reference's blocking torch.save everywhere."""
         t0 = time.time()
         net = getattr(self.alg, "net", None)
         if (net is None or not str(self.device).startswith("cuda") or os.environ.get("HGYM_ASYNC_SAVE", "1") == "0"

@@ -150,6 +150,7 @@ class PPO:
         self._sample_step = torch.zeros(1, dtype=torch.int64, device=self.device)
         self._perm_seed = (torch.initial_seed() * 0x9E3779B97F4A7C15 + 0xABCD + 104729 * self._rank) & 0xFFFFFFFFFFFFFFFF
         self._perm_draws = 0
+        self._deferred_ready = False        # deferred_values() has run since the last compute_returns()
         self._perm_draws_dev = torch.zeros(1, dtype=torch.int64, device=self.device)      # the same number where a captured update reads it
         ac._sample_step = self._sample_step
         # exploration-noise key: from the run's seed (as the permutation key above) and the rank
@@ -296,7 +297,7 @@ class PPO:
         return dist_utils.allreduce_adv_stats(stats)
 
     def compute_returns(self, last_critic_obs):
-        if getattr(self, "_deferred_ready", False):       # deferred_values() has evaluated the bootstrap observation with the rest
+        if self._deferred_ready:        # deferred_values() has evaluated the bootstrap observation with the rest
             self._deferred_ready = False
             self.storage.compute_returns(self.storage.last_values, self.gamma, self.lam, stats_hook=self._adv_stats,
                                          time_outs=self.storage.time_outs)
@@ -321,7 +322,14 @@ class PPO:
         import ctypes as C
         return (bytes(C.string_at(C.addressof(self._ppo_cfg), C.sizeof(self._ppo_cfg))), self.num_learning_epochs, self.num_mini_batches,
                 float(self.gamma), float(self.lam), self.permutation, self._perm_seed, id(self.storage), id(self.net),
-                bool(dist_utils.active()), bool(self._comm_p2p), bytes(C.string_at(C.addressof(self.net.cfg), C.sizeof(self.net.cfg))))
+                bool(dist_utils.active()), bool(self._comm_p2p), bytes(C.string_at(C.addressof(self.net.cfg), C.sizeof(self.net.cfg))),
+                self.storage._obs_bf16 is not None, bool(self.comm_flip), self._world)
+
+    def after_rollout_replay(self, shadow_valid, deferred):
+        """Host-side book-keeping of one replayed rollout: a full storage, the shadow slots the capture wrote, deferred_values() if deferred."""
+        self.storage.step = self.storage.num_transitions_per_env
+        self._deferred_ready = self._deferred_ready or deferred
+        self.storage.shadow_valid = list(shadow_valid)
 
     def after_update_replay(self):
         """Host-side book-keeping of one replayed compute_returns() + update(sync=False): what the Python of those two calls changes on the

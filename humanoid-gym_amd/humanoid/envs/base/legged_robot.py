@@ -69,10 +69,10 @@ class LeggedRobot(BaseTask):
         self.max_episode_length = np.ceil(self.max_episode_length_s / self.dt)
         self.cfg.domain_rand.push_interval = np.ceil(self.cfg.domain_rand.push_interval_s / self.dt)
 
-    def native_config_digest(self):
-        """Hash of the HgymEnvConfig the next launches will carry (by value): lets a caller that captured launches into a HIP
-        graph notice that the configuration was edited since."""
-        return hash(bytes(self._ncfg)) if self._ncfg is not None else None
+    def rollout_graph_key(self):
+        """What this env's launches carry by value (a hash of the HgymEnvConfig, the carried-row switches): a caller that captured them
+        into a HIP graph re-captures when it changes."""
+        return hash(bytes(self._ncfg)) if self._ncfg is not None else None, self._rows_ahead, self._l0_ahead
 
     def _native_config(self):
         """XBotLCfg -> HgymEnvConfig.  Scalars are combined in python double arithmetic and rounded to fp32 last,
@@ -373,12 +373,15 @@ class LeggedRobot(BaseTask):
         # (a split step -- user-defined reward terms -- always runs its finaliser itself)
         self._defer = bool(defer_finalize) and sink is not None and not getattr(self, "_custom_terms", None)
 
+    def log_sink_supported(self):
+        """bind_log_sink(True) takes: the log sink covers the kernel's own reward terms only."""
+        return not getattr(self, "_custom_terms", None) and set(self.extras.get("episode", {})) == {"rew_" + n for n in self.reward_names}
+
     def bind_log_sink(self, on):
         """Native extension: while on, the step finaliser keeps the runner's per-step logging book-keeping on the device
         (HgymEnvOut.log_*: running episode return / length per env, the last-100-episodes rings, the per-step sums of
-        extras["episode"]); read with log_sink_read().  Only the kernel's own reward terms are covered."""
-        on = (bool(on) and not getattr(self, "_custom_terms", None)
-              and set(self.extras.get("episode", {})) == {"rew_" + n for n in self.reward_names})
+        extras["episode"]); read with log_sink_read().  Returns whether it is on (log_sink_supported)."""
+        on = bool(on) and self.log_sink_supported()
         self._buf.log_sink = on
         if on:
             self._buf.log_cur.zero_()
