@@ -192,6 +192,37 @@ static void launch_measure_heights(const EnvArgs& A, hipStream_t s) {
     hipLaunchKernelGGL(measure_heights_kernel, dim3((unsigned)ceil_div(total, (int64_t)256)), dim3(256), 0, s, A);
 }
 
+// XBot-L's default options: none of the generic LeggedRobot options (HgymEnvConfig tail) and no user-defined reward terms
+static bool xbotl_default_options(const HgymEnvConfig* cfg) {
+    return !(cfg->custom_origins || cfg->terrain_curriculum || cfg->num_height_points > 0 || cfg->command_curriculum ||
+             !cfg->heading_command || cfg->num_custom_rewards > 0);
+}
+
+// The EnvArgs record of one env step (launch_step, rollout_env_args), after checking the output and history buffers every step writes
+static int32_t env_args(const HgymEnvConfig* cfg, const HgymSimTensors* sim, const HgymEnvState* st, const HgymEnvOut* out,
+                        float* actions_in, int mode, int fused, int envs_per_block, EnvArgs* A) {
+    HG_REQUIRE(out->obs && out->priv_obs && out->rew && out->reset && out->time_out && out->extras_time_outs && out->extras_episode,
+               HGYM_E_BADARG, "null output buffer");
+    HG_REQUIRE(st->obs_ring && st->priv_ring && st->episode_acc, HGYM_E_BADARG, "null ring/episode_acc");
+    memset(A, 0, sizeof(*A));
+    A->cfg = *cfg;
+    A->sim = *sim;
+    A->st = *st;
+    A->out = *out;
+    A->actions_in = actions_in;
+    A->origins_hbm = st->env_origins;
+    A->mode = mode;
+    A->fused = fused;
+    A->envs_per_block = envs_per_block;
+    set_body_offsets(*A);
+    // fast staging when the state fields are one contiguous [136][N] allocation
+    bool contig = true;
+    float* const* f = &st->commands;
+    for (int i = 0; i + 1 < kNumStateFields; ++i) contig = contig && (f[i + 1] == f[i] + (int64_t)state_field_comps(i) * cfg->num_envs);
+    A->state_contig = contig ? 1 : 0;
+    return HGYM_OK;
+}
+
 static int32_t launch_step(const HgymEnvConfig* cfg, const HgymSimTensors* sim, const HgymEnvState* st, const HgymEnvOut* out,
                            const HgymEnvNoise* noise, float* actions_in, int mode, int fused, hipStream_t s, int phase = 0) {
     int32_t rc = check_common(cfg, sim, st);
@@ -208,40 +239,21 @@ static int32_t launch_step(const HgymEnvConfig* cfg, const HgymSimTensors* sim, 
                        j, cfg->custom_reward_pos[j]);
     }
     HG_REQUIRE(sim && out, HGYM_E_BADARG, "null sim/out");
-    HG_REQUIRE(out->obs && out->priv_obs && out->rew && out->reset && out->time_out && out->extras_time_outs && out->extras_episode,
-               HGYM_E_BADARG, "null output buffer");
-    HG_REQUIRE(st->obs_ring && st->priv_ring && st->episode_acc, HGYM_E_BADARG, "null ring/episode_acc");
+    EnvArgs A;
+    rc = env_args(cfg, sim, st, out, actions_in, mode, fused, pick_envs_per_block(cfg->num_envs), &A);
+    if (rc) return rc;
     HG_REQUIRE(!out->t_rewards || ((out->t_values || out->t_time_outs) && out->t_dones), HGYM_E_BADARG,
                "transition sink needs t_values (or, deferred values, t_time_outs) and t_dones");
-    EnvArgs A;
-    memset(&A, 0, sizeof(A));
-    A.cfg = *cfg;
-    A.sim = *sim;
-    A.st = *st;
-    A.out = *out;
     A.out.obs_ahead = A.out.priv_ahead = nullptr;      // the rows-ahead protocol exists in hgym_rollout_step only (a stand-alone step
     A.out.obs_older_ready = 0;                          // would write one frame of those rows and nothing else)
     if (noise) A.noise = *noise;
-    A.actions_in = actions_in;
-    A.origins_hbm = st->env_origins;
-    A.mode = mode;
     A.phase = phase;
-    A.fused = fused;
-    A.envs_per_block = pick_envs_per_block(cfg->num_envs);
-    set_body_offsets(A);
-    {   // fast staging when the state fields are one contiguous [136][N] allocation
-        bool contig = true;
-        float* const* f = &st->commands;
-        for (int i = 0; i + 1 < kNumStateFields; ++i) contig = contig && (f[i + 1] == f[i] + (int64_t)state_field_comps(i) * cfg->num_envs);
-        A.state_contig = contig ? 1 : 0;
-    }
     const int blocks = ceil_div(cfg->num_envs, A.envs_per_block);
     const size_t lds = step_smem_bytes(A.envs_per_block);
     prof_begin(HGYM_PROF_ENV_STEP, s);
     const bool std_stack = cfg->frame_stack == 15 && cfg->c_frame_stack == 3;
     // the generic LeggedRobot options (HgymEnvConfig tail) have their own instantiation: off, none of their code is compiled in
-    const bool generic = cfg->custom_origins || cfg->terrain_curriculum || cfg->num_height_points > 0 || cfg->command_curriculum ||
-                         !cfg->heading_command || phase != 0 || cfg->num_custom_rewards > 0;
+    const bool generic = !xbotl_default_options(cfg) || phase != 0;
     if (std_stack && A.envs_per_block == 16 && !generic && mode == MODE_STEP)
         hipLaunchKernelGGL((env_step_kernel<15, 3, 16, false, true>), dim3(blocks), dim3(256), lds, s, A);
     else if (std_stack && A.envs_per_block == 16 && !generic)
@@ -279,32 +291,14 @@ int32_t rollout_env_args(const HgymEnvConfig* cfg, const HgymSimTensors* sim, co
     int32_t rc = check_common(cfg, sim, st);
     if (rc) return rc;
     HG_REQUIRE(sim && out && actions, HGYM_E_BADARG, "null sim / out / actions");
-    HG_REQUIRE(out->obs && out->priv_obs && out->rew && out->reset && out->time_out && out->extras_time_outs && out->extras_episode,
-               HGYM_E_BADARG, "null output buffer");
-    HG_REQUIRE(st->obs_ring && st->priv_ring && st->episode_acc, HGYM_E_BADARG, "null ring/episode_acc");
+    rc = env_args(cfg, sim, st, out, actions, MODE_STEP, 1, 32, A);
+    if (rc) return rc;
     HG_REQUIRE(out->t_rewards && (out->t_values || out->t_time_outs) && out->t_dones && out->t_step && out->defer_finalize, HGYM_E_BADARG,
                "the fused rollout step stores the transition itself: transition sink (immediate: t_values; deferred: t_time_outs) + defer_finalize required");
-    const bool generic = cfg->custom_origins || cfg->terrain_curriculum || cfg->num_height_points > 0 || cfg->command_curriculum ||
-                         !cfg->heading_command || cfg->num_custom_rewards > 0;
-    HG_REQUIRE(!generic && !cfg->use_ref_actions && cfg->frame_stack == 15 && cfg->c_frame_stack == 3, HGYM_E_UNSUPPORTED,
+    HG_REQUIRE(xbotl_default_options(cfg) && !cfg->use_ref_actions && cfg->frame_stack == 15 && cfg->c_frame_stack == 3, HGYM_E_UNSUPPORTED,
                "fused rollout step: XBot-L default options only");
     HG_REQUIRE(cfg->num_envs % 32 == 0, HGYM_E_UNSUPPORTED, "fused rollout step: num_envs must be a multiple of 32");
-    memset(A, 0, sizeof(*A));
-    A->cfg = *cfg;
-    A->sim = *sim;
-    A->st = *st;
-    A->out = *out;
-    A->actions_in = actions;
-    A->origins_hbm = st->env_origins;
-    A->mode = MODE_STEP;
-    A->fused = 1;
-    A->envs_per_block = 32;
-    set_body_offsets(*A);
-    bool contig = true;
-    float* const* f = &st->commands;
-    for (int i = 0; i + 1 < kNumStateFields; ++i) contig = contig && (f[i + 1] == f[i] + (int64_t)state_field_comps(i) * cfg->num_envs);
-    A->state_contig = contig ? 1 : 0;
-    HG_REQUIRE(contig && sim->root.env_stride == 1 && sim->dof_pos.env_stride == 1 && sim->dof_vel.env_stride == 1 &&
+    HG_REQUIRE(A->state_contig && sim->root.env_stride == 1 && sim->dof_pos.env_stride == 1 && sim->dof_vel.env_stride == 1 &&
                    sim->contact.env_stride == 1 && sim->rigid.env_stride == 1, HGYM_E_UNSUPPORTED,
                "fused rollout step: contiguous [136][N] state and SoA sim tensors required");
     return HGYM_OK;

@@ -286,7 +286,7 @@ class OnPolicyRunner:
         st = self.alg.storage
 
         def rollout(obs, critic_obs, log):
-            return self._rollout_fused(plan, obs, critic_obs) if plan.fuse else self._rollout_stepwise(plan, obs, critic_obs, log)
+            return self._rollout_fused(plan) if plan.fuse else self._rollout_stepwise(plan, obs, critic_obs, log)
 
         def capture():
             log_c = _EpisodeLog(log.on, (log.reward_sum, log.length, log.done))       # (the capture refills its own list at every replay)
@@ -296,21 +296,15 @@ class OnPolicyRunner:
                                       lambda held: self.alg.after_rollout_replay(held["shadow_valid"], plan.fuse == "deferred"))
         return r["out"] + (r["log"],)
 
-    def _rollout_fused(self, plan, obs, critic_obs):
-        """act, env.step and process_env_step as ONE launch per vec-step.  "deferred": no critic tiles; the critic runs once over the
-        stored rows behind the last step (only the time-out bootstrap needs V(s_t), and compute_returns applies it: ppo.py:107-108)."""
-        env, alg, T, deferred = self.env, self.alg, self.num_steps_per_env, plan.fuse == "deferred"
-        obs_all, priv_all = alg.storage._obs_all, alg.storage._priv_all
-        env.rollout_begin(alg._sample_step, T)
-        for i in range(T):
-            # ahead: the slot after next, whose older frames this launch writes, off the next one's critical path (inline form only)
-            ahead = (obs_all[i + 2], priv_all[i + 2]) if (i + 2 <= T and not deferred) else None
-            alg.fused_rollout_step(env, i, obs, critic_obs, obs_all[i + 1], priv_all[i + 1], ahead, deferred=deferred)
-            obs, critic_obs = obs_all[i + 1], priv_all[i + 1]
-        env.rollout_end()
+    def _rollout_fused(self, plan):
+        """act, env.step and process_env_step as ONE launch per vec-step, from the storage's slot 0.  "deferred": no critic tiles; the
+        critic runs once over the stored rows behind the last step (only the time-out bootstrap needs V(s_t), and compute_returns
+        applies it: ppo.py:107-108)."""
+        alg, deferred = self.alg, plan.fuse == "deferred"
+        alg.fused_rollout_step(self.env, self.num_steps_per_env, deferred)
         if deferred:
             alg.deferred_values()       # part of the collection (and of the captured graph): V of all T + 1 slots in one pass
-        return obs, critic_obs
+        return alg.storage._obs_all[self.num_steps_per_env], alg.storage._priv_all[self.num_steps_per_env]
 
     def _rollout_stepwise(self, plan, obs, critic_obs, log):
         env, alg, fin = self.env, self.alg, None

@@ -214,36 +214,34 @@ class PPO:
             self._sample_step += 1
         return t.actions
 
-    def fused_rollout_step(self, env, i, obs, critic_obs, next_obs, next_critic_obs, ahead=None, deferred=False):
-        """act() + env.step() + process_env_step() of rollout step i as ONE launch (LeggedRobot.rollout_step): the policy's outputs
-        land in storage slot i, the env writes the next observations into the slots handed in, the finaliser riding in the
-        following launch stores rewards / dones of slot i (time-out bootstrap included).  ahead: (obs, critic_obs) of the slot after
-        next_obs, whose older frames this launch may write ahead (LeggedRobot.rollout_step).
-        deferred: the launch has no critic tiles; slot i receives the RAW reward and the bootstrap's time-out flags, and
-        deferred_values() -- once, after the last step -- fills storage.values and applies the bootstrap in compute_returns."""
-        st, s = self.storage, self.storage.step
-        if s >= st.num_transitions_per_env:
-            raise AssertionError("Rollout buffer overflow")
+    def rollout_columns(self, deferred):
+        """The storage's slot columns a fused rollout fills (LeggedRobot.rollout_begin): launch i reads slot i of the observations,
+        writes slot i + 1 and the policy's outputs of slot i; its finaliser stores rewards / dones of slot i (time-out bootstrap
+        included).  deferred: no values column -- slot i receives the RAW reward and the bootstrap's time-out flags, and
+        deferred_values() fills storage.values and has compute_returns apply the bootstrap."""
+        st = self.storage
         if deferred:
             st.enable_deferred_values()
-            out = dict(actions=st.actions[s], mu=st.mu[s], sigma=st.sigma[s], logp=st.actions_log_prob[s].view(-1), values=None)
-            sink = dict(values=None, rewards=st.rewards[s], dones=st.dones[s], time_outs=st.time_outs[s], step=self._sample_step, gamma=self.gamma)
-            own = obs.data_ptr() == st._obs_all[s].data_ptr() and critic_obs.data_ptr() == st._priv_all[s].data_ptr()
-            sh = (st._obs_bf16[s], None) if (own and st._obs_bf16 is not None) else None      # (the priv shadow: deferred_values)
-            self._deferred_shadow = bool(own and st._obs_bf16 is not None and (s == 0 or getattr(self, "_deferred_shadow", False)))
-            env.rollout_step(self.net, i, obs, critic_obs, next_obs, next_critic_obs, sink, self.actor_critic._sample_seed, out, shadow=sh)
-            st.step += 1
-            return
-        out = dict(actions=st.actions[s], mu=st.mu[s], sigma=st.sigma[s], logp=st.actions_log_prob[s].view(-1), values=st.values[s])
-        sink = dict(values=st.values[s], rewards=st.rewards[s], dones=st.dones[s], step=self._sample_step, gamma=self.gamma)
-        sh = st.shadow_slot(s) if (obs.data_ptr() == st._obs_all[s].data_ptr() and critic_obs.data_ptr() == st._priv_all[s].data_ptr()) else None
-        # the bf16 shadow of the NEXT slot's observation rows: this launch writes the columns it already knows (the carried first layer)
-        sh_next = None
-        if (sh is not None and s + 1 < st.num_transitions_per_env and next_obs.data_ptr() == st._obs_all[s + 1].data_ptr()):
-            sh_next = st._obs_bf16[s + 1]
-        env.rollout_step(self.net, i, obs, critic_obs, next_obs, next_critic_obs, sink, self.actor_critic._sample_seed, out, shadow=sh,
-                         ahead=ahead, shadow_next=sh_next)
-        st.step += 1
+        return dict(obs=st._obs_all, priv=st._priv_all, actions=st.actions, mu=st.mu, sigma=st.sigma, logp=st.actions_log_prob,
+                    values=None if deferred else st.values, rewards=st.rewards, dones=st.dones, time_outs=st.time_outs if deferred else None,
+                    obs_bf16=st._obs_bf16, priv_bf16=st._priv_bf16, step=self._sample_step, gamma=self.gamma,
+                    seed=self.actor_critic._sample_seed)
+
+    def fused_rollout_step(self, env, T=None, deferred=False, rows_ahead=None, l0_ahead=None):
+        """All T fused rollout steps: act() + env.step() + process_env_step() as ONE launch each (LeggedRobot.rollout_step) into
+        storage slots 0 .. T (default: the whole storage).  deferred: see rollout_columns; the caller follows with deferred_values().
+        rows_ahead / l0_ahead: None = the env's HGYM_ROWS_AHEAD / HGYM_L0_AHEAD (LeggedRobot.rollout_begin)."""
+        st = self.storage
+        T = st.num_transitions_per_env if T is None else int(T)
+        if st.step != 0 or T > st.num_transitions_per_env:
+            raise AssertionError("Rollout buffer overflow")
+        env.rollout_begin(self.net, self.rollout_columns(deferred), T, rows_ahead, l0_ahead)
+        for i in range(T):
+            env.rollout_step(i)
+        env.rollout_end()
+        st.step = T
+        if not deferred and st._obs_bf16 is not None:      # each launch wrote its slot's shadows (deferred: deferred_values)
+            st.shadow_valid[:T] = [True] * T
 
     def transition_sink(self):
         """The scalar columns of the storage slot act() has just filled, for an env that can store them itself
@@ -273,14 +271,14 @@ class PPO:
         self.actor_critic.reset(dones)
 
     def deferred_values(self):
-        """After a rollout of fused_rollout_step(deferred=True) launches: ActorCritic.evaluate over EVERY stored privileged row in one
+        """After a fused_rollout_step(deferred=True): ActorCritic.evaluate over EVERY stored privileged row in one
         pass (the T slots -> storage.values, the bootstrap observation in slot T -> storage.last_values), 64-row tiles at the update's
         efficiency instead of T + 1 latency-bound launches; the tiles also leave the bf16 shadow of the rows they read.  The
         reference evaluates V(s_t) inside PPO.act (ppo.py:96, on_policy_runner.py:129) -- same weights (they do not change during
         collection), same rows, same kernel arithmetic."""
         st = self.storage
         T, N = st.num_transitions_per_env, st.num_envs
-        shadow = st._priv_bf16.flatten(0, 1) if (st._priv_bf16 is not None and getattr(self, "_deferred_shadow", False)) else None
+        shadow = st._priv_bf16.flatten(0, 1) if st._priv_bf16 is not None else None
         self.net.critic_values(st._priv_all[:T].flatten(0, 1), st.values.view(-1), shadow)
         self.net.critic_values(st._priv_all[T], st.last_values.view(-1))
         if shadow is not None:

@@ -11,6 +11,8 @@ There is no CPU implementation behind this class: without libhgym_hip.so and a g
 import ctypes as C
 import math
 import os
+from dataclasses import dataclass
+from typing import Optional
 
 import numpy as np
 import torch
@@ -31,6 +33,38 @@ DOF_EFFORT = [100.0, 100.0, 250.0, 250.0, 100.0, 100.0] * 2          # urdf/XBot
 DOF_LOWER = [-0.44, -1.05, -1.57, -1.05, -0.70, -0.44, -1.57, -1.05, -1.31, -1.10, -0.87, -0.44]
 DOF_UPPER = [1.57, 1.05, 1.31, 1.10, 0.87, 0.44, 0.44, 1.05, 1.57, 1.05, 0.70, 0.44]
 NOMINAL_BASE_MASS = 15.0   # synthetic backend: base link + collapsed upper body (URDF base_link alone is 9.96 kg)
+
+
+@dataclass(frozen=True)
+class RolloutLaunch:
+    """What launch i of a fused rollout gets besides storage slots i (its rows and outputs) and i + 1 (its next rows): rollout_plan."""
+    parity: int                 # the rew / reset / time_out set the step writes (1: the alternate one); the last launch has 0
+    prev: bool                  # the previous launch's finaliser rides in this one (prev_out)
+    ahead: Optional[int]        # the slot whose older frames this launch writes for the next one (obs_ahead / priv_ahead)
+    obs_older_ready: bool       # the previous launch wrote the older frames of this one's next rows
+    l0_ahead: Optional[int]     # l0_partial buffer receiving the actor's first-layer sums for the next launch's rows
+    l0_ready: Optional[int]     # l0_partial buffer this launch's first layer starts from
+    bf16_ahead: bool            # obs_bf16_ahead = the next slot's bf16 shadow (its known columns are written with l0_ahead)
+    shadow_obs: bool            # HgymObsShadow: the slot's obs shadow is written ...
+    shadow_priv: bool           # ... and its priv shadow (deferred: PPO.deferred_values writes that one)
+
+
+def rollout_plan(T, deferred, rows_ahead, l0_ahead, shadows):
+    """The T launches of a fused rollout that reads slot i and writes slot i + 1 at step i (no side effects).  deferred: no critic
+    tiles, hence none of their side jobs (rows ahead, the carried first layer).  rows_ahead / l0_ahead: HGYM_ROWS_AHEAD / HGYM_L0_AHEAD.
+    shadows: the storage has bf16 shadows of its T slots."""
+    plan = []
+    for i in range(T):
+        prev = plan[-1] if plan else None
+        ahead = i + 2 if (not deferred and rows_ahead and i + 2 <= T) else None
+        shadow_next = shadows and i + 1 < T
+        # the first layer is carried only between launches with the same shadow arrangement
+        carry = ahead is not None and l0_ahead and shadows == shadow_next
+        older = prev is not None and prev.ahead == i + 1
+        plan.append(RolloutLaunch(parity=(T - 1 - i) & 1, prev=prev is not None, ahead=ahead, obs_older_ready=older,
+                                  l0_ahead=i & 1 if carry else None, l0_ready=prev.l0_ahead if older else None,
+                                  bf16_ahead=carry and shadow_next, shadow_obs=shadows, shadow_priv=shadows and not deferred))
+    return plan
 
 
 class _CommandRanges(dict):
@@ -459,78 +493,50 @@ class LeggedRobot(BaseTask):
             return "deferred"
         return None
 
-    def rollout_begin(self, step_counter, num_steps):
+    def rollout_begin(self, net, cols, T, rows_ahead=None, l0_ahead=None):
+        """A fused rollout of T launches (rollout_step(0) .. rollout_step(T - 1), then rollout_end()).  cols: the rollout storage's
+        slot columns (PPO.rollout_columns): obs / priv (T + 1 slots), actions, mu, sigma, logp, values (None: the deferred form,
+        hgym_rollout_step with values = NULL), rewards, dones, time_outs (deferred), obs_bf16 / priv_bf16 (None: no shadows), the
+        policy's step counter, gamma and sampling seed.  rows_ahead / l0_ahead: None = HGYM_ROWS_AHEAD / HGYM_L0_AHEAD."""
         if getattr(self, "_pending_fin", None) is not None:
             raise RuntimeError("a postponed step finaliser is pending; run it before a fused rollout")
-        self._ro_T, self._ro_prev, self._ro_ahead, self._ro_l0 = int(num_steps), None, None, None
-        self._L.check(self._L.lib.hgym_rollout_begin(C.byref(self._st_s), self._L.i64ptr(step_counter), C.c_void_p(self._buf.rollout_scratch.data_ptr()),
-                                                     (self._ro_T - 1) & 1, self._stream()), "hgym_rollout_begin")
+        self._ro_net, self._ro_cols, self._ro_prev, self._ro_i = net, cols, None, 0
+        self._ro_plan = rollout_plan(T, cols["values"] is None, self._rows_ahead if rows_ahead is None else rows_ahead,
+                                     self._l0_ahead if l0_ahead is None else l0_ahead, cols["obs_bf16"] is not None)
+        self._L.check(self._L.lib.hgym_rollout_begin(C.byref(self._st_s), self._L.i64ptr(cols["step"]), C.c_void_p(self._buf.rollout_scratch.data_ptr()),
+                                                     (T - 1) & 1, self._stream()), "hgym_rollout_begin")
 
-    def rollout_step(self, net, i, obs, priv, next_obs, next_priv, sink, seed, out, shadow=None, ahead=None, shadow_next=None):
-        """Step i of the rollout begun with rollout_begin: actions / mu / sigma / logp / values of PPO.act into `out`, this env's
-        step on those actions with the observations written to next_obs / next_priv, the transition sink of step i stored by
-        the finaliser that rides in step i + 1 (or in rollout_end).  The last step uses the primary rew / reset / time_out
-        buffers, so that they read as after a plain step() once the rollout is over.  shadow: optional (obs_bf16, priv_bf16)
-        storage-slot tensors receiving the bf16 of `obs` / `priv` (HgymObsShadow).  ahead: (obs, priv) rows the NEXT step will write
-        its observations to (HgymEnvOut.obs_ahead / priv_ahead): this launch writes their older frames off its critical path, and the
-        next call -- recognised by its next_obs being that tensor -- skips the copy.  Same rows either way (HGYM_ROWS_AHEAD=0: never).
-        shadow_next: the bf16 shadow tensor of next_obs (the NEXT call's shadow[0]), or None.  With `ahead` given there is a next
-        launch: this one also forms 20 of the 24 k-steps of the actor's first layer for next_obs (HgymEnvOut.l0_ahead; the rows are
-        this call's rows shifted by a frame) and writes columns [0, 640) of shadow_next; the next call -- recognised by its obs being
-        this call's next_obs -- starts from those sums (l0_ready).  Bit-identical outputs (HGYM_L0_AHEAD=0: never)."""
-        sh = None if shadow is None else net.shadow_struct(*shadow)
-        L = self._L
-        parity = (self._ro_T - 1 - i) & 1
-        if out["values"] is None:           # deferred values (hgym_rollout_step with values = NULL): no critic tiles, hence none of their side jobs
-            assert ahead is None and shadow_next is None and sink["values"] is None
-            o = self._buf.out_struct(next_obs, next_priv, sink, True, alt=bool(parity))
-            prev = self._ro_prev
-            L.check(L.lib.hgym_rollout_step(C.byref(net.cfg), C.byref(net.struct), C.byref(self._ncfg), C.byref(self._sim_s), C.byref(self._st_s),
-                                            C.byref(o), C.byref(prev[0]) if prev is not None else None, L.fptr(obs), L.fptr(priv),
-                                            int(seed) & 0xFFFFFFFFFFFFFFFF, L.fptr(out["actions"]), L.fptr(out["mu"]), L.fptr(out["sigma"]),
-                                            L.fptr(out["logp"]), None, C.c_void_p(self._buf.rollout_scratch.data_ptr()), parity,
-                                            None if sh is None else C.byref(sh), self._stream()), "hgym_rollout_step")
-            self._ro_prev = (o, parity, sink)
-            self._ro_ahead = self._ro_l0 = None
-            self.obs_buf, self.privileged_obs_buf = next_obs, next_priv
-            return
-        o = self._buf.out_struct(next_obs, next_priv, sink, True, alt=bool(parity))
-        if not self._rows_ahead:
-            ahead = None
-        o.obs_older_ready = int(self._ro_prev is not None and self._ro_ahead is not None
-                                and self._ro_ahead == (next_obs.data_ptr(), next_priv.data_ptr()))
-        if ahead is not None:
-            a_obs, a_priv = ahead
-            assert a_obs.is_contiguous() and a_obs.shape == next_obs.shape and a_obs.data_ptr() != next_obs.data_ptr()
-            assert a_priv.is_contiguous() and a_priv.shape == next_priv.shape and a_priv.data_ptr() != next_priv.data_ptr()
-            o.obs_ahead, o.priv_ahead = L.fptr(a_obs), L.fptr(a_priv)
-        self._ro_ahead = None if ahead is None else (ahead[0].data_ptr(), ahead[1].data_ptr())
-        # the carried first layer rides with the rows-ahead protocol (the steady-state launch): ready if the previous launch formed the
-        # sums for exactly these rows, with the same shadow arrangement
-        l0 = self._ro_l0
-        if (l0 is not None and o.obs_older_ready and l0[0] == obs.data_ptr()
-                and l0[2] == (None if shadow is None else shadow[0].data_ptr())):
-            o.l0_ready = L.fptr(self._buf.l0_partial(l0[1]))
-        self._ro_l0 = None
-        if self._l0_ahead and ahead is not None and (shadow is None) == (shadow_next is None):
-            k = i & 1
-            o.l0_ahead = L.fptr(self._buf.l0_partial(k))
-            if shadow_next is not None:
-                assert shadow_next.dtype == torch.bfloat16 and shadow_next.is_contiguous() and shadow_next.shape[0] == self.num_envs
-                o.obs_bf16_ahead, o.ld_obs_bf16_ahead = C.c_void_p(shadow_next.data_ptr()), shadow_next.shape[-1]
-            self._ro_l0 = (next_obs.data_ptr(), k, None if shadow_next is None else shadow_next.data_ptr())
-        prev = self._ro_prev
+    def rollout_step(self, i):
+        """Launch i of the rollout (rollout_plan(...)[i]): actions / mu / sigma / logp / values of PPO.act into slot i, this env's
+        step on those actions with the observations written to slot i + 1, the transition sink of slot i stored by the finaliser
+        that rides in launch i + 1 (or in rollout_end).  The last launch uses the primary rew / reset / time_out buffers, so that
+        they read as after a plain step() once the rollout is over.  Rows ahead: this launch also writes the older frames of slot
+        i + 2 and the next one skips its copy; the carried first layer: it forms 20 of the 24 k-steps of the actor's first layer
+        for slot i + 1 (and those columns of its bf16 shadow), and the next launch starts from those sums.  Bit-identical outputs."""
+        L, net, c, p = self._L, self._ro_net, self._ro_cols, self._ro_plan[i]
+        if i != self._ro_i:
+            raise RuntimeError("fused rollout: launch %d is next, not %d" % (self._ro_i, i))
+        at = lambda name, s=i: None if c[name] is None else c[name][s]          # slot s of a column
+        l0 = lambda k: None if k is None else L.fptr(self._buf.l0_partial(k))
+        sink = dict(values=at("values"), rewards=at("rewards"), dones=at("dones"), time_outs=at("time_outs"), step=c["step"], gamma=c["gamma"])
+        o = self._buf.out_struct(at("obs", i + 1), at("priv", i + 1), sink, True, alt=bool(p.parity))
+        o.obs_older_ready, o.l0_ready, o.l0_ahead = int(p.obs_older_ready), l0(p.l0_ready), l0(p.l0_ahead)
+        if p.ahead is not None:
+            o.obs_ahead, o.priv_ahead = L.fptr(at("obs", p.ahead)), L.fptr(at("priv", p.ahead))
+        if p.bf16_ahead:
+            o.obs_bf16_ahead, o.ld_obs_bf16_ahead = C.c_void_p(at("obs_bf16", i + 1).data_ptr()), c["obs_bf16"].shape[-1]
+        sh = net.shadow_struct(at("obs_bf16"), at("priv_bf16") if p.shadow_priv else None) if p.shadow_obs else None
         L.check(L.lib.hgym_rollout_step(C.byref(net.cfg), C.byref(net.struct), C.byref(self._ncfg), C.byref(self._sim_s), C.byref(self._st_s),
-                                        C.byref(o), C.byref(prev[0]) if prev is not None else None, L.fptr(obs), L.fptr(priv),
-                                        int(seed) & 0xFFFFFFFFFFFFFFFF, L.fptr(out["actions"]), L.fptr(out["mu"]), L.fptr(out["sigma"]),
-                                        L.fptr(out["logp"]), L.fptr(out["values"]), C.c_void_p(self._buf.rollout_scratch.data_ptr()), parity,
+                                        C.byref(o), C.byref(self._ro_prev[0]) if p.prev else None, L.fptr(at("obs")), L.fptr(at("priv")),
+                                        int(c["seed"]) & 0xFFFFFFFFFFFFFFFF, L.fptr(at("actions")), L.fptr(at("mu")), L.fptr(at("sigma")),
+                                        L.fptr(at("logp")), L.fptr(at("values")), C.c_void_p(self._buf.rollout_scratch.data_ptr()), p.parity,
                                         None if sh is None else C.byref(sh), self._stream()), "hgym_rollout_step")
-        self._ro_prev = (o, parity, sink)          # keeps the struct (and the tensors it points at) alive for the next launch
-        self.obs_buf, self.privileged_obs_buf = next_obs, next_priv
+        self._ro_prev, self._ro_i = (o, p.parity), i + 1      # the struct is the next launch's prev_out (it points into the storage)
+        self.obs_buf, self.privileged_obs_buf = at("obs", i + 1), at("priv", i + 1)
 
     def rollout_end(self):
         """The finaliser of the last step on its own."""
-        o, parity, _ = self._ro_prev
+        o, parity = self._ro_prev
         self._L.check(self._L.lib.hgym_rollout_end(C.byref(self._ncfg), C.byref(self._st_s), C.byref(o), C.c_void_p(self._buf.rollout_scratch.data_ptr()),
                                                    parity, self._stream()), "hgym_rollout_end")
         self._ro_prev = None

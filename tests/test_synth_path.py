@@ -165,15 +165,9 @@ def test_rollout_step_env_part_vs_oracle_gpu(monkeypatch, ahead):
     priv_all[0].copy_(env.get_privileged_observations())
     alg.env_stores_transitions = True
     with torch.inference_mode():
-        env.rollout_begin(alg._sample_step, T)
-        obs, pobs = obs_all[0], priv_all[0]
-        for i in range(T):
-            # ahead: the launch also writes the older frames of the slot after next (HgymEnvOut.obs_ahead) and the next one skips
-            # its own copy -- the rows compared below are produced by a different launch, and must not differ
-            alg.fused_rollout_step(env, i, obs, pobs, obs_all[i + 1], priv_all[i + 1],
-                                   (obs_all[i + 2], priv_all[i + 2]) if (ahead and i + 2 <= T) else None)
-            obs, pobs = obs_all[i + 1], priv_all[i + 1]
-        env.rollout_end()
+        # rows ahead: each launch also writes the older frames of the slot after next (HgymEnvOut.obs_ahead) and the next one skips
+        # its own copy -- the rows compared below are produced by a different launch, and must not differ
+        alg.fused_rollout_step(env, T, rows_ahead=ahead)
     torch.cuda.synchronize()
     flips = [0]
     counts = dict(reset=0, timeout=0, push=0, boot=0)
@@ -333,12 +327,7 @@ def test_deferred_values_rollout_vs_oracle_gpu(monkeypatch, N):
     priv_all[0].copy_(env.get_privileged_observations())
     alg.env_stores_transitions = True
     with torch.inference_mode():
-        env.rollout_begin(alg._sample_step, T)
-        obs, pobs = obs_all[0], priv_all[0]
-        for i in range(T):
-            alg.fused_rollout_step(env, i, obs, pobs, obs_all[i + 1], priv_all[i + 1], deferred=True)
-            obs, pobs = obs_all[i + 1], priv_all[i + 1]
-        env.rollout_end()
+        alg.fused_rollout_step(env, T, deferred=True)
         torch.cuda.synchronize()
         raw = st.rewards.clone()
         assert float(st.values.abs().max()) == 0.0           # nothing has evaluated the critic yet

@@ -21,20 +21,19 @@ torch.cuda.synchronize()
 nb = N // 32
 buf = torch.zeros(nb * 3 * 8, dtype=torch.int64, device="cuda")
 L.check(L.lib.hgym_prof_phase_buffer(C.c_void_p(buf.data_ptr()), buf.numel()))
-alg, st = runner.alg, runner.alg.storage
-obs_all, priv_all = st._obs_all, st._priv_all
+alg = runner.alg
 alg.env_stores_transitions = True
 # HGYM_PROBE_BURST=K: K launches back to back without a host synchronisation in between (as the captured graph runs them: every
 # launch finds the caches the way the previous one left them), the phase clock of the LAST one; default: 4 launches, a
 # synchronisation behind each
 BURST = int(os.environ.get("HGYM_PROBE_BURST", "0"))
 NS = BURST if BURST > 0 else 4
-env.rollout_begin(alg._sample_step, NS)
+env.rollout_begin(alg.net, alg.rollout_columns(False), NS + 1)       # (planned one launch longer: every launch run writes rows ahead)
 acc = []
 for i in range(NS):
     if BURST == 0:
         buf.zero_()
-    alg.fused_rollout_step(env, i, obs_all[i], priv_all[i], obs_all[i + 1], priv_all[i + 1], (obs_all[i + 2], priv_all[i + 2]))
+    env.rollout_step(i)
     if BURST == 0:
         torch.cuda.synchronize()
         acc.append(buf.clone())
@@ -42,7 +41,6 @@ torch.cuda.synchronize()
 if BURST > 0:
     acc = [None, buf.clone()]
 env.rollout_end()
-st.step = 0
 L.check(L.lib.hgym_prof_phase_buffer(None, 0))
 FWD = ["input0+draws", "layer0 k-loop", "epilogue0+sync", "layer1+sync", "layer2+sync", "head"]
 ENV = ["hist stores", "joints+sync", "per-env chain+sync", "stage-out", "phase B"]
