@@ -424,8 +424,9 @@ __device__ __forceinline__ float log_sigma(float s) { return __fmul_rn(__builtin
 // ---- the actor's first layer carried ACROSS launches of the rollout (round 4) ----------------------------------------------------
 // An observation row is a stack of frames: the row of step t + 1 is the row of step t shifted by one frame (47 columns) plus the
 // frame step t produces, so columns [0, 640) of the NEXT row -- 20 of the first layer's 24 k-steps -- are known when launch t starts.
-// Launch t's critic workgroup of the tile (idle from ~16 us of the ~40 us launch on) forms those 20 k-steps of the actor's first
-// layer for the next row (`l0_partial_ahead`) and leaves the fp32 accumulators in the caller's scratch; launch t + 1's actor tile
+// Launch t's critic workgroup of the tile (idle from ~16 us of the ~40 us launch on; in the 64-row layout of the steady-state launch
+// the side-job workgroup of two tiles) forms those k-steps of the actor's first layer for the next row (`l0_partial_ahead`) and
+// leaves the fp32 accumulators in the caller's scratch; launch t + 1's actor tile
 // (`fwd_body<.., PART>`) starts from them and runs the last 128-column chunk only: the same fragments, the same k order, the same
 // accumulator chain -- the pre-activations are bit-identical -- and 8 of the first layer's 9.5 us leave the launch's critical path.
 // Rows whose env was reset in between have zero older frames: their partial sums are dropped (0 + the chunk's products, as the
@@ -443,21 +444,23 @@ struct L0Ahead {
     int kb0;                 // k-steps formed ahead
 };
 
-// by ALL 8 wavefronts of a 32-row workgroup whose own tile is finished (the caller has synchronised): rows m0 .. m0 + 31 of net n's fp32
-// input, columns [shift, shift + 32 kb0) -> bf16 (the rounding fwd_body's staging applies) -> LDS block layout -> k-steps [0, kb0) of
-// the first layer with fwd_body<32, 8, 4, G1>'s wave -> strip mapping -> acc_out.  kb0 % 4 == 0.
-template <int G1>
-__device__ __forceinline__ void l0_partial_ahead(const FusedNet& n, const L0Ahead& ah, int M, char* smem) {
-    constexpr int BM = 32, NW = 8, MB = 2, D = 4;
+// by ALL 8 wavefronts of a workgroup (the caller has synchronised if the workgroup ran a tile of its own before): rows
+// tile * BM .. tile * BM + BM - 1 of net n's fp32 input, columns [shift, shift + 32 kb0) -> bf16 (the rounding fwd_body's staging
+// applies) -> LDS block layout -> k-steps [0, kb0) of the first layer with fwd_body<32, 8, 4, G1>'s wave -> strip mapping -> acc_out,
+// in the layout of the 32-row actor tiles that consume it (a 64-row call streams the weights once for two of them).  kb0 % 4 == 0.
+template <int G1, int BM = 32>
+__device__ __forceinline__ void l0_partial_ahead(const FusedNet& n, const L0Ahead& ah, int M, char* smem, int tile) {
+    static_assert(BM == 32 || BM == 64, "whole 32-row actor tiles");
+    constexpr int NW = 8, MB = BM / 16, D = 4;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int m0 = blockIdx.x * BM;
+    const int m0 = tile * BM;
     const FusedLayer& L0 = n.layer[0];
     const int CB = 2 * ah.kb0, groups = 8 * ah.kb0;          // column blocks of 16 / groups of 4 columns per row
     const int nb0 = wave * G1;
     WRing<G1, D> r0;
     const u32x4* wl0 = L0.Wf + (int64_t)nb0 * L0.KB * 64 + lane;
     wring_prime<G1, D>(r0, wl0, L0.KB * 64, ah.kb0);
-    constexpr int IPR = 5;                                       // items per lane per round: (row, 4 consecutive new columns)
+    constexpr int IPR = 5 * BM / 32;                             // items per lane per round: (row, 4 consecutive new columns)
     for (int j0 = 0; j0 < BM * groups; j0 += NW * 64 * IPR) {
         F4 v[IPR];
         int row[IPR], c4[IPR];
@@ -483,11 +486,13 @@ __device__ __forceinline__ void l0_partial_ahead(const FusedNet& n, const L0Ahea
     f32x4 acc[MB][G1];
     zero_acc<G1, MB>(acc);
     mma_stream<G1, MB, D, 1>(r0, wl0, L0.KB * 64, ah.kb0, smem, CB, lane, acc);
-    f32x4* dst = reinterpret_cast<f32x4*>(ah.acc_out) + ((int64_t)(blockIdx.x * NW + wave) * (MB * G1)) * 64 + lane;
+    // row block i belongs to 32-row tile tile * BM / 32 + i / 2, where it is that tile's row block i % 2
 #pragma unroll
-    for (int i = 0; i < MB; ++i)
+    for (int i = 0; i < MB; ++i) {
+        f32x4* dst = reinterpret_cast<f32x4*>(ah.acc_out) + ((int64_t)((tile * (BM / 32) + i / 2) * NW + wave) * (2 * G1) + (i & 1) * G1) * 64 + lane;
 #pragma unroll
-        for (int g = 0; g < G1; ++g) dst[(i * G1 + g) * 64] = acc[i][g];
+        for (int g = 0; g < G1; ++g) dst[g * 64] = acc[i][g];
+    }
 }
 
 struct FwdArgs {
@@ -534,19 +539,21 @@ template <int BM, int NW, int D, int G1, bool WIDE = false, bool XB16 = false, b
 __device__ __forceinline__ void fwd_body(const FwdArgs& a, const FusedNet& n, bool is_actor, char* smem, Early&& hook_early = Early(),
                                          Mid&& hook_mid = Mid(), Put&& hook_put = Put(), const Extra& extra = Extra(),
                                          Idle&& hook_idle = Idle(), Head&& hook_head = Head(), char* h2_lds = nullptr,
-                                         int* rowidx_lds = nullptr, L2Idle&& hook_l2idle = L2Idle(), const L0Part* part = nullptr) {
+                                         int* rowidx_lds = nullptr, L2Idle&& hook_l2idle = L2Idle(), const L0Part* part = nullptr,
+                                         int tile = -1) {
     // PART (the rollout's actor tile, hgym_rollout.hip): the first layer starts from the partial sums *part and runs chunks
     // [part->kb0 / 4, NC) only (struct L0Part above)
     static_assert(!PART || !XB16, "the carried first layer exists for fp32 input rows only");
     // rowidx_lds (BM ints of LDS): receives the storage row of every tile row (a.idx gathered once, by the lanes that stage the
     // input) for whoever needs it later in the tile; hook_l2idle(extra): runs on the wavefronts that have no strip in the third
     // layer while the others compute it (the fused forward + backward kernel gathers its loss inputs there).
+    // tile: the BM-row tile this workgroup computes (-1: blockIdx.x; the rollout's 64-row critic tiles sit at other grid columns)
     constexpr int MB = BM / 16;
     constexpr int IT = BM * 32 / (NW * 64);           // staging items per thread per chunk (BM rows x 32 float4)
     constexpr int RPP = NW * 2;                       // rows covered per staging pass (32 lanes per row)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 15, q = lane >> 4;
-    const int m0 = blockIdx.x * BM;
+    const int m0 = (tile < 0 ? (int)blockIdx.x : tile) * BM;
     const int64_t mbg0 = m0 >> 4;
     char* P = smem;
     char* Q = smem + fused_lds_p(n, BM);

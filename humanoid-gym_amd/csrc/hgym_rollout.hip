@@ -9,6 +9,8 @@
 //                                            32 envs, fed with the tile's sampled actions through LDS;
 //                             blockIdx.y = 1: CRITIC tile (values of the transition being collected);
 //                             blockIdx.y = 2: the finaliser of the PREVIOUS env step, one workgroup.
+//                             (rows 0 and 1 trade places on odd columns; in the steady-state launch the non-actor workgroups are
+//                             64-row critic tiles and side-job workgroups instead, rollout_step_kernel below)
 //
 //   actor workgroup timeline  issue {bias, first weight k-steps, first input chunk} | issue the env step's state / sim loads |
 //   Philox draws of the env step (ALU under all of those loads) | layer 0 | issue the loads of the 14 + 2 older history frames
@@ -91,6 +93,8 @@ constexpr int RO_NIP = hist_ni<3, HGYM_PRIV_FRAME, RO_E, RO_NT>();
 // (profiles/r05a_bench_ab_base_rofast_dw32.txt).
 constexpr int RO_NIA_C = hist_ni<15, HGYM_OBS_FRAME, RO_E, RO_NT, 2>();
 constexpr int RO_NIAP_C = hist_ni<3, HGYM_PRIV_FRAME, RO_E, RO_NT, 2>();
+constexpr int RO_NIA64 = hist_ni<15, HGYM_OBS_FRAME, 2 * RO_E, RO_NT, 2>();
+constexpr int RO_NIAP64 = hist_ni<3, HGYM_PRIV_FRAME, 2 * RO_E, RO_NT, 2>();
 constexpr int RO_CHAIN = 64 * kChainRoles;     // lanes of the per-env chain: four wavefronts by role (env_step_phase_a3)
 
 // PRE (HgymEnvOut.obs_older_ready): the 14 older frames of this launch's stacked observation rows were written by the previous launch
@@ -101,9 +105,12 @@ constexpr int RO_CHAIN = 64 * kChainRoles;     // lanes of the per-env chain: fo
 // NOCRITIC (hgym_rollout_step with values = NULL, header v7): no critic tiles -- grid rows = the actor + env workgroups and the
 // finaliser; the critic runs once over the stored rows after the rollout (hgym_critic_values).  With PRE = PART = false the actor
 // workgroup draws its own random numbers and copies its own history rows, as in the first launch of a rollout.
-template <bool FIN, bool PRE, bool PART = false, bool NOCRITIC = false>
+// C64: the non-actor workgroups in the 64-row layout (see below), instantiated for the steady-state launch (PART) only -- one code
+// object for both layouts of every form would exceed the kernel size guard (build.py), and the other forms run once per rollout.
+template <bool FIN, bool PRE, bool PART = false, bool NOCRITIC = false, bool C64 = false>
 __global__ __launch_bounds__(RO_NT) void rollout_step_kernel(const FwdArgs f, const EnvArgs e, const FinArgs fin, const RolloutPP pp) {
     static_assert(!NOCRITIC || (!PRE && !PART), "rows ahead and the carried first layer are the critic workgroups' side jobs");
+    static_assert(!C64 || (PRE && PART), "the 64-row layout is instantiated for the steady-state launch");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     if (FIN && blockIdx.y >= (NOCRITIC ? 1 : 2)) {
         // (phase clock: slot 6 of the env row = when this workgroup of the third grid row started, slot 7 of block 0 = the finaliser's end)
@@ -119,6 +126,47 @@ __global__ __launch_bounds__(RO_NT) void rollout_step_kernel(const FwdArgs f, co
     // actor and critic workgroups alternate in dispatch order (tile b: row 0 holds its actor when b is even, its critic when b
     // is odd), so that the long actor + env workgroups are spread evenly over neighbouring compute units
     const bool critic_wg = !NOCRITIC && ((blockIdx.x + blockIdx.y) & 1) != 0;
+    if constexpr (C64) if (critic_wg) {
+        // 64-row layout: the non-actor workgroup of grid column x serves the 64 rows of tiles 2 (x / 2) and
+        // 2 (x / 2) + 1, as their CRITIC tile or as their SIDE-JOB workgroup.  A tile's time is its weight stream, not its rows, so
+        // one 64-row critic tile costs about what a 32-row one did, and the side jobs get a workgroup of their own.  Of the two
+        // columns of a pair one is the critic and one the side job, and the choice flips every 8 columns, so that each XCD (column
+        // x mod 8 in both grid rows) receives as many of each role as of the other.
+        const int b = (int)blockIdx.x >> 1;
+        const bool side = (((int)blockIdx.x ^ ((int)blockIdx.x >> 3)) & 1) != 0;
+        // side jobs of rows [64 b, 64 b + 64), in the order the critic workgroup of the 32-row layout runs them: the rows after next
+        // (loads issued first, they travel while the draws are computed), the next step's draws, the copy's stores, then the actor's
+        // first layer ahead, under whose weight loads the stores are acknowledged.  The critic workgroup, shorter by the first
+        // layer ahead, computes the draws of the first of the two tiles behind its own tile, the side-job workgroup those of the second.
+        float ha[RO_NIA64][4], hp[RO_NIAP64][4];
+        const int ring_s = (int)pp.in[1];
+        if (!side) {
+            fwd_body<2 * RO_E, 8, 2, 3 * U>(f, f.net[1], false, smem, FwdNoop(), FwdNoop(), FwdNoop(), 0, FwdNoop(), FwdNoop(), nullptr,
+                                            nullptr, FwdNoop(), nullptr, b);
+        } else {
+            phase_stamp(f.dbg, 0);
+            hist_load<15, HGYM_OBS_FRAME, RO_NIA64, 2>(e.st.obs_ring, b * 2 * RO_E, 2 * RO_E, ring_s % 15, (int)threadIdx.x, RO_NT, ha);
+            hist_load<3, HGYM_PRIV_FRAME, RO_NIAP64, 2>(e.st.priv_ring, b * 2 * RO_E, 2 * RO_E, ring_s % 3, (int)threadIdx.x, RO_NT, hp);
+        }
+        if (pp.draws_out) {
+            const int tile = 2 * b + (side ? 1 : 0);
+            float* base = pp.draws_out + (int64_t)tile * pp.draws_len - lds_map(RO_E).u_delay;
+            env_fill_draws<RO_E>(e, tile, (int)threadIdx.x, RO_NT, base, pp.in[0] + 1);
+        }
+        if (side) {
+            phase_stamp(f.dbg, 1);
+            if (e.out.obs_ahead) {
+                hist_store<15, HGYM_OBS_FRAME, RO_NIA64, 2>(e.out.obs_ahead, b * 2 * RO_E, 2 * RO_E, ring_s % 15, (int)threadIdx.x, RO_NT, nullptr,
+                                                            e.cfg.clip_obs, ha);
+                hist_store<3, HGYM_PRIV_FRAME, RO_NIAP64, 2>(e.out.priv_ahead, b * 2 * RO_E, 2 * RO_E, ring_s % 3, (int)threadIdx.x, RO_NT, nullptr,
+                                                             e.cfg.clip_obs, hp);
+            }
+            phase_stamp(f.dbg, 2);
+            if (pp.ah.acc_out) l0_partial_ahead<2 * U, 2 * RO_E>(f.net[0], pp.ah, f.M, smem, b);
+        }
+        phase_stamp(f.dbg, 7);
+        return;
+    }
     if (critic_wg) {                                // critic tile
         // one instantiation only (first hidden layer 768 wide, rollout_fwd_args checks): with the three-way dispatch of
         // mlp_fwd_kernel next to the actor + env branch the compiler keeps a private-memory copy of the whole 3 KB argument
@@ -142,7 +190,7 @@ __global__ __launch_bounds__(RO_NT) void rollout_step_kernel(const FwdArgs f, co
         }
         if (pp.ah.acc_out) {     // k-steps [0, kb0) of the ACTOR's first layer for the next step's rows of this tile
             __syncthreads();     // (the head wavefronts of this tile may still read its LDS)
-            l0_partial_ahead<2 * U>(f.net[0], pp.ah, f.M, smem);
+            l0_partial_ahead<2 * U>(f.net[0], pp.ah, f.M, smem, (int)blockIdx.x);
         }
         phase_stamp(f.dbg, 7);
         return;
@@ -261,6 +309,15 @@ __global__ void rollout_begin_kernel(const int64_t* __restrict__ counters, const
 
 __global__ __launch_bounds__(1024) void rollout_fin_kernel(const FinArgs f) { fin_block(f, threadIdx.x, blockDim.x); }
 
+// Role layout of the launch's non-actor workgroups: 64-row critic tiles next to side-job workgroups (rollout_step_kernel) wherever the
+// launch has critic tiles and the 32-row tiles pair up; HGYM_RO_CRITIC64=0 keeps the 32-row critic tiles that carry the side jobs
+// themselves (A/B runs).  Both layouts compute the same bits.
+static bool rollout_critic64(int M, bool nocritic) {
+    const char* v = getenv("HGYM_RO_CRITIC64");       // (read per call, as HGYM_L0_KB0)
+    if (v && atoi(v) == 0) return false;
+    return !nocritic && M >= 4 * RO_E && (M / RO_E) % 2 == 0;
+}
+
 static FinArgs parity_fin(const HgymEnvConfig& cfg, const HgymEnvState& st, const HgymEnvOut& out, RolloutScratch* scr, int parity) {
     FinArgs f = make_fin_args(cfg, st, out, FIN_MODE_STEP);
     f.reset_count = &scr->reset_cnt[parity];
@@ -343,14 +400,22 @@ int32_t hgym_rollout_step(const HgymNetConfig* cfg, const HgymNet* net, const Hg
     memset(&pp.l0, 0, sizeof(pp.l0));
     memset(&pp.ah, 0, sizeof(pp.ah));
     const bool part = out->l0_ready != nullptr;
+    // the layout is chosen per env count, so that the k-steps carried ahead agree between the launch that forms them and the next;
+    // the steady-state launch (part) runs it, the first launch of a rollout keeps the 32-row critic tiles
+    const bool critic64 = rollout_critic64(M, nocritic);
+    const bool c64 = critic64 && part;
+    int kb0_ahead = 0;
     {   // first layer of the actor carried across launches (HgymEnvOut.l0_ahead / l0_ready)
-        // k-steps formed ahead: whole 128-column chunks, at most 20 (640 of the 658 columns of the 14 older frames).  12 by default:
-        // the critic workgroup pays for every k-step it takes over at the same L2 -> CU fill rate, and with all 20 it becomes the
-        // launch's longest workgroup (profiles/r04_l0_ahead_ab.txt: collection 2.33 -> 2.27 ms with 12, 2.30 with 20, 2.34 with 8).
-        // HGYM_L0_KB0 tunes the split (A/B runs).
+        // k-steps formed ahead: whole 128-column chunks, at most 20 (640 of the 658 columns of the 14 older frames).  With 32-row critic
+        // tiles 12 by default: the critic workgroup pays for every k-step it takes over at the same L2 -> CU fill rate, and with all 20
+        // it becomes the launch's longest workgroup (profiles/r04_l0_ahead_ab.txt: collection 2.33 -> 2.27 ms with 12, 2.30 with 20,
+        // 2.34 with 8).  With 64-row critic tiles the side-job workgroup carries them, one weight stream for two actor tiles: all 20
+        // (DESIGN.md section 13).  HGYM_L0_KB0 tunes the split (A/B runs).
+        const int kb0_def = critic64 ? 20 : 12;
         const char* kb0_env = getenv("HGYM_L0_KB0");          // (read per call: the tests run several splits in one process)
-        const int kb0_v = kb0_env ? atoi(kb0_env) : 12;
-        const int KB0_AHEAD = (kb0_v >= 4 && kb0_v <= 20 && kb0_v % 4 == 0) ? kb0_v : 12;
+        const int kb0_v = kb0_env ? atoi(kb0_env) : kb0_def;
+        const int KB0_AHEAD = (kb0_v >= 4 && kb0_v <= 20 && kb0_v % 4 == 0) ? kb0_v : kb0_def;
+        kb0_ahead = KB0_AHEAD;
         HG_REQUIRE(!part || prev_out, HGYM_E_BADARG, "l0_ready on the first step of a rollout: no launch has left partial sums");
         HG_REQUIRE(!(part || out->l0_ahead) || (f.net[0].layer[0].KB == 24 && f.net[0].layer[0].N == 512 && HGYM_OBS_FRAME * 14 >= 32 * KB0_AHEAD),
                    HGYM_E_UNSUPPORTED, "the carried first layer is built for XBot-L's 15 x 47 -> 512 actor input");
@@ -372,7 +437,11 @@ int32_t hgym_rollout_step(const HgymNetConfig* cfg, const HgymNet* net, const Hg
         }
     }
     f.dbg = phase_buffer((int64_t)(M / RO_E) * 3);
-    const size_t lds = (size_t)pp.env_lds_off + step_smem_bytes(RO_E);
+    size_t lds = (size_t)pp.env_lds_off + step_smem_bytes(RO_E);
+    if (c64) {               // the 64-row critic tile's buffers; the side jobs' first-layer staging (64 rows x 32 kb0 bf16 columns)
+        lds = std::max(lds, (size_t)fwd_lds_bytes(f.net[1], 2 * RO_E));
+        if (out->l0_ahead) lds = std::max(lds, (size_t)2 * RO_E * 32 * kb0_ahead * 2);
+    }
     const bool pre = out->obs_older_ready != 0;
     HG_REQUIRE(!pre || prev_out, HGYM_E_BADARG, "obs_older_ready on the first step of a rollout: no launch has written those frames");
     HG_REQUIRE(!part || pre, HGYM_E_UNSUPPORTED, "l0_ready is built together with obs_older_ready (the steady-state launch)");
@@ -382,6 +451,7 @@ int32_t hgym_rollout_step(const HgymNetConfig* cfg, const HgymNet* net, const Hg
     {
         const void* fn = nocritic ? (prev_out ? reinterpret_cast<const void*>(&rollout_step_kernel<true, false, false, true>)
                                               : reinterpret_cast<const void*>(&rollout_step_kernel<false, false, false, true>))
+                       : c64 ? reinterpret_cast<const void*>(&rollout_step_kernel<true, true, true, false, true>)
                        : part ? reinterpret_cast<const void*>(&rollout_step_kernel<true, true, true>)
                        : pre ? reinterpret_cast<const void*>(&rollout_step_kernel<true, true>)
                              : (prev_out ? reinterpret_cast<const void*>(&rollout_step_kernel<true, false>)
@@ -393,6 +463,7 @@ int32_t hgym_rollout_step(const HgymNetConfig* cfg, const HgymNet* net, const Hg
     prof_begin(HGYM_PROF_ROLLOUT, s);
     if (nocritic && prev_out) hipLaunchKernelGGL((rollout_step_kernel<true, false, false, true>), dim3(M / RO_E, 2), dim3(RO_NT), lds, s, f, e, fin, pp);
     else if (nocritic) hipLaunchKernelGGL((rollout_step_kernel<false, false, false, true>), dim3(M / RO_E, 1), dim3(RO_NT), lds, s, f, e, fin, pp);
+    else if (c64) hipLaunchKernelGGL((rollout_step_kernel<true, true, true, false, true>), dim3(M / RO_E, 3), dim3(RO_NT), lds, s, f, e, fin, pp);
     else if (part) hipLaunchKernelGGL((rollout_step_kernel<true, true, true>), dim3(M / RO_E, 3), dim3(RO_NT), lds, s, f, e, fin, pp);
     else if (pre) hipLaunchKernelGGL((rollout_step_kernel<true, true>), dim3(M / RO_E, 3), dim3(RO_NT), lds, s, f, e, fin, pp);
     else if (prev_out) hipLaunchKernelGGL((rollout_step_kernel<true, false>), dim3(M / RO_E, 3), dim3(RO_NT), lds, s, f, e, fin, pp);

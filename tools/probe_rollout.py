@@ -51,7 +51,25 @@ for i, b in enumerate(acc[1:], NS - 1 if BURST > 0 else 1):
         a_, c_ = t[0].clone(), t[1].clone()
         a_[odd], c_[odd] = t[1][odd], t[0][odd]
         t = torch.stack([a_, c_, t[2]])
+    c64 = os.environ.get("HGYM_RO_CRITIC64", "1") != "0" and nb % 2 == 0 and N >= 128
+    if c64:
+        # 64-row layout (steady-state launches): the non-actor workgroup of column x is the critic tile of rows [64 (x / 2), + 64) when
+        # (x ^ x / 8) is even, else those rows' side jobs -- stamps 0 start, 1 rows-after-next loads + draws, 2 their stores, 7 end
+        x = torch.arange(nb)
+        crit, side = t[1][((x ^ (x >> 3)) & 1) == 0], t[1][((x ^ (x >> 3)) & 1) == 1]
+        d = crit
+        print("step %d %-28s block mean %.1f us: " % (i, "critic (64 rows)", (d[:, 6] - d[:, 0]).mean().item()) +
+              ", ".join("%s %.1f" % (n, (d[:, k + 1] - d[:, k]).mean().item()) for k, n in enumerate(FWD)) +
+              " | workgroup mean %.1f max %.1f" % ((d[:, 7] - d[:, 0]).mean().item(), (d[:, 7] - d[:, 0]).max().item()))
+        d = side
+        print("step %d %-28s workgroup mean %.1f us, max %.1f: loads+draws %.1f, rows-after-next stores %.1f, first layer ahead %.1f" % (
+            i, "side jobs (64 rows)", (d[:, 7] - d[:, 0]).mean().item(), (d[:, 7] - d[:, 0]).max().item(), (d[:, 1] - d[:, 0]).mean().item(),
+            (d[:, 2] - d[:, 1]).mean().item(), (d[:, 7] - d[:, 2]).mean().item()))
+        t0 = t[0][:, 0].min()
+        print("step %d   critic end offsets: max %.1f | side-job end offsets: max %.1f" % (i, (crit[:, 7] - t0).max().item(), (side[:, 7] - t0).max().item()))
     for row, tag, names in ((0, "actor", FWD), (1, "critic", FWD), (2, "env (behind the actor tile)", ENV)):
+        if c64 and row == 1:
+            continue
         d = t[row]
         segs = [(d[:, k + 1] - d[:, k]).mean().item() for k in range(len(names))]
         print("step %d %-28s block mean %.1f us: " % (i, tag, (d[:, len(names)] - d[:, 0]).mean().item()) +
