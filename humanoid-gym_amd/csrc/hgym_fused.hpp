@@ -1267,6 +1267,14 @@ struct ScalArgs {
                            // consecutive rows are added first, ((p0 + p1) + p2) + p3 in fp32 -- the sum mlp_fb_kernel's 64-row tile forms
                            // over its four head waves -- and nblocks counts those groups
 };
+// ppo.py:140-145, the one copy of the rule (ppo_scalars_block here, apply_prologue in hgym_net.hip).  The reference compares the fp32
+// 0-dim tensor kl_mean with python floats, which torch rounds to fp32: the comparisons are fp32 ones against float32(desired_kl * 2) and
+// float32(desired_kl / 2) -- 2 * desired_kl and desired_kl / 2 of the fp32 field, exactly -- while the learning rate is a python double.
+__device__ __forceinline__ double adapt_lr(double lr, float kl, float desired_kl, double lr_min, double lr_max) {
+    if (kl > desired_kl * 2.0f) return fmax(lr_min, lr / 1.5);
+    if (kl < desired_kl * 0.5f && kl > 0.0f) return fmin(lr_max, lr * 1.5);
+    return lr;
+}
 __device__ __forceinline__ void ppo_scalars_block(const ScalArgs& a, int tid, int nthreads) {
     __shared__ double red[16][LOSS_PARTIALS + 1];
     // beta1^t, beta2^t for hgym_ppo_apply's prologue: two double-precision pow() are ~6 us in that single-thread kernel, on the
@@ -1320,17 +1328,16 @@ __device__ __forceinline__ void ppo_scalars_block(const ScalArgs& a, int tid, in
         if (q == 1) opt[4] += t / B;
         if (q == 2) opt[5] += t / B;
         if (q == 3) {
+            const float kl = (float)(t / B);  // the reference's kl_mean is an fp32 tensor: the decision, here and in apply_prologue, is taken on it
             opt[2] += t / B;
-            opt[8] = t / B;
+            opt[8] = (double)kl;
             opt[7] += 1.0;
             opt[9] = 0.0;                     // squared gradient norm: accumulated by reduce_slabs_kernel later in this call
-            a.kl_slot[0] = (float)(t / B);    // grads[P]: travels with the gradient in the ranks' one all-reduce
-            if (a.do_prologue && !(opt[13] == opt[1] && opt[1] > 0.0)) {      // apply_prologue_kernel's arithmetic (hgym_net.hip), one rank: ppo.py:140-148 in python doubles
+            a.kl_slot[0] = kl;                // grads[P]: travels with the gradient in the ranks' one all-reduce
+            if (a.do_prologue && !(opt[13] == opt[1] && opt[1] > 0.0)) {      // apply_prologue_kernel's arithmetic (hgym_net.hip), one rank: ppo.py:140-148
                 double lr = opt[0];
                 if (a.adaptive_lr) {
-                    const double kl = t / B;
-                    if (kl > (double)a.desired_kl * 2.0) lr = fmax(a.lr_min, lr / 1.5);
-                    else if (kl < (double)a.desired_kl / 2.0 && kl > 0.0) lr = fmin(a.lr_max, lr * 1.5);
+                    lr = adapt_lr(lr, kl, a.desired_kl, a.lr_min, a.lr_max);
                     opt[0] = lr;
                 }
                 const double ts = opt[1] + 1.0;           // (= opt[13]: the two lanes above prepared beta^ts before the barrier)

@@ -580,7 +580,7 @@ __global__ __launch_bounds__(256) void reduce_slabs_kernel(const SegTable tab, i
 // (inv_w: 1 / world_size -- with several ranks the gradient vector holds the all-reduced SUM and the mean is formed in sqnorm_prologue_kernel and in
 // adam_kernel: an fp32 product, what `grad.mul_(1 / world)` would have stored; 1.0f for one rank, which is exact.)
 
-// ppo.py:140-148 (adaptive-KL learning rate, python-double arithmetic) + Adam step counter + the squared norm Adam will clip with: `sq` when
+// ppo.py:140-148 (adaptive-KL learning rate: adapt_lr, hgym_fused.hpp) + Adam step counter + the squared norm Adam will clip with: `sq` when
 // this call determined it itself (sqnorm_prologue_kernel), 0 when a norm pass follows, untouched when the gradient call left it (have_sq < 0)
 __device__ __forceinline__ void apply_prologue(const HgymPPOConfig& p, const float* __restrict__ kl_slot, float inv_w, double* __restrict__ opt,
                                                int have_sq, double sq) {
@@ -589,13 +589,7 @@ __device__ __forceinline__ void apply_prologue(const HgymPPOConfig& p, const flo
         if (have_sq >= 0) opt[9] = have_sq ? sq : 0.0;                // caller applies with another configuration: not a second time
         return;
     }
-    if (p.adaptive_lr) {
-        const double kl = opt[8];
-        double lr = opt[0];
-        if (kl > (double)p.desired_kl * 2.0) lr = fmax(p.lr_min, lr / 1.5);
-        else if (kl < (double)p.desired_kl / 2.0 && kl > 0.0) lr = fmin(p.lr_max, lr * 1.5);
-        opt[0] = lr;
-    }
+    if (p.adaptive_lr) opt[0] = adapt_lr(opt[0], (float)opt[8], p.desired_kl, p.lr_min, p.lr_max);      // (opt[8] as the caller left it: rounded)
     const double t = opt[1] + 1.0;
     opt[1] = t;
     // Adam's bias corrections, once per step instead of two double-precision pow() per thread of adam_kernel (1.1 M threads): the

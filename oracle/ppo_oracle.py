@@ -17,6 +17,7 @@ the reference is torch fp32 code (same primitive kernels => tight pin).
 """
 import math
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -211,11 +212,13 @@ def ppo_loss_and_grads(p, obs, priv, actions, old_values, adv, returns, old_logp
 
 
 def adapt_lr(lr, kl, desired_kl=0.01):
-    """ppo.py:142-145 (python-double learning rate)."""
-    kl = float(kl)
-    if kl > desired_kl * 2.0:
+    """ppo.py:142-145 (python-double learning rate).  The reference compares the fp32 0-dim tensor kl_mean with python floats: torch
+    rounds the float to the tensor's dtype, so the comparisons are fp32 ones against float32(desired_kl * 2) and float32(desired_kl / 2)
+    (at kl == float32(0.005) < 0.005 the rate is kept, not raised)."""
+    kl = np.float32(float(kl))
+    if kl > np.float32(desired_kl * 2.0):
         return max(1e-5, lr / 1.5)
-    if kl < desired_kl / 2.0 and kl > 0.0:
+    if kl < np.float32(desired_kl / 2.0) and kl > np.float32(0.0):
         return min(1e-2, lr * 1.5)
     return lr
 
