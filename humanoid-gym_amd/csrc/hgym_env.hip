@@ -118,6 +118,69 @@ __global__ __launch_bounds__(1024) void command_curriculum_kernel(const EnvArgs 
     for (int e = threadIdx.x; e < A.cfg.num_envs; e += blockDim.x) command_curriculum_fix_env(A, rk, e, xr[0], xr[1], ring_step);
 }
 
+// ---- hgym_env_reset_idx: LeggedRobot.reset_idx(env_ids) for a subset of envs, three launches (four with the command curriculum) ---
+// 1. the per-env mask from the id list (one workgroup: clear every byte, barrier, mark the listed envs; ids outside [-N, N) are
+//    counted, never dereferenced)
+__global__ __launch_bounds__(1024) void reset_idx_mask_kernel(const int64_t* ids, int n_ids, int N, uint8_t* mask, int64_t* rejected) {
+    __shared__ int bad;
+    if (threadIdx.x == 0) bad = 0;
+    for (int i = threadIdx.x; i < N; i += blockDim.x) mask[i] = 0;
+    __syncthreads();
+    int mine = 0;
+    for (int i = threadIdx.x; i < n_ids; i += blockDim.x) mine += reset_idx_mark(mask, ids, i, N) ? 0 : 1;
+    if (mine) atomicAdd(&bad, mine);
+    __syncthreads();
+    if (threadIdx.x == 0) rejected[0] = bad;
+}
+
+// 2. one lane per env: the reset branch for the marked envs; then the workgroup zeroes their history rows together
+__global__ __launch_bounds__(256) void reset_idx_kernel(const EnvArgs A, const uint8_t* mask) {
+    __shared__ int list[256];
+    __shared__ int n;
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (threadIdx.x == 0) n = 0;
+    __syncthreads();
+    if (e < A.cfg.num_envs && mask[e]) {
+        reset_idx_env(A, reset_idx_rng_key(A), e);
+        list[atomicAdd(&n, 1)] = e;
+    }
+    __syncthreads();
+    for (int k = 0; k < n; ++k) reset_idx_clear_rows(A, list[k], threadIdx.x, blockDim.x);
+}
+
+// 3. (commands.curriculum only) update_command_curriculum inside reset_idx (legged_robot.py:179-180): due when common_step_counter is a
+//    multiple of max_episode_length, judged on the mean over the listed envs; the listed envs' x / y commands are then redone from the
+//    same draws, as command_curriculum_kernel does for a step
+__global__ __launch_bounds__(1024) void reset_idx_curriculum_kernel(const EnvArgs A, const uint8_t* mask) {
+    __shared__ int due;
+    __shared__ float xr[2];
+    if (threadIdx.x == 0) {
+        due = command_curriculum_due(A, A.st.counters[0]) ? 1 : 0;
+        if (due) {
+            double lo, hi;
+            command_curriculum_move(A, A.st.command_range_x[0], A.st.command_range_x[1], lo, hi);
+            A.st.command_range_x[0] = lo;
+            A.st.command_range_x[1] = hi;
+            xr[0] = (float)lo;
+            xr[1] = (float)(hi - lo);
+        }
+    }
+    __syncthreads();
+    if (!due) return;
+    const RngKey rk = reset_idx_rng_key(A);
+    const int64_t ring_step = A.st.counters[2];
+    for (int e = threadIdx.x; e < A.cfg.num_envs; e += blockDim.x)
+        if (mask[e]) command_curriculum_fix_env(A, rk, e, xr[0], xr[1], ring_step);
+}
+
+// 4. the finaliser of the call (hgym_finalize.hpp: fin_part1, then fin_reset_idx_tail)
+__global__ __launch_bounds__(1024) void reset_idx_finalize_kernel(const EnvArgs A) {
+    const FinArgs F = fin_of(A);
+    fin_part1(F, threadIdx.x, blockDim.x);
+    __syncthreads();       // every lane has read the reset count before it is cleared
+    if (threadIdx.x == 0) fin_reset_idx_tail(F);
+}
+
 __global__ __launch_bounds__(256) void pre_physics_kernel(const EnvArgs A) {
     const int N = A.cfg.num_envs;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -390,6 +453,47 @@ int32_t hgym_env_prime(const HgymEnvConfig* cfg, const HgymSimTensors* sim, cons
 int32_t hgym_env_reset_all(const HgymEnvConfig* cfg, const HgymSimTensors* sim, const HgymEnvState* st, const HgymEnvOut* out,
                            const HgymEnvNoise* noise, void* stream) {
     return launch_step(cfg, sim, st, out, noise, nullptr, MODE_RESET_ALL, 0, (hipStream_t)stream);
+}
+
+int32_t hgym_env_reset_idx(const HgymEnvConfig* cfg, const HgymSimTensors* sim, const HgymEnvState* st, const HgymEnvOut* out,
+                           const HgymEnvNoise* noise, const int64_t* env_ids, int32_t n_ids, uint8_t* mask_scratch, int64_t* rejected,
+                           void* stream) {
+    int32_t rc = check_common(cfg, sim, st);
+    if (rc) return rc;
+    HG_REQUIRE(sim && out, HGYM_E_BADARG, "null sim/out");
+    HG_REQUIRE(n_ids >= 0 && (n_ids == 0 || env_ids), HGYM_E_BADARG, "n_ids=%d with env_ids %p", n_ids, (const void*)env_ids);
+    HG_REQUIRE(mask_scratch && rejected, HGYM_E_BADARG, "null mask_scratch / rejected");
+    HG_REQUIRE(cfg->num_custom_rewards >= 0 && cfg->num_custom_rewards <= HGYM_MAX_CUSTOM_REWARDS, HGYM_E_SHAPE, "num_custom_rewards=%d",
+               cfg->num_custom_rewards);
+    if (cfg->num_custom_rewards > 0)
+        HG_REQUIRE(st->custom_sums && st->custom_acc && out->extras_custom, HGYM_E_BADARG,
+                   "user-defined reward terms need custom_sums / custom_acc / extras_custom");
+    EnvArgs A;
+    rc = env_args(cfg, sim, st, out, nullptr, MODE_RESET_ALL, 0, 256, &A);
+    if (rc) return rc;
+    // the outputs a reset_idx owns: reset bytes, extras; no observation, no transition or logging sink
+    A.out.t_values = nullptr;
+    A.out.t_rewards = nullptr;
+    A.out.t_dones = nullptr;
+    A.out.t_step = nullptr;
+    A.out.t_time_outs = nullptr;
+    A.out.defer_finalize = 0;
+    A.out.log_cur = A.out.log_stats = nullptr;
+    A.out.obs_ahead = A.out.priv_ahead = nullptr;
+    if (noise) A.noise = *noise;
+    const hipStream_t s = (hipStream_t)stream;
+    const int N = cfg->num_envs;
+    hipLaunchKernelGGL(reset_idx_mask_kernel, dim3(1), dim3(1024), 0, s, env_ids, (int)n_ids, N, mask_scratch, rejected);
+    HG_CHECK_LAUNCH("reset_idx_mask_kernel");
+    hipLaunchKernelGGL(reset_idx_kernel, dim3(ceil_div(N, 256)), dim3(256), 0, s, A, (const uint8_t*)mask_scratch);
+    HG_CHECK_LAUNCH("reset_idx_kernel");
+    if (cfg->command_curriculum) {
+        hipLaunchKernelGGL(reset_idx_curriculum_kernel, dim3(1), dim3(N > 256 ? 1024 : 256), 0, s, A, (const uint8_t*)mask_scratch);
+        HG_CHECK_LAUNCH("reset_idx_curriculum_kernel");
+    }
+    hipLaunchKernelGGL(reset_idx_finalize_kernel, dim3(1), dim3(N > 256 ? 1024 : 256), 0, s, A);
+    HG_CHECK_LAUNCH("reset_idx_finalize_kernel");
+    return HGYM_OK;
 }
 
 int32_t hgym_post_physics(const HgymEnvConfig* cfg, const HgymSimTensors* sim, const HgymEnvState* st, const HgymEnvOut* out,

@@ -1874,6 +1874,48 @@ HG_HD void command_curriculum_fix_env(const EnvArgs& A, const RngKey& rk, int e,
     }
 }
 
+// ------------------------------------------------------------------------------------------------ host-side partial reset
+// LeggedRobot.reset_idx(env_ids) for a caller-chosen set of envs (hgym_env_reset_idx, legged_robot.py:163-215 + humanoid_env.py:264-269):
+// the reset branch of the per-env chain exactly as reset_idx(all) runs it (A.mode = MODE_RESET_ALL, generic chain), for the envs whose
+// mask byte is set -- every other env is not even read.  State and sim tensors are addressed in place (no LDS staging), so nothing is
+// stored for an env outside the set.
+
+// Key of the draws of a host-side reset: the call number HgymEnvState.counters[3] in the two step words, with bit 30 of the high word
+// set.  No env-step draw uses that word (common_step_counter; bit 31 marks prime / reset_all) and neither does the policy's sampling.
+HG_HD RngKey reset_idx_rng_key(const EnvArgs& A) {
+    const int64_t call = A.st.counters[3];
+    RngKey rk;
+    rk.k0 = (uint32_t)A.cfg.seed;
+    rk.k1 = (uint32_t)(A.cfg.seed >> 32);
+    rk.s0 = (uint32_t)call;
+    rk.s1 = (uint32_t)(call >> 32) ^ 0x40000000u;
+    return rk;
+}
+
+// entry i of the caller's id list -> the env's mask byte.  Negative ids wrap as torch indexing does; an id outside [-N, N) is
+// reported (false) and causes no memory access.
+HG_HD bool reset_idx_mark(uint8_t* mask, const int64_t* ids, int64_t i, int N) {
+    const int64_t id = ids[i];
+    if (id < -(int64_t)N || id >= (int64_t)N) return false;
+    mask[id < 0 ? id + N : id] = 1;
+    return true;
+}
+
+// the reset branch for env e: dofs, root (+ custom origins, terrain curriculum), commands, zeroed buffers, episode sums into the
+// accumulators, gravity / Euler angles of the new pose, reset byte; no observation
+HG_HD void reset_idx_env(const EnvArgs& A, const RngKey& rk, int e) {
+    post_physics_env<true>(A, rk, A.st.counters[0], e, A.cfg.num_envs, nullptr, nullptr);
+}
+
+// humanoid_env.py:264-269: both history rings of env e zeroed, lanes t, t + nthreads, ... of the caller's group
+HG_HD void reset_idx_clear_rows(const EnvArgs& A, int e, int t, int nthreads) {
+    const int64_t no = (int64_t)A.cfg.frame_stack * HGYM_OBS_FRAME, np = (int64_t)A.cfg.c_frame_stack * HGYM_PRIV_FRAME;
+    float* ro = A.st.obs_ring + (int64_t)e * no;
+    float* rp = A.st.priv_ring + (int64_t)e * np;
+    for (int64_t i = t; i < no; i += nthreads) ro[i] = 0.0f;
+    for (int64_t i = t; i < np; i += nthreads) rp[i] = 0.0f;
+}
+
 // ------------------------------------------------------------------------------------------------ history stacking
 // Stacked, clipped observation rows (humanoid_env.py:250-262, legged_robot.py:105-108), oldest -> newest.
 //   ring      [N][H][F] unclipped frames, the newest goes to slot `slot_new`

@@ -86,6 +86,16 @@ HG_HD void fin_part2(const FinArgs& F) {
     if (F.mode != FIN_MODE_RESET_ALL) F.counters[2] += 1;
 }
 
+// The finaliser of a host-side partial reset (hgym_env_reset_idx), after fin_part1 and a barrier: extras["episode"] / the user-defined
+// terms' means and extras["time_outs"] have been refreshed as for reset_idx(all) -- or left as they were if no env was reset (never
+// 0/0).  Here the reset count is cleared and the call number counters[3] (the key of the next host reset's draws) advances; the step
+// counters [0] / [2] do not move, and neither the transition sink nor the logging sink is touched: the reference's runner counts
+// finished episodes from the dones of step(), not from reset_idx.
+HG_HD void fin_reset_idx_tail(const FinArgs& F) {
+    F.reset_count[0] = 0;
+    F.counters[3] += 1;
+}
+
 // Optional logging sink (HgymEnvOut::log_*): OnPolicyRunner.learn's per-step book-keeping (on_policy_runner.py:143-156).
 // Thread t refreshed extras_episode[t] in part 1, so it may add it up here without a barrier.  Finished episodes are appended to
 // the two 100-entry rings in env order (the reference extends its deques with cur_reward_sum[new_ids], ascending ids): envs are

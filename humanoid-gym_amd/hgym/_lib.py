@@ -164,6 +164,8 @@ SYMBOLS = {
     "hgym_env_config_default": (C.c_int32, [_P(EnvConfig), C.c_int32]),
     "hgym_env_prime": (C.c_int32, [_P(EnvConfig), _P(SimTensors), _P(EnvState), _P(EnvOut), _P(EnvNoise), C.c_void_p]),
     "hgym_env_reset_all": (C.c_int32, [_P(EnvConfig), _P(SimTensors), _P(EnvState), _P(EnvOut), _P(EnvNoise), C.c_void_p]),
+    "hgym_env_reset_idx": (C.c_int32, [_P(EnvConfig), _P(SimTensors), _P(EnvState), _P(EnvOut), _P(EnvNoise), c_i64_p, C.c_int32, c_u8_p,
+                                       c_i64_p, C.c_void_p]),
     "hgym_pre_physics": (C.c_int32, [_P(EnvConfig), _P(EnvState), c_float_p, _P(EnvNoise), C.c_void_p]),
     "hgym_pd_torques": (C.c_int32, [_P(EnvConfig), _P(SimTensors), _P(EnvState), C.c_void_p]),
     "hgym_synth_physics": (C.c_int32, [_P(EnvConfig), _P(SimTensors), _P(EnvState), C.c_void_p]),

@@ -73,6 +73,11 @@ class EnvBuffers:
         self.log_cur = z(2, N)
         self.log_stats = z(L.LOG_STATS)
         self.log_sink = False
+        # hgym_env_reset_idx (a host-side partial reset): the per-env mask it builds, the device copy of host-given ids (grown on
+        # demand), and the count of ids it skipped as out of range
+        self.reset_idx_mask = torch.zeros(N, dtype=torch.uint8, device=dev)
+        self.reset_idx_ids = torch.zeros(N, dtype=torch.int64, device=dev)
+        self.reset_idx_rejected = torch.zeros((), dtype=torch.int64, device=dev)
         # sim tensors
         self.sim_layout = sim_layout
         if sim_layout == "soa":

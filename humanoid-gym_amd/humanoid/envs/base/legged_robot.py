@@ -67,6 +67,27 @@ def rollout_plan(T, deferred, rows_ahead, l0_ahead, shadows):
     return plan
 
 
+def host_env_ids(env_ids, num_envs):
+    """env ids given on the host (list, numpy array, CPU tensor) -> a flat int64 CPU tensor, range-checked the way torch indexing
+    checks them: IndexError for an id outside [-num_envs, num_envs).  Negative ids are kept (the device wraps them)."""
+    t = env_ids if torch.is_tensor(env_ids) else torch.as_tensor(np.asarray(env_ids))
+    if t.dtype == torch.bool or t.dtype == torch.uint8 or t.is_floating_point() or t.is_complex():
+        raise IndexError("env_ids must be integer indices, not %s" % t.dtype)
+    t = t.reshape(-1).to(torch.int64)
+    if t.numel() and (int(t.min()) < -num_envs or int(t.max()) >= num_envs):
+        bad = t[(t < -num_envs) | (t >= num_envs)][0]
+        raise IndexError("index %d is out of bounds for dimension 0 with size %d" % (int(bad), num_envs))
+    return t.contiguous()
+
+
+def device_env_ids(env_ids):
+    """env ids already on the device -> flat contiguous int64 ids on the same device, without a host synchronisation (the range check
+    happens in the kernel)."""
+    if env_ids.dtype == torch.bool or env_ids.dtype == torch.uint8 or env_ids.is_floating_point() or env_ids.is_complex():
+        raise IndexError("env_ids must be integer indices, not %s" % env_ids.dtype)
+    return env_ids.reshape(-1).to(torch.int64).contiguous()
+
+
 class _CommandRanges(dict):
     """`env.command_ranges`: with cfg.commands.curriculum the lin_vel_x range lives on the device (the curriculum kernel moves
     it, legged_robot.py:422-431); reading that key reads it back."""
@@ -450,7 +471,8 @@ class LeggedRobot(BaseTask):
         (commands, pushes, noise, reset offsets) and the clock of the push / curriculum intervals -- where a run that has done
         `iteration` learning iterations has it, so that a resumed run continues the env's draw streams instead of replaying them
         from step 0.  The reference's checkpoint carries no generator state either (on_policy_runner.py:274-281); the counter is
-        a function of the iteration number.  The history ring position is left alone."""
+        a function of the iteration number.  The history ring position is left alone, and so is the call number of host-side
+        partial resets (counters[3], the key of reset_idx's draws)."""
         if not hasattr(self, "_seek_base"):                    # no reset() yet: this IS the fresh env
             self._seek_base = int(self._buf.counters[0])
         self._buf.counters[0] = self._seek_base + int(iteration) * int(steps_per_iteration)
@@ -505,6 +527,7 @@ class LeggedRobot(BaseTask):
                                      self._l0_ahead if l0_ahead is None else l0_ahead, cols["obs_bf16"] is not None)
         self._L.check(self._L.lib.hgym_rollout_begin(C.byref(self._st_s), self._L.i64ptr(cols["step"]), C.c_void_p(self._buf.rollout_scratch.data_ptr()),
                                                      (T - 1) & 1, self._stream()), "hgym_rollout_begin")
+        self._in_rollout = True       # (a partial reset_idx is refused until rollout_end, or until a launch of this rollout fails)
 
     def rollout_step(self, i):
         """Launch i of the rollout (rollout_plan(...)[i]): actions / mu / sigma / logp / values of PPO.act into slot i, this env's
@@ -526,11 +549,14 @@ class LeggedRobot(BaseTask):
         if p.bf16_ahead:
             o.obs_bf16_ahead, o.ld_obs_bf16_ahead = C.c_void_p(at("obs_bf16", i + 1).data_ptr()), c["obs_bf16"].shape[-1]
         sh = net.shadow_struct(at("obs_bf16"), at("priv_bf16") if p.shadow_priv else None) if p.shadow_obs else None
-        L.check(L.lib.hgym_rollout_step(C.byref(net.cfg), C.byref(net.struct), C.byref(self._ncfg), C.byref(self._sim_s), C.byref(self._st_s),
-                                        C.byref(o), C.byref(self._ro_prev[0]) if p.prev else None, L.fptr(at("obs")), L.fptr(at("priv")),
-                                        int(c["seed"]) & 0xFFFFFFFFFFFFFFFF, L.fptr(at("actions")), L.fptr(at("mu")), L.fptr(at("sigma")),
-                                        L.fptr(at("logp")), L.fptr(at("values")), C.c_void_p(self._buf.rollout_scratch.data_ptr()), p.parity,
-                                        None if sh is None else C.byref(sh), self._stream()), "hgym_rollout_step")
+        rc = L.lib.hgym_rollout_step(C.byref(net.cfg), C.byref(net.struct), C.byref(self._ncfg), C.byref(self._sim_s), C.byref(self._st_s),
+                                     C.byref(o), C.byref(self._ro_prev[0]) if p.prev else None, L.fptr(at("obs")), L.fptr(at("priv")),
+                                     int(c["seed"]) & 0xFFFFFFFFFFFFFFFF, L.fptr(at("actions")), L.fptr(at("mu")), L.fptr(at("sigma")),
+                                     L.fptr(at("logp")), L.fptr(at("values")), C.c_void_p(self._buf.rollout_scratch.data_ptr()), p.parity,
+                                     None if sh is None else C.byref(sh), self._stream())
+        if rc != 0:
+            self._in_rollout = False      # the rollout cannot go on: nothing carried across its launches is left to protect
+        L.check(rc, "hgym_rollout_step")
         self._ro_prev, self._ro_i = (o, p.parity), i + 1      # the struct is the next launch's prev_out (it points into the storage)
         self.obs_buf, self.privileged_obs_buf = at("obs", i + 1), at("priv", i + 1)
 
@@ -540,6 +566,7 @@ class LeggedRobot(BaseTask):
         self._L.check(self._L.lib.hgym_rollout_end(C.byref(self._ncfg), C.byref(self._st_s), C.byref(o), C.c_void_p(self._buf.rollout_scratch.data_ptr()),
                                                    parity, self._stream()), "hgym_rollout_end")
         self._ro_prev = None
+        self._in_rollout = False
 
     def _next_out(self):
         if self._bound_out is not None:
@@ -596,15 +623,50 @@ class LeggedRobot(BaseTask):
                                         C.byref(self._noise_none), self._stream()), "hgym_env_step_end")
 
     def reset_idx(self, env_ids):
-        """Only the all-envs form exists on the device (per-env resets are mask-driven inside the step kernel)."""
+        """legged_robot.py:163-215 (+ humanoid_env.py:264-269).  env_ids: a CUDA or CPU integer tensor, a list or a numpy array.
+        An id list of length num_envs means all envs -- hgym_env_reset_all, even for a list with repeats or gaps (the all-envs form
+        as it has always been).  Any other non-empty list: hgym_env_reset_idx for the listed envs only; every other env keeps its
+        state bit for bit.  Host ids are range-checked here (IndexError, like torch, before anything is launched); device ids go
+        to the kernel as they are, without a host synchronisation: ids outside [-N, N) are skipped there and counted in
+        `reset_idx_rejected` (a 0-dim device tensor).  One deliberate deviation: a repeated id resets its env once and counts once
+        in extras["episode"], where the reference's torch.mean counts it as often as it is listed.  No observation is computed
+        (obs_buf stays as it is, as in the reference); reset_buf reads True for the listed envs."""
         if len(env_ids) == 0:
             return
         if len(env_ids) != self.num_envs:
-            raise NotImplementedError("partial reset_idx from the host is not part of the hot path; resets are mask-driven on the device")
+            return self._reset_subset(env_ids)
         L = self._L
         out = self._buf.out_struct(self.obs_buf, self.privileged_obs_buf)
         L.check(L.lib.hgym_env_reset_all(C.byref(self._ncfg), C.byref(self._sim_s), C.byref(self._st_s), C.byref(out),
                                          C.byref(self._noise_none), self._stream()), "hgym_env_reset_all")
+
+    @property
+    def reset_idx_rejected(self):
+        """ids the last partial reset_idx skipped as outside [-N, N) (device ids only; host ids raise instead): 0-dim int64 device tensor."""
+        return self._buf.reset_idx_rejected
+
+    def _reset_subset(self, env_ids):
+        if getattr(self, "_pending_fin", None) is not None:
+            raise RuntimeError("the previous step's finaliser was postponed (bind_transition(defer_finalize=True)) and never run")
+        if getattr(self, "_in_rollout", False):
+            raise RuntimeError("reset_idx inside a fused rollout (rollout_begin ... rollout_end): its carried rows assume that nothing "
+                               "writes the env state between its launches")
+        L, b = self._L, self._buf
+        if torch.is_tensor(env_ids) and env_ids.device.type != "cpu":
+            ids = device_env_ids(env_ids)
+        else:
+            host = host_env_ids(env_ids, self.num_envs)
+            if host.numel() > b.reset_idx_ids.numel():
+                b.reset_idx_ids = torch.zeros(host.numel(), dtype=torch.int64, device=self.device)
+            ids = b.reset_idx_ids[:host.numel()]
+            ids.copy_(host)
+        out = b.out_struct(self.obs_buf, self.privileged_obs_buf)
+        L.check(L.lib.hgym_env_reset_idx(C.byref(self._ncfg), C.byref(self._sim_s), C.byref(self._st_s), C.byref(out), C.byref(self._noise_none),
+                                         L.i64ptr(ids), int(ids.numel()), L.u8ptr(b.reset_idx_mask), L.i64ptr(b.reset_idx_rejected),
+                                         self._stream()), "hgym_env_reset_idx")
+        self._refresh_extras()
+        if hasattr(self, "_terrain_level_mean"):
+            torch.mean(self.terrain_levels.float(), dim=0, out=self._terrain_level_mean)
 
     def reset(self):
         """legged_robot.py:112-117: reset every env, then one zero-action step."""

@@ -47,7 +47,9 @@ extern "C" {
                              *    (same version, later: HgymNetConfig.activation / act_alpha / act_scale appended -- ELU, SELU, LeakyReLU / ReLU,
                              *    Tanh or Sigmoid between the Linear layers; a zero-filled tail is the ELU(1) every earlier layout meant)
                              *    (same version, later still: HgymPPOConfig.value_loss_unclipped appended -- the value loss (R - V)^2 instead of
-                             *    the clipped form; a zero-filled tail is the clipped loss every earlier layout meant) */
+                             *    the clipped form; a zero-filled tail is the clipped loss every earlier layout meant)
+                             *    (same version, later: hgym_env_reset_idx -- reset_idx for a caller-chosen subset of envs, its draws keyed by
+                             *    the call number in HgymEnvState.counters[3]; no layout changes) */
 
 enum {
     HGYM_OK = 0,
@@ -168,7 +170,9 @@ typedef struct HgymSimTensors {
 typedef struct HgymEnvState {
     int64_t* episode_length;   /* [N] int64, VecEnv.episode_length_buf */
     int64_t* counters;         /* [4] int64 device scalars: [0] common_step_counter, [1] resets this step,
-                                  [2] ring step (frames pushed so far), [3] reserved */
+                                  [2] ring step (frames pushed so far), [3] host-reset call number: hgym_env_reset_idx
+                                  keys its draws by it and advances it (zero-filled by the caller once; seek-style moves of
+                                  [0] leave it alone) */
     float* commands;           /* 4 */
     float* actions;            /* 12 */
     float* last_actions;       /* 12 */
@@ -302,6 +306,27 @@ int32_t hgym_env_prime(const HgymEnvConfig* cfg, const HgymSimTensors* sim, cons
  * cleared, no observation pushed (the caller follows with a zero-action step, :115-116). */
 int32_t hgym_env_reset_all(const HgymEnvConfig* cfg, const HgymSimTensors* sim, const HgymEnvState* st,
                            const HgymEnvOut* out, const HgymEnvNoise* noise, void* stream);
+
+/* LeggedRobot.reset_idx(env_ids) (legged_robot.py:163-215 + humanoid_env.py:264-269) for the envs listed in env_ids: n_ids int64
+ * DEVICE indices; negative ids wrap as torch indexing does, ids outside [-N, N) are skipped (never dereferenced) and counted in
+ * *rejected (a device int64, overwritten); a repeated id resets its env once and counts once in the episode means (the reference's
+ * torch.mean counts repeats).  mask_scratch: N device bytes of caller scratch.  Three launches on `stream` (four with the command
+ * curriculum), no host synchronisation, capturable.  For the listed envs, in the reference's order: terrain curriculum on the pre-reset root and commands; the command
+ * curriculum when common_step_counter % max_episode_length == 0, judged on the listed envs; dofs, root (custom origins), command
+ * resample; actions / last_actions / last_last_actions / last_dof_vel / feet_air_time / episode_length zeroed; reset byte = 1;
+ * episode sums (built-in and user-defined terms) accumulated, then zeroed; projected_gravity and base_euler of the new pose; both
+ * history rings zeroed for those rows.  Every other env keeps every state field, sim tensor row, ring row and reset byte bit for
+ * bit.  No observation is written (the reference's reset_idx computes none).  Finaliser: extras_episode / extras_custom = mean
+ * over the reset envs / episode_length_s and extras_time_outs = time_out, unchanged when no env was reset; counters[0] and [2] do
+ * not move, counters[1] is cleared, counters[3] advances; the transition and logging sinks of `out` are not touched.
+ * Draws: the internal Philox stream keyed by (seed, counters[3], env, slot) with bit 30 of the high step word set -- words no step
+ * draw uses, so two host resets, or a host reset and the next step's reset of the same env, draw different numbers.  `noise`
+ * tables (u_dof, u_cmd[:, 3:6], u_xy, r_level; indexed by env id) override the draws as for the step.
+ * Precondition: no step finaliser is pending (HgymEnvOut.defer_finalize) and no fused rollout is between hgym_rollout_begin and
+ * hgym_rollout_end (their carried rows assume nobody writes the state in between). */
+int32_t hgym_env_reset_idx(const HgymEnvConfig* cfg, const HgymSimTensors* sim, const HgymEnvState* st, const HgymEnvOut* out,
+                           const HgymEnvNoise* noise, const int64_t* env_ids, int32_t n_ids, uint8_t* mask_scratch, int64_t* rejected,
+                           void* stream);
 
 /* XBotLFreeEnv.step head + LeggedRobot.step clip (humanoid_env.py:189-197, legged_robot.py:90-91):
  * st->actions <- clip(blend(clip(actions_in), st->actions) * (1 + noise)).  actions_in (N,12) row-major; read-only
