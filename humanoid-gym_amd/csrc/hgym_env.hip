@@ -350,13 +350,14 @@ static int32_t launch_step(const HgymEnvConfig* cfg, const HgymSimTensors* sim, 
 // after checking everything the fused rollout kernel compiles in (XBot-L default options, 15 / 3 history, contiguous SoA state
 // and sim tensors, a whole number of 32-env blocks).
 int32_t rollout_env_args(const HgymEnvConfig* cfg, const HgymSimTensors* sim, const HgymEnvState* st, const HgymEnvOut* out,
-                         float* actions, EnvArgs* A) {
+                         float* actions, EnvArgs* A, bool sink) {
     int32_t rc = check_common(cfg, sim, st);
     if (rc) return rc;
     HG_REQUIRE(sim && out && actions, HGYM_E_BADARG, "null sim / out / actions");
     rc = env_args(cfg, sim, st, out, actions, MODE_STEP, 1, 32, A);
     if (rc) return rc;
-    HG_REQUIRE(out->t_rewards && (out->t_values || out->t_time_outs) && out->t_dones && out->t_step && out->defer_finalize, HGYM_E_BADARG,
+    // (sink = false: the evaluation launch, hgym_rollout_eval_step, which stores no transition and has checked that itself)
+    HG_REQUIRE(!sink || (out->t_rewards && (out->t_values || out->t_time_outs) && out->t_dones && out->t_step && out->defer_finalize), HGYM_E_BADARG,
                "the fused rollout step stores the transition itself: transition sink (immediate: t_values; deferred: t_time_outs) + defer_finalize required");
     HG_REQUIRE(xbotl_default_options(cfg) && !cfg->use_ref_actions && cfg->frame_stack == 15 && cfg->c_frame_stack == 3, HGYM_E_UNSUPPORTED,
                "fused rollout step: XBot-L default options only");

@@ -1464,6 +1464,24 @@ int32_t rollout_fwd_args(const HgymNetConfig* cfg, const HgymNet* net, int M, co
     return HGYM_OK;
 }
 
+// The evaluation launch's tile (hgym_rollout_eval_step): the actor alone, no sampling epilogue, its head outputs written to `actions`.
+int32_t rollout_eval_fwd_args(const HgymNetConfig* cfg, const HgymNet* net, int M, const float* obs, float* actions, FwdArgs* out,
+                              size_t* lds_bytes) {
+    WsLayout w;
+    int32_t rc = check_net(cfg, net, &w);
+    if (rc) return rc;
+    HG_REQUIRE(w.net[0].fused, HGYM_E_UNSUPPORTED, "the fused evaluation step needs the bf16 fused path");
+    HG_REQUIRE(M > 0 && M <= w.maxM, HGYM_E_SHAPE, "batch %d exceeds max_batch %lld", M, (long long)w.maxM);
+    HG_REQUIRE(cfg->actor_dims[1] == 512, HGYM_E_UNSUPPORTED, "fused evaluation step: first hidden width 512 (XBot-L) only, not %d",
+               cfg->actor_dims[1]);
+    const FusedPath R(NetBase{*cfg, *net, w, nullptr, (char*)net->workspace});
+    const NetIO io[3] = {{obs, cfg->num_obs, actions, cfg->num_actions}, {}, {}};
+    *out = R.make_fwd_args(0, 1, M, io, nullptr, false, nullptr, nullptr, nullptr);
+    out->nets = 1;
+    *lds_bytes = fwd_lds(*out, 1, 32);
+    return HGYM_OK;
+}
+
 }  // namespace hgym
 
 using namespace hgym;

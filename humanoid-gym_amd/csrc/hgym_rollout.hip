@@ -42,8 +42,10 @@ namespace hgym {
 int32_t rollout_fwd_args(const HgymNetConfig* cfg, const HgymNet* net, int M, const float* obs, const float* priv, uint64_t seed,
                          const int64_t* step, float* actions, float* mu, float* sigma, float* logp, float* values, FwdArgs* out,
                          size_t* lds_bytes, const HgymObsShadow* sh);
+int32_t rollout_eval_fwd_args(const HgymNetConfig* cfg, const HgymNet* net, int M, const float* obs, float* actions, FwdArgs* out,
+                              size_t* lds_bytes);
 int32_t rollout_env_args(const HgymEnvConfig* cfg, const HgymSimTensors* sim, const HgymEnvState* st, const HgymEnvOut* out,
-                         float* actions, EnvArgs* A);
+                         float* actions, EnvArgs* A, bool sink = true);
 
 constexpr int RO_E = 32;       // envs (= policy rows) per workgroup
 constexpr int RO_NT = 512;     // lanes per workgroup: 8 wavefronts, as mlp_fwd_kernel<32, 8, 4>
@@ -107,9 +109,14 @@ constexpr int RO_CHAIN = 64 * kChainRoles;     // lanes of the per-env chain: fo
 // workgroup draws its own random numbers and copies its own history rows, as in the first launch of a rollout.
 // C64: the non-actor workgroups in the 64-row layout (see below), instantiated for the steady-state launch (PART) only -- one code
 // object for both layouts of every form would exceed the kernel size guard (build.py), and the other forms run once per rollout.
-template <bool FIN, bool PRE, bool PART = false, bool NOCRITIC = false, bool C64 = false>
+// EVAL (hgym_rollout_eval_step): the NOCRITIC form that just RUNS the policy -- action = mu.  The tile is launched without the sampling
+// epilogue (FwdArgs.sample = 0: no Philox draw for the policy, no sigma, no log-probability; the head's outputs go to `actions` through
+// FusedNet.out) and hands its head outputs to the env image through fwd_body's head hook instead of the sampling epilogue's put hook.
+// A template parameter, so that the training instantiations stay as they were.
+template <bool FIN, bool PRE, bool PART = false, bool NOCRITIC = false, bool C64 = false, bool EVAL = false>
 __global__ __launch_bounds__(RO_NT) void rollout_step_kernel(const FwdArgs f, const EnvArgs e, const FinArgs fin, const RolloutPP pp) {
     static_assert(!NOCRITIC || (!PRE && !PART), "rows ahead and the carried first layer are the critic workgroups' side jobs");
+    static_assert(!EVAL || NOCRITIC, "the evaluation launch has no critic tiles");
     static_assert(!C64 || (PRE && PART), "the 64-row layout is instantiated for the steady-state launch");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     if (FIN && blockIdx.y >= (NOCRITIC ? 1 : 2)) {
@@ -235,7 +242,18 @@ __global__ __launch_bounds__(RO_NT) void rollout_step_kernel(const FwdArgs f, co
         // the two head wavefronts finish the tile: three quarters of that store phase leave the chain behind the tile
         if (!PRE) hist_store<15, HGYM_OBS_FRAME, RO_NIO>(E.out.obs, block * RO_E, RO_E, (int)(ring_step % 15), t, RO_NT, nullptr, E.cfg.clip_obs, hist_o);
     };
-    fwd_body<32, 8, 4, 2 * U, false, false, PART>(f, f.net[0], true, smem, early, mid, put, e, idle, FwdNoop(), nullptr, nullptr, FwdNoop(), &pp.l0);
+    if constexpr (EVAL) {
+        // every lane of the two head wavefronts, with its row and its four head outputs (columns 4 q .. 4 q + 3 of the 16-column block)
+        auto put_mu = [&](int wave, int, int, const float (&mu)[4]) {
+            const int row = wave * 16 + (t & 15), q = (t & 63) >> 4;
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if (4 * q + c < HGYM_NUM_ACTIONS) esm[act_off + row * 12 + 4 * q + c] = mu[c];
+        };
+        fwd_body<32, 8, 4, 2 * U, false, false, false>(f, f.net[0], false, smem, early, mid, FwdNoop(), e, idle, put_mu);      // (not `is_actor`: no sampling epilogue)
+    } else {
+        fwd_body<32, 8, 4, 2 * U, false, false, PART>(f, f.net[0], true, smem, early, mid, put, e, idle, FwdNoop(), nullptr, nullptr, FwdNoop(), &pp.l0);
+    }
     if (PART && f.net[0].xs) {
         // rows of this tile whose env was reset by the previous step: columns [0, 32 kb0) of their bf16 shadow were written ahead from
         // the un-reset history -- the row's older frames are zero now (the launch that reset them zeroed the fp32 row)
@@ -480,6 +498,58 @@ int32_t hgym_rollout_step(const HgymNetConfig* cfg, const HgymNet* net, const Hg
         prof_end(HGYM_PROF_ROLLOUT, s, (double)M * (env_b + pol_b - (nocritic ? 4.0 * (cfg->num_priv + 1) : 0.0)) + w_b);
     }
     HG_CHECK_LAUNCH("rollout_step_kernel");
+    return HGYM_OK;
+}
+
+int32_t hgym_rollout_eval_step(const HgymNetConfig* cfg, const HgymNet* net, const HgymEnvConfig* env_cfg, const HgymSimTensors* sim,
+                               const HgymEnvState* st, const HgymEnvOut* out, const HgymEnvOut* prev_out, const float* obs, float* actions,
+                               void* scratch, int32_t parity, void* stream) {
+    HG_REQUIRE(cfg && net && env_cfg && sim && st && out && scratch && obs && actions, HGYM_E_BADARG, "null argument");
+    HG_REQUIRE(parity == 0 || parity == 1, HGYM_E_BADARG, "parity=%d", parity);
+    HG_REQUIRE(cfg->num_actions == HGYM_NUM_ACTIONS && cfg->num_obs == 15 * HGYM_OBS_FRAME, HGYM_E_UNSUPPORTED,
+               "fused evaluation step: actor shape %d -> %d is not XBot-L's 705 -> 12", cfg->num_obs, cfg->num_actions);
+    HG_REQUIRE(!out->t_rewards && !out->t_values && !out->t_dones && !out->t_step && !out->t_time_outs && !out->log_stats && out->defer_finalize,
+               HGYM_E_BADARG, "the evaluation step stores no transition and keeps no training log: sinks NULL, defer_finalize = 1");
+    HG_REQUIRE(!out->obs_ahead && !out->priv_ahead && !out->obs_older_ready && !out->l0_ahead && !out->l0_ready && !out->obs_bf16_ahead,
+               HGYM_E_BADARG, "rows ahead / the carried first layer do not exist in the evaluation launch");
+    HG_REQUIRE(out->obs != obs, HGYM_E_BADARG, "the next observation rows must not be the rows this launch reads");
+    RolloutScratch* scr = (RolloutScratch*)scratch;
+    const int M = env_cfg->num_envs;
+    FwdArgs f;
+    EnvArgs e;
+    FinArgs fin;
+    RolloutPP pp;
+    memset(&fin, 0, sizeof(fin));
+    memset(&pp, 0, sizeof(pp));
+    size_t lds_pol = 0;
+    int32_t rc = rollout_eval_fwd_args(cfg, net, M, obs, actions, &f, &lds_pol);
+    if (rc) return rc;
+    rc = rollout_env_args(env_cfg, sim, st, out, actions, &e, false);
+    if (rc) return rc;
+    e.reset_count = &scr->reset_cnt[parity];
+    e.st.episode_acc = scr->acc[parity];
+    if (prev_out) {
+        HG_REQUIRE(prev_out->rew != out->rew && prev_out->reset != out->reset && prev_out->time_out != out->time_out, HGYM_E_BADARG,
+                   "this step's and the previous step's rew / reset / time_out must be distinct buffers (the finaliser runs concurrently)");
+        HG_REQUIRE(prev_out->time_out && prev_out->extras_time_outs && prev_out->extras_episode && prev_out->rew && prev_out->reset &&
+                       !prev_out->t_rewards && !prev_out->log_stats, HGYM_E_BADARG, "null finaliser buffer, or a sink in prev_out");
+        fin = parity_fin(*env_cfg, *st, *prev_out, scr, parity ^ 1);
+    }
+    pp.in = scr->pp[parity];
+    pp.out = scr->pp[parity ^ 1];
+    pp.env_lds_off = (int)round_up((int64_t)lds_pol, 16);
+    {
+        const LdsMap m = lds_map(RO_E);
+        pp.draws_len = m.frame - m.u_delay;       // (no tables are handed over: every workgroup draws its own step's numbers)
+    }
+    f.dbg = nullptr;
+    const size_t lds = (size_t)pp.env_lds_off + step_smem_bytes(RO_E);
+    rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&rollout_step_kernel<true, false, false, true, false, true>), lds, "rollout_step_kernel (evaluation)");
+    if (rc) return rc;
+    // grid row 1 = the previous step's finaliser; the first launch of an evaluation has none and is launched without that row
+    hipLaunchKernelGGL((rollout_step_kernel<true, false, false, true, false, true>), dim3(M / RO_E, prev_out ? 2 : 1), dim3(RO_NT), lds,
+                       (hipStream_t)stream, f, e, fin, pp);
+    HG_CHECK_LAUNCH("rollout_step_kernel (evaluation)");
     return HGYM_OK;
 }
 

@@ -199,6 +199,10 @@ SYMBOLS = {
                                       c_float_p, C.c_uint64, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, C.c_void_p, C.c_int32,
                                       _P(ObsShadow), C.c_void_p]),
     "hgym_rollout_end": (C.c_int32, [_P(EnvConfig), _P(EnvState), _P(EnvOut), C.c_void_p, C.c_int32, C.c_void_p]),
+    "hgym_rollout_eval_step": (C.c_int32, [_P(NetConfig), _P(Net), _P(EnvConfig), _P(SimTensors), _P(EnvState), _P(EnvOut), _P(EnvOut), c_float_p,
+                                           c_float_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "hgym_eval_reset": (C.c_int32, [C.c_int32, c_f64_p, C.c_void_p]),
+    "hgym_eval_accumulate": (C.c_int32, [C.c_int32, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, c_u8_p, c_u8_p, c_f64_p, C.c_void_p]),
     "hgym_ppo_grad": (C.c_int32, [_P(NetConfig), _P(PPOConfig), _P(Net), _P(Batch), C.c_void_p]),
     "hgym_ppo_grad_part": (C.c_int32, [_P(NetConfig), _P(PPOConfig), _P(Net), _P(Batch), C.c_int32, C.c_void_p]),
     "hgym_net_param_offset": (C.c_int64, [_P(NetConfig), C.c_int32]),
@@ -274,6 +278,24 @@ def i64ptr(t):
 
 def f64ptr(t):
     return None if t is None else C.cast(t.data_ptr(), c_f64_p)
+
+
+# the evaluation accumulator's block (include/hgym.h: HGYM_EVAL_*)
+EVAL_SUMS, EVAL_ENVS_PER_PARTIAL = 32, 256
+EVAL_STEPS, EVAL_ENV_STEPS, EVAL_LIN_ERR, EVAL_ANG_ERR, EVAL_REWARD, EVAL_EPISODES, EVAL_TIMEOUTS, EVAL_RETURN, EVAL_LENGTH = range(9)
+EVAL_TICKET, EVAL_TERMS = 9, 10
+
+
+def eval_block_doubles(n):
+    """HGYM_EVAL_BLOCK_DOUBLES(n) of include/hgym.h."""
+    n = int(n)
+    return EVAL_SUMS * (1 + (n + EVAL_ENVS_PER_PARTIAL - 1) // EVAL_ENVS_PER_PARTIAL) + 24 * n
+
+
+def eval_block(n, device):
+    """The accumulator block of hgym_eval_reset / hgym_eval_accumulate for n envs, zero-filled."""
+    import torch
+    return torch.zeros(eval_block_doubles(n), dtype=torch.float64, device=device)
 
 
 def gae_stats(n, device):

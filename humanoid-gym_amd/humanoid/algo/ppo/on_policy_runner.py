@@ -179,6 +179,9 @@ class OnPolicyRunner:
         self.last_collection_time = self.last_learn_time = 0.0
         self._rollout_capture = _CapturedGraph()     # the rollout as a HIP graph, and the tensors it owns
         self._update_capture = _CapturedGraph()      # compute_returns() + update() as a second HIP graph
+        self._eval_capture = _CapturedGraph()        # the fused evaluation rollout as a HIP graph of its own (evaluate)
+        self.eval_env = None                         # set_eval_env: learn() evaluates on it every cfg["eval_interval"] iterations
+        self.last_eval = None
         _, _ = self.env.reset()
 
     _graph = property(lambda self: self._rollout_capture.graph)
@@ -245,6 +248,7 @@ class OnPolicyRunner:
                                                              mean_value_loss=mean_value_loss, mean_surrogate_loss=mean_surrogate_loss))
                 if log_on and it % self.save_interval == 0:
                     self.save(os.path.join(self.log_dir, "model_{}.pt".format(it)), wait=False)
+                self._maybe_evaluate(it)            # behind the iteration's timing marks, like everything that is not the iteration
         finally:
             # also on an exception inside the loop: the last finished iteration's log block is printed, the env's bindings released
             if pending is not None:
@@ -259,6 +263,88 @@ class OnPolicyRunner:
         self._check_replicas("end of learn() at iteration %d" % self.current_learning_iteration)
         if log_on:      # (the background writer finishes the file; wait_for_saves() / load() / interpreter exit wait for it: save())
             self.save(os.path.join(self.log_dir, "model_{}.pt".format(self.current_learning_iteration)), wait=False)
+
+    # ------------------------------------------------------------------ evaluation on mean actions
+    def set_eval_env(self, env):
+        """The env learn() evaluates on every cfg["eval_interval"] iterations (0 / absent: never) for cfg["eval_steps"] steps: a
+        LeggedRobot of its own, never the training env."""
+        if env is self.env:
+            raise ValueError("the evaluation env must not be the training env")
+        self.eval_env = env
+
+    def _maybe_evaluate(self, it):
+        every = int(self.cfg.get("eval_interval", 0) or 0)
+        if every <= 0 or self.eval_env is None or (it + 1) % every != 0:
+            return
+        from . import dist_utils
+        if dist_utils.active() and torch.distributed.get_rank() != 0:       # N > 1 ranks: rank 0 evaluates (no collective inside)
+            return
+        self.last_eval = self.evaluate(self.eval_env, int(self.cfg.get("eval_steps", self.num_steps_per_env)))
+        if self.writer is not None:
+            for k, v in self.last_eval.items():
+                self.writer.add_scalar("Eval/" + k, v, it)
+
+    def evaluate(self, env, num_steps, reset=True, fused=None):
+        """How good is the current policy: num_steps vec-steps of `env` on the policy's MEAN action (what play.py and an exported policy
+        run), summarised over all its envs.  env: a separate LeggedRobot -- any num_envs, its own config (play.py's overrides are the
+        typical ones) -- never the training env.  reset: env.reset() first; without it the running episodes are counted from here.
+
+        Where env.eval_rollout_supported(net) (and fused is not False) every vec-step is ONE launch (hgym_rollout_eval_step: actor tile
+        with action = mu + env step + the previous step's finaliser) and the whole evaluation one replayed HIP graph; otherwise the
+        policy's mean (act_inference) + env.step per step (other activations, widths, fp32, terrain options, user-defined reward terms).
+        Both paths feed the same device-side accumulator (hgym_eval_accumulate: fp64 sums in a fixed order), read back once, so the
+        result does not depend on the path.
+
+        Returns python floats: episodes (int), mean_episode_return, mean_episode_length, timeout_fraction, fall_fraction (over the
+        episodes that ended inside the evaluation), mean_reward_per_step, lin_vel_tracking_error, ang_vel_tracking_error (over all
+        env-steps) and rew_<term> for the kernel's reward terms (mean episode sum / episode_length_s, as extras["episode"] divides;
+        the terms of an episode's last step are not in them: the env step consumes the sums inside its launch).  With zero finished
+        episodes the episode fields and rew_<term> are nan and `episodes` is 0.
+
+        No side effect on training: the rollout storage, the policy's sampling step (PPO._sample_step), the permutation draw number,
+        the training env and the two captured training graphs are not touched."""
+        if env is self.env:
+            raise ValueError("evaluate() needs an env of its own: the training env's state belongs to learn()")
+        num_steps = int(num_steps)
+        if num_steps <= 0:
+            raise ValueError("num_steps=%d" % num_steps)
+        ac, net = self.alg.actor_critic, getattr(self.alg, "net", None)
+        use_fused = bool(fused is not False and net is not None and hasattr(env, "eval_rollout_supported") and env.eval_rollout_supported(net))
+        if fused is True and not use_fused:
+            raise RuntimeError("fused=True, but env.eval_rollout_supported(net) is False for this env / policy")
+        with torch.inference_mode():
+            if reset:
+                env.reset()
+            env.eval_prepare(keep_episodes=not reset)
+            if use_fused:
+                def launches():
+                    env.eval_reset()
+                    env.eval_begin(net, num_steps)
+                    for i in range(num_steps):
+                        env.eval_step(i)
+                    env.eval_end()
+                    return env, net
+
+                graph_on = (str(self.device).startswith("cuda") and os.environ.get("HGYM_GRAPH", "1") != "0" and hasattr(torch.cuda, "CUDAGraph"))
+                # The captured launches carry the env's and the net's device addresses.  The capture HOLDS both objects (what launches()
+                # returns stays in _CapturedGraph.held), so their buffers live as long as the graph does and their id()s cannot be handed
+                # to other objects; a graph captured for another env or net is dropped here, never replayed.
+                cap = self._eval_capture
+                if cap.graph is not None and (cap.held[0] is not env or cap.held[1] is not net):
+                    cap = self._eval_capture = _CapturedGraph()      # (eager now, captured at this env's next evaluation)
+                key = (num_steps, env.rollout_graph_key())
+                cap.run(graph_on, key, launches, launches, lambda held: None)
+                env.eval_finish(num_steps)
+            else:
+                env.eval_reset()
+                obs = env.get_observations()
+                mb = int(net.cfg.max_batch) if (net is not None and obs.is_cuda) else obs.shape[0]
+                for _ in range(num_steps):
+                    # (an env larger than the net's max_batch: the rows in pieces)
+                    a = ac.act_inference(obs) if obs.shape[0] <= mb else torch.cat([ac.act_inference(obs[k:k + mb]) for k in range(0, obs.shape[0], mb)])
+                    obs = env.step(a)[0]
+                    env.eval_accumulate()
+            return env.eval_read()
 
     def _open_writer(self):
         if self.log_dir is not None and self.writer is None:

@@ -88,6 +88,30 @@ def device_env_ids(env_ids):
     return env_ids.reshape(-1).to(torch.int64).contiguous()
 
 
+EVAL_KEYS = ("episodes", "mean_episode_return", "mean_episode_length", "timeout_fraction", "fall_fraction", "mean_reward_per_step",
+             "lin_vel_tracking_error", "ang_vel_tracking_error")
+
+
+def eval_summary(totals, reward_names, episode_length_s):
+    """The dict OnPolicyRunner.evaluate returns from the totals of the evaluation accumulator (the first HGYM_EVAL_SUMS doubles of its
+    block, include/hgym.h), python floats: per-step means over the env-steps seen, per-episode means over the episodes that ENDED
+    inside the evaluation (nan when none did; `episodes` is 0 then), and rew_<term> for every kernel reward term in reward_names: the
+    mean over those episodes of the term's episode sum / episode_length_s, the division extras["episode"] makes."""
+    from hgym import _lib as L
+    t = [float(v) for v in totals]
+    nan = float("nan")
+    per = lambda x, n: x / n if n > 0 else nan
+    eps, steps = t[L.EVAL_EPISODES], t[L.EVAL_ENV_STEPS]
+    out = dict(episodes=int(eps), mean_episode_return=per(t[L.EVAL_RETURN], eps), mean_episode_length=per(t[L.EVAL_LENGTH], eps),
+               timeout_fraction=per(t[L.EVAL_TIMEOUTS], eps), fall_fraction=per(eps - t[L.EVAL_TIMEOUTS], eps),
+               mean_reward_per_step=per(t[L.EVAL_REWARD], steps), lin_vel_tracking_error=per(t[L.EVAL_LIN_ERR], steps),
+               ang_vel_tracking_error=per(t[L.EVAL_ANG_ERR], steps))
+    for n in reward_names:
+        if n in KERNEL_REWARD_TERMS:
+            out["rew_" + n] = per(t[L.EVAL_TERMS + KERNEL_REWARD_TERMS.index(n)], eps) / float(episode_length_s)
+    return out
+
+
 class _CommandRanges(dict):
     """`env.command_ranges`: with cfg.commands.curriculum the lin_vel_x range lives on the device (the curriculum kernel moves
     it, legged_robot.py:422-431); reading that key reads it back."""
@@ -481,6 +505,21 @@ class LeggedRobot(BaseTask):
     # One launch per vec-step: PPO.act, this env's step (synthetic-physics backend) and the previous step's finaliser
     # (include/hgym.h: hgym_rollout_begin / _step / _end).  Used by OnPolicyRunner when nothing on the host needs the per-step
     # results; every other caller keeps act() + step().
+    def _fused_env_ok(self):
+        """The env side of what hgym_rollout_step / hgym_rollout_eval_step accept: the XBot-L default options, 15 / 3 history, whole tiles."""
+        c = self._ncfg
+        generic = c.custom_origins or c.terrain_curriculum or c.num_height_points > 0 or c.command_curriculum or not c.heading_command
+        # the fused launch never calls step(): a task class that overrides step() / post_physics_step() (a wrapper, extra
+        # book-keeping around the step) must keep getting its own code, i.e. the act() + step() path
+        own_step = type(self).step is LeggedRobot.step and type(self).post_physics_step is LeggedRobot.post_physics_step
+        own_step = own_step and not getattr(self, "_custom_terms", None)       # user-defined reward terms: the two-launch step
+        return bool(own_step and not generic and not c.use_ref_actions and c.frame_stack == 15 and c.c_frame_stack == 3 and self.num_envs % 32 == 0)
+
+    def _fused_actor_ok(self, net):
+        """The actor side: the bf16 net, four layers, first hidden width 512, 12 actions."""
+        nc = net.cfg
+        return bool(nc.precision == self._L.BF16 and nc.actor_layers == 4 and nc.actor_dims[1] == 512 and nc.num_actions == 12)
+
     def rollout_fused_supported(self, net):
         """The fused rollout launch WITH the critic's tiles inline serves this env / net (rollout_fused_mode == "inline")."""
         return self.rollout_fused_mode(net) == "inline"
@@ -492,16 +531,10 @@ class LeggedRobot(BaseTask):
         8192 envs: collection 3.68 -> 3.49 ms against the two-launch path, same call (profiles/r05d_deferred_values_ab.txt; round 3's
         attempt WITH the critic's tiles in a second round of workgroups lost: profiles/r03_seq_rollout_8192_negative_result.txt); at
         4096 envs the inline form wins (2.15 vs 2.76 ms: half the chip would idle); None: the two-launch path.  HGYM_ROLLOUT_CRITIC=inline|deferred|auto (default auto) restricts / forces the choice."""
-        c, nc = self._ncfg, net.cfg
-        generic = c.custom_origins or c.terrain_curriculum or c.num_height_points > 0 or c.command_curriculum or not c.heading_command
+        nc = net.cfg
         cus = max(int(self._L.lib.hgym_device_cus()), 1)
-        # the fused launch never calls step(): a task class that overrides step() / post_physics_step() (a wrapper, extra
-        # book-keeping around the step) must keep getting its own code, i.e. the act() + step() path
-        own_step = type(self).step is LeggedRobot.step and type(self).post_physics_step is LeggedRobot.post_physics_step
-        own_step = own_step and not getattr(self, "_custom_terms", None)       # user-defined reward terms: the two-launch step
-        ok = bool(own_step and not generic and not c.use_ref_actions and c.frame_stack == 15 and c.c_frame_stack == 3 and self.num_envs % 32 == 0
-                  and nc.precision == self._L.BF16 and nc.actor_layers == 4 and nc.critic_layers == 4 and nc.actor_dims[1] == 512
-                  and nc.critic_dims[1] == 768 and nc.num_actions == 12 and getattr(self.cfg.env, "send_timeouts", False))
+        ok = bool(self._fused_env_ok() and self._fused_actor_ok(net) and nc.critic_layers == 4 and nc.critic_dims[1] == 768
+                  and getattr(self.cfg.env, "send_timeouts", False))
         # ... and only on a net that took the fused kernels: a bf16 net whose update tile does not fit in LDS runs the generic path
         # (hgym_net_shadow_ld = 0 there), which hgym_rollout_step refuses
         ok = ok and net.shadow_ld(0) > 0
@@ -567,6 +600,94 @@ class LeggedRobot(BaseTask):
                                                    parity, self._stream()), "hgym_rollout_end")
         self._ro_prev = None
         self._in_rollout = False
+
+    # ------------------------------------------------------------------ evaluation rollout (native extension)
+    # The policy's MEAN action on the same hot path: hgym_rollout_eval_step (actor tile with action = mu + this env's step + the previous
+    # step's finaliser, one launch) and the evaluation accumulator behind every step.  Nothing of training is touched: no storage, no
+    # sampling step, no transition sink; the env is an evaluation env of its own (OnPolicyRunner.evaluate).
+    def eval_rollout_supported(self, net):
+        """hgym_rollout_eval_step serves this env / net: the rules of rollout_fused_mode minus everything that concerns the critic, the
+        storage and send_timeouts, and no more envs than the net's max_batch.  No limit from the chip's size: the launch's workgroups
+        hand nothing to each other, so more of them than compute units simply run in a further round."""
+        ok = bool(self._fused_env_ok() and self._fused_actor_ok(net) and self.num_envs <= net.cfg.max_batch)
+        return bool(ok and net.shadow_ld(0) > 0)         # ... on a net that took the fused kernels (see rollout_fused_mode)
+
+    def eval_prepare(self, keep_episodes=False):
+        """Host book-keeping in front of an evaluation (never part of a captured graph): the current observations into the first
+        output set, which eval_step(0) reads.  Every episode is counted from here, after a reset() too (whose zero-action step has
+        already been added to the env's reward-term sums): the env's episode sums start at zero like the accumulator's returns and
+        lengths.  The env's own episode_length_buf is left alone -- it decides the time-outs: after reset() it stands at 1, so a
+        time-out ends an episode of max_episode_length - 1 counted steps; with keep_episodes (an evaluation without reset()) at
+        wherever the running episodes are."""
+        if getattr(self, "_pending_fin", None) is not None:
+            raise RuntimeError("a postponed step finaliser is pending; run it before an evaluation")
+        if self.obs_buf.data_ptr() != self._outs[0][0].data_ptr():
+            self._outs[0][0].copy_(self.obs_buf)
+            self._outs[0][1].copy_(self.privileged_obs_buf)
+        self._flip, self._bound_out = 0, None
+        self.obs_buf, self.privileged_obs_buf = self._outs[0]
+        self._buf.f["episode_sums"].zero_()
+        if getattr(self, "_eval_block", None) is None:
+            self._eval_block = self._L.eval_block(self.num_envs, self.device)
+            self._eval_actions = torch.zeros(self.num_envs, self.num_actions, device=self.device)
+            self._eval_step_dummy = torch.zeros(1, dtype=torch.int64, device=self.device)     # hgym_rollout_begin's (unused) sampling step
+
+    def eval_reset(self):
+        """Zero the accumulator block (a launch)."""
+        self._L.check(self._L.lib.hgym_eval_reset(self.num_envs, self._L.f64ptr(self._eval_block), self._stream()), "hgym_eval_reset")
+
+    def eval_accumulate(self, alt=False):
+        """The accumulator launch behind a step: this env's state and the step's rew / reset / time_out (alt: the alternate set)."""
+        b, L = self._buf, self._L
+        rew, reset, time_out = (b.rew_alt, b.reset_alt, b.time_out_alt) if alt else (b.rew, b.reset, b.time_out)
+        L.check(L.lib.hgym_eval_accumulate(self.num_envs, L.fptr(b.f["commands"]), L.fptr(b.f["base_lin_vel"]), L.fptr(b.f["base_ang_vel"]),
+                                           L.fptr(b.f["episode_sums"]), L.fptr(rew), L.u8ptr(reset), L.u8ptr(time_out),
+                                           L.f64ptr(self._eval_block), self._stream()), "hgym_eval_accumulate")
+
+    def eval_begin(self, net, T):
+        """A fused evaluation of T launches (eval_step(0) .. eval_step(T - 1), then eval_end()), after eval_prepare()."""
+        self._ev_net, self._ev_T, self._ev_prev, self._ev_i = net, int(T), None, 0
+        self._L.check(self._L.lib.hgym_rollout_begin(C.byref(self._st_s), self._L.i64ptr(self._eval_step_dummy),
+                                                     C.c_void_p(self._buf.rollout_scratch.data_ptr()), (T - 1) & 1, self._stream()),
+                      "hgym_rollout_begin")
+        self._in_rollout = True
+
+    def eval_step(self, i):
+        """Launch i: mu of the rows in output set i & 1 into eval_actions, this env's step on them with the observations written to the
+        other set, the previous step's finaliser; then the accumulator.  The last launch uses the primary rew / reset / time_out."""
+        L, net = self._L, self._ev_net
+        if i != self._ev_i:
+            raise RuntimeError("fused evaluation: launch %d is next, not %d" % (self._ev_i, i))
+        parity = (self._ev_T - 1 - i) & 1
+        src, dst = self._outs[i & 1], self._outs[(i + 1) & 1]
+        o = self._buf.out_struct(dst[0], dst[1], None, True, alt=bool(parity))
+        o.log_cur, o.log_stats = None, None          # (an evaluation keeps no training log)
+        rc = L.lib.hgym_rollout_eval_step(C.byref(net.cfg), C.byref(net.struct), C.byref(self._ncfg), C.byref(self._sim_s), C.byref(self._st_s),
+                                          C.byref(o), C.byref(self._ev_prev[0]) if self._ev_prev else None, L.fptr(src[0]),
+                                          L.fptr(self._eval_actions), C.c_void_p(self._buf.rollout_scratch.data_ptr()), parity, self._stream())
+        if rc != 0:
+            self._in_rollout = False
+        L.check(rc, "hgym_rollout_eval_step")
+        self.eval_accumulate(alt=bool(parity))
+        self._ev_prev, self._ev_i = (o, parity), i + 1
+
+    def eval_end(self):
+        """The finaliser of the last step on its own."""
+        o, parity = self._ev_prev
+        self._L.check(self._L.lib.hgym_rollout_end(C.byref(self._ncfg), C.byref(self._st_s), C.byref(o), C.c_void_p(self._buf.rollout_scratch.data_ptr()),
+                                                   parity, self._stream()), "hgym_rollout_end")
+        self._ev_prev = None
+        self._in_rollout = False
+
+    def eval_finish(self, T):
+        """Host book-keeping behind a fused evaluation of T steps (also behind a replayed graph): where the observations are now."""
+        self._flip = T & 1
+        self.obs_buf, self.privileged_obs_buf = self._outs[self._flip]
+
+    def eval_read(self):
+        """The evaluation's dict (eval_summary); ONE device read-back."""
+        from hgym import _lib as L
+        return eval_summary(self._eval_block[:L.EVAL_SUMS].cpu().tolist(), self.reward_names, self.max_episode_length_s)
 
     def _next_out(self):
         if self._bound_out is not None:

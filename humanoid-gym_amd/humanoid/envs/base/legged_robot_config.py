@@ -52,4 +52,6 @@ class LeggedRobotCfgPPO(BaseConfig):
                    num_learning_epochs=5, num_mini_batches=4, learning_rate=1.0e-3, schedule="adaptive", gamma=0.99, lam=0.95,
                    desired_kl=0.01, max_grad_norm=1.0)
     runner = ns("runner", policy_class_name="ActorCritic", algorithm_class_name="PPO", num_steps_per_env=24, max_iterations=1500,
-                save_interval=100, experiment_name="test", run_name="", resume=False, load_run=-1, checkpoint=-1, resume_path=None)
+                save_interval=100, experiment_name="test", run_name="", resume=False, load_run=-1, checkpoint=-1, resume_path=None,
+                # native extension (OnPolicyRunner.set_eval_env): evaluate on mean actions every eval_interval iterations (0: never) for eval_steps steps
+                eval_interval=0, eval_steps=60)

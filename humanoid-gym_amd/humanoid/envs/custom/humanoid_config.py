@@ -54,6 +54,8 @@ class XBotLCfgPPO(_P):
                    num_mini_batches=4)
     runner = ns("runner", policy_class_name="ActorCritic", algorithm_class_name="PPO", num_steps_per_env=60, max_iterations=3001,
                 save_interval=100, experiment_name="XBot_ppo", run_name="", resume=False, load_run=-1, checkpoint=-1, resume_path=None)
+    # (this runner block is the reference's, key for key: tests/golden/config_dump.json.  The native keys runner.eval_interval = 0 / runner.eval_steps
+    # of LeggedRobotCfgPPO.runner -- OnPolicyRunner.set_eval_env -- are read with those defaults when absent; set them on an instance: cfg.runner.eval_interval = 50)
 
 
 class XBotLDWLCfgPPO(XBotLCfgPPO):

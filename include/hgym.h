@@ -49,7 +49,9 @@ extern "C" {
                              *    (same version, later still: HgymPPOConfig.value_loss_unclipped appended -- the value loss (R - V)^2 instead of
                              *    the clipped form; a zero-filled tail is the clipped loss every earlier layout meant)
                              *    (same version, later: hgym_env_reset_idx -- reset_idx for a caller-chosen subset of envs, its draws keyed by
-                             *    the call number in HgymEnvState.counters[3]; no layout changes) */
+                             *    the call number in HgymEnvState.counters[3]; no layout changes)
+                             *    (same version, later: hgym_rollout_eval_step -- the rollout launch on the policy's mean action -- and the
+                             *    evaluation accumulator hgym_eval_reset / hgym_eval_accumulate; no layout changes) */
 
 enum {
     HGYM_OK = 0,
@@ -585,6 +587,62 @@ int32_t hgym_rollout_step(const HgymNetConfig* cfg, const HgymNet* net, const Hg
                           void* scratch, int32_t parity, const HgymObsShadow* shadow, void* stream);
 int32_t hgym_rollout_end(const HgymEnvConfig* env_cfg, const HgymEnvState* st, const HgymEnvOut* last_out, void* scratch,
                          int32_t parity, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Evaluation rollout (header v9, no layout change): the policy's MEAN action instead of a sample, what scripts/play.py and an
+ * exported policy run (ActorCritic.act_inference, actor_critic.py:122-124, followed by VecEnv.step).
+ *
+ * hgym_rollout_eval_step is the values = NULL form of hgym_rollout_step without everything that serves training: workgroup b computes
+ * the actor tile of envs [32 b, 32 b + 32) and runs their env step on action = mu right behind it; a second grid row carries the
+ * finaliser of the PREVIOUS step (prev_out; NULL on the first step).  No Philox draw for the policy, no sigma, no log-probability, no
+ * critic tile, no storage slot, no bf16 shadow, no transition sink.  `actions` (N, 12) receives mu: bit for bit what hgym_policy_act
+ * returns as `mu` for the same rows, and the env step is that of hgym_env_step_synth on those actions.
+ * Calling sequence for T steps, parity(t) alternating: hgym_rollout_begin(st, any device int64, scratch, parity(0)); T calls with
+ * out[t].obs / priv_obs = where the observations of step t + 1 go (not the rows the call reads), the sinks NULL, defer_finalize = 1,
+ * rew / reset / time_out distinct from out[t-1]'s; hgym_rollout_end(env_cfg, st, out[T-1], scratch, parity(T-1)).  Same scratch block,
+ * same restrictions as hgym_rollout_step (HGYM_E_UNSUPPORTED otherwise; callers fall back to hgym_mlp_forward + hgym_env_step_synth),
+ * except that nothing is asked of the critic.
+ * ---------------------------------------------------------------------------------------------- */
+int32_t hgym_rollout_eval_step(const HgymNetConfig* cfg, const HgymNet* net, const HgymEnvConfig* env_cfg, const HgymSimTensors* sim,
+                               const HgymEnvState* st, const HgymEnvOut* out, const HgymEnvOut* prev_out, const float* obs,
+                               float* actions, void* scratch, int32_t parity, void* stream);
+
+/* The evaluation accumulator: one caller-owned block of HGYM_EVAL_BLOCK_DOUBLES(n) doubles, zeroed by hgym_eval_reset, added to by one
+ * hgym_eval_accumulate behind every vec-step (fused or not: it reads the env state and the step's outputs as any env step leaves them),
+ * read back once.  fp64 sums formed in a fixed order (per-workgroup partials, added by the last workgroup to arrive): the same
+ * trajectory gives the same bits.  Totals, block[HGYM_EVAL_*]:
+ *   STEPS       vec-steps seen                       ENV_STEPS   env-steps seen (n per vec-step)
+ *   LIN_ERR     sum of |commands[:, :2] - base_lin_vel[:, :2]|_2        ANG_ERR   sum of |commands[:, 2] - base_ang_vel[:, 2]|
+ *   REWARD      sum of rew
+ *   EPISODES    envs with reset set                  TIMEOUTS    ... of which time_out was set
+ *   RETURN      sum over finished episodes of their return (sum of rew since the env's previous reset, or since hgym_eval_reset)
+ *   LENGTH      ... of their length in steps
+ *   TERMS + k   ... of HgymEnvState.episode_sums[k] as it stood BEFORE the episode's last step: the env step consumes and zeroes the
+ *               finished sums inside its launch, so the accumulator credits the copy it took one step earlier (k in the order of
+ *               HgymEnvConfig.reward_scales; the last step's terms are missing from these 22 sums, not from RETURN)
+ * The velocity errors compare the command and the base velocity as the step leaves them (for an env that has just reset: its new
+ * command and its reset velocity).  Behind the totals the block holds the per-workgroup partials and the per-env running return,
+ * length and copy of the episode sums.  commands / base_lin_vel / base_ang_vel / episode_sums: the [C][n] arrays of HgymEnvState;
+ * rew / reset / time_out: that step's HgymEnvOut buffers. */
+#define HGYM_EVAL_SUMS 32
+#define HGYM_EVAL_STEPS 0
+#define HGYM_EVAL_ENV_STEPS 1
+#define HGYM_EVAL_LIN_ERR 2
+#define HGYM_EVAL_ANG_ERR 3
+#define HGYM_EVAL_REWARD 4
+#define HGYM_EVAL_EPISODES 5
+#define HGYM_EVAL_TIMEOUTS 6
+#define HGYM_EVAL_RETURN 7
+#define HGYM_EVAL_LENGTH 8
+#define HGYM_EVAL_TICKET 9      /* arrival counter of the running call (an integer in the slot's first word; zero between calls) */
+#define HGYM_EVAL_TERMS 10      /* 22 slots */
+#define HGYM_EVAL_ENVS_PER_PARTIAL 256
+#define HGYM_EVAL_BLOCK_DOUBLES(n) ((size_t)HGYM_EVAL_SUMS * (1 + ((size_t)(n) + HGYM_EVAL_ENVS_PER_PARTIAL - 1) / HGYM_EVAL_ENVS_PER_PARTIAL) + \
+                                    (size_t)(2 + HGYM_NUM_REWARDS) * (size_t)(n))
+int32_t hgym_eval_reset(int32_t n, double* block, void* stream);
+int32_t hgym_eval_accumulate(int32_t n, const float* commands, const float* base_lin_vel, const float* base_ang_vel,
+                             const float* episode_sums, const float* rew, const uint8_t* reset, const uint8_t* time_out, double* block,
+                             void* stream);
 
 /* One minibatch of PPO.update up to and including backward (ppo.py:128-171), device side only:
  * gathers rows `idx[0..B)` (indices into the flattened (T*N) storage, rollout_storage.py:151-182) of the
