@@ -191,6 +191,108 @@ class EnvBuffers:
             self.contact.copy_(contact.to(dev).view_as(self.contact))
             self.rigid.copy_(rigid.to(dev).view_as(self.rigid))
 
+    # ---- the state: snapshot / restore --------------------------------------------------------------
+    STATE_FORMAT = 1
+    # Buffers the C structs point to that are NOT part of the state, each with the reason a restored env does not need it.  Every
+    # other buffer the structs name is listed by state_entries(); tests/test_env_state.py holds the two tables against the structs.
+    STATE_EXCLUDED = {
+        "terrain_types": "constant after construction (an env keeps its terrain column)",
+        "terrain_origins": "constant after construction (the terrain map)",
+        "height_samples": "constant after construction (the terrain map)",
+        "height_points": "constant after construction (the sample grid)",
+        "height_pose": "scratch: written and read inside one step",
+        "custom_rew": "scratch: refilled by the caller between the two launches of every split step",
+        "log_cur": "logging state: bind_log_sink zeroes it at every learn()",
+        "log_stats": "logging state: bind_log_sink zeroes it at every learn()",
+        "rollout_scratch": "scratch of one fused rollout: hgym_rollout_begin re-seats its counters, every finaliser leaves its accumulators "
+                           "zero, and a rollout's first launch draws its own noise tables",
+        "_l0_partial": "carried between the launches of one fused rollout only: the first launch of a rollout reads none (rollout_plan)",
+        "reset_idx_mask": "scratch of hgym_env_reset_idx, rebuilt by every call",
+        "reset_idx_ids": "scratch of hgym_env_reset_idx, rebuilt by every call",
+        "reset_idx_rejected": "output of the last hgym_env_reset_idx, overwritten by every call",
+    }
+
+    def state_entries(self):
+        """THE list that defines the state of one env shard: (name, tensor or None, optional) for every buffer a later step reads.
+        `state` is the whole [C][N] block (friction, base mass and env origins included: the domain-randomisation draws survive);
+        `obs` / `priv_obs` are the current observation rows.  An optional entry is None where its option is off."""
+        sim = ([("root", self.root, False), ("dof_pos", self.dof_pos, False), ("dof_vel", self.dof_vel, False)] if self.sim_layout == "soa"
+               else [("root", self.root, False), ("dof_state", self.dof_state, False)])
+        return ([("state", self._state, False), ("episode_length", self.episode_length, False), ("counters", self.counters, False),
+                 ("episode_acc", self.episode_acc, False), ("obs_ring", self.obs_ring, False), ("priv_ring", self.priv_ring, False)]
+                + sim + [("contact", self.contact, False), ("rigid", self.rigid, False),
+                         ("rew", self.rew, False), ("reset", self.reset, False), ("time_out", self.time_out, False),
+                         ("rew_alt", self.rew_alt, False), ("reset_alt", self.reset_alt, False), ("time_out_alt", self.time_out_alt, False),
+                         ("extras_time_outs", self.extras_time_outs, False), ("extras_episode", self.extras_episode, False),
+                         ("obs", self.obs, False), ("priv_obs", self.priv_obs, False),
+                         ("terrain_levels", self.terrain_levels, True), ("measured_heights", self.measured_heights, True),
+                         ("command_range_x", self.command_range_x, True), ("custom_sums", self.custom_sums, True),
+                         ("custom_acc", self.custom_acc, True), ("extras_custom", self.extras_custom, True)])
+
+    def state_meta(self):
+        return dict(version=self.STATE_FORMAT, num_envs=self.N, frame_stack=int(self.cfg.frame_stack), c_frame_stack=int(self.cfg.c_frame_stack),
+                    sim_layout=self.sim_layout, optional={n: t is not None for n, t, opt in self.state_entries() if opt})
+
+    def state_host_buffers(self, pin=True):
+        """Host tensors with the shapes and dtypes of the state entries, pinned by default: what state_dict(out=...) copies into."""
+        mk = lambda t: torch.empty(t.shape, dtype=t.dtype).pin_memory() if pin else torch.empty(t.shape, dtype=t.dtype)
+        return {n: mk(t) for n, t, _ in self.state_entries() if t is not None}
+
+    def state_dict(self, out=None, current=None):
+        """A complete snapshot: {name: tensor} for every entry of state_entries() that exists, plus "meta" (state_meta()).  The
+        tensors are clones on the buffers' own device, enqueued on the current stream; no host synchronisation.  out: a dict of
+        caller-given tensors (state_host_buffers()) that receive the copies instead, non-blocking -- the caller orders its reads
+        behind them with an event.  current: (obs, priv_obs) tensors holding the current observation rows where they are not in
+        this object's own output buffers (an env that writes into a rollout storage): their CONTENTS are copied."""
+        sd = {}
+        with torch.no_grad():
+            for name, t, _ in self.state_entries():
+                if t is None:
+                    continue
+                if current is not None and name in ("obs", "priv_obs"):
+                    t = current[0] if name == "obs" else current[1]
+                if out is None:
+                    sd[name] = t.detach().clone()
+                else:
+                    out[name].copy_(t, non_blocking=True)
+                    sd[name] = out[name]
+        sd["meta"] = self.state_meta()
+        return sd
+
+    def check_state_dict(self, sd):
+        """ValueError naming the first thing in which a snapshot does not fit this object."""
+        meta, mine = sd.get("meta"), self.state_meta()
+        if not isinstance(meta, dict):
+            raise ValueError("env state: no `meta` entry")
+        for key in ("version", "num_envs", "frame_stack", "c_frame_stack", "sim_layout"):
+            if meta.get(key) != mine[key]:
+                raise ValueError("env state: %s is %r in the snapshot, %r here" % (key, meta.get(key), mine[key]))
+        for name, present in mine["optional"].items():
+            if bool(meta.get("optional", {}).get(name, False)) != present or (name in sd) != present:
+                raise ValueError("env state: optional block `%s` is %s in the snapshot and %s here"
+                                 % (name, "present" if name in sd else "absent", "present" if present else "absent"))
+        for name, t, _ in self.state_entries():
+            if t is None:
+                continue
+            if name not in sd:
+                raise ValueError("env state: `%s` is missing from the snapshot" % name)
+            s = sd[name]
+            if tuple(s.shape) != tuple(t.shape) or s.dtype != t.dtype:
+                raise ValueError("env state: `%s` is %s %s in the snapshot, %s %s here" % (name, tuple(s.shape), s.dtype, tuple(t.shape), t.dtype))
+
+    def load_state_dict(self, sd, current=None):
+        """Restore a state_dict() IN PLACE (copy_ into the existing buffers: captured HIP graphs and the cached pointer structs keep
+        their addresses; nothing is re-allocated).  current: where the observation rows go instead of obs / priv_obs.  Refuses with a
+        ValueError naming the mismatch (check_state_dict) before anything is written."""
+        self.check_state_dict(sd)
+        with torch.inference_mode():
+            for name, t, _ in self.state_entries():
+                if t is None:
+                    continue
+                if current is not None and name in ("obs", "priv_obs"):
+                    t = current[0] if name == "obs" else current[1]
+                t.copy_(sd[name])
+
     # ---- C structs ---------------------------------------------------------------------------------
     def _strided(self, t, soa):
         N = self.N

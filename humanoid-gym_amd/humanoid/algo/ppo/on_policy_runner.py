@@ -182,6 +182,8 @@ class OnPolicyRunner:
         self._eval_capture = _CapturedGraph()        # the fused evaluation rollout as a HIP graph of its own (evaluate)
         self.eval_env = None                         # set_eval_env: learn() evaluates on it every cfg["eval_interval"] iterations
         self.last_eval = None
+        self._keep_episode_lengths = False           # set by an exact resume (load): the next learn() keeps the restored episode lengths
+        self._warned_env_state = False
         _, _ = self.env.reset()
 
     _graph = property(lambda self: self._rollout_capture.graph)
@@ -190,6 +192,10 @@ class OnPolicyRunner:
     # ------------------------------------------------------------------
     def learn(self, num_learning_iterations, init_at_random_ep_len=False):
         self._open_writer()
+        if init_at_random_ep_len and self._keep_episode_lengths:
+            init_at_random_ep_len = False            # (once: the episode lengths are part of the env state load() has just restored)
+        self._keep_episode_lengths = False
+        exact = self._exact_resume_on()
         if init_at_random_ep_len:
             self.env.episode_length_buf = torch.randint_like(self.env.episode_length_buf, high=int(self.env.max_episode_length))
         env, alg, log_on = self.env, self.alg, self.log_dir is not None
@@ -247,7 +253,9 @@ class OnPolicyRunner:
                                                              collection_time=collection_time, learn_time=learn_time,
                                                              mean_value_loss=mean_value_loss, mean_surrogate_loss=mean_surrogate_loss))
                 if log_on and it % self.save_interval == 0:
-                    self.save(os.path.join(self.log_dir, "model_{}.pt".format(it)), wait=False)
+                    # (current_learning_iteration still holds the value from the start of learn(), the reference's quirk, and "iter"
+                    # in model_<it>.pt keeps it; the sidecar records the true count)
+                    self.save(os.path.join(self.log_dir, "model_{}.pt".format(it)), wait=False, env_state=exact, iterations_done=it + 1)
                 self._maybe_evaluate(it)            # behind the iteration's timing marks, like everything that is not the iteration
         finally:
             # also on an exception inside the loop: the last finished iteration's log block is printed, the env's bindings released
@@ -262,7 +270,7 @@ class OnPolicyRunner:
         self.current_learning_iteration += num_learning_iterations
         self._check_replicas("end of learn() at iteration %d" % self.current_learning_iteration)
         if log_on:      # (the background writer finishes the file; wait_for_saves() / load() / interpreter exit wait for it: save())
-            self.save(os.path.join(self.log_dir, "model_{}.pt".format(self.current_learning_iteration)), wait=False)
+            self.save(os.path.join(self.log_dir, "model_{}.pt".format(self.current_learning_iteration)), wait=False, env_state=exact)
 
     # ------------------------------------------------------------------ evaluation on mean actions
     def set_eval_env(self, env):
@@ -580,9 +588,45 @@ class OnPolicyRunner:
         """Drop the captured rollout; the next learn() iteration runs eagerly and the one after re-captures."""
         self._rollout_capture, self._update_capture = _CapturedGraph(), _CapturedGraph()
 
-    def save(self, path, infos=None, wait=True):
-        """on_policy_runner.py:274-281 (same dict, same keys).  wait=True (the reference's semantics, and what a direct caller gets): the
-        file is on disk when the call returns.  On the device path the tensors are first copied to pinned host memory stream-side (behind
+    @staticmethod
+    def env_state_path(path):
+        """The sidecar that goes with checkpoint `path`: envstate_<it>.pt next to model_<it>.pt.  Its name never contains "model":
+        helpers.get_load_path takes the last file of a run directory whose name does."""
+        d, base = os.path.split(path)
+        return os.path.join(d, "envstate" + base[len("model"):] if base.startswith("model") else "envstate_" + base.replace("model", "ckpt"))
+
+    def _exact_resume_on(self):
+        """cfg["exact_resume"] (absent: off), on one rank.  Data-parallel runs: every rank's env is its own and only rank 0 writes
+        checkpoints, so env state is not saved there -- said once, and the run goes on as without the switch."""
+        if not self.cfg.get("exact_resume", False):
+            return False
+        if getattr(self.alg, "_world", 1) > 1:
+            if not self._warned_env_state:
+                self._warned_env_state = True
+                print("exact_resume: env state is not saved in a data-parallel run (world size %d); checkpoints are written as without it"
+                      % self.alg._world)
+            return False
+        return True
+
+    def _env_state_extra(self, iterations_done):
+        return dict(iterations_done=int(self.current_learning_iteration if iterations_done is None else iterations_done),
+                    num_steps_per_env=int(self.num_steps_per_env), world_size=int(getattr(self.alg, "_world", 1)),
+                    rank=int(getattr(self.alg, "_rank", 0)))
+
+    def save(self, path, infos=None, wait=True, env_state=False, iterations_done=None):
+        """on_policy_runner.py:274-281 (same dict, same keys).
+
+        env_state=True (learn() passes it when cfg["exact_resume"] is set; `python scripts/train.py` sets that from HGYM_EXACT_RESUME=1)
+        also writes the sidecar env_state_path(path), envstate_<it>.pt: {"env": env.state_dict(), "iterations_done", "num_steps_per_env",
+        "world_size", "rank"} -- with model_<it>.pt everything load() needs to CONTINUE the run bit for bit (see load()).
+        iterations_done: the true number of finished iterations (default current_learning_iteration; learn() passes it + 1 for an
+        in-loop checkpoint, whose "iter" is the stale value the reference writes).  model_<it>.pt itself is unchanged: same four keys,
+        same bytes.  The sidecar is renamed into place BEFORE the model file, so a visible model_<it>.pt of such a run has its sidecar.
+        On the background path the env snapshot follows the parameters': stream-ordered copies into two alternating pinned host sets,
+        the file written by the same writer job.
+
+        wait=True (the reference's semantics, and what a direct caller gets): the file is on disk when the call returns.  On the
+        device path the tensors are first copied to pinned host memory stream-side (behind
         whatever the update has enqueued -- the host does not wait) and pickled + written by a background thread, so a checkpoint costs the
         training thread ~0.1 ms instead of a device sync + 5-15 ms.  learn() passes wait=False for ALL its checkpoints, the final one
         included (round 6: default; `test_background_checkpoint_equals_the_synchronous_one`): the file of the last iteration is complete a
@@ -593,6 +637,12 @@ class OnPolicyRunner:
         net = getattr(self.alg, "net", None)
         if (net is None or not str(self.device).startswith("cuda") or os.environ.get("HGYM_ASYNC_SAVE", "1") == "0"
                 or not hasattr(self.alg.actor_critic, "_net")):
+            if env_state:
+                side = dict(env={k: (v.cpu() if torch.is_tensor(v) else v) for k, v in self.env.state_dict().items()},
+                            **self._env_state_extra(iterations_done))
+                side_path = self.env_state_path(path)
+                torch.save(side, side_path + ".tmp%d" % os.getpid())
+                os.replace(side_path + ".tmp%d" % os.getpid(), side_path)
             torch.save({"model_state_dict": self.alg.actor_critic.state_dict(),
                         "optimizer_state_dict": self.alg.optimizer.state_dict(),
                         "iter": self.current_learning_iteration, "infos": infos}, path)
@@ -612,6 +662,12 @@ class OnPolicyRunner:
             buf["m"].copy_(net.adam_m, non_blocking=True)
             buf["v"].copy_(net.adam_v, non_blocking=True)
             buf["opt"].copy_(net.opt_state, non_blocking=True)
+            side = None
+            if env_state:
+                if "env" not in buf:        # (pinned on first use: a run without the switch allocates nothing)
+                    buf["env"] = self.env.state_host_buffers()
+                side = dict(env=self.env.state_dict(out=buf["env"]), **self._env_state_extra(iterations_done))
+                side_path = self.env_state_path(path)
             done = torch.cuda.Event()
             done.record()
             # name -> (offset, shape) of every parameter in the flat vector: state_dict order = nn.Module's named_parameters order
@@ -644,6 +700,9 @@ class OnPolicyRunner:
                           "iter": it, "infos": infos}
                     tmp = path + ".tmp%d" % os.getpid()
                     tj.append(time.perf_counter())
+                    if side is not None:
+                        torch.save(side, side_path + ".tmp%d" % os.getpid())
+                        os.replace(side_path + ".tmp%d" % os.getpid(), side_path)
                     torch.save(ck, tmp)
                     tj.append(time.perf_counter())
                     os.replace(tmp, path)
@@ -664,12 +723,52 @@ class OnPolicyRunner:
         _WRITER.wait()
         self.save_time_s = getattr(self, "save_time_s", 0.0) + (time.time() - t0)
 
-    def load(self, path, load_optimizer=True):
+    def load(self, path, load_optimizer=True, env_state=None):
+        """on_policy_runner.py:283-290, plus the generators' counters (PPO.seek, LeggedRobot.seek).
+
+        With a sidecar -- envstate_<it>.pt beside `path` (env_state_path), or env_state=<its path>; env_state=False ignores one -- the
+        run CONTINUES: the iteration count becomes the sidecar's iterations_done (the true one, not the model file's "iter"),
+        PPO.seek() gets that count, the env is restored with env.load_state_dict() (its own counters included, so LeggedRobot.seek is
+        not called), and the next learn(..., init_at_random_ep_len=True) keeps the restored episode lengths, once.  With parameters and
+        Adam's state loaded as well, the iterations that follow compute bit for bit what the saved run computed after that checkpoint
+        (tests/test_exact_resume_gpu.py).  The optimiser: loaded when load_optimizer is true, and regardless of it when the run asked for
+        cfg["exact_resume"]; a plain load(path, load_optimizer=False) keeps its meaning.
+
+        Scope.  Exact for PPO.permutation = "device" (the default) on one rank: with "torch" the minibatch permutation comes from
+        torch's global generator, which the sidecar does not carry; a data-parallel run says once that it ignores the sidecar and resumes as without it.
+        The log sink's rings and the host's rewbuffer / lenbuffer are logging state, zeroed at every learn(): the first log blocks
+        after a resume average over fewer episodes.  An evaluation env (set_eval_env) is not touched.  Without a sidecar: as ever."""
         _WRITER.wait()                      # a checkpoint this process is still writing
+        side_path = None
+        if env_state is not False:
+            side_path = env_state if isinstance(env_state, (str, os.PathLike)) else self.env_state_path(path)
+            if not isinstance(env_state, (str, os.PathLike)) and not os.path.exists(side_path):
+                side_path = None
+        if side_path is not None and getattr(self.alg, "_world", 1) > 1:
+            if not self._warned_env_state:
+                self._warned_env_state = True
+                print("exact_resume: %s is not loaded in a data-parallel run (world size %d); resuming as without it"
+                      % (os.path.basename(side_path), self.alg._world))
+            side_path = None
+        side = None
+        if side_path is not None:
+            side = torch.load(side_path, map_location="cpu")
+            if int(side["world_size"]) != 1:
+                raise ValueError("env state: world_size is %d in the sidecar; exact resume covers one rank" % int(side["world_size"]))
+            if int(side["num_steps_per_env"]) != int(self.num_steps_per_env):
+                raise ValueError("env state: num_steps_per_env is %d in the sidecar, %d here" % (int(side["num_steps_per_env"]), self.num_steps_per_env))
+            self.env.check_state_dict(side["env"])      # (a sidecar that does not fit this env: refused before anything is changed)
         loaded = torch.load(path, map_location=self.device)
         self.alg.actor_critic.load_state_dict(loaded["model_state_dict"])
-        if load_optimizer:
+        if load_optimizer or (side is not None and self.cfg.get("exact_resume", False)):
             self.alg.optimizer.load_state_dict(loaded["optimizer_state_dict"])
+        if side is not None:
+            self.current_learning_iteration = int(side["iterations_done"])
+            if hasattr(self.alg, "seek"):
+                self.alg.seek(self.current_learning_iteration, self.num_steps_per_env)
+            self.env.load_state_dict(side["env"])
+            self._keep_episode_lengths = True
+            return loaded["infos"]
         self.current_learning_iteration = loaded["iter"]
         if hasattr(self.alg, "seek"):
             self.alg.seek(self.current_learning_iteration, self.num_steps_per_env)

@@ -496,10 +496,71 @@ class LeggedRobot(BaseTask):
         `iteration` learning iterations has it, so that a resumed run continues the env's draw streams instead of replaying them
         from step 0.  The reference's checkpoint carries no generator state either (on_policy_runner.py:274-281); the counter is
         a function of the iteration number.  The history ring position is left alone, and so is the call number of host-side
-        partial resets (counters[3], the key of reset_idx's draws)."""
+        partial resets (counters[3], the key of reset_idx's draws).  This is a warm start: episodes, commands, histories and
+        curricula stay those of the env as it stands.  A run that is to CONTINUE restores the whole env with state_dict() /
+        load_state_dict() instead (OnPolicyRunner.save(env_state=True) / load()), which carries all four counter words."""
         if not hasattr(self, "_seek_base"):                    # no reset() yet: this IS the fresh env
             self._seek_base = int(self._buf.counters[0])
         self._buf.counters[0] = self._seek_base + int(iteration) * int(steps_per_iteration)
+
+    # ------------------------------------------------------------------ snapshot / restore (native extension)
+    def _refuse_mid_step(self, what):
+        """state_dict() / load_state_dict() see the env between two whole steps only."""
+        if getattr(self, "_pending_fin", None) is not None:
+            raise ValueError("%s: a postponed step finaliser is pending (_pending_fin); run it first (run_finalize)" % what)
+        if getattr(self, "_in_rollout", False):
+            raise ValueError("%s: a fused rollout is open (_in_rollout: rollout_begin ... rollout_end); the state between its launches "
+                             "is partly in flight" % what)
+
+    def state_host_buffers(self, pin=True):
+        """Pinned host tensors for state_dict(out=...) (EnvBuffers.state_host_buffers)."""
+        return self._buf.state_host_buffers(pin)
+
+    def state_dict(self, out=None):
+        """A complete snapshot of this env shard: a flat dict of tensors (EnvBuffers.state_entries: the whole [C][N] state block with the
+        friction / base-mass / origin draws, episode lengths, all four counter words, the episode accumulators, both history rings,
+        the sim tensors, both rew / reset / time_out sets, the extras buffers, the CURRENT observation rows -- copied by content, also
+        where they live in a rollout storage -- and, where the options exist, terrain levels, measured heights, the command-curriculum
+        range and the custom-reward sums) plus "meta": format version, num_envs, history depths, which optional blocks exist, and the
+        host-side bits (the output-set flip, seek()'s base).  Clones on the device, stream-ordered, no host synchronisation; with
+        out = state_host_buffers() the copies go into those (pinned) host tensors instead, non-blocking.
+
+        Not in it, because a later step cannot see them: the fused rollout's scratch block and first-layer partial sums
+        (hgym_rollout_begin re-seats the scratch counters, every finaliser leaves its accumulators zero, and the first launch of a
+        rollout computes its own noise tables and reads no partial sums -- tests/test_exact_resume_gpu.py resumes into an env whose
+        scratch was left by a different number of rollouts); the log sink's rings (zeroed by bind_log_sink at every learn()); the
+        terrain map and sample grid (constant); per-step scratch.  EnvBuffers.STATE_EXCLUDED lists each with its reason.
+
+        Refuses (ValueError) while a postponed finaliser is pending or a fused rollout is open."""
+        self._refuse_mid_step("state_dict")
+        sd = self._buf.state_dict(out=out, current=(self.obs_buf, self.privileged_obs_buf))
+        sd["meta"].update(flip=int(self._flip), seek_base=getattr(self, "_seek_base", None))
+        return sd
+
+    def check_state_dict(self, sd, what="load_state_dict"):
+        """Every refusal of load_state_dict(sd), without writing anything."""
+        self._refuse_mid_step(what)
+        self._buf.check_state_dict(sd)
+        if sd["meta"].get("flip", 0) not in (0, 1):
+            raise ValueError("env state: flip is %r in the snapshot" % (sd["meta"].get("flip"),))
+
+    def load_state_dict(self, sd):
+        """Restore a state_dict() in place: every tensor is copied into the existing buffer (captured HIP graphs and the cached pointer
+        structs keep their addresses), the observation rows into this env's own output set, at which obs_buf / privileged_obs_buf
+        point afterwards.  The env then steps exactly as the env the snapshot was taken from: same draws (all counter words travel,
+        reset_idx's call number included), same episodes, same curricula.  Output bindings of a runner (bind_outputs) are dropped.
+        Refuses with a ValueError naming the mismatch when num_envs, a history depth, the format version or the presence of an
+        optional block differs, while a postponed finaliser is pending, and while a fused rollout is open; nothing is written then."""
+        self.check_state_dict(sd)
+        meta = sd["meta"]
+        flip = int(meta.get("flip", 0))
+        self._buf.load_state_dict(sd, current=self._outs[flip])
+        self._flip, self._bound_out = flip, None
+        self.obs_buf, self.privileged_obs_buf = self._outs[flip]
+        if meta.get("seek_base") is not None:
+            self._seek_base = int(meta["seek_base"])
+        if hasattr(self, "_terrain_level_mean"):
+            torch.mean(self.terrain_levels.float(), dim=0, out=self._terrain_level_mean)
 
     # ------------------------------------------------------------------ fused rollout step (native extension)
     # One launch per vec-step: PPO.act, this env's step (synthetic-physics backend) and the previous step's finaliser

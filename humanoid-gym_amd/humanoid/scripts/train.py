@@ -4,7 +4,11 @@ Several GPUs of one node: the same command line under torch.distributed.run, one
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29500 \\
            humanoid-gym_amd/humanoid/scripts/train.py --task=humanoid_ppo --headless --num_envs 4096
 -- every rank owns --num_envs envs on its own GPU (its own env stream: helpers.shard_seed) and the ranks exchange [gradient | KL] once
-per minibatch (algo/ppo/dist_utils.py); rank 0 alone logs and writes checkpoints (the replicas are bit-identical)."""
+per minibatch (algo/ppo/dist_utils.py); rank 0 alone logs and writes checkpoints (the replicas are bit-identical).
+
+HGYM_EXACT_RESUME=1 sets the train config's `runner.exact_resume` attribute (not a key of the config classes, whose lists are the
+reference's): every checkpoint gets an envstate_<it>.pt sidecar, and --resume from such a checkpoint continues the saved run bit
+for bit instead of warm-starting a new one (OnPolicyRunner.load; one rank)."""
 import os
 import sys
 
@@ -18,6 +22,8 @@ from humanoid.utils.helpers import init_distributed  # noqa: E402
 def train(args):
     rank, world = init_distributed(args)
     env, env_cfg = task_registry.make_env(name=args.task, args=args)
+    if os.environ.get("HGYM_EXACT_RESUME", "0") == "1":
+        task_registry.get_cfgs(args.task)[1].runner.exact_resume = True
     ppo_runner, train_cfg = task_registry.make_alg_runner(env=env, name=args.task, args=args, **({} if rank == 0 else {"log_root": None}))
     ppo_runner.learn(num_learning_iterations=train_cfg.runner.max_iterations, init_at_random_ep_len=True)
     if os.environ.get("HGYM_TRAIN_SIGNATURE"):      # tests: a signature of this rank's final parameters (replicas must agree bit for bit)

@@ -66,7 +66,10 @@ class TaskRegistry:
             load_root = log_root if log_root is not None else os.path.join(LEGGED_GYM_ROOT_DIR, "logs", train_cfg.runner.experiment_name)
             resume_path = get_load_path(load_root, load_run=train_cfg.runner.load_run, checkpoint=train_cfg.runner.checkpoint)
             print(f"Loading model from: {resume_path}")
-            runner.load(resume_path, load_optimizer=False)
+            # as in the reference, a resume is a warm start without the optimiser's state -- unless the run asks for an exact resume
+            # (runner.exact_resume, OnPolicyRunner.load) and the checkpoint has its env-state sidecar: then it continues the saved run
+            exact = bool(getattr(train_cfg.runner, "exact_resume", False)) and os.path.exists(runner.env_state_path(resume_path))
+            runner.load(resume_path, load_optimizer=exact)
         return runner, train_cfg
 
 
