@@ -131,8 +131,13 @@ class XBotEnvOracle:
 
     def __init__(self, n, frictions=None, body_mass=None, frame_stack=C.FRAME_STACK,
                  c_frame_stack=C.C_FRAME_STACK, use_ref_actions=False, terrain=None, command_curriculum=False, max_curriculum=1.0,
-                 heading_command=True, extra_rewards=None):
+                 heading_command=True, extra_rewards=None, reward_scales_dt=None, only_positive_rewards=True, cycle_time=None):
         self.n = n
+        # what a test may set away from the XBot-L configuration: the 22 scales (already times dt, legged_robot.py:523-528),
+        # cfg.rewards.only_positive_rewards (legged_robot.py:229-230) and cfg.rewards.cycle_time (humanoid_env.py:101)
+        self.reward_scales_dt = list(C.REWARD_SCALES_DT if reward_scales_dt is None else reward_scales_dt)
+        self.only_positive_rewards = bool(only_positive_rewards)
+        self.cycle_time = C.CYCLE_TIME if cycle_time is None else cycle_time
         # user-defined reward terms, legged_robot.py:518-541: name -> (fn(oracle) -> (N,) raw value, scale).  Every non-zero scale
         # names a `_reward_<name>` found by getattr; the terms are evaluated and summed in the order of the scales dict, which
         # class_to_dict builds with dir(), i.e. alphabetically (helpers.py:41-56) -- so extra names interleave with the 22 built-in
@@ -207,7 +212,7 @@ class XBotEnvOracle:
     # ------------------------------------------------------------------ gait clock (E9)
     def _sin_phase(self):
         """humanoid_env.py:100-108: int64 * python double -> fp32, / 0.64, * 2pi, sin."""
-        phase = self.ep_len * C.DT / C.CYCLE_TIME
+        phase = self.ep_len * C.DT / self.cycle_time
         return phase, torch.sin(2 * torch.pi * phase)
 
     def _stance_mask(self):
@@ -394,7 +399,7 @@ class XBotEnvOracle:
         """legged_robot.py:422-431: widen lin_vel_x by 0.5 each way (capped) when the resetting envs tracked well."""
         k = C.REWARD_NAMES.index("tracking_lin_vel")
         mean_sum = self.episode_sums[m, k].mean()
-        if bool(mean_sum / float(C.MAX_EPISODE_LENGTH) > 0.8 * C.REWARD_SCALES_DT[k]):     # fp32 tensor against python doubles
+        if bool(mean_sum / float(C.MAX_EPISODE_LENGTH) > 0.8 * self.reward_scales_dt[k]):     # fp32 tensor against python doubles
             lo = min(max(self.cmd_range_x[0] - 0.5, -self.max_curriculum), 0.0)
             hi = min(max(self.cmd_range_x[1] + 0.5, 0.0), self.max_curriculum)
             self.cmd_range_x = [lo, hi]
@@ -527,7 +532,6 @@ class XBotEnvOracle:
         raw = self._rewards()
         extra.update({n: sc(n) for n in self.extra_rewards if n > "feet_clearance"})
         self.rew = torch.zeros(self.n)
-        scales = torch.tensor(C.REWARD_SCALES_DT, dtype=torch.float64)
         self.reward_terms = torch.zeros(self.n, C.NUM_REWARDS)
         for name in sorted(set(C.REWARD_NAMES) | set(extra)):
             if name == "termination":      # legged_robot.py:533-534: not in the function list; added after the clip (:229-235)
@@ -537,11 +541,12 @@ class XBotEnvOracle:
                 self.extra_sums[name] = self.extra_sums[name] + extra[name]
                 continue
             k = C.REWARD_NAMES.index(name)
-            term = raw[:, k] * C.REWARD_SCALES_DT[k]
+            term = raw[:, k] * self.reward_scales_dt[k]
             self.rew = self.rew + term
             self.episode_sums[:, k] += term
             self.reward_terms[:, k] = term
-        self.rew = torch.clip(self.rew, min=0.0)
+        if self.only_positive_rewards:
+            self.rew = torch.clip(self.rew, min=0.0)
         if "termination" in extra:         # legged_robot.py:231-235
             self.rew = self.rew + extra["termination"]
             self.extra_sums["termination"] = self.extra_sums["termination"] + extra["termination"]

@@ -85,7 +85,7 @@ class HostBackend:
     name = "host"
     device = "cpu"
 
-    def __init__(self, envs_per_block=8, nthreads=64, split=False):
+    def __init__(self, envs_per_block=8, nthreads=64, split=False, hist=False):
         """split: the phase sequence of the XBot-L fast kernels (per-joint work on (env, joint) lanes around a shorter per-env
         chain: env_step_phase_j / _a<split> / _f) instead of the monolithic per-env chain; default options only.  2 / 3: that chain on
         four wavefronts by role (env_step_phase_a3 + env_step_reward_sum, what the fused rollout launch runs), its roles emulated in ascending /
@@ -93,7 +93,8 @@ class HostBackend:
         sys.path.insert(0, os.path.join(ROOT, "tests", "hostcheck"))
         import build_hostcheck
         self.lib = C.CDLL(build_hostcheck.build())
-        self.epb, self.nthreads, self.split = envs_per_block, nthreads, int(split)
+        # hist: the older frames of the stacked rows through hist_load / hist_store (what the device kernels run) instead of stack_old
+        self.epb, self.nthreads, self.split = envs_per_block, nthreads, int(split) | (8 if hist else 0)
 
     def step_call(self, mode, cfg, sim, st, out, noise):
         m = {"post": 0, "prime": 1, "reset_all": 2}[mode]

@@ -94,7 +94,11 @@ int hc_env_step(const HgymEnvConfig* cfg, const HgymSimTensors* sim, const HgymE
     return hc_env_step_ex(cfg, sim, st, out, noise, actions_in, mode, fused, epb, nthreads, 0);
 }
 int hc_env_step_ex(const HgymEnvConfig* cfg, const HgymSimTensors* sim, const HgymEnvState* st, const HgymEnvOut* out,
-                   const HgymEnvNoise* noise, float* actions_in, int mode, int fused, int epb, int nthreads, int split) {
+                   const HgymEnvNoise* noise, float* actions_in, int mode, int fused, int epb, int nthreads, int split_arg) {
+    // bit 3 of `split`: the older frames go through hist_load / hist_store, the register-prefetched copy the device kernels use for the
+    // compiled-in geometry, instead of stack_old (XBot-L frame stacks, epb <= 32, nthreads >= 32)
+    const bool hist = (split_arg & 8) != 0 && epb <= 32 && nthreads >= 32;
+    const int split = split_arg & 7;
     const EnvArgs A = make_args(cfg, sim, st, out, noise, actions_in, mode, fused, epb);
     const int N = cfg->num_envs;
     const int blocks = (N + epb - 1) / epb;
@@ -153,7 +157,15 @@ int hc_env_step_ex(const HgymEnvConfig* cfg, const HgymSimTensors* sim, const Hg
         }
         if (!(xbot && A.out.obs_older_ready))
             for (int t = 0; t < nthreads; ++t) {   // the device runs this on its idle wavefronts, concurrently with phase A
-                if (xbot) env_step_stack_old<15, 3, 0>(A, b, t, nthreads, ring);
+                if (xbot && hist && mode != MODE_RESET_ALL) {
+                    const StackGeom g = stack_geom<15, 3, 0>(A, b);
+                    constexpr int NO = HistGeom<15, HGYM_OBS_FRAME>::kSlots, NP = HistGeom<3, HGYM_PRIV_FRAME>::kSlots;   // 32 envs on 32 lanes
+                    float vo[NO][4], vp[NP][4];
+                    hist_load<15, HGYM_OBS_FRAME, NO>(A.st.obs_ring, g.e0, g.nE, (int)(ring % 15), t, nthreads, vo);
+                    hist_store<15, HGYM_OBS_FRAME, NO>(A.out.obs, g.e0, g.nE, (int)(ring % 15), t, nthreads, nullptr, A.cfg.clip_obs, vo);
+                    hist_load<3, HGYM_PRIV_FRAME, NP>(A.st.priv_ring, g.e0, g.nE, (int)(ring % 3), t, nthreads, vp);
+                    hist_store<3, HGYM_PRIV_FRAME, NP>(A.out.priv_obs, g.e0, g.nE, (int)(ring % 3), t, nthreads, nullptr, A.cfg.clip_obs, vp);
+                } else if (xbot) env_step_stack_old<15, 3, 0>(A, b, t, nthreads, ring);
                 else env_step_stack_old<0, 0, 0>(A, b, t, nthreads, ring);
             }
         // (the block sizes the device compiles in take their instantiation: its fast path -- env_stage_out_fast -- where the layout allows)
