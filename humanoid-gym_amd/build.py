@@ -22,6 +22,7 @@ EXTRA = {
     "hgym_gae.hip": ["-ffp-contract=off"],
     "hgym_eval.hip": ["-ffp-contract=off"],          # the accumulator's fp64 expressions as a test restates them, one rounding per operation
     "hgym_rollout.hip": ["-ffp-contract=off"],      # contains the env arithmetic; hgym_fused.hpp restores its own setting by pragma
+    "hgym_rollout_act.hip": ["-ffp-contract=off"],  # the same kernel with any resolved activation (hgym_rollout.hpp)
 }
 
 

@@ -336,24 +336,88 @@ __device__ __forceinline__ float elu_bf(float z) {
     return z > 0.0f ? z : (__builtin_amdgcn_exp2f(z * 1.4426950408889634f) - 1.0f);
 }
 
+// ---- any resolved activation (HgymNetConfig.fused_activation) -------------------------------------------------------------------
+// Every fused device function below takes one more template parameter, GA: false = ELU(1), today's expressions (elu_bf in the
+// epilogues, y > 0 ? 1 : y + 1 in the dZ chain) untouched; true = whatever struct Act (hgym_gemm.hpp) holds, carried in FwdArgs::act.
+//
+// Forward, v = f(v) over a wave's accumulators: one branch on the (wave-uniform) kind around the unrolled element loops, as
+// act_fwd_tile has.  LeakyReLU / ReLU: z > 0 ? z : alpha z.  ELU(alpha) / SELU, Tanh and Sigmoid share one form built on
+// E = expm1(t) -- ONE v_exp_f32 and ONE v_rcp_f32 per element, in the style of elu_bf:
+//     ELU      t = z    scale * (z > 0 ? z : alpha * E)
+//     Tanh     t = 2z   E / (E + 2)                          (= 1 - 2 / (1 + e^2z), without its cancellation at small |z|)
+//     Sigmoid  t = z    e^t / (E + 2)                        (= 1 / (1 + e^-z))
+// with E = exp2(t log2 e) - 1, and t (1 + t / 2) where |t| < 2^-6: there exp2() - 1 cancels (absolute error 1.2e-7, the spacing of
+// fp32 at 1) while the two-term series is within t^2 / 6 <= 4e-5 relative, so E holds ~1e-5 relative or better everywhere -- far below
+// bf16's 2^-9, which is what lets a planted pre-activation of 1e-6 come out within one bf16 ulp.  The exponent is clamped at 120, so
+// e^t stays finite and E / (E + 2) = e^t / (E + 2) = 1 exactly from there on; towards -inf exp2 gives 0 and the forms give
+// -scale alpha, -1 and 0.  No infinity meets a zero: nothing here can produce a NaN from a finite z.
+//
+// f(0) != 0 (Sigmoid: 0.5).  Nothing in the fused kernels relies on f(0) = 0 for its zero padding:
+//   * rows past M in a tile re-read row M - 1 (clamped addresses), so their activations are those of a real row, finite under every
+//     kind; their head gradient dZ3 is written as zero (`valid`), hence every dZ of the chain is 0 * f' = 0 and dW = dZ^T X adds nothing;
+//   * the zeroed older frames of a reset row and the first layer's K padding (705 -> 768, zero input columns against zero weight
+//     fragments) are zeros in the INPUT of a product: they add 0 to a pre-activation, and f is applied to the complete sum + bias;
+//   * hidden widths are multiples of 128 and the head has no activation: no padded column ever passes through f.
+template <int G, int MB>
+__device__ __forceinline__ void act_any_tile(f32x4 (&v)[MB][G], const Act& a) {
+#define HG_FACT_LOOP(BODY)                                       \
+    _Pragma("unroll") for (int i = 0; i < MB; ++i)               \
+        _Pragma("unroll") for (int g = 0; g < G; ++g)            \
+            _Pragma("unroll") for (int e = 0; e < 4; ++e) { BODY; }
+    if (a.kind == HGYM_ACT_LEAKY_RELU) {
+        const float al = a.alpha;
+        HG_FACT_LOOP(const float z = v[i][g][e]; v[i][g][e] = z > 0.0f ? z : __builtin_fmaf(al, z, 0.0f))      /* (+ 0: ReLU's al z = -0 becomes the +0 that f gives) */
+        return;
+    }
+    const bool elu = a.kind == HGYM_ACT_ELU, sig = a.kind == HGYM_ACT_SIGMOID;
+    const float c2 = a.kind == HGYM_ACT_TANH ? 2.0f : 1.0f, k = c2 * 1.4426950408889634f;
+    const float q = elu ? 0.0f : 1.0f, d0 = elu ? 1.0f : 2.0f;          // denominator q E + d0: 1 (ELU), E + 2
+    const float sn = elu ? a.scale * a.alpha : 1.0f, sp = a.scale;
+    const float thr = elu ? 0.0f : INFINITY;                            // the linear side exists for ELU only
+    HG_FACT_LOOP(const float z = v[i][g][e]; const float t = z * c2;
+                 const float ex = __builtin_amdgcn_exp2f(fminf(z * k, 120.0f));
+                 const float em1 = fabsf(t) < 0.015625f ? t * __builtin_fmaf(0.5f, t, 1.0f) : ex - 1.0f;
+                 const float y = (sn * (sig ? ex : em1)) * __builtin_amdgcn_rcpf(__builtin_fmaf(q, em1, d0));
+                 v[i][g][e] = z > thr ? sp * z : y)
+#undef HG_FACT_LOOP
+}
+
 // bias + ELU, bf16, -> LDS block layout (next layer's input) and, when Hg != null, the same blocks in HBM
-template <int G, int MB, bool STORE>
+// (GA: bias + FwdArgs::act, applied to the accumulators in place ahead of the stores)
+template <int G, int MB, bool STORE, bool GA = false>
 __device__ __forceinline__ void epilogue_elu_t(f32x4 (&acc)[MB][G], const float* __restrict__ bias, int nb0, char* out_lds, int CBo,
-                                               __bf16* __restrict__ Hg, int64_t mbg0, int lane) {
+                                               __bf16* __restrict__ Hg, int64_t mbg0, int lane, const Act& fn) {
     const int r = lane & 15, q = lane >> 4;
     const int loff = r * 32 + q * 8;
     static_assert(MB % 2 == 0, "row blocks are stored in pairs");
+    if constexpr (GA) {
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const F4 b = *reinterpret_cast<const F4*>(bias + (nb0 + g) * 16 + 4 * q);
+#pragma unroll
+            for (int i = 0; i < MB; ++i)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[i][g][e] += b.v[e];
+        }
+        act_any_tile<G, MB>(acc, fn);
+    }
 #pragma unroll
     for (int g = 0; g < G; ++g) {
-        const F4 b = *reinterpret_cast<const F4*>(bias + (nb0 + g) * 16 + 4 * q);
+        F4 b = {{0.f, 0.f, 0.f, 0.f}};
+        if constexpr (!GA) b = *reinterpret_cast<const F4*>(bias + (nb0 + g) * 16 + 4 * q);
 #pragma unroll
         for (int i = 0; i < MB; i += 2) {
             u32x2 pk[2];
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 float v[4];
+                if constexpr (GA) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = elu_bf(acc[i + h][g][e] + b.v[e]);
+                    for (int e = 0; e < 4; ++e) v[e] = acc[i + h][g][e];
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = elu_bf(acc[i + h][g][e] + b.v[e]);
+                }
                 pk[h] = pack_bf16x4(v[0], v[1], v[2], v[3]);
                 *reinterpret_cast<u32x2*>(out_lds + ((i + h) * CBo + nb0 + g) * 512 + loff) = pk[h];
             }
@@ -365,11 +429,11 @@ __device__ __forceinline__ void epilogue_elu_t(f32x4 (&acc)[MB][G], const float*
     }
 }
 // (the store decision is wave-uniform and taken once here, not per block inside the unrolled epilogue)
-template <int G, int MB>
+template <int G, int MB, bool GA = false>
 __device__ __forceinline__ void epilogue_elu(f32x4 (&acc)[MB][G], const float* __restrict__ bias, int nb0, char* out_lds, int CBo,
-                                             __bf16* __restrict__ Hg, int64_t mbg0, int lane) {
-    if (Hg) epilogue_elu_t<G, MB, true>(acc, bias, nb0, out_lds, CBo, Hg, mbg0, lane);
-    else epilogue_elu_t<G, MB, false>(acc, bias, nb0, out_lds, CBo, Hg, mbg0, lane);
+                                             __bf16* __restrict__ Hg, int64_t mbg0, int lane, const Act& fn) {
+    if (Hg) epilogue_elu_t<G, MB, true, GA>(acc, bias, nb0, out_lds, CBo, Hg, mbg0, lane, fn);
+    else epilogue_elu_t<G, MB, false, GA>(acc, bias, nb0, out_lds, CBo, Hg, mbg0, lane, fn);
 }
 
 template <int G, int MB>
@@ -390,9 +454,9 @@ __device__ __forceinline__ void hidden_prime(WRing<GR, D>& R, const FusedLayer& 
     if (nb0 < L.NB) wring_prime<G, D>(R, L.Wf + (int64_t)nb0 * L.KB * 64 + lane, L.KB * 64, L.KB);
 }
 
-template <int G, int MB, int NW, int D, bool AHEAD, int GR, class Next>
+template <int G, int MB, int NW, int D, bool AHEAD, bool GA = false, int GR, class Next>
 __device__ __forceinline__ void hidden_layer(WRing<GR, D>& R, const FusedLayer& L, const float* bias, const char* in_lds, int CBin,
-                                             char* out_lds, __bf16* Hg, int64_t mbg0, int wave, int lane, Next prime_next) {
+                                             char* out_lds, __bf16* Hg, int64_t mbg0, int wave, int lane, Next prime_next, const Act& fn) {
     bool primed = false;
     for (int nb0 = wave * G; nb0 < L.NB; nb0 += NW * G) {
         f32x4 acc[MB][G];
@@ -404,7 +468,7 @@ __device__ __forceinline__ void hidden_layer(WRing<GR, D>& R, const FusedLayer& 
         const int nxt = nb0 + NW * G;
         if (nxt < L.NB) wring_prime<G, D>(R, L.Wf + (int64_t)nxt * L.KB * 64 + lane, L.KB * 64, L.KB);
         else if (AHEAD) { prime_next(); primed = true; }
-        epilogue_elu<G, MB>(acc, bias, nb0, out_lds, L.NB, Hg, mbg0, lane);
+        epilogue_elu<G, MB, GA>(acc, bias, nb0, out_lds, L.NB, Hg, mbg0, lane, fn);
     }
     if (AHEAD && !primed) prime_next();       // waves without a strip in this layer
 }
@@ -513,6 +577,8 @@ struct FwdArgs {
     float* logp;              // (M,)
     int nets;                 // networks in this launch (blockIdx.y < nets)
     FinArgs fin;              // postponed env-step finaliser riding in this launch (blockIdx.y == nets, one workgroup); fin.N == 0: none
+    Act act;                  // the hidden layers' activation of every net of the launch; read by the GA instantiations only (last member:
+                              // no other member's offset in the kernel argument moves)
 };
 
 // Hooks of the fused rollout step (hgym_rollout.hip), three callables: `early()` runs once per workgroup right after the tile's
@@ -534,7 +600,7 @@ struct FwdNoop {
     __device__ __forceinline__ void operator()(int, int, int, const float (&)[4]) const {}
 };
 
-template <int BM, int NW, int D, int G1, bool WIDE = false, bool XB16 = false, bool PART = false, class Early = FwdNoop, class Mid = FwdNoop,
+template <int BM, int NW, int D, int G1, bool WIDE = false, bool XB16 = false, bool PART = false, bool GA = false, class Early = FwdNoop, class Mid = FwdNoop,
           class Put = FwdNoop, class Extra = int, class Idle = FwdNoop, class Head = FwdNoop, class L2Idle = FwdNoop>
 __device__ __forceinline__ void fwd_body(const FwdArgs& a, const FusedNet& n, bool is_actor, char* smem, Early&& hook_early = Early(),
                                          Mid&& hook_mid = Mid(), Put&& hook_put = Put(), const Extra& extra = Extra(),
@@ -643,7 +709,7 @@ __device__ __forceinline__ void fwd_body(const FwdArgs& a, const FusedNet& n, bo
         mma_chunk<G1, MB, D, true, XBF>(r0, wl0, L0.KB * 64, (NC - 1) * 4, Q + ((NC - 1) & 1) * (BM * FUSED_CHUNK * 2), 8, lane, acc);
         phase_stamp(a.dbg, 2);
         if (AHEAD) prime1();
-        epilogue_elu<G1, MB>(acc, bl, nb0, P, L0.NB, train_h ? n.H[0] : nullptr, mbg0, lane);
+        epilogue_elu<G1, MB, GA>(acc, bl, nb0, P, L0.NB, train_h ? n.H[0] : nullptr, mbg0, lane, a.act);
     } else {
         const int NC = L0.KB / 4;
         const int CB0 = 2 * L0.KB;
@@ -746,7 +812,7 @@ __device__ __forceinline__ void fwd_body(const FwdArgs& a, const FusedNet& n, bo
         mma_chunk<G1, MB, D, true, XBF>(r0, wl0, L0.KB * 64, (NC - 1 - c0) * 4, Q + ((NC - 1 - c0) & 1) * (BM * FUSED_CHUNK * 2), 8, lane, acc);
         phase_stamp(a.dbg, 2);
         if (AHEAD) prime1();
-        epilogue_elu<G1, MB>(acc, bl, nb0, P, L0.NB, train_h ? n.H[0] : nullptr, mbg0, lane);
+        epilogue_elu<G1, MB, GA>(acc, bl, nb0, P, L0.NB, train_h ? n.H[0] : nullptr, mbg0, lane, a.act);
     }
     __syncthreads();
     phase_stamp(a.dbg, 3);
@@ -754,7 +820,7 @@ __device__ __forceinline__ void fwd_body(const FwdArgs& a, const FusedNet& n, bo
     if (!AHEAD) prime1();
     // ---------------------------------------------------------------- layers 1, 2: input resident in LDS
     auto prime2 = [&]() { hidden_prime<GH, D>(r2, L2, wave, lane); };
-    hidden_layer<GH, MB, NW, D, AHEAD>(r1, L1, bl + L0.N, P, L0.NB, Q, train_h ? n.H[1] : nullptr, mbg0, wave, lane, prime2);
+    hidden_layer<GH, MB, NW, D, AHEAD, GA>(r1, L1, bl + L0.N, P, L0.NB, Q, train_h ? n.H[1] : nullptr, mbg0, wave, lane, prime2, a.act);
     __syncthreads();
     phase_stamp(a.dbg, 4);
     if (!AHEAD) prime2();
@@ -762,7 +828,7 @@ __device__ __forceinline__ void fwd_body(const FwdArgs& a, const FusedNet& n, bo
     auto prime3 = [&]() {
         if (wave < MB) wring_prime<1, 4>(r3, L3.Wf + lane, 0, L3.KB);
     };
-    hidden_layer<GH, MB, NW, D, AHEAD>(r2, L2, bl + L0.N + L1.N, Q, L1.NB, PH2, train_h ? n.H[2] : nullptr, mbg0, wave, lane, prime3);
+    hidden_layer<GH, MB, NW, D, AHEAD, GA>(r2, L2, bl + L0.N + L1.N, Q, L1.NB, PH2, train_h ? n.H[2] : nullptr, mbg0, wave, lane, prime3, a.act);
     if (wave * GH >= L2.NB) hook_l2idle(extra);       // wavefronts without a strip in this layer
     __syncthreads();
     phase_stamp(a.dbg, 5);
@@ -867,6 +933,18 @@ __global__ __launch_bounds__(NW * 64) void mlp_fwd_kernel(const FwdArgs a) {
     else if (g1 == U) fwd_body<BM, NW, D, U>(a, n, which == 0, smem);
 }
 
+// The forward with any resolved activation (GA): ONE net per launch (FwdArgs::net0, grid (tiles, 1)) and one kernel per first hidden
+// width G1U * 256 / wide head, instead of mlp_fwd_kernel's dispatch over three or four tile bodies per kernel.  The GA epilogues are
+// ~90 bytes of code per accumulator element against elu_bf's ~24, and a kernel that carries every body -- mlp_fwd_kernel is 72 .. 97 KB,
+// mlp_fb_kernel 130 000 bytes -- would leave build.py's 128 KiB per kernel behind; these are 20 .. 45 KB each.  A postponed env-step
+// finaliser is the caller's own launch here.
+template <int BM, int NW, int D, int G1U, bool WIDE>
+__global__ __launch_bounds__(NW * 64) void mlp_fwd_act_kernel(const FwdArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int U = 16 / NW;             // n-blocks per wave per 256 columns
+    fwd_body<BM, NW, D, G1U * U, WIDE, false, false, true>(a, a.net[a.net0], !WIDE && a.net0 == 0, smem);
+}
+
 // ================================================================================================ backward (dX chain)
 // dZ_out[m][k'] = (sum_n dZ_in[m][n] * W[n][k']) * elu'(H[m][k']): W^T fragments as the MFMA A operand.
 // R: ring primed with this wave's first strip (bwd_prime); prime_next: called before the epilogue of the last strip.
@@ -879,11 +957,14 @@ __device__ __forceinline__ void bwd_prime(WRing<GR, D>& R, const u32x4* __restri
 // HLDS / H_lds: the tile's y = elu(z) in LDS (block layout, NBo column blocks) instead of the global Hg -- the fused forward +
 // backward kernel still has it there; out_lds may then be the SAME buffer (every lane reads a block entry and later writes that
 // very entry).
-template <int G, int MB, int NW, int D, bool AHEAD, bool HLDS = false, int GR, class Next>
+// GA: f'(z) in Act's parametric form c0 + y (c1 - dq y) on the rounded y, exactly as act_bwd_tile takes it (no branch on the kind)
+template <int G, int MB, int NW, int D, bool AHEAD, bool HLDS = false, bool GA = false, int GR, class Next>
 __device__ __forceinline__ void bwd_step(WRing<GR, D>& R, const u32x4* __restrict__ WTf, int NBo, int NBBc, const char* in_lds, int CBin,
                                          char* out_lds, __bf16* __restrict__ dZg, const __bf16* __restrict__ Hg, int64_t mbg0, int wave,
-                                         int lane, Next prime_next, const char* H_lds = nullptr) {
+                                         int lane, Next prime_next, const char* H_lds = nullptr, const Act* fn = nullptr) {
     const int r = lane & 15, q = lane >> 4;
+    float d0p = 0.f, d1p = 0.f, d0n = 0.f, d1n = 0.f, ndq = 0.f;
+    if constexpr (GA) { d0p = fn->d0p; d1p = fn->d1p; d0n = fn->d0n; d1n = fn->d1n; ndq = -fn->dq; }
     const int loff = r * 32 + q * 8;
     bool primed = false;
     for (int nb0 = wave * G; nb0 < NBo; nb0 += NW * G) {
@@ -914,8 +995,16 @@ __device__ __forceinline__ void bwd_step(WRing<GR, D>& R, const u32x4* __restric
                     const float y[4] = {bf16_bits_to_f32(w0 & 0xffffu), bf16_bits_to_f32(w0 >> 16), bf16_bits_to_f32(w1 & 0xffffu),
                                         bf16_bits_to_f32(w1 >> 16)};
                     float d[4];
+                    if constexpr (GA) {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) d[e] = acc[i + h][g][e] * ((y[e] > 0.0f) ? 1.0f : (y[e] + 1.0f));   // elu'(z) from y = elu(z)
+                        for (int e = 0; e < 4; ++e) {
+                            const bool p = y[e] > 0.0f;
+                            d[e] = acc[i + h][g][e] * fmaf(y[e], fmaf(ndq, y[e], p ? d1p : d1n), p ? d0p : d0n);
+                        }
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) d[e] = acc[i + h][g][e] * ((y[e] > 0.0f) ? 1.0f : (y[e] + 1.0f));   // elu'(z) from y = elu(z)
+                    }
                     pk[h] = pack_bf16x4(d[0], d[1], d[2], d[3]);
                     if (out_lds) *reinterpret_cast<u32x2*>(out_lds + ((i + h) * NBo + nb0 + g) * 512 + loff) = pk[h];
                 }
@@ -981,7 +1070,7 @@ inline int fb_lds_bytes(const int32_t* dims) {
 }
 
 // VU: the unclipped value loss (HgymPPOConfig.value_loss_unclipped); a template parameter, so that the clipped kernels stay as they were
-template <int G1, bool AUX = false, bool XB16 = false, bool VU = false>
+template <int G1, bool AUX = false, bool XB16 = false, bool VU = false, bool GA = false>
 __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const FusedNet& n, bool is_actor, char* smem) {
     constexpr int BM = 64, NW = 16, D = 2, MB = BM / 16;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1180,14 +1269,14 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
         }
     };
     if constexpr (AUX) {
-        fwd_body<BM, NW, D, G1, true, XB16>(a, n, false, smem, FwdNoop(), FwdNoop(), FwdNoop(), 0, FwdNoop(), head_aux, H2, rowidx);
+        fwd_body<BM, NW, D, G1, true, XB16, false, GA>(a, n, false, smem, FwdNoop(), FwdNoop(), FwdNoop(), 0, FwdNoop(), head_aux, H2, rowidx);
         if (wave < MB) {
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) aux_se += __shfl_xor(aux_se, o, 64);
             if (lane == 0) red[wave * 32 + 29] = aux_se;
         }
     } else {
-        fwd_body<BM, NW, D, G1, false, XB16>(a, n, is_actor, smem, FwdNoop(), FwdNoop(), FwdNoop(), 0, FwdNoop(), head, H2, rowidx, l2idle);
+        fwd_body<BM, NW, D, G1, false, XB16, false, GA>(a, n, is_actor, smem, FwdNoop(), FwdNoop(), FwdNoop(), 0, FwdNoop(), head, H2, rowidx, l2idle);
     }
     __syncthreads();          // dZ3 tile and the per-wave sums are in LDS; H0 sits in P, H1 in Q, H2 in its own buffer
     if (tid < 32) {
@@ -1201,13 +1290,13 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
     WRing<G1, D> rc;
     auto none = [&]() {};
     bwd_prime<1, D>(ra, n.layer[3].WTf, N2 / 16, NBB3, wave, lane);
-    bwd_step<1, MB, NW, D, false, true>(ra, n.layer[3].WTf, N2 / 16, NBB3, R0, 2 * NBB3, H2, n.dZ[2], nullptr, mbg0, wave, lane, none, H2);
+    bwd_step<1, MB, NW, D, false, true, GA>(ra, n.layer[3].WTf, N2 / 16, NBB3, R0, 2 * NBB3, H2, n.dZ[2], nullptr, mbg0, wave, lane, none, H2, &a.act);
     __syncthreads();
     bwd_prime<1, D>(rb, n.layer[2].WTf, N1 / 16, n.layer[2].NBB, wave, lane);
-    bwd_step<1, MB, NW, D, false, true>(rb, n.layer[2].WTf, N1 / 16, n.layer[2].NBB, H2, N2 / 16, Q, n.dZ[1], nullptr, mbg0, wave, lane, none, Q);
+    bwd_step<1, MB, NW, D, false, true, GA>(rb, n.layer[2].WTf, N1 / 16, n.layer[2].NBB, H2, N2 / 16, Q, n.dZ[1], nullptr, mbg0, wave, lane, none, Q, &a.act);
     __syncthreads();
     bwd_prime<G1, D>(rc, n.layer[1].WTf, N0 / 16, n.layer[1].NBB, wave, lane);
-    bwd_step<G1, MB, NW, D, false, true>(rc, n.layer[1].WTf, N0 / 16, n.layer[1].NBB, Q, N1 / 16, nullptr, n.dZ[0], nullptr, mbg0, wave, lane, none, P);
+    bwd_step<G1, MB, NW, D, false, true, GA>(rc, n.layer[1].WTf, N0 / 16, n.layer[1].NBB, Q, N1 / 16, nullptr, n.dZ[0], nullptr, mbg0, wave, lane, none, P, &a.act);
     phase_stamp(a.dbg, 7);
 }
 
@@ -1237,6 +1326,44 @@ int32_t launch_mlp_fb_form(const FwdArgs& fb, const FbLoss& fl, bool shadow, int
     if (rc) return rc;
     if (shadow) hipLaunchKernelGGL((mlp_fb_kernel<true, VU>), dim3(tiles, nets), dim3(1024), lds, s, fb, fl);
     else hipLaunchKernelGGL((mlp_fb_kernel<false, VU>), dim3(tiles, nets), dim3(1024), lds, s, fb, fl);
+    return HGYM_OK;
+}
+
+// The update tile with any resolved activation (GA): one net per launch and one kernel per tile body, for the reason given at
+// mlp_fwd_act_kernel (mlp_fb_kernel<false, false> is 130 000 bytes of the 131 072 a kernel may have).  Every net's tiles write their own
+// entries of the per-tile partial sums, so the launches of a minibatch are independent of each other.
+template <int G1, bool AUX, bool XB16, bool VU>
+__global__ __launch_bounds__(1024) void mlp_fb_act_kernel(const FwdArgs a, const FbLoss L) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    fb_body<G1, AUX, XB16, VU, true>(a, L, a.net[a.net0], !AUX && a.net0 == 0, smem);
+}
+
+template <int G1, bool AUX, bool VU>
+int32_t launch_mlp_fb_act_one(const FwdArgs& fb, const FbLoss& fl, bool shadow, int tiles, size_t lds, hipStream_t s) {
+    const int32_t rc = shadow ? ensure_dynamic_lds(reinterpret_cast<const void*>(&mlp_fb_act_kernel<G1, AUX, true, VU>), lds, "mlp_fb_act_kernel<shadow>")
+                              : ensure_dynamic_lds(reinterpret_cast<const void*>(&mlp_fb_act_kernel<G1, AUX, false, VU>), lds, "mlp_fb_act_kernel");
+    if (rc) return rc;
+    if (shadow) hipLaunchKernelGGL((mlp_fb_act_kernel<G1, AUX, true, VU>), dim3(tiles), dim3(1024), lds, s, fb, fl);
+    else hipLaunchKernelGGL((mlp_fb_act_kernel<G1, AUX, false, VU>), dim3(tiles), dim3(1024), lds, s, fb, fl);
+    return HGYM_OK;
+}
+// the launches of mlp_fb_act_kernel for nets [0, nets) of fb0 (hgym_update_act.hip: clipped value loss, hgym_update_act_vu.hip: unclipped)
+template <bool VU>
+int32_t launch_mlp_fb_act_form(const FwdArgs& fb0, const FbLoss& fl, bool shadow, int tiles, int nets, hipStream_t s) {
+    for (int i = 0; i < nets; ++i) {
+        FwdArgs fb = fb0;
+        fb.net0 = i;
+        fb.nets = 1;
+        if (fb.dbg) fb.dbg += (int64_t)i * tiles * 8;      // phase stamps: this net's slots
+        const size_t lds = (size_t)fb_lds_bytes(fb.net[i]);
+        const int g1 = fb.net[i].layer[0].NB / 16;         // first hidden width 256 / 512 / 768
+        int32_t rc = HGYM_E_UNSUPPORTED;
+        if (i == 2) rc = launch_mlp_fb_act_one<2, true, VU>(fb, fl, shadow, tiles, lds, s);      // the auxiliary head: first width 512
+        else if (g1 == 1) rc = launch_mlp_fb_act_one<1, false, VU>(fb, fl, shadow, tiles, lds, s);
+        else if (g1 == 2) rc = launch_mlp_fb_act_one<2, false, VU>(fb, fl, shadow, tiles, lds, s);
+        else if (g1 == 3) rc = launch_mlp_fb_act_one<3, false, VU>(fb, fl, shadow, tiles, lds, s);
+        if (rc) return rc;
+    }
     return HGYM_OK;
 }
 

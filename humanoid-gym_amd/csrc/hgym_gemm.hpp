@@ -45,8 +45,9 @@ enum { ACT_NONE = 0, ACT_APPLY = 1 };
 
 // The hidden layers' activation (HgymNetConfig.activation), resolved by the host (act_resolve, hgym_net.hip): defaults filled in,
 // SELU folded into the ELU form.  act_fwd_tile / act_bwd_tile apply it on the generic path with libm (fp32 parity within
-// 1e-5 of torch).  The fused bf16 kernels (hgym_fused.hpp) implement ELU(1) only: a configuration with any other activation
-// takes this path (fused_supported, hgym_net.hip).
+// 1e-5 of torch).  The fused bf16 kernels (hgym_fused.hpp) have two instantiations: ELU(1), and a generic one (act_any_tile, fast
+// hardware exp2 / rcp forms) that a configuration with any other activation takes only when it sets HgymNetConfig.fused_activation;
+// without the flag such a configuration takes this path (ws_layout, hgym_net.hip).
 struct Act {
     int kind;            // HGYM_ACT_ELU (also SELU), HGYM_ACT_LEAKY_RELU, HGYM_ACT_TANH, HGYM_ACT_SIGMOID
     float alpha, scale;  // ELU: scale * (z > 0 ? z : alpha * (exp(z) - 1)); LeakyReLU: alpha = the negative slope
@@ -55,6 +56,9 @@ struct Act {
     // Tanh: (1, 0) both, dq 1 (1 - y^2); Sigmoid: (0, 1) both, dq 1 (y (1 - y)).
     float d0p, d1p, d0n, d1n, dq;
 };
+
+// the activation of the fused bf16 kernels' default instantiation; every other resolved one runs their generic instantiation
+inline bool act_is_elu1(const Act& a) { return a.kind == HGYM_ACT_ELU && a.alpha == 1.0f && a.scale == 1.0f; }
 
 struct GemmArgs {
     const void* A;     // [rowsA][lda]  K-contiguous

@@ -21,6 +21,9 @@ namespace hgym {
 
 // hgym_update.hip
 int32_t launch_mlp_fb(const FwdArgs& fb, const FbLoss& fl, bool shadow, bool unclipped, int tiles, int nets, size_t lds, hipStream_t s);
+// hgym_update_act.hip, hgym_fwd_act.hip: the same tiles with any resolved activation, one launch per net
+int32_t launch_mlp_fb_act(const FwdArgs& fb, const FbLoss& fl, bool shadow, bool unclipped, int tiles, int nets, hipStream_t s);
+int32_t launch_mlp_fwd_act(const FwdArgs& a, int nets, bool wide, int64_t dbg_tiles, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------ layouts
 struct LayerLayout {
@@ -122,8 +125,6 @@ static int32_t act_resolve(const HgymNetConfig* c, Act* a) {
     }
     return HGYM_OK;
 }
-// the activation the fused bf16 kernels implement (their epilogues and dZ chain are ELU(1) only)
-static bool act_is_elu1(const Act& a) { return a.kind == HGYM_ACT_ELU && a.alpha == 1.0f && a.scale == 1.0f; }
 
 static int32_t ws_layout(const HgymNetConfig* c, WsLayout* w) {
     HG_REQUIRE(c, HGYM_E_BADARG, "null net config");
@@ -143,7 +144,9 @@ static int32_t ws_layout(const HgymNetConfig* c, WsLayout* w) {
     w->SE = c->precision == HGYM_F32 ? stage_elems<float>() : stage_elems<__bf16>();
     w->maxM = c->max_batch;
     w->Mp = round_up(c->max_batch, w->SE);
-    const bool fused = fused_supported(c) && act_is_elu1(w->act);
+    HG_REQUIRE(c->fused_activation == 0 || c->fused_activation == 1, HGYM_E_BADARG,
+               "HgymNetConfig.fused_activation=%d (0: the fused bf16 kernels for ELU(1) only, 1: for any activation)", c->fused_activation);
+    const bool fused = fused_supported(c) && (act_is_elu1(w->act) || c->fused_activation == 1);
     w->Mpad = round_up(c->max_batch, 64);
     int64_t off = 0, poff = c->num_actions;  // std first (state_dict order)
     auto take = [&](int64_t bytes) {
@@ -1142,6 +1145,19 @@ struct FusedPath : NetBase {
     }
     template <int BM, int NW, int D>
     int32_t launch_fwd(const FwdArgs& a, int nets) {
+        if (!act_is_elu1(w.act)) {      // the generic instantiation: one launch per net, the postponed finaliser as its own (tiny) launch
+            if (a.fin.N > 0) {
+                hipLaunchKernelGGL(fin_only_kernel, dim3(1), dim3(1024), 0, s, a.fin);
+                HG_CHECK_LAUNCH("fin_only_kernel");
+            }
+            FwdArgs b = a;
+            const int64_t tiles = ceil_div(a.M, BM);
+            b.dbg = phase_buffer(tiles * nets);
+            const int32_t rc = launch_mlp_fwd_act(b, nets, BM == 64, tiles, s);
+            if (rc) return rc;
+            HG_CHECK_LAUNCH("mlp_fwd_act_kernel");
+            return HGYM_OK;
+        }
         return a.fin.N > 0 ? launch_fwd_k<BM, NW, D, true>(a, nets) : launch_fwd_k<BM, NW, D, false>(a, nets);
     }
 
@@ -1156,6 +1172,7 @@ struct FusedPath : NetBase {
             if (first <= 1 && first + nets > 1 && sh->priv) { a.net[1].xs = (__bf16*)sh->priv; a.net[1].ldxs = sh->ld_priv; }
         }
         a.net0 = first;
+        a.act = w.act;
         a.M = M;
         a.idx = idx;
         if (fin) a.fin = *fin;
@@ -1337,7 +1354,8 @@ struct FusedPath : NetBase {
             fb.nets = nets;
             fb.dbg = phase_buffer((int64_t)tiles * nets);
             prof_begin(HGYM_PROF_MLP_FWD, s);
-            const int32_t rc_fb = launch_mlp_fb(fb, fl, shadow, ppo.value_loss_unclipped != 0, tiles, nets, lds, s);      // (hgym_update.hip: the kernel's own code object)
+            const int32_t rc_fb = act_is_elu1(w.act) ? launch_mlp_fb(fb, fl, shadow, ppo.value_loss_unclipped != 0, tiles, nets, lds, s)      // (hgym_update.hip: the kernel's own code object)
+                                                     : launch_mlp_fb_act(fb, fl, shadow, ppo.value_loss_unclipped != 0, tiles, nets, s);
             if (rc_fb) return rc_fb;
             double flops = 0.0;
             for (int i = 0; i < nets; ++i) {

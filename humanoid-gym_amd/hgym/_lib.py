@@ -108,7 +108,8 @@ class NetConfig(C.Structure):
                 ("actor_dims", C.c_int32 * (MAX_LAYERS + 1)), ("critic_dims", C.c_int32 * (MAX_LAYERS + 1)),
                 ("precision", C.c_int32), ("max_batch", C.c_int32),
                 ("aux_layers", C.c_int32), ("aux_dims", C.c_int32 * (MAX_LAYERS + 1)), ("aux_target_offset", C.c_int32),
-                ("activation", C.c_int32), ("act_alpha", C.c_float), ("act_scale", C.c_float)]
+                ("activation", C.c_int32), ("act_alpha", C.c_float), ("act_scale", C.c_float),
+                ("fused_activation", C.c_int32)]
 
 
 class PPOConfig(C.Structure):

@@ -34,11 +34,15 @@ def activation_spec(activation):
 
 
 def make_net_config(num_obs, num_priv, num_actions, actor_hidden, critic_hidden, precision, max_batch, aux_hidden=None, aux_out=0,
-                    aux_target_offset=0, activation=None):
+                    aux_target_offset=0, activation=None, fused_activation=False):
     """aux_hidden / aux_out / aux_target_offset: the optional auxiliary (denoising) head obs -> aux_hidden -> aux_out that regresses
     columns [aux_target_offset, aux_target_offset + aux_out) of the privileged row (HgymNetConfig.aux_*).
-    activation: the torch module between the Linear layers of every MLP (activation_spec; None: ELU)."""
+    activation: the torch module between the Linear layers of every MLP (activation_spec; None: ELU).
+    fused_activation: HgymNetConfig.fused_activation -- a bf16 net of the widths the fused kernels take runs them (forward, update tiles,
+    bf16 observation shadow) with any activation, not only ELU(1); off by default, because the fused kernels' fast exp2 / rcp forms round
+    differently from the layer-by-layer path's libm.  Ignored where the fused kernels are refused anyway; no effect on ELU(1)."""
     c = L.NetConfig()
+    c.fused_activation = 1 if fused_activation else 0
     c.activation, c.act_alpha, c.act_scale = activation_spec(activation)
     c.num_obs, c.num_priv, c.num_actions = int(num_obs), int(num_priv), int(num_actions)
     ad = [num_obs] + list(actor_hidden) + [num_actions]

@@ -8,6 +8,7 @@ act / evaluate / log-prob run through libhgym_hip.so (MFMA forward, fused Gaussi
 kernels update the very memory the module's parameters alias.
 """
 import math
+import os
 
 import torch
 import torch.nn as nn
@@ -27,17 +28,21 @@ def _mlp(sizes, activation):
 class ActorCritic(nn.Module):
     def __init__(self, num_actor_obs, num_critic_obs, num_actions, actor_hidden_dims=[256, 256, 256],
                  critic_hidden_dims=[256, 256, 256], init_noise_std=1.0, activation=nn.ELU(), denoiser_hidden_dims=None,
-                 denoiser_targets=0, **kwargs):
+                 denoiser_targets=0, fused_activation=None, **kwargs):
         """denoiser_hidden_dims / denoiser_targets (native extension, BASELINE configs[4]): an auxiliary head
         obs -> denoiser_hidden_dims -> denoiser_targets that regresses the newest `denoiser_targets` columns of the
         privileged observation (the clean single-frame privileged state) from the noisy observation history; trained jointly
-        with PPO (PPO(denoise_coef=...)).  The reference has no code for it (README.md:113); off by default."""
+        with PPO (PPO(denoise_coef=...)).  The reference has no code for it (README.md:113); off by default.
+        fused_activation (native extension): run the fused bf16 kernels with `activation` whatever it is, not only with ELU(1)
+        (HgymNetConfig.fused_activation; PPO passes it into the net config).  None: the environment variable HGYM_FUSED_ACT ("1": on),
+        else off."""
         if kwargs:
             print("ActorCritic.__init__ got unexpected arguments, which will be ignored: " + str(list(kwargs.keys())))
         super().__init__()
         from hgym.net import activation_spec
         activation_spec(activation)          # NotImplementedError (listing what is supported) for anything the kernels lack
         self.activation = activation
+        self.fused_activation = (os.environ.get("HGYM_FUSED_ACT", "0") == "1") if fused_activation is None else bool(fused_activation)
         self.num_actor_obs, self.num_critic_obs, self.num_actions = num_actor_obs, num_critic_obs, num_actions
         self.actor_hidden_dims, self.critic_hidden_dims = list(actor_hidden_dims), list(critic_hidden_dims)
         self.actor = _mlp([num_actor_obs] + self.actor_hidden_dims + [num_actions], activation)

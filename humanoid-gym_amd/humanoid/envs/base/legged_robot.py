@@ -603,9 +603,13 @@ class LeggedRobot(BaseTask):
             return None
         want = os.environ.get("HGYM_ROLLOUT_CRITIC", "auto").lower()
         tiles = self.num_envs // 32
-        if want != "deferred" and 2 * tiles <= cus:
+        # the launch WITH critic tiles is built for ELU(1) only (its kernel with the generic epilogues of two tiles would pass the
+        # per-kernel code limit): a net on the fused kernels with another activation (HgymNetConfig.fused_activation) takes the
+        # deferred form at every env count.  (HGYM_ACT_ELU = 0 with alpha, scale 0 or 1; a record without the fields is an ELU(1) one)
+        elu1 = getattr(nc, "activation", 0) == 0 and getattr(nc, "act_alpha", 0.0) in (0.0, 1.0) and getattr(nc, "act_scale", 0.0) in (0.0, 1.0)
+        if want != "deferred" and 2 * tiles <= cus and elu1:
             return "inline"
-        if want != "inline" and tiles <= cus:
+        if (want != "inline" or not elu1) and tiles <= cus:
             return "deferred"
         return None
 

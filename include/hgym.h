@@ -48,6 +48,8 @@ extern "C" {
                              *    Tanh or Sigmoid between the Linear layers; a zero-filled tail is the ELU(1) every earlier layout meant)
                              *    (same version, later still: HgymPPOConfig.value_loss_unclipped appended -- the value loss (R - V)^2 instead of
                              *    the clipped form; a zero-filled tail is the clipped loss every earlier layout meant)
+                             *    (same version, later: HgymNetConfig.fused_activation appended -- the fused bf16 forward / update kernels for
+                             *    every activation instead of ELU(1) only; a zero-filled tail is the ELU(1)-only rule every earlier layout meant)
                              *    (same version, later: hgym_env_reset_idx -- reset_idx for a caller-chosen subset of envs, its draws keyed by
                              *    the call number in HgymEnvState.counters[3]; no layout changes)
                              *    (same version, later: hgym_rollout_eval_step -- the rollout launch on the policy's mean action -- and the
@@ -428,9 +430,9 @@ enum { HGYM_F32 = 0, HGYM_BF16 = 1 };
  * 1 : alpha; Tanh: 1 - y^2; Sigmoid: y (1 - y)), so no kind needs more workspace than another.  Anything else (an unknown kind,
  * alpha or scale < 0, a parameter a kind does not use set) is refused by hgym_net_param_count / hgym_net_workspace_bytes and
  * every call taking the configuration.
- * Supported: every kind at HGYM_F32 and HGYM_BF16 on the layer-by-layer GEMM path; the fused bf16 kernels (hgym_rollout_step, the
- * update's fused tiles) implement ELU(1) only, so a bf16 configuration with any other activation runs the GEMM path, as a net too
- * wide for the fused tiles' LDS does. */
+ * Supported: every kind at HGYM_F32 and HGYM_BF16 on the layer-by-layer GEMM path.  The fused bf16 kernels take ELU(1), and every
+ * other kind when HgymNetConfig.fused_activation = 1 (hgym_rollout_step: in its values = NULL form); without it a
+ * bf16 configuration with another activation runs the GEMM path, as a net too wide for the fused tiles' LDS does. */
 enum { HGYM_ACT_ELU = 0, HGYM_ACT_SELU = 1, HGYM_ACT_LEAKY_RELU = 2, HGYM_ACT_TANH = 3, HGYM_ACT_SIGMOID = 4 };
 
 typedef struct HgymNetConfig {
@@ -450,6 +452,17 @@ typedef struct HgymNetConfig {
     int32_t aux_target_offset;
     int32_t activation;                                  /* HGYM_ACT_* (0: ELU, the reference default) */
     float act_alpha, act_scale;                          /* its parameters, see HGYM_ACT_* (0, 0: the kind's defaults) */
+    int32_t fused_activation;       /* which activations take the fused bf16 kernels (forward tiles, the update's fused tiles, the bf16
+                                         observation shadow), in a bf16 configuration those kernels accept:
+                                         0: ELU(1) only; every other activation runs the layer-by-layer GEMM path  (the default)
+                                         1: any resolved activation, through the kernels' generic instantiation: hardware exp2 / rcp forms
+                                            where the GEMM path calls libm, so the two paths round differently (both within the bf16 bars).
+                                            With ELU(1) it changes nothing: same kernels, same bits.  hgym_rollout_eval_step and
+                                            hgym_rollout_step with values = NULL serve such a net; hgym_rollout_step WITH the critic's
+                                            tiles (values != NULL) is built for ELU(1) only and returns HGYM_E_UNSUPPORTED.
+                                       Ignored wherever the fused kernels are refused anyway (HGYM_F32, widths they do not take, an
+                                       auxiliary head outside their shapes).  Any other value: HGYM_E_BADARG from every call taking the
+                                       configuration.  Appended later within header v9, so a zero-filled tail is ELU(1) only. */
 } HgymNetConfig;
 
 typedef struct HgymPPOConfig {
