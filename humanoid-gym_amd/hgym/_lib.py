@@ -204,6 +204,9 @@ SYMBOLS = {
                                            c_float_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "hgym_eval_reset": (C.c_int32, [C.c_int32, c_f64_p, C.c_void_p]),
     "hgym_eval_accumulate": (C.c_int32, [C.c_int32, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, c_u8_p, c_u8_p, c_f64_p, C.c_void_p]),
+    "hgym_ppo_diag_reset": (C.c_int32, [C.c_int64, c_f64_p, C.c_void_p]),
+    "hgym_ppo_diag_reduce": (C.c_int32, [C.c_int64] + [c_float_p] * 10 + [C.c_float, C.c_int64, C.c_int64, C.c_int32, c_f64_p, C.c_void_p]),
+    "hgym_ppo_diagnostics": (C.c_int32, [_P(NetConfig), _P(PPOConfig), _P(Net), _P(Batch), C.c_int64, c_float_p, c_f64_p, C.c_void_p]),
     "hgym_ppo_grad": (C.c_int32, [_P(NetConfig), _P(PPOConfig), _P(Net), _P(Batch), C.c_void_p]),
     "hgym_ppo_grad_part": (C.c_int32, [_P(NetConfig), _P(PPOConfig), _P(Net), _P(Batch), C.c_int32, C.c_void_p]),
     "hgym_net_param_offset": (C.c_int64, [_P(NetConfig), C.c_int32]),
@@ -303,3 +306,20 @@ def gae_stats(n, device):
     """The `stats` buffer of hgym_gae / hgym_gae_bootstrap for n envs: HGYM_GAE_STATS_DOUBLES(n) zero-filled doubles (include/hgym.h)."""
     import torch
     return torch.zeros(4 + 2 * ((int(n) + 15) // 16), dtype=torch.float64, device=device)
+
+
+# the diagnostics pass's block (include/hgym.h: HGYM_DIAG_*)
+DIAG_SUMS, DIAG_ROWS_PER_PARTIAL = 16, 256
+(DIAG_COUNT, DIAG_KL, DIAG_APPROX_KL, DIAG_RATIO, DIAG_CLIPPED, DIAG_RATIO_MAX, DIAG_RATIO_MIN, DIAG_SURROGATE, DIAG_RET, DIAG_RET_SQ,
+ DIAG_ERR_OLD, DIAG_ERR_OLD_SQ, DIAG_ERR_NEW, DIAG_ERR_NEW_SQ, DIAG_VALUE_CLIPPED, DIAG_ENTROPY) = range(16)
+
+
+def diag_block_doubles(total_rows):
+    """HGYM_DIAG_BLOCK_DOUBLES(total_rows) of include/hgym.h."""
+    return DIAG_SUMS * (1 + (int(total_rows) + DIAG_ROWS_PER_PARTIAL - 1) // DIAG_ROWS_PER_PARTIAL)
+
+
+def diag_block(total_rows, device):
+    """The block of hgym_ppo_diag_reset / hgym_ppo_diag_reduce / hgym_ppo_diagnostics for total_rows rows, zero-filled."""
+    import torch
+    return torch.zeros(diag_block_doubles(total_rows), dtype=torch.float64, device=device)

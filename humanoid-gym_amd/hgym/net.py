@@ -194,6 +194,24 @@ class NetBuffers:
                                       L.fptr(out["logp"]), L.fptr(out["values"]), sh, self.stream()), "hgym_policy_act")
         return out
 
+    def ppo_diagnostics(self, ppo, cols, out_block):
+        """hgym_ppo_diagnostics over the rows of `cols` -- the nine flattened storage columns in make_batch's order (obs, priv, actions,
+        values, advantages, returns, logp, mu, sigma), contiguous fp32, any number M of rows -- with the parameters as they are now:
+        hgym_ppo_diag_reset, the two forwards piece by piece, the reduction.  out_block: L.diag_block(M, device) of the caller; it
+        holds the sums afterwards in stream order (diag_from_block reads them).  Nothing is read back, nothing allocated after the
+        first call (the forwards' scratch, max_batch x 13 floats, is kept)."""
+        M = int(cols[0].shape[0])
+        for t in cols:
+            assert t.is_contiguous() and t.dtype == torch.float32 and t.shape[0] == M
+        assert out_block.dtype == torch.float64 and out_block.is_contiguous() and out_block.numel() >= L.diag_block_doubles(M)
+        if getattr(self, "_diag_scratch", None) is None:
+            self._diag_scratch = torch.empty(int(self.cfg.max_batch) * 13, dtype=torch.float32, device=self.device)
+        rows = L.Batch(*[L.fptr(t) for t in cols], None, 0, None, None, M)
+        L.check(L.lib.hgym_ppo_diag_reset(M, L.f64ptr(out_block), self.stream()), "hgym_ppo_diag_reset")
+        L.check(L.lib.hgym_ppo_diagnostics(C.byref(self.cfg), C.byref(ppo), C.byref(self.struct), C.byref(rows), M, L.fptr(self._diag_scratch),
+                                           L.f64ptr(out_block), self.stream()), "hgym_ppo_diagnostics")
+        return out_block
+
     def ppo_grad(self, ppo, batch):
         L.check(L.lib.hgym_ppo_grad(C.byref(self.cfg), C.byref(ppo), C.byref(self.struct), C.byref(batch), self.stream()), "hgym_ppo_grad")
 
@@ -226,3 +244,36 @@ def make_batch(obs, priv, actions, values, advantages, returns, logp, mu, sigma,
         sb = (C.c_void_p(obs_bf16.data_ptr()), C.c_void_p(priv_bf16.data_ptr()))
     return L.Batch(L.fptr(obs), L.fptr(priv), L.fptr(actions), L.fptr(values), L.fptr(advantages), L.fptr(returns), L.fptr(logp),
                    L.fptr(mu), L.fptr(sigma), L.i64ptr(idx), int(idx.numel()), sb[0], sb[1], int(obs.shape[0]))
+
+
+DIAG_KEYS = ("samples", "clip_fraction", "kl", "approx_kl", "ratio_mean", "ratio_max", "ratio_min", "surrogate", "entropy",
+             "value_clip_fraction", "return_mean", "return_std", "explained_variance", "explained_variance_new", "value_rmse",
+             "value_rmse_new")
+
+
+def diag_from_block(block, clip_param=None):
+    """The sums of a diagnostics block (hgym_ppo_diag_reduce's totals, block[:HGYM_DIAG_SUMS]: a tensor, or any sequence of 16 numbers)
+    -> a dict of python floats, DIAG_KEYS:
+      samples (int), clip_fraction (rows whose ratio left [1 - clip, 1 + clip]), kl (mean analytic KL(old || new)), approx_kl (mean of
+      ratio - 1 - log ratio), ratio_mean / ratio_max / ratio_min, surrogate (the clipped surrogate loss over the whole batch), entropy,
+      value_clip_fraction (rows with |V_new - V_old| > clip), return_mean / return_std (population), explained_variance = 1 -
+      Var(R - V_old) / Var(R) for the critic that collected the data and explained_variance_new for the updated one, value_rmse /
+      value_rmse_new = sqrt(mean (R - V)^2).
+    Var(R) == 0: nan for both explained variances; samples == 0: nan for everything but samples.  Pure host arithmetic in python
+    doubles.  clip_param is not needed (the counts were taken on the device); accepted so that callers may pass what they ran with."""
+    import math
+    b = [float(x) for x in (block[:L.DIAG_SUMS].tolist() if hasattr(block, "tolist") else list(block)[:L.DIAG_SUMS])]
+    n = b[L.DIAG_COUNT]
+    nan = float("nan")
+    if n <= 0:
+        return dict({k: nan for k in DIAG_KEYS}, samples=0)
+    mean = lambda i: b[i] / n
+    var = lambda i, i2: max(b[i2] / n - (b[i] / n) ** 2, 0.0)
+    var_r = var(L.DIAG_RET, L.DIAG_RET_SQ)
+    ev = lambda i, i2: (1.0 - var(i, i2) / var_r) if var_r > 0.0 else nan
+    return dict(samples=int(n), clip_fraction=mean(L.DIAG_CLIPPED), kl=mean(L.DIAG_KL), approx_kl=mean(L.DIAG_APPROX_KL),
+                ratio_mean=mean(L.DIAG_RATIO), ratio_max=b[L.DIAG_RATIO_MAX], ratio_min=b[L.DIAG_RATIO_MIN], surrogate=mean(L.DIAG_SURROGATE),
+                entropy=mean(L.DIAG_ENTROPY), value_clip_fraction=mean(L.DIAG_VALUE_CLIPPED), return_mean=mean(L.DIAG_RET),
+                return_std=math.sqrt(var_r), explained_variance=ev(L.DIAG_ERR_OLD, L.DIAG_ERR_OLD_SQ),
+                explained_variance_new=ev(L.DIAG_ERR_NEW, L.DIAG_ERR_NEW_SQ), value_rmse=math.sqrt(mean(L.DIAG_ERR_OLD_SQ)),
+                value_rmse_new=math.sqrt(mean(L.DIAG_ERR_NEW_SQ)))

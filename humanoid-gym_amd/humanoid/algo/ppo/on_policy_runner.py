@@ -182,6 +182,9 @@ class OnPolicyRunner:
         self._eval_capture = _CapturedGraph()        # the fused evaluation rollout as a HIP graph of its own (evaluate)
         self.eval_env = None                         # set_eval_env: learn() evaluates on it every cfg["eval_interval"] iterations
         self.last_eval = None
+        self.last_diag = None                        # PPO.diagnostics() of the last iteration cfg["diag_interval"] selected (learn)
+        self.last_diag_iteration = None
+        self._diag_pin = None
         self._keep_episode_lengths = False           # set by an exact resume (load): the next learn() keeps the restored episode lengths
         self._warned_env_state = False
         _, _ = self.env.reset()
@@ -222,6 +225,9 @@ class OnPolicyRunner:
         if not plan.graph_update:
             self._update_capture.graph = None
         pending, marks = None, []
+        # cfg["diag_interval"] (0 / absent: never): every that many iterations PPO.diagnostics() right behind the update, outside both graphs
+        diag_every = int(self.cfg.get("diag_interval", 0) or 0) if hasattr(alg, "diagnostics") else 0
+        diag_wait = None
         try:
             for it in range(self.current_learning_iteration, self.current_learning_iteration + num_learning_iterations):
                 start = time.time()
@@ -236,7 +242,11 @@ class OnPolicyRunner:
                         torch.cuda.synchronize()
                 stop = time.time()
                 collection_time, start = stop - start, stop
+                diag_now = diag_every > 0 and (it + 1) % diag_every == 0
+                if diag_now:
+                    alg.diagnostics_prepare()       # slot 0's observation rows, before the update's clear() rotates them away
                 mean_value_loss, mean_surrogate_loss = self._learn_step(plan, gkey, ukey, critic_obs)
+                diag = alg.diagnostics(sync=False) if diag_now else None       # enqueued; read where this path reads anything
                 if plan.zero_copy:                  # storage.clear() rotated slot T into slot 0
                     obs, critic_obs = obs_all[0], priv_all[0]
                 if it % self.save_interval == 0:
@@ -246,9 +256,13 @@ class OnPolicyRunner:
                     ev[2].record()
                 if plan.async_mode == "events":
                     marks.append(ev)
+                    if diag is not None:
+                        diag_wait = (it, self._diag_snapshot(diag, 0))      # read once, behind the loop's last event
                 elif plan.async_mode == "log":
-                    pending = self._finish_async_log(it, ev, pending, num_learning_iterations)
+                    pending = self._finish_async_log(it, ev, pending, num_learning_iterations, diag)
                 else:
+                    if diag is not None:
+                        self._diag_publish(it, diag.cpu())      # (this path synchronises every iteration anyway)
                     self._finish_sync(plan, log, rings, dict(it=it, num_learning_iterations=num_learning_iterations,
                                                              collection_time=collection_time, learn_time=learn_time,
                                                              mean_value_loss=mean_value_loss, mean_surrogate_loss=mean_surrogate_loss))
@@ -267,6 +281,9 @@ class OnPolicyRunner:
             self._unbind(plan)
         if marks:
             self._read_event_times(marks)
+        if diag_wait is not None:
+            torch.cuda.synchronize()
+            self._diag_publish(diag_wait[0], diag_wait[1])
         self.current_learning_iteration += num_learning_iterations
         self._check_replicas("end of learn() at iteration %d" % self.current_learning_iteration)
         if log_on:      # (the background writer finishes the file; wait_for_saves() / load() / interpreter exit wait for it: save())
@@ -439,9 +456,27 @@ class OnPolicyRunner:
         return self._update_capture.run(plan.graph_update and self._rollout_capture.valid(gkey), ukey, lambda: launches(not plan.async_mode),
                                         launches, lambda held: self.alg.after_update_replay())
 
-    def _finish_async_log(self, it, ev, pending, num_learning_iterations):
+    def _diag_snapshot(self, block, slot):
+        """Stream-ordered device -> pinned-host copy of a diagnostics block's sums (no host wait) -> the pinned tensor."""
+        from hgym import _lib as L
+        if self._diag_pin is None:
+            self._diag_pin = [torch.zeros(L.DIAG_SUMS, dtype=torch.float64).pin_memory() for _ in range(2)]
+        self._diag_pin[slot].copy_(block[:L.DIAG_SUMS], non_blocking=True)
+        return self._diag_pin[slot]
+
+    def _diag_publish(self, it, sums):
+        """last_diag <- the dict of a host copy of the sums; Diag/<key> to the writer."""
+        from hgym import diag_from_block
+        self.last_diag, self.last_diag_iteration = diag_from_block(sums, getattr(self.alg, "clip_param", None)), it
+        if self.writer is not None:
+            for k, v in self.last_diag.items():
+                self.writer.add_scalar("Diag/" + k, v, it)
+
+    def _finish_async_log(self, it, ev, pending, num_learning_iterations, diag=None):
         """Log sink: iteration k's block is printed from pinned-host copies while the device runs k + 1.  -> the new pending block."""
+        diag_pin = None if diag is None else self._diag_snapshot(diag, it & 1)      # (in front of the snapshot's event)
         snap = self._log_snapshot(self.env, self.alg, it & 1)
+        snap["diag"] = diag_pin
         if pending is not None:
             self._log_flush(pending, num_learning_iterations)
         return dict(it=it, ev=ev, snap=snap)
@@ -520,6 +555,8 @@ class OnPolicyRunner:
         snap["done"].synchronize()
         if snap.get("comm") is not None:       # N > 1 with the direct gradient exchange: an expired wait must not go unnoticed
             self.alg.check_comm(snap["comm"].tolist())
+        if snap.get("diag") is not None:
+            self._diag_publish(pending["it"], snap["diag"])
         pin, slot = self._log_pin, snap["slot"]
         o, ls = pin["opt"][slot], pin["ls"][slot]
         n = max(float(o[7]), 1.0)

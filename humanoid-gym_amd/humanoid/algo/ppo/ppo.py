@@ -151,6 +151,10 @@ class PPO:
         self._perm_seed = (torch.initial_seed() * 0x9E3779B97F4A7C15 + 0xABCD + 104729 * self._rank) & 0xFFFFFFFFFFFFFFFF
         self._perm_draws = 0
         self._deferred_ready = False        # deferred_values() has run since the last compute_returns()
+        # diagnostics(): slot 0 of the observations as the update saw it (diagnostics_prepare), whether an update has run on the stored rows
+        self._diag_rows0 = None
+        self._diag_saved = self._diag_updated = False
+        self._diag_block = None
         self._perm_draws_dev = torch.zeros(1, dtype=torch.int64, device=self.device)      # the same number where a captured update reads it
         ac._sample_step = self._sample_step
         # exploration-noise key: from the run's seed (as the permutation key above) and the rank
@@ -197,6 +201,7 @@ class PPO:
         """env_fin (native extension): a postponed env-step finaliser to run inside this policy launch
         (LeggedRobot.take_pending_finalize)."""
         st, s = self.storage, self.storage.step
+        self._diag_saved = self._diag_updated = False      # (the rows diagnostics() would read are being overwritten)
         out = None
         if s < st.num_transitions_per_env:     # write straight into the storage slot (no add_transitions copies)
             out = dict(actions=st.actions[s], mu=st.mu[s], sigma=st.sigma[s], logp=st.actions_log_prob[s].view(-1), values=st.values[s])
@@ -235,6 +240,7 @@ class PPO:
         T = st.num_transitions_per_env if T is None else int(T)
         if st.step != 0 or T > st.num_transitions_per_env:
             raise AssertionError("Rollout buffer overflow")
+        self._diag_saved = self._diag_updated = False
         env.rollout_begin(self.net, self.rollout_columns(deferred), T, rows_ahead, l0_ahead)
         for i in range(T):
             env.rollout_step(i)
@@ -326,6 +332,7 @@ class PPO:
     def after_rollout_replay(self, shadow_valid, deferred):
         """Host-side book-keeping of one replayed rollout: a full storage, the shadow slots the capture wrote, deferred_values() if deferred."""
         self.storage.step = self.storage.num_transitions_per_env
+        self._diag_saved = self._diag_updated = False
         self._deferred_ready = self._deferred_ready or deferred
         self.storage.shadow_valid = list(shadow_valid)
 
@@ -336,6 +343,7 @@ class PPO:
         if self.permutation == "device":
             self._perm_draws += 1
         self._deferred_ready = False
+        self._diag_updated = True
         st.step = 0
         st.shadow_valid = [False] * st.num_transitions_per_env
         if dist_utils.active() and self._comm is not None and self._comm_p2p:
@@ -405,6 +413,7 @@ class PPO:
                         self.comm_timing.append(ev + ("p2p" if (self._comm is not None and self._comm_p2p != bool(self.comm_flip)) else "collective",))
                 net.ppo_apply(self._ppo_cfg)
         st.clear()
+        self._diag_updated = True
         if not sync:
             return None, None
         o = net.opt_state.cpu()                # the one host read-back of the update
@@ -412,3 +421,65 @@ class PPO:
         n = max(float(o[7]), 1.0)
         self.last_denoise_loss = float(o[10]) / n if self._ppo_cfg.aux_coef > 0.0 else None
         return float(o[4]) / n, float(o[3]) / n
+
+    # ------------------------------------------------------------------ diagnostics of an update
+    def diagnostics_prepare(self):
+        """Call between a rollout and the update() (or its graph replay) that diagnostics() is to follow.  update() ends with
+        storage.clear(), which copies the bootstrap observation (slot T) over slot 0: of everything the update trains on, the N
+        observation rows of slot 0 are the one thing the storage no longer holds afterwards.  This keeps them: two device copies
+        (N x (num_obs + num_priv) floats) on the current stream, outside both HIP graphs; nothing else changes."""
+        st = self.storage
+        with torch.inference_mode():
+            if self._diag_rows0 is None:
+                self._diag_rows0 = (torch.empty_like(st._obs_all[0]), None if st._priv_all is None else torch.empty_like(st._priv_all[0]))
+            self._diag_rows0[0].copy_(st._obs_all[0])
+            if st._priv_all is not None:
+                self._diag_rows0[1].copy_(st._priv_all[0])
+        self._diag_saved, self._diag_updated = True, False
+
+    def diagnostics(self, sync=True):
+        """What the last update did to the policy, measured on the T * N rows it trained on: the UPDATED actor and critic are evaluated
+        once more on the stored observations and the result is reduced on the device against the stored actions, old mu / sigma /
+        log-probability / values, returns and advantages (hgym_ppo_diagnostics: fp64 sums in a fixed order, the same bits in every run).
+
+        Valid after diagnostics_prepare() + update() and before the next rollout writes slot 0; RuntimeError otherwise.  Around the pass
+        slot 0 of the observations holds the saved rows again and is then re-filled from slot T, as clear() left it: the next rollout
+        reads the same bits.  Parameters, gradients, Adam's state, opt_state, the bf16 shadows and every storage column are left alone.
+
+        sync=True: the dict of python floats of hgym.diag_from_block (samples, clip_fraction, kl, approx_kl, ratio_mean / _max / _min,
+        surrogate, entropy, value_clip_fraction, return_mean, return_std, explained_variance, explained_variance_new, value_rmse,
+        value_rmse_new) -- one read-back.  sync=False: the device block (its first 16 doubles are the sums), nothing read back: the
+        runner copies it into a pinned slot behind the update.  May be called again: same rows, same bits.
+
+        `kl` is the exact KL(old || new) of the two Gaussians, averaged over the WHOLE batch after the LAST minibatch step; the
+        learning-rate rule sees one minibatch at a time, before its step, and its expression carries + 1e-5 inside the logarithm.
+
+        Data-parallel runs: every rank reports its own shard of the batch; no collective is added."""
+        st = self.storage
+        if st is None or not self._diag_updated:
+            raise RuntimeError("PPO.diagnostics(): no update() has run on the rows in the storage (call it after update(), before the next rollout)")
+        if st.step != 0:
+            raise RuntimeError("PPO.diagnostics(): the storage is being filled again (storage.step = %d)" % st.step)
+        if not self._diag_saved:
+            raise RuntimeError("PPO.diagnostics(): call diagnostics_prepare() between the rollout and update() -- update() ends with "
+                               "storage.clear(), which overwrites the observations of slot 0 with the bootstrap observation")
+        T, N = st.num_transitions_per_env, st.num_envs
+        L = self._hgym._lib
+        fl = lambda t: t.flatten(0, 1)
+        with torch.inference_mode():
+            if self._diag_block is None:
+                self._diag_block = L.diag_block(T * N, self.device)
+            st._obs_all[0].copy_(self._diag_rows0[0])
+            if st._priv_all is not None:
+                st._priv_all[0].copy_(self._diag_rows0[1])
+            obs = fl(st.observations)
+            priv = fl(st.privileged_observations) if st.privileged_observations is not None else obs
+            cols = (obs, priv, fl(st.actions), st.values.view(-1), st.advantages.view(-1), st.returns.view(-1),
+                    st.actions_log_prob.view(-1), fl(st.mu), fl(st.sigma))
+            self.net.ppo_diagnostics(self._ppo_cfg, cols, self._diag_block)
+            st._obs_all[0].copy_(st._obs_all[T])
+            if st._priv_all is not None:
+                st._priv_all[0].copy_(st._priv_all[T])
+        if not sync:
+            return self._diag_block
+        return self._hgym.diag_from_block(self._diag_block.cpu(), self.clip_param)

@@ -8,7 +8,10 @@ per minibatch (algo/ppo/dist_utils.py); rank 0 alone logs and writes checkpoints
 
 HGYM_EXACT_RESUME=1 sets the train config's `runner.exact_resume` attribute (not a key of the config classes, whose lists are the
 reference's): every checkpoint gets an envstate_<it>.pt sidecar, and --resume from such a checkpoint continues the saved run bit
-for bit instead of warm-starting a new one (OnPolicyRunner.load; one rank)."""
+for bit instead of warm-starting a new one (OnPolicyRunner.load; one rank).
+
+HGYM_DIAG_INTERVAL=<n> sets `runner.diag_interval` the same way: every n iterations PPO.diagnostics() runs behind the update (clip fraction,
+KL, probability ratios, explained variance over the whole batch) and is logged as Diag/<key>; 0 or unset: never."""
 import os
 import sys
 
@@ -24,6 +27,8 @@ def train(args):
     env, env_cfg = task_registry.make_env(name=args.task, args=args)
     if os.environ.get("HGYM_EXACT_RESUME", "0") == "1":
         task_registry.get_cfgs(args.task)[1].runner.exact_resume = True
+    if int(os.environ.get("HGYM_DIAG_INTERVAL", "0") or 0) > 0:
+        task_registry.get_cfgs(args.task)[1].runner.diag_interval = int(os.environ["HGYM_DIAG_INTERVAL"])
     ppo_runner, train_cfg = task_registry.make_alg_runner(env=env, name=args.task, args=args, **({} if rank == 0 else {"log_root": None}))
     ppo_runner.learn(num_learning_iterations=train_cfg.runner.max_iterations, init_at_random_ep_len=True)
     if os.environ.get("HGYM_TRAIN_SIGNATURE"):      # tests: a signature of this rank's final parameters (replicas must agree bit for bit)

@@ -53,7 +53,9 @@ extern "C" {
                              *    (same version, later: hgym_env_reset_idx -- reset_idx for a caller-chosen subset of envs, its draws keyed by
                              *    the call number in HgymEnvState.counters[3]; no layout changes)
                              *    (same version, later: hgym_rollout_eval_step -- the rollout launch on the policy's mean action -- and the
-                             *    evaluation accumulator hgym_eval_reset / hgym_eval_accumulate; no layout changes) */
+                             *    evaluation accumulator hgym_eval_reset / hgym_eval_accumulate; no layout changes)
+                             *    (same version, later: the diagnostics pass behind an update -- hgym_ppo_diag_reset, hgym_ppo_diag_reduce,
+                             *    hgym_ppo_diagnostics; no layout changes) */
 
 enum {
     HGYM_OK = 0,
@@ -703,6 +705,70 @@ int32_t hgym_ppo_grad_part(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, c
 /* offset (floats) in the flat parameter / gradient vector of the first parameter of net `which` (0 actor, 1 critic, 2 auxiliary
  * head; which == number of nets: the parameter count); -1 on a bad argument */
 int64_t hgym_net_param_offset(const HgymNetConfig* cfg, int32_t which);
+
+/* ------------------------------------------------------------------------------------------------
+ * Diagnostics of an update (header v9, no layout change): what the update did to the policy, measured on the rows it trained on.
+ * The reference logs none of this (ppo.py:176-184 returns the two mean losses); the per-row forms are those of its loss (ppo.py:128-166).
+ *
+ * hgym_ppo_diag_reduce is the reduction alone over M rows: actions / mu_old / sigma_old / mu_new (M, 12) fp32 row-major, 16-byte
+ * aligned; logp_old / values_old / returns / advantages / values_new (M,) fp32; std = the 12 current standard deviations (the head of
+ * HgymNet.params).  Per row, in fp32:
+ *     logp_new  = sum_j -(a_j - mu_new_j)^2 / (2 std_j^2) - log std_j - log sqrt(2 pi)       ratio = expf(logp_new - logp_old)
+ *     kl        = sum_j log(std_j / sigma_old_j) + (sigma_old_j^2 + (mu_old_j - mu_new_j)^2) / (2 std_j^2) - 1/2     (old || new, exact;
+ *                 the learning-rate rule's expression, ppo.py:138-139, has + 1e-5 inside the logarithm: 1.2e-4 for a policy that did
+ *                 not move at all, so its sum in opt_state[2] lies that much above this one)
+ *     surrogate = max(-A ratio, -A clamp(ratio, 1 - clip, 1 + clip))                         entropy = sum_j 1/2 + log sqrt(2 pi) + log std_j
+ * and, widened to fp64, combined into block[HGYM_DIAG_*]:
+ *   COUNT          rows                                   KL           sum kl
+ *   APPROX_KL      sum (ratio - 1) - (logp_new - logp_old)             RATIO        sum ratio
+ *   CLIPPED        rows with ratio < 1 - clip or ratio > 1 + clip (the bounds formed in fp32, as torch.clamp gets them)
+ *   RATIO_MAX, RATIO_MIN    over all rows (-inf, +inf without rows)    SURROGATE    sum surrogate
+ *   RET, RET_SQ    sum R, sum R^2                         ERR_OLD, ERR_OLD_SQ   sum (R - V_old), sum (R - V_old)^2
+ *   ERR_NEW, ERR_NEW_SQ     the same with V_new           VALUE_CLIPPED         rows with |V_new - V_old| > clip
+ *   ENTROPY        sum entropy
+ * Order of summation: one partial per 256 GLOBAL rows -- rows [row0, row0 + M) of total_rows fill slots row0 / 256 ... of the block --
+ * formed by a fixed tree over lanes, then wavefronts; the call with finish = 1 then combines the partials of rows [0, row0 + M) in slot
+ * order and WRITES the totals.  The same rows give the same bits in every run, reduced by one call or by several; no atomics.
+ * row0 must be a multiple of 256, and so must M in every call but the last (finish = 1); M = 0 with finish = 1 is legal; rows beyond
+ * total_rows (what the block was sized for) are refused: all HGYM_E_BADARG, and nothing is launched.
+ * block: HGYM_DIAG_BLOCK_DOUBLES(total_rows) doubles of the caller, zeroed by hgym_ppo_diag_reset (the totals, then 16 per partial).
+ *
+ * hgym_ppo_diagnostics is the whole pass over the M rows `rows` points to (an HgymBatch whose idx is not read -- the rows are taken in
+ * order; B, the shadows and num_rows are ignored): in pieces of at most cfg->max_batch rows rounded down to a multiple of 256 (M <=
+ * max_batch: one piece), the actor forward (hgym_mlp_forward, which = 0) and the critic forward (hgym_critic_values, no shadow) of
+ * the piece into `scratch` (max_batch x 13 floats, 16-byte aligned: mu_new, then values_new), then hgym_ppo_diag_reduce on it with
+ * clip = ppo->clip_param, finish on the last piece.  The block equals, bit for bit, what those three calls give when the caller makes
+ * them.  Allocates nothing, synchronises nothing; reads the parameters and writes only scratch, block and the forwards' workspace:
+ * opt_state, the gradients, the Adam moments and the observation shadows are not touched.  Legal between hgym_ppo_apply and the next
+ * rollout launch on the same stream.  M > max_batch with max_batch < 256: HGYM_E_SHAPE. */
+#define HGYM_DIAG_SUMS 16
+#define HGYM_DIAG_COUNT 0
+#define HGYM_DIAG_KL 1
+#define HGYM_DIAG_APPROX_KL 2
+#define HGYM_DIAG_RATIO 3
+#define HGYM_DIAG_CLIPPED 4
+#define HGYM_DIAG_RATIO_MAX 5
+#define HGYM_DIAG_RATIO_MIN 6
+#define HGYM_DIAG_SURROGATE 7
+#define HGYM_DIAG_RET 8
+#define HGYM_DIAG_RET_SQ 9
+#define HGYM_DIAG_ERR_OLD 10
+#define HGYM_DIAG_ERR_OLD_SQ 11
+#define HGYM_DIAG_ERR_NEW 12
+#define HGYM_DIAG_ERR_NEW_SQ 13
+#define HGYM_DIAG_VALUE_CLIPPED 14
+#define HGYM_DIAG_ENTROPY 15
+#define HGYM_DIAG_ROWS_PER_PARTIAL 256
+#define HGYM_DIAG_MAX_ROWS 2147483648      /* 2^31: partial slots and launch grids stay 32-bit */
+#define HGYM_DIAG_BLOCK_DOUBLES(total_rows) \
+    ((size_t)HGYM_DIAG_SUMS * (1 + ((size_t)(total_rows) + HGYM_DIAG_ROWS_PER_PARTIAL - 1) / HGYM_DIAG_ROWS_PER_PARTIAL))
+int32_t hgym_ppo_diag_reset(int64_t total_rows, double* block, void* stream);
+int32_t hgym_ppo_diag_reduce(int64_t M, const float* actions, const float* mu_old, const float* sigma_old, const float* mu_new,
+                             const float* logp_old, const float* values_old, const float* returns, const float* advantages,
+                             const float* values_new, const float* std, float clip_param, int64_t row0, int64_t total_rows, int32_t finish,
+                             double* block, void* stream);
+int32_t hgym_ppo_diagnostics(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const HgymNet* net, const HgymBatch* rows, int64_t M,
+                             float* scratch, double* block, void* stream);
 
 /* clip_grad_norm_ + Adam.step (ppo.py:173-174) on net->grads (the rank-SUM when world_size > 1: divided by
  * world_size here, as is the KL in grads[P] before the learning-rate decision), refreshes the
