@@ -25,8 +25,8 @@ namespace hgym {
 template <int H_T, int HC_T, int E_T, bool kGeneric, bool kStep = false>
 __global__ __launch_bounds__(256) void env_step_kernel(const EnvArgs A) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int64_t csc0 = A.st.counters[0];
-    const int64_t ring_step = A.st.counters[2];
+    const int64_t csc0 = A.st.counters[HGYM_CNT_STEP];
+    const int64_t ring_step = A.st.counters[HGYM_CNT_RING];
     const int t = threadIdx.x;
     // compiled-in geometry: wavefronts 1..3 prefetch the observation history into registers here, so the whole step makes
     // ONE round trip to memory for its inputs, and store it (clipped) while wavefront 0 runs the per-env scalar chains
@@ -99,7 +99,7 @@ __global__ __launch_bounds__(256) void measure_heights_kernel(const EnvArgs A) {
 __global__ __launch_bounds__(1024) void command_curriculum_kernel(const EnvArgs A) {
     __shared__ int due;
     __shared__ float xr[2];
-    const int64_t csc0 = A.st.counters[0];
+    const int64_t csc0 = A.st.counters[HGYM_CNT_STEP];
     if (threadIdx.x == 0) {
         due = command_curriculum_due(A, A.mode == MODE_STEP ? csc0 + 1 : csc0) ? 1 : 0;   // the finaliser has not bumped the counter yet
         if (due) {
@@ -114,7 +114,7 @@ __global__ __launch_bounds__(1024) void command_curriculum_kernel(const EnvArgs 
     __syncthreads();
     if (!due) return;
     const RngKey rk = make_rng_key(A, csc0);
-    const int64_t ring_step = A.st.counters[2];
+    const int64_t ring_step = A.st.counters[HGYM_CNT_RING];
     for (int e = threadIdx.x; e < A.cfg.num_envs; e += blockDim.x) command_curriculum_fix_env(A, rk, e, xr[0], xr[1], ring_step);
 }
 
@@ -155,7 +155,7 @@ __global__ __launch_bounds__(1024) void reset_idx_curriculum_kernel(const EnvArg
     __shared__ int due;
     __shared__ float xr[2];
     if (threadIdx.x == 0) {
-        due = command_curriculum_due(A, A.st.counters[0]) ? 1 : 0;
+        due = command_curriculum_due(A, A.st.counters[HGYM_CNT_STEP]) ? 1 : 0;
         if (due) {
             double lo, hi;
             command_curriculum_move(A, A.st.command_range_x[0], A.st.command_range_x[1], lo, hi);
@@ -168,7 +168,7 @@ __global__ __launch_bounds__(1024) void reset_idx_curriculum_kernel(const EnvArg
     __syncthreads();
     if (!due) return;
     const RngKey rk = reset_idx_rng_key(A);
-    const int64_t ring_step = A.st.counters[2];
+    const int64_t ring_step = A.st.counters[HGYM_CNT_RING];
     for (int e = threadIdx.x; e < A.cfg.num_envs; e += blockDim.x)
         if (mask[e]) command_curriculum_fix_env(A, rk, e, xr[0], xr[1], ring_step);
 }
@@ -185,7 +185,7 @@ __global__ __launch_bounds__(256) void pre_physics_kernel(const EnvArgs A) {
     const int N = A.cfg.num_envs;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= N) return;
-    const int64_t csc0 = A.st.counters[0];
+    const int64_t csc0 = A.st.counters[HGYM_CNT_STEP];
     RngKey rk = {(uint32_t)A.cfg.seed, (uint32_t)(A.cfg.seed >> 32), (uint32_t)csc0, (uint32_t)(csc0 >> 32)};
     pre_physics_env(A, rk, e, N);
 }
@@ -201,7 +201,7 @@ __global__ __launch_bounds__(256) void synth_physics_kernel(const EnvArgs A) {
     const int N = A.cfg.num_envs;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= N) return;
-    const int64_t csc0 = A.st.counters[0];
+    const int64_t csc0 = A.st.counters[HGYM_CNT_STEP];
     RngKey rk = {(uint32_t)A.cfg.seed, (uint32_t)(A.cfg.seed >> 32), (uint32_t)csc0, (uint32_t)(csc0 >> 32)};
     synth_physics_env(A, rk, e, N);
 }

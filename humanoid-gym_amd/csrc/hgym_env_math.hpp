@@ -27,7 +27,7 @@ struct EnvArgs {
     HgymEnvNoise noise;
     float* actions_in;        // (N,12) row-major or null; written only when cfg.use_ref_actions (humanoid_env.py:190-191)
     float* origins_hbm;       // st.env_origins as the caller gave it (the LDS shadow replaces st.env_origins by its staged copy)
-    int64_t* reset_count;     // where resetting envs count themselves for the step finaliser; null: &st.counters[1]
+    int64_t* reset_count;     // where resetting envs count themselves for the step finaliser; null: &st.counters[HGYM_CNT_RESETS]
     int mode;
     int phase;                // user-defined reward terms (cfg.num_custom_rewards > 0) split the step in two launches: 1 = derive (action
                               // processing, physics, derived state, commands, pushes, termination flags -- what the reference has
@@ -893,7 +893,7 @@ HG_HD StepFlags post_physics_env(const EnvArgs& A, const RngKey& rk, int64_t csc
         }
         ep = 0;
         // extras["episode"]: mean over resetting envs, finished by the step finaliser
-        if (kMain) hg_atomic_inc(A.reset_count ? A.reset_count : &S.counters[1]);
+        if (kMain) hg_atomic_inc(A.reset_count ? A.reset_count : &S.counters[HGYM_CNT_RESETS]);
 #pragma unroll
         for (int k = 0; k < HGYM_NUM_REWARDS; ++k) {
             if (ROLE != ROLE_ALL) break;          // env_step_reward_sum, once the terms of this step are in
@@ -1835,7 +1835,7 @@ HG_HD bool command_curriculum_due(const EnvArgs& A, int64_t csc) {
     const HgymEnvConfig& c = A.cfg;
     if (!c.command_curriculum || !A.st.command_range_x || A.mode == MODE_PRIME) return false;
     if (csc % c.max_episode_length != 0) return false;
-    const int64_t cnt = A.reset_count ? A.reset_count[0] : A.st.counters[1];
+    const int64_t cnt = A.reset_count ? A.reset_count[0] : A.st.counters[HGYM_CNT_RESETS];
     if (cnt <= 0) return false;
     constexpr int kTrack = 20;                       // "tracking_lin_vel" in the alphabetical reward order
     const float mean_sum = A.st.episode_acc[kTrack] / (float)cnt;
@@ -1880,10 +1880,10 @@ HG_HD void command_curriculum_fix_env(const EnvArgs& A, const RngKey& rk, int e,
 // mask byte is set -- every other env is not even read.  State and sim tensors are addressed in place (no LDS staging), so nothing is
 // stored for an env outside the set.
 
-// Key of the draws of a host-side reset: the call number HgymEnvState.counters[3] in the two step words, with bit 30 of the high word
+// Key of the draws of a host-side reset: the call number HgymEnvState.counters[HGYM_CNT_RESET_CALL] in the two step words, with bit 30 of the high word
 // set.  No env-step draw uses that word (common_step_counter; bit 31 marks prime / reset_all) and neither does the policy's sampling.
 HG_HD RngKey reset_idx_rng_key(const EnvArgs& A) {
-    const int64_t call = A.st.counters[3];
+    const int64_t call = A.st.counters[HGYM_CNT_RESET_CALL];
     RngKey rk;
     rk.k0 = (uint32_t)A.cfg.seed;
     rk.k1 = (uint32_t)(A.cfg.seed >> 32);
@@ -1904,7 +1904,7 @@ HG_HD bool reset_idx_mark(uint8_t* mask, const int64_t* ids, int64_t i, int N) {
 // the reset branch for env e: dofs, root (+ custom origins, terrain curriculum), commands, zeroed buffers, episode sums into the
 // accumulators, gravity / Euler angles of the new pose, reset byte; no observation
 HG_HD void reset_idx_env(const EnvArgs& A, const RngKey& rk, int e) {
-    post_physics_env<true>(A, rk, A.st.counters[0], e, A.cfg.num_envs, nullptr, nullptr);
+    post_physics_env<true>(A, rk, A.st.counters[HGYM_CNT_STEP], e, A.cfg.num_envs, nullptr, nullptr);
 }
 
 // humanoid_env.py:264-269: both history rings of env e zeroed, lanes t, t + nthreads, ... of the caller's group

@@ -21,7 +21,7 @@ struct FinArgs {
     int mode;
     float episode_length_s;
     int64_t* counters;       // HgymEnvState::counters
-    int64_t* reset_count;    // envs that reset in the step being finalised: &counters[1], or the step's own slot when the finaliser
+    int64_t* reset_count;    // envs that reset in the step being finalised: &counters[HGYM_CNT_RESETS], or the step's own slot when the finaliser
                              // runs concurrently with the NEXT step's env phase (rollout_step_kernel)
     float* episode_acc;      // HgymEnvState::episode_acc (same remark)
     int ncustom;             // user-defined reward terms (HgymEnvConfig::num_custom_rewards)
@@ -35,7 +35,7 @@ HG_HD FinArgs make_fin_args(const HgymEnvConfig& cfg, const HgymEnvState& st, co
     f.mode = mode;
     f.episode_length_s = cfg.episode_length_s;
     f.counters = st.counters;
-    f.reset_count = st.counters + 1;
+    f.reset_count = st.counters + HGYM_CNT_RESETS;
     f.episode_acc = st.episode_acc;
     f.ncustom = (st.custom_acc && out.extras_custom) ? cfg.num_custom_rewards : 0;
     f.custom_acc = st.custom_acc;
@@ -82,18 +82,18 @@ HG_HD void fin_part2(const FinArgs& F) {
     // reads it at entry)
     if (F.out.t_rewards && F.out.t_step && !F.out.defer_finalize) F.out.t_step[0] += 1;
     F.reset_count[0] = 0;
-    if (F.mode == FIN_MODE_STEP) F.counters[0] += 1;
-    if (F.mode != FIN_MODE_RESET_ALL) F.counters[2] += 1;
+    if (F.mode == FIN_MODE_STEP) F.counters[HGYM_CNT_STEP] += 1;
+    if (F.mode != FIN_MODE_RESET_ALL) F.counters[HGYM_CNT_RING] += 1;
 }
 
 // The finaliser of a host-side partial reset (hgym_env_reset_idx), after fin_part1 and a barrier: extras["episode"] / the user-defined
 // terms' means and extras["time_outs"] have been refreshed as for reset_idx(all) -- or left as they were if no env was reset (never
-// 0/0).  Here the reset count is cleared and the call number counters[3] (the key of the next host reset's draws) advances; the step
-// counters [0] / [2] do not move, and neither the transition sink nor the logging sink is touched: the reference's runner counts
+// 0/0).  Here the reset count is cleared and the call number counters[HGYM_CNT_RESET_CALL] (the key of the next host reset's draws) advances; the step
+// counters [HGYM_CNT_STEP] / [HGYM_CNT_RING] do not move, and neither the transition sink nor the logging sink is touched: the reference's runner counts
 // finished episodes from the dones of step(), not from reset_idx.
 HG_HD void fin_reset_idx_tail(const FinArgs& F) {
     F.reset_count[0] = 0;
-    F.counters[3] += 1;
+    F.counters[HGYM_CNT_RESET_CALL] += 1;
 }
 
 // Optional logging sink (HgymEnvOut::log_*): OnPolicyRunner.learn's per-step book-keeping (on_policy_runner.py:143-156).
@@ -106,10 +106,10 @@ __device__ __forceinline__ void fin_log(const FinArgs& F, int t, int nthreads) {
     float* cur = F.out.log_cur;
     __shared__ int s_wave[32];
     __shared__ int s_head;
-    if (t < HGYM_NUM_REWARDS) LS[t] += F.out.extras_episode[t];
+    if (t < HGYM_NUM_REWARDS) LS[HGYM_LOG_TERMS + t] += F.out.extras_episode[t];
     if (t == 0) {
-        LS[22] += 1.0f;
-        s_head = (int)LS[24];
+        LS[HGYM_LOG_STEPS] += 1.0f;
+        s_head = (int)LS[HGYM_LOG_RING_HEAD];
     }
     const int lane = t & 63, wave = t >> 6, nw = (nthreads + 63) >> 6;
     int appended = 0;                    // finished episodes of the rows walked so far (uniform)
@@ -133,10 +133,10 @@ __device__ __forceinline__ void fin_log(const FinArgs& F, int t, int nthreads) {
             total += c;
         }
         if (done) {
-            if (off >= total - 100) {    // more than 100 in one row: only the last 100 can survive (and keep their slots distinct)
-                const int pos = (s_head + appended + off) % 100;
-                LS[32 + pos] = r;
-                LS[132 + pos] = l;
+            if (off >= total - HGYM_LOG_RING) {    // more than 100 in one row: only the last 100 can survive (and keep their slots distinct)
+                const int pos = (s_head + appended + off) % HGYM_LOG_RING;
+                LS[HGYM_LOG_RETURNS + pos] = r;
+                LS[HGYM_LOG_LENGTHS + pos] = l;
             }
             r = 0.0f;
             l = 0.0f;
@@ -149,9 +149,9 @@ __device__ __forceinline__ void fin_log(const FinArgs& F, int t, int nthreads) {
         __syncthreads();
     }
     if (t == 0) {
-        LS[24] = (float)((s_head + appended) % 100);
-        const float filled = LS[25] + (float)appended;
-        LS[25] = filled > 100.0f ? 100.0f : filled;
+        LS[HGYM_LOG_RING_HEAD] = (float)((s_head + appended) % HGYM_LOG_RING);
+        const float filled = LS[HGYM_LOG_RING_FILL] + (float)appended;
+        LS[HGYM_LOG_RING_FILL] = filled > (float)HGYM_LOG_RING ? (float)HGYM_LOG_RING : filled;
     }
 }
 
@@ -172,10 +172,10 @@ __device__ __forceinline__ bool fin_log_fused(const FinArgs& F, int t, int nthre
     if ((F.N & 7) != 0 || !al(O.reset, 8) || !al(O.rew, 16) || !al(cur, 16)) return false;
     __shared__ int s_wave[32];
     __shared__ int s_head;
-    if (t < HGYM_NUM_REWARDS) LS[t] += O.extras_episode[t];      // (thread t refreshed extras_episode[t] itself: no barrier)
+    if (t < HGYM_NUM_REWARDS) LS[HGYM_LOG_TERMS + t] += O.extras_episode[t];      // (thread t refreshed extras_episode[t] itself: no barrier)
     if (t == 0) {
-        LS[22] += 1.0f;
-        s_head = (int)LS[24];
+        LS[HGYM_LOG_STEPS] += 1.0f;
+        s_head = (int)LS[HGYM_LOG_RING_HEAD];
     }
     const int lane = t & 63, wave = t >> 6, nw = (nthreads + 63) >> 6;
     const int G = F.N >> 3;
@@ -219,10 +219,10 @@ __device__ __forceinline__ bool fin_log_fused(const FinArgs& F, int t, int nthre
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             if (((rs >> (8 * k)) & 0xffull) != 0) {
-                if (off >= total - 100) {                      // more than 100 in one trip: only the last 100 can survive (distinct slots)
-                    const int pos = (s_head + appended + off) % 100;
-                    LS[32 + pos] = c[k >> 2][k & 3];
-                    LS[132 + pos] = l[k >> 2][k & 3];
+                if (off >= total - HGYM_LOG_RING) {                      // more than 100 in one trip: only the last 100 can survive (distinct slots)
+                    const int pos = (s_head + appended + off) % HGYM_LOG_RING;
+                    LS[HGYM_LOG_RETURNS + pos] = c[k >> 2][k & 3];
+                    LS[HGYM_LOG_LENGTHS + pos] = l[k >> 2][k & 3];
                 }
                 ++off;
                 c[k >> 2][k & 3] = 0.0f;
@@ -240,9 +240,9 @@ __device__ __forceinline__ bool fin_log_fused(const FinArgs& F, int t, int nthre
         __syncthreads();
     }
     if (t == 0) {
-        LS[24] = (float)((s_head + appended) % 100);
-        const float filled = LS[25] + (float)appended;
-        LS[25] = filled > 100.0f ? 100.0f : filled;
+        LS[HGYM_LOG_RING_HEAD] = (float)((s_head + appended) % HGYM_LOG_RING);
+        const float filled = LS[HGYM_LOG_RING_FILL] + (float)appended;
+        LS[HGYM_LOG_RING_FILL] = filled > (float)HGYM_LOG_RING ? (float)HGYM_LOG_RING : filled;
     }
     return true;
 }
@@ -329,8 +329,8 @@ __device__ __forceinline__ void fin_block(const FinArgs& F, int t, int nthreads)
     const bool bump_step = F.out.t_rewards && F.out.t_step && !F.out.defer_finalize;
     int64_t c0 = 0, c2 = 0, ts = 0;
     if (t == 0) {
-        c0 = F.counters[0];
-        c2 = F.counters[2];
+        c0 = F.counters[HGYM_CNT_STEP];
+        c2 = F.counters[HGYM_CNT_RING];
         if (bump_step) ts = F.out.t_step[0];
     }
     if (!fin_fused(F, t, nthreads)) {
@@ -346,8 +346,8 @@ __device__ __forceinline__ void fin_block(const FinArgs& F, int t, int nthreads)
         // = fin_part2, on the values loaded above
         if (bump_step) F.out.t_step[0] = ts + 1;
         F.reset_count[0] = 0;
-        if (F.mode == FIN_MODE_STEP) F.counters[0] = c0 + 1;
-        if (F.mode != FIN_MODE_RESET_ALL) F.counters[2] = c2 + 1;
+        if (F.mode == FIN_MODE_STEP) F.counters[HGYM_CNT_STEP] = c0 + 1;
+        if (F.mode != FIN_MODE_RESET_ALL) F.counters[HGYM_CNT_RING] = c2 + 1;
     }
 }
 

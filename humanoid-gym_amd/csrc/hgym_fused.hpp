@@ -1022,6 +1022,9 @@ __device__ __forceinline__ void bwd_step(WRing<GR, D>& R, const u32x4* __restric
 // runs on the resident tile: through W3 against H2 (LDS, in place), through W2 against H1 (LDS, in place), through W1 against
 // H0 (LDS: the forward is told to put H2 into a buffer of its own instead of over H0).
 // HBM traffic per minibatch drops by the H re-reads and the loss kernel's own gathers; three launch boundaries go away.
+// The loss partial row: what one loss workgroup (ppo_loss_kernel in hgym_net.hip, fb_body below) hands to ppo_scalars_block.
+constexpr int LOSS_PARTIALS = 32;   // floats per loss workgroup: surrogate, value loss, entropy, kl, dstd[12], dbias_mu[12], dbias_v, aux, pad
+enum { LP_SURROGATE = 0, LP_VALUE = 1, LP_ENTROPY = 2, LP_KL = 3, LP_DSTD = 4, LP_DBIAS_MU = 16, LP_DBIAS_V = 28, LP_AUX = 29 };
 struct FbLoss {
     const float* actions;      // (T*N, A) storage columns, gathered through FwdArgs::idx
     const float* old_mu;
@@ -1031,7 +1034,7 @@ struct FbLoss {
     const float* returns;
     const float* logp;
     float clip, value_coef, entropy_coef;
-    float* partials;           // [tiles][32] per-tile sums, ppo_loss_kernel's layout: 0 surrogate, 1 value loss, 2 entropy, 3 kl,
+    float* partials;           // [tiles][LOSS_PARTIALS] per-tile sums, the LP_* row: 0 surrogate, 1 value loss, 2 entropy, 3 kl,
                                // 4..15 d std, 16..27 sum d mu (head bias gradient), 28 sum d V, 29 the auxiliary head's squared error;
                                // the actor tile writes its entries, the critic tile its two, the auxiliary tile its one
     // auxiliary (denoising) head, a third grid row: MSE against columns [aux_off, aux_off + layer[3].N) of the gathered target rows
@@ -1256,15 +1259,15 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
             part[k] = v;
         }
         if (r == 0) {
-            float* w = red + hw * 32;
+            float* w = red + hw * LOSS_PARTIALS;
             if (is_actor) {
-                if (q == 0) { w[0] = part[0]; w[2] = part[1]; w[3] = part[2]; }
+                if (q == 0) { w[LP_SURROGATE] = part[0]; w[LP_ENTROPY] = part[1]; w[LP_KL] = part[2]; }
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
-                    if (4 * q + e < 12) { w[4 + 4 * q + e] = part[3 + e]; w[16 + 4 * q + e] = part[7 + e]; }
+                    if (4 * q + e < 12) { w[LP_DSTD + 4 * q + e] = part[3 + e]; w[LP_DBIAS_MU + 4 * q + e] = part[7 + e]; }
             } else if (q == 0) {
-                w[1] = part[0];
-                w[28] = part[1];
+                w[LP_VALUE] = part[0];
+                w[LP_DBIAS_V] = part[1];
             }
         }
     };
@@ -1273,15 +1276,15 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
         if (wave < MB) {
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) aux_se += __shfl_xor(aux_se, o, 64);
-            if (lane == 0) red[wave * 32 + 29] = aux_se;
+            if (lane == 0) red[wave * LOSS_PARTIALS + LP_AUX] = aux_se;
         }
     } else {
         fwd_body<BM, NW, D, G1, false, XB16, false, GA>(a, n, is_actor, smem, FwdNoop(), FwdNoop(), FwdNoop(), 0, FwdNoop(), head, H2, rowidx, l2idle);
     }
     __syncthreads();          // dZ3 tile and the per-wave sums are in LDS; H0 sits in P, H1 in Q, H2 in its own buffer
-    if (tid < 32) {
-        const bool mine = AUX ? tid == 29 : (is_actor ? (tid != 1 && tid < 28) : (tid == 1 || tid == 28));
-        if (mine) L.partials[(int64_t)blockIdx.x * 32 + tid] = red[tid] + red[32 + tid] + red[64 + tid] + red[96 + tid];
+    if (tid < LOSS_PARTIALS) {
+        const bool mine = AUX ? tid == LP_AUX : (is_actor ? (tid != LP_VALUE && tid < LP_DBIAS_V) : (tid == LP_VALUE || tid == LP_DBIAS_V));
+        if (mine) L.partials[(int64_t)blockIdx.x * LOSS_PARTIALS + tid] = red[tid] + red[LOSS_PARTIALS + tid] + red[2 * LOSS_PARTIALS + tid] + red[3 * LOSS_PARTIALS + tid];
     }
     // ---- dZ chain on the resident tile
     const int N0 = n.layer[0].N, N1 = n.layer[1].N, N2 = n.layer[2].N;
@@ -1368,7 +1371,6 @@ int32_t launch_mlp_fb_act_form(const FwdArgs& fb0, const FbLoss& fl, bool shadow
 }
 
 // ================================================================================================ per-minibatch loss scalars
-constexpr int LOSS_PARTIALS = 32;   // floats per loss workgroup: surrogate, value loss, entropy, kl, dstd[12], dbias_mu[12], dbias_v, aux, pad
 // Sums the per-tile loss partials of a minibatch ([nblocks][32], mlp_fb_kernel / ppo_loss_kernel) into opt_state and writes the
 // gradients that are plain column sums: std, the two head biases (fused path), the KL slot behind the flat gradient.
 // One workgroup of 256 or 512 threads -- its own launch (ppo_scalars_kernel) or, on the fused path, one extra workgroup of the
@@ -1382,7 +1384,7 @@ struct ScalArgs {
     float* grads_bv;
     float* kl_slot;
     double* opt;
-    double beta1, beta2;   // Adam's: beta^t of the step this gradient will be applied in is left in opt[13..15] (below)
+    double beta1, beta2;   // Adam's: beta^t of the step this gradient will be applied in is left in opt[HGYM_OPT_PROLOGUE_STEP .. HGYM_OPT_BETA2_POW] (below)
     // hgym_ppo_apply's single-thread prologue (adaptive-KL learning rate, Adam step count, bias corrections) done HERE, beside the
     // weight-gradient launch, when the caller has promised that exactly this gradient is applied next on one rank
     // (HgymPPOConfig.grad_norm_ready): it needs nothing but the minibatch KL this block has just formed, and as a launch of its own it
@@ -1402,19 +1404,22 @@ __device__ __forceinline__ double adapt_lr(double lr, float kl, float desired_kl
     if (kl < desired_kl * 0.5f && kl > 0.0f) return fmin(lr_max, lr * 1.5);
     return lr;
 }
+// The "prologue done, not applied yet" marker (ppo_scalars_block below, apply_prologue / adam_kernel in hgym_net.hip).  A macro: as an
+// inlined function the same expression compiles to different code in ppo_scalars_block and apply_prologue.
+#define PROLOGUE_PENDING(opt) ((opt)[HGYM_OPT_PROLOGUE_STEP] == (opt)[HGYM_OPT_STEP] && (opt)[HGYM_OPT_STEP] > 0.0)
 __device__ __forceinline__ void ppo_scalars_block(const ScalArgs& a, int tid, int nthreads) {
     __shared__ double red[16][LOSS_PARTIALS + 1];
     // beta1^t, beta2^t for hgym_ppo_apply's prologue: two double-precision pow() are ~6 us in that single-thread kernel, on the
     // minibatch's critical path; here they run on two lanes of the last wavefront beside a launch that takes 170 us anyway.  Keyed
-    // by t (opt[13]): the prologue recomputes them if the step count is not the one assumed here.
-    // opt[13] is also the "prologue done, not applied yet" marker: == opt[1] (> 0) after a prologue taken here or in apply_prologue_kernel,
+    // by t (opt[PROLOGUE_STEP]): the prologue recomputes them if the step count is not the one assumed here.
+    // opt[PROLOGUE_STEP] is also the "prologue done, not applied yet" marker (PROLOGUE_PENDING): == opt[STEP] (> 0) after a prologue taken here or in apply_prologue_kernel,
     // -1 once adam_kernel has applied the step.  A second gradient call before the apply finds the marker set and leaves the step's
     // learning-rate decision, step count and powers alone (the update then is the reference's: one optimiser step per apply).
-    if (tid >= nthreads - 2 && !(a.opt[13] == a.opt[1] && a.opt[1] > 0.0)) {
-        const double t = a.opt[1] + 1.0;
+    if (tid >= nthreads - 2 && !PROLOGUE_PENDING(a.opt)) {
+        const double t = a.opt[HGYM_OPT_STEP] + 1.0;
         const double pw = pow(tid == nthreads - 2 ? a.beta1 : a.beta2, t);
-        a.opt[tid == nthreads - 2 ? 14 : 15] = pw;
-        if (tid == nthreads - 2) a.opt[13] = t;
+        a.opt[tid == nthreads - 2 ? HGYM_OPT_BETA1_POW : HGYM_OPT_BETA2_POW] = pw;
+        if (tid == nthreads - 2) a.opt[HGYM_OPT_PROLOGUE_STEP] = t;
     }
     const float* __restrict__ partials = a.partials;
     const int nblocks = a.nblocks, B = a.B, A = a.A;
@@ -1451,33 +1456,33 @@ __device__ __forceinline__ void ppo_scalars_block(const ScalArgs& a, int tid, in
         for (int p = 0; p < 16; ++p) t += red[p][tid];
         const int q = tid;
         double* __restrict__ opt = a.opt;
-        if (q == 0) opt[3] += t / B;
-        if (q == 1) opt[4] += t / B;
-        if (q == 2) opt[5] += t / B;
-        if (q == 3) {
+        if (q == LP_SURROGATE) opt[HGYM_OPT_SURROGATE_SUM] += t / B;
+        if (q == LP_VALUE) opt[HGYM_OPT_VALUE_SUM] += t / B;
+        if (q == LP_ENTROPY) opt[HGYM_OPT_ENTROPY_SUM] += t / B;
+        if (q == LP_KL) {
             const float kl = (float)(t / B);  // the reference's kl_mean is an fp32 tensor: the decision, here and in apply_prologue, is taken on it
-            opt[2] += t / B;
-            opt[8] = (double)kl;
-            opt[7] += 1.0;
-            opt[9] = 0.0;                     // squared gradient norm: accumulated by reduce_slabs_kernel later in this call
+            opt[HGYM_OPT_KL_SUM] += t / B;
+            opt[HGYM_OPT_KL_LAST] = (double)kl;
+            opt[HGYM_OPT_MINIBATCHES] += 1.0;
+            opt[HGYM_OPT_GRAD_SQNORM] = 0.0;  // squared gradient norm: accumulated by reduce_slabs_kernel later in this call
             a.kl_slot[0] = kl;                // grads[P]: travels with the gradient in the ranks' one all-reduce
-            if (a.do_prologue && !(opt[13] == opt[1] && opt[1] > 0.0)) {      // apply_prologue_kernel's arithmetic (hgym_net.hip), one rank: ppo.py:140-148
-                double lr = opt[0];
+            if (a.do_prologue && !PROLOGUE_PENDING(opt)) {      // apply_prologue_kernel's arithmetic (hgym_net.hip), one rank: ppo.py:140-148
+                double lr = opt[HGYM_OPT_LR];
                 if (a.adaptive_lr) {
                     lr = adapt_lr(lr, kl, a.desired_kl, a.lr_min, a.lr_max);
-                    opt[0] = lr;
+                    opt[HGYM_OPT_LR] = lr;
                 }
-                const double ts = opt[1] + 1.0;           // (= opt[13]: the two lanes above prepared beta^ts before the barrier)
-                opt[1] = ts;
-                const double bc1 = 1.0 - opt[14], bc2 = 1.0 - opt[15];
-                opt[11] = (double)(float)(lr / bc1);      // step size
-                opt[12] = (double)(float)sqrt(bc2);
+                const double ts = opt[HGYM_OPT_STEP] + 1.0;           // (= opt[PROLOGUE_STEP]: the two lanes above prepared beta^ts before the barrier)
+                opt[HGYM_OPT_STEP] = ts;
+                const double bc1 = 1.0 - opt[HGYM_OPT_BETA1_POW], bc2 = 1.0 - opt[HGYM_OPT_BETA2_POW];
+                opt[HGYM_OPT_STEP_SIZE] = (double)(float)(lr / bc1);      // step size
+                opt[HGYM_OPT_SQRT_BC2] = (double)(float)sqrt(bc2);
             }
         }
-        if (q >= 4 && q < 16 && q - 4 < A) a.grads_std[q - 4] = (float)t;
-        if (q >= 16 && q < 28 && q - 16 < A && a.grads_bmu) a.grads_bmu[q - 16] = (float)t;
-        if (q == 28 && a.grads_bv) a.grads_bv[0] = (float)t;
-        if (q == 29 && a.aux_No > 0) opt[10] += t / ((double)B * (double)a.aux_No);    // auxiliary head's MSE (the fused kernel's third grid row)
+        if (q >= LP_DSTD && q < LP_DBIAS_MU && q - LP_DSTD < A) a.grads_std[q - LP_DSTD] = (float)t;
+        if (q >= LP_DBIAS_MU && q < LP_DBIAS_V && q - LP_DBIAS_MU < A && a.grads_bmu) a.grads_bmu[q - LP_DBIAS_MU] = (float)t;
+        if (q == LP_DBIAS_V && a.grads_bv) a.grads_bv[0] = (float)t;
+        if (q == LP_AUX && a.aux_No > 0) opt[HGYM_OPT_AUX_SUM] += t / ((double)B * (double)a.aux_No);    // auxiliary head's MSE (the fused kernel's third grid row)
     }
 }
 

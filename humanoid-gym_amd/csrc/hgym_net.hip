@@ -292,7 +292,7 @@ __global__ __launch_bounds__(256) void rowsum_kernel(int Mp, int per, const T* _
 
 // Auxiliary head loss: L = coef * mean_b mean_j (y[b][j] - t[b][j])^2 with t = priv[idx[b]][off + j].  Writes
 // dL/dy in operand precision, row-major (dY, leading dimension ld) and transposed (dYT [No16][Mp]) for the generic backward,
-// zero in the contraction padding rows B..Bp, and adds the (unweighted) minibatch MSE to opt[10].
+// zero in the contraction padding rows B..Bp, and adds the (unweighted) minibatch MSE to opt[HGYM_OPT_AUX_SUM].
 template <typename T>
 __global__ __launch_bounds__(256) void aux_mse_kernel(int B, int Bp, int No, const float* __restrict__ y, const float* __restrict__ priv,
                                                       int64_t ldp, int off, const int64_t* __restrict__ idx, float coef,
@@ -318,7 +318,7 @@ __global__ __launch_bounds__(256) void aux_mse_kernel(int B, int Bp, int No, con
     for (int o = 32; o > 0; o >>= 1) se += __shfl_down(se, o, 64);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = se;
     __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(&opt[10], (double)(red[0] + red[1] + red[2] + red[3]) / ((double)B * (double)No));
+    if (threadIdx.x == 0) atomicAdd(&opt[HGYM_OPT_AUX_SUM], (double)(red[0] + red[1] + red[2] + red[3]) / ((double)B * (double)No));
 }
 
 // PPO.act epilogue (actor_critic.py:111-120): a = mu + sigma*z, logp = sum log N(a; mu, sigma); sigma = std.
@@ -459,19 +459,19 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(const LossArgs a) {
             const float g_mu = d_lp * d / (s * s);
             const float g_sg = d_lp * (d * d / (s * s * s) - 1.0f / s) - (a.entropy_coef * invB) / s;
             if (j < 12) {
-                acc[4 + j] = g_sg;
-                acc[16 + j] = g_mu;
+                acc[LP_DSTD + j] = g_sg;
+                acc[LP_DBIAS_MU + j] = g_mu;
             }
             dmu[(int64_t)i * a.ld_dmu + j] = from_f32<T>(g_mu);
             dmuT[(int64_t)j * a.ld_t + i] = from_f32<T>(g_mu);
         }
         dval[(int64_t)i * a.ld_dval] = from_f32<T>(d_v);
         dvalT[i] = from_f32<T>(d_v);
-        acc[0] = surr;
-        acc[1] = vl;
-        acc[2] = ent;
-        acc[3] = kl;
-        acc[28] = d_v;
+        acc[LP_SURROGATE] = surr;
+        acc[LP_VALUE] = vl;
+        acc[LP_ENTROPY] = ent;
+        acc[LP_KL] = kl;
+        acc[LP_DBIAS_V] = d_v;
     } else if (i < a.Bp) {   // zero the contraction padding of the gradients
         for (int j = 0; j < A; ++j) dmuT[(int64_t)j * a.ld_t + i] = from_f32<T>(0.0f);
         dvalT[i] = from_f32<T>(0.0f);
@@ -488,8 +488,7 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(const LossArgs a) {
         red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
 
-// opt_state: [0] lr [1] adam step [2] kl sum [3] surrogate sum [4] value-loss sum [5] entropy sum [6] grad norm
-//            [7] minibatches accumulated [8] last minibatch mean KL [9] grad sq-norm accumulator
+// opt_state: the HGYM_OPT_* slots of include/hgym.h.
 // grads_bmu / grads_bv (fused path only): gradients of the two head biases = column sums of the head gradients.
 __global__ __launch_bounds__(512) void ppo_scalars_kernel(const ScalArgs a) { ppo_scalars_block(a, threadIdx.x, blockDim.x); }
 
@@ -511,7 +510,7 @@ struct SegTable {
     Segment s[2 * HGYM_MAX_LAYERS * 2 + 1];
 };
 
-// Also accumulates the squared norm of the finished gradient into opt[9] (zeroed by ppo_scalars_kernel earlier in the same
+// Also accumulates the squared norm of the finished gradient into opt[HGYM_OPT_GRAD_SQNORM] (zeroed by ppo_scalars_kernel earlier in the same
 // hgym_ppo_grad): with one rank that IS the norm clip_grad_norm_ needs, and hgym_ppo_apply skips its own pass over the
 // gradient.  (Segments whose gradient is already final -- splits == 0 -- are only read.)
 // The norm stays on fp64 atomics in arrival order (1 632 workgroups, one non-returning atomicAdd each) -- made order-INDEPENDENT by rounding every
@@ -569,14 +568,14 @@ __global__ __launch_bounds__(256) void reduce_slabs_kernel(const SegTable tab, i
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sq;
     __syncthreads();
     if (threadIdx.x == 0) {
-        // Pre-rounded to a common quantum (2^-46): every partial, and therefore every intermediate value of opt[9], is an integer multiple of
+        // Pre-rounded to a common quantum (2^-46): every partial, and therefore every intermediate value of opt[GRAD_SQNORM], is an integer multiple of
         // it, so while the total stays below 2^53 quanta = 128 (a gradient norm of 11.3, eleven times the clip threshold) the fp64 additions
         // are EXACT -- and exact additions commute: the atomics may arrive in any order, the sum has the same bits.  (Above 128 the additions
         // round again and the last bits depend on the order, as they always did; the step is then clipped by more than 11x and sees `total`
         // as a float.)  Cost of the rounding: at most 1 632 x 2^-47 = 1.2e-11 absolute on the squared norm.
         double t = red[0] + red[1] + red[2] + red[3];
         t = __builtin_rint(t * 0x1p46) * 0x1p-46;
-        if (t != 0.0) atomicAdd(&opt[9], t);
+        if (t != 0.0) atomicAdd(&opt[HGYM_OPT_GRAD_SQNORM], t);
     }
 }
 
@@ -587,22 +586,22 @@ __global__ __launch_bounds__(256) void reduce_slabs_kernel(const SegTable tab, i
 // this call determined it itself (sqnorm_prologue_kernel), 0 when a norm pass follows, untouched when the gradient call left it (have_sq < 0)
 __device__ __forceinline__ void apply_prologue(const HgymPPOConfig& p, const float* __restrict__ kl_slot, float inv_w, double* __restrict__ opt,
                                                int have_sq, double sq) {
-    if (p.world_size > 1) opt[8] = (double)(kl_slot[0] * inv_w);     // mean over ranks of the minibatch KL: same LR branch everywhere
-    if (opt[13] == opt[1] && opt[1] > 0.0) {     // the gradient call already took this step's prologue (marker: ppo_scalars_block) and the
-        if (have_sq >= 0) opt[9] = have_sq ? sq : 0.0;                // caller applies with another configuration: not a second time
+    if (p.world_size > 1) opt[HGYM_OPT_KL_LAST] = (double)(kl_slot[0] * inv_w);     // mean over ranks of the minibatch KL: same LR branch everywhere
+    if (PROLOGUE_PENDING(opt)) {     // the gradient call already took this step's prologue (marker: ppo_scalars_block) and the
+        if (have_sq >= 0) opt[HGYM_OPT_GRAD_SQNORM] = have_sq ? sq : 0.0;                // caller applies with another configuration: not a second time
         return;
     }
-    if (p.adaptive_lr) opt[0] = adapt_lr(opt[0], (float)opt[8], p.desired_kl, p.lr_min, p.lr_max);      // (opt[8] as the caller left it: rounded)
-    const double t = opt[1] + 1.0;
-    opt[1] = t;
+    if (p.adaptive_lr) opt[HGYM_OPT_LR] = adapt_lr(opt[HGYM_OPT_LR], (float)opt[HGYM_OPT_KL_LAST], p.desired_kl, p.lr_min, p.lr_max);      // (KL_LAST as the caller left it: rounded)
+    const double t = opt[HGYM_OPT_STEP] + 1.0;
+    opt[HGYM_OPT_STEP] = t;
     // Adam's bias corrections, once per step instead of two double-precision pow() per thread of adam_kernel (1.1 M threads): the
     // same double arithmetic, rounded to the floats the update uses
-    const bool cached = opt[13] == t;             // ppo_scalars_block left beta^t of this step (same pow(), same arguments): kernel 8.1 -> 4.8 us
-    const double bc1 = 1.0 - (cached ? opt[14] : pow((double)p.beta1, t)), bc2 = 1.0 - (cached ? opt[15] : pow((double)p.beta2, t));
-    opt[11] = (double)(float)(opt[0] / bc1);      // step size
-    opt[12] = (double)(float)sqrt(bc2);
-    opt[13] = t;                                  // marker: this step's prologue is done (adam_kernel clears it)
-    if (have_sq >= 0) opt[9] = have_sq ? sq : 0.0;
+    const bool cached = opt[HGYM_OPT_PROLOGUE_STEP] == t;             // ppo_scalars_block left beta^t of this step (same pow(), same arguments): kernel 8.1 -> 4.8 us
+    const double bc1 = 1.0 - (cached ? opt[HGYM_OPT_BETA1_POW] : pow((double)p.beta1, t)), bc2 = 1.0 - (cached ? opt[HGYM_OPT_BETA2_POW] : pow((double)p.beta2, t));
+    opt[HGYM_OPT_STEP_SIZE] = (double)(float)(opt[HGYM_OPT_LR] / bc1);      // step size
+    opt[HGYM_OPT_SQRT_BC2] = (double)(float)sqrt(bc2);
+    opt[HGYM_OPT_PROLOGUE_STEP] = t;                              // marker: this step's prologue is done (adam_kernel clears it)
+    if (have_sq >= 0) opt[HGYM_OPT_GRAD_SQNORM] = have_sq ? sq : 0.0;
 }
 __global__ void apply_prologue_kernel(const HgymPPOConfig p, const float* __restrict__ kl_slot, float inv_w, double* __restrict__ opt) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -669,14 +668,14 @@ __global__ __launch_bounds__(256) void adam_kernel(const SegTable tab, const Hgy
     const Segment& sg = tab.s[blockIdx.y];
     const int64_t n = (int64_t)sg.rows * sg.cols;
     // nn.utils.clip_grad_norm_: coef = max_norm / (total_norm + 1e-6), clamped to 1 (fp32 tensor arithmetic)
-    const float total = (float)sqrt(opt[9]);
+    const float total = (float)sqrt(opt[HGYM_OPT_GRAD_SQNORM]);
     float coef = p.max_grad_norm / (total + 1e-6f);
     coef = fminf(coef, 1.0f);
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
-        opt[6] = (double)total;
-        opt[13] = -1.0;                           // the step whose prologue was pending is being applied (nobody reads opt[13] in this launch)
+        opt[HGYM_OPT_GRAD_NORM] = (double)total;
+        opt[HGYM_OPT_PROLOGUE_STEP] = -1.0;       // the step whose prologue was pending is being applied (nobody reads the marker in this launch)
     }
-    const float step_size = (float)opt[11], sqrt_bc2 = (float)opt[12];      // apply_prologue_kernel: lr / (1 - beta1^t), sqrt(1 - beta2^t)
+    const float step_size = (float)opt[HGYM_OPT_STEP_SIZE], sqrt_bc2 = (float)opt[HGYM_OPT_SQRT_BC2];      // apply_prologue_kernel: lr / (1 - beta1^t), sqrt(1 - beta2^t)
     auto adam1 = [&](int64_t q) -> float {            // one parameter: clip, moments, step; returns the new weight
         const float g = (grads[q] * inv_w) * coef;
         grads[q] = g;
@@ -852,7 +851,7 @@ struct NetBase {
     int32_t apply(const HgymPPOConfig& ppo, bool prologue_done) {
         prof_begin(HGYM_PROF_APPLY, s);
         const float inv_w = ppo.world_size > 1 ? (float)(1.0 / (double)ppo.world_size) : 1.0f;
-        if (ppo.world_size > 1 || !ppo.grad_norm_ready)        // else: reduce_slabs_kernel left the squared norm in opt[9]
+        if (ppo.world_size > 1 || !ppo.grad_norm_ready)        // else: reduce_slabs_kernel left the squared norm in opt[HGYM_OPT_GRAD_SQNORM]
             hipLaunchKernelGGL(sqnorm_prologue_kernel, dim3(SQN_BLOCKS), dim3(256), 0, s, w.P, net.grads, inv_w, ppo, net.grads + w.P, net.opt_state,
                                at<double>(w.sqn));
         else if (!prologue_done)

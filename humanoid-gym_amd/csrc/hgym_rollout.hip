@@ -35,8 +35,8 @@ namespace hgym {
 
 __global__ void rollout_begin_kernel(const int64_t* __restrict__ counters, const int64_t* __restrict__ step, RolloutScratch* scr, int parity) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    scr->pp[parity][0] = counters[0];
-    scr->pp[parity][1] = counters[2];
+    scr->pp[parity][0] = counters[HGYM_CNT_STEP];
+    scr->pp[parity][1] = counters[HGYM_CNT_RING];
     scr->pp[parity][2] = step[0];
 }
 

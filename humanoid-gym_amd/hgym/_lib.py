@@ -224,7 +224,16 @@ def rollout_scratch_bytes(num_envs):
     """HGYM_ROLLOUT_SCRATCH_BYTES(num_envs) of include/hgym.h."""
     return ROLLOUT_SCRATCH_HEADER_BYTES + ROLLOUT_DRAW_BYTES_PER_ENV * int(num_envs)
 
+# HgymEnvOut.log_stats (include/hgym.h: HGYM_LOG_*)
 LOG_STATS = 256
+LOG_TERMS, LOG_STEPS, LOG_CLEAR, LOG_RING_HEAD, LOG_RING_FILL = 0, 22, 23, 24, 25
+LOG_RING, LOG_RETURNS, LOG_LENGTHS = 100, 32, 132
+# HgymEnvState.counters (HGYM_CNT_*)
+CNT_STEP, CNT_RESETS, CNT_RING, CNT_RESET_CALL = range(4)
+# HgymNet.opt_state (HGYM_OPT_*)
+OPT_STATE = 16
+(OPT_LR, OPT_STEP, OPT_KL_SUM, OPT_SURROGATE_SUM, OPT_VALUE_SUM, OPT_ENTROPY_SUM, OPT_GRAD_NORM, OPT_MINIBATCHES, OPT_KL_LAST,
+ OPT_GRAD_SQNORM, OPT_AUX_SUM, OPT_STEP_SIZE, OPT_SQRT_BC2, OPT_PROLOGUE_STEP, OPT_BETA1_POW, OPT_BETA2_POW) = range(16)
 
 
 def prof_summary(cls):

@@ -28,6 +28,17 @@ def grid_origins(n, spacing=3.0):
     return o
 
 
+def log_stats_summary(ls, reward_names, terms):
+    """A log_stats snapshot (HgymEnvOut.log_stats: a tensor, or any sequence of HGYM_LOG_STATS numbers) -> (extras["episode"] means over the
+    steps since the sums were cleared (at least 1), returns of the last <= HGYM_LOG_RING finished episodes, their lengths).  terms: the
+    kernel's reward terms in slot order; reward_names: those to report."""
+    steps = max(float(ls[L.LOG_STEPS]), 1.0)
+    ep = {"rew_" + n: float(ls[L.LOG_TERMS + terms.index(n)]) / steps for n in reward_names}
+    k = int(ls[L.LOG_RING_FILL])
+    seq = lambda s: s.tolist() if hasattr(s, "tolist") else list(s)
+    return ep, seq(ls[L.LOG_RETURNS:L.LOG_RETURNS + k]), seq(ls[L.LOG_LENGTHS:L.LOG_LENGTHS + k])
+
+
 class EnvBuffers:
     """All device memory of one env shard.
 
@@ -104,6 +115,10 @@ class EnvBuffers:
         self.height_samples = self.height_points = self.height_pose = self.measured_heights = None
         self.command_range_x = None
         self.custom_rew = self.custom_sums = self.custom_acc = self.extras_custom = None     # set_custom_rewards
+
+    def clear_log_sums(self):
+        """Clear the log sink's per-step sums after reading them; the rings persist."""
+        self.log_stats[:L.LOG_CLEAR].zero_()
 
     # ---- generic options (SURVEY.md 8f item 3) --------------------------------------------------------
     def set_terrain(self, origins, levels, types, env_length, curriculum, height_samples=None, height_points=None, border_size=0.0,

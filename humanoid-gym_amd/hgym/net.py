@@ -99,8 +99,8 @@ class NetBuffers:
             grads_ext.zero_()
         self.grads_ext = grads_ext[:self.P + 1] if grads_ext is not None else z(self.P + 1)      # flat gradient + the minibatch KL slot: what the ranks all-reduce, in one piece
         self.grads = self.grads_ext[:self.P]
-        self.opt_state = z(16, torch.float64)
-        self.opt_state[0] = learning_rate
+        self.opt_state = z(L.OPT_STATE, torch.float64)
+        self.opt_state[L.OPT_LR] = learning_rate
         self.workspace = torch.zeros(nbytes + 256, dtype=torch.uint8, device=self.device)
         off = (-self.workspace.data_ptr()) % 256
         self._ws_ptr = self.workspace.data_ptr() + off
@@ -277,3 +277,11 @@ def diag_from_block(block, clip_param=None):
                 return_std=math.sqrt(var_r), explained_variance=ev(L.DIAG_ERR_OLD, L.DIAG_ERR_OLD_SQ),
                 explained_variance_new=ev(L.DIAG_ERR_NEW, L.DIAG_ERR_NEW_SQ), value_rmse=math.sqrt(mean(L.DIAG_ERR_OLD_SQ)),
                 value_rmse_new=math.sqrt(mean(L.DIAG_ERR_NEW_SQ)))
+
+
+def opt_summary(o, aux):
+    """What a log block takes from an opt_state snapshot (a tensor, or any sequence of HGYM_OPT_STATE numbers) after an update: the per-update
+    sums over the minibatches they were taken on (at least 1).  aux: the auxiliary head is trained (else denoise_loss is None)."""
+    n = max(float(o[L.OPT_MINIBATCHES]), 1.0)
+    return dict(mean_value_loss=float(o[L.OPT_VALUE_SUM]) / n, mean_surrogate_loss=float(o[L.OPT_SURROGATE_SUM]) / n,
+                denoise_loss=float(o[L.OPT_AUX_SUM]) / n if aux else None, learning_rate=float(o[L.OPT_LR]))

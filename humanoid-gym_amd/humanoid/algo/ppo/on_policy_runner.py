@@ -526,7 +526,7 @@ class OnPolicyRunner:
         comm = getattr(alg, "_comm", None)
         if comm is not None and (getattr(alg, "_comm_p2p", False) or getattr(alg, "_comm_direct_used", False)):
             expired = int(comm.read_status()[0] != 0)
-        self.last_replica_digest = dist_utils.check_replicas(net.params, lr=float(net.opt_state[0]), comm_expired=expired, what=what)
+        self.last_replica_digest = dist_utils.check_replicas(net.params, lr=alg.learning_rate, comm_expired=expired, what=what)
         return self.last_replica_digest
 
     def _log_snapshot(self, env, alg, slot):
@@ -542,7 +542,7 @@ class OnPolicyRunner:
         pin["ls"][slot].copy_(env._buf.log_stats, non_blocking=True)
         pin["std"][slot].copy_(alg.actor_critic.std.detach().mean().reshape(1), non_blocking=True)
         comm_words = alg.comm_status_snapshot(slot) if hasattr(alg, "comm_status_snapshot") else None
-        env._buf.log_stats[:23].zero_()
+        env._buf.clear_log_sums()
         done = torch.cuda.Event()
         done.record()
         return dict(slot=slot, done=done, aux=alg._ppo_cfg.aux_coef > 0.0, comm=comm_words)
@@ -550,6 +550,7 @@ class OnPolicyRunner:
     def _log_flush(self, pending, num_learning_iterations):
         """Print / record the log block of a finished iteration from its host snapshot (no device access: the device is busy with
         the next iteration)."""
+        import hgym
         from humanoid.envs.base.legged_robot import KERNEL_REWARD_TERMS
         snap, ev = pending["snap"], pending["ev"]
         snap["done"].synchronize()
@@ -558,18 +559,15 @@ class OnPolicyRunner:
         if snap.get("diag") is not None:
             self._diag_publish(pending["it"], snap["diag"])
         pin, slot = self._log_pin, snap["slot"]
-        o, ls = pin["opt"][slot], pin["ls"][slot]
-        n = max(float(o[7]), 1.0)
-        self.alg.last_denoise_loss = float(o[10]) / n if snap["aux"] else None
-        steps = max(float(ls[22]), 1.0)
-        ep = {"rew_" + nm: float(ls[KERNEL_REWARD_TERMS.index(nm)]) / steps for nm in self.env.reward_names}
-        k = int(ls[25])
+        o = hgym.opt_summary(pin["opt"][slot], snap["aux"])
+        self.alg.last_denoise_loss = o["denoise_loss"]
+        ep, returns, lengths = hgym.log_stats_summary(pin["ls"][slot], self.env.reward_names, KERNEL_REWARD_TERMS)
         collection_time, learn_time = ev[0].elapsed_time(ev[1]) * 1e-3, ev[1].elapsed_time(ev[2]) * 1e-3
         self.last_collection_time, self.last_learn_time = collection_time, learn_time
         self.log(dict(it=pending["it"], num_learning_iterations=num_learning_iterations, collection_time=collection_time,
-                      learn_time=learn_time, mean_value_loss=float(o[4]) / n, mean_surrogate_loss=float(o[3]) / n, ep_infos=[ep],
-                      rewbuffer=deque(ls[32:32 + k].tolist(), maxlen=100), lenbuffer=deque(ls[132:132 + k].tolist(), maxlen=100),
-                      learning_rate=float(o[0]), mean_std=float(pin["std"][slot][0])))
+                      learn_time=learn_time, mean_value_loss=o["mean_value_loss"], mean_surrogate_loss=o["mean_surrogate_loss"], ep_infos=[ep],
+                      rewbuffer=deque(returns, maxlen=100), lenbuffer=deque(lengths, maxlen=100),
+                      learning_rate=o["learning_rate"], mean_std=float(pin["std"][slot][0])))
 
     def log(self, locs, width=80, pad=35):
         self.tot_timesteps += self.num_steps_per_env * self.env.num_envs

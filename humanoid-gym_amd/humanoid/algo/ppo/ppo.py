@@ -35,7 +35,7 @@ class _DeviceAdam:
         net = self._ppo.net
         state = {}
         if net is not None:
-            step = float(net.opt_state[1])
+            step = float(net.opt_state[self._ppo._hgym._lib.OPT_STEP])
             base = net.params.data_ptr()
             for i, (name, v) in enumerate(net.views.items()):
                 o = (v.data_ptr() - base) // 4
@@ -52,7 +52,7 @@ class _DeviceAdam:
                 o = (v.data_ptr() - base) // 4
                 net.adam_m[o:o + v.numel()].copy_(sd["state"][i]["exp_avg"].flatten())
                 net.adam_v[o:o + v.numel()].copy_(sd["state"][i]["exp_avg_sq"].flatten())
-                net.opt_state[1] = float(sd["state"][i]["step"])
+                net.opt_state[self._ppo._hgym._lib.OPT_STEP] = float(sd["state"][i]["step"])
         if sd.get("param_groups"):
             self._ppo.learning_rate = sd["param_groups"][0]["lr"]
 
@@ -103,16 +103,17 @@ class PPO:
     # ------------------------------------------------------------------
     @property
     def learning_rate(self):
-        return float(self.net.opt_state[0]) if self.net is not None else self._lr0
+        return float(self.net.opt_state[self._hgym._lib.OPT_LR]) if self.net is not None else self._lr0
 
     @learning_rate.setter
     def learning_rate(self, v):
         self._lr0 = v
         if self.net is not None:
-            self.net.opt_state[0] = v
+            self.net.opt_state[self._hgym._lib.OPT_LR] = v
 
     def init_storage(self, num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape):
         import hgym
+        self._hgym = hgym
         self.storage = RolloutStorage(num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape, self.device)
         ac = self.actor_critic
         mb = (num_envs * num_transitions_per_env) // self.num_mini_batches
@@ -159,7 +160,6 @@ class PPO:
         ac._sample_step = self._sample_step
         # exploration-noise key: from the run's seed (as the permutation key above) and the rank
         ac._sample_seed = (torch.initial_seed() * 0xD1342543DE82EF95 + 0x5EED + 7919 * self._rank) & 0xFFFFFFFFFFFFFFFF
-        self._hgym = hgym
 
     def seek(self, iteration, steps_per_iteration):
         """Position the device generators' counters where a run that has done `iteration` learning iterations has them
@@ -381,9 +381,9 @@ class PPO:
         if sh is not None and self._check_shadow:
             st.check_shadows()
         sh = dict(obs_bf16=sh[0], priv_bf16=sh[1]) if sh is not None else {}
-        net.opt_state[2:8] = 0.0               # the per-update sums [2..5], [7] (and the informational last norm [6]): one fill
+        net.opt_state[hgym._lib.OPT_KL_SUM:hgym._lib.OPT_MINIBATCHES + 1] = 0.0     # the four per-update sums and their count (and the informational last norm between them): one fill
         if self._ppo_cfg.aux_coef > 0.0:
-            net.opt_state[10:11] = 0.0     # (a slice: a fill kernel -- an indexed scalar store is a host-to-device copy, which a stream capture refuses)
+            net.opt_state[hgym._lib.OPT_AUX_SUM:hgym._lib.OPT_AUX_SUM + 1] = 0.0     # (a slice: a fill kernel -- an indexed scalar store is a host-to-device copy, which a stream capture refuses)
         for _ in range(self.num_learning_epochs):
             for i in range(self.num_mini_batches):
                 idx = perm[i * mb:(i + 1) * mb]
@@ -418,9 +418,9 @@ class PPO:
             return None, None
         o = net.opt_state.cpu()                # the one host read-back of the update
         self.check_comm()                      # (the stream is idle now: reading the exchange's status costs one small copy)
-        n = max(float(o[7]), 1.0)
-        self.last_denoise_loss = float(o[10]) / n if self._ppo_cfg.aux_coef > 0.0 else None
-        return float(o[4]) / n, float(o[3]) / n
+        o = hgym.opt_summary(o, self._ppo_cfg.aux_coef > 0.0)
+        self.last_denoise_loss = o["denoise_loss"]
+        return o["mean_value_loss"], o["mean_surrogate_loss"]
 
     # ------------------------------------------------------------------ diagnostics of an update
     def diagnostics_prepare(self):

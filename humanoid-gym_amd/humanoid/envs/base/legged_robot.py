@@ -416,11 +416,13 @@ class LeggedRobot(BaseTask):
 
     @property
     def common_step_counter(self):
-        return int(self._buf.counters[0])
+        from hgym import _lib as L
+        return int(self._buf.counters[L.CNT_STEP])
 
     @common_step_counter.setter
     def common_step_counter(self, v):
-        self._buf.counters[0] = int(v)
+        from hgym import _lib as L
+        self._buf.counters[L.CNT_STEP] = int(v)
 
     def _refresh_extras(self):
         b = self._buf
@@ -470,12 +472,10 @@ class LeggedRobot(BaseTask):
     def log_sink_read(self):
         """(episode means dict, returns of the last <= 100 finished episodes, their lengths) since the last call; one device
         read-back.  The per-step sums are cleared, the rings persist (they are the runner's rewbuffer / lenbuffer)."""
-        ls = self._buf.log_stats.cpu()
-        steps = max(float(ls[22]), 1.0)
-        ep = {"rew_" + n: float(ls[KERNEL_REWARD_TERMS.index(n)]) / steps for n in self.reward_names}
-        k = int(ls[25])
-        self._buf.log_stats[:23].zero_()
-        return ep, ls[32:32 + k].tolist(), ls[132:132 + k].tolist()
+        import hgym
+        out = hgym.log_stats_summary(self._buf.log_stats.cpu(), self.reward_names, KERNEL_REWARD_TERMS)
+        self._buf.clear_log_sums()
+        return out
 
     def take_pending_finalize(self):
         p, self._pending_fin = getattr(self, "_pending_fin", None), None
@@ -496,12 +496,12 @@ class LeggedRobot(BaseTask):
         `iteration` learning iterations has it, so that a resumed run continues the env's draw streams instead of replaying them
         from step 0.  The reference's checkpoint carries no generator state either (on_policy_runner.py:274-281); the counter is
         a function of the iteration number.  The history ring position is left alone, and so is the call number of host-side
-        partial resets (counters[3], the key of reset_idx's draws).  This is a warm start: episodes, commands, histories and
+        partial resets (counters[CNT_RESET_CALL], the key of reset_idx's draws).  This is a warm start: episodes, commands, histories and
         curricula stay those of the env as it stands.  A run that is to CONTINUE restores the whole env with state_dict() /
         load_state_dict() instead (OnPolicyRunner.save(env_state=True) / load()), which carries all four counter words."""
         if not hasattr(self, "_seek_base"):                    # no reset() yet: this IS the fresh env
-            self._seek_base = int(self._buf.counters[0])
-        self._buf.counters[0] = self._seek_base + int(iteration) * int(steps_per_iteration)
+            self._seek_base = self.common_step_counter
+        self.common_step_counter = self._seek_base + int(iteration) * int(steps_per_iteration)
 
     # ------------------------------------------------------------------ snapshot / restore (native extension)
     def _refuse_mid_step(self, what):
@@ -861,7 +861,7 @@ class LeggedRobot(BaseTask):
         if not hasattr(self, "_seek_base"):
             # iteration 0 of seek(): the counter right after the FIRST reset (OnPolicyRunner.__init__ calls it), recorded here and not
             # lazily in seek() -- a load() after learn() would otherwise take the already-advanced counter for the base
-            self._seek_base = int(self._buf.counters[0])
+            self._seek_base = self.common_step_counter
         return obs, privileged_obs
 
     def _prime(self):

@@ -34,9 +34,10 @@ def train(args):
     if os.environ.get("HGYM_TRAIN_SIGNATURE"):      # tests: a signature of this rank's final parameters (replicas must agree bit for bit)
         import json
         import torch
+        from hgym import _lib as L
         net = ppo_runner.alg.net
         bits = net.params.view(torch.int32).to(torch.int64)
-        json.dump(dict(world=world, steps=int(float(net.opt_state[1])), lr=float(net.opt_state[0]),
+        json.dump(dict(world=world, steps=int(float(net.opt_state[L.OPT_STEP])), lr=float(net.opt_state[L.OPT_LR]),
                        params=[int(bits.sum()), int((bits * (torch.arange(bits.numel(), device=bits.device) % 8191 + 1)).sum())],
                        comm=getattr(ppo_runner.alg, "comm_report", None)),
                   open(os.path.join(os.environ["HGYM_TRAIN_SIGNATURE"], "rank%d.json" % rank), "w"))

@@ -51,11 +51,13 @@ extern "C" {
                              *    (same version, later: HgymNetConfig.fused_activation appended -- the fused bf16 forward / update kernels for
                              *    every activation instead of ELU(1) only; a zero-filled tail is the ELU(1)-only rule every earlier layout meant)
                              *    (same version, later: hgym_env_reset_idx -- reset_idx for a caller-chosen subset of envs, its draws keyed by
-                             *    the call number in HgymEnvState.counters[3]; no layout changes)
+                             *    the call number in HgymEnvState.counters[HGYM_CNT_RESET_CALL]; no layout changes)
                              *    (same version, later: hgym_rollout_eval_step -- the rollout launch on the policy's mean action -- and the
                              *    evaluation accumulator hgym_eval_reset / hgym_eval_accumulate; no layout changes)
                              *    (same version, later: the diagnostics pass behind an update -- hgym_ppo_diag_reset, hgym_ppo_diag_reduce,
-                             *    hgym_ppo_diagnostics; no layout changes) */
+                             *    hgym_ppo_diagnostics; no layout changes)
+                             *    (same version, later: names for the slots of opt_state, log_stats and counters -- HGYM_OPT_*, HGYM_LOG_*,
+                             *    HGYM_CNT_*; no layout changes) */
 
 enum {
     HGYM_OK = 0,
@@ -178,7 +180,7 @@ typedef struct HgymEnvState {
     int64_t* counters;         /* [4] int64 device scalars: [0] common_step_counter, [1] resets this step,
                                   [2] ring step (frames pushed so far), [3] host-reset call number: hgym_env_reset_idx
                                   keys its draws by it and advances it (zero-filled by the caller once; seek-style moves of
-                                  [0] leave it alone) */
+                                  [0] leave it alone) -- HGYM_CNT_* below */
     float* commands;           /* 4 */
     float* actions;            /* 12 */
     float* last_actions;       /* 12 */
@@ -219,6 +221,11 @@ typedef struct HgymEnvState {
     float* custom_sums;             /* (K, N) their episode sums (episode_sums of the reference, legged_robot.py:225-227) */
     float* custom_acc;              /* (K,)   sum over the envs resetting this step of their episode sums (-> HgymEnvOut.extras_custom) */
 } HgymEnvState;
+/* slots of HgymEnvState.counters */
+#define HGYM_CNT_STEP 0          /* common_step_counter */
+#define HGYM_CNT_RESETS 1        /* resets this step */
+#define HGYM_CNT_RING 2          /* ring step (frames pushed so far) */
+#define HGYM_CNT_RESET_CALL 3    /* host-reset call number */
 
 /* Outputs of one env step = the 5-tuple of VecEnv.step (algo/vec_env.py:50-51) plus the extras tensors. */
 typedef struct HgymEnvOut {
@@ -247,13 +254,13 @@ typedef struct HgymEnvOut {
     /* Optional logging sink (log_stats == NULL: off): the step finaliser also keeps OnPolicyRunner.learn's per-step book-keeping
      * (algo/ppo/on_policy_runner.py:143-156) on the device, so that a logging run needs no host work between vec-steps:
      *   log_cur   (2, N) fp32   cur_reward_sum | cur_episode_length of every env (+= rew, += 1; zeroed when the env is done)
-     *   log_stats HGYM_LOG_STATS floats:
-     *     [0, 22)    sum over the steps since the caller last cleared it of extras["episode"][k] (what ep_infos.append collects)
-     *     [22]       number of those steps
-     *     [24], [25] head / fill count of the two rings below
-     *     [32, 132)  returns of the last 100 finished episodes (rewbuffer, a deque(maxlen=100)), in env order within a step
-     *     [132, 232) their lengths (lenbuffer)
-     * The caller zero-fills both once and clears log_stats[0, 23) after reading it. */
+     *   log_stats HGYM_LOG_STATS floats (HGYM_LOG_* below):
+     *     [0, 22)    TERMS      sum over the steps since the caller last cleared it of extras["episode"][k] (what ep_infos.append collects)
+     *     [22]       STEPS      number of those steps
+     *     [24], [25] RING_HEAD, RING_FILL  head / fill count of the two rings below
+     *     [32, 132)  RETURNS    returns of the last 100 (RING) finished episodes (rewbuffer, a deque(maxlen=100)), in env order within a step
+     *     [132, 232) LENGTHS    their lengths (lenbuffer)
+     * The caller zero-fills both once and clears log_stats[0, 23) = [0, HGYM_LOG_CLEAR) after reading it. */
     float* log_cur;
     float* log_stats;
     float* extras_custom;      /* (K,) extras["episode"]["rew_<name>"] of the user-defined terms, same staleness rule as extras_episode */
@@ -290,6 +297,14 @@ typedef struct HgymEnvOut {
     uint8_t* t_time_outs;
 } HgymEnvOut;
 #define HGYM_LOG_STATS 256
+#define HGYM_LOG_TERMS 0         /* 22 slots */
+#define HGYM_LOG_STEPS 22
+#define HGYM_LOG_CLEAR 23        /* the caller clears [0, HGYM_LOG_CLEAR) after reading */
+#define HGYM_LOG_RING_HEAD 24
+#define HGYM_LOG_RING_FILL 25
+#define HGYM_LOG_RING 100        /* entries of each of the two rings */
+#define HGYM_LOG_RETURNS 32
+#define HGYM_LOG_LENGTHS 132
 
 /* Optional externally supplied random draws (parity mode), row-major (N,k) tables indexed by env id.
  * A NULL member means "draw it from the internal Philox4x32-10 stream keyed by (seed, step, env, slot)". */
@@ -323,9 +338,9 @@ int32_t hgym_env_reset_all(const HgymEnvConfig* cfg, const HgymSimTensors* sim, 
  * episode sums (built-in and user-defined terms) accumulated, then zeroed; projected_gravity and base_euler of the new pose; both
  * history rings zeroed for those rows.  Every other env keeps every state field, sim tensor row, ring row and reset byte bit for
  * bit.  No observation is written (the reference's reset_idx computes none).  Finaliser: extras_episode / extras_custom = mean
- * over the reset envs / episode_length_s and extras_time_outs = time_out, unchanged when no env was reset; counters[0] and [2] do
- * not move, counters[1] is cleared, counters[3] advances; the transition and logging sinks of `out` are not touched.
- * Draws: the internal Philox stream keyed by (seed, counters[3], env, slot) with bit 30 of the high step word set -- words no step
+ * over the reset envs / episode_length_s and extras_time_outs = time_out, unchanged when no env was reset; counters[HGYM_CNT_STEP] and [HGYM_CNT_RING] do
+ * not move, counters[HGYM_CNT_RESETS] is cleared, counters[HGYM_CNT_RESET_CALL] advances; the transition and logging sinks of `out` are not touched.
+ * Draws: the internal Philox stream keyed by (seed, counters[HGYM_CNT_RESET_CALL], env, slot) with bit 30 of the high step word set -- words no step
  * draw uses, so two host resets, or a host reset and the next step's reset of the same env, draw different numbers.  `noise`
  * tables (u_dof, u_cmd[:, 3:6], u_xy, r_level; indexed by env id) override the draws as for the step.
  * Precondition: no step finaliser is pending (HgymEnvOut.defer_finalize) and no fused rollout is between hgym_rollout_begin and
@@ -476,18 +491,18 @@ typedef struct HgymPPOConfig {
                                        net->grads across ranks; apply forms the means (gradient and KL) itself */
     float aux_coef;                 /* weight of the auxiliary head's MSE in the total loss (0 with aux_layers = 0) */
     int32_t grad_norm_ready;        /* 1: net->grads is exactly what the preceding hgym_ppo_grad left (one rank, nothing touched it),
-                                       so its squared norm is already in opt_state[9] and apply skips its own pass over the
+                                       so its squared norm is already in opt_state[9] (GRAD_SQNORM) and apply skips its own pass over the
                                        gradient; 0 (or world_size > 1): apply computes the norm itself.  The flag is a PROMISE that every
                                        hgym_ppo_grad is followed by exactly one hgym_ppo_apply with the same configuration: on the fused
                                        bf16 path hgym_ppo_grad then also takes the adaptive-KL learning-rate decision and advances Adam's
                                        step count (the work of apply's prologue, done beside the weight-gradient launch).  A marker in
-                                       opt_state[13] keeps the two honest: a second hgym_ppo_grad before the apply does not advance the step
+                                       opt_state[13] (PROLOGUE_STEP) keeps the two honest: a second hgym_ppo_grad before the apply does not advance the step
                                        again, and an apply under another configuration does not repeat a prologue already taken.  (Not
                                        covered: a gradient call WITHOUT the flag followed by an apply WITH it -- no prologue runs.) */
     int32_t value_loss_unclipped;   /* the value loss (the reference's use_clipped_value_loss, ppo.py:158-166), in every path:
                                          0: max((V - R)^2, (V_old + clamp(V - V_old, -clip, clip) - R)^2).mean()  (the reference default)
                                          1: (R - V)^2.mean()  (use_clipped_value_loss = False)
-                                       opt_state[4] sums the form in use.  Any other value: HGYM_E_BADARG from every call taking the
+                                       opt_state[4] (VALUE_SUM) sums the form in use.  Any other value: HGYM_E_BADARG from every call taking the
                                        configuration.  Appended later within header v9, so a zero-filled tail is the clipped form. */
 } HgymPPOConfig;
 
@@ -497,7 +512,7 @@ int64_t hgym_net_workspace_bytes(const HgymNetConfig* net);
 
 /* Master parameters are ONE flat fp32 array in state_dict order
  * (std, actor.{0,2,4,6}.{weight,bias}, critic.{0,2,4,6}.{weight,bias}; SURVEY.md §5 checkpoint row);
- * grads/adam_m/adam_v have the same layout.  opt_state: 16 doubles on the device
+ * grads/adam_m/adam_v have the same layout.  opt_state: 16 doubles on the device (HGYM_OPT_* below, one name per slot)
  * [0] learning rate (python-double semantics of ppo.py:142-148)   [1] Adam step count
  * [2] sum of minibatch mean KL  [3] sum of surrogate losses  [4] sum of value losses  [5] sum of mean entropies
  * [6] gradient norm of the last step (before clipping)  [7] minibatches accumulated in [2..5]
@@ -508,12 +523,29 @@ int64_t hgym_net_workspace_bytes(const HgymNetConfig* net);
  * "prologue done, not applied" marker: Adam's betas must not change between a gradient call and the apply that follows it).
  * workspace: hgym_net_workspace_bytes() bytes, 256-byte aligned, ZERO-FILLED once by the caller before first use
  * (padding rows/columns of the operand buffers rely on it). */
+#define HGYM_OPT_STATE 16
+#define HGYM_OPT_LR 0                /* learning rate */
+#define HGYM_OPT_STEP 1              /* Adam step count */
+#define HGYM_OPT_KL_SUM 2            /* sum of minibatch mean KL */
+#define HGYM_OPT_SURROGATE_SUM 3     /* sum of surrogate losses */
+#define HGYM_OPT_VALUE_SUM 4         /* sum of value losses */
+#define HGYM_OPT_ENTROPY_SUM 5       /* sum of mean entropies */
+#define HGYM_OPT_GRAD_NORM 6         /* gradient norm of the last step (before clipping) */
+#define HGYM_OPT_MINIBATCHES 7       /* minibatches accumulated in [2..5] and [10] */
+#define HGYM_OPT_KL_LAST 8           /* mean KL of the last minibatch, rounded to fp32 */
+#define HGYM_OPT_GRAD_SQNORM 9       /* internal: squared norm of the gradient being formed */
+#define HGYM_OPT_AUX_SUM 10          /* sum of the auxiliary head's minibatch MSE losses */
+#define HGYM_OPT_STEP_SIZE 11        /* lr / (1 - beta1^t), as a float */
+#define HGYM_OPT_SQRT_BC2 12         /* sqrt(1 - beta2^t), as a float */
+#define HGYM_OPT_PROLOGUE_STEP 13    /* internal: the step whose beta^t lie in the next two / the "prologue done, not applied" marker */
+#define HGYM_OPT_BETA1_POW 14        /* internal: beta1^t */
+#define HGYM_OPT_BETA2_POW 15        /* internal: beta2^t */
 typedef struct HgymNet {
     float* params;
     float* grads;          /* hgym_net_param_count() + 1 floats: the flat gradient, then ONE slot carrying the minibatch mean KL */
     float* adam_m;
     float* adam_v;
-    double* opt_state;     /* [16] */
+    double* opt_state;     /* [HGYM_OPT_STATE] */
     void* workspace;       /* hgym_net_workspace_bytes() bytes, 256-byte aligned */
 } HgymNet;
 
@@ -661,7 +693,7 @@ int32_t hgym_eval_accumulate(int32_t n, const float* commands, const float* base
 
 /* One minibatch of PPO.update up to and including backward (ppo.py:128-171), device side only:
  * gathers rows `idx[0..B)` (indices into the flattened (T*N) storage, rollout_storage.py:151-182) of the
- * nine storage tensors, forward, KL -> learning-rate adaptation (written to opt_state[0]), clipped
+ * nine storage tensors, forward, KL -> learning-rate adaptation (written to opt_state[HGYM_OPT_LR]), clipped
  * surrogate + clipped value loss + entropy bonus, hand-written backward -> net->grads (un-clipped). */
 typedef struct HgymBatch {
     const float* obs;        /* (T*N, num_obs)   */
@@ -697,7 +729,7 @@ int32_t hgym_ppo_grad(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const 
  * (Until round 3 part 1 also launched the critic's weight-gradient products on their own, so that the first bucket travelled
  * under them: two launches of 144 and 112 workgroups on 256 CUs took 2 x 142 us against 178 us for the one launch, more than the
  * exchange they hid.  PPO.update now calls hgym_ppo_grad and exchanges ONE bucket.)
- * part 0 followed by part 1 leaves net->grads exactly as hgym_ppo_grad does (bit-identical), and opt_state[9] (the squared norm
+ * part 0 followed by part 1 leaves net->grads exactly as hgym_ppo_grad does (bit-identical), and opt_state[HGYM_OPT_GRAD_SQNORM] (the squared norm
  * hgym_ppo_apply may reuse with grad_norm_ready) complete: part 0 zeroes it and adds its bucket's share, part 1 adds the rest.
  * Between part 0 and part 1 it is partial; with world_size > 1 apply recomputes the norm of the rank mean regardless. */
 int32_t hgym_ppo_grad_part(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const HgymNet* net,
@@ -716,7 +748,7 @@ int64_t hgym_net_param_offset(const HgymNetConfig* cfg, int32_t which);
  *     logp_new  = sum_j -(a_j - mu_new_j)^2 / (2 std_j^2) - log std_j - log sqrt(2 pi)       ratio = expf(logp_new - logp_old)
  *     kl        = sum_j log(std_j / sigma_old_j) + (sigma_old_j^2 + (mu_old_j - mu_new_j)^2) / (2 std_j^2) - 1/2     (old || new, exact;
  *                 the learning-rate rule's expression, ppo.py:138-139, has + 1e-5 inside the logarithm: 1.2e-4 for a policy that did
- *                 not move at all, so its sum in opt_state[2] lies that much above this one)
+ *                 not move at all, so its sum in opt_state[HGYM_OPT_KL_SUM] lies that much above this one)
  *     surrogate = max(-A ratio, -A clamp(ratio, 1 - clip, 1 + clip))                         entropy = sum_j 1/2 + log sqrt(2 pi) + log std_j
  * and, widened to fp64, combined into block[HGYM_DIAG_*]:
  *   COUNT          rows                                   KL           sum kl

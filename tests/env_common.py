@@ -17,6 +17,7 @@ sys.path.insert(0, os.path.join(ROOT, "humanoid-gym_amd"))
 
 from oracle import xbot_constants as K  # noqa: E402
 from oracle.xbot_env_oracle import XBotEnvOracle  # noqa: E402
+from hgym import _lib as L
 
 RTOL, ATOL = 1e-5, 2e-6
 
@@ -293,7 +294,7 @@ def run_random_trace(backend, N, steps, seed, sim_layout="soa", frame_stack=15, 
         o.episode_sums = sums.clone()
         env.buf.view("episode_sums").copy_(sums)
     o.common_step_counter = csc
-    env.buf.counters[0] = csc
+    env.buf.counters[L.CNT_STEP] = csc
     counts = dict(reset=0, timeout=0, push=0, stale=0, level_up=0, level_down=0, range_moves=0)
     for t in range(steps):
         a_in = torch.randn(N, 12, generator=g) * 1.5
@@ -358,7 +359,7 @@ def run_generic_golden(backend, golden_dir):
     close(b.root, G["prime_root"], "prime root (spawn jitter)")
     exact(b.terrain_levels, G["terrain_levels0"], "prime levels")
     b.episode_length.copy_(T(G["init_ep_len"]))
-    b.counters[0] = int(G["init_common_step_counter"])
+    b.counters[L.CNT_STEP] = int(G["init_common_step_counter"])
     b.view("episode_sums").copy_(T(G["init_episode_sums"]))
     moved = 0
     for t in range(G["rew"].shape[0]):
@@ -379,7 +380,7 @@ def run_generic_golden(backend, golden_dir):
         H, HC = 15, 3
         close(b.obs[:, (H - 1) * 47:], np.clip(G["frame"][t], -K.CLIP_OBS, K.CLIP_OBS), tag + "newest obs frame")
         close(b.priv_obs[:, (HC - 1) * 73:], np.clip(G["priv_frame"][t], -K.CLIP_OBS, K.CLIP_OBS), tag + "newest priv frame")
-        close(b.obs_ring.view(N, H, 47)[:, (int(b.counters[2]) - 1) % H], G["frame"][t], tag + "ring frame")
+        close(b.obs_ring.view(N, H, 47)[:, (int(b.counters[L.CNT_RING]) - 1) % H], G["frame"][t], tag + "ring frame")
         moved += int(t > 0 and list(G["cmd_range_x"][t]) != list(G["cmd_range_x"][t - 1]))
     assert moved == 1
     return env
@@ -397,7 +398,7 @@ def run_reset_golden(backend, golden_dir):
     env.prime(Tn(G["prime_u_dof"]), Tn(G["prime_u_cmd"]), Tn(G["prime_z_obs"]))
     backend.sync()
     env.buf.episode_length.copy_(Tn(G["init_ep_len"]))
-    env.buf.counters[0] = int(G["init_common_step_counter"])
+    env.buf.counters[L.CNT_STEP] = int(G["init_common_step_counter"])
 
     def step(g, a_in, tag):
         frame = (Tn(g("root")), Tn(g("dof")), Tn(g("contact")), Tn(g("rigid")))

@@ -34,6 +34,7 @@ import torch
 import env_common as EC
 from oracle import xbot_constants as K
 from oracle.xbot_env_oracle import XBotEnvOracle
+from hgym import _lib as L
 
 F = lambda x: float(np.float32(x))
 FEET, KNEES, BASE = list(K.FEET_BODIES), list(K.KNEE_BODIES), K.BASE_BODY
@@ -583,7 +584,7 @@ def make_pair(plan, cfg, backend=None, sim_layout="soa", rows_ahead=False):
         b.view("last_contacts").copy_(plan.last_contacts.float())
         b.dof_pos_view().copy_(plan.pre_dof_pos)
         b.dof_vel_view().copy_(plan.pre_dof_vel)
-        b.counters[0] = cfg["csc"]
+        b.counters[L.CNT_STEP] = cfg["csc"]
     return o, env
 
 
@@ -960,7 +961,7 @@ def run_generic(backend, pass_name, sim_layout="soa"):
     csc = K.MAX_EPISODE_LENGTH - 1                                      # the step lands on the command-curriculum check (and on a push)
     o.ep_len, o.commands, o.episode_sums, o.common_step_counter = ep.clone(), cmd.clone(), sums.clone(), csc
     b = env.buf
-    b.episode_length.copy_(ep); b.view("commands").copy_(cmd); b.view("episode_sums").copy_(sums); b.counters[0] = csc
+    b.episode_length.copy_(ep); b.view("commands").copy_(cmd); b.view("episode_sums").copy_(sums); b.counters[L.CNT_STEP] = csc
     if gp["range0"] is not None:
         o.cmd_range_x = list(gp["range0"])
         b.command_range_x.copy_(torch.tensor(gp["range0"], dtype=torch.float64))

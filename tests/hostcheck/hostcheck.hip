@@ -53,7 +53,7 @@ int hc_env_step_phase(const HgymEnvConfig* cfg, const HgymSimTensors* sim, const
     const EnvArgs A = make_args(cfg, sim, st, out, noise, actions_in, MODE_STEP, phase == 2 ? 0 : fused, epb, phase);
     const int N = cfg->num_envs;
     const int blocks = (N + epb - 1) / epb;
-    const int64_t csc0 = st->counters[0], ring = st->counters[2];
+    const int64_t csc0 = st->counters[HGYM_CNT_STEP], ring = st->counters[HGYM_CNT_RING];
     std::vector<float> smem(step_smem_bytes(epb) / sizeof(float));
     for (int b = 0; b < blocks; ++b) {
         for (int t = 0; t < nthreads; ++t) env_stage_in<0>(A, b, t, nthreads, smem.data());
@@ -102,7 +102,7 @@ int hc_env_step_ex(const HgymEnvConfig* cfg, const HgymSimTensors* sim, const Hg
     const EnvArgs A = make_args(cfg, sim, st, out, noise, actions_in, mode, fused, epb);
     const int N = cfg->num_envs;
     const int blocks = (N + epb - 1) / epb;
-    const int64_t csc0 = st->counters[0], ring = st->counters[2];
+    const int64_t csc0 = st->counters[HGYM_CNT_STEP], ring = st->counters[HGYM_CNT_RING];
     std::vector<float> smem(step_smem_bytes(epb) / sizeof(float));
     // the previous step's reset flags, as hgym_rollout_step is handed them (prev_out->reset): the rows-ahead protocol below zeroes the
     // frames that step copied ahead for an env it then reset in the NEXT call, as the device does since round 4 (HGYM_RO_AHEAD_CRITIC)
@@ -221,7 +221,7 @@ int hc_finalize_forms(const HgymEnvConfig* cfg, const HgymEnvState* st, const Hg
 
 int hc_pre_physics(const HgymEnvConfig* cfg, const HgymEnvState* st, float* actions_in, const HgymEnvNoise* noise) {
     const EnvArgs A = make_args(cfg, nullptr, st, nullptr, noise, actions_in, MODE_STEP, 0, 4);
-    const RngKey rk = make_rng_key(A, st->counters[0]);
+    const RngKey rk = make_rng_key(A, st->counters[HGYM_CNT_STEP]);
     for (int e = 0; e < cfg->num_envs; ++e) pre_physics_env(A, rk, e, cfg->num_envs);
     return 0;
 }
@@ -234,7 +234,7 @@ int hc_pd_torques(const HgymEnvConfig* cfg, const HgymSimTensors* sim, const Hgy
 
 int hc_synth_physics(const HgymEnvConfig* cfg, const HgymSimTensors* sim, const HgymEnvState* st) {
     const EnvArgs A = make_args(cfg, sim, st, nullptr, nullptr, nullptr, MODE_STEP, 0, 4);
-    const RngKey rk = make_rng_key(A, st->counters[0]);
+    const RngKey rk = make_rng_key(A, st->counters[HGYM_CNT_STEP]);
     for (int e = 0; e < cfg->num_envs; ++e) synth_physics_env(A, rk, e, cfg->num_envs);
     return 0;
 }

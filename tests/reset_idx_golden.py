@@ -8,6 +8,7 @@ import torch
 import env_common as EC
 from oracle import xbot_constants as K
 from oracle.xbot_env_oracle import XBotEnvOracle
+from hgym import _lib as L
 
 Tn = lambda a: torch.from_numpy(np.asarray(a))
 AFTER_FIELDS = ("commands", "actions", "last_actions", "last_last_actions", "last_dof_vel", "feet_air_time", "episode_sums",
@@ -81,7 +82,7 @@ def run_reset_idx_golden(backend, path):
         env.prime(Tn(G["prime_u_dof"]), Tn(G["prime_u_cmd"]), Tn(G["prime_z_obs"]), *prime_extra)
         backend.sync()
         env.buf.episode_length.copy_(Tn(G["init_ep_len"]))
-        env.buf.counters[0] = int(G["init_common_step_counter"])
+        env.buf.counters[L.CNT_STEP] = int(G["init_common_step_counter"])
     else:
         o = XBotEnvOracle(N, frictions=Tn(G["friction"]), body_mass=Tn(G["body_mass"]), terrain=spec, command_curriculum=generic,
                           max_curriculum=max_curr if generic else 1.0)

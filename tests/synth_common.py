@@ -15,6 +15,7 @@ import env_common as EC
 from oracle import synth_env_oracle as S
 from oracle import xbot_constants as K
 from oracle.xbot_env_oracle import XBotEnvOracle
+from hgym import _lib as L
 
 LOW_SPEED_QUANTUM = 3.2 * 0.2 * K.DT + 1e-5      # largest jump of the low_speed term (-2 <-> 1.2) times its scale times dt
 
@@ -51,9 +52,9 @@ def oracle_from_buffers(buf):
         setattr(o, name, c(buf.view(name)).contiguous())
     o.last_contacts = c(buf.view("last_contacts")) > 0.5
     o.ep_len = c(buf.episode_length)
-    o.common_step_counter = int(buf.counters[0])
+    o.common_step_counter = int(buf.counters[L.CNT_STEP])
     H, HC = o.H, o.Hc
-    ring = int(buf.counters[2])
+    ring = int(buf.counters[L.CNT_RING])
     order = [(ring + k) % H for k in range(H)]                       # oldest -> newest
     o.obs_hist = c(buf.obs_ring).view(N, H, K.NUM_SINGLE_OBS)[:, order].contiguous()
     order_c = [(ring + k) % HC for k in range(HC)]
@@ -98,7 +99,7 @@ def plant(buf, o, gen, csc=397):
     ep = torch.randint(0, 2400, (N,), generator=gen)
     ep[: min(N, 8)] = torch.tensor([2399, 2398, 799, 1598, 0, 2396, 798, 2397])[: min(N, 8)]
     buf.episode_length.copy_(ep.to(buf.episode_length.device))
-    buf.counters[0] = csc
+    buf.counters[L.CNT_STEP] = csc
     if o is not None:
         o.ep_len = ep.clone()
         o.common_step_counter = csc

@@ -14,6 +14,7 @@ import torch.nn as nn
 import bf16_report as BR
 import layer_path_common as LP
 from oracle import ppo_oracle as P
+from hgym import _lib as L
 
 pytestmark = pytest.mark.gpu
 
@@ -140,7 +141,7 @@ def test_gradient_vs_restated_reference(name, shape, precision, monkeypatch):
     BR.check("gradient %s %s %s vs restated reference (worst tensor: %s)" % (name, shape, precision, worst), errs[worst],
              GRAD_TOL if precision == "bf16" else F32_GRAD_TOL)
     opt = net.opt_state.cpu()
-    np.testing.assert_allclose(float(opt[4]), float(want["value_loss"]), rtol=1e-2)
+    np.testing.assert_allclose(float(opt[L.OPT_VALUE_SUM]), float(want["value_loss"]), rtol=1e-2)
 
 
 def test_denoiser_head_under_tanh():
@@ -210,11 +211,11 @@ def test_runner_trains_and_captured_update_equals_eager(name, monkeypatch, tmp_p
         r.learn(num_learning_iterations=3, init_at_random_ep_len=False)
         torch.cuda.synchronize()
         assert (r._update_graph is not None) == (mode == "1")
-        assert int(alg.net.opt_state[1]) == 3 * alg.num_learning_epochs * alg.num_mini_batches
+        assert int(alg.net.opt_state[L.OPT_STEP]) == 3 * alg.num_learning_epochs * alg.num_mini_batches
         opt = alg.net.opt_state.clone()
-        assert torch.isfinite(opt[:9]).all() and torch.isfinite(alg.net.params).all()
-        if float(opt[9]) >= 128.0:      # fp64 atomics beyond their exact range (tests/test_fused_gpu.py)
-            opt[9] = 0.0
+        assert torch.isfinite(opt[:L.OPT_GRAD_SQNORM]).all() and torch.isfinite(alg.net.params).all()
+        if float(opt[L.OPT_GRAD_SQNORM]) >= 128.0:      # fp64 atomics beyond their exact range (tests/test_fused_gpu.py)
+            opt[L.OPT_GRAD_SQNORM] = 0.0
         outs[mode] = (alg.net.params.clone(), alg.net.adam_m.clone(), alg.net.adam_v.clone(), opt)
         if mode == "0":
             policy = r.get_inference_policy()           # act_inference: the HIP forward

@@ -5,6 +5,7 @@ privileged row) under coef * MSE, trained jointly with PPO (one flat gradient, o
 import numpy as np
 import pytest
 import torch
+from hgym import _lib as L
 
 pytestmark = pytest.mark.gpu
 AUX_OUT, AUX_OFF = 73, 146
@@ -65,7 +66,7 @@ def test_aux_head_forward_loss_and_gradient_vs_autograd(precision, tol, shape):
     cols, idx, batch = _batch(S, B)
     ppo_plain, ppo_full = make_ppo_config(), make_ppo_config(aux_coef=coef)
     plain.ppo_grad(ppo_plain, batch)
-    full.opt_state[10] = 0.0
+    full.opt_state[L.OPT_AUX_SUM] = 0.0
     for _ in range(2):                                      # twice: nothing may accumulate across calls except opt[10]
         full.ppo_grad(ppo_full, batch)
     torch.cuda.synchronize()
@@ -79,7 +80,7 @@ def test_aux_head_forward_loss_and_gradient_vs_autograd(precision, tol, shape):
     y = model(obs)
     mse = ((y - priv[:, AUX_OFF:AUX_OFF + AUX_OUT]) ** 2).mean()
     (coef * mse).backward()
-    np.testing.assert_allclose(float(full.opt_state[10]) / 2, float(mse.detach()), rtol=tol)
+    np.testing.assert_allclose(float(full.opt_state[L.OPT_AUX_SUM]) / 2, float(mse.detach()), rtol=tol)
     yk = full.forward(2, obs.contiguous())
     torch.cuda.synchronize()
     scale = float(y.abs().max())
@@ -102,10 +103,10 @@ def test_joint_update_moves_the_head_and_lowers_its_loss(shape):
     ppo = make_ppo_config(aux_coef=1.0, grad_norm_ready=True)
     losses = []
     for it in range(6):
-        full.opt_state[10] = 0.0
+        full.opt_state[L.OPT_AUX_SUM] = 0.0
         full.ppo_grad(ppo, batch)
         full.ppo_apply(ppo)
-        losses.append(float(full.opt_state[10]))
+        losses.append(float(full.opt_state[L.OPT_AUX_SUM]))
     torch.cuda.synchronize()
     assert torch.isfinite(full.params).all()
     assert losses[-1] < losses[0], losses

@@ -14,6 +14,7 @@ import torch
 import env_common as EC
 from oracle import xbot_constants as K
 from oracle.xbot_env_oracle import XBotEnvOracle
+from hgym import _lib as L
 
 # name -> (scale, oracle fn, product fn over the env buffers): one term that sorts first, one in the middle, one last, and one
 # that REPLACES a built-in term (a subclass overriding `_reward_torques`)
@@ -74,7 +75,7 @@ def run_custom_trace(be, N, steps, seed):
     o.ep_len = ep.clone()
     b.episode_length.copy_(ep)
     o.common_step_counter = 397
-    b.counters[0] = 397
+    b.counters[L.CNT_STEP] = 397
     resets = 0
     for t in range(steps):
         a_in = torch.randn(N, 12, generator=g) * 1.5

@@ -8,6 +8,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
+from hgym import _lib as L
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -31,14 +32,14 @@ def _worker(rank, world, port, out_dir):
     inv_w = torch.tensor(1.0 / world, dtype=torch.float32)
     grads = ext[:P] * inv_w
     opt = torch.zeros(16, dtype=torch.float64)
-    opt[8] = float(ext[P] * inv_w)
+    opt[L.OPT_KL_LAST] = float(ext[P] * inv_w)
     # advantage statistics of this rank's shard
     adv = torch.randn(60, 7, generator=g) * (1 + rank) + rank
     stats = torch.tensor([adv.double().sum(), (adv.double() ** 2).sum(), adv.numel()], dtype=torch.float64)
     D.allreduce_adv_stats(stats)
     w = torch.full((5,), float(rank))
     D.broadcast_parameters([torch.nn.Parameter(w)])
-    torch.save(dict(g_in=g_in, g_out=grads, kl=opt[8].clone(), adv=adv, stats=stats, w=w), os.path.join(out_dir, "r%d.pt" % rank))
+    torch.save(dict(g_in=g_in, g_out=grads, kl=opt[L.OPT_KL_LAST].clone(), adv=adv, stats=stats, w=w), os.path.join(out_dir, "r%d.pt" % rank))
     dist.destroy_process_group()
 
 

@@ -10,6 +10,7 @@ import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
+from hgym import _lib as L
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -94,7 +95,7 @@ def _worker(rank, world, port, out_dir, backend="gloo", num_envs=256, iters=4, c
         p2p = t if want_p2p else None
     else:
         assert not want_p2p
-    torch.save(dict(p_init=p_init.cpu(), params=net.params.cpu(), lr=float(net.opt_state[0]), steps=float(net.opt_state[1]),
+    torch.save(dict(p_init=p_init.cpu(), params=net.params.cpu(), lr=float(net.opt_state[L.OPT_LR]), steps=float(net.opt_state[L.OPT_STEP]),
                     obs=runner.alg.storage._obs_all[1].cpu(), graph=runner._graph is not None, friction=friction, commands0=commands0,
                     env_seed=seed, comm_events=len(runner.alg.comm_timing or []), update_graph=runner._update_graph is not None,
                     comm_calls=(runner.alg._comm.seq if runner.alg._comm is not None else 0), split=net.bucket_split, P=net.P, p2p=p2p, report=rep),
@@ -358,7 +359,7 @@ def _single_rank_worker(rank, world, port, out_dir, collectives):
     runner.learn(num_learning_iterations=4, init_at_random_ep_len=True)
     torch.cuda.synchronize()
     net = runner.alg.net
-    torch.save(dict(params=net.params.cpu(), lr=float(net.opt_state[0]), comm_events=len(runner.alg.comm_timing)),
+    torch.save(dict(params=net.params.cpu(), lr=float(net.opt_state[L.OPT_LR]), comm_events=len(runner.alg.comm_timing)),
                os.path.join(out_dir, "single%d.pt" % int(collectives)))
     if collectives:
         dist.destroy_process_group()

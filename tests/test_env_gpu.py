@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import env_common as EC
+from hgym import _lib as L
 
 pytestmark = pytest.mark.gpu
 T = lambda a: torch.from_numpy(np.asarray(a))
@@ -30,7 +31,7 @@ def test_golden_trace_gpu(hip, golden_dir, name):
     EC.close(env.buf.obs, G["prime_obs"], "prime obs")
     EC.close(env.buf.priv_obs, G["prime_priv"], "prime priv")
     env.buf.episode_length.copy_(T(G["init_ep_len"]))
-    env.buf.counters[0] = int(G["init_common_step_counter"])
+    env.buf.counters[L.CNT_STEP] = int(G["init_common_step_counter"])
     full = {int(s) for s in G["full_steps"]}
     for t in range(G["rew"].shape[0]):
         frame = (T(G["root"][t]), T(G["dof"][t]), T(G["contact"][t]), T(G["rigid"][t]))
@@ -148,7 +149,7 @@ def test_fused_synthetic_step_properties(hip, N):
         assert bool((buf.time_out <= reset).all())
         total_resets += int(reset.sum())
         prev_obs, prev_ep = obs.clone(), buf.episode_length.clone()
-    assert int(buf.counters[0]) == 30 and int(buf.counters[2]) == 31
+    assert int(buf.counters[L.CNT_STEP]) == 30 and int(buf.counters[L.CNT_RING]) == 31
     assert total_resets > 0
 
 

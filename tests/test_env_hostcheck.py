@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import env_common as EC
+from hgym import _lib as L
 
 T = lambda a: torch.from_numpy(np.asarray(a))
 
@@ -31,7 +32,7 @@ def test_golden_trace_host(host, golden_dir, name):
     EC.close(env.buf.obs, G["prime_obs"], "prime obs")
     EC.close(env.buf.priv_obs, G["prime_priv"], "prime priv")
     env.buf.episode_length.copy_(T(G["init_ep_len"]))
-    env.buf.counters[0] = int(G["init_common_step_counter"])
+    env.buf.counters[L.CNT_STEP] = int(G["init_common_step_counter"])
     full = {int(s) for s in G["full_steps"]}
     for t in range(G["rew"].shape[0]):
         frame = (T(G["root"][t]), T(G["dof"][t]), T(G["contact"][t]), T(G["rigid"][t]))
@@ -165,7 +166,7 @@ def test_finaliser_one_pass_form_equals_the_general_one_host(N, nthreads, resets
         buf.time_out.copy_(torch.rand(N, generator=gg) < 0.4)
         buf.extras_time_outs.copy_(torch.rand(N, generator=gg) < 0.5)
         buf.episode_acc.copy_(torch.randn(24, generator=gg))
-        buf.counters[1] = resets
+        buf.counters[L.CNT_RESETS] = resets
         sink = dict(values=torch.randn(N, generator=gg), rewards=torch.full((N,), float("nan")), dones=torch.zeros(N, dtype=torch.bool),
                     step=torch.zeros(1, dtype=torch.int64), gamma=0.994)
         st, out = buf.state_struct(), buf.out_struct(sink=sink)
@@ -206,7 +207,7 @@ def test_finaliser_deferred_sink_stores_raw_rewards_and_bootstrap_flags_host(N, 
         buf.time_out.copy_(torch.rand(N, generator=gg) < 0.4)
         buf.extras_time_outs.copy_(torch.rand(N, generator=gg) < 0.5)
         buf.episode_acc.copy_(torch.randn(24, generator=gg))
-        buf.counters[1] = resets
+        buf.counters[L.CNT_RESETS] = resets
         values = torch.randn(N, generator=gg)
         sink = dict(values=None if kind != "immediate" else values, rewards=torch.full((N,), float("nan")), dones=torch.zeros(N, dtype=torch.bool),
                     time_outs=torch.full((N,), 7, dtype=torch.uint8), step=torch.zeros(1, dtype=torch.int64), gamma=0.994)

@@ -17,6 +17,7 @@ import torch
 import bf16_report as BR
 import evaluate_common as ECM
 import evaluate_common as EC
+from hgym import _lib as L
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -59,7 +60,7 @@ def _seed_window(env):
     """Time-outs, command resampling and a push inside a 60-step window (tests/test_fused_gpu.py)."""
     n = env.num_envs
     env.episode_length_buf = (torch.arange(n, device="cuda") * 37) % 2400
-    env._buf.counters[0] = 390
+    env._buf.counters[L.CNT_STEP] = 390
 
 
 EC_np = ECM.EvalAccumulatorNp
@@ -402,10 +403,10 @@ def test_learn_evaluates_every_eval_interval(tmp_path, interval):
     r.wait_for_saves()
     rows = [x for x in r.writer.rows if x[0] == "Eval/mean_episode_return"]
     if interval == 0:
-        assert not [x for x in r.writer.rows if x[0].startswith("Eval/")] and int(env._buf.counters[0]) == 0 and r.last_eval is None
+        assert not [x for x in r.writer.rows if x[0].startswith("Eval/")] and int(env._buf.counters[L.CNT_STEP]) == 0 and r.last_eval is None
     else:
         assert [x[2] for x in rows] == [1, 3] and set(r.last_eval) >= {"episodes", "mean_reward_per_step"}
-        assert int(env._buf.counters[0]) > 0
+        assert int(env._buf.counters[L.CNT_STEP]) > 0
 
 
 def test_evaluate_script_prints_one_json_line():

@@ -24,6 +24,7 @@ import os
 
 import pytest
 import torch
+from hgym import _lib as L
 
 pytestmark = pytest.mark.gpu
 
@@ -182,7 +183,7 @@ def test_reset_idx_after_a_restore_draws_what_the_original_draws():
     A.reset_idx([3, 9])
     A.reset_idx([50, 9])
     sd = A.state_dict()
-    assert int(sd["counters"][3]) == 2
+    assert int(sd["counters"][L.CNT_RESET_CALL]) == 2
     A.reset_idx([7, 40])
     A.step(actions[4])
     end_a = A.state_dict()
@@ -194,12 +195,12 @@ def test_reset_idx_after_a_restore_draws_what_the_original_draws():
     B.reset_idx([7, 40])
     B.step(actions[4])
     _same_state(B.state_dict(), end_a, "reset_idx after a restore")
-    assert int(B._buf.counters[3]) == 3
+    assert int(B._buf.counters[L.CNT_RESET_CALL]) == 3
     # ... and it is the call number that does it: with counters[3] put back to 0 the same call draws other joint offsets
     C_ = _env(args, env_cfg)
     C_.reset()
     C_.load_state_dict(sd)
-    C_._buf.counters[3] = 0
+    C_._buf.counters[L.CNT_RESET_CALL] = 0
     C_.reset_idx([7, 40])
     B.load_state_dict(sd)
     B.reset_idx([7, 40])
@@ -272,7 +273,7 @@ def _runner(tmp, num_envs=64, seed=31, exact=True, presteps=0, save_interval=2):
 def _run_state(r):
     torch.cuda.synchronize()
     alg, net = r.alg, r.alg.net
-    return dict(params=net.params.clone(), adam_m=net.adam_m.clone(), adam_v=net.adam_v.clone(), opt01=net.opt_state[0:2].clone(),
+    return dict(params=net.params.clone(), adam_m=net.adam_m.clone(), adam_v=net.adam_v.clone(), opt01=net.opt_state[L.OPT_LR:L.OPT_STEP + 1].clone(),
                 sample_step=alg._sample_step.clone(), perm_draws=torch.tensor([alg._perm_draws, int(alg._perm_draws_dev)]),
                 iteration=torch.tensor(r.current_learning_iteration), obs_slot0=alg.storage._obs_all[0].clone(),
                 priv_slot0=alg.storage._priv_all[0].clone()), r.env.state_dict()
@@ -324,7 +325,7 @@ def test_resumed_run_is_the_run_default_plan(tmp_path):
     assert torch.load(os.path.join(u.log_dir, "envstate_4.pt"), map_location="cpu")["iterations_done"] == 4
     ck = torch.load(os.path.join(u.log_dir, "model_2.pt"), map_location="cpu")
     assert set(ck) == KEYS4 and ck["iter"] == 0          # (the reference's stale count: why the sidecar carries its own)
-    assert int(side["env"]["counters"][0]) == 1 + 3 * u.num_steps_per_env
+    assert int(side["env"]["counters"][L.CNT_STEP]) == 1 + 3 * u.num_steps_per_env
     r = _resumed(tmp_path / "r", os.path.join(u.log_dir, "model_2.pt"))
     assert r.current_learning_iteration == 4 and r._graph is None        # (R's one iteration ran eagerly; U's fourth was a graph replay)
     _exact_regime(u, "default plan")
@@ -394,7 +395,7 @@ def test_off_means_off(tmp_path, monkeypatch):
     before = r.env.state_dict()
     r.load(os.path.join(u.log_dir, "model_3.pt"))
     after = r.env.state_dict()
-    assert int(after["counters"][0]) == r.env._seek_base + 3 * r.num_steps_per_env and r.current_learning_iteration == 3
+    assert int(after["counters"][L.CNT_STEP]) == r.env._seek_base + 3 * r.num_steps_per_env and r.current_learning_iteration == 3
     assert torch.equal(after["counters"][1:], before["counters"][1:])
     _same_state(before, after, "load() without a sidecar", skip=("counters",))
     assert not r._keep_episode_lengths
@@ -426,12 +427,12 @@ def test_load_optimizer_false_keeps_its_meaning_without_the_switch(tmp_path):
     plain = _runner(None, exact=False)
     plain.load(path, load_optimizer=False)
     torch.cuda.synchronize()
-    assert plain.current_learning_iteration == 1 and float(plain.alg.net.adam_v.abs().max()) == 0.0 and int(plain.alg.net.opt_state[1]) == 0
+    assert plain.current_learning_iteration == 1 and float(plain.alg.net.adam_v.abs().max()) == 0.0 and int(plain.alg.net.opt_state[L.OPT_STEP]) == 0
     _same_state(plain.env.state_dict(), u.env.state_dict(), "env restored")
     exact = _runner(None, exact=True)
     exact.load(path, load_optimizer=False)
     torch.cuda.synchronize()
-    assert torch.equal(exact.alg.net.adam_v, u.alg.net.adam_v) and torch.equal(exact.alg.net.opt_state[0:2], u.alg.net.opt_state[0:2])
+    assert torch.equal(exact.alg.net.adam_v, u.alg.net.adam_v) and torch.equal(exact.alg.net.opt_state[L.OPT_LR:L.OPT_STEP + 1], u.alg.net.opt_state[L.OPT_LR:L.OPT_STEP + 1])
     ignored = _runner(None, exact=True, presteps=2)
     before = ignored.env.state_dict()
     ignored.load(path, env_state=False)                  # today's load(), sidecar or not

@@ -16,6 +16,7 @@ import torch.nn as nn
 import bf16_report as BR
 import layer_path_common as LP
 from oracle import ppo_oracle as P
+from hgym import _lib as L
 
 pytestmark = pytest.mark.gpu
 
@@ -204,7 +205,7 @@ def test_gradient_vs_restated_reference(name, shape, xb16, unclipped, monkeypatc
     worst = max(errs, key=errs.get)
     BR.check("fused gradient %s %s %s%s vs restated reference (worst tensor: %s)" % (name, shape, "shadow" if xb16 else "fp32 rows",
                                                                                     ", unclipped" if unclipped else "", worst), errs[worst], GRAD_TOL)
-    np.testing.assert_allclose(float(net.opt_state[4]), float(want["value_loss"]), rtol=1e-2)
+    np.testing.assert_allclose(float(net.opt_state[L.OPT_VALUE_SUM]), float(want["value_loss"]), rtol=1e-2)
 
 
 # ---------------------------------------------------------------------------------------------- 5. auxiliary head
@@ -249,7 +250,7 @@ def test_auxiliary_head_under_tanh():
             h = z
     mse = ((h - priv[idx].double()[:, OFF:OFF + 32]) ** 2).mean()
     (coef * mse).backward()
-    np.testing.assert_allclose(float(net.opt_state[10]), float(mse.detach()), rtol=1e-2)
+    np.testing.assert_allclose(float(net.opt_state[L.OPT_AUX_SUM]), float(mse.detach()), rtol=1e-2)
     gv = net.grad_views()
     errs = {}
     for l, (W, b) in enumerate(layers):
@@ -301,7 +302,7 @@ def test_fused_rollout_step_equals_act_then_step(name, num_envs, monkeypatch):
         r = _runner(num_envs, 31, ACTS[name], monkeypatch, steps=6)
         assert r.alg.net.shadow_ld(0) == 768 and r.env.rollout_fused_mode(r.alg.net) is not None
         r.env.episode_length_buf = 2400 - 2 - (torch.arange(num_envs, device="cuda") % 5)       # time-outs at steps 1 .. 5 of every rollout
-        r.env._buf.counters[0] = 398                                                            # a push (every 400 steps) too
+        r.env._buf.counters[L.CNT_STEP] = 398                                                            # a push (every 400 steps) too
         r.learn(num_learning_iterations=2, init_at_random_ep_len=False)
         torch.cuda.synchronize()
         st, b = r.alg.storage, r.env._buf
@@ -372,11 +373,11 @@ def test_runner_trains_and_captured_update_equals_eager(name, monkeypatch, tmp_p
         r.learn(num_learning_iterations=3, init_at_random_ep_len=False)
         torch.cuda.synchronize()
         assert (r._update_graph is not None) == (mode == "1") and r._graph is not None
-        assert int(alg.net.opt_state[1]) == 3 * alg.num_learning_epochs * alg.num_mini_batches
+        assert int(alg.net.opt_state[L.OPT_STEP]) == 3 * alg.num_learning_epochs * alg.num_mini_batches
         opt = alg.net.opt_state.clone()
-        assert torch.isfinite(opt[:9]).all() and torch.isfinite(alg.net.params).all()
-        if float(opt[9]) >= 128.0:      # fp64 atomics beyond their exact range (tests/test_fused_gpu.py)
-            opt[9] = 0.0
+        assert torch.isfinite(opt[:L.OPT_GRAD_SQNORM]).all() and torch.isfinite(alg.net.params).all()
+        if float(opt[L.OPT_GRAD_SQNORM]) >= 128.0:      # fp64 atomics beyond their exact range (tests/test_fused_gpu.py)
+            opt[L.OPT_GRAD_SQNORM] = 0.0
         outs[mode] = (alg.net.params.clone(), alg.net.adam_m.clone(), alg.net.adam_v.clone(), opt)
         if mode == "0":
             policy = r.get_inference_policy()

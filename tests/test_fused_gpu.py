@@ -11,6 +11,7 @@ import torch
 import bf16_report as BR
 from oracle import ppo_oracle as P
 from oracle import xbot_constants as K
+from hgym import _lib as L
 
 pytestmark = pytest.mark.gpu
 NAMES = ["std"] + ["actor.%d.%s" % (i, k) for i in (0, 2, 4, 6) for k in ("weight", "bias")] + \
@@ -125,8 +126,8 @@ def test_fused_grad_vs_oracle_per_tensor(S, B, n_obs, n_priv):
     print("fused bf16 gradient vs bf16-operand oracle: worst per-tensor rel-L2 %.3e (S=%d, B=%d)" % (worst, S, B))
     assert _rel(net.forward(0, c(obs[idx][:64])).cpu(), P.mlp_forward(obs[idx][:64], p.actor, quant=P.bf16_round)) <= 2e-3
     opt = net.opt_state.cpu()
-    np.testing.assert_allclose(float(opt[8]), float(out["kl"]), rtol=2e-2, atol=1e-4)
-    np.testing.assert_allclose(float(opt[4]) / 2, float(out["value_loss"]), rtol=1e-2)
+    np.testing.assert_allclose(float(opt[L.OPT_KL_LAST]), float(out["kl"]), rtol=2e-2, atol=1e-4)
+    np.testing.assert_allclose(float(opt[L.OPT_VALUE_SUM]) / 2, float(out["value_loss"]), rtol=1e-2)
 
 
 def test_gradient_norm_of_the_gradient_call_has_the_same_bits_every_time():
@@ -152,10 +153,10 @@ def test_gradient_norm_of_the_gradient_call_has_the_same_bits_every_time():
         net.load_state_dict(dict(zip(NAMES, p.tensors())))
         net.ppo_grad(make_ppo_config(), make_batch(obs, priv, act, val, adv, ret, lp_o, mu_o, sg_o, idx))
         torch.cuda.synchronize()
-        sq = float(net.opt_state[9])
+        sq = float(net.opt_state[L.OPT_GRAD_SQNORM])
         want = float(net.grads[:net.P].double().pow(2).sum())
         assert 0.0 < sq < 128.0 and abs(sq - want) <= 2e-11 + 1e-13 * want, (sq, want)
-        seen.append((net.opt_state[9].clone(), net.grads.clone()))
+        seen.append((net.opt_state[L.OPT_GRAD_SQNORM].clone(), net.grads.clone()))
         del net
     for a, b in seen[1:]:
         assert torch.equal(b, seen[0][1])                                      # (the gradient itself: fixed-order slab sums)
@@ -261,13 +262,13 @@ def test_captured_update_equals_eager_update(monkeypatch):
         alg, st = r.alg, r.alg.storage
         assert (r._update_graph is not None) == (mode == "1") and r._graph is not None
         assert alg._perm_draws == 7 and int(alg._perm_draws_dev) == 7
-        assert int(alg.net.opt_state[1]) == 7 * alg.num_learning_epochs * alg.num_mini_batches
+        assert int(alg.net.opt_state[L.OPT_STEP]) == 7 * alg.num_learning_epochs * alg.num_mini_batches
         opt = alg.net.opt_state.clone()
         # [9], the squared gradient norm, arrives through fp64 atomics in any order: reduce_slabs_kernel rounds the partials to a common
         # quantum, which makes the sum exact -- the same bits in every run -- while it is below 128 (the kernel's comment); beyond, its last
         # bits may differ under EITHER launch mechanism and only the norm it rounds to ([6]) is compared
-        if float(opt[9]) >= 128.0:
-            opt[9] = 0.0
+        if float(opt[L.OPT_GRAD_SQNORM]) >= 128.0:
+            opt[L.OPT_GRAD_SQNORM] = 0.0
         outs[mode] = (alg.net.params.clone(), alg.net.adam_m.clone(), alg.net.adam_v.clone(), opt, st._perm.clone(),
                       st._obs_all.clone(), st.returns.clone(), st.advantages.clone(), alg._sample_step.clone())
         del r
@@ -293,7 +294,7 @@ def test_fused_rollout_step_equals_act_then_step(monkeypatch, graph):
         np.random.seed(4321)
         r = _runner(512, 31)
         r.env.episode_length_buf = (torch.arange(512, device="cuda") * 37) % 2400       # time-outs, command resampling inside the window
-        r.env._buf.counters[0] = 390                                                   # a push (every 400 steps) too
+        r.env._buf.counters[L.CNT_STEP] = 390                                                   # a push (every 400 steps) too
         n_iter = 3 if graph == "1" else 2
         r.learn(num_learning_iterations=n_iter, init_at_random_ep_len=False)
         torch.cuda.synchronize()
@@ -336,7 +337,7 @@ def test_single_launch_env_step_equals_componentwise_calls(use_ref_actions):
         L.check(L.lib.hgym_env_prime(C.byref(cfg), C.byref(b.sim_struct()), C.byref(b.state_struct()), C.byref(b.out_struct()),
                                      C.byref(b.noise_struct()), s))
         b.episode_length.copy_((torch.arange(N) * 7 % 2400).cuda())
-        b.counters[0] = 395                          # a push (every 400 steps) falls inside the window
+        b.counters[L.CNT_STEP] = 395                          # a push (every 400 steps) falls inside the window
         bufs.append((cfg, b))
     g = torch.Generator().manual_seed(3)
     for t in range(25):
@@ -500,13 +501,13 @@ def test_update_from_the_bf16_shadow_equals_update_from_fp32_rows(S, B):
     torch.cuda.synchronize()
     want, want_opt = net.grads_ext.clone(), net.opt_state.clone()
     net.grads_ext.zero_()
-    net.opt_state[2:10] = 0.0
+    net.opt_state[L.OPT_KL_SUM:L.OPT_GRAD_SQNORM + 1] = 0.0
     net.ppo_grad(make_ppo_config(), make_batch(*cols, obs_bf16=so, priv_bf16=sp))
     torch.cuda.synchronize()
     assert torch.equal(net.grads_ext, want)
-    assert torch.equal(net.opt_state[2:9], want_opt[2:9])          # loss sums, KL, counters
+    assert torch.equal(net.opt_state[L.OPT_KL_SUM:L.OPT_GRAD_SQNORM], want_opt[2:9])          # loss sums, KL, counters
     # the squared gradient norm is accumulated with fp64 atomics across workgroups: order-dependent in the last bits
-    np.testing.assert_allclose(float(net.opt_state[9]), float(want_opt[9]), rtol=1e-12)
+    np.testing.assert_allclose(float(net.opt_state[L.OPT_GRAD_SQNORM]), float(want_opt[9]), rtol=1e-12)
     # ... and in two halves (the data-parallel update's buckets)
     net.grads_ext.zero_()
     for part in (0, 1):
@@ -581,7 +582,7 @@ def test_deferred_values_rollout_equals_inline_rollout(monkeypatch):
         r.learn(num_learning_iterations=3, init_at_random_ep_len=True)
         torch.cuda.synchronize()
         assert r._graph is not None and torch.isfinite(r.alg.net.params).all() and not torch.equal(r.alg.net.params, p0)
-        assert int(r.alg.net.opt_state[1]) == 24 and float(r.alg.storage.values.abs().max()) > 0
+        assert int(r.alg.net.opt_state[L.OPT_STEP]) == 24 and float(r.alg.storage.values.abs().max()) > 0
         outs[mode] = snap
         del r
     a, b = outs["inline"], outs["deferred"]

@@ -14,6 +14,7 @@ import torch
 
 import bf16_report as BR
 from oracle import ppo_oracle as P
+from hgym import _lib as L
 
 pytestmark = pytest.mark.gpu
 
@@ -147,14 +148,14 @@ def test_gradient_apply_and_shadows(row, n_obs, n_priv, S, B):
     BR.check("%s gradient %s, %d / %d inputs, S = %d, B = %d vs bf16-operand oracle (worst tensor)" % (
         "fused" if fused else "generic", row, n_obs, n_priv, S, B), max(errs.values()), tol)
     opt = net.opt_state.cpu()
-    np.testing.assert_allclose(float(opt[8]), float(want["kl"]), rtol=2e-2, atol=1e-4)
-    np.testing.assert_allclose(float(opt[4]) / 2, float(want["value_loss"]), rtol=1e-2)
+    np.testing.assert_allclose(float(opt[L.OPT_KL_LAST]), float(want["kl"]), rtol=2e-2, atol=1e-4)
+    np.testing.assert_allclose(float(opt[L.OPT_VALUE_SUM]) / 2, float(want["value_loss"]), rtol=1e-2)
 
     # (2) Adam on a known gradient
     g0 = net.grads.clone()
-    assert float(net.opt_state[1]) == 0.0
+    assert float(net.opt_state[L.OPT_STEP]) == 0.0
     ppo = make_ppo_config(max_grad_norm=1.0, adaptive=False)
-    lr = float(net.opt_state[0])
+    lr = float(net.opt_state[L.OPT_LR])
     ref_p = P.Params([(W.clone(), b.clone()) for W, b in p.actor], [(W.clone(), b.clone()) for W, b in p.critic], p.std.clone())
     adam = P.Adam(ref_p)
     for step, norm in enumerate((3.0, 0.5)):
@@ -166,8 +167,8 @@ def test_gradient_apply_and_shadows(row, n_obs, n_priv, S, B):
         rg = P.Params([(gs[1 + 2 * i], gs[2 + 2 * i]) for i in range(4)], [(gs[9 + 2 * i], gs[10 + 2 * i]) for i in range(4)], gs[0])
         total = float(P.clip_grad_norm(rg, 1.0))
         adam.step(ref_p, rg, lr)
-        assert float(net.opt_state[1]) == step + 1 and float(net.opt_state[0]) == lr
-        np.testing.assert_allclose(float(net.opt_state[6]), total, rtol=1e-5)
+        assert float(net.opt_state[L.OPT_STEP]) == step + 1 and float(net.opt_state[L.OPT_LR]) == lr
+        np.testing.assert_allclose(float(net.opt_state[L.OPT_GRAD_NORM]), total, rtol=1e-5)
         err = max(float((v.cpu() - r).abs().max()) for v, r in zip(net.views.values(), ref_p.tensors())) / lr
         BR.check("apply (fp32) %s, S = %d, B = %d, step %d (gradient norm %.1f): max |param - oracle| / lr" % (row, S, B, step, norm),
                  err, APPLY_TOL)
@@ -199,12 +200,12 @@ def test_update_from_the_bf16_shadow_equals_update_from_fp32_rows(row, n_obs, n_
     torch.cuda.synchronize()
     want, want_opt = net.grads_ext.clone(), net.opt_state.clone()
     net.grads_ext.zero_()
-    net.opt_state[2:10] = 0.0
+    net.opt_state[L.OPT_KL_SUM:L.OPT_GRAD_SQNORM + 1] = 0.0
     net.ppo_grad(make_ppo_config(), make_batch(*cols, idx, obs_bf16=so, priv_bf16=sp))
     torch.cuda.synchronize()
     assert torch.equal(net.grads_ext, want)
-    assert torch.equal(net.opt_state[2:9], want_opt[2:9])
-    np.testing.assert_allclose(float(net.opt_state[9]), float(want_opt[9]), rtol=1e-12)
+    assert torch.equal(net.opt_state[L.OPT_KL_SUM:L.OPT_GRAD_SQNORM], want_opt[2:9])
+    np.testing.assert_allclose(float(net.opt_state[L.OPT_GRAD_SQNORM]), float(want_opt[9]), rtol=1e-12)
 
 
 # ------------------------------------------------------------------------------------------------ auxiliary (denoising) head
@@ -250,7 +251,7 @@ def test_aux_head_gradient_vs_oracle(case, monkeypatch):
         hg = P.mlp_backward(2.0 * coef * (y - t) / (B * out), hd, acts, pres, quant=_q64)
     keep = [c.cuda().contiguous() for c in cols] + [idx.cuda()]
     for _ in range(2):                  # twice: nothing may carry over from the first call
-        net.opt_state[10] = 0.0
+        net.opt_state[L.OPT_AUX_SUM] = 0.0
         net.ppo_grad(make_ppo_config(aux_coef=coef), make_batch(*keep))
     torch.cuda.synchronize()
     gv = net.grad_views()
@@ -262,7 +263,7 @@ def test_aux_head_gradient_vs_oracle(case, monkeypatch):
         for nm, r in (("weight", gw), ("bias", gb)):
             errs[(l, nm)] = _rel_l2(gv["denoiser.%d.%s" % (2 * l, nm)].cpu(), r)
     BR.check("denoiser %s -> %d (%s) gradient vs bf16-operand oracle (worst tensor)" % (hidden, out, case), max(errs.values()), tol)
-    np.testing.assert_allclose(float(net.opt_state[10]), mse, rtol=1e-2)
+    np.testing.assert_allclose(float(net.opt_state[L.OPT_AUX_SUM]), mse, rtol=1e-2)
 
 
 # ------------------------------------------------------------------------------------------------ end to end
@@ -306,11 +307,11 @@ def test_runner_trains_at_other_widths_and_captured_update_equals_eager(actor_hi
         torch.cuda.synchronize()
         assert (alg.storage._obs_bf16 is not None) == fused
         assert (r._update_graph is not None) == (mode == "1")
-        assert int(alg.net.opt_state[1]) == 2 * alg.num_learning_epochs * alg.num_mini_batches
+        assert int(alg.net.opt_state[L.OPT_STEP]) == 2 * alg.num_learning_epochs * alg.num_mini_batches
         opt = alg.net.opt_state.clone()
-        assert torch.isfinite(opt[:9]).all() and torch.isfinite(alg.net.params).all()
-        if float(opt[9]) >= 128.0:      # fp64 atomics beyond their exact range (tests/test_fused_gpu.py)
-            opt[9] = 0.0
+        assert torch.isfinite(opt[:L.OPT_GRAD_SQNORM]).all() and torch.isfinite(alg.net.params).all()
+        if float(opt[L.OPT_GRAD_SQNORM]) >= 128.0:      # fp64 atomics beyond their exact range (tests/test_fused_gpu.py)
+            opt[L.OPT_GRAD_SQNORM] = 0.0
         outs[mode] = (alg.net.params.clone(), alg.net.adam_m.clone(), alg.net.adam_v.clone(), opt)
         del r
     for nm, a, b in zip(("params", "adam_m", "adam_v", "opt_state"), outs["1"], outs["0"]):

@@ -11,6 +11,7 @@ import bf16_report as BR
 import layer_path_common as LP
 from oracle import ppo_oracle as P
 from oracle import xbot_constants as K
+from hgym import _lib as L
 
 pytestmark = pytest.mark.gpu
 
@@ -144,9 +145,9 @@ def _check_grad(name, precision, B, net, grads_ref, want, opt0, what):
     BR.check("%s (worst tensor: %s)" % (what, worst), errs[worst], bar)
     opt = net.opt_state.cpu()
     rtol, atol = (1e-4, 1e-6) if precision == "f32" else (1e-2, 1e-4)
-    np.testing.assert_allclose(float(opt[8]), float(want["kl"]), rtol=rtol, atol=atol)
-    np.testing.assert_allclose(float(opt[4] - opt0[4]), float(want["value_loss"]), rtol=rtol, atol=atol)
-    np.testing.assert_allclose(float(opt[3] - opt0[3]), float(want["surrogate"]), rtol=rtol, atol=atol)
+    np.testing.assert_allclose(float(opt[L.OPT_KL_LAST]), float(want["kl"]), rtol=rtol, atol=atol)
+    np.testing.assert_allclose(float(opt[L.OPT_VALUE_SUM] - opt0[4]), float(want["value_loss"]), rtol=rtol, atol=atol)
+    np.testing.assert_allclose(float(opt[L.OPT_SURROGATE_SUM] - opt0[3]), float(want["surrogate"]), rtol=rtol, atol=atol)
 
 
 @pytest.mark.parametrize("precision", PRECISIONS)
@@ -389,11 +390,11 @@ def test_runner_trains_the_deep_case_and_captured_update_equals_eager(precision,
         r.learn(num_learning_iterations=2, init_at_random_ep_len=False)
         torch.cuda.synchronize()
         assert (r._update_graph is not None) == (mode == "1")
-        assert int(alg.net.opt_state[1]) == 2 * alg.num_learning_epochs * alg.num_mini_batches
+        assert int(alg.net.opt_state[L.OPT_STEP]) == 2 * alg.num_learning_epochs * alg.num_mini_batches
         opt = alg.net.opt_state.clone()
-        assert torch.isfinite(opt[:9]).all() and torch.isfinite(alg.net.params).all()
-        if float(opt[9]) >= 128.0:      # fp64 atomics beyond their exact range (tests/test_fused_gpu.py)
-            opt[9] = 0.0
+        assert torch.isfinite(opt[:L.OPT_GRAD_SQNORM]).all() and torch.isfinite(alg.net.params).all()
+        if float(opt[L.OPT_GRAD_SQNORM]) >= 128.0:      # fp64 atomics beyond their exact range (tests/test_fused_gpu.py)
+            opt[L.OPT_GRAD_SQNORM] = 0.0
         outs[mode] = (alg.net.params.clone(), alg.net.adam_m.clone(), alg.net.adam_v.clone(), opt)
         del r
     for nm, a, b in zip(("params", "adam_m", "adam_v", "opt_state"), outs["1"], outs["0"]):

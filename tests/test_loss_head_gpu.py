@@ -23,6 +23,7 @@ import torch
 
 import bf16_report as BR
 import loss_head_common as H
+from hgym import _lib as L
 
 pytestmark = pytest.mark.gpu
 
@@ -66,7 +67,7 @@ def _run(net, case, shape, clipped, shadow):
             kw[key] = s.cuda().contiguous()
     batch = make_batch(*cols, idx, **kw)
     ppo = make_ppo_config(clip_param=0.2, value_loss_coef=1.0, entropy_coef=0.001, clipped_value_loss=clipped)
-    net.opt_state[2:10] = 0.0
+    net.opt_state[L.OPT_KL_SUM:L.OPT_GRAD_SQNORM + 1] = 0.0
     net.grads_ext.fill_(float("nan"))
     net.ppo_grad(ppo, batch)
     torch.cuda.synchronize()
@@ -112,10 +113,10 @@ def _check(tag, case, fused, bf16, g, opt, ref, un, fails, worst):
         sums = (("actor.6.bias", g["actor.6.bias"], ref["g_mu"], un["g_mu"], stored, 0.0),
                 ("critic.6.bias", g["critic.6.bias"][0], ref["d_v"], un["d_v"], stored, 0.0),
                 ("std", g["std"], ref["g_sigma"], un["g_sigma"], False, 0.0),
-                ("opt_state[3] surrogate", opt[3] * B, ref["surr"], un["surr"], False, 0.0),
-                ("opt_state[4] value loss", opt[4] * B, ref["vl"], un["vl"], False, 0.0),
-                ("opt_state[5] entropy", opt[5] * B, ref["ent"], un["ent"], False, 0.0),
-                ("opt_state[8] KL", opt[8] * B, ref["kl"], un["kl"], False, H.U24 * float(kl_sum.abs())))     # stored as a float
+                ("opt_state[OPT_SURROGATE_SUM] surrogate", opt[L.OPT_SURROGATE_SUM] * B, ref["surr"], un["surr"], False, 0.0),
+                ("opt_state[OPT_VALUE_SUM] value loss", opt[L.OPT_VALUE_SUM] * B, ref["vl"], un["vl"], False, 0.0),
+                ("opt_state[OPT_ENTROPY_SUM] entropy", opt[L.OPT_ENTROPY_SUM] * B, ref["ent"], un["ent"], False, 0.0),
+                ("opt_state[OPT_KL_LAST] KL", opt[L.OPT_KL_LAST] * B, ref["kl"], un["kl"], False, H.U24 * float(kl_sum.abs())))     # stored as a float
         for name, got, terms, unit, st, extra in sums:
             want = terms.sum(0)
             bar = H.sum_bar(unit, terms, FACTOR, st) + extra

@@ -12,6 +12,7 @@ import torch
 import bf16_report as BR
 from oracle import ppo_oracle as P
 from oracle import xbot_constants as K
+from hgym import _lib as L
 
 pytestmark = pytest.mark.gpu
 T = lambda a: torch.from_numpy(np.asarray(a))
@@ -165,7 +166,7 @@ def _run_iteration(G, precision):
             net.ppo_grad(ppo, b)
             net.ppo_apply(ppo)
             torch.cuda.synchronize()
-            lrs.append(float(net.opt_state[0]))
+            lrs.append(float(net.opt_state[L.OPT_LR]))
             if g0 is None:
                 g0 = {k: v.clone().cpu() for k, v in net.grad_views().items()}
     res.update(lrs=lrs, g0=g0, opt=net.opt_state.cpu().clone())
@@ -204,9 +205,9 @@ def _check_iteration_f32(G):
         ref = G["pF_" + k.replace(".", "_")]
         np.testing.assert_allclose(r["net"].views[k].cpu().numpy(), ref, rtol=2e-4, atol=5e-6, err_msg=k)
     opt = r["opt"]
-    np.testing.assert_allclose(float(opt[4] / opt[7]), float(G["mean_value_loss"]), rtol=1e-4)
-    np.testing.assert_allclose(float(opt[3] / opt[7]), float(G["mean_surrogate_loss"]), rtol=1e-3, atol=1e-6)
-    assert int(opt[1]) == 8 and int(opt[7]) == 8
+    np.testing.assert_allclose(float(opt[L.OPT_VALUE_SUM] / opt[L.OPT_MINIBATCHES]), float(G["mean_value_loss"]), rtol=1e-4)
+    np.testing.assert_allclose(float(opt[L.OPT_SURROGATE_SUM] / opt[L.OPT_MINIBATCHES]), float(G["mean_surrogate_loss"]), rtol=1e-3, atol=1e-6)
+    assert int(opt[L.OPT_STEP]) == 8 and int(opt[L.OPT_MINIBATCHES]) == 8
 
 
 def test_ppo_iteration_bf16_close_to_reference(golden_dir):
@@ -250,9 +251,9 @@ def test_grad_vs_oracle_full_width():
     for k, ref in zip(NAMES, out["grads"].tensors()):
         assert _rel_err(gv[k].cpu().numpy(), ref.numpy()) <= 5e-5, (k, _rel_err(gv[k].cpu().numpy(), ref.numpy()))
     opt = net.opt_state.cpu()
-    np.testing.assert_allclose(float(opt[8]), float(out["kl"]), rtol=1e-4)
-    np.testing.assert_allclose(float(opt[4]), float(out["value_loss"]), rtol=1e-4)
-    np.testing.assert_allclose(float(opt[3]), float(out["surrogate"]), rtol=1e-4, atol=1e-6)
+    np.testing.assert_allclose(float(opt[L.OPT_KL_LAST]), float(out["kl"]), rtol=1e-4)
+    np.testing.assert_allclose(float(opt[L.OPT_VALUE_SUM]), float(out["value_loss"]), rtol=1e-4)
+    np.testing.assert_allclose(float(opt[L.OPT_SURROGATE_SUM]), float(out["surrogate"]), rtol=1e-4, atol=1e-6)
 
 
 FULL_SIZE_BF16_TOL = 5e-3      # fused kernels vs the bf16-operand oracle per tensor, rel-L2: the bound tests/test_fused_gpu.py holds at B = 4096
@@ -304,9 +305,9 @@ def test_update_full_size_vs_oracle():
             worst = max(worst, l2)
             assert l2 <= tol, (prec, k, l2)
         opt = net.opt_state.cpu()
-        np.testing.assert_allclose(float(opt[8]), float(ref["kl"]), rtol=1e-3, atol=1e-5)
-        np.testing.assert_allclose(float(opt[4]), float(ref["value_loss"]), rtol=1e-3)
-        np.testing.assert_allclose(float(opt[3]), float(ref["surrogate"]), rtol=1e-3, atol=1e-5)
+        np.testing.assert_allclose(float(opt[L.OPT_KL_LAST]), float(ref["kl"]), rtol=1e-3, atol=1e-5)
+        np.testing.assert_allclose(float(opt[L.OPT_VALUE_SUM]), float(ref["value_loss"]), rtol=1e-3)
+        np.testing.assert_allclose(float(opt[L.OPT_SURROGATE_SUM]), float(ref["surrogate"]), rtol=1e-3, atol=1e-5)
         rep.append("%s path vs %s oracle at B = %d: worst per-tensor rel-L2 %.3e (bound %.0e)" % (prec, "bf16-operand" if prec == "bf16" else "fp32", B, worst, tol))
         before = net.params.clone()
         net.ppo_apply(make_ppo_config())
@@ -335,14 +336,14 @@ def test_apply_with_world_size_forms_the_rank_mean_itself(precision):
         g = torch.randn(net.P, device="cuda") * 3.0            # norm >> max_grad_norm: the clip is active
         net.grads.copy_(g * w)
         net.grads_ext[net.P] = 0.004 * w                        # mean KL 0.004 < desired_kl / 2 -> lr x 1.5
-        net.opt_state[8] = 123.0 if w > 1 else 0.004            # multi-rank: the local double is NOT what decides
+        net.opt_state[L.OPT_KL_LAST] = 123.0 if w > 1 else 0.004            # multi-rank: the local double is NOT what decides
         net.ppo_apply(make_ppo_config(world_size=w))
         torch.cuda.synchronize()
         nets.append(net)
     a, b = nets
     assert torch.equal(a.params, b.params) and torch.equal(a.adam_m, b.adam_m) and torch.equal(a.adam_v, b.adam_v)
-    assert float(a.opt_state[0]) == float(b.opt_state[0]) == pytest.approx(1.5e-3)
-    assert float(a.opt_state[6]) == float(b.opt_state[6])       # same pre-clip gradient norm
+    assert float(a.opt_state[L.OPT_LR]) == float(b.opt_state[L.OPT_LR]) == pytest.approx(1.5e-3)
+    assert float(a.opt_state[L.OPT_GRAD_NORM]) == float(b.opt_state[L.OPT_GRAD_NORM])       # same pre-clip gradient norm
     assert torch.equal(a.workspace, b.workspace)                # bf16 operand shadows follow
 
 
@@ -373,8 +374,8 @@ def test_apply_can_reuse_the_norm_left_by_grad(precision):
         torch.cuda.synchronize()
         nets.append(net)
     a, b = nets
-    assert float(a.opt_state[6]) > 1.0                         # the clip really acted (advantages x30)
-    np.testing.assert_allclose(float(b.opt_state[6]), float(a.opt_state[6]), rtol=1e-6)
+    assert float(a.opt_state[L.OPT_GRAD_NORM]) > 1.0                         # the clip really acted (advantages x30)
+    np.testing.assert_allclose(float(b.opt_state[L.OPT_GRAD_NORM]), float(a.opt_state[L.OPT_GRAD_NORM]), rtol=1e-6)
     np.testing.assert_allclose(b.params.cpu().numpy(), a.params.cpu().numpy(), rtol=1e-7, atol=1e-9)
 
 
@@ -407,13 +408,13 @@ def test_prologue_marker_keeps_grad_and_apply_in_step():
             net.ppo_apply(plain if mode == "apply without the flag" else ready)
         torch.cuda.synchronize()
         res[mode] = (net.params.clone(), net.opt_state.clone())
-    lr0, steps0 = float(res["normal"][1][0]), float(res["normal"][1][1])
+    lr0, steps0 = float(res["normal"][1][L.OPT_LR]), float(res["normal"][1][L.OPT_STEP])
     assert steps0 == 2.0 and lr0 != 1e-3
     for mode in ("grad twice", "apply without the flag"):
         o = res[mode][1]
-        assert float(o[1]) == 2.0 and float(o[0]) == lr0, (mode, o)
+        assert float(o[L.OPT_STEP]) == 2.0 and float(o[L.OPT_LR]) == lr0, (mode, o)
         np.testing.assert_allclose(res[mode][0].cpu().numpy(), res["normal"][0].cpu().numpy(), rtol=1e-6, atol=1e-8, err_msg=mode)
-    assert float(res["normal"][1][13]) == -1.0                  # applied: nothing pending
+    assert float(res["normal"][1][L.OPT_PROLOGUE_STEP]) == -1.0                  # applied: nothing pending
 
 
 @pytest.mark.parametrize("precision", ["f32", "bf16"])
@@ -508,8 +509,8 @@ def test_ppo_iteration_full_width_matches_reference_f32():
         assert d["sample_max_err"] <= 2e-2 and d["rel_l2"] <= 1e-3 and abs(d["norm_ratio"] - 1) <= 2e-3, (name, d)
     print("\n".join(rep))
     opt = r["opt"]
-    np.testing.assert_allclose(float(opt[4] / opt[7]), float(G["mean_value_loss"]), rtol=1e-4)
-    np.testing.assert_allclose(float(opt[3] / opt[7]), float(G["mean_surrogate_loss"]), rtol=1e-3, atol=1e-6)
+    np.testing.assert_allclose(float(opt[L.OPT_VALUE_SUM] / opt[L.OPT_MINIBATCHES]), float(G["mean_value_loss"]), rtol=1e-4)
+    np.testing.assert_allclose(float(opt[L.OPT_SURROGATE_SUM] / opt[L.OPT_MINIBATCHES]), float(G["mean_surrogate_loss"]), rtol=1e-3, atol=1e-6)
 
 
 # per-tensor tolerance of the bf16 FUSED path against the reference's fp32 autograd, first-minibatch clipped gradient (measured:
@@ -583,14 +584,14 @@ def test_norm_pass_of_apply_is_one_launch_and_reproducible():
         net.ppo_apply(make_ppo_config(world_size=4))
         torch.cuda.synchronize()
         want = float((g.double() * float(np.float32(0.25))).pow(2).sum().sqrt())
-        assert abs(float(net.opt_state[6]) - float(np.float32(want))) <= 1e-6 * want       # opt[6] = the fp32 norm the clip used
-        assert abs(float(net.opt_state[9]) - want * want) <= 1e-12 * want * want
+        assert abs(float(net.opt_state[L.OPT_GRAD_NORM]) - float(np.float32(want))) <= 1e-6 * want       # opt[6] = the fp32 norm the clip used
+        assert abs(float(net.opt_state[L.OPT_GRAD_SQNORM]) - want * want) <= 1e-12 * want * want
         outs.append((net.opt_state.clone(), net.params.clone(), net.adam_v.clone()))
         if rep == 0:                                  # a second step on the same net: the counter was reset
             net.grads.copy_(g)
             net.grads_ext[net.P] = 0.02
             net.ppo_apply(make_ppo_config(world_size=4))
             torch.cuda.synchronize()
-            assert int(net.opt_state[1]) == 2 and torch.isfinite(net.params).all()
+            assert int(net.opt_state[L.OPT_STEP]) == 2 and torch.isfinite(net.params).all()
     for o in outs[1:]:
         assert torch.equal(o[0], outs[0][0]) and torch.equal(o[1], outs[0][1]) and torch.equal(o[2], outs[0][2])

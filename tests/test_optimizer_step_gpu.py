@@ -19,6 +19,7 @@ import torch
 import bf16_report as BR
 import layer_path_common as LP
 from oracle import ppo_oracle as P
+from hgym import _lib as L
 
 pytestmark = pytest.mark.gpu
 
@@ -153,26 +154,26 @@ def test_grad_norm_and_step_in_every_regime(kind, regime):
     torch.cuda.synchronize()
     G = net.grads.double().cpu().numpy()
     sq64 = math.fsum(G * G)
-    opt9 = float(net.opt_state[9])
+    opt9 = float(net.opt_state[L.OPT_GRAD_SQNORM])
     nwg = _nwg(net)
     bound9 = nwg * 2.0 ** -47 + (nwg + 128) * 2.0 ** -53 * sq64
     what = "%s %s (|g| = %.3g)" % (kind, regime, math.sqrt(sq64))
-    BR.check("opt[9] %s: |opt[9] - float64 sum| / derived bound" % what, abs(opt9 - sq64) / bound9, 1.0)
+    BR.check("opt[OPT_GRAD_SQNORM] %s: |opt[OPT_GRAD_SQNORM] - float64 sum| / derived bound" % what, abs(opt9 - sq64) / bound9, 1.0)
     if regime == "large":
         assert sq64 > 1e4
     elif regime == "tiny":
         assert sq64 < 1e-12 and abs(opt9 - sq64) <= nwg * 2.0 ** -47
     net.ppo_apply(ppo)
     torch.cuda.synchronize()
-    assert float(net.opt_state[6]) == float(np.float32(math.sqrt(opt9)))
-    assert f32_ulps(float(net.opt_state[6]), math.sqrt(sq64)) <= 1.0 or sq64 < 1e-12
+    assert float(net.opt_state[L.OPT_GRAD_NORM]) == float(np.float32(math.sqrt(opt9)))
+    assert f32_ulps(float(net.opt_state[L.OPT_GRAD_NORM]), math.sqrt(sq64)) <= 1.0 or sq64 < 1e-12
     worst, coef = _check_step(before, _state(net), G, sq64, 1, 1e-3, ppo, what)
     BR.check("clip + Adam %s: worst err / derived bound" % what, worst, 1.0)
     if regime == "unit_clipped" or regime == "large":
         assert coef < 0.99
     else:
         assert coef == 1.0                            # tiny: the unclipped step (total ~ 0, coef = max_norm / 1e-6 clamped)
-    assert math.isclose(float(net.opt_state[11]), 1e-3 / (1 - float(np.float32(0.9))), rel_tol=U)
+    assert math.isclose(float(net.opt_state[L.OPT_STEP_SIZE]), 1e-3 / (1 - float(np.float32(0.9))), rel_tol=U)
 
 
 # ---------------------------------------------------------------------------------------------- 2. a long trajectory of hgym_ppo_apply
@@ -227,7 +228,7 @@ def test_apply_trajectory(kind, world):
         G = pool[k % 3] * norms[k]
         if world == 1:
             net.grads.copy_(G)
-            net.opt_state[8] = kls[k]
+            net.opt_state[L.OPT_KL_LAST] = kls[k]
         else:
             net.grads.copy_(G * world)                               # x2, x0.5: exact
             net.grads_ext[net.P] = float(np.float32(kls[k])) * world
@@ -242,11 +243,11 @@ def test_apply_trajectory(kind, world):
         seen["lo"] += lr == LR_MIN
         opt = net.opt_state.cpu()
         what = "%s world=%d step %d kl=%r" % (kind, world, t, kls[k])
-        assert float(opt[0]) == lr, "%s: lr %r, reference %r" % (what, float(opt[0]), lr)
-        assert float(opt[1]) == t
+        assert float(opt[L.OPT_LR]) == lr, "%s: lr %r, reference %r" % (what, float(opt[L.OPT_LR]), lr)
+        assert float(opt[L.OPT_STEP]) == t
         b1, b2 = float(np.float32(ppo.beta1)), float(np.float32(ppo.beta2))
-        assert f32_ulps(float(opt[11]), lr / (1 - b1 ** t)) <= 1.0, what
-        assert f32_ulps(float(opt[12]), math.sqrt(1 - b2 ** t)) <= 1.0, what
+        assert f32_ulps(float(opt[L.OPT_STEP_SIZE]), lr / (1 - b1 ** t)) <= 1.0, what
+        assert f32_ulps(float(opt[L.OPT_SQRT_BC2]), math.sqrt(1 - b2 ** t)) <= 1.0, what
         if sampled:
             sq64 = math.fsum(G64 * G64)
             r, _ = _check_step(before, _state(net), G64, sq64, t, lr, ppo, what)
@@ -278,10 +279,10 @@ def test_apply_5000_steps_bias_corrections():
         net.ppo_apply(ppo)
         if t in samples:
             opt = net.opt_state.cpu()
-            assert float(opt[1]) == t and float(opt[0]) == lr
+            assert float(opt[L.OPT_STEP]) == t and float(opt[L.OPT_LR]) == lr
             b1, b2 = float(np.float32(ppo.beta1)), float(np.float32(ppo.beta2))
-            assert f32_ulps(float(opt[11]), lr / (1 - b1 ** t)) <= 1.0, t
-            assert f32_ulps(float(opt[12]), math.sqrt(1 - b2 ** t)) <= 1.0, t
+            assert f32_ulps(float(opt[L.OPT_STEP_SIZE]), lr / (1 - b1 ** t)) <= 1.0, t
+            assert f32_ulps(float(opt[L.OPT_SQRT_BC2]), math.sqrt(1 - b2 ** t)) <= 1.0, t
             r, _ = _check_step(before, _state(net), G64, math.fsum(G64 * G64), t, lr, ppo, "thin t=%d" % t)
             worst = max(worst, r)
     BR.check("apply 5000 steps thin-f32: worst err / derived bound", worst, 1.0)
@@ -313,13 +314,13 @@ def test_boundary_kl_in_the_gradient_and_the_apply_prologue(side):
     net.ppo_apply(ppo)
     torch.cuda.synchronize()
     assert np.float32(float(net.grads_ext[net.P])) == kl32          # the same minibatch, the same KL
-    results["gradient prologue"] = float(net.opt_state[0])
+    results["gradient prologue"] = float(net.opt_state[L.OPT_LR])
     for q in (-0.25, 0.25):
         _, net, _, _ = _net("fused", B, 61, lr)
         ppo = make_ppo_config(desired_kl=desired, grad_norm_ready=False)
         net.ppo_grad(ppo, batch)
-        net.opt_state[8] = float(kl32) + q * float(np.spacing(kl32))
+        net.opt_state[L.OPT_KL_LAST] = float(kl32) + q * float(np.spacing(kl32))
         net.ppo_apply(ppo)
         torch.cuda.synchronize()
-        results["apply prologue, kl32 %+.2f ulp" % q] = float(net.opt_state[0])
+        results["apply prologue, kl32 %+.2f ulp" % q] = float(net.opt_state[L.OPT_LR])
     assert all(v == lr for v in results.values()), results

@@ -13,6 +13,7 @@ import torch
 import env_common as EC
 import reset_idx_common as RC
 from oracle import xbot_constants as K
+from hgym import _lib as L
 
 pytestmark = pytest.mark.gpu
 
@@ -58,7 +59,7 @@ def test_random_subsets_against_oracle_gpu(hip, N):
         tag = "N=%d, %d envs" % (N, k)
         RC.check_untouched(env.buf, before, m, tag)
         RC.compare_reset(env, o, m, tag)
-        assert int(env.buf.reset_idx_rejected) == 0 and int(env.buf.counters[1]) == 0
+        assert int(env.buf.reset_idx_rejected) == 0 and int(env.buf.counters[L.CNT_RESETS]) == 0
         _step_both(env, o, g, tag=tag + ": the step after")
 
 

@@ -5,6 +5,7 @@ import os
 import numpy as np
 import pytest
 import torch
+from hgym import _lib as L
 
 pytestmark = pytest.mark.gpu
 
@@ -56,7 +57,7 @@ def test_training_iterations_and_checkpoint(tmp_path):
     torch.cuda.synchronize()
     net = runner.alg.net
     assert torch.isfinite(net.params).all() and not torch.equal(p0, net.params)
-    assert int(net.opt_state[1]) == 3 * 8                       # 2 epochs x 4 minibatches per iteration
+    assert int(net.opt_state[L.OPT_STEP]) == 3 * 8                       # 2 epochs x 4 minibatches per iteration
     assert 1e-5 <= runner.alg.learning_rate <= 1e-2
     st = runner.alg.storage
     assert torch.isfinite(st.returns).all() and torch.isfinite(st.advantages).all()
@@ -78,9 +79,9 @@ def test_training_iterations_and_checkpoint(tmp_path):
     # permutation draw and the env's common step counter (the Philox counter word of commands / pushes / noise / reset draws)
     T = r2.num_steps_per_env
     assert int(r2.alg._sample_step) == 3 * T and r2.alg._perm_draws == 3
-    assert int(env2._buf.counters[0]) == int(runner.env._buf.counters[0]) == 1 + 3 * T
+    assert int(env2._buf.counters[L.CNT_STEP]) == int(runner.env._buf.counters[L.CNT_STEP]) == 1 + 3 * T
     r2.load(os.path.join(runner.log_dir, "model_3.pt"))        # idempotent
-    assert int(env2._buf.counters[0]) == 1 + 3 * T
+    assert int(env2._buf.counters[L.CNT_STEP]) == 1 + 3 * T
     x = torch.randn(64, 705, device="cuda")
     a1 = runner.alg.actor_critic.act_inference(x)
     a2 = r2.alg.actor_critic.act_inference(x)
@@ -294,7 +295,7 @@ def test_other_frame_stacks_and_a_ragged_env_count_train(precision, tmp_path):
         st = runner.alg.storage
         assert tuple(st.observations.shape) == (24, 100, 188) and tuple(st.privileged_observations.shape) == (24, 100, 146)
         net = runner.alg.net
-        assert torch.isfinite(net.params).all() and int(net.opt_state[1]) == 3 * 2 * 2      # 2 epochs x 2 minibatches x 3 iterations
+        assert torch.isfinite(net.params).all() and int(net.opt_state[L.OPT_STEP]) == 3 * 2 * 2      # 2 epochs x 2 minibatches x 3 iterations
         assert torch.isfinite(st.returns).all() and torch.isfinite(st.advantages).all()
         runner.wait_for_saves()
         path = os.path.join(runner.log_dir, "model_3.pt")

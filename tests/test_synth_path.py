@@ -21,6 +21,7 @@ import synth_common as SC
 from oracle import synth_env_oracle as S
 from oracle import xbot_constants as K
 from oracle.xbot_env_oracle import XBotEnvOracle
+from hgym import _lib as L
 
 
 def test_oracle_draw_layout_matches_kernel_source_streams():
@@ -91,7 +92,7 @@ def test_fused_synthetic_step_host_vs_oracle(N, epb, nthreads, split):
         counts["push"] += int(info["pushed"])
     SC.report("kernel source on the host (hc_env_step_ex, fused, split=%d) vs oracle, N=%d, 30 steps: %s" % (split, N, counts), flips[0])
     assert counts["push"] == 1 and counts["timeout"] >= 3 and counts["reset"] > counts["timeout"] - 1
-    assert int(buf.counters[0]) == 397 + 30
+    assert int(buf.counters[L.CNT_STEP]) == 397 + 30
 
 
 # ------------------------------------------------------------------------------------------------ GPU
@@ -198,7 +199,7 @@ def test_rollout_step_env_part_vs_oracle_gpu(monkeypatch, ahead):
     EC.compare_state(SC.Holder(buf), o, "after the rollout", check_obs=False)
     SC.report("fused rollout step (hgym_rollout_step, rows ahead: %s), env part vs oracle, N=%d, %d steps: %s" % (ahead, N, T, counts), flips[0])
     assert counts["push"] == 1 and counts["timeout"] >= 3 and counts["reset"] > counts["timeout"] and counts["boot"] >= 3
-    assert int(buf.counters[0]) == 390 + T and int(alg._sample_step) == T
+    assert int(buf.counters[L.CNT_STEP]) == 390 + T and int(alg._sample_step) == T
 
 
 @pytest.mark.gpu
@@ -278,7 +279,7 @@ def test_two_launch_rollout_8192_envs_vs_oracle_gpu(monkeypatch):
     SC.report("two-launch rollout (policy_act_fin<64-row tiles> + env_step_synth, deferred finaliser), N=8192, %d steps vs oracle: %s"
               % (T, counts), flips[0])
     assert counts["push"] == 1 and counts["timeout"] >= 3 and counts["reset"] > counts["timeout"] and counts["boot"] >= 3
-    assert int(buf.counters[0]) == 392 + T and int(alg._sample_step) == T
+    assert int(buf.counters[L.CNT_STEP]) == 392 + T and int(alg._sample_step) == T
 
 
 @pytest.mark.gpu
@@ -382,4 +383,4 @@ def test_deferred_values_rollout_vs_oracle_gpu(monkeypatch, N):
     SC.report("fused rollout step WITHOUT critic tiles + one critic pass (deferred values), N=%d, %d steps vs oracle: %s; one-pass vs per-step "
               "critic: %.2e" % (N, T, counts, worst), flips[0])
     assert counts["push"] == 1 and counts["timeout"] >= 3 and counts["reset"] > counts["timeout"] and counts["boot"] >= 3
-    assert int(buf.counters[0]) == 394 + T and int(alg._sample_step) == T
+    assert int(buf.counters[L.CNT_STEP]) == 394 + T and int(alg._sample_step) == T

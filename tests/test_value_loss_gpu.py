@@ -175,6 +175,7 @@ def test_one_minibatch_on_every_path(name):
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 sys.path.insert(0, GOLDEN)
 import value_loss_case as V  # noqa: E402
+from hgym import _lib as L
 
 # rel-L2 distance between the unclipped and the clipped fixture's 8-step parameter change, as gen_value_loss_fixtures.py prints it, of
 # the tensors where it is at least 10x the bar the replay is held to (fp32 dP: 1e-3): only those can show which form the replay took
@@ -230,10 +231,10 @@ def test_ppo_iteration_unclipped_matches_reference_f32(monkeypatch):
         pf = r["net"].views[k].cpu().numpy().reshape(-1)
         np.testing.assert_allclose(pf[V.sample_index(k, pf.size, "pF")], U["pF_s32_" + key], rtol=2e-4, atol=5e-6, err_msg=k)
     opt = r["opt"]
-    np.testing.assert_allclose(float(opt[4] / opt[7]), float(U["mean_value_loss"]), rtol=1e-4)
-    np.testing.assert_allclose(float(opt[3] / opt[7]), float(U["mean_surrogate_loss"]), rtol=1e-3, atol=1e-6)
+    np.testing.assert_allclose(float(opt[L.OPT_VALUE_SUM] / opt[L.OPT_MINIBATCHES]), float(U["mean_value_loss"]), rtol=1e-4)
+    np.testing.assert_allclose(float(opt[L.OPT_SURROGATE_SUM] / opt[L.OPT_MINIBATCHES]), float(U["mean_surrogate_loss"]), rtol=1e-3, atol=1e-6)
     # the clipped fixture is out of reach: its mean value loss, and the parameter change of the separated tensors
-    assert abs(float(opt[4] / opt[7]) - float(Cl["mean_value_loss"])) > 10 * 1e-4 * float(Cl["mean_value_loss"])
+    assert abs(float(opt[L.OPT_VALUE_SUM] / opt[L.OPT_MINIBATCHES]) - float(Cl["mean_value_loss"])) > 10 * 1e-4 * float(Cl["mean_value_loss"])
     for k in SEPARATION_SMALL:
         key = k.replace(".", "_")
         pf = r["net"].views[k].cpu().numpy().reshape(-1).astype(np.float64)
@@ -266,14 +267,14 @@ def test_ppo_iteration_full_width_unclipped_f32(monkeypatch):
         assert d["sample_max_err"] <= 2e-2 and d["rel_l2"] <= 1e-3 and abs(d["norm_ratio"] - 1) <= 2e-3, (name, d)
     print("\n".join(rep))
     opt = r["opt"]
-    np.testing.assert_allclose(float(opt[4] / opt[7]), float(U["mean_value_loss"]), rtol=1e-4)
-    np.testing.assert_allclose(float(opt[3] / opt[7]), float(U["mean_surrogate_loss"]), rtol=1e-3, atol=1e-6)
+    np.testing.assert_allclose(float(opt[L.OPT_VALUE_SUM] / opt[L.OPT_MINIBATCHES]), float(U["mean_value_loss"]), rtol=1e-4)
+    np.testing.assert_allclose(float(opt[L.OPT_SURROGATE_SUM] / opt[L.OPT_MINIBATCHES]), float(U["mean_surrogate_loss"]), rtol=1e-3, atol=1e-6)
     # ... and away from the clipped fixture (its full fp16 copy of dP), where the recorded distance allows telling them apart
     Cl = np.load(os.path.join(GOLDEN, "ppo_update_full.npz"))
     cmp_c = F.compare(Cl, "dP", dP)
     for k, d in SEPARATION_FULL.items():
         assert cmp_c[k]["rel_l2"] >= 0.5 * d, (k, cmp_c[k])
-    assert abs(float(opt[4] / opt[7]) - float(Cl["mean_value_loss"])) > 10 * 1e-4 * float(Cl["mean_value_loss"])
+    assert abs(float(opt[L.OPT_VALUE_SUM] / opt[L.OPT_MINIBATCHES]) - float(Cl["mean_value_loss"])) > 10 * 1e-4 * float(Cl["mean_value_loss"])
 
 
 def test_ppo_iteration_full_width_unclipped_bf16_fused(monkeypatch, capsys):
@@ -339,10 +340,10 @@ def test_runner_trains_unclipped_and_captured_update_equals_eager(monkeypatch, t
         torch.cuda.synchronize()
         assert (r._update_graph is not None) == (mode == "1")
         opt = alg.net.opt_state.clone()
-        assert int(opt[1]) == 3 * alg.num_learning_epochs * alg.num_mini_batches
-        mean_value_loss = float(opt[4]) / float(opt[7])          # what the runner logs
+        assert int(opt[L.OPT_STEP]) == 3 * alg.num_learning_epochs * alg.num_mini_batches
+        mean_value_loss = float(opt[L.OPT_VALUE_SUM]) / float(opt[L.OPT_MINIBATCHES])          # what the runner logs
         assert np.isfinite(mean_value_loss) and mean_value_loss > 0
-        assert torch.isfinite(opt[:9]).all() and torch.isfinite(alg.net.params).all()
+        assert torch.isfinite(opt[:L.OPT_GRAD_SQNORM]).all() and torch.isfinite(alg.net.params).all()
         if mode == "1":
             # the captured update is keyed on the whole configuration: flipping the form asks for a new capture
             key = alg.update_graph_key()
@@ -350,8 +351,8 @@ def test_runner_trains_unclipped_and_captured_update_equals_eager(monkeypatch, t
             assert alg.update_graph_key() != key
             alg._ppo_cfg.value_loss_unclipped = 1
             assert alg.update_graph_key() == key
-        if float(opt[9]) >= 128.0:      # fp64 atomics beyond their exact range (tests/test_fused_gpu.py)
-            opt[9] = 0.0
+        if float(opt[L.OPT_GRAD_SQNORM]) >= 128.0:      # fp64 atomics beyond their exact range (tests/test_fused_gpu.py)
+            opt[L.OPT_GRAD_SQNORM] = 0.0
         outs[mode] = (alg.net.params.clone(), alg.net.adam_m.clone(), alg.net.adam_v.clone(), opt)
         if mode == "0":
             path = str(tmp_path / "model.pt")
@@ -377,5 +378,5 @@ def test_dwl_runner_one_unclipped_iteration(monkeypatch):
     r.learn(num_learning_iterations=1, init_at_random_ep_len=True)
     torch.cuda.synchronize()
     opt = alg.net.opt_state
-    assert np.isfinite(float(opt[4]) / float(opt[7])) and torch.isfinite(alg.net.params).all()
+    assert np.isfinite(float(opt[L.OPT_VALUE_SUM]) / float(opt[L.OPT_MINIBATCHES])) and torch.isfinite(alg.net.params).all()
     assert not torch.equal(alg.net.params, before)
