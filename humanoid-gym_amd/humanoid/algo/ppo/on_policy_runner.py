@@ -145,11 +145,47 @@ class _CapturedGraph:
 
 
 class _EpisodeLog:
-    """Host logging book-keeping (on: no log sink): per-step extras["episode"], running return / length, finished-episode sums."""
+    """Host logging book-keeping (on: no log sink): per-step extras["episode"], running return / length per env, and the reference's
+    rewbuffer / lenbuffer -- deque(maxlen=100) -- as two circular buffers in device tensors: ring (2, 101) fp32 (slot 100 takes the
+    writes of the envs that did not finish), meta = [head, fill] int64.  Every operation is stream-ordered torch with fixed shapes, so the
+    loop needs no read-back per step and can be captured; read() is the one read-back per iteration."""
+    RING = 100
 
     def __init__(self, on, tensors):
         self.on, self.ep_infos = on, []
-        self.reward_sum, self.length, self.done = tensors
+        self.reward_sum, self.length, self.ring, self.meta = tensors
+
+    @classmethod
+    def tensors(cls, num_envs, device):
+        z = lambda *s, dtype=torch.float32: torch.zeros(*s, dtype=dtype, device=device)
+        return [z(num_envs), z(num_envs), z(2, cls.RING + 1), z(2, dtype=torch.int64)]
+
+    def step(self, rewards, dones):
+        """on_policy_runner.py:144-154: cur_reward_sum += rewards, cur_episode_length += 1, the buffers .extend(cur[new_ids]) in
+        ascending env order, cur[new_ids] = 0.  The k-th finished env of the step goes to slot (head + k) % 100; of more than 100 only
+        the last 100 are written (what the deque keeps), so no slot is written twice."""
+        R = self.RING
+        self.reward_sum.add_(rewards.reshape(-1))
+        self.length.add_(1)
+        d = dones.reshape(-1) > 0
+        incl = torch.cumsum(d, 0)
+        total = incl[-1]
+        order = incl - 1
+        keep = d & (order >= total - R)
+        head, fill = self.meta[0].clone(), self.meta[1].clone()
+        pos = torch.where(keep, (head + order) % R, torch.full_like(order, R))
+        self.ring[0].scatter_(0, pos, self.reward_sum)
+        self.ring[1].scatter_(0, pos, self.length)
+        self.meta[0] = (head + total) % R
+        self.meta[1] = torch.clamp(fill + total, max=R)
+        self.reward_sum.masked_fill_(d, 0.0)
+        self.length.masked_fill_(d, 0.0)
+
+    def read(self):
+        """(rewbuffer, lenbuffer) as deques, oldest episode first."""
+        ring, (head, fill) = self.ring.cpu(), self.meta.cpu().tolist()
+        slots = [(head - fill + k) % self.RING for k in range(fill)]
+        return tuple(deque((float(ring[j, s]) for s in slots), maxlen=self.RING) for j in (0, 1))
 
 
 class OnPolicyRunner:
@@ -211,8 +247,7 @@ class OnPolicyRunner:
             priv_all[0].copy_(critic_obs)
             obs, critic_obs = obs_all[0], priv_all[0]
         alg.actor_critic.train()
-        log = _EpisodeLog(log_on and not plan.log_sink, [torch.zeros(n, device=self.device) for n in (env.num_envs, env.num_envs, 3)])
-        rings = (deque(maxlen=100), deque(maxlen=100))          # the reference's rewbuffer / lenbuffer
+        log = _EpisodeLog(log_on and not plan.log_sink, _EpisodeLog.tensors(env.num_envs, self.device))
         if plan.env_sink:
             alg.env_stores_transitions = True
         if plan.log_sink:
@@ -263,9 +298,9 @@ class OnPolicyRunner:
                 else:
                     if diag is not None:
                         self._diag_publish(it, diag.cpu())      # (this path synchronises every iteration anyway)
-                    self._finish_sync(plan, log, rings, dict(it=it, num_learning_iterations=num_learning_iterations,
-                                                             collection_time=collection_time, learn_time=learn_time,
-                                                             mean_value_loss=mean_value_loss, mean_surrogate_loss=mean_surrogate_loss))
+                    self._finish_sync(plan, log, dict(it=it, num_learning_iterations=num_learning_iterations,
+                                                      collection_time=collection_time, learn_time=learn_time,
+                                                      mean_value_loss=mean_value_loss, mean_surrogate_loss=mean_surrogate_loss))
                 if log_on and it % self.save_interval == 0:
                     # (current_learning_iteration still holds the value from the start of learn(), the reference's quirk, and "iter"
                     # in model_<it>.pt keeps it; the sidecar records the true count)
@@ -400,7 +435,7 @@ class OnPolicyRunner:
             return self._rollout_fused(plan) if plan.fuse else self._rollout_stepwise(plan, obs, critic_obs, log)
 
         def capture():
-            log_c = _EpisodeLog(log.on, (log.reward_sum, log.length, log.done))       # (the capture refills its own list at every replay)
+            log_c = _EpisodeLog(log.on, (log.reward_sum, log.length, log.ring, log.meta))       # (the capture refills its own list at every replay)
             return dict(out=rollout(st._obs_all[0], st._priv_all[0], log_c), log=log_c, shadow_valid=list(getattr(st, "shadow_valid", [])))
 
         r = self._rollout_capture.run(plan.graph, gkey, lambda: dict(out=rollout(obs, critic_obs, log), log=log), capture,
@@ -434,14 +469,7 @@ class OnPolicyRunner:
             if log.on:
                 if "episode" in infos:
                     log.ep_infos.append({k: v.clone() for k, v in infos["episode"].items()})
-                log.reward_sum.add_(rewards)
-                log.length.add_(1)
-                d = dones.to(torch.float)
-                log.done[0] += (log.reward_sum * d).sum()
-                log.done[1] += (log.length * d).sum()
-                log.done[2] += d.sum()
-                log.reward_sum.mul_(1.0 - d)
-                log.length.mul_(1.0 - d)
+                log.step(rewards, dones)
         if plan.defer_fin:
             env.run_finalize(fin)           # the last step has no following policy launch
         return obs, critic_obs
@@ -481,7 +509,7 @@ class OnPolicyRunner:
             self._log_flush(pending, num_learning_iterations)
         return dict(it=it, ev=ev, snap=snap)
 
-    def _finish_sync(self, plan, log, rings, locs):
+    def _finish_sync(self, plan, log, locs):
         self.last_collection_time, self.last_learn_time = locs["collection_time"], locs["learn_time"]
         if self.log_dir is not None:
             if plan.log_sink:
@@ -489,12 +517,8 @@ class OnPolicyRunner:
                 ep_mean, ring_r, ring_l = self.env.log_sink_read()
                 locs.update(ep_infos=[ep_mean], rewbuffer=deque(ring_r, maxlen=100), lenbuffer=deque(ring_l, maxlen=100))
             else:
-                s = log.done.cpu()
-                if float(s[2]) > 0:
-                    rings[0].append(float(s[0] / s[2]))
-                    rings[1].append(float(s[1] / s[2]))
-                log.done.zero_()
-                locs.update(ep_infos=log.ep_infos, rewbuffer=rings[0], lenbuffer=rings[1])
+                rewbuffer, lenbuffer = log.read()
+                locs.update(ep_infos=log.ep_infos, rewbuffer=rewbuffer, lenbuffer=lenbuffer)
             self.log(locs)
         if self._graph is None or log is not self._rollout_capture.held["log"]:
             log.ep_infos.clear()

@@ -176,6 +176,8 @@ def test_log_sink_is_the_reference_bookkeeping():
     ep_mean, ring_r, ring_l = env.log_sink_read()
     assert len(rewbuffer) == 100 == len(ring_r)
     assert sorted(ring_l) == sorted(lenbuffer) and sorted(ring_r) == sorted(rewbuffer)     # the same 100 episodes (ring order is a rotation)
+    head = int(env._buf.log_stats[L.LOG_RING_HEAD])                                        # ... by exactly the head: slot (head + k) % 100 = the k-th oldest
+    assert ring_l[head:] + ring_l[:head] == list(lenbuffer) and ring_r[head:] + ring_r[:head] == list(rewbuffer)
     for k in ep_infos[0]:
         want = float(np.mean([e[k] for e in ep_infos]))
         assert abs(ep_mean[k] - want) <= 1e-6 + 1e-5 * abs(want), (k, ep_mean[k], want)
@@ -213,6 +215,57 @@ def test_asynchronous_log_prints_what_the_synchronous_one_does(tmp_path, capsys,
     assert sync_blocks == async_blocks == 4
     assert any("Mean reward" in ln for ln in sync_lines) and any("rew_tracking_lin_vel" in ln for ln in sync_lines)
     assert sync_lines == async_lines
+
+
+@pytest.mark.parametrize("num_envs", [264, 8192])
+def test_device_log_sink_prints_what_the_host_loop_does(num_envs, tmp_path, capsys, monkeypatch):
+    """The same seed trained for 3 iterations with HGYM_LOG_SINK=0 -- the reference's per-step book-keeping on the host side of the
+    loop (on_policy_runner.py:143-156, _EpisodeLog), stepwise rollout -- and with the default: the book-keeping inside the step
+    finaliser, which rides in the fused rollout launch (8192 envs: its 512-lane workgroup takes two trips of the one-pass form).
+    Every log line that is not a wall-clock figure must be identical: losses, noise std, Mean reward, Mean episode length, all 22 rew_*.
+    (The two loop plans differ in everything BUT the arithmetic: stepwise against fused rollout, synchronous against asynchronous log;
+    tests/test_fused_gpu.py holds the rollouts bit-equal.)  200 envs are planted ten steps before their time-out in the first iteration
+    and again in the last one, so more than 100 episodes end in ONE step -- asserted from the stored dones, both times: the sink's
+    last-100-survive rule and the host loop's agree on Mean reward only if both keep the same 100.  (learn(1) + learn(2): the storage
+    holds one iteration's dones; both calls start from empty buffers on either path.)"""
+    from humanoid.envs import task_registry
+    from humanoid.utils import get_args
+    N, T = num_envs, 60
+    plant = torch.arange(0, 200, device="cuda")
+
+    def run(tag, sink_on):
+        monkeypatch.setenv("HGYM_LOG_SINK", "1" if sink_on else "0")
+        args = get_args(["--task=humanoid_ppo", "--headless", "--num_envs", str(N), "--seed", "3"])
+        env, _ = task_registry.make_env(name=args.task, args=args)
+        runner, _ = task_registry.make_alg_runner(env=env, name=args.task, args=args, log_root=str(tmp_path / tag))
+        assert runner.num_steps_per_env == T
+        g = torch.Generator().manual_seed(17)
+        ep = torch.randint(2150, 2390, (N,), generator=g).cuda()          # (behind the runner's env.reset(), which zeroes the lengths)
+        ep[plant] = 2400 - 10
+        env.episode_length_buf = ep
+        capsys.readouterr()
+        most = []
+        for iters in (1, 2):
+            runner.learn(num_learning_iterations=iters, init_at_random_ep_len=False)
+            torch.cuda.synchronize()
+            most.append(int(runner.alg.storage.dones.view(T, N).bool().sum(1).max()))
+            ep = env.episode_length_buf.clone()
+            ep[plant] = 2400 - (T + 10)
+            env.episode_length_buf = ep
+        out = capsys.readouterr().out
+        keep = [ln for ln in out.splitlines() if ":" in ln and not any(w in ln for w in ("steps/s", "time:", "ETA", "Iteration time"))]
+        return keep, out.count("Learning iteration"), most
+
+    # (`--seed` reaches the env through the registered train cfg from the second make_env of a process on: one throw-away pair)
+    args = get_args(["--task=humanoid_ppo", "--headless", "--num_envs", "64", "--seed", "3"])
+    env, _ = task_registry.make_env(name=args.task, args=args)
+    task_registry.make_alg_runner(env=env, name=args.task, args=args, log_root=None)
+    host_lines, host_blocks, host_most = run("host", False)
+    sink_lines, sink_blocks, sink_most = run("sink", True)
+    assert host_blocks == sink_blocks == 3
+    assert min(host_most) > 100 and host_most == sink_most, (host_most, sink_most)
+    assert sum("Mean reward" in ln for ln in sink_lines) == 3 and sum("rew_tracking_lin_vel" in ln for ln in sink_lines) == 3
+    assert host_lines == sink_lines, [(a, b) for a, b in zip(host_lines, sink_lines) if a != b]
 
 
 def test_full_size_rollout_storage_is_self_consistent():
