@@ -156,4 +156,8 @@ HG_HD float uniform_at(const RngKey& k, uint32_t env, uint32_t base, int i) {
 
 HG_HD float clampf(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
 
+// hgym_net.hip: where the kernels read the policy's standard deviations -- the head of net->params (HGYM_STD_SCALAR) or the derived
+// block in the workspace (HGYM_STD_LOG); fails like every call taking the configuration
+int32_t net_sigma_src(const HgymNetConfig* cfg, const HgymNet* net, const float** out);
+
 }  // namespace hgym

@@ -196,8 +196,11 @@ int32_t hgym_ppo_diagnostics(const HgymNetConfig* cfg, const HgymPPOConfig* ppo,
                (long long)mb);
     float* mu_new = scratch;
     float* v_new = scratch + mb * HGYM_NUM_ACTIONS;
+    const float* std = nullptr;      // sigma itself in either HgymNetConfig.std_param mode
+    const int32_t rc_std = net_sigma_src(cfg, net, &std);
+    if (rc_std) return rc_std;
     if (M == 0)
-        return hgym_ppo_diag_reduce(0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, net->params,
+        return hgym_ppo_diag_reduce(0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, std,
                                     ppo->clip_param, 0, 0, 1, block, stream);
     for (int64_t m0 = 0; m0 < M; m0 += piece) {
         const int64_t n = std::min<int64_t>(piece, M - m0);
@@ -207,7 +210,7 @@ int32_t hgym_ppo_diagnostics(const HgymNetConfig* cfg, const HgymPPOConfig* ppo,
         if (rc) return rc;
         rc = hgym_ppo_diag_reduce(n, rows->actions + m0 * HGYM_NUM_ACTIONS, rows->mu + m0 * HGYM_NUM_ACTIONS,
                                   rows->sigma + m0 * HGYM_NUM_ACTIONS, mu_new, rows->logp + m0, rows->values + m0, rows->returns + m0,
-                                  rows->advantages + m0, v_new, net->params, ppo->clip_param, m0, M, m0 + n >= M ? 1 : 0, block, stream);
+                                  rows->advantages + m0, v_new, std, ppo->clip_param, m0, M, m0 + n >= M ? 1 : 0, block, stream);
         if (rc) return rc;
     }
     return HGYM_OK;

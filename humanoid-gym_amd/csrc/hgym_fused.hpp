@@ -1395,6 +1395,7 @@ struct ScalArgs {
     int group;             // 0 / 1: `partials` holds one row per loss workgroup; 4: one row per 16-row block (mlp_fb2_kernel), four
                            // consecutive rows are added first, ((p0 + p1) + p2) + p3 in fp32 -- the sum mlp_fb_kernel's 64-row tile forms
                            // over its four head waves -- and nblocks counts those groups
+    const float* sigma;    // HGYM_STD_LOG: the derived sigma block -- the std gradient leaves as d/d(log sigma) = d/d(sigma) * sigma; null: as it is
 };
 // ppo.py:140-145, the one copy of the rule (ppo_scalars_block here, apply_prologue in hgym_net.hip).  The reference compares the fp32
 // 0-dim tensor kl_mean with python floats, which torch rounds to fp32: the comparisons are fp32 ones against float32(desired_kl * 2) and
@@ -1479,7 +1480,12 @@ __device__ __forceinline__ void ppo_scalars_block(const ScalArgs& a, int tid, in
                 opt[HGYM_OPT_SQRT_BC2] = (double)(float)sqrt(bc2);
             }
         }
-        if (q >= LP_DSTD && q < LP_DBIAS_MU && q - LP_DSTD < A) a.grads_std[q - LP_DSTD] = (float)t;
+        if (q >= LP_DSTD && q < LP_DBIAS_MU && q - LP_DSTD < A) {
+            // (log mode: the sum rounded to fp32 as ever, then ONE fp32 product -- the chain rule of sigma = exp(log sigma); in place before
+            // any pass squares the gradient, so the clip norm is that of the log-std gradient)
+            const float g = (float)t;
+            a.grads_std[q - LP_DSTD] = a.sigma ? __fmul_rn(g, a.sigma[q - LP_DSTD]) : g;
+        }
         if (q >= LP_DBIAS_MU && q < LP_DBIAS_V && q - LP_DBIAS_MU < A && a.grads_bmu) a.grads_bmu[q - LP_DBIAS_MU] = (float)t;
         if (q == LP_DBIAS_V && a.grads_bv) a.grads_bv[0] = (float)t;
         if (q == LP_AUX && a.aux_No > 0) opt[HGYM_OPT_AUX_SUM] += t / ((double)B * (double)a.aux_No);    // auxiliary head's MSE (the fused kernel's third grid row)

@@ -59,6 +59,8 @@ struct WsLayout {
     int64_t partials;        // [MAX_LOSS_BLOCKS][16] fp32
     int64_t zeros;           // 4 KiB that nothing ever writes (the workspace arrives zero-filled)
     int64_t sqn;             // [SQN_BLOCKS] fp64 per-workgroup sums of sqnorm_prologue_kernel + its arrival counter (zero between launches)
+    int64_t sigma;           // HGYM_STD_LOG: [SIGMA_FLOATS] fp32, sigma[j] = exp(params[j]) for j < A (sigma_of; adam_kernel and
+                             // sync_shadow_kernel keep it current); -1 in HGYM_STD_SCALAR, where the parameters are sigma and nothing is taken
     int64_t total_bytes;
     Act act;                 // the hidden layers' activation (HgymNetConfig.activation, resolved)
     int64_t Mpad;            // fused path: batch padded to the 64-row tile
@@ -68,6 +70,7 @@ struct WsLayout {
 constexpr int MAX_LOSS_BLOCKS = 8192;   // 256 samples each: minibatches up to 2 M samples
 constexpr int SQN_BLOCKS = 256;         // workgroups of sqnorm_prologue_kernel
 constexpr int RSN_X = 96;               // workgroups per segment of reduce_slabs_kernel
+constexpr int SIGMA_FLOATS = 16;        // the derived sigma block (log mode): num_actions <= 12 entries, padded to 64 bytes
 
 // the hidden widths the fused kernels are instantiated for, and the update's tile fits (hgym_fused.hpp: fb_lds_bytes)
 static bool fused_trunk_ok(const int32_t* d) {
@@ -146,6 +149,8 @@ static int32_t ws_layout(const HgymNetConfig* c, WsLayout* w) {
     w->Mp = round_up(c->max_batch, w->SE);
     HG_REQUIRE(c->fused_activation == 0 || c->fused_activation == 1, HGYM_E_BADARG,
                "HgymNetConfig.fused_activation=%d (0: the fused bf16 kernels for ELU(1) only, 1: for any activation)", c->fused_activation);
+    HG_REQUIRE(c->std_param == HGYM_STD_SCALAR || c->std_param == HGYM_STD_LOG, HGYM_E_BADARG,
+               "HgymNetConfig.std_param=%d (HGYM_STD_SCALAR = 0: the parameters hold sigma, HGYM_STD_LOG = 1: log sigma)", c->std_param);
     const bool fused = fused_supported(c) && (act_is_elu1(w->act) || c->fused_activation == 1);
     w->Mpad = round_up(c->max_batch, 64);
     int64_t off = 0, poff = c->num_actions;  // std first (state_dict order)
@@ -221,6 +226,7 @@ static int32_t ws_layout(const HgymNetConfig* c, WsLayout* w) {
     w->partials = take((int64_t)MAX_LOSS_BLOCKS * LOSS_PARTIALS * 4);
     w->zeros = take(4096);
     w->sqn = take((SQN_BLOCKS + 2) * 8);
+    w->sigma = c->std_param == HGYM_STD_LOG ? take(SIGMA_FLOATS * 4) : -1;     // behind everything else: no other offset moves
     w->total_bytes = off;
     return HGYM_OK;
 }
@@ -504,6 +510,7 @@ struct Segment {
     void* Wf;        // fused path: forward fragments [NB][KB][64][8] or null
     void* WTf;       // fused path: backward fragments [K/16][NBB][64][8]
     int KB, NBB;
+    float* sigma;    // the std segment in HGYM_STD_LOG: the derived sigma block, rewritten wherever the parameter is; null otherwise
 };
 struct SegTable {
     int n;
@@ -648,6 +655,10 @@ __global__ __launch_bounds__(256) void sqnorm_prologue_kernel(int64_t P, const f
     }
 }
 
+// HGYM_STD_LOG: sigma from its parameter log sigma -- the ONE place that forms it (adam_kernel behind a step, sync_shadow_kernel behind a
+// load; everything that reads sigma reads the block they fill).  expf: 1 ulp as HIP documents it; exp(0) = 1 exactly.
+__device__ __forceinline__ float sigma_of(float log_sigma) { return expf(log_sigma); }
+
 // writes one master weight into every compute-precision operand copy of its layer
 template <typename T>
 __device__ __forceinline__ void write_shadows(const Segment& sg, int r, int c, float w) {
@@ -693,6 +704,8 @@ __global__ __launch_bounds__(256) void adam_kernel(const SegTable tab, const Hgy
         if (sg.Wp || sg.Wf) {
             const int r = (int)(i / sg.cols), c = (int)(i - (int64_t)r * sg.cols);
             write_shadows<T>(sg, r, c, w);
+        } else if (sg.sigma) {
+            sg.sigma[i] = sigma_of(w);      // same launch: a captured update keeps the block current without a node of its own
         }
     }
 }
@@ -700,6 +713,9 @@ __global__ __launch_bounds__(256) void adam_kernel(const SegTable tab, const Hgy
 template <typename T>
 __global__ __launch_bounds__(256) void sync_shadow_kernel(const SegTable tab, const float* __restrict__ params) {
     const Segment& sg = tab.s[blockIdx.y];
+    if (sg.sigma)       // (ahead of the early return: the std segment has no operand copy, but in log mode it has this one)
+        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (int64_t)sg.rows * sg.cols; i += (int64_t)gridDim.x * blockDim.x)
+            sg.sigma[i] = sigma_of(params[sg.off + i]);
     if (!sg.Wp && !sg.Wf) return;
     const int64_t n = (int64_t)sg.rows * sg.cols;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -771,6 +787,12 @@ static size_t fwd_lds(const FwdArgs& a, int nets, int BM) {
     return lds;
 }
 
+// Where the kernels read sigma: the head of the parameter vector (HGYM_STD_SCALAR) or the derived block (HGYM_STD_LOG).  Every site that
+// hands sigma to a kernel goes through here.
+static const float* sigma_src(const WsLayout& w, const HgymNet& net) {
+    return w.sigma >= 0 ? reinterpret_cast<const float*>((const char*)net.workspace + w.sigma) : net.params;
+}
+
 // What both paths share: the workspace, the segment table of the slab reduction / Adam / the shadow refresh, and those two launches.
 struct NetBase {
     const HgymNetConfig& cfg;
@@ -780,6 +802,9 @@ struct NetBase {
     char* ws;
 
     template <typename U> U* at(int64_t off) const { return reinterpret_cast<U*>(ws + off); }
+    const float* sigma_in() const { return sigma_src(w, net); }
+    // ScalArgs::sigma: the chain-rule factor of the std gradient (log mode), null where the gradient is sigma's own
+    const float* grad_sigma() const { return w.sigma >= 0 ? sigma_in() : nullptr; }
 
     // split-K slabs of a weight gradient on the layer-by-layer path, for a minibatch whose contraction padding is Mp
     // (restated in tests/layer_path_common.py: split_count -- keep the two in step)
@@ -812,6 +837,7 @@ struct NetBase {
         sd.off = 0;
         sd.rows = cfg.num_actions;
         sd.cols = 1;
+        if (w.sigma >= 0) sd.sigma = at<float>(w.sigma);
         for (int which = 0; which < w.nnets; ++which) {
             const NetLayout& n = w.net[which];
             for (int l = 0; l < n.L; ++l) {
@@ -1023,7 +1049,7 @@ struct GemmPath : NetBase {
         a.A = A;
         a.mu = mu;
         a.val = val;
-        a.std_ = net.params;
+        a.std_ = sigma_in();
         a.clip = ppo.clip_param;
         a.value_coef = ppo.value_loss_coef;
         a.entropy_coef = ppo.entropy_coef;
@@ -1042,7 +1068,7 @@ struct GemmPath : NetBase {
         prof_end(HGYM_PROF_LOSS, s, (double)B * (4.0 * (5 * A + 6) + (double)sizeof(T) * (2 * A + 2)));
         HG_CHECK_LAUNCH("ppo_loss_kernel");
         const ScalArgs sc = {nblocks, B, A, 0, at<float>(w.partials), net.grads, nullptr, nullptr, net.grads + w.P, net.opt_state,
-                             (double)ppo.beta1, (double)ppo.beta2, 0, 0, 0.0f, 0.0, 0.0, 1};
+                             (double)ppo.beta1, (double)ppo.beta2, 0, 0, 0.0f, 0.0, 0.0, 1, grad_sigma()};
         hipLaunchKernelGGL(ppo_scalars_kernel, dim3(1), dim3(512), 0, s, sc);
         HG_CHECK_LAUNCH("ppo_scalars_kernel");
         rc = backward(0, B);
@@ -1070,7 +1096,7 @@ struct GemmPath : NetBase {
         if (rc) return rc;
         rc = forward(1, M, priv, cfg.num_priv, nullptr, values, 1, false);
         if (rc) return rc;
-        hipLaunchKernelGGL(act_sample_kernel, dim3(ceil_div(M, 256)), dim3(256), 0, s, M, cfg.num_actions, mu, net.params, z, seed, step,
+        hipLaunchKernelGGL(act_sample_kernel, dim3(ceil_div(M, 256)), dim3(256), 0, s, M, cfg.num_actions, mu, sigma_in(), z, seed, step,
                            actions, sigma, logp);
         HG_CHECK_LAUNCH("act_sample_kernel");
         return HGYM_OK;
@@ -1177,7 +1203,7 @@ struct FusedPath : NetBase {
         if (fin) a.fin = *fin;
         a.train = train ? 3 : 0;
         a.A = cfg.num_actions;
-        a.std_ = net.params;
+        a.std_ = sigma_in();
         if (smp) {
             a.sample = 1;
             a.z = smp->z;
@@ -1369,7 +1395,7 @@ struct FusedPath : NetBase {
         const ScalArgs sc = {tiles, B, A, nets == 3 ? w.net[2].layer[3].N : 0, at<float>(w.partials), net.grads,
                              net.grads + w.net[0].layer[3].b_off, net.grads + w.net[1].layer[3].b_off, net.grads + w.P, net.opt_state,
                              (double)ppo.beta1, (double)ppo.beta2, prologue_in_grad(ppo) ? 1 : 0, ppo.adaptive_lr, ppo.desired_kl, ppo.lr_min,
-                             ppo.lr_max, 1};
+                             ppo.lr_max, 1, grad_sigma()};
         int32_t rc = dw(nets, B, sc, shadow ? &b : nullptr);
         if (rc) return rc;
         if (w.nnets > 2 && nets == 2) {
@@ -1499,6 +1525,15 @@ int32_t rollout_eval_fwd_args(const HgymNetConfig* cfg, const HgymNet* net, int 
     return HGYM_OK;
 }
 
+// For hgym_diag.hip: sigma_src behind the configuration check.
+int32_t net_sigma_src(const HgymNetConfig* cfg, const HgymNet* net, const float** out) {
+    WsLayout w;
+    const int32_t rc = check_net(cfg, net, &w);
+    if (rc) return rc;
+    *out = sigma_src(w, *net);
+    return HGYM_OK;
+}
+
 }  // namespace hgym
 
 using namespace hgym;
@@ -1515,6 +1550,12 @@ int64_t hgym_net_workspace_bytes(const HgymNetConfig* cfg) {
     WsLayout w;
     if (ws_layout(cfg, &w)) return -1;
     return w.total_bytes;
+}
+
+int64_t hgym_net_sigma_offset(const HgymNetConfig* cfg) {
+    WsLayout w;
+    if (ws_layout(cfg, &w)) return -2;
+    return w.sigma;      // -1: HGYM_STD_SCALAR
 }
 
 int32_t hgym_net_sync_shadow(const HgymNetConfig* cfg, const HgymNet* net, void* stream) {

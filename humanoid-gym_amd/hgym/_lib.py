@@ -19,6 +19,7 @@ MAX_LAYERS = 8
 MAX_CUSTOM_REWARDS = 24
 F32, BF16 = 0, 1
 ACT_ELU, ACT_SELU, ACT_LEAKY_RELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3, 4    # HGYM_ACT_*
+STD_SCALAR, STD_LOG = 0, 1    # HGYM_STD_*: params[:A] hold sigma / log sigma (HgymNetConfig.std_param)
 
 c_float_p = C.POINTER(C.c_float)
 c_u8_p = C.POINTER(C.c_uint8)
@@ -109,7 +110,7 @@ class NetConfig(C.Structure):
                 ("precision", C.c_int32), ("max_batch", C.c_int32),
                 ("aux_layers", C.c_int32), ("aux_dims", C.c_int32 * (MAX_LAYERS + 1)), ("aux_target_offset", C.c_int32),
                 ("activation", C.c_int32), ("act_alpha", C.c_float), ("act_scale", C.c_float),
-                ("fused_activation", C.c_int32)]
+                ("std_param", C.c_int32), ("fused_activation", C.c_int32)]
 
 
 class PPOConfig(C.Structure):
@@ -187,6 +188,7 @@ SYMBOLS = {
     "hgym_critic_values": (C.c_int32, [_P(NetConfig), _P(Net), C.c_int64, c_float_p, c_float_p, _P(ObsShadow), C.c_void_p]),
     "hgym_net_param_count": (C.c_int64, [_P(NetConfig)]),
     "hgym_net_workspace_bytes": (C.c_int64, [_P(NetConfig)]),
+    "hgym_net_sigma_offset": (C.c_int64, [_P(NetConfig)]),
     "hgym_net_sync_shadow": (C.c_int32, [_P(NetConfig), _P(Net), C.c_void_p]),
     "hgym_mlp_forward": (C.c_int32, [_P(NetConfig), _P(Net), C.c_int32, C.c_int32, c_float_p, C.c_int64, c_float_p, C.c_void_p]),
     "hgym_net_shadow_ld": (C.c_int64, [_P(NetConfig), C.c_int32]),

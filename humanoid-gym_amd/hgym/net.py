@@ -33,15 +33,28 @@ def activation_spec(activation):
     raise NotImplementedError("activation %r is not implemented by the HIP kernels; supported: %s" % (m, SUPPORTED_ACTIVATIONS))
 
 
+NOISE_STD_TYPES = ("scalar", "log")
+
+
+def std_param_spec(noise_std_type):
+    """HgymNetConfig.std_param of ActorCritic(noise_std_type=...): "scalar" (the parameter is sigma) or "log" (it is log sigma)."""
+    if noise_std_type not in NOISE_STD_TYPES:
+        raise ValueError("noise_std_type=%r: must be \"scalar\" or \"log\"" % (noise_std_type,))
+    return L.STD_LOG if noise_std_type == "log" else L.STD_SCALAR
+
+
 def make_net_config(num_obs, num_priv, num_actions, actor_hidden, critic_hidden, precision, max_batch, aux_hidden=None, aux_out=0,
-                    aux_target_offset=0, activation=None, fused_activation=False):
+                    aux_target_offset=0, activation=None, fused_activation=False, noise_std_type="scalar"):
     """aux_hidden / aux_out / aux_target_offset: the optional auxiliary (denoising) head obs -> aux_hidden -> aux_out that regresses
     columns [aux_target_offset, aux_target_offset + aux_out) of the privileged row (HgymNetConfig.aux_*).
     activation: the torch module between the Linear layers of every MLP (activation_spec; None: ELU).
     fused_activation: HgymNetConfig.fused_activation -- a bf16 net of the widths the fused kernels take runs them (forward, update tiles,
     bf16 observation shadow) with any activation, not only ELU(1); off by default, because the fused kernels' fast exp2 / rcp forms round
-    differently from the layer-by-layer path's libm.  Ignored where the fused kernels are refused anyway; no effect on ELU(1)."""
+    differently from the layer-by-layer path's libm.  Ignored where the fused kernels are refused anyway; no effect on ELU(1).
+    noise_std_type: "scalar" -- the first num_actions parameters are the standard deviations -- or "log" -- they are their logarithms
+    (HgymNetConfig.std_param); anything else: ValueError."""
     c = L.NetConfig()
+    c.std_param = std_param_spec(noise_std_type)
     c.fused_activation = 1 if fused_activation else 0
     c.activation, c.act_alpha, c.act_scale = activation_spec(activation)
     c.num_obs, c.num_priv, c.num_actions = int(num_obs), int(num_priv), int(num_actions)
@@ -109,7 +122,13 @@ class NetBuffers:
         # named views
         self.views = {}
         A = cfg.num_actions
-        self.views["std"] = self.params[:A]
+        # the head of the flat vector: sigma ("std") or, with HgymNetConfig.std_param = HGYM_STD_LOG, log sigma ("log_std").  `sigma` is
+        # the A standard deviations in both modes: the same memory as "std", or the block of the workspace the library derives
+        so = int(L.lib.hgym_net_sigma_offset(C.byref(cfg)))
+        if so < -1:
+            raise L.HgymError("bad net config: %s" % L.lib.hgym_last_error().decode())
+        self.views["log_std" if so >= 0 else "std"] = self.params[:A]
+        self.sigma = self.params[:A] if so < 0 else self.workspace[off + so:off + so + 4 * A].view(torch.float32)
         off = A
         nets = [("actor", cfg.actor_dims, cfg.actor_layers), ("critic", cfg.critic_dims, cfg.critic_layers)]
         if cfg.aux_layers > 0:

@@ -28,18 +28,22 @@ def _mlp(sizes, activation):
 class ActorCritic(nn.Module):
     def __init__(self, num_actor_obs, num_critic_obs, num_actions, actor_hidden_dims=[256, 256, 256],
                  critic_hidden_dims=[256, 256, 256], init_noise_std=1.0, activation=nn.ELU(), denoiser_hidden_dims=None,
-                 denoiser_targets=0, fused_activation=None, **kwargs):
+                 denoiser_targets=0, fused_activation=None, noise_std_type="scalar", **kwargs):
         """denoiser_hidden_dims / denoiser_targets (native extension, BASELINE configs[4]): an auxiliary head
         obs -> denoiser_hidden_dims -> denoiser_targets that regresses the newest `denoiser_targets` columns of the
         privileged observation (the clean single-frame privileged state) from the noisy observation history; trained jointly
         with PPO (PPO(denoise_coef=...)).  The reference has no code for it (README.md:113); off by default.
         fused_activation (native extension): run the fused bf16 kernels with `activation` whatever it is, not only with ELU(1)
         (HgymNetConfig.fused_activation; PPO passes it into the net config).  None: the environment variable HGYM_FUSED_ACT ("1": on),
-        else off."""
+        else off.
+        noise_std_type (as in current rsl_rl): "scalar" -- the reference's parameter `std`, the standard deviations themselves, which
+        nothing keeps positive -- or "log" -- the parameter is `log_std` (first in the state dict, where `std` is otherwise) and
+        sigma = exp(log_std) stays positive wherever the optimiser moves it.  `noise_std` is sigma in both modes."""
+        from hgym.net import activation_spec, std_param_spec
+        std_param_spec(noise_std_type)       # ValueError for anything but "scalar" / "log", before anything is built
         if kwargs:
             print("ActorCritic.__init__ got unexpected arguments, which will be ignored: " + str(list(kwargs.keys())))
         super().__init__()
-        from hgym.net import activation_spec
         activation_spec(activation)          # NotImplementedError (listing what is supported) for anything the kernels lack
         self.activation = activation
         self.fused_activation = (os.environ.get("HGYM_FUSED_ACT", "0") == "1") if fused_activation is None else bool(fused_activation)
@@ -53,7 +57,11 @@ class ActorCritic(nn.Module):
             self.denoiser = _mlp([num_actor_obs] + self.denoiser_hidden_dims + [self.denoiser_targets], activation)
         print(f"Actor MLP: {self.actor}")
         print(f"Critic MLP: {self.critic}")
-        self.std = nn.Parameter(init_noise_std * torch.ones(num_actions))
+        self.noise_std_type = noise_std_type
+        if noise_std_type == "log":
+            self.log_std = nn.Parameter(torch.log(init_noise_std * torch.ones(num_actions)))
+        else:
+            self.std = nn.Parameter(init_noise_std * torch.ones(num_actions))
         self._net = None          # hgym.NetBuffers once bound
         self._last = None         # outputs of the last act(): mu, sigma, logp, values
         self._sample_seed = 0
@@ -99,6 +107,13 @@ class ActorCritic(nn.Module):
         raise NotImplementedError
 
     @property
+    def noise_std(self):
+        """The num_actions standard deviations, whichever way they are parametrised."""
+        if self.noise_std_type != "log":
+            return self.std.detach()
+        return self._net.sigma if self._net is not None else torch.exp(self.log_std.detach())
+
+    @property
     def action_mean(self):
         return self._last["mu"]
 
@@ -113,7 +128,7 @@ class ActorCritic(nn.Module):
     def update_distribution(self, observations):
         net = self._need_net()
         mu = net.forward(0, observations.contiguous())
-        self._last = dict(mu=mu, sigma=mu * 0.0 + self.std.detach())
+        self._last = dict(mu=mu, sigma=mu * 0.0 + self.noise_std)
 
     def act(self, observations, critic_observations=None, out=None, env_fin=None, shadow=None, **kwargs):
         """Sample actions.  With critic_observations the critic runs in the same call (what PPO.act needs)."""

@@ -564,12 +564,18 @@ class OnPolicyRunner:
         pin = self._log_pin
         pin["opt"][slot].copy_(alg.net.opt_state, non_blocking=True)
         pin["ls"][slot].copy_(env._buf.log_stats, non_blocking=True)
-        pin["std"][slot].copy_(alg.actor_critic.std.detach().mean().reshape(1), non_blocking=True)
+        pin["std"][slot].copy_(self._noise_std(alg.actor_critic).mean().reshape(1), non_blocking=True)
         comm_words = alg.comm_status_snapshot(slot) if hasattr(alg, "comm_status_snapshot") else None
         env._buf.clear_log_sums()
         done = torch.cuda.Event()
         done.record()
         return dict(slot=slot, done=done, aux=alg._ppo_cfg.aux_coef > 0.0, comm=comm_words)
+
+    @staticmethod
+    def _noise_std(ac):
+        """The policy's standard deviations: `noise_std` (sigma whichever way it is parametrised), else the reference's `std`."""
+        s = getattr(ac, "noise_std", None)
+        return (ac.std if s is None else s).detach()
 
     def _log_flush(self, pending, num_learning_iterations):
         """Print / record the log block of a finished iteration from its host snapshot (no device access: the device is busy with
@@ -608,7 +614,7 @@ class OnPolicyRunner:
                     value = float(vals.mean())
                 scal("Episode/" + key, value, locs["it"])
                 ep_string += f"""{f'Mean episode {key}:':>{pad}} {value:.4f}\n"""
-        mean_std = locs["mean_std"] if "mean_std" in locs else float(self.alg.actor_critic.std.detach().mean())
+        mean_std = locs["mean_std"] if "mean_std" in locs else float(self._noise_std(self.alg.actor_critic).mean())
         learning_rate = locs["learning_rate"] if "learning_rate" in locs else self.alg.learning_rate
         fps = int(self.num_steps_per_env * self.env.num_envs / iteration_time)
         scal("Loss/value_function", locs["mean_value_loss"], locs["it"])
@@ -818,6 +824,12 @@ class OnPolicyRunner:
                 raise ValueError("env state: num_steps_per_env is %d in the sidecar, %d here" % (int(side["num_steps_per_env"]), self.num_steps_per_env))
             self.env.check_state_dict(side["env"])      # (a sidecar that does not fit this env: refused before anything is changed)
         loaded = torch.load(path, map_location=self.device)
+        # a checkpoint of the other noise parametrisation: its first entry is another quantity under another name
+        msd, mine = loaded["model_state_dict"], getattr(self.alg.actor_critic, "noise_std_type", "scalar")
+        theirs = "log" if "log_std" in msd else ("scalar" if "std" in msd else mine)
+        if theirs != mine:
+            raise RuntimeError("%s was trained with noise_std_type=\"%s\" (its model_state_dict has `%s`); this policy was built with "
+                               "noise_std_type=\"%s\"" % (os.path.basename(str(path)), theirs, "log_std" if theirs == "log" else "std", mine))
         self.alg.actor_critic.load_state_dict(loaded["model_state_dict"])
         if load_optimizer or (side is not None and self.cfg.get("exact_resume", False)):
             self.alg.optimizer.load_state_dict(loaded["optimizer_state_dict"])

@@ -121,7 +121,8 @@ class PPO:
         cfg = hgym.make_net_config(ac.num_actor_obs, ac.num_critic_obs, ac.num_actions, ac.actor_hidden_dims, ac.critic_hidden_dims,
                                    self.precision, max(mb, num_envs), aux_hidden=aux, aux_out=getattr(ac, "denoiser_targets", 0),
                                    aux_target_offset=ac.num_critic_obs - getattr(ac, "denoiser_targets", 0),
-                                   activation=getattr(ac, "activation", None), fused_activation=getattr(ac, "fused_activation", False))
+                                   activation=getattr(ac, "activation", None), fused_activation=getattr(ac, "fused_activation", False),
+                                   noise_std_type=getattr(ac, "noise_std_type", "scalar"))
         # data-parallel update: the exchange is chosen here, once (HGYM_COMM=auto: the direct kernel over peer mappings is set up,
         # checked and timed against the collective, and used when it is faster; any failure falls back on every rank -- dist_utils).
         # With the direct exchange the gradient vector lives in peer-mapped memory.

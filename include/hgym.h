@@ -57,7 +57,9 @@ extern "C" {
                              *    (same version, later: the diagnostics pass behind an update -- hgym_ppo_diag_reset, hgym_ppo_diag_reduce,
                              *    hgym_ppo_diagnostics; no layout changes)
                              *    (same version, later: names for the slots of opt_state, log_stats and counters -- HGYM_OPT_*, HGYM_LOG_*,
-                             *    HGYM_CNT_*; no layout changes) */
+                             *    HGYM_CNT_*; no layout changes)
+                             *    (same version, later: HgymNetConfig.std_param added ahead of fused_activation -- the action noise trained as log sigma
+                             *    (HGYM_STD_LOG) -- and hgym_net_sigma_offset; a zero-filled field is the sigma parameter every earlier layout meant) */
 
 enum {
     HGYM_OK = 0,
@@ -452,6 +454,19 @@ enum { HGYM_F32 = 0, HGYM_BF16 = 1 };
  * bf16 configuration with another activation runs the GEMM path, as a net too wide for the fused tiles' LDS does. */
 enum { HGYM_ACT_ELU = 0, HGYM_ACT_SELU = 1, HGYM_ACT_LEAKY_RELU = 2, HGYM_ACT_TANH = 3, HGYM_ACT_SIGMOID = 4 };
 
+/* What slots [0, num_actions) of the flat parameter vector hold (HgymNetConfig.std_param):
+ *   HGYM_STD_SCALAR  the standard deviations sigma themselves (the reference's `std`, actor_critic.py:80; nothing keeps them positive)
+ *   HGYM_STD_LOG     log sigma; sigma = exp(log sigma) is positive wherever the optimiser moves the parameter, and an Adam step is a
+ *                    relative change of sigma (noise_std_type = "log" of current rsl_rl)
+ * In HGYM_STD_LOG the library keeps sigma[j] = expf(params[j]), j < num_actions, in a block of 16 floats of the workspace
+ * (hgym_net_sigma_offset) and every kernel reads sigma from there -- the same kernels, the same arithmetic, the same bits as
+ * HGYM_STD_SCALAR with those values as parameters.  The block is rewritten where the parameter changes and nowhere else: by
+ * hgym_ppo_apply (inside the Adam launch, so a captured update keeps it current) and by hgym_net_sync_shadow (call it after writing
+ * params, as for the operand copies; until the first of the two the block is the zero fill).  The gradient of slots [0, num_actions)
+ * is that of the parameter: d/d(log sigma) = fp32(d/d sigma) * sigma, one fp32 product applied where hgym_ppo_grad / hgym_ppo_grad_part
+ * (part 0, ahead of a rank exchange) write it, so the squared norm in opt_state[HGYM_OPT_GRAD_SQNORM] and the clip are the parameter's too. */
+enum { HGYM_STD_SCALAR = 0, HGYM_STD_LOG = 1 };
+
 typedef struct HgymNetConfig {
     int32_t num_obs, num_priv, num_actions;
     int32_t actor_layers, critic_layers;                 /* number of Linear layers (4, 4) */
@@ -469,6 +484,13 @@ typedef struct HgymNetConfig {
     int32_t aux_target_offset;
     int32_t activation;                                  /* HGYM_ACT_* (0: ELU, the reference default) */
     float act_alpha, act_scale;                          /* its parameters, see HGYM_ACT_* (0, 0: the kind's defaults) */
+    int32_t std_param;              /* HGYM_STD_* above: HGYM_STD_SCALAR (0, the default) -- params[0 .. num_actions) are sigma; HGYM_STD_LOG (1) --
+                                       they are log sigma.  The outputs named `sigma` and `std` of every call are sigma in both modes, never
+                                       its logarithm.  Any other value: HGYM_E_BADARG from every call taking the configuration.  Added
+                                       later within header v9, AHEAD of fused_activation, which stays the last field of the struct (its
+                                       mirrors and their tests locate it as the struct's last four bytes): a zero-filled field is
+                                       HGYM_STD_SCALAR, and a caller built against an earlier v9 header is rebuilt against this one, as
+                                       for every field the struct has gained (hgym_sizeof("HgymNetConfig") tells a stale mirror). */
     int32_t fused_activation;       /* which activations take the fused bf16 kernels (forward tiles, the update's fused tiles, the bf16
                                          observation shadow), in a bf16 configuration those kernels accept:
                                          0: ELU(1) only; every other activation runs the layer-by-layer GEMM path  (the default)
@@ -509,9 +531,13 @@ typedef struct HgymPPOConfig {
 /* Sizes (bytes) of the caller-allocated blocks, as functions of the configuration. */
 int64_t hgym_net_param_count(const HgymNetConfig* net);          /* 926105 for XBot-L */
 int64_t hgym_net_workspace_bytes(const HgymNetConfig* net);
+/* byte offset inside the workspace of the derived sigma block (16 floats, the first num_actions in use) with HGYM_STD_LOG; -1 with
+ * HGYM_STD_SCALAR (sigma is params[0 .. num_actions) then); -2 for a configuration the library refuses (hgym_last_error says why) */
+int64_t hgym_net_sigma_offset(const HgymNetConfig* net);
 
 /* Master parameters are ONE flat fp32 array in state_dict order
- * (std, actor.{0,2,4,6}.{weight,bias}, critic.{0,2,4,6}.{weight,bias}; SURVEY.md §5 checkpoint row);
+ * (std, actor.{0,2,4,6}.{weight,bias}, critic.{0,2,4,6}.{weight,bias}; SURVEY.md §5 checkpoint row; with HgymNetConfig.std_param =
+ * HGYM_STD_LOG the first num_actions slots are log_std = log sigma, same place, same count);
  * grads/adam_m/adam_v have the same layout.  opt_state: 16 doubles on the device (HGYM_OPT_* below, one name per slot)
  * [0] learning rate (python-double semantics of ppo.py:142-148)   [1] Adam step count
  * [2] sum of minibatch mean KL  [3] sum of surrogate losses  [4] sum of value losses  [5] sum of mean entropies
@@ -581,7 +607,7 @@ int32_t hgym_critic_values(const HgymNetConfig* cfg, const HgymNet* net, int64_t
                            const HgymObsShadow* shadow, void* stream);
 
 /* PPO.act (ppo.py:91-101): mu = actor(obs); sigma = std; a = mu + sigma*z; V = critic(priv);
- * logp = sum log N(a; mu, sigma).  z (M,12) standard normal draws or NULL -> Philox(seed, *step_counter).
+ * logp = sum log N(a; mu, sigma).  (HGYM_STD_LOG: std = exp(log_std), read from the derived block; the `sigma` output is sigma itself.)  z (M,12) standard normal draws or NULL -> Philox(seed, *step_counter).
  * Outputs row-major: actions/mu/sigma (M,12), logp (M,), values (M,). */
 int32_t hgym_policy_act(const HgymNetConfig* cfg, const HgymNet* net, int32_t M, const float* obs,
                         const float* priv, const float* z, uint64_t seed, const int64_t* step_counter,
@@ -744,7 +770,8 @@ int64_t hgym_net_param_offset(const HgymNetConfig* cfg, int32_t which);
  *
  * hgym_ppo_diag_reduce is the reduction alone over M rows: actions / mu_old / sigma_old / mu_new (M, 12) fp32 row-major, 16-byte
  * aligned; logp_old / values_old / returns / advantages / values_new (M,) fp32; std = the 12 current standard deviations (the head of
- * HgymNet.params).  Per row, in fp32:
+ * HgymNet.params; with HGYM_STD_LOG the derived block at hgym_net_sigma_offset, NOT the parameters: `std` is always sigma, never its
+ * logarithm -- hgym_ppo_diagnostics passes the right one itself).  Per row, in fp32:
  *     logp_new  = sum_j -(a_j - mu_new_j)^2 / (2 std_j^2) - log std_j - log sqrt(2 pi)       ratio = expf(logp_new - logp_old)
  *     kl        = sum_j log(std_j / sigma_old_j) + (sigma_old_j^2 + (mu_old_j - mu_new_j)^2) / (2 std_j^2) - 1/2     (old || new, exact;
  *                 the learning-rate rule's expression, ppo.py:138-139, has + 1e-5 inside the logarithm: 1.2e-4 for a policy that did
