@@ -18,6 +18,7 @@ PRIV_FRAME = 73
 MAX_LAYERS = 8
 MAX_CUSTOM_REWARDS = 24
 F32, BF16 = 0, 1
+MIRROR_MAX_WIDTH = 2048     # HGYM_MIRROR_MAX_WIDTH
 ACT_ELU, ACT_SELU, ACT_LEAKY_RELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3, 4    # HGYM_ACT_*
 STD_SCALAR, STD_LOG = 0, 1    # HGYM_STD_*: params[:A] hold sigma / log sigma (HgymNetConfig.std_param)
 
@@ -185,6 +186,8 @@ SYMBOLS = {
     "hgym_adv_normalize": (C.c_int32, [C.c_int64, c_float_p, c_f64_p, C.c_void_p]),
     "hgym_gae_bootstrap": (C.c_int32, [C.c_int32, C.c_int32, c_float_p, c_float_p, c_u8_p, c_u8_p, c_float_p, C.c_float, C.c_float,
                                        c_float_p, c_float_p, c_f64_p, C.c_void_p]),
+    "hgym_mirror_rows": (C.c_int32, [C.c_int64, C.c_int32, C.POINTER(C.c_int32), c_float_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32,
+                                     C.c_int32, C.c_void_p]),
     "hgym_critic_values": (C.c_int32, [_P(NetConfig), _P(Net), C.c_int64, c_float_p, c_float_p, _P(ObsShadow), C.c_void_p]),
     "hgym_net_param_count": (C.c_int64, [_P(NetConfig)]),
     "hgym_net_workspace_bytes": (C.c_int64, [_P(NetConfig)]),

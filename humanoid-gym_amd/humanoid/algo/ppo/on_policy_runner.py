@@ -188,6 +188,13 @@ class _EpisodeLog:
         return tuple(deque((float(ring[j, s]) for s in slots), maxlen=self.RING) for j in (0, 1))
 
 
+def _split_algorithm_cfg(alg_cfg):
+    """The train config's algorithm block -> (keyword arguments of PPO.__init__, symmetry on?).  `symmetry` is a native key (absent:
+    off), not a parameter of the reference's PPO: it is taken out here and becomes PPO.symmetry."""
+    kwargs = dict(alg_cfg)
+    return kwargs, bool(kwargs.pop("symmetry", False))
+
+
 class OnPolicyRunner:
     def __init__(self, env: VecEnv, train_cfg, log_dir=None, device="cpu"):
         self.cfg = train_cfg["runner"]
@@ -202,7 +209,11 @@ class OnPolicyRunner:
         actor_critic_class = eval(self.cfg["policy_class_name"])  # ActorCritic
         actor_critic = actor_critic_class(self.env.num_obs, num_critic_obs, self.env.num_actions, **self.policy_cfg).to(self.device)
         alg_class = eval(self.cfg["algorithm_class_name"])  # PPO
-        self.alg = alg_class(actor_critic, device=self.device, **self.alg_cfg)
+        alg_kwargs, symmetry = _split_algorithm_cfg(self.alg_cfg)
+        self.alg = alg_class(actor_critic, device=self.device, **alg_kwargs)
+        if symmetry:        # left-right augmentation with XBot-L's tables; read by init_storage below
+            from humanoid.utils.symmetry import xbot_l_mirror
+            self.alg.symmetry = xbot_l_mirror(self.env.cfg)
         self.num_steps_per_env = self.cfg["num_steps_per_env"]
         self.save_interval = self.cfg["save_interval"]
         self.alg.init_storage(self.env.num_envs, self.num_steps_per_env, [self.env.num_obs], [self.env.num_privileged_obs],

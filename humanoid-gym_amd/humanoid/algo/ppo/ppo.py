@@ -68,6 +68,11 @@ class PPO:
     permutation = "device"
     # compute precision of the dense layers: "bf16" (MFMA fast path, BASELINE config) or "f32" (parity mode)
     precision = os.environ.get("HGYM_PRECISION", "bf16")
+    # left-right symmetry augmentation: None, or a humanoid.utils.symmetry.MirrorSpec -- the update then also trains on the mirrored
+    # transition of every stored row (RolloutStorage.enable_mirror / mirror), minibatches twice as large, as many Adam steps.  Read once,
+    # in init_storage.  The adaptive learning-rate rule's KL is the fused loss's mean over the WHOLE minibatch, mirrored rows included
+    # (rsl_rl averages it over the original rows only): it also sees the policy's asymmetry.  DESIGN.md section 21.
+    symmetry = None
 
     def __init__(self, actor_critic, num_learning_epochs=1, num_mini_batches=1, clip_param=0.2, gamma=0.998, lam=0.95,
                  value_loss_coef=1.0, entropy_coef=0.0, learning_rate=1e-3, max_grad_norm=1.0, use_clipped_value_loss=True,
@@ -115,8 +120,11 @@ class PPO:
         import hgym
         self._hgym = hgym
         self.storage = RolloutStorage(num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape, self.device)
+        self._symmetry = self.symmetry
+        if self._symmetry is not None:
+            self.storage.enable_mirror(self._symmetry)      # (before enable_shadow and before anything binds a slot's address)
         ac = self.actor_critic
-        mb = (num_envs * num_transitions_per_env) // self.num_mini_batches
+        mb = ((2 if self._symmetry is not None else 1) * num_envs * num_transitions_per_env) // self.num_mini_batches
         aux = getattr(ac, "denoiser_hidden_dims", None)
         cfg = hgym.make_net_config(ac.num_actor_obs, ac.num_critic_obs, ac.num_actions, ac.actor_hidden_dims, ac.critic_hidden_dims,
                                    self.precision, max(mb, num_envs), aux_hidden=aux, aux_out=getattr(ac, "denoiser_targets", 0),
@@ -328,7 +336,8 @@ class PPO:
         return (bytes(C.string_at(C.addressof(self._ppo_cfg), C.sizeof(self._ppo_cfg))), self.num_learning_epochs, self.num_mini_batches,
                 float(self.gamma), float(self.lam), self.permutation, self._perm_seed, id(self.storage), id(self.net),
                 bool(dist_utils.active()), bool(self._comm_p2p), bytes(C.string_at(C.addressof(self.net.cfg), C.sizeof(self.net.cfg))),
-                self.storage._obs_bf16 is not None, bool(self.comm_flip), self._world)
+                self.storage._obs_bf16 is not None, bool(self.comm_flip), self._world,
+                None if self._symmetry is None else self._symmetry.key())
 
     def after_rollout_replay(self, shadow_valid, deferred):
         """Host-side book-keeping of one replayed rollout: a full storage, the shadow slots the capture wrote, deferred_values() if deferred."""
@@ -357,7 +366,10 @@ class PPO:
         (None, None), so the host can already enqueue the next rollout while this update runs."""
         hgym, net, st = self._hgym, self.net, self.storage
         T, N = st.num_transitions_per_env, st.num_envs
-        batch = T * N
+        sym = self._symmetry is not None
+        if sym:
+            st.mirror()      # the mirrored half of every column, from the finished rollout (returns, advantages, values, shadows: all there)
+        batch = (2 if sym else 1) * T * N
         mb = batch // self.num_mini_batches
         # one permutation for every epoch (rollout_storage.py:149,165-170)
         if self.permutation == "device":
@@ -373,12 +385,10 @@ class PPO:
             perm = st.permutation(self.num_mini_batches * mb, self._perm_seed, self._perm_draws_dev)
         else:
             perm = torch.randperm(self.num_mini_batches * mb, device=self.device)
-        fl = lambda t: t.flatten(0, 1)
-        obs = fl(st.observations)
-        priv = fl(st.privileged_observations) if st.privileged_observations is not None else obs
-        cols = (obs, priv, fl(st.actions), st.values.view(-1), st.advantages.view(-1), st.returns.view(-1),
-                st.actions_log_prob.view(-1), fl(st.mu), fl(st.sigma))
-        sh = st.shadows() if hasattr(st, "shadows") else None
+        if sym:
+            perm = st.mirror_index(perm)      # drawn over 2 T N rows; the mirrored half lies behind the bootstrap slot
+        cols = st.batch_columns()
+        sh = st.shadows(mirrored=sym)
         if sh is not None and self._check_shadow:
             st.check_shadows()
         sh = dict(obs_bf16=sh[0], priv_bf16=sh[1]) if sh is not None else {}

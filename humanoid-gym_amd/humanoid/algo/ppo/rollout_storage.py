@@ -58,6 +58,8 @@ class RolloutStorage:
         self.shadow_valid = [False] * T
         # deferred values (enable_deferred_values): the bootstrap flags of every step + the value of the bootstrap observation
         self.time_outs = self.last_values = None
+        # left-right mirrored half (enable_mirror): the device tables, None without it
+        self._mirror = None
 
     def enable_shadow(self, ld_obs, ld_priv):
         """Native extension: allocate (T, N, ld) bfloat16 copies of `observations` / `privileged_observations` (ld = the widths
@@ -65,9 +67,101 @@ class RolloutStorage:
         if self._priv_all is None or ld_obs <= 0 or ld_priv <= 0:
             return False
         T, N = self.num_transitions_per_env, self.num_envs
-        self._obs_bf16 = torch.zeros(T, N, int(ld_obs), dtype=torch.bfloat16, device=self.device)
-        self._priv_bf16 = torch.zeros(T, N, int(ld_priv), dtype=torch.bfloat16, device=self.device)
+        slots = T if self._mirror is None else 2 * T + 1       # (enable_mirror: the same slot layout as every mirrored column)
+        self._obs_bf16_store = torch.zeros(slots, N, int(ld_obs), dtype=torch.bfloat16, device=self.device)
+        self._priv_bf16_store = torch.zeros(slots, N, int(ld_priv), dtype=torch.bfloat16, device=self.device)
+        self._obs_bf16, self._priv_bf16 = self._obs_bf16_store[:T], self._priv_bf16_store[:T]
         return True
+
+    # ------------------------------------------------------------------ left-right symmetry augmentation
+    MIRRORED = ("actions", "mu", "sigma", "values", "returns", "advantages", "actions_log_prob")
+
+    def enable_mirror(self, spec):
+        """Native extension (PPO.symmetry): room for the left-right mirrored transition of every stored row, in every column the update
+        gathers -- observations and privileged observations (fp32 and, with enable_shadow, the bf16 shadows), actions, mu, sigma, values,
+        returns, advantages, actions_log_prob.  spec: a humanoid.utils.symmetry.MirrorSpec whose table widths are this storage's.
+
+        Addressing: each of those columns becomes ONE allocation of 2 T + 1 slots of N rows -- slots 0 .. T - 1 the rollout (what the
+        attributes of the same names keep showing, shapes unchanged), slot T the bootstrap observation (unused in the other columns),
+        slots T + 1 .. 2 T the mirrored rollout.  The update still gets one base pointer per column and one index slice: row r < T N is
+        row r, mirrored row T N + r is row (T + 1) N + r (mirror_index).  Call it before anything binds the slots' addresses."""
+        if self._priv_all is None:
+            raise ValueError("enable_mirror needs privileged observations (the update's critic rows)")
+        widths = (self.obs_shape[0], self.privileged_obs_shape[0], self.actions_shape[0])
+        if (len(spec.obs_src), len(spec.priv_src), len(spec.act_src)) != widths:
+            raise ValueError("MirrorSpec tables are %d / %d / %d wide, the storage's rows %d / %d / %d"
+                             % ((len(spec.obs_src), len(spec.priv_src), len(spec.act_src)) + widths))
+        T, N = self.num_transitions_per_env, self.num_envs
+
+        def grow(t, keep):      # (keep leading slots of t) -> a zero-filled (2 T + 1)-slot allocation holding them
+            g = torch.zeros(2 * T + 1, *t.shape[1:], dtype=t.dtype, device=self.device)
+            g[:keep].copy_(t[:keep])
+            return g
+        self._obs_store, self._priv_store = grow(self._obs_all, T + 1), grow(self._priv_all, T + 1)
+        self._obs_all, self._priv_all = self._obs_store[:T + 1], self._priv_store[:T + 1]
+        self.observations, self.privileged_observations = self._obs_store[:T], self._priv_store[:T]
+        self._col_store = {}
+        for name in self.MIRRORED:
+            self._col_store[name] = grow(getattr(self, name), T)
+            setattr(self, name, self._col_store[name][:T])
+        dev = lambda v, dt: torch.tensor(v, dtype=dt, device=self.device)
+        self._mirror = dict(spec=spec, obs=(dev(spec.obs_src, torch.int32), dev(spec.obs_sign, torch.float32)),
+                            priv=(dev(spec.priv_src, torch.int32), dev(spec.priv_sign, torch.float32)),
+                            act=(dev(spec.act_src, torch.int32), dev(spec.act_sign, torch.float32)),
+                            sigma=(dev(spec.act_src, torch.int32), torch.ones(len(spec.act_src), dtype=torch.float32, device=self.device)),
+                            hi=torch.empty(0, dtype=torch.bool, device=self.device))
+        if self._obs_bf16 is not None:      # shadows allocated before: the same layout for them
+            self.enable_shadow(self._obs_bf16.shape[2], self._priv_bf16.shape[2])
+            self.shadow_valid = [False] * T
+        return True
+
+    @property
+    def mirrored(self):
+        return self._mirror is not None
+
+    def mirror(self):
+        """Fill the mirrored half from the current rollout (after compute_returns, and after the deferred critic wrote values and the
+        privileged shadow): hgym_mirror_rows per tensor, device copies for the four scalar columns, all on the current stream with
+        fixed arguments (capturable).  The T N original rows and slot T are only read.  The bf16 shadows are mirrored from the shadows
+        (a sign-bit flip commutes with the rounding), and only when every slot of them is valid -- otherwise the update does not read them."""
+        import hgym
+        m, T = self._mirror, self.num_transitions_per_env
+        fl = lambda t: t.flatten(0, 1)
+        hgym.mirror_rows(fl(self._obs_store[:T]), fl(self._obs_store[T + 1:]), *m["obs"])
+        hgym.mirror_rows(fl(self._priv_store[:T]), fl(self._priv_store[T + 1:]), *m["priv"])
+        for name, table in (("actions", "act"), ("mu", "act"), ("sigma", "sigma")):
+            c = self._col_store[name]
+            hgym.mirror_rows(fl(c[:T]), fl(c[T + 1:]), *m[table])
+        if self.shadows() is not None:
+            for store, table in ((self._obs_bf16_store, "obs"), (self._priv_bf16_store, "priv")):
+                hgym.mirror_rows(fl(store[:T]), fl(store[T + 1:]), *m[table], zero_to=store.shape[2])
+        for name in ("values", "returns", "advantages", "actions_log_prob"):
+            c = self._col_store[name]
+            c[T + 1:].copy_(c[:T])
+
+    def mirror_index(self, perm):
+        """Row numbers of [0, 2 T N) -- T N + r is the mirror of row r -- to rows of the (2 T + 1)-slot columns, in place: the upper half
+        moves past slot T.  Two launches, no allocation after the first call."""
+        T, N, m = self.num_transitions_per_env, self.num_envs, self._mirror
+        with torch.inference_mode():
+            if m["hi"].shape != perm.shape:
+                m["hi"] = torch.empty(perm.shape, dtype=torch.bool, device=perm.device)
+            torch.ge(perm, T * N, out=m["hi"])
+            perm.add_(m["hi"], alpha=N)
+        return perm
+
+    def batch_columns(self):
+        """(obs, priv, actions, values, advantages, returns, actions_log_prob, mu, sigma) flattened as hgym.make_batch takes them: T N rows,
+        or all (2 T + 1) N rows of the enlarged columns with enable_mirror."""
+        fl = lambda t: t.flatten(0, 1)
+        if self._mirror is None:
+            obs = fl(self.observations)
+            priv = fl(self.privileged_observations) if self.privileged_observations is not None else obs
+            return (obs, priv, fl(self.actions), self.values.view(-1), self.advantages.view(-1), self.returns.view(-1),
+                    self.actions_log_prob.view(-1), fl(self.mu), fl(self.sigma))
+        c = self._col_store
+        return (fl(self._obs_store), fl(self._priv_store), fl(c["actions"]), c["values"].view(-1), c["advantages"].view(-1), c["returns"].view(-1),
+                c["actions_log_prob"].view(-1), fl(c["mu"]), fl(c["sigma"]))
 
     def enable_deferred_values(self):
         """Native extension: columns for a rollout whose critic runs ONCE after collection (PPO.deferred_values): time_outs (T, N, 1)
@@ -84,10 +178,13 @@ class RolloutStorage:
         self.shadow_valid[s] = True
         return self._obs_bf16[s], self._priv_bf16[s]
 
-    def shadows(self):
-        """The flattened (T*N, ld) shadows when every slot of the current rollout was written by its policy launch, else None."""
+    def shadows(self, mirrored=False):
+        """The flattened (T*N, ld) shadows when every slot of the current rollout was written by its policy launch, else None.
+        mirrored (enable_mirror): all (2 T + 1) N rows, laid out like batch_columns()."""
         if self._obs_bf16 is None or not all(self.shadow_valid):
             return None
+        if mirrored and self._mirror is not None:
+            return self._obs_bf16_store.flatten(0, 1), self._priv_bf16_store.flatten(0, 1)
         return self._obs_bf16.flatten(0, 1), self._priv_bf16.flatten(0, 1)
 
     # ------------------------------------------------------------------

@@ -59,7 +59,9 @@ extern "C" {
                              *    (same version, later: names for the slots of opt_state, log_stats and counters -- HGYM_OPT_*, HGYM_LOG_*,
                              *    HGYM_CNT_*; no layout changes)
                              *    (same version, later: HgymNetConfig.std_param added ahead of fused_activation -- the action noise trained as log sigma
-                             *    (HGYM_STD_LOG) -- and hgym_net_sigma_offset; a zero-filled field is the sigma parameter every earlier layout meant) */
+                             *    (HGYM_STD_LOG) -- and hgym_net_sigma_offset; a zero-filled field is the sigma parameter every earlier layout meant)
+                             *    (same version, later: hgym_mirror_rows -- the mirrored copy of stored rows for left-right symmetry augmentation;
+                             *    no layout changes) */
 
 enum {
     HGYM_OK = 0,
@@ -433,6 +435,22 @@ int32_t hgym_adv_normalize(int64_t count, float* advantages, const double* stats
  * hgym_store_step -- before the scan uses it, so that afterwards every storage column is what the per-step path leaves. */
 int32_t hgym_gae_bootstrap(int32_t T, int32_t n, float* rewards, const float* values, const uint8_t* dones, const uint8_t* time_outs,
                            const float* last_values, float gamma, float lam, float* returns, float* advantages, double* stats, void* stream);
+
+/* Left-right symmetry augmentation (header v9, no layout change; PPO.symmetry): the mirrored copy of M stored
+ * rows.  For every row m and c < width, dst[m * ld_dst + c] is the BIT PATTERN of src[m * ld_src + src_col[c]] with the sign bit inverted
+ * where sign[c] < 0 -- a flip, not a multiply, so the call is exact for every input (NaN payloads, denormals, +-0, +-inf) and the bf16
+ * mirror of a shadow row equals bf16(mirror(fp32 row)) bit for bit.  Columns [width, zero_to) of every dst row are written as +0 (the
+ * pad columns of a shadow; zero_to = width: none); columns [zero_to, ld_dst) are not touched.  dtype: HGYM_F32 (4-byte elements) or
+ * HGYM_BF16 (2-byte); ld_src / ld_dst in elements.  Rows need only be aligned to their element (705 floats are 2820 bytes); 16-byte
+ * accesses are used wherever the addresses allow.  src_col (width int32) and sign (width floats) are DEVICE arrays of the caller, read
+ * by the launch: the library cannot validate their contents (the Python layer does, humanoid/utils/symmetry.py: MirrorSpec); an entry
+ * outside [0, width) reads the row's last column.  The table need not be an involution.
+ * HGYM_E_BADARG, and nothing launched: a null pointer, M < 0, width < 1, ld_src or ld_dst < width, zero_to outside [width, ld_dst], a
+ * pointer not aligned to its element, an unknown dtype, or src and dst ranges that overlap.  HGYM_E_UNSUPPORTED: zero_to (hence width)
+ * > HGYM_MIRROR_MAX_WIDTH -- the kernel stages whole rows and the table in LDS -- or M > 2^40, ld > 2^20.  M = 0: HGYM_OK, no launch. */
+#define HGYM_MIRROR_MAX_WIDTH 2048
+int32_t hgym_mirror_rows(int64_t M, int32_t width, const int32_t* src_col, const float* sign, const void* src, int64_t ld_src, void* dst,
+                         int64_t ld_dst, int32_t zero_to, int32_t dtype /* HGYM_F32 | HGYM_BF16 */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Actor / critic (algo/ppo/actor_critic.py) and PPO update (algo/ppo/ppo.py:119-184)
