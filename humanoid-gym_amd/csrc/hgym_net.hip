@@ -16,6 +16,7 @@
 
 #include "hgym_gemm.hpp"
 #include "hgym_fused.hpp"
+#include "hgym_norm.hpp"
 
 namespace hgym {
 
@@ -516,6 +517,12 @@ struct SegTable {
     int n;
     Segment s[2 * HGYM_MAX_LAYERS * 2 + 1];
 };
+// Observation normalisation (HgymNet.norm, hgym_norm.hip): per segment of a table, the per-column scale its operand copies carry -- T(w * cs[c])
+// instead of T(w) -- for the first-layer weight segments, null for every other.  An argument of adam_norm_kernel / sync_shadow_norm_kernel only: a
+// net without normalisation launches adam_kernel / sync_shadow_kernel with the arguments they always had.
+struct NormCols {
+    const float* cs[2 * HGYM_MAX_LAYERS * 2 + 1];
+};
 
 // Also accumulates the squared norm of the finished gradient into opt[HGYM_OPT_GRAD_SQNORM] (zeroed by ppo_scalars_kernel earlier in the same
 // hgym_ppo_grad): with one rank that IS the norm clip_grad_norm_ needs, and hgym_ppo_apply skips its own pass over the
@@ -672,11 +679,12 @@ __device__ __forceinline__ void write_shadows(const Segment& sg, int r, int c, f
     }
 }
 
+// One body for adam_kernel and its twin for a normalised net.  colscale: null, or -- a first-layer weight segment of a normalised net (HgymNet.norm,
+// hgym_norm.hip) -- the per-column scale its operand copies carry, T(w * colscale[c]) instead of T(w).  adam_kernel passes a literal null, which
+// folds: it keeps the arguments and the code it had before the feature existed.
 template <typename T>
-__global__ __launch_bounds__(256) void adam_kernel(const SegTable tab, const HgymPPOConfig p, float* __restrict__ params,
-                                                   float* __restrict__ grads, float* __restrict__ m_, float* __restrict__ v_,
-                                                   float inv_w, double* __restrict__ opt) {
-    const Segment& sg = tab.s[blockIdx.y];
+__device__ __forceinline__ void adam_body(const Segment& sg, const HgymPPOConfig& p, float* params, float* grads, float* m_, float* v_, float inv_w,
+                                          double* opt, const float* colscale) {
     const int64_t n = (int64_t)sg.rows * sg.cols;
     // nn.utils.clip_grad_norm_: coef = max_norm / (total_norm + 1e-6), clamped to 1 (fp32 tensor arithmetic)
     const float total = (float)sqrt(opt[HGYM_OPT_GRAD_SQNORM]);
@@ -703,7 +711,7 @@ __global__ __launch_bounds__(256) void adam_kernel(const SegTable tab, const Hgy
         const float w = adam1(sg.off + i);
         if (sg.Wp || sg.Wf) {
             const int r = (int)(i / sg.cols), c = (int)(i - (int64_t)r * sg.cols);
-            write_shadows<T>(sg, r, c, w);
+            write_shadows<T>(sg, r, c, colscale ? w * colscale[c] : w);
         } else if (sg.sigma) {
             sg.sigma[i] = sigma_of(w);      // same launch: a captured update keeps the block current without a node of its own
         }
@@ -711,8 +719,20 @@ __global__ __launch_bounds__(256) void adam_kernel(const SegTable tab, const Hgy
 }
 
 template <typename T>
-__global__ __launch_bounds__(256) void sync_shadow_kernel(const SegTable tab, const float* __restrict__ params) {
-    const Segment& sg = tab.s[blockIdx.y];
+__global__ __launch_bounds__(256) void adam_kernel(const SegTable tab, const HgymPPOConfig p, float* __restrict__ params,
+                                                   float* __restrict__ grads, float* __restrict__ m_, float* __restrict__ v_,
+                                                   float inv_w, double* __restrict__ opt) {
+    adam_body<T>(tab.s[blockIdx.y], p, params, grads, m_, v_, inv_w, opt, nullptr);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void adam_norm_kernel(const SegTable tab, const HgymPPOConfig p, float* __restrict__ params,
+                                                        float* __restrict__ grads, float* __restrict__ m_, float* __restrict__ v_,
+                                                        float inv_w, double* __restrict__ opt, const NormCols nc) {
+    adam_body<T>(tab.s[blockIdx.y], p, params, grads, m_, v_, inv_w, opt, nc.cs[blockIdx.y]);
+}
+
+template <typename T>
+__device__ __forceinline__ void sync_shadow_body(const Segment& sg, const float* params, const float* colscale) {
     if (sg.sigma)       // (ahead of the early return: the std segment has no operand copy, but in log mode it has this one)
         for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (int64_t)sg.rows * sg.cols; i += (int64_t)gridDim.x * blockDim.x)
             sg.sigma[i] = sigma_of(params[sg.off + i]);
@@ -720,8 +740,17 @@ __global__ __launch_bounds__(256) void sync_shadow_kernel(const SegTable tab, co
     const int64_t n = (int64_t)sg.rows * sg.cols;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const int r = (int)(i / sg.cols), c = (int)(i - (int64_t)r * sg.cols);
-        write_shadows<T>(sg, r, c, params[sg.off + i]);
+        write_shadows<T>(sg, r, c, colscale ? params[sg.off + i] * colscale[c] : params[sg.off + i]);
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void sync_shadow_kernel(const SegTable tab, const float* __restrict__ params) {
+    sync_shadow_body<T>(tab.s[blockIdx.y], params, nullptr);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void sync_shadow_norm_kernel(const SegTable tab, const float* __restrict__ params, const NormCols nc) {
+    sync_shadow_body<T>(tab.s[blockIdx.y], params, nc.cs[blockIdx.y]);
 }
 
 // ------------------------------------------------------------------------------------------------ GEMM dispatch
@@ -801,7 +830,14 @@ struct NetBase {
     hipStream_t s;
     char* ws;
 
+    NormLayout nl;           // observation normalisation (net.norm set): the block's layout, else zero
     template <typename U> U* at(int64_t off) const { return reinterpret_cast<U*>(ws + off); }
+    template <typename U> U* norm_at(int64_t off) const { return reinterpret_cast<U*>((char*)net.norm + off); }
+    // The bias the kernels add behind layer l of net `which`: the parameter, or -- first layer of a normalised net -- the effective bias
+    // b - (W o s) m that norm_fold_bias keeps in the block.  Every site that hands a bias to a kernel goes through here.
+    const float* bias_in(int which, int l) const {
+        return (l == 0 && net.norm) ? norm_at<float>(nl.eb[which]) : net.params + w.net[which].layer[l].b_off;
+    }
     const float* sigma_in() const { return sigma_src(w, net); }
     // ScalArgs::sigma: the chain-rule factor of the std gradient (log mode), null where the gradient is sigma's own
     const float* grad_sigma() const { return w.sigma >= 0 ? sigma_in() : nullptr; }
@@ -872,9 +908,22 @@ struct NetBase {
         return t;
     }
 
+    // The scale pointers that go with segments(): the table's order -- std, then weight | bias of every layer of every net
+    NormCols norm_cols() const {
+        NormCols nc;
+        memset(&nc, 0, sizeof(nc));
+        int i = 1;
+        for (int which = 0; which < w.nnets; ++which)
+            for (int l = 0; l < w.net[which].L; ++l, i += 2)
+                if (l == 0 && net.norm) nc.cs[i] = norm_at<float>(nl.sf[which == 1 ? 1 : 0]);
+        return nc;
+    }
+
     // prologue_done: the gradient call has already taken the learning-rate decision and Adam's step scalars (FusedPath::prologue_in_grad)
     template <typename T>
     int32_t apply(const HgymPPOConfig& ppo, bool prologue_done) {
+        HG_REQUIRE(!net.norm || !ppo.grad_norm_ready, HGYM_E_BADARG,
+                   "HgymPPOConfig.grad_norm_ready = 1 with HgymNet.norm set: hgym_net_norm_unfold_grad changes the gradient behind hgym_ppo_grad");
         prof_begin(HGYM_PROF_APPLY, s);
         const float inv_w = ppo.world_size > 1 ? (float)(1.0 / (double)ppo.world_size) : 1.0f;
         if (ppo.world_size > 1 || !ppo.grad_norm_ready)        // else: reduce_slabs_kernel left the squared norm in opt[HGYM_OPT_GRAD_SQNORM]
@@ -885,19 +934,44 @@ struct NetBase {
         const SegTable tab = segments(0);
         // 256 workgroups per segment: the two first-layer matrices hold 57 % of the parameters, and 64 workgroups (a quarter of
         // the CUs) walked them in 22 dependent load -> store rounds per lane (30.7 us; 18.1 us with 256, 20.8 us with 512)
-        hipLaunchKernelGGL((adam_kernel<T>), dim3(256, tab.n), dim3(256), 0, s, tab, ppo, net.params, net.grads, net.adam_m, net.adam_v,
-                           inv_w, net.opt_state);
+        if (net.norm)
+            hipLaunchKernelGGL((adam_norm_kernel<T>), dim3(256, tab.n), dim3(256), 0, s, tab, ppo, net.params, net.grads, net.adam_m, net.adam_v,
+                               inv_w, net.opt_state, norm_cols());
+        else
+            hipLaunchKernelGGL((adam_kernel<T>), dim3(256, tab.n), dim3(256), 0, s, tab, ppo, net.params, net.grads, net.adam_m, net.adam_v,
+                               inv_w, net.opt_state);
         prof_end(HGYM_PROF_APPLY, s, (double)w.P * 36.0);
         HG_CHECK_LAUNCH("adam_kernel");
-        return HGYM_OK;
+        return net.norm ? norm_fold_bias(&cfg, &net, s) : HGYM_OK;      // the first-layer weights moved: their effective biases follow
     }
 
     template <typename T>
     int32_t sync_shadow() {
         const SegTable tab = segments(0);
-        hipLaunchKernelGGL((sync_shadow_kernel<T>), dim3(64, tab.n), dim3(256), 0, s, tab, net.params);
+        if (net.norm) hipLaunchKernelGGL((sync_shadow_norm_kernel<T>), dim3(64, tab.n), dim3(256), 0, s, tab, net.params, norm_cols());
+        else hipLaunchKernelGGL((sync_shadow_kernel<T>), dim3(64, tab.n), dim3(256), 0, s, tab, net.params);
         HG_CHECK_LAUNCH("sync_shadow_kernel");
-        return HGYM_OK;
+        return net.norm ? norm_fold_bias(&cfg, &net, s) : HGYM_OK;
+    }
+
+    // Observation normalisation, after the statistics moved: the operand copies of the first-layer weights (the only ones that hold the
+    // scale) and the effective biases.
+    template <typename T>
+    int32_t norm_refold() {
+        const SegTable all = segments(0);
+        const NormCols cols = norm_cols();
+        SegTable tab;
+        NormCols nc;
+        memset(&tab, 0, sizeof(tab));
+        memset(&nc, 0, sizeof(nc));
+        for (int i = 0; i < all.n; ++i)
+            if (cols.cs[i]) {
+                nc.cs[tab.n] = cols.cs[i];
+                tab.s[tab.n++] = all.s[i];
+            }
+        hipLaunchKernelGGL((sync_shadow_norm_kernel<T>), dim3(64, tab.n), dim3(256), 0, s, tab, net.params, nc);
+        HG_CHECK_LAUNCH("sync_shadow_norm_kernel");
+        return norm_fold_bias(&cfg, &net, s);
     }
 };
 
@@ -933,7 +1007,7 @@ struct GemmPath : NetBase {
             g.M = M;
             g.N = y.N;
             g.K = y.Kp;
-            g.bias = net.params + y.b_off;
+            g.bias = bias_in(which, l);
             if (last) {
                 g.Cf = y_out;
                 g.ldcf = ld_out;
@@ -1116,6 +1190,7 @@ struct GemmPath : NetBase {
 
     int32_t apply(const HgymPPOConfig& ppo) { return NetBase::apply<T>(ppo, false); }
     int32_t sync_shadow() { return NetBase::sync_shadow<T>(); }
+    int32_t norm_refold() { return NetBase::norm_refold<T>(); }
 };
 
 // The fused bf16 path (hgym_fused.hpp): the actor and the critic, and the auxiliary head when it has the fused layout too, through
@@ -1138,7 +1213,7 @@ struct FusedPath : NetBase {
             FusedLayer& d = f.layer[l];
             d.Wf = at<u32x4>(y.Wf);
             d.WTf = at<u32x4>(y.WTf);
-            d.bias = net.params + y.b_off;
+            d.bias = bias_in(which, l);
             d.K = y.K;
             d.N = y.N;
             d.KB = y.KBf;
@@ -1436,6 +1511,7 @@ struct FusedPath : NetBase {
 
     int32_t apply(const HgymPPOConfig& ppo) { return NetBase::apply<__bf16>(ppo, prologue_in_grad(ppo)); }
     int32_t sync_shadow() { return NetBase::sync_shadow<__bf16>(); }
+    int32_t norm_refold() { return NetBase::norm_refold<__bf16>(); }
 };
 
 static int32_t check_net(const HgymNetConfig* cfg, const HgymNet* net, WsLayout* w) {
@@ -1444,7 +1520,14 @@ static int32_t check_net(const HgymNetConfig* cfg, const HgymNet* net, WsLayout*
     if (rc) return rc;
     HG_REQUIRE(net->params && net->workspace, HGYM_E_BADARG, "null params / workspace");
     HG_REQUIRE(((uintptr_t)net->workspace & 255) == 0, HGYM_E_BADARG, "workspace must be 256-byte aligned");
+    HG_REQUIRE(((uintptr_t)net->norm & 255) == 0, HGYM_E_BADARG, "HgymNet.norm must be 256-byte aligned");
     return HGYM_OK;
+}
+
+static NetBase net_base(const HgymNetConfig* cfg, const HgymNet* net, const WsLayout& w, hipStream_t s) {
+    NetBase b{*cfg, *net, w, s, (char*)net->workspace, {}};
+    if (net->norm) norm_layout(cfg, &b.nl);
+    return b;
 }
 
 static int32_t check_ppo(const HgymPPOConfig* ppo) {
@@ -1469,7 +1552,7 @@ static int32_t run(const HgymNetConfig* cfg, const HgymNet* net, void* stream, F
     WsLayout w;
     const int32_t rc = check_net(cfg, net, &w);
     if (rc) return rc;
-    const NetBase b{*cfg, *net, w, (hipStream_t)stream, (char*)net->workspace};
+    const NetBase b = net_base(cfg, net, w, (hipStream_t)stream);
     if (w.net[0].fused) {
         FusedPath R(b);
         return f(R);
@@ -1498,7 +1581,7 @@ int32_t rollout_fwd_args(const HgymNetConfig* cfg, const HgymNet* net, int M, co
                "fused rollout step: first hidden widths 512 / 768 (XBot-L) only, not %d / %d", cfg->actor_dims[1], cfg->critic_dims[1]);
     rc = check_shadow(w, sh);
     if (rc) return rc;
-    const FusedPath R(NetBase{*cfg, *net, w, nullptr, (char*)net->workspace});
+    const FusedPath R(net_base(cfg, net, w, nullptr));
     const NetIO io[3] = {{obs, cfg->num_obs, mu, cfg->num_actions}, {priv, cfg->num_priv, values, 1}, {}};
     const FusedPath::SampleOut smp = {nullptr, seed, step, actions, sigma, logp};
     *out = R.make_fwd_args(0, 2, M, io, nullptr, false, &smp, nullptr, sh);
@@ -1517,7 +1600,7 @@ int32_t rollout_eval_fwd_args(const HgymNetConfig* cfg, const HgymNet* net, int 
     HG_REQUIRE(M > 0 && M <= w.maxM, HGYM_E_SHAPE, "batch %d exceeds max_batch %lld", M, (long long)w.maxM);
     HG_REQUIRE(cfg->actor_dims[1] == 512, HGYM_E_UNSUPPORTED, "fused evaluation step: first hidden width 512 (XBot-L) only, not %d",
                cfg->actor_dims[1]);
-    const FusedPath R(NetBase{*cfg, *net, w, nullptr, (char*)net->workspace});
+    const FusedPath R(net_base(cfg, net, w, nullptr));
     const NetIO io[3] = {{obs, cfg->num_obs, actions, cfg->num_actions}, {}, {}};
     *out = R.make_fwd_args(0, 1, M, io, nullptr, false, nullptr, nullptr, nullptr);
     out->nets = 1;
@@ -1532,6 +1615,20 @@ int32_t net_sigma_src(const HgymNetConfig* cfg, const HgymNet* net, const float*
     if (rc) return rc;
     *out = sigma_src(w, *net);
     return HGYM_OK;
+}
+
+// For hgym_norm.hip: the first layers of the nets in the flat parameter vector, behind the configuration check.
+int32_t net_first_layers(const HgymNetConfig* cfg, NormFirst out[3], int* nnets) {
+    WsLayout w;
+    const int32_t rc = ws_layout(cfg, &w);
+    if (rc) return rc;
+    for (int i = 0; i < w.nnets; ++i) out[i] = NormFirst{w.net[i].layer[0].w_off, w.net[i].layer[0].b_off, w.net[i].layer[0].N, w.net[i].layer[0].K};
+    *nnets = w.nnets;
+    return HGYM_OK;
+}
+
+int32_t net_norm_refold(const HgymNetConfig* cfg, const HgymNet* net, void* stream) {
+    return run(cfg, net, stream, [](auto& R) { return R.norm_refold(); });
 }
 
 }  // namespace hgym

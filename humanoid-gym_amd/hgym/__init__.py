@@ -3,6 +3,7 @@ from . import _lib
 from ._lib import lib, check, HgymError
 from .env_buffers import EnvBuffers, default_env_config, log_stats_summary
 from .net import NetBuffers, make_net_config, make_ppo_config, make_batch, activation_spec, diag_from_block, DIAG_KEYS, opt_summary
+from .net import check_obs_norm, norm_layout
 
 
 def mirror_rows(src, dst, src_col, sign, zero_to=None):

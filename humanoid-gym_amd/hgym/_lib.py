@@ -125,7 +125,7 @@ class PPOConfig(C.Structure):
 
 class Net(C.Structure):
     _fields_ = [("params", c_float_p), ("grads", c_float_p), ("adam_m", c_float_p), ("adam_v", c_float_p),
-                ("opt_state", c_f64_p), ("workspace", C.c_void_p)]
+                ("opt_state", c_f64_p), ("workspace", C.c_void_p), ("norm", C.c_void_p)]
 
 
 class Comm(C.Structure):
@@ -193,6 +193,11 @@ SYMBOLS = {
     "hgym_net_workspace_bytes": (C.c_int64, [_P(NetConfig)]),
     "hgym_net_sigma_offset": (C.c_int64, [_P(NetConfig)]),
     "hgym_net_sync_shadow": (C.c_int32, [_P(NetConfig), _P(Net), C.c_void_p]),
+    "hgym_net_norm_layout": (C.c_int32, [_P(NetConfig), c_i64_p]),
+    "hgym_net_norm_init": (C.c_int32, [_P(NetConfig), _P(Net), C.c_float, C.c_int64, C.c_void_p]),
+    "hgym_net_norm_accumulate": (C.c_int32, [_P(NetConfig), _P(Net), c_float_p, c_float_p, C.c_int64, C.c_void_p]),
+    "hgym_net_norm_merge": (C.c_int32, [_P(NetConfig), _P(Net), C.c_void_p]),
+    "hgym_net_norm_unfold_grad": (C.c_int32, [_P(NetConfig), _P(Net), C.c_void_p]),
     "hgym_mlp_forward": (C.c_int32, [_P(NetConfig), _P(Net), C.c_int32, C.c_int32, c_float_p, C.c_int64, c_float_p, C.c_void_p]),
     "hgym_net_shadow_ld": (C.c_int64, [_P(NetConfig), C.c_int32]),
     "hgym_policy_act": (C.c_int32, [_P(NetConfig), _P(Net), C.c_int32, c_float_p, c_float_p, c_float_p, C.c_uint64, c_i64_p,
@@ -235,6 +240,11 @@ LOG_TERMS, LOG_STEPS, LOG_CLEAR, LOG_RING_HEAD, LOG_RING_FILL = 0, 22, 23, 24, 2
 LOG_RING, LOG_RETURNS, LOG_LENGTHS = 100, 32, 132
 # HgymEnvState.counters (HGYM_CNT_*)
 CNT_STEP, CNT_RESETS, CNT_RING, CNT_RESET_CALL = range(4)
+# hgym_net_norm_layout (HGYM_NORM_*): slots of the layout array; +k: 0 actor / obs, 1 critic / priv (BIAS: + net)
+NORM_LAYOUT = 24
+(NORM_BYTES, NORM_HEADER, NORM_MEAN, NORM_VAR, NORM_MEAN_F, NORM_SCALE_F, NORM_BIAS, NORM_SUMS, NORM_SUMS_DOUBLES, NORM_PARTIALS, NORM_WGS,
+ NORM_ROWS_PER_WG) = (0, 1, 2, 4, 6, 8, 10, 13, 14, 15, 17, 19)
+NORM_HEADER_DOUBLES = 8     # eps, until, count (actor), count (critic), unused
 # HgymNet.opt_state (HGYM_OPT_*)
 OPT_STATE = 16
 (OPT_LR, OPT_STEP, OPT_KL_SUM, OPT_SURROGATE_SUM, OPT_VALUE_SUM, OPT_ENTROPY_SUM, OPT_GRAD_NORM, OPT_MINIBATCHES, OPT_KL_LAST,

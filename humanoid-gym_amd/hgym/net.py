@@ -96,9 +96,12 @@ class NetBuffers:
     """Flat fp32 master parameters (state_dict order), Adam state, optimiser scalars and the zero-filled
     workspace; exposes per-tensor views named like the reference's ActorCritic.state_dict()."""
 
-    def __init__(self, cfg, device, learning_rate=1e-5, grads_ext=None):
+    def __init__(self, cfg, device, learning_rate=1e-5, grads_ext=None, obs_norm=None):
         """grads_ext: optional caller-owned (>= P + 1,) fp32 tensor to hold [gradient | KL] (the data-parallel update's direct exchange
-        keeps it in peer-mapped memory: dist_utils.P2PComm)."""
+        keeps it in peer-mapped memory: dist_utils.P2PComm).
+        obs_norm: None (off), or (eps, until) -- empirical observation normalisation folded into the first layer (HgymNet.norm): this
+        object owns the block, starts it at mean 0 / var 1 / count 0 and exposes norm_state() / load_norm_state(); until None: the
+        statistics never stop.  ValueError for eps < 0 or until < 0."""
         self.cfg = cfg
         self.device = torch.device(device)
         self.P = int(L.lib.hgym_net_param_count(C.byref(cfg)))
@@ -119,6 +122,16 @@ class NetBuffers:
         self._ws_ptr = self.workspace.data_ptr() + off
         self.struct = L.Net(L.fptr(self.params), L.fptr(self.grads), L.fptr(self.adam_m), L.fptr(self.adam_v),
                             L.f64ptr(self.opt_state), C.c_void_p(self._ws_ptr))
+        self.obs_norm = None
+        if obs_norm is not None:
+            self.obs_norm = check_obs_norm(*obs_norm)
+            self.norm_layout = norm_layout(cfg)
+            self._norm_block = torch.zeros(self.norm_layout[L.NORM_BYTES] + 256, dtype=torch.uint8, device=self.device)
+            self._norm_off = (-self._norm_block.data_ptr()) % 256
+            self.struct.norm = C.c_void_p(self._norm_block.data_ptr() + self._norm_off)
+            eps, until = self.obs_norm
+            L.check(L.lib.hgym_net_norm_init(C.byref(cfg), C.byref(self.struct), eps, -1 if until is None else until, self.stream()),
+                    "hgym_net_norm_init")
         # named views
         self.views = {}
         A = cfg.num_actions
@@ -162,6 +175,72 @@ class NetBuffers:
 
     def sync_shadow(self):
         L.check(L.lib.hgym_net_sync_shadow(C.byref(self.cfg), C.byref(self.struct), self.stream()), "hgym_net_sync_shadow")
+
+    # ------------------------------------------------------------------ observation normalisation (obs_norm)
+    def _norm_part(self, slot, count, dtype):
+        """A view of `count` elements of `dtype` at layout slot `slot` of the block."""
+        if self.obs_norm is None:
+            raise RuntimeError("this NetBuffers was built without observation normalisation (obs_norm)")
+        o = self._norm_off + int(self.norm_layout[slot])
+        if int(self.norm_layout[slot]) < 0:
+            raise RuntimeError("the normaliser's block has no part %d for this configuration" % slot)
+        return self._norm_block[o:o + count * torch.empty(0, dtype=dtype).element_size()].view(dtype)
+
+    def norm_view(self, name, k=0):
+        """Device views into the block: "mean" / "var" (fp64) and "mean_f" / "scale_f" (fp32) of statistics k (0: the actor's, over
+        num_obs columns; 1: the critic's, over num_priv), "bias" (fp32, the effective first-layer bias of net k: 0 actor, 1 critic,
+        2 auxiliary head), "header" (8 doubles: eps, until, count 0, count 1), "sums" (fp64, what accumulate leaves)."""
+        K = (self.cfg.num_obs, self.cfg.num_priv)
+        if name in ("mean", "var"):
+            return self._norm_part((L.NORM_MEAN if name == "mean" else L.NORM_VAR) + k, K[k], torch.float64)
+        if name in ("mean_f", "scale_f"):
+            return self._norm_part((L.NORM_MEAN_F if name == "mean_f" else L.NORM_SCALE_F) + k, K[k], torch.float32)
+        if name == "bias":
+            n1 = (self.cfg.actor_dims[1], self.cfg.critic_dims[1], self.cfg.aux_dims[1])[k]
+            return self._norm_part(L.NORM_BIAS + k, n1, torch.float32)
+        if name == "header":
+            return self._norm_part(L.NORM_HEADER, L.NORM_HEADER_DOUBLES, torch.float64)
+        if name == "sums":
+            return self._norm_part(L.NORM_SUMS, int(self.norm_layout[L.NORM_SUMS_DOUBLES]), torch.float64)
+        raise KeyError(name)
+
+    def norm_accumulate(self, obs, priv):
+        """hgym_net_norm_accumulate: the raw fp64 sums (n, sum x, sum x^2 per column) of the M rows of obs (M, num_obs) and priv
+        (M, num_priv), contiguous fp32, into the block's sums part (overwritten)."""
+        assert obs.is_contiguous() and priv.is_contiguous() and obs.dtype == torch.float32 and priv.dtype == torch.float32
+        assert obs.shape[0] == priv.shape[0] and obs.shape[1] == self.cfg.num_obs and priv.shape[1] == self.cfg.num_priv
+        L.check(L.lib.hgym_net_norm_accumulate(C.byref(self.cfg), C.byref(self.struct), L.fptr(obs), L.fptr(priv), int(obs.shape[0]),
+                                               self.stream()), "hgym_net_norm_accumulate")
+
+    def norm_merge(self):
+        """hgym_net_norm_merge: the sums part merged into the running statistics, then the refold."""
+        L.check(L.lib.hgym_net_norm_merge(C.byref(self.cfg), C.byref(self.struct), self.stream()), "hgym_net_norm_merge")
+
+    def norm_unfold_grad(self):
+        """hgym_net_norm_unfold_grad: call between ppo_grad and the exchange / ppo_apply."""
+        L.check(L.lib.hgym_net_norm_unfold_grad(C.byref(self.cfg), C.byref(self.struct), self.stream()), "hgym_net_norm_unfold_grad")
+
+    def norm_state(self):
+        """{"obs": {...}, "critic_obs": {...}}, each mean, var (fp64 clones), count, eps, until -- what a checkpoint carries."""
+        h = self.norm_view("header")
+        eps, until = self.obs_norm
+        return {name: dict(mean=self.norm_view("mean", k).clone(), var=self.norm_view("var", k).clone(), count=h[2 + k].clone(),
+                           eps=eps, until=until) for k, name in enumerate(("obs", "critic_obs"))}
+
+    def load_norm_state(self, state):
+        """The inverse of norm_state() -- mean, var, count of both statistics (eps and until are this object's own) -- then the refold."""
+        h = self.norm_view("header")
+        for k, name in enumerate(("obs", "critic_obs")):
+            st = state[name]
+            for part in ("mean", "var"):
+                v = self.norm_view(part, k)
+                v.copy_(torch.as_tensor(st[part], dtype=torch.float64).to(self.device).view_as(v))
+            h[2 + k:3 + k] = torch.as_tensor(st["count"], dtype=torch.float64).to(self.device).reshape(1)
+        self.norm_sums_clear()
+        self.norm_merge()       # an empty batch: nothing merges, the floats and the fold are recomputed from the loaded state
+
+    def norm_sums_clear(self):
+        self.norm_view("sums").zero_()
 
     def forward(self, which, x):
         M = x.shape[0]
@@ -247,6 +326,26 @@ class NetBuffers:
 
     def ppo_apply(self, ppo):
         L.check(L.lib.hgym_ppo_apply(C.byref(self.cfg), C.byref(ppo), C.byref(self.struct), self.stream()), "hgym_ppo_apply")
+
+
+def check_obs_norm(eps, until):
+    """(float eps, int until or None) of an obs_norm=(eps, until) argument; ValueError for eps < 0 / not finite or until < 0."""
+    import math
+    eps = float(eps)
+    if not (eps >= 0.0 and math.isfinite(eps)):
+        raise ValueError("normalization_eps=%r: must be finite and >= 0" % (eps,))
+    if until is not None:
+        if int(until) != until or until < 0:
+            raise ValueError("normalization_until=%r: must be None or an integer row count >= 0" % (until,))
+        until = int(until)
+    return eps, until
+
+
+def norm_layout(cfg):
+    """hgym_net_norm_layout: the list of HGYM_NORM_LAYOUT numbers (L.NORM_*) for a net config; needs no device."""
+    out = (C.c_int64 * L.NORM_LAYOUT)()
+    L.check(L.lib.hgym_net_norm_layout(C.byref(cfg), out), "hgym_net_norm_layout")
+    return list(out)
 
 
 def make_batch(obs, priv, actions, values, advantages, returns, logp, mu, sigma, idx, obs_bf16=None, priv_bf16=None):

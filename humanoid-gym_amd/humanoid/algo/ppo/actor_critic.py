@@ -28,7 +28,8 @@ def _mlp(sizes, activation):
 class ActorCritic(nn.Module):
     def __init__(self, num_actor_obs, num_critic_obs, num_actions, actor_hidden_dims=[256, 256, 256],
                  critic_hidden_dims=[256, 256, 256], init_noise_std=1.0, activation=nn.ELU(), denoiser_hidden_dims=None,
-                 denoiser_targets=0, fused_activation=None, noise_std_type="scalar", **kwargs):
+                 denoiser_targets=0, fused_activation=None, noise_std_type="scalar", empirical_normalization=False,
+                 normalization_eps=1e-2, normalization_until=None, **kwargs):
         """denoiser_hidden_dims / denoiser_targets (native extension, BASELINE configs[4]): an auxiliary head
         obs -> denoiser_hidden_dims -> denoiser_targets that regresses the newest `denoiser_targets` columns of the
         privileged observation (the clean single-frame privileged state) from the noisy observation history; trained jointly
@@ -38,9 +39,16 @@ class ActorCritic(nn.Module):
         else off.
         noise_std_type (as in current rsl_rl): "scalar" -- the reference's parameter `std`, the standard deviations themselves, which
         nothing keeps positive -- or "log" -- the parameter is `log_std` (first in the state dict, where `std` is otherwise) and
-        sigma = exp(log_std) stays positive wherever the optimiser moves it.  `noise_std` is sigma in both modes."""
-        from hgym.net import activation_spec, std_param_spec
+        sigma = exp(log_std) stays positive wherever the optimiser moves it.  `noise_std` is sigma in both modes.
+        empirical_normalization (as in current rsl_rl): every observation column of the actor, the critic and the denoiser head is
+        standardised by a running mean and standard deviation, (x - mean) / (std + normalization_eps) -- here as part of the first
+        layer: the kernels read raw rows and the statistics are folded into the first-layer operands.  The
+        statistics are updated once per PPO.update(), from the rollout it trained on (rsl_rl: at every env step), until
+        `normalization_until` rows have been seen (None: always).  `obs_normalizer` / `critic_obs_normalizer` expose them
+        (nn.Identity() when off).  The parameters, the state dict and the optimiser stay in the normalised parametrisation."""
+        from hgym.net import activation_spec, std_param_spec, check_obs_norm
         std_param_spec(noise_std_type)       # ValueError for anything but "scalar" / "log", before anything is built
+        normalization_eps, normalization_until = check_obs_norm(normalization_eps, normalization_until)      # ValueError: eps < 0, until < 0
         if kwargs:
             print("ActorCritic.__init__ got unexpected arguments, which will be ignored: " + str(list(kwargs.keys())))
         super().__init__()
@@ -62,6 +70,14 @@ class ActorCritic(nn.Module):
             self.log_std = nn.Parameter(torch.log(init_noise_std * torch.ones(num_actions)))
         else:
             self.std = nn.Parameter(init_noise_std * torch.ones(num_actions))
+        self.empirical_normalization = bool(empirical_normalization)
+        self.normalization_eps, self.normalization_until = normalization_eps, normalization_until
+        if self.empirical_normalization:
+            from .normalizer import EmpiricalNormalization
+            self.obs_normalizer = EmpiricalNormalization(num_actor_obs, normalization_eps, normalization_until, which=0)
+            self.critic_obs_normalizer = EmpiricalNormalization(num_critic_obs, normalization_eps, normalization_until, which=1)
+        else:
+            self.obs_normalizer, self.critic_obs_normalizer = nn.Identity(), nn.Identity()
         self._net = None          # hgym.NetBuffers once bound
         self._last = None         # outputs of the last act(): mu, sigma, logp, values
         self._sample_seed = 0
@@ -76,8 +92,38 @@ class ActorCritic(nn.Module):
                 view.copy_(p.detach().to(view.device))
                 p.data = view
         self._net = net
+        if self.empirical_normalization:
+            if getattr(net, "obs_norm", None) is None:
+                raise RuntimeError("ActorCritic(empirical_normalization=True) bound to a NetBuffers built without obs_norm")
+            self.obs_normalizer.bind(net)
+            self.critic_obs_normalizer.bind(net)
         net.sync_shadow()
         return self
+
+    @property
+    def obs_norm_spec(self):
+        """NetBuffers' obs_norm argument: (eps, until), or None when empirical_normalization is off."""
+        return (self.normalization_eps, self.normalization_until) if self.empirical_normalization else None
+
+    def norm_state_dicts(self):
+        """{"obs_norm_state_dict": ..., "critic_obs_norm_state_dict": ...} for a checkpoint; {} when normalisation is off."""
+        if not self.empirical_normalization:
+            return {}
+        return dict(obs_norm_state_dict=self.obs_normalizer.norm_state_dict(),
+                    critic_obs_norm_state_dict=self.critic_obs_normalizer.norm_state_dict())
+
+    def folded_first_layer(self, which=0):
+        """(W o s, b') in fp32 on the cpu: the first layer of the actor (0), critic (1) or denoiser (2) that takes RAW observations --
+        what an exported policy carries.  b' = b - (W o s) m in float64, rounded once.  Without normalisation: the layer itself."""
+        seq = (self.actor, self.critic, getattr(self, "denoiser", None))[which]
+        W, b = seq[0].weight.detach().cpu().float(), seq[0].bias.detach().cpu().float()
+        if not self.empirical_normalization:
+            return W.clone(), b.clone()
+        nz = self.critic_obs_normalizer if which == 1 else self.obs_normalizer
+        m = nz.mean.cpu().float()
+        sc = (1.0 / (torch.sqrt(nz.var.cpu()) + float(torch.tensor(nz.eps, dtype=torch.float32)))).float()
+        Ws = W * sc[None, :]
+        return Ws, (b.double() - (Ws.double() * m.double()[None, :]).sum(dim=1)).float()
 
     @property
     def bound(self):
@@ -152,7 +198,7 @@ class ActorCritic(nn.Module):
     def act_inference(self, observations):
         if self._net is not None and observations.is_cuda:
             return self._net.forward(0, observations.contiguous())
-        return self.actor(observations)        # exported-policy / CPU evaluation plumbing (BASELINE config #1)
+        return self.actor(self.obs_normalizer(observations))        # exported-policy / CPU evaluation plumbing (BASELINE config #1)
 
     def evaluate(self, critic_observations, **kwargs):
         return self._need_net().forward(1, critic_observations.contiguous())
@@ -163,4 +209,4 @@ class ActorCritic(nn.Module):
             raise RuntimeError("this ActorCritic was built without a denoiser head (denoiser_hidden_dims)")
         if self._net is not None and observations.is_cuda:
             return self._net.forward(2, observations.contiguous())
-        return self.denoiser(observations)
+        return self.denoiser(self.obs_normalizer(observations))

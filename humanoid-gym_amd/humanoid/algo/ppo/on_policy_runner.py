@@ -4,6 +4,7 @@ checkpoint save / load (same dict keys), inference-policy getters, console + opt
 The env writes its observations straight into the rollout-storage slots, and episode book-keeping stays on the device,
 read back once per iteration (the reference syncs the host every step, :146-152)."""
 import atexit
+import gc
 import os
 import sys
 import queue
@@ -137,8 +138,18 @@ class _CapturedGraph:
         torch.cuda.synchronize()
         # thread-local capture mode: with torch.distributed initialised, the RCCL watchdog thread polls events concurrently.  Inference
         # mode: capture_begin updates the generator's graph-state tensors in place, and the first capture created them as inference tensors
-        with torch.inference_mode(), torch.cuda.graph(graph, capture_error_mode="thread_local"):
-            held = capture()
+        # No garbage collection inside the capture: a collection that starts while the stream is capturing runs, on the capturing thread, the
+        # finalisers of whatever cyclic garbage the process has accumulated -- runners, nets and captured graphs of earlier learn() calls --
+        # and releasing device objects is not an operation a capture permits (seen as an abort of the process with the interpreter in
+        # "Garbage-collecting" under this frame).  torch.cuda.graph collects once itself before the capture begins.
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.inference_mode(), torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                held = capture()
+        finally:
+            if gc_was_on:
+                gc.enable()
         self.graph, self.key, self.held = graph, key, held
         graph.replay()
         return held
@@ -195,6 +206,37 @@ def _split_algorithm_cfg(alg_cfg):
     return kwargs, bool(kwargs.pop("symmetry", False))
 
 
+def _split_policy_cfg(policy_cfg, runner_cfg):
+    """The keyword arguments of ActorCritic from the train config's policy block.  `empirical_normalization` is read from the policy
+    block or -- rsl_rl's place for it -- from the runner block and passed on; set in both, the two must agree (ValueError)."""
+    kwargs = dict(policy_cfg)
+    if "empirical_normalization" in runner_cfg:
+        r = bool(runner_cfg["empirical_normalization"])
+        if "empirical_normalization" in kwargs and bool(kwargs["empirical_normalization"]) != r:
+            raise ValueError("empirical_normalization is %r in the policy block and %r in the runner block of the train config"
+                             % (kwargs["empirical_normalization"], runner_cfg["empirical_normalization"]))
+        kwargs["empirical_normalization"] = r
+    return kwargs
+
+
+NORM_KEYS = ("obs_norm_state_dict", "critic_obs_norm_state_dict")      # a checkpoint of a run with empirical_normalization carries both
+
+
+def _check_norm_keys(loaded, has_norm, name, spec=None):
+    """A checkpoint with statistics for a policy built without normalisation, or the reverse: refused, naming the key.  spec: this policy's
+    (eps, until) -- statistics saved under another eps or until are another function of the observations, or stop elsewhere: refused too."""
+    for k in NORM_KEYS:
+        if (k in loaded) != has_norm:
+            if has_norm:
+                raise RuntimeError("%s has no `%s`: it was trained without empirical_normalization, this policy was built with it" % (name, k))
+            raise RuntimeError("%s carries `%s`: it was trained with empirical_normalization, this policy was built without it" % (name, k))
+        if has_norm and spec is not None:
+            theirs = (loaded[k].get("eps"), loaded[k].get("until"))
+            if theirs[0] is None or float(theirs[0]) != float(spec[0]) or theirs[1] != spec[1]:
+                raise RuntimeError("%s: `%s` was saved with normalization_eps=%r, normalization_until=%r; this policy was built with %r, %r"
+                                   % (name, k, theirs[0], theirs[1], spec[0], spec[1]))
+
+
 class OnPolicyRunner:
     def __init__(self, env: VecEnv, train_cfg, log_dir=None, device="cpu"):
         self.cfg = train_cfg["runner"]
@@ -207,7 +249,8 @@ class OnPolicyRunner:
         self.env = env
         num_critic_obs = self.env.num_privileged_obs if self.env.num_privileged_obs is not None else self.env.num_obs
         actor_critic_class = eval(self.cfg["policy_class_name"])  # ActorCritic
-        actor_critic = actor_critic_class(self.env.num_obs, num_critic_obs, self.env.num_actions, **self.policy_cfg).to(self.device)
+        actor_critic = actor_critic_class(self.env.num_obs, num_critic_obs, self.env.num_actions,
+                                          **_split_policy_cfg(self.policy_cfg, self.cfg)).to(self.device)
         alg_class = eval(self.cfg["algorithm_class_name"])  # PPO
         alg_kwargs, symmetry = _split_algorithm_cfg(self.alg_cfg)
         self.alg = alg_class(actor_critic, device=self.device, **alg_kwargs)
@@ -719,9 +762,10 @@ class OnPolicyRunner:
                 side_path = self.env_state_path(path)
                 torch.save(side, side_path + ".tmp%d" % os.getpid())
                 os.replace(side_path + ".tmp%d" % os.getpid(), side_path)
+            norm = self.alg.actor_critic.norm_state_dicts() if hasattr(self.alg.actor_critic, "norm_state_dicts") else {}
             torch.save({"model_state_dict": self.alg.actor_critic.state_dict(),
                         "optimizer_state_dict": self.alg.optimizer.state_dict(),
-                        "iter": self.current_learning_iteration, "infos": infos}, path)
+                        "iter": self.current_learning_iteration, "infos": infos, **norm}, path)
         else:
             if getattr(self, "_save_pin", None) is None:
                 mk = lambda n, dt: torch.empty(n, dtype=dt).pin_memory()
@@ -738,6 +782,17 @@ class OnPolicyRunner:
             buf["m"].copy_(net.adam_m, non_blocking=True)
             buf["v"].copy_(net.adam_v, non_blocking=True)
             buf["opt"].copy_(net.opt_state, non_blocking=True)
+            norm_on = getattr(net, "obs_norm", None) is not None
+            if norm_on:       # the normaliser's state rides with the parameters: header (eps, until, counts), then mean / var of both statistics
+                K = (int(net.cfg.num_obs), int(net.cfg.num_priv))
+                if "norm" not in buf:
+                    buf["norm"] = torch.empty(8 + 2 * (K[0] + K[1]), dtype=torch.float64).pin_memory()
+                parts = [net.norm_view("header")] + [net.norm_view(n, k) for k in (0, 1) for n in ("mean", "var")]
+                o = 0
+                for t in parts:
+                    buf["norm"][o:o + t.numel()].copy_(t, non_blocking=True)
+                    o += t.numel()
+                norm_spec = net.obs_norm
             side = None
             if env_state:
                 if "env" not in buf:        # (pinned on first use: a run without the switch allocates nothing)
@@ -774,6 +829,12 @@ class OnPolicyRunner:
                     ck = {"model_state_dict": model,
                           "optimizer_state_dict": dict(state=state, param_groups=[dict(group, params=list(range(len(state))))]),
                           "iter": it, "infos": infos}
+                    if norm_on:
+                        nb, o = buf["norm"], 8
+                        for k, key in enumerate(NORM_KEYS):
+                            ck[key] = dict(mean=nb[o:o + K[k]].clone(), var=nb[o + K[k]:o + 2 * K[k]].clone(), count=float(nb[2 + k]),
+                                           eps=norm_spec[0], until=norm_spec[1])
+                            o += 2 * K[k]
                     tmp = path + ".tmp%d" % os.getpid()
                     tj.append(time.perf_counter())
                     if side is not None:
@@ -841,6 +902,12 @@ class OnPolicyRunner:
         if theirs != mine:
             raise RuntimeError("%s was trained with noise_std_type=\"%s\" (its model_state_dict has `%s`); this policy was built with "
                                "noise_std_type=\"%s\"" % (os.path.basename(str(path)), theirs, "log_std" if theirs == "log" else "std", mine))
+        # a checkpoint with the normaliser's statistics for a policy without normalisation, or the reverse: another function of the
+        # observations under the same parameter names
+        has_norm = bool(getattr(self.alg.actor_critic, "empirical_normalization", False))
+        _check_norm_keys(loaded, has_norm, os.path.basename(str(path)), getattr(self.alg.actor_critic, "obs_norm_spec", None))
+        if has_norm:        # the statistics first, then the parameters (whose load refolds the first layers with them)
+            self.alg.net.load_norm_state(dict(obs=loaded[NORM_KEYS[0]], critic_obs=loaded[NORM_KEYS[1]]))
         self.alg.actor_critic.load_state_dict(loaded["model_state_dict"])
         if load_optimizer or (side is not None and self.cfg.get("exact_resume", False)):
             self.alg.optimizer.load_state_dict(loaded["optimizer_state_dict"])
@@ -862,7 +929,14 @@ class OnPolicyRunner:
         self.alg.actor_critic.eval()
         if device is not None and str(device) != str(self.device):
             import copy
-            return copy.deepcopy(self.alg.actor_critic.actor).to(device)
+            if not getattr(self.alg.actor_critic, "empirical_normalization", False):
+                return copy.deepcopy(self.alg.actor_critic.actor).to(device)
+            actor = copy.deepcopy(self.alg.actor_critic.actor).to("cpu")      # raw observations in: the folded first layer
+            W, b = self.alg.actor_critic.folded_first_layer(0)
+            with torch.no_grad():
+                actor[0].weight.copy_(W)
+                actor[0].bias.copy_(b)
+            return actor.to(device)
         return self.alg.actor_critic.act_inference
 
     def get_inference_critic(self, device=None):

@@ -141,7 +141,11 @@ class PPO:
         self.comm_report = dist_utils.comm_report()     # mode, used, fallback_reason, probe timings (bench.py prints it)
         self._comm_direct_used = False      # the direct kernel has carried at least one real gradient (also under HGYM_COMM=both)
         self.comm_flip = False      # bench.py: use the OTHER exchange for the next update() (timing both in its profiling iterations)
-        self.net = hgym.NetBuffers(cfg, self.device, learning_rate=self._lr0, grads_ext=None if self._comm is None else self._comm.data)
+        # empirical observation normalisation (ActorCritic(empirical_normalization=True)): the net owns the statistics and folds them into
+        # the first layers; update() unfolds every minibatch gradient and ends with the normaliser step
+        self._obs_norm = getattr(ac, "obs_norm_spec", None)
+        self.net = hgym.NetBuffers(cfg, self.device, learning_rate=self._lr0, grads_ext=None if self._comm is None else self._comm.data,
+                                   obs_norm=self._obs_norm)
         dist_utils.broadcast_parameters(ac.parameters())   # identical initial parameters on every rank
         ac.bind(self.net)
         # bf16 shadows of the stored observation rows: the policy launches leave them behind, the update gathers from them
@@ -153,7 +157,9 @@ class PPO:
                                              self.desired_kl if self.desired_kl is not None else 0.0,
                                              adaptive=(self.desired_kl is not None and self.schedule == "adaptive"),
                                              world_size=self._world,
-                                             grad_norm_ready=True,   # update() applies exactly what hgym_ppo_grad produced
+                                             # update() applies exactly what hgym_ppo_grad produced -- unless the unfold of a normalised
+                                             # net comes between the two: the norm is then taken by hgym_ppo_apply's own pass
+                                             grad_norm_ready=self._obs_norm is None,
                                              aux_coef=self.denoise_coef if aux else 0.0,
                                              clipped_value_loss=self.use_clipped_value_loss)
         self.last_denoise_loss = None
@@ -328,6 +334,8 @@ class PPO:
             return False
         if not dist_utils.active():
             return True
+        if self._obs_norm is not None:      # the normaliser's sums go through a torch.distributed all-reduce: eager
+            return False
         return bool(self._comm is not None and self._comm_p2p and not self.comm_flip and getattr(self._comm, "capturable", False))
 
     def update_graph_key(self):
@@ -337,7 +345,7 @@ class PPO:
                 float(self.gamma), float(self.lam), self.permutation, self._perm_seed, id(self.storage), id(self.net),
                 bool(dist_utils.active()), bool(self._comm_p2p), bytes(C.string_at(C.addressof(self.net.cfg), C.sizeof(self.net.cfg))),
                 self.storage._obs_bf16 is not None, bool(self.comm_flip), self._world,
-                None if self._symmetry is None else self._symmetry.key())
+                None if self._symmetry is None else self._symmetry.key(), self._obs_norm)
 
     def after_rollout_replay(self, shadow_valid, deferred):
         """Host-side book-keeping of one replayed rollout: a full storage, the shadow slots the capture wrote, deferred_values() if deferred."""
@@ -400,6 +408,8 @@ class PPO:
                 idx = perm[i * mb:(i + 1) * mb]
                 batch = hgym.make_batch(*cols, idx, **sh)
                 net.ppo_grad(self._ppo_cfg, batch)
+                if self._obs_norm is not None:
+                    net.norm_unfold_grad()      # first-layer gradients: of the folded operands -> of the master parameters, ahead of the exchange and the norm
                 if dist_utils.active():
                     # ONE bucket, [flat gradient | KL]: nothing of this minibatch is left to run under the exchange (apply needs it),
                     # and two buckets pay the collective's latency twice.  (Rounds 1-2 split the weight-gradient launch in two so that
@@ -423,6 +433,8 @@ class PPO:
                         ev[1].record()
                         self.comm_timing.append(ev + ("p2p" if (self._comm is not None and self._comm_p2p != bool(self.comm_flip)) else "collective",))
                 net.ppo_apply(self._ppo_cfg)
+        if self._obs_norm is not None:
+            self.normalizer_step()
         st.clear()
         self._diag_updated = True
         if not sync:
@@ -432,6 +444,23 @@ class PPO:
         o = hgym.opt_summary(o, self._ppo_cfg.aux_coef > 0.0)
         self.last_denoise_loss = o["denoise_loss"]
         return o["mean_value_loss"], o["mean_surrogate_loss"]
+
+    def normalizer_step(self):
+        """The normaliser's one step per iteration, at the end of update(), ahead of storage.clear(): accumulate the T * N stored raw
+        rows of both kinds (slots 0 .. T - 1; with symmetry on the original rows only -- the mirrored copies lie behind the bootstrap
+        slot), merge them into the running statistics, refold the first layers.  The statistics are therefore frozen while a rollout is
+        collected and while its update runs: the stored mu, sigma and log-probabilities stay those of the net the update
+        differentiates.  (rsl_rl merges at every env step.)  Several ranks: the raw fp64 sums pass through one all-reduce before the
+        merge, so every rank merges the global batch into the same state.  The launches and their arguments are the same in every
+        iteration: on one rank the step is part of the captured update."""
+        st, net = self.storage, self.net
+        T, N = st.num_transitions_per_env, st.num_envs
+        obs = st._obs_all[:T].flatten(0, 1)
+        priv = (st._priv_all if st._priv_all is not None else st._obs_all)[:T].flatten(0, 1)
+        net.norm_accumulate(obs, priv)
+        if dist_utils.active():
+            torch.distributed.all_reduce(net.norm_view("sums"))
+        net.norm_merge()
 
     # ------------------------------------------------------------------ diagnostics of an update
     def diagnostics_prepare(self):

@@ -17,7 +17,10 @@ HGYM_NOISE_STD=log sets `policy.noise_std_type` the same way: the action noise i
 sigma = exp(log_std) cannot leave the positive numbers, the checkpoint's first entry is `log_std`); "scalar" or unset: the reference's `std`.
 
 HGYM_SYMMETRY=1 sets `algorithm.symmetry` the same way: the update also trains on the left-right mirrored copy of every transition
-(PPO.symmetry with XBot-L's tables, humanoid/utils/symmetry.py): minibatches twice as large, as many Adam steps."""
+(PPO.symmetry with XBot-L's tables, humanoid/utils/symmetry.py): minibatches twice as large, as many Adam steps.
+
+HGYM_OBS_NORM=1 sets `policy.empirical_normalization` the same way: every observation column is standardised by running statistics
+folded into the first layers (ActorCritic(empirical_normalization=True)); checkpoints carry the statistics."""
 import os
 import sys
 
@@ -39,6 +42,8 @@ def train(args):
         task_registry.get_cfgs(args.task)[1].policy.noise_std_type = os.environ["HGYM_NOISE_STD"]
     if os.environ.get("HGYM_SYMMETRY", "0") == "1":
         task_registry.get_cfgs(args.task)[1].algorithm.symmetry = True
+    if os.environ.get("HGYM_OBS_NORM", "0") == "1":
+        task_registry.get_cfgs(args.task)[1].policy.empirical_normalization = True
     ppo_runner, train_cfg = task_registry.make_alg_runner(env=env, name=args.task, args=args, **({} if rank == 0 else {"log_root": None}))
     ppo_runner.learn(num_learning_iterations=train_cfg.runner.max_iterations, init_at_random_ep_len=True)
     if os.environ.get("HGYM_TRAIN_SIGNATURE"):      # tests: a signature of this rank's final parameters (replicas must agree bit for bit)

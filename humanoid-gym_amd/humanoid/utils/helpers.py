@@ -168,4 +168,10 @@ def export_policy_as_jit(actor_critic, path):
     os.makedirs(path, exist_ok=True)
     path = os.path.join(path, "policy_1.pt")
     model = copy.deepcopy(actor_critic.actor).to("cpu")
+    if getattr(actor_critic, "empirical_normalization", False):
+        # the normaliser is part of the first layer: the exported nn.Sequential takes RAW observations (sim2sim.py, play.py feed them as before)
+        W, b = actor_critic.folded_first_layer(0)
+        with torch.no_grad():
+            model[0].weight.copy_(W)
+            model[0].bias.copy_(b)
     torch.jit.script(model).save(path)

@@ -61,7 +61,9 @@ extern "C" {
                              *    (same version, later: HgymNetConfig.std_param added ahead of fused_activation -- the action noise trained as log sigma
                              *    (HGYM_STD_LOG) -- and hgym_net_sigma_offset; a zero-filled field is the sigma parameter every earlier layout meant)
                              *    (same version, later: hgym_mirror_rows -- the mirrored copy of stored rows for left-right symmetry augmentation;
-                             *    no layout changes) */
+                             *    no layout changes)
+                             *    (same version, later: HgymNet.norm appended -- empirical observation normalisation folded into the first layer,
+                             *    hgym_net_norm_*; a NULL (zero-filled) member is a net without it) */
 
 enum {
     HGYM_OK = 0,
@@ -591,11 +593,75 @@ typedef struct HgymNet {
     float* adam_v;
     double* opt_state;     /* [HGYM_OPT_STATE] */
     void* workspace;       /* hgym_net_workspace_bytes() bytes, 256-byte aligned */
+    void* norm;            /* observation normalisation (below: hgym_net_norm_*): the caller-owned block of hgym_net_norm_layout()[HGYM_NORM_BYTES]
+                              bytes, 256-byte aligned; NULL: off -- every launch, argument and result is what it is without the feature.
+                              Appended within header v9 as the LAST member: a zero-filled tail is a net without normalisation. */
 } HgymNet;
 
 /* re-derive the compute-precision operand copies (padded W and W^T) from the fp32 master parameters;
  * call after loading a checkpoint.  The Adam kernel keeps them current afterwards. */
 int32_t hgym_net_sync_shadow(const HgymNetConfig* cfg, const HgymNet* net, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Empirical observation normalisation (rsl_rl's `empirical_normalization`; header v9, HgymNet.norm appended).
+ * Every observation column is standardised by a running mean and standard deviation -- as part of the FIRST LAYER:
+ *     W ((x - m) o s) + b  =  (W o s) x + (b - (W o s) m),      s = 1 / (std + eps) per column.
+ * The kernels keep reading RAW rows.  With HgymNet.norm set, the operand-precision copies of a first-layer weight hold T(w * s[c]) -- written
+ * where every operand copy is written, by hgym_ppo_apply's Adam launch and by hgym_net_sync_shadow -- and the first-layer bias the kernels
+ * add is the effective bias b'[r] = b[r] - sum_c Wop[r][c] * m[c] (Wop as rounded to the operand type, so that weight rounding acts on x - m;
+ * the sum in fp64 in a fixed order, rounded once to fp32), recomputed by one more launch behind both.  The actor, the critic and the auxiliary
+ * head all fold; the head shares the actor's statistics and its regression targets stay raw.  params, grads, adam_m / adam_v stay in the
+ * NORMALISED parametrisation (what rsl_rl trains): hgym_ppo_grad leaves the gradient of the operand parametrisation, and
+ * hgym_net_norm_unfold_grad turns the first-layer weight gradients into the master's in place -- call it behind every hgym_ppo_grad (part 1
+ * of hgym_ppo_grad_part), ahead of a rank exchange and of hgym_ppo_apply.  opt_state[HGYM_OPT_GRAD_SQNORM] as the gradient call left it is then not
+ * the final gradient's: HgymPPOConfig.grad_norm_ready must be 0 (hgym_ppo_apply refuses 1 with HGYM_E_BADARG when norm is set).
+ *
+ * Statistics, fp64 on the device, per column; the actor's over num_obs columns, the critic's over num_priv: mean = 0, var = 1, count = 0 at
+ * hgym_net_norm_init.  A batch of n rows with population mean mu_b and variance var_b (= sum x^2 / n - mu_b^2, clamped at 0) merges as
+ *     count += n;  rate = n / count;  d = mu_b - mean;  mean += rate * d;  var += rate * (var_b - var + d * (mu_b - mean_new))
+ * and the kernels' floats are m = (float)mean, s = (float)(1.0 / (sqrt(var) + (double)eps)): a constant column has var = 0 and the finite scale
+ * 1 / eps.  `until` >= 0: once count >= until a merge changes nothing (checked on the device); -1: never stops.
+ *
+ * The block (HgymNet.norm): hgym_net_norm_layout fills layout[HGYM_NORM_LAYOUT] with its size and the byte offsets of its parts -- callable
+ * without a device; HGYM_E_* for a configuration the library refuses or rows wider than 1024 columns.  Index k: 0 = actor / obs, 1 = critic / priv.
+ *   [HGYM_NORM_BYTES]          size of the block (no zero-fill needed: hgym_net_norm_init writes every part that is read)
+ *   [HGYM_NORM_HEADER]         8 doubles: eps, until, count of the actor's statistics, count of the critic's, 4 unused
+ *   [HGYM_NORM_MEAN + k], [HGYM_NORM_VAR + k]          fp64 [K]
+ *   [HGYM_NORM_MEAN_F + k], [HGYM_NORM_SCALE_F + k]    fp32 [K]: m and s above
+ *   [HGYM_NORM_BIAS + i]       fp32 [first width]: effective bias of net i (0 actor, 1 critic, 2 auxiliary head; -1: no such net)
+ *   [HGYM_NORM_SUMS]           fp64 [HGYM_NORM_SUMS_DOUBLES] = [n | sum x [num_obs] | sum x^2 [num_obs] | n | sum x [num_priv] | sum x^2 [num_priv]]:
+ *                              what hgym_net_norm_accumulate leaves and hgym_net_norm_merge reads.  Several ranks: all-reduce (SUM) these
+ *                              doubles between the two calls; every rank then merges the same batch into the same state.
+ *   [HGYM_NORM_PARTIALS + k]   scratch of the accumulate launch; [HGYM_NORM_WGS + k] its workgroups for row kind k, [HGYM_NORM_ROWS_PER_WG] the rows
+ *                              of one row block (a workgroup walks blocks b, b + WGS, ...): informational, for tests that sit on the edges
+ * hgym_net_norm_init       header, mean = 0, var = 1, count = 0, m = 0, s = 1 / (1 + eps), sums = 0.  Follow with hgym_net_sync_shadow.
+ *                          eps >= 0 finite, until >= -1, else HGYM_E_BADARG.
+ * hgym_net_norm_accumulate the sums of M rows of obs ((M, num_obs)) and priv ((M, num_priv)), row-major, contiguous, 4-byte aligned (16-byte
+ *                          aligned bases take the fast path), any M >= 1: OVERWRITES the sums block.  fp64 partial sums per workgroup added in
+ *                          a fixed order, no atomics: the same rows give the same bits.  Two launches.
+ * hgym_net_norm_merge      the merge above from the sums block, then the refold: first-layer operand copies and effective biases.
+ * hgym_net_norm_unfold_grad  G_W[r][c] = (G'_W[r][c] - g_b[r] * m[c]) * s[c] on the first-layer weight gradients of every net, three fp32
+ *                          roundings; bias gradients unchanged.
+ * hgym_net_sync_shadow refolds as well when norm is set.  Everything is enqueued on `stream`, nothing synchronises, every call is capturable.
+ * ---------------------------------------------------------------------------------------------- */
+#define HGYM_NORM_LAYOUT 24
+#define HGYM_NORM_BYTES 0
+#define HGYM_NORM_HEADER 1
+#define HGYM_NORM_MEAN 2
+#define HGYM_NORM_VAR 4
+#define HGYM_NORM_MEAN_F 6
+#define HGYM_NORM_SCALE_F 8
+#define HGYM_NORM_BIAS 10
+#define HGYM_NORM_SUMS 13
+#define HGYM_NORM_SUMS_DOUBLES 14
+#define HGYM_NORM_PARTIALS 15
+#define HGYM_NORM_WGS 17
+#define HGYM_NORM_ROWS_PER_WG 19
+int32_t hgym_net_norm_layout(const HgymNetConfig* cfg, int64_t* layout);
+int32_t hgym_net_norm_init(const HgymNetConfig* cfg, const HgymNet* net, float eps, int64_t until, void* stream);
+int32_t hgym_net_norm_accumulate(const HgymNetConfig* cfg, const HgymNet* net, const float* obs, const float* priv, int64_t M, void* stream);
+int32_t hgym_net_norm_merge(const HgymNetConfig* cfg, const HgymNet* net, void* stream);
+int32_t hgym_net_norm_unfold_grad(const HgymNetConfig* cfg, const HgymNet* net, void* stream);
 
 /* ActorCritic.act_inference / evaluate (actor_critic.py:122-128): which = 0 actor, 1 critic.
  * x (M, in) row-major fp32 with leading dimension ldx; y (M, out) row-major fp32. */
