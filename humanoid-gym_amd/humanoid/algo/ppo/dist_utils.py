@@ -273,7 +273,7 @@ class P2PComm:
         # mappings: an update that uses this communicator issues the same launches with the same arguments every iteration and has no
         # torch.distributed call in it -- PPO.update_capturable
         self.capturable = True
-        self._base, self._peer, self.connected, self.seq = None, [None] * self.world, False, 0
+        self._base, self._peer, self.connected = None, [None] * self.world, False
         base = C.c_void_p()
         with torch.cuda.device(self.device):
             L.check(L.lib.hgym_comm_alloc(self.nbytes, C.byref(base)), "hgym_comm_alloc")
@@ -329,16 +329,13 @@ class P2PComm:
     def allreduce(self):
         """In-place SUM over the ranks of `data`, enqueued on the current stream (the same call sequence on every rank).  The call number
         is the device's (hgym_comm_allreduce(seq = 0), header v9: status[2], advanced by the kernel): the launch is the same every time,
-        so a captured update replays it; `seq` here only counts the calls this object has enqueued (replays are added by the caller)."""
-        self.seq += 1
+        so a captured update replays it, and the host keeps no count of its own."""
         L, C = self._L, self._C
         L.check(L.lib.hgym_comm_allreduce(C.byref(self.struct), 0, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
                 "hgym_comm_allreduce")
 
     def skip_call(self):
-        """This rank does NOT take part in the next exchange (the fault-injection path of the start-up check): the call number moves on
-        as if it had, on the host and on the device."""
-        self.seq += 1
+        """This rank does NOT take part in the next exchange (the start-up check's fault injection): the device's call number moves on as if it had."""
         self.status[2] += 1
 
     def sum64(self, t):
@@ -360,7 +357,7 @@ class P2PComm:
     def raise_if_expired(self, words):
         if int(words[0]) != 0:
             raise CommTimeout("hgym_comm_allreduce: a rank did not arrive within the kernel's bounded wait (rank %d, first at call %d of %d); "
-                              "the gradient of that minibatch is garbage and the replicas have diverged" % (self.rank, int(words[1]), self.seq))
+                              "the gradient of that minibatch is garbage and the replicas have diverged" % (self.rank, int(words[1]), int(words[2])))
 
     def check(self):
         """Synchronises; raises if a bounded wait of any call so far expired (a rank never arrived).  Returns the last call's

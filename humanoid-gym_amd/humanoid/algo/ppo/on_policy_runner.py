@@ -308,8 +308,8 @@ class OnPolicyRunner:
             env.bind_log_sink(True)
         # the captured launches hold HgymEnvConfig and the sink's gamma BY VALUE: a change between learn() calls (what a curriculum
         # script does) must re-capture, as the eager reference would simply see it
-        gkey = (id(env), id(alg.storage), log_on, plan.log_sink, plan.env_sink, plan.defer_fin, plan.fuse, getattr(alg, "gamma", None),
-                env.rollout_graph_key() if hasattr(env, "rollout_graph_key") else None, getattr(alg.storage, "_obs_bf16", None) is not None)
+        gkey = (id(env), alg.rollout_graph_key(), log_on, plan.log_sink, plan.env_sink, plan.defer_fin, plan.fuse,
+                env.rollout_graph_key() if hasattr(env, "rollout_graph_key") else None)
         ukey = (gkey, alg.update_graph_key(), plan.fuse == "deferred") if plan.graph_update else None
         if not plan.graph_update:
             self._update_capture.graph = None
@@ -490,10 +490,10 @@ class OnPolicyRunner:
 
         def capture():
             log_c = _EpisodeLog(log.on, (log.reward_sum, log.length, log.ring, log.meta))       # (the capture refills its own list at every replay)
-            return dict(out=rollout(st._obs_all[0], st._priv_all[0], log_c), log=log_c, shadow_valid=list(getattr(st, "shadow_valid", [])))
+            return dict(out=rollout(st._obs_all[0], st._priv_all[0], log_c), log=log_c, end=self.alg.rollout_end_state())
 
         r = self._rollout_capture.run(plan.graph, gkey, lambda: dict(out=rollout(obs, critic_obs, log), log=log), capture,
-                                      lambda held: self.alg.after_rollout_replay(held["shadow_valid"], plan.fuse == "deferred"))
+                                      lambda held: self.alg.after_rollout_replay(held["end"]))
         return r["out"] + (r["log"],)
 
     def _rollout_fused(self, plan):

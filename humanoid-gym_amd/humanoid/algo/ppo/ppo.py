@@ -216,7 +216,7 @@ class PPO:
         """env_fin (native extension): a postponed env-step finaliser to run inside this policy launch
         (LeggedRobot.take_pending_finalize)."""
         st, s = self.storage, self.storage.step
-        self._diag_saved = self._diag_updated = False      # (the rows diagnostics() would read are being overwritten)
+        self._rows_overwritten()
         out = None
         if s < st.num_transitions_per_env:     # write straight into the storage slot (no add_transitions copies)
             out = dict(actions=st.actions[s], mu=st.mu[s], sigma=st.sigma[s], logp=st.actions_log_prob[s].view(-1), values=st.values[s])
@@ -247,22 +247,32 @@ class PPO:
                     obs_bf16=st._obs_bf16, priv_bf16=st._priv_bf16, step=self._sample_step, gamma=self.gamma,
                     seed=self.actor_critic._sample_seed)
 
+    def _rows_overwritten(self):      # a rollout is writing the rows diagnostics() would read
+        self._diag_saved = self._diag_updated = False
+
+    def _rollout_done(self, step, shadow_valid, deferred_ready):
+        """The host state a finished rollout leaves: fused launches and replays of any form write it here, the stepwise calls piece by piece."""
+        self.storage.step, self.storage.shadow_valid, self._deferred_ready = step, list(shadow_valid), deferred_ready
+        self._rows_overwritten()
+
+    def rollout_end_state(self):      # _rollout_done()'s arguments as the rollout that has just run left them: a captured rollout holds them for its replays
+        return self.storage.step, list(self.storage.shadow_valid), self._deferred_ready
+
     def fused_rollout_step(self, env, T=None, deferred=False, rows_ahead=None, l0_ahead=None):
         """All T fused rollout steps: act() + env.step() + process_env_step() as ONE launch each (LeggedRobot.rollout_step) into
-        storage slots 0 .. T (default: the whole storage).  deferred: see rollout_columns; the caller follows with deferred_values().
-        rows_ahead / l0_ahead: None = the env's HGYM_ROWS_AHEAD / HGYM_L0_AHEAD (LeggedRobot.rollout_begin)."""
+        storage slots 0 .. T (default: the whole storage).  deferred: see rollout_columns; the caller follows with deferred_values(),
+        which ends the rollout.  rows_ahead / l0_ahead: None = the env's HGYM_ROWS_AHEAD / HGYM_L0_AHEAD (LeggedRobot.rollout_begin)."""
         st = self.storage
         T = st.num_transitions_per_env if T is None else int(T)
         if st.step != 0 or T > st.num_transitions_per_env:
             raise AssertionError("Rollout buffer overflow")
-        self._diag_saved = self._diag_updated = False
+        self._rows_overwritten()
         env.rollout_begin(self.net, self.rollout_columns(deferred), T, rows_ahead, l0_ahead)
         for i in range(T):
             env.rollout_step(i)
         env.rollout_end()
-        st.step = T
-        if not deferred and st._obs_bf16 is not None:      # each launch wrote its slot's shadows (deferred: deferred_values)
-            st.shadow_valid[:T] = [True] * T
+        if not deferred:      # each launch wrote its slot's shadows
+            self._rollout_done(T, [True] * T + st.shadow_valid[T:] if st._obs_bf16 is not None else st.shadow_valid, self._deferred_ready)
 
     def transition_sink(self):
         """The scalar columns of the storage slot act() has just filled, for an env that can store them itself
@@ -302,9 +312,7 @@ class PPO:
         shadow = st._priv_bf16.flatten(0, 1) if st._priv_bf16 is not None else None
         self.net.critic_values(st._priv_all[:T].flatten(0, 1), st.values.view(-1), shadow)
         self.net.critic_values(st._priv_all[T], st.last_values.view(-1))
-        if shadow is not None:
-            st.shadow_valid = [True] * T
-        self._deferred_ready = True
+        self._rollout_done(T, [True] * T if shadow is not None else st.shadow_valid, True)
 
     def _adv_stats(self, stats):
         """(sum adv, sum adv^2, count) of this rank's shard -> of the global batch, in place: through the direct exchange's mappings when that
@@ -316,13 +324,13 @@ class PPO:
         return dist_utils.allreduce_adv_stats(stats)
 
     def compute_returns(self, last_critic_obs):
-        if self._deferred_ready:        # deferred_values() has evaluated the bootstrap observation with the rest
-            self._deferred_ready = False
-            self.storage.compute_returns(self.storage.last_values, self.gamma, self.lam, stats_hook=self._adv_stats,
-                                         time_outs=self.storage.time_outs)
-            return
-        last_values = self.actor_critic.evaluate(last_critic_obs)
-        self.storage.compute_returns(last_values, self.gamma, self.lam, stats_hook=self._adv_stats)
+        st, deferred = self.storage, self._deferred_ready       # deferred_values() has evaluated the bootstrap observation with the rest
+        last_values = st.last_values if deferred else self.actor_critic.evaluate(last_critic_obs)
+        st.compute_returns(last_values, self.gamma, self.lam, stats_hook=self._adv_stats, time_outs=st.time_outs if deferred else None)
+        self._returns_done()
+
+    def _returns_done(self):      # what compute_returns() changes on the host, issued or replayed: the deferred values are used up
+        self._deferred_ready = False
 
     # ------------------------------------------------------------------ update
     def update_capturable(self):
@@ -347,32 +355,35 @@ class PPO:
                 self.storage._obs_bf16 is not None, bool(self.comm_flip), self._world,
                 None if self._symmetry is None else self._symmetry.key(), self._obs_norm)
 
-    def after_rollout_replay(self, shadow_valid, deferred):
-        """Host-side book-keeping of one replayed rollout: a full storage, the shadow slots the capture wrote, deferred_values() if deferred."""
-        self.storage.step = self.storage.num_transitions_per_env
-        self._diag_saved = self._diag_updated = False
-        self._deferred_ready = self._deferred_ready or deferred
-        self.storage.shadow_valid = list(shadow_valid)
+    def rollout_graph_key(self):
+        """Everything of this side that a rollout bakes into its launches: the storage's slots, the sink's gamma (BY VALUE), the shadows."""
+        return id(self.storage), self.gamma, self.storage._obs_bf16 is not None
+
+    def after_rollout_replay(self, end_state):
+        """Host-side book-keeping of one replayed rollout.  end_state: rollout_end_state() behind the captured pass."""
+        self._rollout_done(*end_state)
 
     def after_update_replay(self):
-        """Host-side book-keeping of one replayed compute_returns() + update(sync=False): what the Python of those two calls changes on the
-        host besides enqueueing work (kept next to update() so that the two stay in step)."""
-        st = self.storage
+        """Host-side book-keeping of one replayed compute_returns() + update(sync=False)."""
+        self._returns_done()
+        self._update_done()
+
+    def _direct_exchange(self):      # this update's gradient exchange is the direct kernel (comm_flip: not the one init_storage chose)
+        return dist_utils.active() and self._comm is not None and self._comm_p2p != bool(self.comm_flip)
+
+    def _update_done(self):      # what update() changes on the host besides enqueueing work, issued or replayed (an update that raises part-way has not run it)
         if self.permutation == "device":
             self._perm_draws += 1
-        self._deferred_ready = False
+        self.storage.cleared()
         self._diag_updated = True
-        st.step = 0
-        st.shadow_valid = [False] * st.num_transitions_per_env
-        if dist_utils.active() and self._comm is not None and self._comm_p2p:
+        if self._direct_exchange():
             self._comm_direct_used = True
-            self._comm.seq += self.num_learning_epochs * self.num_mini_batches
 
     def update(self, sync=True):
         """ppo.py:119-184.  Returns (mean_value_loss, mean_surrogate_loss) as floats -- the one host read-back of the
         update.  sync=False (native extension, used by the runner when nothing is logged): no read-back, returns
         (None, None), so the host can already enqueue the next rollout while this update runs."""
-        hgym, net, st = self._hgym, self.net, self.storage
+        hgym, net, st, direct = self._hgym, self.net, self.storage, self._direct_exchange()
         T, N = st.num_transitions_per_env, st.num_envs
         sym = self._symmetry is not None
         if sym:
@@ -383,12 +394,11 @@ class PPO:
         if self.permutation == "device":
             # the draw number lives on the device as well: the launch reads it there, so a captured update (OnPolicyRunner's second HIP
             # graph) draws a NEW permutation at every replay.  Eager calls re-seat the device copy from the host count first (the host
-            # count is what seek() / a checkpoint resume set); under capture nothing is re-seated -- replays continue the device count and
-            # after_update_replay() advances the host's.
+            # count is what seek() / a checkpoint resume set); under capture nothing is re-seated -- replays continue the device count.
+            # The host's is advanced by _update_done().
             with torch.inference_mode():        # (the counter may have been created under the runner's inference mode)
                 if not torch.cuda.is_current_stream_capturing():
                     self._perm_draws_dev.fill_(self._perm_draws)
-                self._perm_draws += 1
                 self._perm_draws_dev.add_(1)
             perm = st.permutation(self.num_mini_batches * mb, self._perm_seed, self._perm_draws_dev)
         else:
@@ -416,27 +426,22 @@ class PPO:
                     # the actor's bucket travelled under the critic's products: the two half-empty launches cost 106 us more per
                     # minibatch than the one launch -- more than the exchange they hid; profiles/r03_grad_parts_ab.txt.)
                     probe = self.comm_timing is not None
-                    if self._comm is not None and (self._comm_p2p != bool(self.comm_flip)):
-                        # HGYM_COMM=p2p: one kernel on this stream (reduce-scatter + all-gather over the peer mappings)
-                        if probe:
-                            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                            ev[0].record()
+                    h = None if direct else dist_utils.start_sum(net.grads_ext)
+                    if probe:       # (behind the collective's start: the pair times the wait)
+                        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                        ev[0].record()
+                    if direct:      # HGYM_COMM=p2p: one kernel on this stream (reduce-scatter + all-gather over the peer mappings)
                         self._comm.allreduce()
-                        self._comm_direct_used = True
                     else:
-                        h = dist_utils.start_sum(net.grads_ext)
-                        if probe:
-                            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                            ev[0].record()
                         dist_utils.finish(h)
                     if probe:
                         ev[1].record()
-                        self.comm_timing.append(ev + ("p2p" if (self._comm is not None and self._comm_p2p != bool(self.comm_flip)) else "collective",))
+                        self.comm_timing.append(ev + ("p2p" if direct else "collective",))
                 net.ppo_apply(self._ppo_cfg)
         if self._obs_norm is not None:
             self.normalizer_step()
-        st.clear()
-        self._diag_updated = True
+        st.rotate()
+        self._update_done()
         if not sync:
             return None, None
         o = net.opt_state.cpu()                # the one host read-back of the update

@@ -226,9 +226,15 @@ class RolloutStorage:
                 raise AssertionError("bf16 shadow of %s is stale: a storage slot was written behind the policy launch that shadowed it" % name)
 
     def clear(self):
+        self.rotate()
+        self.cleared()
+
+    def rotate(self):       # clear()'s device part: the bootstrap observation (slot T) becomes slot 0 of the next rollout
         self._obs_all[0].copy_(self._obs_all[self.num_transitions_per_env])
         if self._priv_all is not None:
             self._priv_all[0].copy_(self._priv_all[self.num_transitions_per_env])
+
+    def cleared(self):      # clear()'s host part (PPO._update_done: also behind a replayed update, whose graph holds the copies)
         self.step = 0
         self.shadow_valid = [False] * self.num_transitions_per_env
 

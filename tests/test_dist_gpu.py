@@ -93,12 +93,14 @@ def _worker(rank, world, port, out_dir, backend="gloo", num_envs=256, iters=4, c
             open(os.path.join(out_dir, "timeout%d" % rank), "w").write(str(e))
             os._exit(0)
         p2p = t if want_p2p else None
+        comm_calls = runner.alg._comm.read_status()[2]      # the call number the exchange kernels themselves keep (header v9)
     else:
         assert not want_p2p
+        comm_calls = 0
     torch.save(dict(p_init=p_init.cpu(), params=net.params.cpu(), lr=float(net.opt_state[L.OPT_LR]), steps=float(net.opt_state[L.OPT_STEP]),
                     obs=runner.alg.storage._obs_all[1].cpu(), graph=runner._graph is not None, friction=friction, commands0=commands0,
                     env_seed=seed, comm_events=len(runner.alg.comm_timing or []), update_graph=runner._update_graph is not None,
-                    comm_calls=(runner.alg._comm.seq if runner.alg._comm is not None else 0), split=net.bucket_split, P=net.P, p2p=p2p, report=rep),
+                    comm_calls=comm_calls, direct_used=runner.alg._comm_direct_used, split=net.bucket_split, P=net.P, p2p=p2p, report=rep),
                os.path.join(out_dir, "r%d.pt.tmp" % rank))
     os.replace(os.path.join(out_dir, "r%d.pt.tmp" % rank), os.path.join(out_dir, "r%d.pt" % rank))
     if want_p2p and not _all_done_or_timed_out(out_dir, world, "r"):
@@ -279,6 +281,7 @@ def test_two_ranks_one_gpu_captured_update_with_the_direct_exchange(tmp_path):
     assert torch.isfinite(a["params"]).all() and not torch.equal(a["params"], a["p_init"])
     assert torch.equal(a["params"], c["params"]) and a["lr"] == c["lr"]
     assert a["p2p"] is not None and a["comm_calls"] == c["comm_calls"]
+    assert a["direct_used"] is True and b["direct_used"] is True and c["direct_used"] is True
 
 
 @pytest.mark.timeout(900)

@@ -1,7 +1,9 @@
-"""-m gpu: a replayed HIP graph leaves the host exactly where the eager launches leave it.  The host book-keeping of a replay is mirrored by
-hand (PPO.after_rollout_replay / after_update_replay), so every plain host attribute of the algorithm and its rollout storage is compared
-across the launch mechanisms, for each form of the rollout, after every rollout (before compute_returns: the rollout replay's mirror)
-and after every learn() call (the update replay's); and the update graph's key covers what update() bakes into its launches."""
+"""-m gpu: a replayed HIP graph leaves the host exactly where the eager launches leave it.  What compute_returns(), update() and a fused
+rollout change on the host is written once (PPO._returns_done / _update_done / _rollout_done) and run behind the launches whether they were
+issued, captured or replayed (PPO.after_rollout_replay / after_update_replay only call them): each must have run once per iteration under
+every launch mechanism.  The stepwise rollout reaches its end state call by call, so every plain host attribute of the algorithm and its
+rollout storage is also compared across the launch mechanisms, for each form of the rollout, after every rollout (before compute_returns)
+and after every learn() call; and the update graph's key covers what update() bakes into its launches."""
 import numpy as np
 import pytest
 import torch
@@ -45,7 +47,13 @@ def test_replayed_graphs_leave_the_eager_host_state(monkeypatch, rollout):
         if rollout != "stepwise":
             assert r.env.rollout_fused_mode(alg.net) == rollout
         r.env.episode_length_buf = torch.arange(256, device="cuda") * 7
-        got = []
+        got, calls = [], {}
+        shared = ("_returns_done", "_update_done") + (("_rollout_done",) if rollout != "stepwise" else ())
+        for name in shared:
+            def counted(*a, _name=name, _inner=getattr(alg, name), **k):
+                calls[_name] = calls.get(_name, 0) + 1
+                return _inner(*a, **k)
+            setattr(alg, name, counted)
         learn_step = r._learn_step
 
         def after_rollout(*a, **k):         # (learn() calls it right after the rollout: eager, captured or replayed)
@@ -57,6 +65,8 @@ def test_replayed_graphs_leave_the_eager_host_state(monkeypatch, rollout):
             torch.cuda.synchronize()
             got.append(("after learn()", _snapshot(alg), _snapshot(alg.storage)))
         assert len(got) == 9
+        # one definition of the host book-keeping behind eager, capturing and replaying iterations: once per iteration each
+        assert calls == dict.fromkeys(shared, 7), (graph, graph_update, calls)
         assert (r._graph is not None) == (graph == "1")
         assert (r._update_graph is not None) == (graph == "1" and graph_update == "1")
         snaps[(graph, graph_update)] = got
