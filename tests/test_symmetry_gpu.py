@@ -7,6 +7,8 @@ import ctypes as C
 import pytest
 import torch
 
+from update_options_common import _alg, _fill_rollout, _record_batches      # the update harness, shared with tests/test_update_options_gpu.py
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
@@ -186,53 +188,6 @@ def test_storage_mirror_fills_the_second_half_and_nothing_else():
 
 
 # ---------------------------------------------------------------------------------------------- update
-def _alg(monkeypatch, precision, N, T, symmetry, epochs=1):
-    from humanoid.algo import PPO
-    from humanoid.algo.ppo.actor_critic import ActorCritic
-    monkeypatch.setattr(PPO, "precision", precision)
-    monkeypatch.setattr(PPO, "symmetry", symmetry)
-    torch.manual_seed(21)
-    dims = dict(actor_hidden_dims=[512, 256, 128], critic_hidden_dims=[768, 256, 128]) if precision == "bf16" else dict(actor_hidden_dims=[64, 32], critic_hidden_dims=[64, 32])
-    ac = ActorCritic(705, 219, 12, **dims)      # (bf16: XBot-L's widths, which the fused kernels take)
-    alg = PPO(ac, num_learning_epochs=epochs, num_mini_batches=2, device=DEV)
-    alg.init_storage(N, T, [705], [219], [12])
-    return alg
-
-
-def _fill_rollout(alg, seed):
-    """What a rollout leaves: random observation rows, the policy's own outputs for them (and, on the bf16 path, the shadows its launches
-    write), random returns and advantages."""
-    st = alg.storage
-    T = st.num_transitions_per_env
-    g = torch.Generator(device=DEV).manual_seed(seed)
-    st._obs_all.copy_(torch.randn(st._obs_all.shape, device=DEV, generator=g))
-    st._priv_all.copy_(torch.randn(st._priv_all.shape, device=DEV, generator=g))
-    with torch.inference_mode():
-        for s in range(T):
-            alg.act(st._obs_all[s], st._priv_all[s])
-            st.step = s + 1
-    st.returns.copy_(torch.randn(st.returns.shape, device=DEV, generator=g))
-    st.advantages.copy_(torch.randn(st.advantages.shape, device=DEV, generator=g))
-
-
-def _record_batches(monkeypatch, alg):
-    """Every index slice update() hands to hgym.make_batch, and net.grads after every hgym_ppo_grad."""
-    import hgym
-    idx_log, grad_log = [], []
-    make_batch, ppo_grad = hgym.make_batch, alg.net.ppo_grad
-
-    def mb(*a, **k):
-        idx_log.append(a[9].clone())
-        return make_batch(*a, **k)
-
-    def pg(cfg, batch):
-        ppo_grad(cfg, batch)
-        grad_log.append(alg.net.grads.clone())
-    monkeypatch.setattr(hgym, "make_batch", mb)
-    monkeypatch.setattr(alg.net, "ppo_grad", pg)
-    return idx_log, grad_log
-
-
 @pytest.mark.parametrize("precision", ["f32", "bf16"])
 def test_first_minibatch_gradient_equals_a_twin_on_columns_doubled_with_torch(monkeypatch, precision):
     import hgym
