@@ -181,6 +181,8 @@ int32_t hgym_ppo_diag_reduce(int64_t M, const float* actions, const float* mu_ol
 int32_t hgym_ppo_diagnostics(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const HgymNet* net, const HgymBatch* rows, int64_t M,
                              float* scratch, double* block, void* stream) {
     HG_REQUIRE(cfg && ppo && net && rows && block, HGYM_E_BADARG, "null cfg / ppo / net / rows / block");
+    HG_REQUIRE(ppo->mirror_coef >= 0.0f && ppo->mirror_coef < INFINITY, HGYM_E_BADARG,
+               "HgymPPOConfig.mirror_coef=%g must be finite and >= 0 (0: no mirror loss)", (double)ppo->mirror_coef);      // (a NaN fails it)
     HG_REQUIRE(cfg->num_actions == HGYM_NUM_ACTIONS, HGYM_E_UNSUPPORTED, "num_actions=%d (the reduction reads %d-wide rows)", cfg->num_actions,
                HGYM_NUM_ACTIONS);
     HG_REQUIRE(M >= 0 && M <= HGYM_DIAG_MAX_ROWS, HGYM_E_BADARG, "M=%lld", (long long)M);

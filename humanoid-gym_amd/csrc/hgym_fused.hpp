@@ -6,7 +6,8 @@
 //                        the tile's 32 envs behind it in the same launch) and for inference.
 //   mlp_fb_kernel        the update: the same forward on 64-row tiles, the loss gradient on the head wavefronts (PPO surrogate /
 //                        value loss / the auxiliary head's MSE) and dZ_l = (dZ_{l+1} * W_{l+1}) .* elu'(H_l) for l = 2, 1, 0 on the
-//                        activations still resident in LDS; one grid row per net.
+//                        activations still resident in LDS; one grid row per net.  (mlp_fb_mirror_kernel: the actor's tile with the
+//                        mirror loss of left-right symmetry in its head, HgymPPOConfig.mirror_coef > 0.)
 //   dw_kernel_rs         all weight-gradient products dW_l = dZ_l^T * X_l (+ bias gradients) in ONE launch:
 //                        contraction over the batch, operands staged registers -> LDS and read with the gfx950
 //                        transpose read (ds_read_b64_tr_b16), so no transposed copy of anything exists in HBM.
@@ -1022,9 +1023,9 @@ __device__ __forceinline__ void bwd_step(WRing<GR, D>& R, const u32x4* __restric
 // runs on the resident tile: through W3 against H2 (LDS, in place), through W2 against H1 (LDS, in place), through W1 against
 // H0 (LDS: the forward is told to put H2 into a buffer of its own instead of over H0).
 // HBM traffic per minibatch drops by the H re-reads and the loss kernel's own gathers; three launch boundaries go away.
-// The loss partial row: what one loss workgroup (ppo_loss_kernel in hgym_net.hip, fb_body below) hands to ppo_scalars_block.
-constexpr int LOSS_PARTIALS = 32;   // floats per loss workgroup: surrogate, value loss, entropy, kl, dstd[12], dbias_mu[12], dbias_v, aux, pad
-enum { LP_SURROGATE = 0, LP_VALUE = 1, LP_ENTROPY = 2, LP_KL = 3, LP_DSTD = 4, LP_DBIAS_MU = 16, LP_DBIAS_V = 28, LP_AUX = 29 };
+// The loss partial row: what one loss workgroup (ppo_loss_kernel in hgym_loss.hpp, fb_body below) hands to ppo_scalars_block.
+constexpr int LOSS_PARTIALS = 32;   // floats per loss workgroup: surrogate, value loss, entropy, kl, dstd[12], dbias_mu[12], dbias_v, aux, mirror, pad
+enum { LP_SURROGATE = 0, LP_VALUE = 1, LP_ENTROPY = 2, LP_KL = 3, LP_DSTD = 4, LP_DBIAS_MU = 16, LP_DBIAS_V = 28, LP_AUX = 29, LP_MIRROR = 30 };
 struct FbLoss {
     const float* actions;      // (T*N, A) storage columns, gathered through FwdArgs::idx
     const float* old_mu;
@@ -1043,6 +1044,18 @@ struct FbLoss {
     int aux_off;
     float aux_coef;
 };
+
+// The mirror loss (HgymPPOConfig.mirror_coef > 0): an argument of the ML instantiations only (hgym_update_mirror.hip,
+// hgym_update_act_mirror.hip), so that FbLoss -- a kernel argument of every other update kernel -- keeps its layout.
+struct FbMirror {
+    const float* target;       // (M, A) fp32, row m of the MINIBATCH (contiguous, no gather): the raw mu of row m's partner (the pre-pass)
+    const int32_t* act_src;    // (A,) M_a: t_j = act_sign[j] * target[m][act_src[j]]
+    const float* act_sign;     // (A,)
+    float g;                   // 2 * mirror_coef / (M * A): d L_m / d mu = g * (mu - t)
+    int stage;                 // 1: the launch has FB_MIRROR_LDS more bytes of dynamic LDS behind fb_lds_bytes(net) and the tile's target rows
+                               // and the table are staged there by the wavefronts idle in the third layer (with the other loss inputs)
+};
+constexpr int FB_MIRROR_LDS = 64 * 12 * 4 + 2 * 16 * 4;      // 64 rows x 12 floats, then act_src[16] (ints) and act_sign[16]
 
 // LDS of the fused kernel behind the forward's P / Q / bias regions: the dZ3 tile (64 rows x 32 * layer[3].NBB bf16 columns), the
 // head waves' partial sums, and H2 (64 x layer[2].N bf16) -- the forward writes it there instead of over H0, so that all three
@@ -1073,8 +1086,10 @@ inline int fb_lds_bytes(const int32_t* dims) {
 }
 
 // VU: the unclipped value loss (HgymPPOConfig.value_loss_unclipped); a template parameter, so that the clipped kernels stay as they were
-template <int G1, bool AUX = false, bool XB16 = false, bool VU = false, bool GA = false>
-__device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const FusedNet& n, bool is_actor, char* smem) {
+// ML: the actor's head also forms the mirror loss (FbMirror, *Mr); off by default, `if constexpr`: every other instantiation is what it was
+template <int G1, bool AUX = false, bool XB16 = false, bool VU = false, bool GA = false, bool ML = false>
+__device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const FusedNet& n, bool is_actor, char* smem,
+                                        const FbMirror* Mr = nullptr) {
     constexpr int BM = 64, NW = 16, D = 2, MB = BM / 16;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 15, q = lane >> 4;
@@ -1132,6 +1147,23 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
         if (!pre) return;
         const int j = tid - 8 * 64;                 // 0 .. 511 (wavefronts 8 .. 15)
         if (j < 0) return;
+        if constexpr (ML) {
+            // the tile's target rows (contiguous rows of the minibatch: no index to wait for) and M_a's table -> LDS, beside the other
+            // loss inputs: the head reads them there, one LDS access behind another instead of two dependent trips to memory
+            if (Mr->stage) {
+                float* mt = lin + FB_LIN_ACTOR * 64;
+                const int rw = j / 3 < 63 ? j / 3 : 63, k = j % 3;
+                int mrow = m0 + rw;
+                mrow = mrow < a.M ? mrow : a.M - 1;
+                const F4 vt = *reinterpret_cast<const F4*>(Mr->target + (int64_t)mrow * 12 + 4 * k);
+                const int tj = j & 15;
+                const int sv = Mr->act_src[tj < 12 ? tj : 0];
+                const float gv = Mr->act_sign[tj < 12 ? tj : 0];
+                if (j < 192) *reinterpret_cast<F4*>(mt + rw * 12 + 4 * k) = vt;
+                if (j >= 192 && j < 208) reinterpret_cast<int*>(mt + 64 * 12)[tj] = sv < 0 ? 0 : (sv > 11 ? 11 : sv);
+                if (j >= 208 && j < 224) mt[64 * 12 + 16 + tj] = gv;
+            }
+        }
         if (is_actor) {
             // round 1: (row, quad k): actions 0..2, old mu 3..5, old sigma 6..7; round 2: old sigma quad 2, advantage, old log-prob.
             // Every load is issued before the first LDS write.
@@ -1160,9 +1192,10 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
         const int rl = hw * 16 + r;                 // row of the tile
         const int64_t row = rowidx[rl];
         float g[4] = {0.f, 0.f, 0.f, 0.f};
-        float part[11];
+        constexpr int NPART = ML ? 12 : 11;         // ML: [11] the mirror loss's squared error
+        float part[NPART];
 #pragma unroll
-        for (int k = 0; k < 11; ++k) part[k] = 0.0f;
+        for (int k = 0; k < NPART; ++k) part[k] = 0.0f;
         if (is_actor) {
             float act[4] = {0.f, 0.f, 0.f, 0.f}, mo[4] = {0.f, 0.f, 0.f, 0.f}, so[4] = {1.f, 1.f, 1.f, 1.f}, sg[4] = {1.f, 1.f, 1.f, 1.f};
             if (pre) {
@@ -1220,6 +1253,33 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
                         part[7 + e] = g[e];
                     }
             }
+            if constexpr (ML) {
+                // the mirror loss: g (mu - t) joins d mu (and the head-bias sum), (mu - t)^2 the tile's partial sum; nothing else moves
+                const bool staged = pre && Mr->stage;
+                const float* mt = lin + FB_LIN_ACTOR * 64;
+                const int mrow = valid ? m : a.M - 1;
+                float se = 0.0f;
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (4 * q + e < A) {
+                        float t;
+                        if (staged) {
+                            t = mt[64 * 12 + 16 + 4 * q + e] * mt[rl * 12 + reinterpret_cast<const int*>(mt + 64 * 12)[4 * q + e]];
+                        } else {
+                            int sj = Mr->act_src[4 * q + e];
+                            sj = sj < 0 ? 0 : (sj >= A ? A - 1 : sj);
+                            t = Mr->act_sign[4 * q + e] * Mr->target[(int64_t)mrow * A + sj];
+                        }
+                        const float dm = out[e] - t;
+                        if (valid) {
+                            g[e] += Mr->g * dm;
+                            part[7 + e] = g[e];
+                            se += dm * dm;
+                        }
+                    }
+                se += __shfl_xor(se, 16, 64); se += __shfl_xor(se, 32, 64);
+                if (q == 0) part[11] = se;
+            }
         } else {
             const float ret = pre ? lin[rl * 2] : L.returns[row], vold = pre ? lin[rl * 2 + 1] : L.values[row];
             const float v = out[0];
@@ -1253,7 +1313,7 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
         *reinterpret_cast<u32x2*>(gz + off1) = zero;
         // sums over the 16 rows of this wave (lanes sharing q), then across the head waves through `red`
 #pragma unroll
-        for (int k = 0; k < 11; ++k) {
+        for (int k = 0; k < NPART; ++k) {
             float v = part[k];
             v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64); v += __shfl_xor(v, 8, 64);
             part[k] = v;
@@ -1262,6 +1322,7 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
             float* w = red + hw * LOSS_PARTIALS;
             if (is_actor) {
                 if (q == 0) { w[LP_SURROGATE] = part[0]; w[LP_ENTROPY] = part[1]; w[LP_KL] = part[2]; }
+                if constexpr (ML) { if (q == 0) w[LP_MIRROR] = part[11]; }
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
                     if (4 * q + e < 12) { w[LP_DSTD + 4 * q + e] = part[3 + e]; w[LP_DBIAS_MU + 4 * q + e] = part[7 + e]; }
@@ -1283,7 +1344,7 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
     }
     __syncthreads();          // dZ3 tile and the per-wave sums are in LDS; H0 sits in P, H1 in Q, H2 in its own buffer
     if (tid < LOSS_PARTIALS) {
-        const bool mine = AUX ? tid == LP_AUX : (is_actor ? (tid != LP_VALUE && tid < LP_DBIAS_V) : (tid == LP_VALUE || tid == LP_DBIAS_V));
+        const bool mine = AUX ? tid == LP_AUX : (is_actor ? ((tid != LP_VALUE && tid < LP_DBIAS_V) || (ML && tid == LP_MIRROR)) : (tid == LP_VALUE || tid == LP_DBIAS_V));
         if (mine) L.partials[(int64_t)blockIdx.x * LOSS_PARTIALS + tid] = red[tid] + red[LOSS_PARTIALS + tid] + red[2 * LOSS_PARTIALS + tid] + red[3 * LOSS_PARTIALS + tid];
     }
     // ---- dZ chain on the resident tile
@@ -1351,9 +1412,10 @@ int32_t launch_mlp_fb_act_one(const FwdArgs& fb, const FbLoss& fl, bool shadow, 
     return HGYM_OK;
 }
 // the launches of mlp_fb_act_kernel for nets [0, nets) of fb0 (hgym_update_act.hip: clipped value loss, hgym_update_act_vu.hip: unclipped)
+// first: the first net launched (1: the actor's tiles have their own launch, launch_mlp_fb_act_mirror)
 template <bool VU>
-int32_t launch_mlp_fb_act_form(const FwdArgs& fb0, const FbLoss& fl, bool shadow, int tiles, int nets, hipStream_t s) {
-    for (int i = 0; i < nets; ++i) {
+int32_t launch_mlp_fb_act_form(const FwdArgs& fb0, const FbLoss& fl, bool shadow, int tiles, int nets, hipStream_t s, int first = 0) {
+    for (int i = first; i < nets; ++i) {
         FwdArgs fb = fb0;
         fb.net0 = i;
         fb.nets = 1;
@@ -1368,6 +1430,38 @@ int32_t launch_mlp_fb_act_form(const FwdArgs& fb0, const FbLoss& fl, bool shadow
         if (rc) return rc;
     }
     return HGYM_OK;
+}
+
+// The ACTOR's update tile with the mirror loss in its head (HgymPPOConfig.mirror_coef > 0): one kernel per first hidden width, input
+// form and activation form (GA), the actor alone -- the critic's and the auxiliary head's tiles run through the kernels they always had
+// (mlp_fb_kernel from net 1 on, launch_mlp_fb_act_form with first = 1), so those nets' bits cannot move.  hgym_update_mirror.hip holds
+// the ELU(1) kernels, hgym_update_act_mirror.hip the generic ones.
+template <int G1, bool XB16, bool GA>
+__global__ __launch_bounds__(1024) void mlp_fb_mirror_kernel(const FwdArgs a, const FbLoss L, const FbMirror mr) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    fb_body<G1, false, XB16, false, GA, true>(a, L, a.net[0], true, smem, &mr);
+}
+template <int G1, bool XB16, bool GA>
+int32_t launch_mlp_fb_mirror_one(const FwdArgs& fb, const FbLoss& fl, const FbMirror& mr, int tiles, size_t lds, hipStream_t s) {
+    const int32_t rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&mlp_fb_mirror_kernel<G1, XB16, GA>), lds, "mlp_fb_mirror_kernel");
+    if (rc) return rc;
+    hipLaunchKernelGGL((mlp_fb_mirror_kernel<G1, XB16, GA>), dim3(tiles), dim3(1024), lds, s, fb, fl, mr);
+    return HGYM_OK;
+}
+template <bool GA>
+int32_t launch_mlp_fb_mirror_form(const FwdArgs& fb0, const FbLoss& fl, const FbMirror& mr0, bool shadow, int tiles, hipStream_t s) {
+    FwdArgs fb = fb0;
+    fb.net0 = 0;
+    fb.nets = 1;
+    FbMirror mr = mr0;
+    size_t lds = (size_t)fb_lds_bytes(fb.net[0]);
+    mr.stage = lds + FB_MIRROR_LDS <= FB_LDS_LIMIT ? 1 : 0;      // no room: the head reads the target from memory
+    if (mr.stage) lds += FB_MIRROR_LDS;
+    const int g1 = fb.net[0].layer[0].NB / 16;         // first hidden width 256 / 512 / 768
+    if (g1 == 1) return shadow ? launch_mlp_fb_mirror_one<1, true, GA>(fb, fl, mr, tiles, lds, s) : launch_mlp_fb_mirror_one<1, false, GA>(fb, fl, mr, tiles, lds, s);
+    if (g1 == 2) return shadow ? launch_mlp_fb_mirror_one<2, true, GA>(fb, fl, mr, tiles, lds, s) : launch_mlp_fb_mirror_one<2, false, GA>(fb, fl, mr, tiles, lds, s);
+    if (g1 == 3) return shadow ? launch_mlp_fb_mirror_one<3, true, GA>(fb, fl, mr, tiles, lds, s) : launch_mlp_fb_mirror_one<3, false, GA>(fb, fl, mr, tiles, lds, s);
+    return HGYM_E_UNSUPPORTED;
 }
 
 // ================================================================================================ per-minibatch loss scalars
@@ -1396,6 +1490,7 @@ struct ScalArgs {
                            // consecutive rows are added first, ((p0 + p1) + p2) + p3 in fp32 -- the sum mlp_fb_kernel's 64-row tile forms
                            // over its four head waves -- and nblocks counts those groups
     const float* sigma;    // HGYM_STD_LOG: the derived sigma block -- the std gradient leaves as d/d(log sigma) = d/d(sigma) * sigma; null: as it is
+    double* mirror_sums;   // the mirror loss (HgymBatch.mirror_sums): [0] += the minibatch's MSE, [1] += 1; null: off
 };
 // ppo.py:140-145, the one copy of the rule (ppo_scalars_block here, apply_prologue in hgym_net.hip).  The reference compares the fp32
 // 0-dim tensor kl_mean with python floats, which torch rounds to fp32: the comparisons are fp32 ones against float32(desired_kl * 2) and
@@ -1489,6 +1584,10 @@ __device__ __forceinline__ void ppo_scalars_block(const ScalArgs& a, int tid, in
         if (q >= LP_DBIAS_MU && q < LP_DBIAS_V && q - LP_DBIAS_MU < A && a.grads_bmu) a.grads_bmu[q - LP_DBIAS_MU] = (float)t;
         if (q == LP_DBIAS_V && a.grads_bv) a.grads_bv[0] = (float)t;
         if (q == LP_AUX && a.aux_No > 0) opt[HGYM_OPT_AUX_SUM] += t / ((double)B * (double)a.aux_No);    // auxiliary head's MSE (the fused kernel's third grid row)
+        if (q == LP_MIRROR && a.mirror_sums) {      // the mirror loss's MSE: the tile partials in the fixed order of every other sum
+            a.mirror_sums[0] += t / ((double)B * (double)A);
+            a.mirror_sums[1] += 1.0;
+        }
     }
 }
 

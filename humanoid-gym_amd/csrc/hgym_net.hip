@@ -17,13 +17,19 @@
 #include "hgym_gemm.hpp"
 #include "hgym_fused.hpp"
 #include "hgym_norm.hpp"
+#include "hgym_loss.hpp"
 
 namespace hgym {
 
 // hgym_update.hip
 int32_t launch_mlp_fb(const FwdArgs& fb, const FbLoss& fl, bool shadow, bool unclipped, int tiles, int nets, size_t lds, hipStream_t s);
 // hgym_update_act.hip, hgym_fwd_act.hip: the same tiles with any resolved activation, one launch per net
-int32_t launch_mlp_fb_act(const FwdArgs& fb, const FbLoss& fl, bool shadow, bool unclipped, int tiles, int nets, hipStream_t s);
+int32_t launch_mlp_fb_act(const FwdArgs& fb, const FbLoss& fl, bool shadow, bool unclipped, int tiles, int nets, hipStream_t s, int first);
+// hgym_update_mirror.hip, hgym_update_act_mirror.hip: the actor's tiles with the mirror loss in their head (HgymPPOConfig.mirror_coef > 0)
+int32_t launch_mlp_fb_mirror(const FwdArgs& fb, const FbLoss& fl, const FbMirror& mr, bool shadow, int tiles, hipStream_t s);
+int32_t launch_mlp_fb_act_mirror(const FwdArgs& fb, const FbLoss& fl, const FbMirror& mr, bool shadow, int tiles, hipStream_t s);
+// hgym_loss_mirror.hip: ppo_loss_kernel<.., ML = true>, the layer-by-layer path's loss with the mirror loss
+int32_t launch_ppo_loss_mirror(const LossArgs& a, bool bf16, bool unclipped, int nblocks, hipStream_t s);
 int32_t launch_mlp_fwd_act(const FwdArgs& a, int nets, bool wide, int64_t dbg_tiles, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------ layouts
@@ -358,142 +364,7 @@ __global__ __launch_bounds__(256) void act_sample_kernel(int M, int A, const flo
     logp[m] = lp;
 }
 
-// One thread per sample of the minibatch: ppo.py:128-168 forward scalars + the hand-written backward of `loss`
-// w.r.t. mu, std and V (oracle/ppo_oracle.py:ppo_loss_and_grads is the executable specification).
-struct LossArgs {
-    HgymBatch b;
-    int A;                       // num_actions
-    const float* mu;             // [B][A] current policy mean (fp32 output of the actor)
-    const float* val;            // [B]    current value
-    const float* std_;           // [A]
-    float clip, value_coef, entropy_coef;
-    void* dmu;  int64_t ld_dmu;  // [B][Ncp] operand type
-    void* dmuT; int64_t ld_t;    // [A16][Mp]
-    void* dval; int64_t ld_dval; // [B][Ncp]
-    void* dvalT;                 // [16][Mp]
-    int Bp;                      // contraction padding of B for this call
-    float* partials;             // [gridDim.x][32]: surrogate, value loss, entropy, kl, dstd[12], sum dmu[12], sum dval, pad
-};
-
-// VU: the unclipped value loss (R - V)^2 (HgymPPOConfig.value_loss_unclipped); a template parameter, so that the clipped kernels stay as
-// they were
-template <typename T, bool VU = false>
-__global__ __launch_bounds__(256) void ppo_loss_kernel(const LossArgs a) {
-    __shared__ float red[4][LOSS_PARTIALS];
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int B = a.b.B, A = a.A;
-    const float invB = 1.0f / (float)B;
-    float acc[LOSS_PARTIALS];
-#pragma unroll
-    for (int k = 0; k < LOSS_PARTIALS; ++k) acc[k] = 0.0f;
-    T* dmu = (T*)a.dmu;
-    T* dmuT = (T*)a.dmuT;
-    T* dval = (T*)a.dval;
-    T* dvalT = (T*)a.dvalT;
-    if (i < B) {
-        const int64_t r = a.b.idx[i];
-        const float adv = a.b.advantages[r], ret = a.b.returns[r], vold = a.b.values[r], lpold = a.b.logp[r];
-        const float v = a.val[i];
-        float lp = 0.0f, ent = 0.0f, kl = 0.0f;
-        float diff[16], sg[16];
-        // the gathered rows (actions, old mu, old sigma: A floats each, at a random row r) and this sample's mu row.  For the
-        // XBot-L width (A = 12: 48-byte rows, 16-byte aligned) they are fetched as three 16-byte loads each: a 4-byte load
-        // per element costs the texture path one cache line per lane PER ELEMENT (the rows are scattered), a vector load one
-        // per lane per 4 elements -- the kernel was bound by exactly that (31 us for 61 440 samples).
-        float rowm[16], rowa[16], rowmo[16], rowso[16];
-        if (A == 12) {
-#pragma unroll
-            for (int v = 0; v < 3; ++v) {
-                const float4 qm = reinterpret_cast<const float4*>(a.mu + (int64_t)i * 12)[v];
-                const float4 qa = reinterpret_cast<const float4*>(a.b.actions + r * 12)[v];
-                const float4 qo = reinterpret_cast<const float4*>(a.b.mu + r * 12)[v];
-                const float4 qs = reinterpret_cast<const float4*>(a.b.sigma + r * 12)[v];
-                rowm[4 * v] = qm.x; rowm[4 * v + 1] = qm.y; rowm[4 * v + 2] = qm.z; rowm[4 * v + 3] = qm.w;
-                rowa[4 * v] = qa.x; rowa[4 * v + 1] = qa.y; rowa[4 * v + 2] = qa.z; rowa[4 * v + 3] = qa.w;
-                rowmo[4 * v] = qo.x; rowmo[4 * v + 1] = qo.y; rowmo[4 * v + 2] = qo.z; rowmo[4 * v + 3] = qo.w;
-                rowso[4 * v] = qs.x; rowso[4 * v + 1] = qs.y; rowso[4 * v + 2] = qs.z; rowso[4 * v + 3] = qs.w;
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                if (j >= A) continue;
-                rowm[j] = a.mu[(int64_t)i * A + j];
-                rowa[j] = a.b.actions[r * A + j];
-                rowmo[j] = a.b.mu[r * A + j];
-                rowso[j] = a.b.sigma[r * A + j];
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            diff[j] = 0.0f;
-            sg[j] = 1.0f;
-            if (j >= A) continue;
-            const float m = rowm[j];
-            const float s = m * 0.0f + a.std_[j];
-            const float act = rowa[j];
-            const float mo = rowmo[j], so = rowso[j];
-            const float d = act - m;
-            diff[j] = d;
-            sg[j] = s;
-            lp += -(d * d) / (2.0f * s * s) - logf(s) - 0.9189385332046727f;
-            ent += 0.5f + 0.9189385332046727f + logf(s);
-            kl += logf(s / so + 1.e-5f) + (so * so + (mo - m) * (mo - m)) / (2.0f * (s * s)) - 0.5f;
-        }
-        const float ratio = expf(lp - lpold);
-        const float s1 = -adv * ratio;
-        const float s2 = -adv * clampf(ratio, 1.0f - a.clip, 1.0f + a.clip);
-        const float surr = fmaxf(s1, s2);
-        // backward (torch.max splits ties evenly between its operands; clamp passes gradient on the closed range)
-        const float in_range = (ratio >= 1.0f - a.clip && ratio <= 1.0f + a.clip) ? 1.0f : 0.0f;
-        const float w1 = s1 > s2 ? 1.0f : (s1 == s2 ? 0.5f : 0.0f);
-        const float d_lp = (-adv) * (w1 + (1.0f - w1) * in_range) * invB * ratio;
-        float vl, d_v;
-        if constexpr (VU) {         // (R - V)^2: the stored old value plays no part
-            vl = (v - ret) * (v - ret);
-            d_v = a.value_coef * invB * (2.0f * (v - ret));
-        } else {
-            const float vc = vold + clampf(v - vold, -a.clip, a.clip);
-            const float l1 = (v - ret) * (v - ret), l2 = (vc - ret) * (vc - ret);
-            vl = fmaxf(l1, l2);
-            const float v_in = ((v - vold) >= -a.clip && (v - vold) <= a.clip) ? 1.0f : 0.0f;
-            const float u1 = l1 > l2 ? 1.0f : (l1 == l2 ? 0.5f : 0.0f);
-            d_v = a.value_coef * invB * (u1 * 2.0f * (v - ret) + (1.0f - u1) * 2.0f * (vc - ret) * v_in);
-        }
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            if (j >= A) continue;
-            const float s = sg[j], d = diff[j];
-            const float g_mu = d_lp * d / (s * s);
-            const float g_sg = d_lp * (d * d / (s * s * s) - 1.0f / s) - (a.entropy_coef * invB) / s;
-            if (j < 12) {
-                acc[LP_DSTD + j] = g_sg;
-                acc[LP_DBIAS_MU + j] = g_mu;
-            }
-            dmu[(int64_t)i * a.ld_dmu + j] = from_f32<T>(g_mu);
-            dmuT[(int64_t)j * a.ld_t + i] = from_f32<T>(g_mu);
-        }
-        dval[(int64_t)i * a.ld_dval] = from_f32<T>(d_v);
-        dvalT[i] = from_f32<T>(d_v);
-        acc[LP_SURROGATE] = surr;
-        acc[LP_VALUE] = vl;
-        acc[LP_ENTROPY] = ent;
-        acc[LP_KL] = kl;
-        acc[LP_DBIAS_V] = d_v;
-    } else if (i < a.Bp) {   // zero the contraction padding of the gradients
-        for (int j = 0; j < A; ++j) dmuT[(int64_t)j * a.ld_t + i] = from_f32<T>(0.0f);
-        dvalT[i] = from_f32<T>(0.0f);
-    }
-#pragma unroll
-    for (int k = 0; k < LOSS_PARTIALS; ++k) {
-        float s = acc[k];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < LOSS_PARTIALS) a.partials[(int64_t)blockIdx.x * LOSS_PARTIALS + threadIdx.x] =
-        red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-}
+// ppo_loss_kernel: hgym_loss.hpp (its instantiations with the mirror loss live in hgym_loss_mirror.hip)
 
 // opt_state: the HGYM_OPT_* slots of include/hgym.h.
 // grads_bmu / grads_bv (fused path only): gradients of the two head biases = column sums of the head gradients.
@@ -1108,7 +979,13 @@ struct GemmPath : NetBase {
         float* mu = at<float>(w.net[0].out_f32);
         float* val = at<float>(w.net[1].out_f32);
         // (no zeroing of net.grads: ppo_scalars_kernel writes std's gradient, reduce_slabs_kernel every weight and bias segment)
-        int32_t rc = forward(0, B, b.obs, cfg.num_obs, b.idx, mu, A, true);
+        const bool mirror = ppo.mirror_coef > 0.0f;
+        int32_t rc = HGYM_OK;
+        if (mirror) {     // the pre-pass: the partner rows' raw mu under the current parameters (forward only: no gradient through the target)
+            rc = forward(0, B, b.obs, cfg.num_obs, b.pair_idx, b.mirror_target, A, false);
+            if (rc) return rc;
+        }
+        rc = forward(0, B, b.obs, cfg.num_obs, b.idx, mu, A, true);
         if (rc) return rc;
         rc = forward(1, B, b.priv, cfg.num_priv, b.idx, val, 1, true);
         if (rc) return rc;
@@ -1136,13 +1013,24 @@ struct GemmPath : NetBase {
         a.dvalT = at<T>(lc.dYT);
         a.Bp = Bp;
         a.partials = at<float>(w.partials);
+        if (mirror) {
+            a.mt = b.mirror_target;
+            a.m_src = b.mirror_act_src;
+            a.m_sign = b.mirror_act_sign;
+            a.m_g = 2.0f * ppo.mirror_coef / ((float)B * (float)A);
+        }
         prof_begin(HGYM_PROF_LOSS, s);
         if (ppo.value_loss_unclipped) hipLaunchKernelGGL((ppo_loss_kernel<T, true>), dim3(nblocks), dim3(256), 0, s, a);
         else hipLaunchKernelGGL((ppo_loss_kernel<T>), dim3(nblocks), dim3(256), 0, s, a);
+        if (mirror) {      // behind it: d mu with the term, the LP_DBIAS_MU / LP_MIRROR partials (hgym_loss.hpp)
+            const int32_t rc_ml = launch_ppo_loss_mirror(a, sizeof(T) == 2, ppo.value_loss_unclipped != 0, nblocks, s);
+            if (rc_ml) return rc_ml;
+        }
         prof_end(HGYM_PROF_LOSS, s, (double)B * (4.0 * (5 * A + 6) + (double)sizeof(T) * (2 * A + 2)));
         HG_CHECK_LAUNCH("ppo_loss_kernel");
-        const ScalArgs sc = {nblocks, B, A, 0, at<float>(w.partials), net.grads, nullptr, nullptr, net.grads + w.P, net.opt_state,
-                             (double)ppo.beta1, (double)ppo.beta2, 0, 0, 0.0f, 0.0, 0.0, 1, grad_sigma()};
+        ScalArgs sc = {nblocks, B, A, 0, at<float>(w.partials), net.grads, nullptr, nullptr, net.grads + w.P, net.opt_state,
+                       (double)ppo.beta1, (double)ppo.beta2, 0, 0, 0.0f, 0.0, 0.0, 1, grad_sigma()};
+        if (mirror) sc.mirror_sums = b.mirror_sums;      // (else null: off)
         hipLaunchKernelGGL(ppo_scalars_kernel, dim3(1), dim3(512), 0, s, sc);
         HG_CHECK_LAUNCH("ppo_scalars_kernel");
         rc = backward(0, B);
@@ -1416,6 +1304,14 @@ struct FusedPath : NetBase {
         // profiles/r04_fb2_128row_tiles_negative_result.txt; its source is profiles/r04_fb2_128row_kernel.patch; round 6 rebuilt the idea on role-specialised wavefronts at 64 and 128 rows: profiles/r06_fb3_role_specialised_wavefronts.txt.)
         const int tiles = (int)round_up(B, 64) / 64;
         HG_REQUIRE(tiles <= MAX_LOSS_BLOCKS, HGYM_E_UNSUPPORTED, "minibatch %d too large for the loss partial buffer", B);
+        const bool mirror = ppo.mirror_coef > 0.0f;
+        if (mirror) {
+            // the mirror loss's pre-pass: the raw mu of the partner rows under the current parameters, forward only (no gradient through
+            // the target).  It gathers the fp32 rows, not their bf16 shadow: the forward tiles that gather by index from a shadow exist in
+            // the update kernels only, and the shadow is bf16(fp32 row) exactly -- the same bits reach the first layer either way.
+            const int32_t rc_pre = forward(0, B, b.obs, cfg.num_obs, b.pair_idx, b.mirror_target, A, false);
+            if (rc_pre) return rc_pre;
+        }
         {   // forward + PPO loss + dZ chain of both nets: ONE launch (hgym_fused.hpp: mlp_fb_kernel)
             const NetIO io[3] = {{b.obs, cfg.num_obs, at<float>(w.net[0].out_f32), A},
                                  {b.priv, cfg.num_priv, at<float>(w.net[1].out_f32), 1},
@@ -1454,8 +1350,26 @@ struct FusedPath : NetBase {
             fb.nets = nets;
             fb.dbg = phase_buffer((int64_t)tiles * nets);
             prof_begin(HGYM_PROF_MLP_FWD, s);
-            const int32_t rc_fb = act_is_elu1(w.act) ? launch_mlp_fb(fb, fl, shadow, ppo.value_loss_unclipped != 0, tiles, nets, lds, s)      // (hgym_update.hip: the kernel's own code object)
-                                                     : launch_mlp_fb_act(fb, fl, shadow, ppo.value_loss_unclipped != 0, tiles, nets, s);
+            int32_t rc_fb = HGYM_OK;
+            if (mirror) {
+                // the actor's tiles through the kernels with the mirror loss in their head (their own launch), every other net's through
+                // the kernels they always had, from net 1 on
+                const FbMirror mr = {b.mirror_target, b.mirror_act_src, b.mirror_act_sign, 2.0f * ppo.mirror_coef / ((float)B * (float)A), 0};
+                rc_fb = act_is_elu1(w.act) ? launch_mlp_fb_mirror(fb, fl, mr, shadow, tiles, s) : launch_mlp_fb_act_mirror(fb, fl, mr, shadow, tiles, s);
+                if (rc_fb) return rc_fb;
+                if (act_is_elu1(w.act)) {
+                    FwdArgs rest = fb;
+                    rest.net0 = 1;
+                    rest.nets = nets - 1;
+                    if (rest.dbg) rest.dbg += (int64_t)tiles * 8;      // phase stamps: behind the actor's slots
+                    rc_fb = launch_mlp_fb(rest, fl, shadow, ppo.value_loss_unclipped != 0, tiles, nets - 1, lds, s);
+                } else {
+                    rc_fb = launch_mlp_fb_act(fb, fl, shadow, ppo.value_loss_unclipped != 0, tiles, nets, s, 1);
+                }
+            } else {
+                rc_fb = act_is_elu1(w.act) ? launch_mlp_fb(fb, fl, shadow, ppo.value_loss_unclipped != 0, tiles, nets, lds, s)      // (hgym_update.hip: the kernel's own code object)
+                                           : launch_mlp_fb_act(fb, fl, shadow, ppo.value_loss_unclipped != 0, tiles, nets, s, 0);
+            }
             if (rc_fb) return rc_fb;
             double flops = 0.0;
             for (int i = 0; i < nets; ++i) {
@@ -1467,10 +1381,11 @@ struct FusedPath : NetBase {
         }
         // the minibatch's loss scalars (per-tile partials -> opt_state, std / head-bias gradients, KL slot): one extra workgroup of
         // the weight-gradient launch that follows anyway (it needs nothing but the partials mlp_fb_kernel has just written)
-        const ScalArgs sc = {tiles, B, A, nets == 3 ? w.net[2].layer[3].N : 0, at<float>(w.partials), net.grads,
+        ScalArgs sc = {tiles, B, A, nets == 3 ? w.net[2].layer[3].N : 0, at<float>(w.partials), net.grads,
                              net.grads + w.net[0].layer[3].b_off, net.grads + w.net[1].layer[3].b_off, net.grads + w.P, net.opt_state,
                              (double)ppo.beta1, (double)ppo.beta2, prologue_in_grad(ppo) ? 1 : 0, ppo.adaptive_lr, ppo.desired_kl, ppo.lr_min,
                              ppo.lr_max, 1, grad_sigma()};
+        if (mirror) sc.mirror_sums = b.mirror_sums;      // (else null: off)
         int32_t rc = dw(nets, B, sc, shadow ? &b : nullptr);
         if (rc) return rc;
         if (w.nnets > 2 && nets == 2) {
@@ -1534,11 +1449,21 @@ static int32_t check_ppo(const HgymPPOConfig* ppo) {
     HG_REQUIRE(ppo, HGYM_E_BADARG, "null ppo");
     HG_REQUIRE(ppo->value_loss_unclipped == 0 || ppo->value_loss_unclipped == 1, HGYM_E_BADARG,
                "HgymPPOConfig.value_loss_unclipped=%d (0: clipped value loss, 1: unclipped)", ppo->value_loss_unclipped);
+    // (written so that a NaN fails it)
+    HG_REQUIRE(ppo->mirror_coef >= 0.0f && ppo->mirror_coef < INFINITY, HGYM_E_BADARG,
+               "HgymPPOConfig.mirror_coef=%g must be finite and >= 0 (0: no mirror loss)", (double)ppo->mirror_coef);
     return HGYM_OK;
 }
 
-static int32_t check_batch(const WsLayout& w, const HgymBatch* b) {
+static int32_t check_batch(const WsLayout& w, const HgymPPOConfig* ppo, const HgymBatch* b) {
     HG_REQUIRE(b, HGYM_E_BADARG, "null batch");
+    if (ppo->mirror_coef > 0.0f) {
+        HG_REQUIRE(b->pair_idx && b->mirror_act_src && b->mirror_act_sign && b->mirror_target && b->mirror_sums, HGYM_E_BADARG,
+                   "HgymPPOConfig.mirror_coef > 0 needs HgymBatch.pair_idx, mirror_act_src, mirror_act_sign, mirror_target and mirror_sums");
+        HG_REQUIRE(((uintptr_t)b->mirror_target & 15) == 0, HGYM_E_BADARG, "HgymBatch.mirror_target must be 16-byte aligned");
+        HG_REQUIRE(((uintptr_t)b->mirror_sums & 7) == 0 && ((uintptr_t)b->pair_idx & 7) == 0, HGYM_E_BADARG,
+                   "HgymBatch.mirror_sums / pair_idx must be 8-byte aligned");
+    }
     HG_REQUIRE(b->obs && b->priv && b->actions && b->values && b->advantages && b->returns && b->logp && b->mu && b->sigma && b->idx,
                HGYM_E_BADARG, "null batch tensor");
     HG_REQUIRE(b->B > 0 && b->B <= w.maxM, HGYM_E_SHAPE, "minibatch %d exceeds max_batch %lld", b->B, (long long)w.maxM);
@@ -1712,7 +1637,7 @@ int32_t hgym_ppo_grad(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const 
         int32_t rc = check_ppo(ppo);
         if (rc) return rc;
         HG_REQUIRE(net->grads && net->opt_state, HGYM_E_BADARG, "null grads / opt_state");
-        rc = check_batch(R.w, batch);
+        rc = check_batch(R.w, ppo, batch);
         return rc ? rc : R.grad(*ppo, *batch, -1);
     });
 }
@@ -1724,7 +1649,7 @@ int32_t hgym_ppo_grad_part(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, c
         if (rc) return rc;
         HG_REQUIRE(part == 0 || part == 1, HGYM_E_BADARG, "part=%d (0 or 1)", part);
         HG_REQUIRE(net->grads && net->opt_state, HGYM_E_BADARG, "null grads / opt_state");
-        rc = check_batch(R.w, batch);
+        rc = check_batch(R.w, ppo, batch);
         return rc ? rc : R.grad(*ppo, *batch, part);
     });
 }

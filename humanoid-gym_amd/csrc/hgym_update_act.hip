@@ -6,11 +6,12 @@
 
 namespace hgym {
 
-int32_t launch_mlp_fb_act_unclipped(const FwdArgs& fb, const FbLoss& fl, bool shadow, int tiles, int nets, hipStream_t s);
+int32_t launch_mlp_fb_act_unclipped(const FwdArgs& fb, const FbLoss& fl, bool shadow, int tiles, int nets, hipStream_t s, int first);
 
-int32_t launch_mlp_fb_act(const FwdArgs& fb, const FbLoss& fl, bool shadow, bool unclipped, int tiles, int nets, hipStream_t s) {
-    if (unclipped) return launch_mlp_fb_act_unclipped(fb, fl, shadow, tiles, nets, s);
-    return launch_mlp_fb_act_form<false>(fb, fl, shadow, tiles, nets, s);
+// first: the first net launched (0; 1 when the actor's tiles carry the mirror loss -- hgym_update_act_mirror.hip launches those)
+int32_t launch_mlp_fb_act(const FwdArgs& fb, const FbLoss& fl, bool shadow, bool unclipped, int tiles, int nets, hipStream_t s, int first) {
+    if (unclipped) return launch_mlp_fb_act_unclipped(fb, fl, shadow, tiles, nets, s, first);
+    return launch_mlp_fb_act_form<false>(fb, fl, shadow, tiles, nets, s, first);
 }
 
 }  // namespace hgym

@@ -4,8 +4,8 @@
 
 namespace hgym {
 
-int32_t launch_mlp_fb_act_unclipped(const FwdArgs& fb, const FbLoss& fl, bool shadow, int tiles, int nets, hipStream_t s) {
-    return launch_mlp_fb_act_form<true>(fb, fl, shadow, tiles, nets, s);
+int32_t launch_mlp_fb_act_unclipped(const FwdArgs& fb, const FbLoss& fl, bool shadow, int tiles, int nets, hipStream_t s, int first) {
+    return launch_mlp_fb_act_form<true>(fb, fl, shadow, tiles, nets, s, first);
 }
 
 }  // namespace hgym

@@ -122,6 +122,21 @@ class PPOConfig(C.Structure):
                 ("aux_coef", C.c_float), ("grad_norm_ready", C.c_int32),
                 ("value_loss_unclipped", C.c_int32)]
 
+    # HgymPPOConfig.mirror_coef (float): appended behind value_loss_unclipped, in the four bytes that were the struct's tail padding (the two
+    # doubles align it to 8) -- the size and every earlier offset are what they were, so `_fields_` still ends where its tests pin it and
+    # the new member is reached at its offset.  A fresh PPOConfig() is zero-filled, padding included: off.
+    @property
+    def mirror_coef(self):
+        return C.c_float.from_address(C.addressof(self) + MIRROR_COEF_OFFSET).value
+
+    @mirror_coef.setter
+    def mirror_coef(self, v):
+        C.c_float.from_address(C.addressof(self) + MIRROR_COEF_OFFSET).value = v
+
+
+MIRROR_COEF_OFFSET = PPOConfig.value_loss_unclipped.offset + 4
+assert MIRROR_COEF_OFFSET + 4 <= C.sizeof(PPOConfig)
+
 
 class Net(C.Structure):
     _fields_ = [("params", c_float_p), ("grads", c_float_p), ("adam_m", c_float_p), ("adam_v", c_float_p),
@@ -137,7 +152,10 @@ class Batch(C.Structure):
     _fields_ = [("obs", c_float_p), ("priv", c_float_p), ("actions", c_float_p), ("values", c_float_p),
                 ("advantages", c_float_p), ("returns", c_float_p), ("logp", c_float_p), ("mu", c_float_p),
                 ("sigma", c_float_p), ("idx", c_i64_p), ("B", C.c_int32),
-                ("obs_bf16", C.c_void_p), ("priv_bf16", C.c_void_p), ("num_rows", C.c_int64)]
+                ("obs_bf16", C.c_void_p), ("priv_bf16", C.c_void_p), ("num_rows", C.c_int64),
+                # the mirror loss (PPOConfig.mirror_coef > 0; a zero-filled tail is off)
+                ("pair_idx", c_i64_p), ("mirror_act_src", C.POINTER(C.c_int32)), ("mirror_act_sign", c_float_p),
+                ("mirror_target", c_float_p), ("mirror_sums", c_f64_p)]
 
 
 class ObsShadow(C.Structure):

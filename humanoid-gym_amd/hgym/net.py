@@ -77,8 +77,10 @@ def make_net_config(num_obs, num_priv, num_actions, actor_hidden, critic_hidden,
 
 
 def make_ppo_config(clip_param=0.2, value_loss_coef=1.0, entropy_coef=0.001, max_grad_norm=1.0, desired_kl=0.01,
-                    adaptive=True, world_size=1, grad_norm_ready=False, aux_coef=0.0, clipped_value_loss=True):
-    """clipped_value_loss: the reference's use_clipped_value_loss (False: the value loss (R - V)^2, HgymPPOConfig.value_loss_unclipped)."""
+                    adaptive=True, world_size=1, grad_norm_ready=False, aux_coef=0.0, clipped_value_loss=True, mirror_coef=0.0):
+    """clipped_value_loss: the reference's use_clipped_value_loss (False: the value loss (R - V)^2, HgymPPOConfig.value_loss_unclipped).
+    mirror_coef: weight of the mirror loss (HgymPPOConfig.mirror_coef, rsl_rl's mirror_loss_coeff; 0: off -- make_batch's pair_idx / mirror
+    are then ignored)."""
     p = L.PPOConfig()
     p.clip_param, p.value_loss_coef, p.entropy_coef = clip_param, value_loss_coef, entropy_coef
     p.max_grad_norm, p.desired_kl = max_grad_norm, desired_kl
@@ -89,6 +91,7 @@ def make_ppo_config(clip_param=0.2, value_loss_coef=1.0, entropy_coef=0.001, max
     p.aux_coef = float(aux_coef)
     p.grad_norm_ready = 1 if (grad_norm_ready and int(world_size) == 1) else 0    # see HgymPPOConfig
     p.value_loss_unclipped = 0 if clipped_value_loss else 1
+    p.mirror_coef = float(mirror_coef)
     return p
 
 
@@ -348,9 +351,12 @@ def norm_layout(cfg):
     return list(out)
 
 
-def make_batch(obs, priv, actions, values, advantages, returns, logp, mu, sigma, idx, obs_bf16=None, priv_bf16=None):
+def make_batch(obs, priv, actions, values, advantages, returns, logp, mu, sigma, idx, obs_bf16=None, priv_bf16=None, pair_idx=None, mirror=None):
     """All (T*N, *) flattened, contiguous fp32; idx int64 (B,).  obs_bf16 / priv_bf16: optional (T*N, ld) bfloat16 shadows of obs /
-    priv (ld = NetBuffers.shadow_ld), both or neither."""
+    priv (ld = NetBuffers.shadow_ld), both or neither.
+    The mirror loss (make_ppo_config(mirror_coef > 0); both or neither): pair_idx int64 (B,), the storage row holding the mirrored observation
+    of every row of idx; mirror = (act_src int32 (A,), act_sign fp32 (A,), target fp32 scratch of at least B * A elements, 16-byte aligned,
+    sums float64 (2,)) -- device tensors the caller keeps alive; sums[0] += the minibatch's MSE, sums[1] += 1."""
     for t in (obs, priv, actions, values, advantages, returns, logp, mu, sigma):
         assert t.is_contiguous() and t.dtype == torch.float32
     assert idx.dtype == torch.int64 and idx.is_contiguous()
@@ -360,8 +366,20 @@ def make_batch(obs, priv, actions, values, advantages, returns, logp, mu, sigma,
         assert obs_bf16.dtype == torch.bfloat16 and priv_bf16.dtype == torch.bfloat16 and obs_bf16.is_contiguous() and priv_bf16.is_contiguous()
         assert obs_bf16.shape[0] == obs.shape[0] and priv_bf16.shape[0] == priv.shape[0]
         sb = (C.c_void_p(obs_bf16.data_ptr()), C.c_void_p(priv_bf16.data_ptr()))
-    return L.Batch(L.fptr(obs), L.fptr(priv), L.fptr(actions), L.fptr(values), L.fptr(advantages), L.fptr(returns), L.fptr(logp),
-                   L.fptr(mu), L.fptr(sigma), L.i64ptr(idx), int(idx.numel()), sb[0], sb[1], int(obs.shape[0]))
+    b = L.Batch(L.fptr(obs), L.fptr(priv), L.fptr(actions), L.fptr(values), L.fptr(advantages), L.fptr(returns), L.fptr(logp),
+                L.fptr(mu), L.fptr(sigma), L.i64ptr(idx), int(idx.numel()), sb[0], sb[1], int(obs.shape[0]))
+    assert (pair_idx is None) == (mirror is None)
+    if mirror is not None:
+        src, sign, target, sums = mirror
+        A = int(actions.shape[1])
+        assert pair_idx.dtype == torch.int64 and pair_idx.is_contiguous() and pair_idx.numel() == idx.numel()
+        assert src.dtype == torch.int32 and sign.dtype == torch.float32 and src.numel() == A and sign.numel() == A
+        assert src.is_contiguous() and sign.is_contiguous()
+        assert target.dtype == torch.float32 and target.is_contiguous() and target.numel() >= idx.numel() * A
+        assert sums.dtype == torch.float64 and sums.is_contiguous() and sums.numel() >= 2
+        b.pair_idx, b.mirror_act_src, b.mirror_act_sign = L.i64ptr(pair_idx), C.cast(src.data_ptr(), C.POINTER(C.c_int32)), L.fptr(sign)
+        b.mirror_target, b.mirror_sums = L.fptr(target), L.f64ptr(sums)
+    return b
 
 
 DIAG_KEYS = ("samples", "clip_fraction", "kl", "approx_kl", "ratio_mean", "ratio_max", "ratio_min", "surrogate", "entropy",

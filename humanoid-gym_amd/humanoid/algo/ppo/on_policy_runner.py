@@ -199,11 +199,43 @@ class _EpisodeLog:
         return tuple(deque((float(ring[j, s]) for s in slots), maxlen=self.RING) for j in (0, 1))
 
 
+SYMMETRY_KEYS = ("mirror_loss_coef", "symmetry_augmentation", "symmetry_cfg")      # native keys beside `symmetry`; none is a parameter of PPO.__init__
+
+
 def _split_algorithm_cfg(alg_cfg):
     """The train config's algorithm block -> (keyword arguments of PPO.__init__, symmetry on?).  `symmetry` is a native key (absent:
-    off), not a parameter of the reference's PPO: it is taken out here and becomes PPO.symmetry."""
+    off), not a parameter of the reference's PPO: it is taken out here and becomes PPO.symmetry.  The mirror loss's keys (SYMMETRY_KEYS)
+    are taken out as well; _split_symmetry_cfg reads them."""
     kwargs = dict(alg_cfg)
+    for k in SYMMETRY_KEYS:
+        kwargs.pop(k, None)
     return kwargs, bool(kwargs.pop("symmetry", False))
+
+
+def _split_symmetry_cfg(alg_cfg):
+    """The train config's algorithm block -> (augmentation on?, mirror_loss_coef).  Native keys: `symmetry` (augmentation, as ever),
+    `symmetry_augmentation` (default True; False with `symmetry` keeps the tables but not the augmentation) and `mirror_loss_coef`
+    (default 0: off).  rsl_rl's spelling is accepted too: `symmetry_cfg = {use_data_augmentation, use_mirror_loss, mirror_loss_coeff}`;
+    a native key and its rsl_rl twin that disagree: ValueError.  The caller's dict is left alone."""
+    augmentation = bool(alg_cfg.get("symmetry", False)) and bool(alg_cfg.get("symmetry_augmentation", True))
+    coef = float(alg_cfg.get("mirror_loss_coef", 0.0) or 0.0)
+    sc = alg_cfg.get("symmetry_cfg")
+    if sc:
+        sc = dict(sc)
+        unknown = set(sc) - {"use_data_augmentation", "use_mirror_loss", "mirror_loss_coeff"}
+        if unknown:
+            raise ValueError("algorithm.symmetry_cfg: unknown keys %s (use_data_augmentation, use_mirror_loss, mirror_loss_coeff)" % sorted(unknown))
+        if "use_data_augmentation" in sc:
+            aug = bool(sc["use_data_augmentation"])
+            if ("symmetry" in alg_cfg or "symmetry_augmentation" in alg_cfg) and aug != augmentation:
+                raise ValueError("algorithm.symmetry_cfg.use_data_augmentation=%r disagrees with algorithm.symmetry / symmetry_augmentation" % (aug,))
+            augmentation = aug
+        c = float(sc.get("mirror_loss_coeff", 0.0) or 0.0) if sc.get("use_mirror_loss", False) else 0.0
+        if "use_mirror_loss" in sc or "mirror_loss_coeff" in sc:
+            if "mirror_loss_coef" in alg_cfg and c != coef:
+                raise ValueError("algorithm.symmetry_cfg's mirror loss (%r) disagrees with algorithm.mirror_loss_coef=%r" % (c, coef))
+            coef = c
+    return augmentation, coef
 
 
 def _split_policy_cfg(policy_cfg, runner_cfg):
@@ -253,10 +285,13 @@ class OnPolicyRunner:
                                           **_split_policy_cfg(self.policy_cfg, self.cfg)).to(self.device)
         alg_class = eval(self.cfg["algorithm_class_name"])  # PPO
         alg_kwargs, symmetry = _split_algorithm_cfg(self.alg_cfg)
+        augmentation, mirror_loss_coef = _split_symmetry_cfg(self.alg_cfg)
         self.alg = alg_class(actor_critic, device=self.device, **alg_kwargs)
-        if symmetry:        # left-right augmentation with XBot-L's tables; read by init_storage below
+        if symmetry or augmentation or mirror_loss_coef > 0.0:        # left-right symmetry with XBot-L's tables; read by init_storage below
             from humanoid.utils.symmetry import xbot_l_mirror
             self.alg.symmetry = xbot_l_mirror(self.env.cfg)
+            self.alg.symmetry_augmentation = augmentation
+            self.alg.mirror_loss_coef = mirror_loss_coef
         self.num_steps_per_env = self.cfg["num_steps_per_env"]
         self.save_interval = self.cfg["save_interval"]
         self.alg.init_storage(self.env.num_envs, self.num_steps_per_env, [self.env.num_obs], [self.env.num_privileged_obs],
@@ -613,10 +648,10 @@ class OnPolicyRunner:
         std), then clear the sink's per-iteration sums.  Stream-ordered behind the update; read in _log_flush after the event."""
         if getattr(self, "_log_pin", None) is None:
             mk = lambda n, dt: [torch.empty(n, dtype=dt).pin_memory() for _ in range(2)]
-            self._log_pin = dict(opt=mk(alg.net.opt_state.numel(), alg.net.opt_state.dtype), ls=mk(env._buf.log_stats.numel(), torch.float32),
+            self._log_pin = dict(opt=mk(alg.log_block().numel(), alg.net.opt_state.dtype), ls=mk(env._buf.log_stats.numel(), torch.float32),
                                  std=mk(1, torch.float32))
         pin = self._log_pin
-        pin["opt"][slot].copy_(alg.net.opt_state, non_blocking=True)
+        pin["opt"][slot].copy_(alg.log_block(), non_blocking=True)      # opt_state (+ the mirror loss's sums): one copy
         pin["ls"][slot].copy_(env._buf.log_stats, non_blocking=True)
         pin["std"][slot].copy_(self._noise_std(alg.actor_critic).mean().reshape(1), non_blocking=True)
         comm_words = alg.comm_status_snapshot(slot) if hasattr(alg, "comm_status_snapshot") else None
@@ -645,6 +680,7 @@ class OnPolicyRunner:
         pin, slot = self._log_pin, snap["slot"]
         o = hgym.opt_summary(pin["opt"][slot], snap["aux"])
         self.alg.last_denoise_loss = o["denoise_loss"]
+        self.alg.last_mirror_loss = self.alg.mirror_loss_from(pin["opt"][slot])
         ep, returns, lengths = hgym.log_stats_summary(pin["ls"][slot], self.env.reward_names, KERNEL_REWARD_TERMS)
         collection_time, learn_time = ev[0].elapsed_time(ev[1]) * 1e-3, ev[1].elapsed_time(ev[2]) * 1e-3
         self.last_collection_time, self.last_learn_time = collection_time, learn_time
@@ -676,6 +712,8 @@ class OnPolicyRunner:
         scal("Loss/learning_rate", learning_rate, locs["it"])
         if getattr(self.alg, "denoise_coef", 0.0) and getattr(self.alg, "last_denoise_loss", None) is not None:
             scal("Loss/denoise_mse", self.alg.last_denoise_loss, locs["it"])
+        if getattr(self.alg, "_mirror_coef", 0.0) > 0.0 and getattr(self.alg, "last_mirror_loss", None) is not None:
+            scal("Loss/mirror", self.alg.last_mirror_loss, locs["it"])
         scal("Policy/mean_noise_std", mean_std, locs["it"])
         scal("Perf/total_fps", fps, locs["it"])
         scal("Perf/collection time", locs["collection_time"], locs["it"])

@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn  # noqa: F401  (kept importable like the reference module)
 
 from .actor_critic import ActorCritic
-from .rollout_storage import RolloutStorage
+from .rollout_storage import RolloutStorage, mirror_pair_rows
 from . import dist_utils
 
 
@@ -73,6 +73,13 @@ class PPO:
     # in init_storage.  The adaptive learning-rate rule's KL is the fused loss's mean over the WHOLE minibatch, mirrored rows included
     # (rsl_rl averages it over the original rows only): it also sees the policy's asymmetry.  DESIGN.md section 21.
     symmetry = None
+    # the mirror loss, the other half of rsl_rl's symmetry_cfg (use_mirror_loss / mirror_loss_coeff): mirror_loss_coef * mse(mu(s), M_a mu(M s))
+    # added to the PPO loss, the target under the current parameters and detached (HgymPPOConfig.mirror_coef).  Needs `symmetry` (its
+    # tables; ValueError otherwise).  symmetry_augmentation = False keeps the mirrored observations (the loss's partner rows) but trains on
+    # the T N original rows only: minibatches of today's size, one more actor forward per minibatch.  With the coefficient 0 it is the
+    # same as symmetry off.  Both read once, in init_storage.  `last_mirror_loss`: the mean MSE per minibatch of the last update.
+    mirror_loss_coef = 0.0
+    symmetry_augmentation = True
 
     def __init__(self, actor_critic, num_learning_epochs=1, num_mini_batches=1, clip_param=0.2, gamma=0.998, lam=0.95,
                  value_loss_coef=1.0, entropy_coef=0.0, learning_rate=1e-3, max_grad_norm=1.0, use_clipped_value_loss=True,
@@ -120,11 +127,19 @@ class PPO:
         import hgym
         self._hgym = hgym
         self.storage = RolloutStorage(num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape, self.device)
-        self._symmetry = self.symmetry
+        import math
+        coef = float(self.mirror_loss_coef)
+        if not (coef >= 0.0 and math.isfinite(coef)):
+            raise ValueError("PPO.mirror_loss_coef=%r: must be finite and >= 0" % (self.mirror_loss_coef,))
+        if coef > 0.0 and self.symmetry is None:
+            raise ValueError("PPO.mirror_loss_coef=%r needs the mirror tables: set PPO.symmetry to a MirrorSpec" % (self.mirror_loss_coef,))
+        self._mirror_coef = coef
+        self._augment = self.symmetry is not None and bool(self.symmetry_augmentation)
+        self._symmetry = self.symmetry if (self._augment or coef > 0.0) else None      # neither half asked for: symmetry off
         if self._symmetry is not None:
             self.storage.enable_mirror(self._symmetry)      # (before enable_shadow and before anything binds a slot's address)
         ac = self.actor_critic
-        mb = ((2 if self._symmetry is not None else 1) * num_envs * num_transitions_per_env) // self.num_mini_batches
+        mb = ((2 if self._augment else 1) * num_envs * num_transitions_per_env) // self.num_mini_batches
         aux = getattr(ac, "denoiser_hidden_dims", None)
         cfg = hgym.make_net_config(ac.num_actor_obs, ac.num_critic_obs, ac.num_actions, ac.actor_hidden_dims, ac.critic_hidden_dims,
                                    self.precision, max(mb, num_envs), aux_hidden=aux, aux_out=getattr(ac, "denoiser_targets", 0),
@@ -161,8 +176,13 @@ class PPO:
                                              # net comes between the two: the norm is then taken by hgym_ppo_apply's own pass
                                              grad_norm_ready=self._obs_norm is None,
                                              aux_coef=self.denoise_coef if aux else 0.0,
-                                             clipped_value_loss=self.use_clipped_value_loss)
+                                             clipped_value_loss=self.use_clipped_value_loss, mirror_coef=coef)
         self.last_denoise_loss = None
+        self.last_mirror_loss = None
+        self._mirror_target = self._mirror_sums = None
+        if coef > 0.0:      # the pre-pass's output (one minibatch of raw partner means) and the two sums behind the per-update loss sums
+            self._mirror_target = torch.zeros(max(mb, 1) * ac.num_actions, dtype=torch.float32, device=self.device)
+            self._mirror_sums = torch.zeros(2, dtype=torch.float64, device=self.device)
         self._sample_step = torch.zeros(1, dtype=torch.int64, device=self.device)
         self._perm_seed = (torch.initial_seed() * 0x9E3779B97F4A7C15 + 0xABCD + 104729 * self._rank) & 0xFFFFFFFFFFFFFFFF
         self._perm_draws = 0
@@ -353,7 +373,11 @@ class PPO:
                 float(self.gamma), float(self.lam), self.permutation, self._perm_seed, id(self.storage), id(self.net),
                 bool(dist_utils.active()), bool(self._comm_p2p), bytes(C.string_at(C.addressof(self.net.cfg), C.sizeof(self.net.cfg))),
                 self.storage._obs_bf16 is not None, bool(self.comm_flip), self._world,
-                None if self._symmetry is None else self._symmetry.key(), self._obs_norm)
+                None if self._symmetry is None else self._symmetry.key(),
+                # the mirror loss (its coefficient is also part of _ppo_cfg's bytes above), whether the batch is doubled, the scratch the launches name
+                self._mirror_coef, self._augment,
+                None if self._mirror_target is None else (self._mirror_target.data_ptr(), self._mirror_sums.data_ptr()),
+                self._obs_norm)      # (stays the last entry: tests/test_obs_norm_runner_gpu.py reads it there)
 
     def rollout_graph_key(self):
         """Everything of this side that a rollout bakes into its launches: the storage's slots, the sink's gamma (BY VALUE), the shadows."""
@@ -385,10 +409,12 @@ class PPO:
         (None, None), so the host can already enqueue the next rollout while this update runs."""
         hgym, net, st, direct = self._hgym, self.net, self.storage, self._direct_exchange()
         T, N = st.num_transitions_per_env, st.num_envs
-        sym = self._symmetry is not None
+        sym, aug, mirror_loss = self._symmetry is not None, self._augment, self._mirror_coef > 0.0
         if sym:
-            st.mirror()      # the mirrored half of every column, from the finished rollout (returns, advantages, values, shadows: all there)
-        batch = (2 if sym else 1) * T * N
+            # the mirrored half of every column, from the finished rollout (returns, advantages, values, shadows: all there); the mirror
+            # loss alone reads only the mirrored observations
+            st.mirror(observations_only=not aug)
+        batch = (2 if aug else 1) * T * N
         mb = batch // self.num_mini_batches
         # one permutation for every epoch (rollout_storage.py:149,165-170)
         if self.permutation == "device":
@@ -403,8 +429,13 @@ class PPO:
             perm = st.permutation(self.num_mini_batches * mb, self._perm_seed, self._perm_draws_dev)
         else:
             perm = torch.randperm(self.num_mini_batches * mb, device=self.device)
-        if sym:
+        if aug:
             perm = st.mirror_index(perm)      # drawn over 2 T N rows; the mirrored half lies behind the bootstrap slot
+        pair = mirror = None
+        if mirror_loss:      # every drawn row's partner, original or mirrored (without augmentation only rows < T N are drawn)
+            pair = mirror_pair_rows(perm, T, N)
+            mirror = st._mirror["act"] + (self._mirror_target, self._mirror_sums)
+            self._mirror_sums[0:2] = 0.0      # (a slice: a fill kernel, as below)
         cols = st.batch_columns()
         sh = st.shadows(mirrored=sym)
         if sh is not None and self._check_shadow:
@@ -416,7 +447,10 @@ class PPO:
         for _ in range(self.num_learning_epochs):
             for i in range(self.num_mini_batches):
                 idx = perm[i * mb:(i + 1) * mb]
-                batch = hgym.make_batch(*cols, idx, **sh)
+                if mirror_loss:
+                    batch = hgym.make_batch(*cols, idx, pair_idx=pair[i * mb:(i + 1) * mb], mirror=mirror, **sh)
+                else:
+                    batch = hgym.make_batch(*cols, idx, **sh)
                 net.ppo_grad(self._ppo_cfg, batch)
                 if self._obs_norm is not None:
                     net.norm_unfold_grad()      # first-layer gradients: of the folded operands -> of the master parameters, ahead of the exchange and the norm
@@ -444,11 +478,24 @@ class PPO:
         self._update_done()
         if not sync:
             return None, None
-        o = net.opt_state.cpu()                # the one host read-back of the update
+        o = self.log_block().cpu()             # the one host read-back of the update
         self.check_comm()                      # (the stream is idle now: reading the exchange's status costs one small copy)
+        self.last_mirror_loss = self.mirror_loss_from(o)
         o = hgym.opt_summary(o, self._ppo_cfg.aux_coef > 0.0)
         self.last_denoise_loss = o["denoise_loss"]
         return o["mean_value_loss"], o["mean_surrogate_loss"]
+
+    def log_block(self):
+        """What a log block reads after an update, as ONE device tensor (one copy to the host): opt_state, and behind it the mirror
+        loss's two sums when that loss is on."""
+        return self.net.opt_state if self._mirror_sums is None else torch.cat((self.net.opt_state, self._mirror_sums))
+
+    def mirror_loss_from(self, block):
+        """The mean mirror MSE per minibatch from a host copy of log_block(); None when the loss is off."""
+        if self._mirror_sums is None:
+            return None
+        n = self.net.opt_state.numel()
+        return float(block[n]) / max(float(block[n + 1]), 1.0)
 
     def normalizer_step(self):
         """The normaliser's one step per iteration, at the end of update(), ahead of storage.clear(): accumulate the T * N stored raw

@@ -9,6 +9,15 @@ import ctypes as C
 import torch
 
 
+def mirror_pair_rows(idx, T, N):
+    """The partner of every row of `idx` in the (2 T + 1)-slot layout of RolloutStorage.enable_mirror: the row that holds the mirrored
+    observation of the same transition.  Original row r < T N <-> mirrored row (T + 1) N + r; an involution on those rows; the bootstrap
+    slot (rows [T N, (T + 1) N)) is never named for a row outside it.  A pure function: device operations with fixed arguments, no host
+    read -- capturable."""
+    off = (int(T) + 1) * int(N)
+    return torch.where(idx < int(T) * int(N), idx + off, idx - off)
+
+
 class RolloutStorage:
     class Transition:
         def __init__(self):
@@ -119,8 +128,10 @@ class RolloutStorage:
     def mirrored(self):
         return self._mirror is not None
 
-    def mirror(self):
-        """Fill the mirrored half from the current rollout (after compute_returns, and after the deferred critic wrote values and the
+    def mirror(self, observations_only=False):
+        """observations_only (the mirror loss without augmentation, PPO.symmetry_augmentation = False): only the observation rows and
+        their bf16 shadow -- the one column the update then reads behind the bootstrap slot (the actor's forward over the partner rows).
+        Fill the mirrored half from the current rollout (after compute_returns, and after the deferred critic wrote values and the
         privileged shadow): hgym_mirror_rows per tensor, device copies for the four scalar columns, all on the current stream with
         fixed arguments (capturable).  The T N original rows and slot T are only read.  The bf16 shadows are mirrored from the shadows
         (a sign-bit flip commutes with the rounding), and only when every slot of them is valid -- otherwise the update does not read them."""
@@ -128,6 +139,10 @@ class RolloutStorage:
         m, T = self._mirror, self.num_transitions_per_env
         fl = lambda t: t.flatten(0, 1)
         hgym.mirror_rows(fl(self._obs_store[:T]), fl(self._obs_store[T + 1:]), *m["obs"])
+        if observations_only:
+            if self.shadows() is not None:
+                hgym.mirror_rows(fl(self._obs_bf16_store[:T]), fl(self._obs_bf16_store[T + 1:]), *m["obs"], zero_to=self._obs_bf16_store.shape[2])
+            return
         hgym.mirror_rows(fl(self._priv_store[:T]), fl(self._priv_store[T + 1:]), *m["priv"])
         for name, table in (("actions", "act"), ("mu", "act"), ("sigma", "sigma")):
             c = self._col_store[name]

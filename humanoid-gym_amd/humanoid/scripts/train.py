@@ -19,6 +19,10 @@ sigma = exp(log_std) cannot leave the positive numbers, the checkpoint's first e
 HGYM_SYMMETRY=1 sets `algorithm.symmetry` the same way: the update also trains on the left-right mirrored copy of every transition
 (PPO.symmetry with XBot-L's tables, humanoid/utils/symmetry.py): minibatches twice as large, as many Adam steps.
 
+HGYM_MIRROR_LOSS=<coef> sets `algorithm.mirror_loss_coef`: coef * mse(mu(s), mirror of mu(mirrored s)) joins the PPO loss (rsl_rl's
+mirror_loss_coeff; XBot-L's tables are implied).  HGYM_SYMMETRY=1 still decides the augmentation: without it the minibatches keep their
+size and the update pays one more actor forward.
+
 HGYM_OBS_NORM=1 sets `policy.empirical_normalization` the same way: every observation column is standardised by running statistics
 folded into the first layers (ActorCritic(empirical_normalization=True)); checkpoints carry the statistics."""
 import os
@@ -42,6 +46,8 @@ def train(args):
         task_registry.get_cfgs(args.task)[1].policy.noise_std_type = os.environ["HGYM_NOISE_STD"]
     if os.environ.get("HGYM_SYMMETRY", "0") == "1":
         task_registry.get_cfgs(args.task)[1].algorithm.symmetry = True
+    if float(os.environ.get("HGYM_MIRROR_LOSS", "0") or 0.0) != 0.0:
+        task_registry.get_cfgs(args.task)[1].algorithm.mirror_loss_coef = float(os.environ["HGYM_MIRROR_LOSS"])
     if os.environ.get("HGYM_OBS_NORM", "0") == "1":
         task_registry.get_cfgs(args.task)[1].policy.empirical_normalization = True
     ppo_runner, train_cfg = task_registry.make_alg_runner(env=env, name=args.task, args=args, **({} if rank == 0 else {"log_root": None}))

@@ -63,7 +63,9 @@ extern "C" {
                              *    (same version, later: hgym_mirror_rows -- the mirrored copy of stored rows for left-right symmetry augmentation;
                              *    no layout changes)
                              *    (same version, later: HgymNet.norm appended -- empirical observation normalisation folded into the first layer,
-                             *    hgym_net_norm_*; a NULL (zero-filled) member is a net without it) */
+                             *    hgym_net_norm_*; a NULL (zero-filled) member is a net without it)
+                             *    (same version, later: HgymPPOConfig.mirror_coef and HgymBatch.pair_idx / mirror_act_src / mirror_act_sign /
+                             *    mirror_target / mirror_sums appended -- the mirror loss of left-right symmetry; a zero-filled tail is off) */
 
 enum {
     HGYM_OK = 0,
@@ -546,6 +548,19 @@ typedef struct HgymPPOConfig {
                                          1: (R - V)^2.mean()  (use_clipped_value_loss = False)
                                        opt_state[4] (VALUE_SUM) sums the form in use.  Any other value: HGYM_E_BADARG from every call taking the
                                        configuration.  Appended later within header v9, so a zero-filled tail is the clipped form. */
+    float mirror_coef;              /* weight of the mirror loss (rsl_rl's symmetry_cfg: use_mirror_loss / mirror_loss_coeff).
+                                       For a minibatch of B rows with A actions, row b = storage row idx[b] with partner row pair_idx[b] (the
+                                       mirrored observation of the same transition):
+                                           t_b = M_a(mu(obs[pair_idx[b]]))      current parameters, NO gradient through t_b
+                                           L_m = mirror_coef / (B A) * sum_b sum_j (mu(obs[idx[b]])_j - t_bj)^2
+                                       with M_a(y)_j = mirror_act_sign[j] * y[mirror_act_src[j]].  L_m is added to the PPO loss: it changes d mu
+                                       (hence the actor's gradients) and nothing else -- d std, the critic, the auxiliary head, the KL of the
+                                       learning-rate rule and the loss sums of opt_state are what they are without it.  0: off -- the five
+                                       HgymBatch members below are ignored, the launches and every output bit are those of a library without the
+                                       feature.  > 0: hgym_ppo_grad / hgym_ppo_grad_part (part 0) first run one forward-only actor pass over
+                                       obs[pair_idx] (the fp32 rows, on every path) into HgymBatch.mirror_target.  Negative, NaN or infinite:
+                                       HGYM_E_BADARG from every call taking the configuration, nothing launched.  Appended later within header
+                                       v9, so a zero-filled tail is off. */
 } HgymPPOConfig;
 
 /* Sizes (bytes) of the caller-allocated blocks, as functions of the configuration. */
@@ -825,6 +840,18 @@ typedef struct HgymBatch {
     int64_t num_rows;        /* rows of the storage tensors (T*N), required (> 0) with the shadows: the weight-gradient kernel addresses a
                                 shadow with 32-bit byte offsets, so num_rows * hgym_net_shadow_ld(cfg, 0) * 2 must stay below 4 GiB (2.79 M
                                 rows for XBot-L) -- beyond that the fp32 rows are used */
+    /* the mirror loss (HgymPPOConfig.mirror_coef > 0; ignored at 0; appended within header v9: a zero-filled tail with mirror_coef = 0 is
+     * a batch of any earlier layout).  With mirror_coef > 0 any of the five NULL, or mirror_target not 16-byte aligned: HGYM_E_BADARG and
+     * nothing launched.  pair_idx, mirror_act_src and mirror_act_sign are DEVICE arrays read by the launches: the library cannot
+     * validate their contents without a host synchronisation (the Python layer does: MirrorSpec, mirror_pair_rows); an act_src entry
+     * outside [0, num_actions) is clamped into it. */
+    const int64_t* pair_idx;        /* (B,) the partner's storage row of every row of idx */
+    const int32_t* mirror_act_src;  /* (num_actions,) M_a's source column */
+    const float* mirror_act_sign;   /* (num_actions,) M_a's sign */
+    float* mirror_target;           /* caller-owned scratch, (B, num_actions) fp32, 16-byte aligned: receives the RAW mu(obs[pair_idx]) (M_a is
+                                       applied where the loss reads it) */
+    double* mirror_sums;            /* two device doubles the caller zeroes: [0] += this minibatch's L_m / mirror_coef (the plain MSE),
+                                       [1] += 1 */
 } HgymBatch;
 
 int32_t hgym_ppo_grad(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const HgymNet* net,
