@@ -20,6 +20,7 @@ COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno
 EXTRA = {
     "hgym_env.hip": ["-ffp-contract=off"],
     "hgym_gae.hip": ["-ffp-contract=off"],
+    "hgym_advnorm.hip": ["-ffp-contract=off"],      # adv_normalize_kernel's arithmetic (hgym_gae.hip) restated: the same flags, the same bits
     "hgym_eval.hip": ["-ffp-contract=off"],          # the accumulator's fp64 expressions as a test restates them, one rounding per operation
     "hgym_diag.hip": ["-ffp-contract=off"],          # the per-row fp32 terms as a test restates them in float64, one rounding per operation
     "hgym_rollout.hip": ["-ffp-contract=off"],      # contains the env arithmetic; hgym_fused.hpp restores its own setting by pragma

@@ -24,3 +24,24 @@ def mirror_rows(src, dst, src_col, sign, zero_to=None):
                                C.c_void_p(dst.data_ptr()), ld(dst), width if zero_to is None else int(zero_to),
                                _lib.F32 if src.dtype == torch.float32 else _lib.BF16, C.c_void_p(torch.cuda.current_stream().cuda_stream)),
           "hgym_mirror_rows")
+
+
+def adv_normalize_minibatches(idx, adv, out, segments, scratch):
+    """hgym_adv_normalize_minibatches on the current stream: idx int64 (segments * seg_len,) distinct rows of the columns adv / out (float32,
+    contiguous, the same number of rows, not overlapping); segment s = idx[s * seg_len:(s + 1) * seg_len] ->
+    out[idx[j]] = (adv[idx[j]] - mean_s) / (std_s + 1e-8), the segment's own mean and unbiased deviation.  Rows of `out` that idx does not
+    name are left alone.  scratch: _lib.adv_mb_scratch(segments, seg_len, device), zero-filled once, reusable from call to call."""
+    import ctypes as C
+    import torch
+    segments = int(segments)
+    assert idx.dtype == torch.int64 and idx.is_cuda and idx.is_contiguous() and idx.dim() == 1
+    assert segments >= 1 and idx.numel() % segments == 0
+    seg_len = idx.numel() // segments
+    for t in (adv, out):
+        assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous()
+    assert adv.numel() == out.numel()
+    assert scratch.dtype == torch.float64 and scratch.is_cuda and scratch.is_contiguous()
+    assert scratch.numel() >= _lib.adv_mb_scratch_doubles(segments, seg_len)
+    check(lib.hgym_adv_normalize_minibatches(segments, seg_len, _lib.i64ptr(idx), _lib.fptr(adv), _lib.fptr(out), int(adv.numel()),
+                                             _lib.f64ptr(scratch), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+          "hgym_adv_normalize_minibatches")

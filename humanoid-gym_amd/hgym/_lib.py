@@ -202,6 +202,7 @@ SYMBOLS = {
     "hgym_gae": (C.c_int32, [C.c_int32, C.c_int32, c_float_p, c_float_p, c_u8_p, c_float_p, C.c_float, C.c_float,
                              c_float_p, c_float_p, c_f64_p, C.c_void_p]),
     "hgym_adv_normalize": (C.c_int32, [C.c_int64, c_float_p, c_f64_p, C.c_void_p]),
+    "hgym_adv_normalize_minibatches": (C.c_int32, [C.c_int32, C.c_int64, c_i64_p, c_float_p, c_float_p, C.c_int64, c_f64_p, C.c_void_p]),
     "hgym_gae_bootstrap": (C.c_int32, [C.c_int32, C.c_int32, c_float_p, c_float_p, c_u8_p, c_u8_p, c_float_p, C.c_float, C.c_float,
                                        c_float_p, c_float_p, c_f64_p, C.c_void_p]),
     "hgym_mirror_rows": (C.c_int32, [C.c_int64, C.c_int32, C.POINTER(C.c_int32), c_float_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32,
@@ -348,6 +349,20 @@ def gae_stats(n, device):
     """The `stats` buffer of hgym_gae / hgym_gae_bootstrap for n envs: HGYM_GAE_STATS_DOUBLES(n) zero-filled doubles (include/hgym.h)."""
     import torch
     return torch.zeros(4 + 2 * ((int(n) + 15) // 16), dtype=torch.float64, device=device)
+
+
+ADV_MB_CHUNK = 1024     # entries of a segment whose partial sums one workgroup of hgym_adv_normalize_minibatches forms
+
+
+def adv_mb_scratch_doubles(segments, seg_len):
+    """HGYM_ADV_MB_SCRATCH_DOUBLES(segments, seg_len) of include/hgym.h."""
+    return int(segments) * (3 + 2 * ((int(seg_len) + ADV_MB_CHUNK - 1) // ADV_MB_CHUNK))
+
+
+def adv_mb_scratch(segments, seg_len, device):
+    """The `scratch` buffer of hgym_adv_normalize_minibatches, zero-filled."""
+    import torch
+    return torch.zeros(adv_mb_scratch_doubles(segments, seg_len), dtype=torch.float64, device=device)
 
 
 # the diagnostics pass's block (include/hgym.h: HGYM_DIAG_*)

@@ -205,11 +205,31 @@ SYMMETRY_KEYS = ("mirror_loss_coef", "symmetry_augmentation", "symmetry_cfg")   
 def _split_algorithm_cfg(alg_cfg):
     """The train config's algorithm block -> (keyword arguments of PPO.__init__, symmetry on?).  `symmetry` is a native key (absent:
     off), not a parameter of the reference's PPO: it is taken out here and becomes PPO.symmetry.  The mirror loss's keys (SYMMETRY_KEYS)
-    are taken out as well; _split_symmetry_cfg reads them."""
+    are taken out as well; _split_symmetry_cfg reads them.  So are the advantage normalisation's (ADVANTAGE_KEYS; _split_advantage_cfg)."""
     kwargs = dict(alg_cfg)
-    for k in SYMMETRY_KEYS:
+    for k in SYMMETRY_KEYS + ADVANTAGE_KEYS:
         kwargs.pop(k, None)
     return kwargs, bool(kwargs.pop("symmetry", False))
+
+
+ADVANTAGE_KEYS = ("advantage_normalization", "normalize_advantage_per_mini_batch")      # neither is a parameter of PPO.__init__
+
+
+def _split_advantage_cfg(alg_cfg):
+    """The train config's algorithm block -> PPO.advantage_normalization: "batch" (the default), "minibatch" or "none".  Native key:
+    `advantage_normalization`.  rsl_rl's `normalize_advantage_per_mini_batch` is accepted too: True is "minibatch", False is "batch"; set
+    beside a native key that says otherwise: ValueError, as is an unknown mode.  The caller's dict is left alone."""
+    modes = PPO.ADVANTAGE_NORMALIZATIONS
+    mode = alg_cfg.get("advantage_normalization")
+    if mode is not None and mode not in modes:
+        raise ValueError("algorithm.advantage_normalization=%r: one of %s" % (mode, ", ".join(modes)))
+    if alg_cfg.get("normalize_advantage_per_mini_batch") is not None:
+        theirs = "minibatch" if bool(alg_cfg["normalize_advantage_per_mini_batch"]) else "batch"
+        if mode is not None and mode != theirs:
+            raise ValueError("algorithm.normalize_advantage_per_mini_batch=%r disagrees with algorithm.advantage_normalization=%r"
+                             % (alg_cfg["normalize_advantage_per_mini_batch"], mode))
+        mode = theirs
+    return "batch" if mode is None else mode
 
 
 def _split_symmetry_cfg(alg_cfg):
@@ -292,6 +312,8 @@ class OnPolicyRunner:
             self.alg.symmetry = xbot_l_mirror(self.env.cfg)
             self.alg.symmetry_augmentation = augmentation
             self.alg.mirror_loss_coef = mirror_loss_coef
+        if any(self.alg_cfg.get(k) is not None for k in ADVANTAGE_KEYS):      # read by init_storage below
+            self.alg.advantage_normalization = _split_advantage_cfg(self.alg_cfg)
         self.num_steps_per_env = self.cfg["num_steps_per_env"]
         self.save_interval = self.cfg["save_interval"]
         self.alg.init_storage(self.env.num_envs, self.num_steps_per_env, [self.env.num_obs], [self.env.num_privileged_obs],

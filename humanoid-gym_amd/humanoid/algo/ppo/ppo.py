@@ -80,6 +80,14 @@ class PPO:
     # same as symmetry off.  Both read once, in init_storage.  `last_mirror_loss`: the mean MSE per minibatch of the last update.
     mirror_loss_coef = 0.0
     symmetry_augmentation = True
+    # how the advantages are standardised: "batch" -- the reference's way, once over the whole T N batch at the end of compute_returns (the
+    # all-reduced statistics on several ranks); "minibatch" -- rsl_rl's normalize_advantage_per_mini_batch: compute_returns leaves the raw
+    # advantages, update() standardises every minibatch by its own mean and unbiased deviation (one segmented pass per update into
+    # storage.advantages_mb, which the batch descriptor then names; nothing crosses ranks); "none" -- the raw advantages are used.  With
+    # symmetry augmentation a minibatch's statistics are over its drawn rows, originals and mirrors alike (rsl_rl normalises before it
+    # augments).  Read once, in init_storage.  DESIGN.md section 24.
+    advantage_normalization = "batch"
+    ADVANTAGE_NORMALIZATIONS = ("batch", "minibatch", "none")
 
     def __init__(self, actor_critic, num_learning_epochs=1, num_mini_batches=1, clip_param=0.2, gamma=0.998, lam=0.95,
                  value_loss_coef=1.0, entropy_coef=0.0, learning_rate=1e-3, max_grad_norm=1.0, use_clipped_value_loss=True,
@@ -126,6 +134,9 @@ class PPO:
     def init_storage(self, num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape):
         import hgym
         self._hgym = hgym
+        if self.advantage_normalization not in self.ADVANTAGE_NORMALIZATIONS:
+            raise ValueError("PPO.advantage_normalization=%r: one of %s" % (self.advantage_normalization, ", ".join(self.ADVANTAGE_NORMALIZATIONS)))
+        self._adv_mode = self.advantage_normalization
         self.storage = RolloutStorage(num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape, self.device)
         import math
         coef = float(self.mirror_loss_coef)
@@ -140,6 +151,10 @@ class PPO:
             self.storage.enable_mirror(self._symmetry)      # (before enable_shadow and before anything binds a slot's address)
         ac = self.actor_critic
         mb = ((2 if self._augment else 1) * num_envs * num_transitions_per_env) // self.num_mini_batches
+        if self._adv_mode == "minibatch":
+            if mb < 2:      # (rsl_rl would divide by the NaN deviation of one value)
+                raise ValueError("PPO.advantage_normalization='minibatch' needs minibatches of at least 2 rows (they have %d)" % mb)
+            self.storage.enable_minibatch_advantages(self.num_mini_batches, mb)      # (behind enable_mirror: the enlarged column's layout)
         aux = getattr(ac, "denoiser_hidden_dims", None)
         cfg = hgym.make_net_config(ac.num_actor_obs, ac.num_critic_obs, ac.num_actions, ac.actor_hidden_dims, ac.critic_hidden_dims,
                                    self.precision, max(mb, num_envs), aux_hidden=aux, aux_out=getattr(ac, "denoiser_targets", 0),
@@ -346,7 +361,8 @@ class PPO:
     def compute_returns(self, last_critic_obs):
         st, deferred = self.storage, self._deferred_ready       # deferred_values() has evaluated the bootstrap observation with the rest
         last_values = st.last_values if deferred else self.actor_critic.evaluate(last_critic_obs)
-        st.compute_returns(last_values, self.gamma, self.lam, stats_hook=self._adv_stats, time_outs=st.time_outs if deferred else None)
+        st.compute_returns(last_values, self.gamma, self.lam, stats_hook=self._adv_stats, time_outs=st.time_outs if deferred else None,
+                           normalize=self._adv_mode == "batch")
         self._returns_done()
 
     def _returns_done(self):      # what compute_returns() changes on the host, issued or replayed: the deferred values are used up
@@ -377,6 +393,9 @@ class PPO:
                 # the mirror loss (its coefficient is also part of _ppo_cfg's bytes above), whether the batch is doubled, the scratch the launches name
                 self._mirror_coef, self._augment,
                 None if self._mirror_target is None else (self._mirror_target.data_ptr(), self._mirror_sums.data_ptr()),
+                # how the advantages are standardised, and the column and scratch the per-minibatch pass names
+                self._adv_mode,
+                None if self.storage.advantages_mb is None else (self.storage.advantages_mb.data_ptr(), self.storage._adv_mb_scratch.data_ptr()),
                 self._obs_norm)      # (stays the last entry: tests/test_obs_norm_runner_gpu.py reads it there)
 
     def rollout_graph_key(self):
@@ -437,6 +456,9 @@ class PPO:
             mirror = st._mirror["act"] + (self._mirror_target, self._mirror_sums)
             self._mirror_sums[0:2] = 0.0      # (a slice: a fill kernel, as below)
         cols = st.batch_columns()
+        if self._adv_mode == "minibatch":
+            # the slices below partition perm once for every epoch: all minibatches standardised in one pass, into the column the batches name
+            cols = cols[:4] + (st.normalize_minibatch_advantages(perm, self.num_mini_batches),) + cols[5:]
         sh = st.shadows(mirrored=sym)
         if sh is not None and self._check_shadow:
             st.check_shadows()
@@ -546,6 +568,11 @@ class PPO:
         `kl` is the exact KL(old || new) of the two Gaussians, averaged over the WHOLE batch after the LAST minibatch step; the
         learning-rate rule sees one minibatch at a time, before its step, and its expression carries + 1e-5 inside the logarithm.
 
+        `surrogate` is formed with the advantages the update trained on (PPO.advantage_normalization): the batch-standardised column by
+        default; under "minibatch" storage.advantages_mb -- every original row standardised by the statistics of the minibatch that drew
+        it, and 0 for a row no minibatch drew (batch % num_mini_batches != 0), which then adds nothing to the sum; under "none" the raw
+        returns - values, so its scale is the rewards'.
+
         Data-parallel runs: every rank reports its own shard of the batch; no collective is added."""
         st = self.storage
         if st is None or not self._diag_updated:
@@ -566,7 +593,8 @@ class PPO:
                 st._priv_all[0].copy_(self._diag_rows0[1])
             obs = fl(st.observations)
             priv = fl(st.privileged_observations) if st.privileged_observations is not None else obs
-            cols = (obs, priv, fl(st.actions), st.values.view(-1), st.advantages.view(-1), st.returns.view(-1),
+            adv = st.advantages_mb[:T * N] if self._adv_mode == "minibatch" else st.advantages.view(-1)      # the column the update trained on
+            cols = (obs, priv, fl(st.actions), st.values.view(-1), adv, st.returns.view(-1),
                     st.actions_log_prob.view(-1), fl(st.mu), fl(st.sigma))
             self.net.ppo_diagnostics(self._ppo_cfg, cols, self._diag_block)
             st._obs_all[0].copy_(st._obs_all[T])

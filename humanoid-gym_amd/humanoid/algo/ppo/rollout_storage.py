@@ -69,6 +69,26 @@ class RolloutStorage:
         self.time_outs = self.last_values = None
         # left-right mirrored half (enable_mirror): the device tables, None without it
         self._mirror = None
+        # per-minibatch advantage normalisation (enable_minibatch_advantages): the second advantages column, None without it
+        self.advantages_mb = self._adv_mb_scratch = None
+
+    def enable_minibatch_advantages(self, segments, seg_len):
+        """Native extension (PPO.advantage_normalization = "minibatch"): `advantages_mb`, a second advantages column laid out like the one
+        batch_columns() names (T N rows, or (2 T + 1) N with enable_mirror -- call this after it), zero-filled once, and the scratch of
+        hgym_adv_normalize_minibatches for `segments` minibatches of `seg_len` rows."""
+        from hgym import _lib as L
+        rows = (self.num_transitions_per_env if self._mirror is None else 2 * self.num_transitions_per_env + 1) * self.num_envs
+        self.advantages_mb = torch.zeros(rows, dtype=torch.float32, device=self.device)
+        self._adv_mb_scratch = L.adv_mb_scratch(segments, seg_len, self.device)
+
+    def normalize_minibatch_advantages(self, perm, segments):
+        """advantages_mb[perm[j]] = the advantage of row perm[j] standardised by the mean and unbiased deviation of its minibatch
+        perm[s * mb:(s + 1) * mb] (hgym_adv_normalize_minibatches: one pass, two launches, fixed arguments -- capturable).  perm: distinct
+        rows of the column batch_columns() names (after mirror_index).  Rows perm does not name keep their 0.  -> advantages_mb."""
+        import hgym
+        adv = self.advantages.view(-1) if self._mirror is None else self._col_store["advantages"].view(-1)
+        hgym.adv_normalize_minibatches(perm, adv, self.advantages_mb, segments, self._adv_mb_scratch)
+        return self.advantages_mb
 
     def enable_shadow(self, ld_obs, ld_priv):
         """Native extension: allocate (T, N, ld) bfloat16 copies of `observations` / `privileged_observations` (ld = the widths
@@ -253,9 +273,11 @@ class RolloutStorage:
         self.step = 0
         self.shadow_valid = [False] * self.num_transitions_per_env
 
-    def compute_returns(self, last_values, gamma, lam, stats_hook=None, time_outs=None):
+    def compute_returns(self, last_values, gamma, lam, stats_hook=None, time_outs=None, normalize=True):
         """rollout_storage.py:122-136.  time_outs (native extension, deferred values): `rewards` holds RAW rewards; the time-out
-        bootstrap r += gamma * V * time_outs is applied (and written back) as the scan loads them (hgym_gae_bootstrap)."""
+        bootstrap r += gamma * V * time_outs is applied (and written back) as the scan loads them (hgym_gae_bootstrap).
+        normalize=False (native extension, PPO.advantage_normalization "minibatch" / "none"): rollout_storage.py:136 is left out --
+        neither stats_hook nor hgym_adv_normalize runs, `advantages` stays returns - values as the scan wrote it."""
         from hgym import _lib as L
         T, N = self.num_transitions_per_env, self.num_envs
         if not self.rewards.is_cuda:
@@ -269,6 +291,8 @@ class RolloutStorage:
         else:
             L.check(L.lib.hgym_gae(T, N, L.fptr(self.rewards), L.fptr(self.values), L.u8ptr(self.dones), L.fptr(lv), gamma, lam,
                                    L.fptr(self.returns), L.fptr(self.advantages), L.f64ptr(self._stats), s), "hgym_gae")
+        if not normalize:
+            return
         if stats_hook is not None:
             stats_hook(self._stats[:3])           # multi-GPU: all-reduce (sum, sumsq, count) for a global normalisation
         L.check(L.lib.hgym_adv_normalize(T * N, L.fptr(self.advantages), L.f64ptr(self._stats), s), "hgym_adv_normalize")

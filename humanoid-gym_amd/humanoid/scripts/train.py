@@ -24,7 +24,11 @@ mirror_loss_coeff; XBot-L's tables are implied).  HGYM_SYMMETRY=1 still decides 
 size and the update pays one more actor forward.
 
 HGYM_OBS_NORM=1 sets `policy.empirical_normalization` the same way: every observation column is standardised by running statistics
-folded into the first layers (ActorCritic(empirical_normalization=True)); checkpoints carry the statistics."""
+folded into the first layers (ActorCritic(empirical_normalization=True)); checkpoints carry the statistics.
+
+HGYM_ADV_NORM=minibatch|none|batch sets `algorithm.advantage_normalization` the same way: the advantages standardised per minibatch
+(rsl_rl's normalize_advantage_per_mini_batch), not at all, or -- "batch", unset: the reference's way -- once over the whole batch
+(PPO.advantage_normalization)."""
 import os
 import sys
 
@@ -50,6 +54,8 @@ def train(args):
         task_registry.get_cfgs(args.task)[1].algorithm.mirror_loss_coef = float(os.environ["HGYM_MIRROR_LOSS"])
     if os.environ.get("HGYM_OBS_NORM", "0") == "1":
         task_registry.get_cfgs(args.task)[1].policy.empirical_normalization = True
+    if os.environ.get("HGYM_ADV_NORM"):
+        task_registry.get_cfgs(args.task)[1].algorithm.advantage_normalization = os.environ["HGYM_ADV_NORM"]
     ppo_runner, train_cfg = task_registry.make_alg_runner(env=env, name=args.task, args=args, **({} if rank == 0 else {"log_root": None}))
     ppo_runner.learn(num_learning_iterations=train_cfg.runner.max_iterations, init_at_random_ep_len=True)
     if os.environ.get("HGYM_TRAIN_SIGNATURE"):      # tests: a signature of this rank's final parameters (replicas must agree bit for bit)

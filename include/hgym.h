@@ -65,7 +65,9 @@ extern "C" {
                              *    (same version, later: HgymNet.norm appended -- empirical observation normalisation folded into the first layer,
                              *    hgym_net_norm_*; a NULL (zero-filled) member is a net without it)
                              *    (same version, later: HgymPPOConfig.mirror_coef and HgymBatch.pair_idx / mirror_act_src / mirror_act_sign /
-                             *    mirror_target / mirror_sums appended -- the mirror loss of left-right symmetry; a zero-filled tail is off) */
+                             *    mirror_target / mirror_sums appended -- the mirror loss of left-right symmetry; a zero-filled tail is off)
+                             *    (same version, later: hgym_adv_normalize_minibatches -- advantages standardised per minibatch into a second column;
+                             *    no layout changes) */
 
 enum {
     HGYM_OK = 0,
@@ -434,6 +436,25 @@ int32_t hgym_gae(int32_t T, int32_t n, const float* rewards, const float* values
 
 /* advantages = (adv - mean) / (std_unbiased + 1e-8) from stats (possibly all-reduced by the caller). */
 int32_t hgym_adv_normalize(int64_t count, float* advantages, const double* stats, void* stream);
+
+/* Advantages standardised PER MINIBATCH (rsl_rl's normalize_advantage_per_mini_batch; PPO.advantage_normalization = "minibatch"), one
+ * segmented pass for all minibatches of an update.  Segment s is idx[s * seg_len, (s + 1) * seg_len), s < segments:
+ *     out[idx[j]] = (adv[idx[j]] - mean_s) / (std_s + 1e-8f),   mean_s / std_s (unbiased) over the seg_len gathered values of segment s
+ * in hgym_adv_normalize's arithmetic: fp64 sum and sum of squares of the fp32 values, mean = (float)(s1 / n), var = (s2 - s1 s1 / n) /
+ * (n - 1) clamped at 0, denom = (float)sqrt(var) + 1e-8f, the result (adv - mean) / denom in fp32.  A constant segment gives exactly 0.
+ * The sums are formed per chunk of 1024 consecutive entries of a segment by a fixed tree and added in chunk order: the same bits in every
+ * run, no fp64 atomics.  Two launches, no allocation, no host synchronisation, the same arguments in every iteration (capturable).
+ * idx: a DEVICE array of segments * seg_len DISTINCT row numbers in [0, rows) -- the caller's guarantee (a slice of the update's
+ * permutation); the library cannot validate it without a host synchronisation, and an entry outside [0, rows) reads and writes nothing.
+ * adv, out: columns of `rows` floats each, not overlapping; rows of out that no entry names are not touched.
+ * scratch: HGYM_ADV_MB_SCRATCH_DOUBLES(segments, seg_len) doubles on the device, ZERO-FILLED ONCE by the caller (per segment: sum, sum of
+ * squares, the arrival counter of the segment's chunks, left zero again; behind them the chunks' partial sums).  One call at a time per
+ * scratch buffer.
+ * Nothing launched and HGYM_E_SHAPE: segments < 1, seg_len < 2 (one value has no unbiased deviation; rsl_rl would produce NaN), rows <
+ * segments * seg_len.  HGYM_E_UNSUPPORTED: segments * seg_len > 2^40.  HGYM_E_BADARG: a null pointer, adv and out overlapping within rows. */
+#define HGYM_ADV_MB_SCRATCH_DOUBLES(segments, seg_len) ((int64_t)(segments) * (3 + 2 * (((int64_t)(seg_len) + 1023) / 1024)))
+int32_t hgym_adv_normalize_minibatches(int32_t segments, int64_t seg_len, const int64_t* idx, const float* adv, float* out, int64_t rows,
+                                       double* scratch, void* stream);
 /* hgym_gae for a rollout collected with deferred values (HgymEnvOut.t_time_outs): rewards (T, n) holds the RAW rewards and is
  * overwritten with r_t + gamma * (V_t * time_outs_t) -- PPO.process_env_step's bootstrap (ppo.py:107-108), the three fp32 roundings of
  * hgym_store_step -- before the scan uses it, so that afterwards every storage column is what the per-step path leaves. */
