@@ -1057,6 +1057,17 @@ struct FbMirror {
 };
 constexpr int FB_MIRROR_LDS = 64 * 12 * 4 + 2 * 16 * 4;      // 64 rows x 12 floats, then act_src[16] (ints) and act_sign[16]
 
+// Behaviour cloning (hgym_bc_grad): an argument of the BC instantiations only (hgym_update_bc.hip, hgym_update_act_bc.hip).  The head
+// regresses mu on target[row] -- a storage column gathered through FwdArgs::idx like every other loss input -- and nothing else: no
+// surrogate, no entropy, no KL, no d std.  The tile's 64 target rows are staged in the actor's loss-input region of LDS (fb_lds_lin:
+// 64 x FB_LIN_ACTOR floats, of which a row's first 12 are used), so a BC tile asks for exactly fb_lds_bytes(net).
+struct FbBC {
+    const float* target;       // (num_rows, A) fp32, 16-byte aligned rows when A == 12
+    float inv;                 // 1 / (M * A)
+    float delta;               // Huber's delta (> 0); unused by the MSE
+    int huber;                 // 0: MSE, d mu = 2 e inv; 1: Huber, d mu = clamp(e, -delta, delta) inv
+};
+
 // LDS of the fused kernel behind the forward's P / Q / bias regions: the dZ3 tile (64 rows x 32 * layer[3].NBB bf16 columns), the
 // head waves' partial sums, and H2 (64 x layer[2].N bf16) -- the forward writes it there instead of over H0, so that all three
 // activations are resident for the dZ chain
@@ -1087,9 +1098,12 @@ inline int fb_lds_bytes(const int32_t* dims) {
 
 // VU: the unclipped value loss (HgymPPOConfig.value_loss_unclipped); a template parameter, so that the clipped kernels stay as they were
 // ML: the actor's head also forms the mirror loss (FbMirror, *Mr); off by default, `if constexpr`: every other instantiation is what it was
-template <int G1, bool AUX = false, bool XB16 = false, bool VU = false, bool GA = false, bool ML = false>
+// BC: the actor's head forms the behaviour-cloning regression instead of the PPO loss (FbBC, *Bc); off by default, `if constexpr` and
+// lambdas of its own (l2idle_bc, head_bc) that no other instantiation calls
+template <int G1, bool AUX = false, bool XB16 = false, bool VU = false, bool GA = false, bool ML = false, bool BC = false>
 __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const FusedNet& n, bool is_actor, char* smem,
-                                        const FbMirror* Mr = nullptr) {
+                                        const FbMirror* Mr = nullptr, const FbBC* Bc = nullptr) {
+    static_assert(!BC || (!AUX && !ML && !VU), "the behaviour-cloning head is the actor's alone");
     constexpr int BM = 64, NW = 16, D = 2, MB = BM / 16;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 15, q = lane >> 4;
@@ -1332,7 +1346,74 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
             }
         }
     };
-    if constexpr (AUX) {
+    // Behaviour cloning.  l2idle_bc: wavefronts 8 .. 15 bring the tile's 64 target rows (three 16-byte loads per row, gathered through
+    // rowidx) into lin[row * 12 ..] while the other eight compute the third layer.  head_bc: lane (r, q) of head wave hw holds outputs
+    // 4q .. 4q + 3 of row m: e = mu - t, d mu and the row's loss terms; dZ3 and the partial row leave as in `head`.
+    auto l2idle_bc = [&](int) {
+        if (!pre) return;
+        const int j = tid - 8 * 64;
+        if (j < 0 || j >= 192) return;
+        const int rw = j / 3, k = j - 3 * rw;
+        const int64_t ri = rowidx[rw];
+        const F4 vt = *reinterpret_cast<const F4*>(Bc->target + ri * 12 + 4 * k);
+        *reinterpret_cast<F4*>(lin + rw * 12 + 4 * k) = vt;
+    };
+    auto head_bc = [&](int hw, int m, int, const float (&out)[4]) {
+        const bool valid = m < a.M;
+        const int rl = hw * 16 + r;
+        const int64_t row = rowidx[rl];
+        float g[4] = {0.f, 0.f, 0.f, 0.f};
+        float part[5] = {0.f, 0.f, 0.f, 0.f, 0.f};      // [0] the loss terms, [1 + e] d mu of output 4q + e
+        float ls = 0.0f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int j = 4 * q + e;
+            if (j < A) {
+                const float t = pre ? lin[rl * 12 + j] : Bc->target[row * A + j];
+                const float d = out[e] - t;
+                float gd, le;
+                if (Bc->huber) {
+                    const float ad = fabsf(d);
+                    gd = clampf(d, -Bc->delta, Bc->delta);
+                    le = ad <= Bc->delta ? 0.5f * d * d : Bc->delta * (ad - 0.5f * Bc->delta);
+                } else {
+                    gd = 2.0f * d;
+                    le = d * d;
+                }
+                if (valid) {
+                    g[e] = gd * Bc->inv;
+                    part[1 + e] = g[e];
+                    ls += le;
+                }
+            }
+        }
+        ls += __shfl_xor(ls, 16, 64); ls += __shfl_xor(ls, 32, 64);
+        if (q == 0) part[0] = ls;
+        const u32x2 pk = pack_bf16x4(g[0], g[1], g[2], g[3]);
+        const u32x2 zero = {0u, 0u};
+        const int off0 = (hw * 2 + 0) * 512 + r * 32 + q * 8, off1 = (hw * 2 + 1) * 512 + r * 32 + q * 8;
+        *reinterpret_cast<u32x2*>(R0 + off0) = pk;
+        *reinterpret_cast<u32x2*>(R0 + off1) = zero;
+        char* gz = reinterpret_cast<char*>(n.dZ[3]) + mbg0 * 2 * 512;
+        *reinterpret_cast<u32x2*>(gz + off0) = pk;
+        *reinterpret_cast<u32x2*>(gz + off1) = zero;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            float v = part[k];
+            v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64); v += __shfl_xor(v, 8, 64);
+            part[k] = v;
+        }
+        if (r == 0) {
+            float* w = red + hw * LOSS_PARTIALS;
+            if (q == 0) w[LP_MIRROR] = part[0];      // the partial row's regression slot: the behaviour loss here, the mirror loss in an ML tile
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (4 * q + e < 12) w[LP_DBIAS_MU + 4 * q + e] = part[1 + e];
+        }
+    };
+    if constexpr (BC) {
+        fwd_body<BM, NW, D, G1, false, XB16, false, GA>(a, n, true, smem, FwdNoop(), FwdNoop(), FwdNoop(), 0, FwdNoop(), head_bc, H2, rowidx, l2idle_bc);
+    } else if constexpr (AUX) {
         fwd_body<BM, NW, D, G1, true, XB16, false, GA>(a, n, false, smem, FwdNoop(), FwdNoop(), FwdNoop(), 0, FwdNoop(), head_aux, H2, rowidx);
         if (wave < MB) {
 #pragma unroll
@@ -1344,7 +1425,7 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
     }
     __syncthreads();          // dZ3 tile and the per-wave sums are in LDS; H0 sits in P, H1 in Q, H2 in its own buffer
     if (tid < LOSS_PARTIALS) {
-        const bool mine = AUX ? tid == LP_AUX : (is_actor ? ((tid != LP_VALUE && tid < LP_DBIAS_V) || (ML && tid == LP_MIRROR)) : (tid == LP_VALUE || tid == LP_DBIAS_V));
+        const bool mine = BC ? ((tid >= LP_DBIAS_MU && tid < LP_DBIAS_V) || tid == LP_MIRROR) : AUX ? tid == LP_AUX : (is_actor ? ((tid != LP_VALUE && tid < LP_DBIAS_V) || (ML && tid == LP_MIRROR)) : (tid == LP_VALUE || tid == LP_DBIAS_V));
         if (mine) L.partials[(int64_t)blockIdx.x * LOSS_PARTIALS + tid] = red[tid] + red[LOSS_PARTIALS + tid] + red[2 * LOSS_PARTIALS + tid] + red[3 * LOSS_PARTIALS + tid];
     }
     // ---- dZ chain on the resident tile
@@ -1461,6 +1542,34 @@ int32_t launch_mlp_fb_mirror_form(const FwdArgs& fb0, const FbLoss& fl, const Fb
     if (g1 == 1) return shadow ? launch_mlp_fb_mirror_one<1, true, GA>(fb, fl, mr, tiles, lds, s) : launch_mlp_fb_mirror_one<1, false, GA>(fb, fl, mr, tiles, lds, s);
     if (g1 == 2) return shadow ? launch_mlp_fb_mirror_one<2, true, GA>(fb, fl, mr, tiles, lds, s) : launch_mlp_fb_mirror_one<2, false, GA>(fb, fl, mr, tiles, lds, s);
     if (g1 == 3) return shadow ? launch_mlp_fb_mirror_one<3, true, GA>(fb, fl, mr, tiles, lds, s) : launch_mlp_fb_mirror_one<3, false, GA>(fb, fl, mr, tiles, lds, s);
+    return HGYM_E_UNSUPPORTED;
+}
+
+// The ACTOR's update tile with the behaviour-cloning head (hgym_bc_grad): one kernel per first hidden width, input form and activation
+// form, the actor alone -- no other net has tiles in a cloning step.  hgym_update_bc.hip holds the ELU(1) kernels, hgym_update_act_bc.hip
+// the generic ones.
+template <int G1, bool XB16, bool GA>
+__global__ __launch_bounds__(1024) void mlp_fb_bc_kernel(const FwdArgs a, const FbLoss L, const FbBC bc) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    fb_body<G1, false, XB16, false, GA, false, true>(a, L, a.net[0], true, smem, nullptr, &bc);
+}
+template <int G1, bool XB16, bool GA>
+int32_t launch_mlp_fb_bc_one(const FwdArgs& fb, const FbLoss& fl, const FbBC& bc, int tiles, size_t lds, hipStream_t s) {
+    const int32_t rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&mlp_fb_bc_kernel<G1, XB16, GA>), lds, "mlp_fb_bc_kernel");
+    if (rc) return rc;
+    hipLaunchKernelGGL((mlp_fb_bc_kernel<G1, XB16, GA>), dim3(tiles), dim3(1024), lds, s, fb, fl, bc);
+    return HGYM_OK;
+}
+template <bool GA>
+int32_t launch_mlp_fb_bc_form(const FwdArgs& fb0, const FbLoss& fl, const FbBC& bc, bool shadow, int tiles, hipStream_t s) {
+    FwdArgs fb = fb0;
+    fb.net0 = 0;
+    fb.nets = 1;
+    const size_t lds = (size_t)fb_lds_bytes(fb.net[0]);      // the targets lie in the loss-input region the sum already holds
+    const int g1 = fb.net[0].layer[0].NB / 16;         // first hidden width 256 / 512 / 768
+    if (g1 == 1) return shadow ? launch_mlp_fb_bc_one<1, true, GA>(fb, fl, bc, tiles, lds, s) : launch_mlp_fb_bc_one<1, false, GA>(fb, fl, bc, tiles, lds, s);
+    if (g1 == 2) return shadow ? launch_mlp_fb_bc_one<2, true, GA>(fb, fl, bc, tiles, lds, s) : launch_mlp_fb_bc_one<2, false, GA>(fb, fl, bc, tiles, lds, s);
+    if (g1 == 3) return shadow ? launch_mlp_fb_bc_one<3, true, GA>(fb, fl, bc, tiles, lds, s) : launch_mlp_fb_bc_one<3, false, GA>(fb, fl, bc, tiles, lds, s);
     return HGYM_E_UNSUPPORTED;
 }
 

@@ -167,4 +167,100 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(const LossArgs a) {
         red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
 
+// ------------------------------------------------------------------------------------------------ behaviour cloning (hgym_bc_grad)
+// bc_loss_kernel: the regression head of the layer-by-layer path, one thread per sample: e = mu - target[idx[i]], d mu into the actor's
+// last dY / dYT (the operands of the backward that follows), the sample's loss terms and d mu into the block's partial row (LP_MIRROR --
+// the partial row's regression slot -- and LP_DBIAS_MU).  bc_scalars_kernel: one workgroup that adds the partial rows of either path in a
+// fixed order (16 interleaved fp64 sums per quantity, as ppo_scalars_block) -> sums[0] += loss, sums[1] += 1, opt[HGYM_OPT_GRAD_SQNORM] = 0
+// for the slab sum behind it, and -- fused path -- the head bias gradient.  It touches no other slot of opt_state.
+struct BcLossArgs {
+    const float* mu;             // [B][A] the actor's fp32 output
+    const float* target;         // (num_rows, A), gathered through idx
+    const int64_t* idx;
+    int B, Bp, A;
+    void* dmu;  int64_t ld_dmu;  // [B][Ncp] operand type
+    void* dmuT; int64_t ld_t;    // [A16][Mp]
+    float inv, delta;            // 1 / (B A); Huber's delta
+    int huber;
+    float* partials;             // [gridDim.x][LOSS_PARTIALS]
+};
+struct BcScalArgs {
+    int nblocks, B, A;
+    const float* partials;
+    float* grads_bmu;            // the head bias gradient (fused path), null: it comes from the slabs
+    double* opt;
+    double* sums;
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void bc_loss_kernel(const BcLossArgs a) {
+    __shared__ float red[4][16];
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int A = a.A;
+    float acc[13];               // [0 .. 12) d mu, [12] the loss terms
+#pragma unroll
+    for (int k = 0; k < 13; ++k) acc[k] = 0.0f;
+    T* dmu = (T*)a.dmu;
+    T* dmuT = (T*)a.dmuT;
+    if (i < a.B) {
+        const int64_t r = a.idx[i];
+#pragma unroll
+        for (int j = 0; j < 12; ++j) {
+            if (j >= A) continue;
+            const float d = a.mu[(int64_t)i * A + j] - a.target[r * A + j];
+            float gd, le;
+            if (a.huber) {
+                const float ad = fabsf(d);
+                gd = clampf(d, -a.delta, a.delta);
+                le = ad <= a.delta ? 0.5f * d * d : a.delta * (ad - 0.5f * a.delta);
+            } else {
+                gd = 2.0f * d;
+                le = d * d;
+            }
+            const float g = gd * a.inv;
+            acc[j] = g;
+            acc[12] += le;
+            dmu[(int64_t)i * a.ld_dmu + j] = from_f32<T>(g);
+            dmuT[(int64_t)j * a.ld_t + i] = from_f32<T>(g);
+        }
+    } else if (i < a.Bp) {       // zero the contraction padding of the gradient
+        for (int j = 0; j < A; ++j) dmuT[(int64_t)j * a.ld_t + i] = from_f32<T>(0.0f);
+    }
+#pragma unroll
+    for (int k = 0; k < 13; ++k) {
+        float s = acc[k];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = s;
+    }
+    __syncthreads();
+    const int k = threadIdx.x;
+    if (k < 13) a.partials[(int64_t)blockIdx.x * LOSS_PARTIALS + (k < 12 ? LP_DBIAS_MU + k : LP_MIRROR)] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
+}
+
+template <int THREADS = 512>      // (a template: emitted only where it is launched, hgym_update_bc.hip)
+__global__ __launch_bounds__(THREADS) void bc_scalars_kernel(const BcScalArgs a) {
+    static_assert(THREADS == 16 * LOSS_PARTIALS, "16 partial sums per quantity");
+    __shared__ double red[16][LOSS_PARTIALS + 1];
+    const int tid = threadIdx.x;
+    const int k = tid & (LOSS_PARTIALS - 1), part = tid / LOSS_PARTIALS;      // 512 threads: 16 parts
+    const bool used = (k >= LP_DBIAS_MU && k < LP_DBIAS_V) || k == LP_MIRROR;
+    double s = 0.0;
+    if (used)
+        for (int b = part; b < a.nblocks; b += 16) s += (double)a.partials[(int64_t)b * LOSS_PARTIALS + k];
+    red[part][k] = s;
+    __syncthreads();
+    if (tid < LOSS_PARTIALS && used) {
+        double t = 0.0;
+        for (int p = 0; p < 16; ++p) t += red[p][tid];
+        if (tid == LP_MIRROR) {
+            a.sums[0] += t / ((double)a.B * (double)a.A);
+            a.sums[1] += 1.0;
+            a.opt[HGYM_OPT_GRAD_SQNORM] = 0.0;      // accumulated by reduce_slabs_kernel later in this call
+        } else if (a.grads_bmu && tid - LP_DBIAS_MU < a.A) {
+            a.grads_bmu[tid - LP_DBIAS_MU] = (float)t;
+        }
+    }
+}
+
 }  // namespace hgym

@@ -31,6 +31,11 @@ int32_t launch_mlp_fb_act_mirror(const FwdArgs& fb, const FbLoss& fl, const FbMi
 // hgym_loss_mirror.hip: ppo_loss_kernel<.., ML = true>, the layer-by-layer path's loss with the mirror loss
 int32_t launch_ppo_loss_mirror(const LossArgs& a, bool bf16, bool unclipped, int nblocks, hipStream_t s);
 int32_t launch_mlp_fwd_act(const FwdArgs& a, int nets, bool wide, int64_t dbg_tiles, hipStream_t s);
+// hgym_update_bc.hip, hgym_update_act_bc.hip: the actor's tiles with the behaviour-cloning head, and the small kernels of hgym_bc_grad
+int32_t launch_mlp_fb_bc(const FwdArgs& fb, const FbLoss& fl, const FbBC& bc, bool shadow, int tiles, hipStream_t s);
+int32_t launch_mlp_fb_act_bc(const FwdArgs& fb, const FbLoss& fl, const FbBC& bc, bool shadow, int tiles, hipStream_t s);
+int32_t launch_bc_loss(const BcLossArgs& a, bool bf16, int nblocks, hipStream_t s);
+int32_t launch_bc_scalars(const BcScalArgs& a, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------ layouts
 struct LayerLayout {
@@ -825,6 +830,36 @@ struct NetBase {
         return net.norm ? norm_fold_bias(&cfg, &net, s) : HGYM_OK;
     }
 
+    // hgym_bc_grad, both paths.  bc_zero_grads: the whole gradient vector and the KL slot to +0.0 ahead of the step's launches -- what a
+    // cloning step does not train (std, critic, auxiliary head) must leave Adam with nothing to apply.  bc_reduce_actor: reduce_range over
+    // the actor's segments alone (and, through them, the squared norm: every other entry is zero).
+    int32_t bc_zero_grads() {
+        const hipError_t e = hipMemsetAsync(net.grads, 0, (size_t)(w.P + 1) * sizeof(float), s);
+        HG_REQUIRE(e == hipSuccess, HGYM_E_LAUNCH, "hipMemsetAsync(grads): %s", hipGetErrorString(e));
+        return HGYM_OK;
+    }
+    int32_t bc_reduce_actor(int Mp) { return reduce_range(w.net[0].layer[0].w_off, w.net[1].layer[0].w_off, Mp); }
+
+    // slab reduction of the segments whose parameters lie in [lo, hi) of the flat vector (Mp: an auxiliary head on the layer-by-layer
+    // path took its slab counts from the minibatch's contraction padding)
+    int32_t reduce_range(int64_t lo, int64_t hi, int Mp) {
+        const SegTable all = segments(Mp);
+        SegTable tab;
+        memset(&tab, 0, sizeof(tab));
+        int64_t elems = 0;
+        for (int i = 0; i < all.n; ++i)
+            if (all.s[i].off >= lo && all.s[i].off < hi) {
+                tab.s[tab.n++] = all.s[i];
+                elems += (int64_t)all.s[i].rows * all.s[i].cols;
+            }
+        if (tab.n == 0) return HGYM_OK;
+        prof_begin(HGYM_PROF_REDUCE, s);
+        hipLaunchKernelGGL(reduce_slabs_kernel, dim3(RSN_X, tab.n), dim3(256), 0, s, tab, w.Ps, at<float>(w.slabs), net.grads, net.opt_state);
+        prof_end(HGYM_PROF_REDUCE, s, (double)elems * 4.0 * (w.dw_splits + 1));
+        HG_CHECK_LAUNCH("reduce_slabs_kernel");
+        return HGYM_OK;
+    }
+
     // Observation normalisation, after the statistics moved: the operand copies of the first-layer weights (the only ones that hold the
     // scale) and the effective biases.
     template <typename T>
@@ -1047,6 +1082,44 @@ struct GemmPath : NetBase {
         return HGYM_OK;
     }
 
+    // hgym_bc_grad: the actor's forward, bc_loss_kernel, the actor's backward, the actor's slab sums
+    int32_t bc_grad(const HgymBCConfig& bc, const HgymBatch& b, const float* target, double* sums) {
+        const int B = b.B, A = cfg.num_actions;
+        float* mu = at<float>(w.net[0].out_f32);
+        int32_t rc = bc_zero_grads();
+        if (rc) return rc;
+        rc = forward(0, B, b.obs, cfg.num_obs, b.idx, mu, A, true);
+        if (rc) return rc;
+        const int Bp = (int)round_up(B, w.SE);
+        const int nblocks = ceil_div(Bp, 256);
+        HG_REQUIRE(nblocks <= MAX_LOSS_BLOCKS, HGYM_E_UNSUPPORTED, "minibatch %d too large for the loss partial buffer", B);
+        const LayerLayout& la = w.net[0].layer[w.net[0].L - 1];
+        BcLossArgs a;
+        memset(&a, 0, sizeof(a));
+        a.mu = mu;
+        a.target = target;
+        a.idx = b.idx;
+        a.B = B;
+        a.Bp = Bp;
+        a.A = A;
+        a.dmu = at<T>(la.dY);
+        a.ld_dmu = la.Ncp;
+        a.dmuT = at<T>(la.dYT);
+        a.ld_t = w.Mp;
+        a.inv = 1.0f / ((float)B * (float)A);
+        a.delta = bc.huber_delta;
+        a.huber = bc.loss_type == HGYM_BC_HUBER;
+        a.partials = at<float>(w.partials);
+        rc = launch_bc_loss(a, sizeof(T) == 2, nblocks, s);
+        if (rc) return rc;
+        const BcScalArgs sc = {nblocks, B, A, at<float>(w.partials), nullptr, net.opt_state, sums};
+        rc = launch_bc_scalars(sc, s);
+        if (rc) return rc;
+        rc = backward(0, B);
+        if (rc) return rc;
+        return bc_reduce_actor(Bp);
+    }
+
     int32_t act(int M, const float* obs, const float* priv, const float* z, uint64_t seed, const int64_t* step, float* actions, float* mu,
                 float* sigma, float* logp, float* values, const FinArgs* fin, const HgymObsShadow* sh) {
         HG_REQUIRE(!sh || (!sh->obs && !sh->priv), HGYM_E_UNSUPPORTED, "the observation shadow exists on the fused bf16 path only (hgym_net_shadow_ld = 0 here)");
@@ -1214,7 +1287,8 @@ struct FusedPath : NetBase {
     // rows, same columns -- and every bias gradient of it is a column sum of dZ: its loss has no per-tile partial sums for them)
     // gb (mlp_fb_kernel<XB16> ran): the first-layer operands were never copied -- those products gather their rows by gb->idx from the
     // bf16 shadows
-    int32_t dw(int nets, int B, const ScalArgs& sc, const HgymBatch* gb) {
+    // ride: the loss-scalar workgroup `sc` rides in the launch (false: hgym_bc_grad, whose scalars have a launch of their own)
+    int32_t dw(int nets, int B, const ScalArgs& sc, const HgymBatch* gb, bool ride = true) {
         const int Bp = (int)round_up(B, 64);
         DwArgs d;
         memset(&d, 0, sizeof(d));
@@ -1255,34 +1329,14 @@ struct FusedPath : NetBase {
         d.slab_stride = w.Ps;
         d.zeros = at<char>(w.zeros);
         d.sc = sc;
-        d.scal_bid = tile * (int)round_up(w.dw_splits, 8);
-        const int blocks = d.scal_bid + 1;
+        d.scal_bid = ride ? tile * (int)round_up(w.dw_splits, 8) : -1;
+        const int blocks = tile * (int)round_up(w.dw_splits, 8) + (ride ? 1 : 0);
         const int32_t rc_lds = ensure_dynamic_lds(reinterpret_cast<const void*>(&dw_kernel_rs<3>), DW_LDS_STAGES * DW_STAGE_BYTES, "dw_kernel_rs");
         if (rc_lds != HGYM_OK) return rc_lds;
         prof_begin(HGYM_PROF_DW, s);
         hipLaunchKernelGGL(dw_kernel_rs<3>, dim3(blocks), dim3(DW_THREADS), DW_LDS_STAGES * DW_STAGE_BYTES, s, d);
         prof_end(HGYM_PROF_DW, s, fl);
         HG_CHECK_LAUNCH("dw_kernel_rs");
-        return HGYM_OK;
-    }
-
-    // slab reduction of the segments whose parameters lie in [lo, hi) of the flat vector (Mp: an auxiliary head on the layer-by-layer
-    // path took its slab counts from the minibatch's contraction padding)
-    int32_t reduce_range(int64_t lo, int64_t hi, int Mp) {
-        const SegTable all = segments(Mp);
-        SegTable tab;
-        memset(&tab, 0, sizeof(tab));
-        int64_t elems = 0;
-        for (int i = 0; i < all.n; ++i)
-            if (all.s[i].off >= lo && all.s[i].off < hi) {
-                tab.s[tab.n++] = all.s[i];
-                elems += (int64_t)all.s[i].rows * all.s[i].cols;
-            }
-        if (tab.n == 0) return HGYM_OK;
-        prof_begin(HGYM_PROF_REDUCE, s);
-        hipLaunchKernelGGL(reduce_slabs_kernel, dim3(RSN_X, tab.n), dim3(256), 0, s, tab, w.Ps, at<float>(w.slabs), net.grads, net.opt_state);
-        prof_end(HGYM_PROF_REDUCE, s, (double)elems * 4.0 * (w.dw_splits + 1));
-        HG_CHECK_LAUNCH("reduce_slabs_kernel");
         return HGYM_OK;
     }
 
@@ -1393,6 +1447,50 @@ struct FusedPath : NetBase {
             if (rc) return rc;
         }
         return part == 0 ? reduce_range(0, critic_off, Mp) : reduce_range(0, w.P, Mp);
+    }
+
+    // hgym_bc_grad: the actor's tiles with the regression head (forward, d mu, dZ chain: one launch), the scalars, the actor's four
+    // weight-gradient products, the actor's slab sums
+    int32_t bc_grad(const HgymBCConfig& bc, const HgymBatch& b, const float* target, double* sums) {
+        const int B = b.B, A = cfg.num_actions;
+        const int Mp = (int)round_up(B, w.SE);
+        const bool shadow = b.obs_bf16 && b.num_rows > 0 && b.num_rows * shadow_ld(w, 0) * 2 < ((int64_t)1 << 32);
+        const int tiles = (int)round_up(B, 64) / 64;
+        HG_REQUIRE(tiles <= MAX_LOSS_BLOCKS, HGYM_E_UNSUPPORTED, "minibatch %d too large for the loss partial buffer", B);
+        HG_REQUIRE(A != 12 || ((uintptr_t)target & 15) == 0, HGYM_E_BADARG, "hgym_bc_grad: target must be 16-byte aligned");
+        int32_t rc = bc_zero_grads();
+        if (rc) return rc;
+        const NetIO io[3] = {{b.obs, cfg.num_obs, at<float>(w.net[0].out_f32), A}, {}, {}};
+        FwdArgs fb = make_fwd_args(0, 1, B, io, b.idx, true, nullptr, nullptr);
+        if (shadow) {
+            HG_REQUIRE(((uintptr_t)b.obs_bf16 & 15) == 0, HGYM_E_BADARG, "observation shadows must be 16-byte aligned");
+            fb.net[0].xb = (const __bf16*)b.obs_bf16;
+            fb.net[0].ldxb = shadow_ld(w, 0);
+            fb.net[0].X0 = nullptr;
+        }
+        FbLoss fl;
+        memset(&fl, 0, sizeof(fl));
+        fl.partials = at<float>(w.partials);
+        HG_REQUIRE((size_t)fb_lds_bytes(fb.net[0]) <= FB_LDS_LIMIT, HGYM_E_UNSUPPORTED, "mlp_fb_bc_kernel needs %d bytes of LDS", fb_lds_bytes(fb.net[0]));
+        fb.nets = 1;
+        fb.dbg = phase_buffer((int64_t)tiles);
+        const FbBC hb = {target, 1.0f / ((float)B * (float)A), bc.huber_delta, bc.loss_type == HGYM_BC_HUBER ? 1 : 0};
+        prof_begin(HGYM_PROF_MLP_FWD, s);
+        rc = act_is_elu1(w.act) ? launch_mlp_fb_bc(fb, fl, hb, shadow, tiles, s) : launch_mlp_fb_act_bc(fb, fl, hb, shadow, tiles, s);
+        double flops = 0.0;
+        for (int l = 0; l < 4; ++l) flops += 2.0 * (double)B * w.net[0].layer[l].N * w.net[0].layer[l].K;
+        for (int l = 1; l < 4; ++l) flops += 2.0 * (double)B * w.net[0].layer[l].K * w.net[0].layer[l].N;
+        prof_end(HGYM_PROF_MLP_FWD, s, flops);      // (before the error return: a refused launch must not leave the interval open)
+        if (rc) return rc;
+        HG_CHECK_LAUNCH("mlp_fb_bc_kernel");
+        const BcScalArgs sc = {tiles, B, A, at<float>(w.partials), net.grads + w.net[0].layer[3].b_off, net.opt_state, sums};
+        rc = launch_bc_scalars(sc, s);
+        if (rc) return rc;
+        ScalArgs none;
+        memset(&none, 0, sizeof(none));
+        rc = dw(1, B, none, shadow ? &b : nullptr, false);
+        if (rc) return rc;
+        return bc_reduce_actor(Mp);
     }
 
     int32_t act(int M, const float* obs, const float* priv, const float* z, uint64_t seed, const int64_t* step, float* actions, float* mu,
@@ -1651,6 +1749,27 @@ int32_t hgym_ppo_grad_part(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, c
         HG_REQUIRE(net->grads && net->opt_state, HGYM_E_BADARG, "null grads / opt_state");
         rc = check_batch(R.w, ppo, batch);
         return rc ? rc : R.grad(*ppo, *batch, part);
+    });
+}
+
+int32_t hgym_bc_grad(const HgymNetConfig* cfg, const HgymBCConfig* bc, const HgymNet* net, const HgymBatch* batch, const float* target,
+                     double* sums, void* stream) {
+    // every refusal below comes before anything is launched (and before any pointer of `net` is looked at)
+    HG_REQUIRE(cfg && bc && net && batch, HGYM_E_BADARG, "hgym_bc_grad: null cfg / bc / net / batch");
+    HG_REQUIRE(target && sums, HGYM_E_BADARG, "hgym_bc_grad: null target / sums");
+    HG_REQUIRE(((uintptr_t)sums & 7) == 0 && ((uintptr_t)target & 3) == 0, HGYM_E_BADARG, "hgym_bc_grad: misaligned target / sums");
+    HG_REQUIRE(bc->loss_type == HGYM_BC_MSE || bc->loss_type == HGYM_BC_HUBER, HGYM_E_BADARG,
+               "HgymBCConfig.loss_type=%d (HGYM_BC_MSE = 0, HGYM_BC_HUBER = 1)", bc->loss_type);
+    // (written so that a NaN fails it)
+    HG_REQUIRE(bc->loss_type != HGYM_BC_HUBER || (bc->huber_delta > 0.0f && bc->huber_delta < INFINITY), HGYM_E_BADARG,
+               "HgymBCConfig.huber_delta=%g must be finite and > 0", (double)bc->huber_delta);
+    HG_REQUIRE(batch->B >= 1 && batch->B <= cfg->max_batch, HGYM_E_BADARG, "hgym_bc_grad: B=%d outside [1, max_batch = %d]", batch->B,
+               cfg->max_batch);
+    HG_REQUIRE(batch->obs && batch->idx, HGYM_E_BADARG, "hgym_bc_grad: null HgymBatch.obs / idx");
+    return run(cfg, net, stream, [&](auto& R) -> int32_t {
+        HG_REQUIRE(net->grads && net->opt_state, HGYM_E_BADARG, "null grads / opt_state");
+        HG_REQUIRE(!net->norm, HGYM_E_UNSUPPORTED, "hgym_bc_grad with HgymNet.norm set: observation normalisation is not part of a cloning step");
+        return R.bc_grad(*bc, *batch, target, sums);
     });
 }
 

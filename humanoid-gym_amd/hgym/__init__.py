@@ -4,6 +4,7 @@ from ._lib import lib, check, HgymError
 from .env_buffers import EnvBuffers, default_env_config, log_stats_summary
 from .net import NetBuffers, make_net_config, make_ppo_config, make_batch, activation_spec, diag_from_block, DIAG_KEYS, opt_summary
 from .net import check_obs_norm, norm_layout
+from .net import make_bc_config, make_bc_batch, BC_LOSS_TYPES
 
 
 def mirror_rows(src, dst, src_col, sign, zero_to=None):

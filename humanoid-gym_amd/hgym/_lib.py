@@ -158,6 +158,14 @@ class Batch(C.Structure):
                 ("mirror_target", c_float_p), ("mirror_sums", c_f64_p)]
 
 
+BC_MSE, BC_HUBER = 0, 1    # HGYM_BC_*
+
+
+class BCConfig(C.Structure):
+    """HgymBCConfig: the loss of a behaviour-cloning minibatch (hgym_bc_grad)."""
+    _fields_ = [("loss_type", C.c_int32), ("huber_delta", C.c_float)]
+
+
 class ObsShadow(C.Structure):
     """HgymObsShadow: where a policy launch leaves the bf16 of the observation rows it reads (row-major, ld in elements)."""
     _fields_ = [("obs", C.c_void_p), ("ld_obs", C.c_int64), ("priv", C.c_void_p), ("ld_priv", C.c_int64)]
@@ -165,7 +173,7 @@ class ObsShadow(C.Structure):
 
 STRUCTS = dict(HgymEnvConfig=EnvConfig, HgymStrided=Strided, HgymSimTensors=SimTensors, HgymEnvState=EnvState,
                HgymEnvOut=EnvOut, HgymEnvNoise=EnvNoise, HgymNetConfig=NetConfig, HgymPPOConfig=PPOConfig,
-               HgymNet=Net, HgymBatch=Batch, HgymObsShadow=ObsShadow, HgymComm=Comm)
+               HgymNet=Net, HgymBatch=Batch, HgymObsShadow=ObsShadow, HgymComm=Comm, HgymBCConfig=BCConfig)
 
 # every symbol include/hgym.h declares: name -> (restype, argtypes)
 _P = C.POINTER
@@ -238,6 +246,7 @@ SYMBOLS = {
     "hgym_ppo_diagnostics": (C.c_int32, [_P(NetConfig), _P(PPOConfig), _P(Net), _P(Batch), C.c_int64, c_float_p, c_f64_p, C.c_void_p]),
     "hgym_ppo_grad": (C.c_int32, [_P(NetConfig), _P(PPOConfig), _P(Net), _P(Batch), C.c_void_p]),
     "hgym_ppo_grad_part": (C.c_int32, [_P(NetConfig), _P(PPOConfig), _P(Net), _P(Batch), C.c_int32, C.c_void_p]),
+    "hgym_bc_grad": (C.c_int32, [_P(NetConfig), _P(BCConfig), _P(Net), _P(Batch), c_float_p, c_f64_p, C.c_void_p]),
     "hgym_net_param_offset": (C.c_int64, [_P(NetConfig), C.c_int32]),
     "hgym_ppo_apply": (C.c_int32, [_P(NetConfig), _P(PPOConfig), _P(Net), C.c_void_p]),
     "hgym_prof_enable": (C.c_int32, [C.c_int32]),

@@ -322,6 +322,13 @@ class NetBuffers:
         L.check(L.lib.hgym_ppo_grad_part(C.byref(self.cfg), C.byref(ppo), C.byref(self.struct), C.byref(batch), int(part), self.stream()),
                 "hgym_ppo_grad_part")
 
+    def bc_grad(self, bc, batch, target, sums):
+        """hgym_bc_grad: one behaviour-cloning minibatch of the actor (make_bc_config, make_bc_batch).  target: (rows, num_actions) fp32,
+        contiguous, gathered through the batch's idx; sums: float64 (2,), [0] += the minibatch's loss, [1] += 1."""
+        assert target.dtype == torch.float32 and target.is_contiguous() and sums.dtype == torch.float64 and sums.numel() >= 2
+        L.check(L.lib.hgym_bc_grad(C.byref(self.cfg), C.byref(bc), C.byref(self.struct), C.byref(batch), L.fptr(target), L.f64ptr(sums),
+                                   self.stream()), "hgym_bc_grad")
+
     @property
     def bucket_split(self):
         """Offset of the critic's first parameter in the flat vector: the boundary of the two gradient buckets."""
@@ -379,6 +386,33 @@ def make_batch(obs, priv, actions, values, advantages, returns, logp, mu, sigma,
         assert sums.dtype == torch.float64 and sums.is_contiguous() and sums.numel() >= 2
         b.pair_idx, b.mirror_act_src, b.mirror_act_sign = L.i64ptr(pair_idx), C.cast(src.data_ptr(), C.POINTER(C.c_int32)), L.fptr(sign)
         b.mirror_target, b.mirror_sums = L.fptr(target), L.f64ptr(sums)
+    return b
+
+
+BC_LOSS_TYPES = ("mse", "huber")
+
+
+def make_bc_config(loss_type="mse", huber_delta=1.0):
+    """HgymBCConfig of hgym_bc_grad: loss_type "mse" (torch's mse_loss) or "huber" (torch's huber_loss with delta = huber_delta > 0, finite).
+    ValueError for anything else."""
+    import math
+    if loss_type not in BC_LOSS_TYPES:
+        raise ValueError("loss_type=%r: one of %s" % (loss_type, ", ".join(BC_LOSS_TYPES)))
+    d = float(huber_delta)
+    if loss_type == "huber" and not (d > 0.0 and math.isfinite(d)):
+        raise ValueError("huber_delta=%r: must be finite and > 0" % (huber_delta,))
+    return L.BCConfig(L.BC_HUBER if loss_type == "huber" else L.BC_MSE, d)
+
+
+def make_bc_batch(obs, idx, obs_bf16=None):
+    """The HgymBatch hgym_bc_grad reads: obs (rows, num_obs) fp32 contiguous, idx int64 (B,), optionally the (rows, ld) bfloat16 shadow of
+    obs.  Every other member stays NULL."""
+    assert obs.is_contiguous() and obs.dtype == torch.float32 and idx.dtype == torch.int64 and idx.is_contiguous()
+    b = L.Batch()
+    b.obs, b.idx, b.B, b.num_rows = L.fptr(obs), L.i64ptr(idx), int(idx.numel()), int(obs.shape[0])
+    if obs_bf16 is not None:
+        assert obs_bf16.dtype == torch.bfloat16 and obs_bf16.is_contiguous() and obs_bf16.shape[0] == obs.shape[0]
+        b.obs_bf16 = C.c_void_p(obs_bf16.data_ptr())
     return b
 
 

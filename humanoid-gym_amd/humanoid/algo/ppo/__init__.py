@@ -1,4 +1,6 @@
 from .ppo import PPO
+from .student_teacher import StudentTeacher
+from .distillation import Distillation
 from .on_policy_runner import OnPolicyRunner
 from .actor_critic import ActorCritic
 from .rollout_storage import RolloutStorage

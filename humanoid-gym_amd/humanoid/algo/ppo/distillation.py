@@ -1,0 +1,134 @@
+"""Distillation: rsl_rl's second algorithm on the MI355X hot path -- behaviour cloning of a trained teacher into the student of a
+StudentTeacher policy, on the states the student itself visits (DAgger style).
+
+A subclass of PPO, so the runner's loop plans, both rollout forms, the sinks, logging, save and load carry over.  The rollout is PPO's:
+the student acts with its noise; the critic's values are computed as ever and then ignored.  compute_returns() runs no GAE: it makes one
+pass of the teacher over the T N stored observation rows into storage.teacher_actions.  update() walks the storage in slices of
+`gradient_length` steps, in storage order (rsl_rl's order: no permutation), one hgym_bc_grad + hgym_ppo_apply -- one Adam step -- per
+slice and epoch.  Nothing but the student is trained: the critic and sigma keep their bits through a whole run.
+"""
+import math
+
+import torch
+
+from .ppo import PPO
+from .student_teacher import StudentTeacher
+
+NO_CLIP = 3.0e38      # max_grad_norm=None: a clip that never binds (coef = min(max_norm / (norm + 1e-6), 1) = 1)
+
+
+class Distillation(PPO):
+    policy: StudentTeacher
+    LOSS_TYPES = ("mse", "huber")
+
+    def __init__(self, policy, num_learning_epochs=1, gradient_length=15, learning_rate=1e-3, max_grad_norm=None, loss_type="mse",
+                 huber_delta=1.0, device="cpu"):
+        if loss_type not in self.LOSS_TYPES:
+            raise ValueError("Distillation.loss_type=%r: one of %s" % (loss_type, ", ".join(self.LOSS_TYPES)))
+        if loss_type == "huber" and not (float(huber_delta) > 0.0 and math.isfinite(float(huber_delta))):
+            raise ValueError("Distillation.huber_delta=%r: must be finite and > 0" % (huber_delta,))
+        if int(gradient_length) != gradient_length or gradient_length < 1:
+            raise ValueError("Distillation.gradient_length=%r: must be an integer >= 1" % (gradient_length,))
+        if max_grad_norm is not None and not (float(max_grad_norm) > 0.0):
+            raise ValueError("Distillation.max_grad_norm=%r: must be None or > 0" % (max_grad_norm,))
+        super().__init__(policy, num_learning_epochs=num_learning_epochs, num_mini_batches=1, learning_rate=learning_rate,
+                         max_grad_norm=NO_CLIP if max_grad_norm is None else float(max_grad_norm), schedule="fixed", desired_kl=None,
+                         device=device)
+        self.policy = policy
+        self.gradient_length = int(gradient_length)
+        self.loss_type, self.huber_delta = loss_type, float(huber_delta)
+        self.last_behavior_loss = None
+        self._bc_sums = None
+
+    @staticmethod
+    def check_setup(policy, num_transitions_per_env, gradient_length, world=1, symmetry=None, mirror_loss_coef=0.0,
+                    advantage_normalization="batch"):
+        """What init_storage refuses, as a function that needs no device (ValueError each): more than one rank; symmetry, the mirror loss or
+        an advantage normalisation other than the default; a policy that is not a StudentTeacher; T % gradient_length != 0 (rsl_rl
+        silently carries the remainder over to the next rollout)."""
+        if int(world) > 1:
+            raise ValueError("Distillation runs on one rank (world size %d)" % int(world))
+        if symmetry is not None or float(mirror_loss_coef or 0.0) != 0.0:
+            raise ValueError("Distillation does not support PPO.symmetry / PPO.mirror_loss_coef")
+        if advantage_normalization != PPO.advantage_normalization:
+            raise ValueError("Distillation uses no advantages: advantage_normalization=%r must stay %r"
+                             % (advantage_normalization, PPO.advantage_normalization))
+        if not isinstance(policy, StudentTeacher):
+            raise ValueError("Distillation needs a StudentTeacher policy, not %s" % type(policy).__name__)
+        if int(num_transitions_per_env) % int(gradient_length) != 0:
+            raise ValueError("Distillation: num_steps_per_env=%d is not a multiple of gradient_length=%d"
+                             % (int(num_transitions_per_env), int(gradient_length)))
+
+    def init_storage(self, num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape):
+        self.check_setup(self.actor_critic, num_transitions_per_env, self.gradient_length, self._world, self.symmetry,
+                         self.mirror_loss_coef, self.advantage_normalization)
+        # one "minibatch" is one slice: gradient_length * N rows (PPO.init_storage sizes the net's max_batch from it)
+        self.num_mini_batches = int(num_transitions_per_env) // self.gradient_length
+        super().init_storage(num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape)
+        hgym, st = self._hgym, self.storage
+        T, N = st.num_transitions_per_env, st.num_envs
+        st.teacher_actions = torch.zeros(T, N, *action_shape, dtype=torch.float32, device=self.device)
+        self._bc_cfg = hgym.make_bc_config(self.loss_type, self.huber_delta)
+        # the step is hgym_ppo_apply's: no learning-rate rule, its own norm pass, the clip as asked for
+        self._ppo_cfg = hgym.make_ppo_config(max_grad_norm=self.max_grad_norm, desired_kl=0.0, adaptive=False, world_size=1,
+                                             grad_norm_ready=False)
+        self._bc_sums = torch.zeros(2, dtype=torch.float64, device=self.device)
+        self._rows = torch.arange(T * N, dtype=torch.int64, device=self.device)
+
+    # ------------------------------------------------------------------
+    def compute_returns(self, last_critic_obs):
+        """No returns: the teacher's mean action for every stored observation row -> storage.teacher_actions, one pass in pieces of at
+        most max_batch rows.  Nothing inside a rollout consumes the teacher's action, so the pass is deferred to here, as the critic's is
+        on the deferred-values path."""
+        st = self.storage
+        T = st.num_transitions_per_env
+        self.actor_critic.teacher_pass(st._obs_all[:T].flatten(0, 1), st.teacher_actions.flatten(0, 1))
+        self._returns_done()
+
+    def update_capturable(self):
+        return False      # the update is issued eagerly; capturing it is not built
+
+    def _update_done(self):      # no permutation was drawn: the draw counters stay where they are
+        self.storage.cleared()
+
+    def update(self, sync=True):
+        """For each epoch and each of the T / gradient_length slices in storage order: hgym_bc_grad on rows [t0 N, (t0 + gradient_length) N)
+        against storage.teacher_actions, then hgym_ppo_apply.  Returns (0.0, mean_behavior_loss); sync=False: (None, None), nothing read back."""
+        if not self.actor_critic.loaded_teacher:
+            raise RuntimeError("teacher not loaded")
+        hgym, net, st = self._hgym, self.net, self.storage
+        T, N = st.num_transitions_per_env, st.num_envs
+        mb = self.gradient_length * N
+        obs, target = st._obs_all[:T].flatten(0, 1), st.teacher_actions.flatten(0, 1)
+        sh = st.shadows()
+        self._bc_sums[0:2] = 0.0
+        for _ in range(self.num_learning_epochs):
+            for k in range(T // self.gradient_length):
+                batch = hgym.make_bc_batch(obs, self._rows[k * mb:(k + 1) * mb], None if sh is None else sh[0])
+                net.bc_grad(self._bc_cfg, batch, target, self._bc_sums)
+                net.ppo_apply(self._ppo_cfg)
+        st.rotate()
+        self._update_done()
+        if not sync:
+            return None, None
+        self.last_behavior_loss = self.behavior_loss_from(self.log_block().cpu())
+        return 0.0, self.last_behavior_loss
+
+    def log_block(self):
+        """opt_state and, behind it, the behaviour loss's two sums: ONE device tensor, one copy to the host."""
+        return torch.cat((self.net.opt_state, self._bc_sums))
+
+    def mirror_loss_from(self, block):
+        return None
+
+    def behavior_loss_from(self, block):
+        """The mean behaviour loss per Adam step of the last update from a host copy of log_block()."""
+        n = self.net.opt_state.numel()
+        return float(block[n]) / max(float(block[n + 1]), 1.0)
+
+    # ------------------------------------------------------------------ what a cloning run has no use for
+    def diagnostics_prepare(self):
+        raise RuntimeError("Distillation has no PPO diagnostics (no ratios, no advantages, no trained critic)")
+
+    def diagnostics(self, sync=True):
+        raise RuntimeError("Distillation has no PPO diagnostics (no ratios, no advantages, no trained critic)")

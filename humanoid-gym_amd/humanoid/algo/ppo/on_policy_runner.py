@@ -20,6 +20,8 @@ import torch
 
 from .ppo import PPO
 from .actor_critic import ActorCritic
+from .student_teacher import StudentTeacher  # noqa: F401  (policy_class_name is eval'ed below)
+from .distillation import Distillation  # noqa: F401  (algorithm_class_name likewise)
 from humanoid.algo.vec_env import VecEnv
 
 try:  # optional: logging back-ends are not part of the hot path
@@ -341,6 +343,8 @@ class OnPolicyRunner:
 
     # ------------------------------------------------------------------
     def learn(self, num_learning_iterations, init_at_random_ep_len=False):
+        if getattr(self.alg.actor_critic, "loaded_teacher", True) is False:      # a StudentTeacher that was never given its teacher (load)
+            raise RuntimeError("teacher not loaded")
         self._open_writer()
         if init_at_random_ep_len and self._keep_episode_lengths:
             init_at_random_ep_len = False            # (once: the episode lengths are part of the env state load() has just restored)
@@ -703,6 +707,8 @@ class OnPolicyRunner:
         o = hgym.opt_summary(pin["opt"][slot], snap["aux"])
         self.alg.last_denoise_loss = o["denoise_loss"]
         self.alg.last_mirror_loss = self.alg.mirror_loss_from(pin["opt"][slot])
+        if hasattr(self.alg, "behavior_loss_from"):      # Distillation: the loss rides in the same block
+            self.alg.last_behavior_loss = self.alg.behavior_loss_from(pin["opt"][slot])
         ep, returns, lengths = hgym.log_stats_summary(pin["ls"][slot], self.env.reward_names, KERNEL_REWARD_TERMS)
         collection_time, learn_time = ev[0].elapsed_time(ev[1]) * 1e-3, ev[1].elapsed_time(ev[2]) * 1e-3
         self.last_collection_time, self.last_learn_time = collection_time, learn_time
@@ -729,6 +735,9 @@ class OnPolicyRunner:
         mean_std = locs["mean_std"] if "mean_std" in locs else float(self._noise_std(self.alg.actor_critic).mean())
         learning_rate = locs["learning_rate"] if "learning_rate" in locs else self.alg.learning_rate
         fps = int(self.num_steps_per_env * self.env.num_envs / iteration_time)
+        behavior = getattr(self.alg, "last_behavior_loss", None)
+        if behavior is not None:      # Distillation.update() hands its loss back in the surrogate's place; a cloning run has no surrogate
+            locs = dict(locs, mean_surrogate_loss=0.0)
         scal("Loss/value_function", locs["mean_value_loss"], locs["it"])
         scal("Loss/surrogate", locs["mean_surrogate_loss"], locs["it"])
         scal("Loss/learning_rate", learning_rate, locs["it"])
@@ -736,6 +745,8 @@ class OnPolicyRunner:
             scal("Loss/denoise_mse", self.alg.last_denoise_loss, locs["it"])
         if getattr(self.alg, "_mirror_coef", 0.0) > 0.0 and getattr(self.alg, "last_mirror_loss", None) is not None:
             scal("Loss/mirror", self.alg.last_mirror_loss, locs["it"])
+        if behavior is not None:
+            scal("Loss/behavior", behavior, locs["it"])
         scal("Policy/mean_noise_std", mean_std, locs["it"])
         scal("Perf/total_fps", fps, locs["it"])
         scal("Perf/collection time", locs["collection_time"], locs["it"])
@@ -752,6 +763,8 @@ class OnPolicyRunner:
                f"""{'Value function loss:':>{pad}} {locs['mean_value_loss']:.4f}\n"""
                f"""{'Surrogate loss:':>{pad}} {locs['mean_surrogate_loss']:.4f}\n"""
                f"""{'Mean action noise std:':>{pad}} {mean_std:.2f}\n""")
+        if behavior is not None:
+            out += f"""{'Behavior loss:':>{pad}} {behavior:.6f}\n"""
         if have_eps:
             out += (f"""{'Mean reward:':>{pad}} {statistics.mean(locs['rewbuffer']):.2f}\n"""
                     f"""{'Mean episode length:':>{pad}} {statistics.mean(locs['lenbuffer']):.2f}\n""")
@@ -815,7 +828,9 @@ class OnPolicyRunner:
         t0 = time.time()
         net = getattr(self.alg, "net", None)
         if (net is None or not str(self.device).startswith("cuda") or os.environ.get("HGYM_ASYNC_SAVE", "1") == "0"
-                or not hasattr(self.alg.actor_critic, "_net")):
+                or not hasattr(self.alg.actor_critic, "_net")
+                # a StudentTeacher's teacher.* entries live in a second flat vector: the blocking form, which cuts nothing by offset
+                or getattr(self.alg.actor_critic, "_teacher_net", None) is not None):
             if env_state:
                 side = dict(env={k: (v.cpu() if torch.is_tensor(v) else v) for k, v in self.env.state_dict().items()},
                             **self._env_state_extra(iterations_done))
@@ -936,6 +951,15 @@ class OnPolicyRunner:
         The log sink's rings and the host's rewbuffer / lenbuffer are logging state, zeroed at every learn(): the first log blocks
         after a resume average over fewer episodes.  An evaluation env (set_eval_env) is not touched.  Without a sidecar: as ever."""
         _WRITER.wait()                      # a checkpoint this process is still writing
+        loaded = None
+        if isinstance(self.alg.actor_critic, StudentTeacher):
+            # a distillation run: a checkpoint without `teacher.*` entries is the TEACHER's PPO checkpoint (StudentTeacher.load_state_dict):
+            # its weights become the teacher, and nothing else of it -- no optimiser state, no env sidecar, iteration 0
+            loaded = torch.load(path, map_location=self.device)
+            if not any(k.startswith("teacher.") for k in loaded["model_state_dict"]):
+                self.alg.actor_critic.load_state_dict(loaded["model_state_dict"])
+                self.current_learning_iteration = 0
+                return loaded.get("infos")
         side_path = None
         if env_state is not False:
             side_path = env_state if isinstance(env_state, (str, os.PathLike)) else self.env_state_path(path)
@@ -955,7 +979,8 @@ class OnPolicyRunner:
             if int(side["num_steps_per_env"]) != int(self.num_steps_per_env):
                 raise ValueError("env state: num_steps_per_env is %d in the sidecar, %d here" % (int(side["num_steps_per_env"]), self.num_steps_per_env))
             self.env.check_state_dict(side["env"])      # (a sidecar that does not fit this env: refused before anything is changed)
-        loaded = torch.load(path, map_location=self.device)
+        if loaded is None:
+            loaded = torch.load(path, map_location=self.device)
         # a checkpoint of the other noise parametrisation: its first entry is another quantity under another name
         msd, mine = loaded["model_state_dict"], getattr(self.alg.actor_critic, "noise_std_type", "scalar")
         theirs = "log" if "log_std" in msd else ("scalar" if "std" in msd else mine)

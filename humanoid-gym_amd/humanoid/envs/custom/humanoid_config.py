@@ -64,3 +64,16 @@ class XBotLDWLCfgPPO(XBotLCfgPPO):
     policy = ns("policy", XBotLCfgPPO.policy, denoiser_hidden_dims=[512, 256, 128], denoiser_targets=_SINGLE_PRIV)
     algorithm = ns("algorithm", XBotLCfgPPO.algorithm, denoise_coef=1.0)
     runner = ns("runner", XBotLCfgPPO.runner, experiment_name="XBot_dwl_ppo")
+
+
+class XBotLDistillCfgPPO(XBotLCfgPPO):
+    """Distillation of a trained XBot-L actor into a smaller one (rsl_rl's Distillation / StudentTeacher): the
+    teacher has the reference actor's widths, the student [256, 128, 128].  The algorithm block carries Distillation.__init__'s keys only.
+    scripts/distill.py takes the teacher from the PPO experiment's log directory."""
+    policy = ns("policy", init_noise_std=0.1, student_hidden_dims=[256, 128, 128], teacher_hidden_dims=[512, 256, 128],
+                critic_hidden_dims=[768, 256, 128])
+    algorithm = ns("algorithm", num_learning_epochs=1, gradient_length=15, learning_rate=1e-3, max_grad_norm=None, loss_type="mse",
+                   huber_delta=1.0)
+    runner = ns("runner", XBotLCfgPPO.runner, policy_class_name="StudentTeacher", algorithm_class_name="Distillation",
+                experiment_name="XBot_e2e_distill")
+    teacher_experiment_name = XBotLCfgPPO.runner.experiment_name      # where scripts/distill.py looks for the teacher's checkpoint

@@ -1,0 +1,40 @@
+"""python humanoid-gym_amd/humanoid/scripts/distill.py --task=humanoid_distill --headless [--load_run RUN] [--checkpoint IT]
+
+Distils a trained actor into the student of the task's StudentTeacher policy (Distillation).  The teacher is a PPO
+checkpoint, located with the existing --load_run / --checkpoint through get_load_path on the PPO experiment's log directory
+(the train config's `teacher_experiment_name`, XBot_ppo for humanoid_distill), as rsl_rl does; the run itself trains into the
+distillation experiment's own directory.  --resume continues a distillation run from its own checkpoint instead (make_alg_runner)."""
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+
+from humanoid import LEGGED_GYM_ROOT_DIR  # noqa: E402
+from humanoid.envs import *  # noqa: F401,F403,E402
+from humanoid.utils import get_args, get_load_path, task_registry  # noqa: E402
+
+
+def teacher_path(train_cfg, args, log_root=None):
+    """The teacher's checkpoint: the newest run (or --load_run) and the highest model_<it>.pt (or --checkpoint) of the PPO experiment."""
+    root = log_root if log_root is not None else os.path.join(LEGGED_GYM_ROOT_DIR, "logs", train_cfg.teacher_experiment_name)
+    return get_load_path(root, load_run=args.load_run if args.load_run is not None else -1,
+                         checkpoint=args.checkpoint if args.checkpoint is not None else -1)
+
+
+def distill(args, teacher_log_root=None):
+    env, _ = task_registry.make_env(name=args.task, args=args)
+    train_cfg = task_registry.get_cfgs(args.task)[1]
+    if train_cfg.runner.algorithm_class_name != "Distillation":
+        raise ValueError("task %r does not train with Distillation (algorithm_class_name=%r)" % (args.task, train_cfg.runner.algorithm_class_name))
+    resume = bool(args.resume)
+    path = None if resume else teacher_path(train_cfg, args, teacher_log_root)      # (before the runner is built: a missing teacher costs nothing)
+    runner, train_cfg = task_registry.make_alg_runner(env=env, name=args.task, args=args)
+    if not resume:
+        print(f"Loading teacher from: {path}")
+        runner.load(path)
+    runner.learn(num_learning_iterations=train_cfg.runner.max_iterations, init_at_random_ep_len=True)
+    return runner
+
+
+if __name__ == "__main__":
+    distill(get_args())

@@ -67,7 +67,9 @@ extern "C" {
                              *    (same version, later: HgymPPOConfig.mirror_coef and HgymBatch.pair_idx / mirror_act_src / mirror_act_sign /
                              *    mirror_target / mirror_sums appended -- the mirror loss of left-right symmetry; a zero-filled tail is off)
                              *    (same version, later: hgym_adv_normalize_minibatches -- advantages standardised per minibatch into a second column;
-                             *    no layout changes) */
+                             *    no layout changes)
+                             *    (same version, later: hgym_bc_grad and HgymBCConfig -- one behaviour-cloning minibatch of the actor, rsl_rl's
+                             *    Distillation; no layout changes) */
 
 enum {
     HGYM_OK = 0,
@@ -895,6 +897,31 @@ int32_t hgym_ppo_grad_part(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, c
 /* offset (floats) in the flat parameter / gradient vector of the first parameter of net `which` (0 actor, 1 critic, 2 auxiliary
  * head; which == number of nets: the parameter count); -1 on a bad argument */
 int64_t hgym_net_param_offset(const HgymNetConfig* cfg, int32_t which);
+
+/* ------------------------------------------------------------------------------------------------
+ * Behaviour cloning (header v9, no layout change): one minibatch of rsl_rl's Distillation.update up to and including backward -- the actor
+ * regresses its mean on a stored target, nothing else is trained.  With B rows, A actions and e = mu(obs[idx[b]])_j - target[idx[b]][j]:
+ *   HGYM_BC_MSE:    L = sum e^2 / (B A),  dL/d mu = 2 e / (B A)                                   (torch's mse_loss)
+ *   HGYM_BC_HUBER:  0.5 e^2 where |e| <= delta, else delta (|e| - 0.5 delta), the mean over B A;   (torch's huber_loss)
+ *                   dL/d mu = clamp(e, -delta, delta) / (B A)
+ * The call reads batch->obs, obs_bf16 (optional: the bf16 shadow of obs, as in hgym_ppo_grad), idx, B and num_rows only; every other
+ * member of HgymBatch may be NULL.  target: (num_rows, num_actions) fp32, gathered through idx like obs (16-byte aligned on the fused
+ * path).  sums: two device doubles the caller zeroes, [0] += this minibatch's L, [1] += 1.
+ * After the call (stream order) net->grads holds: the gradient of L in the actor's weights and biases; exactly +0.0 in the std / log_std
+ * slots, the whole critic region, the auxiliary head's region and the KL slot; opt_state[HGYM_OPT_GRAD_SQNORM] the squared norm, as
+ * hgym_ppo_grad leaves it.  No other slot of opt_state is touched: no learning-rate decision, no loss sums, no step count.
+ * The step is hgym_ppo_apply's, with adaptive_lr = 0 and grad_norm_ready = 0: zero gradient on zero moments moves nothing, so the critic
+ * and sigma keep their bits through a whole run of cloning steps.
+ * HGYM_E_BADARG before anything is launched: NULL target or sums, loss_type outside {0, 1}, Huber with a delta that is not finite and
+ * positive, B < 1 or B > max_batch.  HGYM_E_UNSUPPORTED with HgymNet.norm set. */
+#define HGYM_BC_MSE 0
+#define HGYM_BC_HUBER 1
+typedef struct HgymBCConfig {
+    int32_t loss_type;       /* HGYM_BC_MSE / HGYM_BC_HUBER */
+    float huber_delta;       /* > 0, finite (read with HGYM_BC_HUBER only) */
+} HgymBCConfig;
+int32_t hgym_bc_grad(const HgymNetConfig* cfg, const HgymBCConfig* bc, const HgymNet* net, const HgymBatch* batch, const float* target,
+                     double* sums, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Diagnostics of an update (header v9, no layout change): what the update did to the policy, measured on the rows it trained on.
