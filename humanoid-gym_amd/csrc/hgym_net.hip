@@ -816,7 +816,18 @@ struct NetBase {
         else
             hipLaunchKernelGGL((adam_kernel<T>), dim3(256, tab.n), dim3(256), 0, s, tab, ppo, net.params, net.grads, net.adam_m, net.adam_v,
                                inv_w, net.opt_state);
-        prof_end(HGYM_PROF_APPLY, s, (double)w.P * 36.0);
+        {   // HBM bytes the launches above move: adam_body reads and rewrites gradient, both moments and the master weight (32 B per
+            // parameter) and stores every weight's two operand copies (2 sizeof(T) B per weight; biases and std have none -- in log mode
+            // std has its derived sigma, 4 B); sqnorm_prologue_kernel, where it runs, reads the gradient once more (4 B per parameter)
+            double bytes = 32.0 * (double)w.P;
+            for (int i = 0; i < tab.n; ++i) {
+                const double n = (double)tab.s[i].rows * tab.s[i].cols;
+                if (tab.s[i].Wp || tab.s[i].Wf) bytes += 2.0 * sizeof(T) * n;
+                else if (tab.s[i].sigma) bytes += 4.0 * n;
+            }
+            if (ppo.world_size > 1 || !ppo.grad_norm_ready) bytes += 4.0 * (double)w.P;
+            prof_end(HGYM_PROF_APPLY, s, bytes);
+        }
         HG_CHECK_LAUNCH("adam_kernel");
         return net.norm ? norm_fold_bias(&cfg, &net, s) : HGYM_OK;      // the first-layer weights moved: their effective biases follow
     }

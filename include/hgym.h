@@ -1063,9 +1063,23 @@ enum {
 };
 int32_t hgym_prof_enable(int32_t on);  /* 1: start collecting (clears previous events), 0: stop */
 int32_t hgym_prof_summary(int32_t cls, int64_t* launches, double* total_ms, double* work);
-/* Kernel-internal phase clock for tuning the fused MLP kernels: while a caller-owned device buffer of `slots` int64 is
- * set, thread 0 of workgroup b of every fused MLP launch (forward, update, rollout step) writes the 100 MHz wall clock at up to 8 phase
- * boundaries into dev[b*8 + phase] (launches with more than slots/8 workgroups are not instrumented).  NULL: off. */
+/* Kernel-internal phase clock for tuning the fused MLP kernels: while a caller-owned device buffer of `slots` int64 is set, thread 0
+ * of every workgroup of every fused MLP launch (forward, update, rollout step) writes the 100 MHz wall clock at up to 8 phase boundaries
+ * into dev[g*8 + slot], g = blockIdx.y * gridDim.x + blockIdx.x.  A launch asks for G groups and is not instrumented at all unless
+ * 8 G <= slots; slots nobody stamps keep the caller's contents.  NULL: off.  Not capturable in a hipGraph.
+ *   forward (hgym_policy_act, hgym_mlp_forward, each piece of hgym_critic_values): G = tiles x nets in the launch (+ tiles for the
+ *     finaliser's grid row of hgym_policy_act_fin, which stamps nothing); group = tile x of net y; slots 0 start, 1 first input chunk
+ *     staged, 2 first layer's products, 3 its epilogue, 4 layer 1, 5 layer 2, 6 head.  With an activation other than ELU(1) every net
+ *     is a launch of its own: net i writes behind the i * tiles groups of the nets before it.
+ *   update tile (hgym_ppo_grad, hgym_bc_grad): G = ceil(B / 64) x nets (hgym_bc_grad: the actor alone); slots 0-6 as above, 7 end of the dZ
+ *     chain; per-net launches laid out as above.
+ *   hgym_rollout_step: G = 3 x num_envs / 32 whatever the launch's grid rows.  Rows 0 and 1: the column's actor tile (0-6) and its
+ *     non-actor workgroup -- a critic tile (0-6, 7 its end behind its side jobs) or, in the 64-row layout, a side-job workgroup (0 start,
+ *     1 draws done, 2 rows ahead stored, 7 end; 3-6 untouched).  Row 2 is written by OTHER workgroups: group 2 * gridDim.x + x holds
+ *     the env part of column x's actor workgroup (0 its start, 1 history stored, 2 joints, 3 per-env chain and rewards, 4 staged out, 5 end)
+ *     and, where the launch carries the previous finaliser, slot 6 = start of workgroup x of the finaliser's grid row and (x = 0) slot 7 =
+ *     the finaliser's end; the two writers' stamps are ordered within each writer only.
+ *   hgym_rollout_eval_step is never instrumented. */
 int32_t hgym_prof_phase_buffer(void* dev, int64_t slots);
 
 #ifdef __cplusplus

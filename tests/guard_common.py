@@ -225,3 +225,84 @@ def guard_env(buf, arena):
     if buf._l0_partial is None:
         buf._l0_partial = arena.zeros((2, buf.N, 512), torch.float32, name="env._l0_partial")
     return buf
+
+
+# ------------------------------------------------------------------------------------------------ the phase buffer's grids
+# hgym_prof_phase_buffer (include/hgym.h): what every instrumented launch asks of the buffer and who stamps what,
+# restated from the launch sites (csrc/hgym_net.hip, hgym_fwd_act.hip, hgym_fused.hpp, hgym_rollout.hip / .hpp) in plain Python.
+FWD_SLOTS = (0, 1, 2, 3, 4, 5, 6)          # fwd_body: start, first chunk staged, first layer's products, its epilogue, layer 1, layer 2, head
+FB_SLOTS = FWD_SLOTS + (7,)                # fb_body: + the end of the dZ chain
+SIDE_SLOTS = (0, 1, 2, 7)                  # the rollout step's side-job workgroup: start, draws done, rows ahead stored, end
+ENV_SLOTS = (0, 1, 2, 3, 4, 5)             # the rollout step's env part, in grid row 2's groups
+
+
+class PhaseLaunch:
+    """One phase_buffer(groups) request of the library: `groups` groups of 8 slots, and per group that anybody stamps the slot tuples of
+    its writers, each in the writer's program order.  (Several kernel launches may share one request: the per-net launches of the
+    any-activation kernels offset the pointer by the nets before them.)"""
+
+    def __init__(self, groups, stamps):
+        self.groups, self.stamps = int(groups), {int(g): [tuple(w) for w in ws] for g, ws in stamps.items()}
+        assert all(0 <= g < self.groups for g in self.stamps)
+
+    def __eq__(self, other):
+        return (self.groups, self.stamps) == (other.groups, other.stamps)
+
+    def __repr__(self):
+        return "PhaseLaunch(%d, %r)" % (self.groups, self.stamps)
+
+    def slots(self):
+        """Every slot index (group * 8 + slot) that must change."""
+        return sorted(g * 8 + s for g, ws in self.stamps.items() for w in ws for s in w)
+
+
+def rollout_side_column(x):
+    """64-row layout: is grid column x's non-actor workgroup the side-job workgroup of its pair of tiles (else their critic tile)?"""
+    return ((x ^ (x >> 3)) & 1) != 0
+
+
+def phase_groups(entry, shape):
+    """[PhaseLaunch] of one call of `entry` at `shape` (a dict).  Entries and their shape keys:
+      policy_act      M, cus, fin (hgym_policy_act_fin), generic (an activation other than ELU(1))
+      mlp_forward     M, cus                 (which = 0, 1, 2 and every piece of hgym_critic_values: one net)
+      ppo_grad        B, nets (2, or 3 with the fused auxiliary head)      (ELU(1), any activation, either value loss: the same grid)
+      bc_grad         B
+      rollout_step    N, form: "first" (inline, no finaliser), "next" (inline with the finaliser, 32-row layout: <1,0>, <1,1>, <1,1,1>),
+                      "steady64" (<1,1,1,0,1>), "deferred_first", "deferred_next" (values = NULL, either activation form)
+      rollout_eval_step  N                   (never instrumented)"""
+    cdiv = lambda a, b: -(-int(a) // int(b))
+    if entry in ("policy_act", "mlp_forward"):
+        nets = 2 if entry == "policy_act" else 1
+        M = int(shape["M"])
+        bm = 64 if nets * cdiv(M, 32) > int(shape["cus"]) else 32          # forward_nets: 32-row tiles while they fit the chip in one round
+        tiles = cdiv(M, bm)
+        rows = nets + (1 if shape.get("fin") and not shape.get("generic") else 0)      # the finaliser's grid row stamps nothing
+        return [PhaseLaunch(tiles * rows, {g: [FWD_SLOTS] for g in range(tiles * nets)})]
+    if entry in ("ppo_grad", "bc_grad"):
+        nets = int(shape.get("nets", 2)) if entry == "ppo_grad" else 1
+        tiles = cdiv(shape["B"], 64)
+        return [PhaseLaunch(tiles * nets, {g: [FB_SLOTS] for g in range(tiles * nets)})]
+    if entry == "rollout_eval_step":
+        return []
+    if entry == "rollout_step":
+        N, form = int(shape["N"]), shape["form"]
+        assert N % 32 == 0
+        X = N // 32
+        stamps = {}
+        for x in range(X):
+            if form.startswith("deferred"):
+                stamps[x] = [FWD_SLOTS]                                # the actor tile; grid row 1 is the finaliser's (or absent)
+            else:
+                actor_row = x & 1                                      # rows 0 and 1 trade places on odd columns
+                stamps[actor_row * X + x] = [FWD_SLOTS]
+                other = (1 - actor_row) * X + x
+                if form == "steady64":
+                    stamps[other] = [SIDE_SLOTS if rollout_side_column(x) else FB_SLOTS]      # 64-row critic tile: fwd_body's seven + the end
+                else:
+                    stamps[other] = [FB_SLOTS]                         # 32-row critic tile + its side jobs' end
+            row2 = [ENV_SLOTS]                                          # written by the column's actor + env workgroup
+            if form not in ("first", "deferred_first"):
+                row2.append((6, 7) if x == 0 else (6,))               # the finaliser row's workgroup x; workgroup 0 is the finaliser
+            stamps[2 * X + x] = row2
+        return [PhaseLaunch(3 * X, stamps)]
+    raise KeyError(entry)

@@ -159,3 +159,38 @@ def test_net_sizes_come_from_the_library():
         ld = [int(L.lib.hgym_net_shadow_ld(C.byref(cfg), k)) for k in (0, 1)]
         assert ld == ([768, 256] if path == "bf16-fused" else [0, 0])
         assert G.net_arena_bytes(cfg, obs_norm=True) >= ws + lay[L.NORM_BYTES] + 16 * int(L.lib.hgym_net_param_count(C.byref(cfg)))
+
+
+def test_phase_groups_by_hand():
+    """guard_common.phase_groups at two shapes per entry, against grids worked out by hand from the launch sites."""
+    P, F, FB, S, E = G.PhaseLaunch, G.FWD_SLOTS, G.FB_SLOTS, G.SIDE_SLOTS, G.ENV_SLOTS
+    pg = G.phase_groups
+    # hgym_policy_act: M = 33 -> two 32-row tiles per net, grid (2, 2); with the finaliser's row grid (2, 3), whose last row is silent
+    assert pg("policy_act", dict(M=33, cus=256)) == [P(4, {0: [F], 1: [F], 2: [F], 3: [F]})]
+    assert pg("policy_act", dict(M=33, cus=256, fin=True)) == [P(6, {0: [F], 1: [F], 2: [F], 3: [F]})]
+    assert pg("policy_act", dict(M=33, cus=256, fin=True, generic=True)) == [P(4, {0: [F], 1: [F], 2: [F], 3: [F]})]
+    # 256 CUs: 2 * ceil(4097 / 32) = 258 > 256 -> 64-row tiles, ceil(4097 / 64) = 65 per net; 4096 rows still fit in 32-row tiles
+    big = pg("policy_act", dict(M=4097, cus=256))[0]
+    assert big.groups == 130 and sorted(big.stamps) == list(range(130)) and len(big.slots()) == 130 * 7
+    assert pg("policy_act", dict(M=4096, cus=256))[0].groups == 256
+    # hgym_mlp_forward / a piece of hgym_critic_values: one net
+    assert pg("mlp_forward", dict(M=1, cus=256)) == [P(1, {0: [F]})]
+    assert pg("mlp_forward", dict(M=65, cus=256)) == [P(3, {0: [F], 1: [F], 2: [F]})]
+    # the update tile: 64 rows; B = 200 -> 4 tiles, 2 or 3 nets
+    assert pg("ppo_grad", dict(B=1, nets=2)) == [P(2, {0: [FB], 1: [FB]})]
+    assert pg("ppo_grad", dict(B=200, nets=3))[0].groups == 12 and pg("ppo_grad", dict(B=65, nets=2))[0].groups == 4
+    assert pg("bc_grad", dict(B=65)) == [P(2, {0: [FB], 1: [FB]})] and pg("bc_grad", dict(B=200))[0].groups == 4
+    # the rollout step at N = 64: two columns, six groups; column 0 has its actor in row 0, column 1 in row 1
+    assert pg("rollout_step", dict(N=64, form="first")) == [P(6, {0: [F], 3: [F], 2: [FB], 1: [FB], 4: [E], 5: [E]})]
+    assert pg("rollout_step", dict(N=64, form="next")) == [P(6, {0: [F], 3: [F], 2: [FB], 1: [FB], 4: [E, (6, 7)], 5: [E, (6,)]})]
+    assert pg("rollout_step", dict(N=64, form="deferred_first")) == [P(6, {0: [F], 1: [F], 4: [E], 5: [E]})]
+    assert pg("rollout_step", dict(N=64, form="deferred_next")) == [P(6, {0: [F], 1: [F], 4: [E, (6, 7)], 5: [E, (6,)]})]
+    # the 64-row layout at N = 320: ten columns; side jobs at columns 1, 3, 5, 7 and -- swapped -- 8; critic tiles at 0, 2, 4, 6 and 9
+    assert [x for x in range(10) if G.rollout_side_column(x)] == [1, 3, 5, 7, 8]
+    st = pg("rollout_step", dict(N=320, form="steady64"))[0]
+    assert st.groups == 30
+    non_actor = {x: ((1 - (x & 1)) * 10 + x) for x in range(10)}
+    assert [x for x in range(10) if st.stamps[non_actor[x]] == [S]] == [1, 3, 5, 7, 8]
+    assert [x for x in range(10) if st.stamps[non_actor[x]] == [FB]] == [0, 2, 4, 6, 9]
+    assert all(st.stamps[(x & 1) * 10 + x] == [F] for x in range(10)) and st.stamps[20] == [E, (6, 7)] and st.stamps[29] == [E, (6,)]
+    assert pg("rollout_step", dict(N=128, form="steady64"))[0].stamps[4 + 0] == [FB] and pg("rollout_eval_step", dict(N=64)) == []

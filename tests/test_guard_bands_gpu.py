@@ -13,8 +13,8 @@ Detected: every store outside the stated ranges up to BAND (256 KiB) away, and e
 bytes that is masked out afterwards -- at the end of a real allocation it would still be out of bounds; only a sanitizer could see
 it, and none may run on the GPU here.
 
-Out of scope: hgym_comm_* (several processes and peer-mapped memory the caller does not carve), hgym_prof_*, and any search of
-compiled code."""
+Out of scope: hgym_comm_* (several processes and peer-mapped memory the caller does not carve) and any search of compiled code.
+(hgym_prof_*: tests/test_prof_hooks_gpu.py, on this module's helpers.)"""
 import ctypes as C
 
 import numpy as np
@@ -275,8 +275,9 @@ NET_NAMES = ["%s%s" % (p, "-aux" if a else "") for p, a in NET_IDS]
 _NETS, _CASES = {}, {}
 
 
-def _opts(path, aux=False, std="scalar", norm=False, unclipped=False):
-    return U.Options(path, None, std, unclipped, aux, norm, False)
+def _opts(path, aux=False, std="scalar", norm=False, unclipped=False, act=None):
+    """act: None (ELU(1)) or update_options_common.TANH, which the fused kernels run through their any-activation instantiations."""
+    return U.Options(path, act, std, unclipped, aux, norm, False)
 
 
 def _case(opts, B=97):
@@ -286,17 +287,18 @@ def _case(opts, B=97):
     return _CASES[key]
 
 
-def _nets(opts, net=None):
+def _nets(opts, net=None, max_batch=MAX_BATCH):
     """(twin, guarded net, the guarded net's arena) per configuration; the guarded net's buffers have exactly the header's sizes.
-    net: (num_obs, num_priv, num_actions, actor hidden, critic hidden) instead of the path's own shape."""
+    net: (num_obs, num_priv, num_actions, actor hidden, critic hidden) instead of the path's own shape.  max_batch: for the fused rollout
+    at more than 256 envs (a launch is one batch of num_envs rows)."""
     from hgym import NetBuffers, make_net_config, norm_layout
-    key = (opts.path, opts.aux, opts.std, opts.norm, str(net))
+    key = (opts.path, opts.aux, opts.std, opts.norm, str(net), opts.activation is not None, max_batch)
     if key not in _NETS:
         sh = U.SHAPES[opts.path]
         no, npv, A, ah, ch = net or sh["net"]
         kw = dict(aux_hidden=sh["aux"][0], aux_out=sh["aux"][1], aux_target_offset=sh["aux"][2]) if opts.aux else {}
-        cfg = make_net_config(no, npv, A, ah, ch, "f32" if opts.path == "f32-layer" else "bf16", MAX_BATCH,
-                              fused_activation=opts.path == "bf16-fused", noise_std_type=opts.std, **kw)
+        cfg = make_net_config(no, npv, A, ah, ch, "f32" if opts.path == "f32-layer" else "bf16", max_batch,
+                              fused_activation=opts.path == "bf16-fused", noise_std_type=opts.std, activation=opts.activation, **kw)
         on = (U.EPS, None) if opts.norm else None
         twin = NetBuffers(cfg, DEV, learning_rate=LR, obs_norm=on)
         arena = G.Arena(DEV, G.net_arena_bytes(cfg, opts.norm))
@@ -761,89 +763,213 @@ def test_env_split_step_and_heights(N, layout):
     _pair(run, "split step + heights N=%d %s" % (N, layout))
 
 
+def _direct(name, i, call):
+    call()
+
+
+def _rollout_sequence(side, N, T, deferred, opts, case, watch=_direct, info=None, warm=0):
+    """T steps of hgym_rollout_begin / _step / _end as rollout_plan(T, deferred, rows ahead, carried first layer, shadows) lays them out
+    -- with the critic's tiles inline, or in the values = NULL form followed by hgym_critic_values over every slot -- and one
+    hgym_rollout_eval_step.  The storage slots of obs / priv / the shadows and of every per-step column are carved ONE SLOT AT A TIME, with
+    bands between them: a write past row N of slot t cannot hide in slot t + 1.  l0_ahead is exactly (2, N, 512), the scratch exactly
+    HGYM_ROLLOUT_SCRATCH_BYTES(N).  watch(name, i, call) runs every hgym_rollout_step / hgym_rollout_eval_step launch (tests/test_prof_hooks_gpu.py
+    times them and reads the phase buffer in between); info receives the plan and the EnvBuffers.  warm: hgym_env_step_synth steps into slot 0
+    ahead of the rollout -- after hgym_env_prime the frame history is zero, and with it every first-layer sum a launch carries ahead (columns
+    [47, 47 + 32 kb0) of its rows: the frames of 15 steps ago and later); 15 steps fill the stack."""
+    from humanoid.envs.base.legged_robot import rollout_plan
+    no, npv, A = _dims(opts)
+    net, A_, out = side.net, side.A, {}
+    _fresh(net, opts, case)
+    cfg, buf = _make_env(side, N, "soa")
+    ld = net.shadow_ld(0), net.shadow_ld(1)
+    slots = lambda n, shape, dt, **kw: [A_.carve(shape, dt, **kw) for _ in range(n)]
+    c = dict(obs=slots(T + 1, (N, no), F32), priv=slots(T + 1, (N, npv), F32), obs_bf16=slots(T, (N, ld[0]), BF16),
+             priv_bf16=slots(T, (N, ld[1]), BF16), actions=slots(T, (N, A), F32), mu=slots(T, (N, A), F32), sigma=slots(T, (N, A), F32),
+             logp=slots(T, N, F32), values=slots(T, N, F32), rewards=slots(T, N, F32), dones=slots(T, N, U8, skew=1),
+             time_outs=slots(T, N, U8, skew=1))
+    step = A_.place(torch.tensor([0], dtype=I64))
+    sim, st = buf.sim_struct(), buf.state_struct()
+    nz = buf.noise_struct()
+    o0 = buf.out_struct(c["obs"][0], c["priv"][0])
+    L.check(L.lib.hgym_env_prime(C.byref(cfg), C.byref(sim), C.byref(st), C.byref(o0), C.byref(nz), _s()), "hgym_env_prime")
+    side.verify("hgym_env_prime into slot 0")
+    if warm:
+        g, wa = _gen(N + warm), A_.carve((N, A), F32)
+        for t in range(warm):
+            wa.copy_(torch.randn(N, A, generator=g))
+            L.check(L.lib.hgym_env_step_synth(C.byref(cfg), C.byref(sim), C.byref(st), C.byref(o0), L.fptr(wa), _s()), "hgym_env_step_synth")
+        side.verify("%d warm-up steps into slot 0" % warm)
+        assert bool((c["obs"][0][:, :47] != 0).any()), "the oldest frame of slot 0 is still zero"
+    _plant(buf, N)
+    scratch = C.c_void_p(buf.rollout_scratch.data_ptr())
+    plan = rollout_plan(T, deferred, True, True, True)
+    if info is not None:
+        info.update(plan=plan, buf=buf)
+    L.check(L.lib.hgym_rollout_begin(C.byref(st), L.i64ptr(step), scratch, (T - 1) & 1, _s()), "hgym_rollout_begin")
+    side.verify("hgym_rollout_begin")
+    prev = None
+    l0 = lambda k: None if k is None else L.fptr(buf.l0_partial(k))
+    for i, p in enumerate(plan):
+        vals = None if deferred else c["values"][i]
+        sink = dict(values=vals, rewards=c["rewards"][i], dones=c["dones"][i], time_outs=c["time_outs"][i] if deferred else None, step=step,
+                    gamma=0.99)
+        o = buf.out_struct(c["obs"][i + 1], c["priv"][i + 1], sink, True, alt=bool(p.parity))
+        o.obs_older_ready, o.l0_ready, o.l0_ahead = int(p.obs_older_ready), l0(p.l0_ready), l0(p.l0_ahead)
+        if p.ahead is not None:
+            o.obs_ahead, o.priv_ahead = L.fptr(c["obs"][p.ahead]), L.fptr(c["priv"][p.ahead])
+        if p.bf16_ahead:
+            o.obs_bf16_ahead, o.ld_obs_bf16_ahead = C.c_void_p(c["obs_bf16"][i + 1].data_ptr()), ld[0]
+        sh = net.shadow_struct(c["obs_bf16"][i], c["priv_bf16"][i] if p.shadow_priv else None) if p.shadow_obs else None
+        watch("hgym_rollout_step", i, lambda: L.check(L.lib.hgym_rollout_step(
+            C.byref(net.cfg), C.byref(net.struct), C.byref(cfg), C.byref(sim), C.byref(st), C.byref(o), C.byref(prev) if p.prev else None,
+            L.fptr(c["obs"][i]), L.fptr(c["priv"][i]), 99, L.fptr(c["actions"][i]), L.fptr(c["mu"][i]), L.fptr(c["sigma"][i]),
+            L.fptr(c["logp"][i]), L.fptr(vals), scratch, p.parity, None if sh is None else C.byref(sh), _s()), "hgym_rollout_step"))
+        side.verify("hgym_rollout_step %d" % i)
+        prev = o
+    L.check(L.lib.hgym_rollout_end(C.byref(cfg), C.byref(st), C.byref(prev), scratch, plan[-1].parity, _s()), "hgym_rollout_end")
+    side.verify("hgym_rollout_end")
+    assert int(step) == T and int(buf.counters[L.CNT_STEP]) == 397 + T
+    assert sum(int(d.sum()) for d in c["dones"]) > 0, "the planted time-outs did not happen"
+    if deferred:        # nobody has written these yet: the critic runs once over the stored rows, slot by slot here
+        assert all(_all_ff(t) for t in c["values"] + c["priv_bf16"])
+        for i in range(T):
+            sh = net.shadow_struct(None, c["priv_bf16"][i])
+            L.check(L.lib.hgym_critic_values(C.byref(net.cfg), C.byref(net.struct), N, L.fptr(c["priv"][i]), L.fptr(c["values"][i]), C.byref(sh),
+                                             _s()), "hgym_critic_values")
+            side.verify("hgym_critic_values slot %d" % i)
+    else:
+        assert all(_all_ff(t) for t in c["time_outs"])
+        c.pop("time_outs")
+    for k, v in c.items():
+        for i, t in enumerate(v):
+            out["%s[%d]" % (k, i)] = t
+    _env_state(buf, out, "rollout.")
+    if buf._l0_partial is not None and any(p.l0_ahead is not None for p in plan):
+        out["l0_partial"] = buf._l0_partial
+    # the evaluation launch: mu of slot T's rows, the env step on it, observations into two fresh rows
+    eo, ep, act = A_.carve((N, no), F32), A_.carve((N, npv), F32), A_.carve((N, A), F32)
+    L.check(L.lib.hgym_rollout_begin(C.byref(st), L.i64ptr(step), scratch, 0, _s()), "hgym_rollout_begin")
+    o = buf.out_struct(eo, ep, None, True, alt=False)
+    o.log_cur, o.log_stats = None, None
+    watch("hgym_rollout_eval_step", 0, lambda: L.check(L.lib.hgym_rollout_eval_step(
+        C.byref(net.cfg), C.byref(net.struct), C.byref(cfg), C.byref(sim), C.byref(st), C.byref(o), None, L.fptr(c["obs"][T]), L.fptr(act),
+        scratch, 0, _s()), "hgym_rollout_eval_step"))
+    side.verify("hgym_rollout_eval_step")
+    L.check(L.lib.hgym_rollout_end(C.byref(cfg), C.byref(st), C.byref(o), scratch, 0, _s()), "hgym_rollout_end")
+    side.verify("hgym_rollout_end after the evaluation launch")
+    out.update(eval_obs=eo, eval_priv=ep, eval_actions=act)
+    _env_state(buf, out, "eval.")
+    return out
+
+
+def rollout_arena_bytes(N, T, opts):
+    """arena_bytes of what _rollout_sequence carves from the side's allocator (the env's own buffers have an arena of their own)."""
+    no, npv, A = _dims(opts)
+    ld = [_nets(opts)[0].shadow_ld(k) for k in (0, 1)]
+    per_slot = [4 * N * no, 4 * N * npv]
+    per_step = [2 * N * ld[0], 2 * N * ld[1]] + [4 * N * A] * 3 + [4 * N] * 3 + [N] * 2
+    return G.arena_bytes(*(per_slot * (T + 1) + per_step * T + [8] + [4 * N * no, 4 * N * npv, 4 * N * A] + [4 * N * A]))
+
+
 @pytest.mark.parametrize("deferred", [False, True], ids=["inline", "deferred"])
 def test_fused_rollout_launches(deferred):
     """Three steps of hgym_rollout_begin / _step / _end -- with the critic's tiles inline, and in the values = NULL form followed by
-    hgym_critic_values over every slot -- and one hgym_rollout_eval_step at N = 64 (the
-    launch takes whole 32-env tiles only: at the sizes of the other env cases the runner's rollout_fused_mode is None).  The storage
-    slots of obs / priv / the shadows and of every per-step column are carved ONE SLOT AT A TIME, with bands between them: a write past
-    row N of slot t cannot hide in slot t + 1.  l0_ahead is exactly (2, N, 512), the scratch exactly HGYM_ROLLOUT_SCRATCH_BYTES(N)."""
-    from humanoid.envs.base.legged_robot import rollout_plan
+    hgym_critic_values over every slot -- and one hgym_rollout_eval_step at N = 64 (the launch takes whole 32-env tiles only: at the sizes
+    of the other env cases the runner's rollout_fused_mode is None).  _rollout_sequence says what is carved how.  At N = 64 every launch
+    takes the 32-row layout (rollout_critic64 in csrc/hgym_rollout.hip asks for at least four tiles):
+    rollout_step_kernel<0,0>, <1,1,1> twice (inline); <0,0,0,1>, <1,0,0,1> twice (deferred); <1,0,0,1,0,1> (evaluation)."""
     N, T = 64, 3
     opts = _opts("bf16-fused")
     case = _case(opts)
-    nets = _nets(opts)
-    no, npv, A = _dims(opts)
+    _pair(lambda side: _rollout_sequence(side, N, T, deferred, opts, case), "fused rollout N=%d %s" % (N, "deferred" if deferred else "inline"),
+          nbytes=96 << 20, nets=_nets(opts))
+
+
+# (N, HGYM_L0_KB0): the forms of the production launch (csrc/hgym_rollout.hip).  T = 4: launches 1, 2, 3 are the steady-state launch
+# (l0_ready set), with both l0 parities, launches 1 and 2 with rows ahead and launch 3 without.
+#   96   3 tiles, an odd count: the 32-row layout, whose critic tiles carry the side jobs; rollout_step_kernel<1,1,1> on a (3, 3) grid
+#   128  the smallest N with the 64-row layout (4 tiles): rollout_step_kernel<1,1,1,0,1>
+#   320  10 grid columns: columns 8 and 9 are the first whose critic / side-job roles are swapped ((x ^ (x >> 3)) & 1)
+#   128 with HGYM_L0_KB0=4: the smallest carried-first-layer split; the side jobs' staging buffer is sized by it
+ROLLOUT_FORMS = [(96, None), (128, None), (320, None), (128, "4")]
+WARM = 15      # env steps ahead of these rollouts: a full frame stack, so that the sums carried ahead are not sums of zeros
+ROLLOUT_FORM_IDS = ["N%d%s" % (n, "-kb0_%s" % k if k else "") for n, k in ROLLOUT_FORMS]
+
+
+def _assert_form(N, info, c64):
+    plan, buf = info["plan"], info["buf"]
+    ready = [p for p in plan if p.l0_ready is not None]
+    assert len(ready) >= 2 and {p.l0_ready for p in ready} == {0, 1}, "the steady-state launch did not run with both l0 parities"
+    assert any(p.ahead is not None for p in ready) and any(p.ahead is None for p in ready)
+    tiles = N // 32
+    assert N % 32 == 0 and ((tiles % 2 == 0 and tiles >= 4) == c64), (N, c64)
+    for k in (0, 1):
+        assert bool((buf.l0_partial(k) != 0).any()), "l0_partial(%d) was never written: the carried first layer did not run" % k
+
+
+def _set_rollout_env(monkeypatch, kb0, critic64=None):
+    for name, v in (("HGYM_L0_KB0", kb0), ("HGYM_RO_CRITIC64", critic64)):
+        if v is None:
+            monkeypatch.delenv(name, raising=False)
+        else:
+            monkeypatch.setenv(name, v)
+
+
+_ROLLOUT_GUARDED = {}
+
+
+@pytest.mark.parametrize("N,kb0", ROLLOUT_FORMS, ids=ROLLOUT_FORM_IDS)
+def test_fused_rollout_forms(monkeypatch, N, kb0):
+    """The inline rollout of test_fused_rollout_launches, T = 4, at the env counts at which the launch changes form (ROLLOUT_FORMS)."""
+    T = 4
+    _set_rollout_env(monkeypatch, kb0)
+    opts = _opts("bf16-fused")
+    case = _case(opts)
+    infos = []
 
     def run(side):
-        net, A_, out = side.net, side.A, {}
-        _fresh(net, opts, case)
-        cfg, buf = _make_env(side, N, "soa")
-        ld = net.shadow_ld(0), net.shadow_ld(1)
-        slots = lambda n, shape, dt, **kw: [A_.carve(shape, dt, **kw) for _ in range(n)]
-        c = dict(obs=slots(T + 1, (N, no), F32), priv=slots(T + 1, (N, npv), F32), obs_bf16=slots(T, (N, ld[0]), BF16),
-                 priv_bf16=slots(T, (N, ld[1]), BF16), actions=slots(T, (N, A), F32), mu=slots(T, (N, A), F32), sigma=slots(T, (N, A), F32),
-                 logp=slots(T, N, F32), values=slots(T, N, F32), rewards=slots(T, N, F32), dones=slots(T, N, U8, skew=1),
-                 time_outs=slots(T, N, U8, skew=1))
-        step = A_.place(torch.tensor([0], dtype=I64))
-        sim, st = buf.sim_struct(), buf.state_struct()
-        nz = buf.noise_struct()
-        o0 = buf.out_struct(c["obs"][0], c["priv"][0])
-        L.check(L.lib.hgym_env_prime(C.byref(cfg), C.byref(sim), C.byref(st), C.byref(o0), C.byref(nz), _s()), "hgym_env_prime")
-        side.verify("hgym_env_prime into slot 0")
-        _plant(buf, N)
-        scratch = C.c_void_p(buf.rollout_scratch.data_ptr())
-        plan = rollout_plan(T, deferred, True, True, True)
-        L.check(L.lib.hgym_rollout_begin(C.byref(st), L.i64ptr(step), scratch, (T - 1) & 1, _s()), "hgym_rollout_begin")
-        side.verify("hgym_rollout_begin")
-        prev = None
-        l0 = lambda k: None if k is None else L.fptr(buf.l0_partial(k))
-        for i, p in enumerate(plan):
-            vals = None if deferred else c["values"][i]
-            sink = dict(values=vals, rewards=c["rewards"][i], dones=c["dones"][i], time_outs=c["time_outs"][i] if deferred else None, step=step,
-                        gamma=0.99)
-            o = buf.out_struct(c["obs"][i + 1], c["priv"][i + 1], sink, True, alt=bool(p.parity))
-            o.obs_older_ready, o.l0_ready, o.l0_ahead = int(p.obs_older_ready), l0(p.l0_ready), l0(p.l0_ahead)
-            if p.ahead is not None:
-                o.obs_ahead, o.priv_ahead = L.fptr(c["obs"][p.ahead]), L.fptr(c["priv"][p.ahead])
-            if p.bf16_ahead:
-                o.obs_bf16_ahead, o.ld_obs_bf16_ahead = C.c_void_p(c["obs_bf16"][i + 1].data_ptr()), ld[0]
-            sh = net.shadow_struct(c["obs_bf16"][i], c["priv_bf16"][i] if p.shadow_priv else None) if p.shadow_obs else None
-            L.check(L.lib.hgym_rollout_step(C.byref(net.cfg), C.byref(net.struct), C.byref(cfg), C.byref(sim), C.byref(st), C.byref(o),
-                                            C.byref(prev) if p.prev else None, L.fptr(c["obs"][i]), L.fptr(c["priv"][i]), 99,
-                                            L.fptr(c["actions"][i]), L.fptr(c["mu"][i]), L.fptr(c["sigma"][i]), L.fptr(c["logp"][i]),
-                                            L.fptr(vals), scratch, p.parity, None if sh is None else C.byref(sh), _s()), "hgym_rollout_step")
-            side.verify("hgym_rollout_step %d" % i)
-            prev = o
-        L.check(L.lib.hgym_rollout_end(C.byref(cfg), C.byref(st), C.byref(prev), scratch, plan[-1].parity, _s()), "hgym_rollout_end")
-        side.verify("hgym_rollout_end")
-        assert int(step) == T and int(buf.counters[L.CNT_STEP]) == 400
-        assert sum(int(d.sum()) for d in c["dones"]) > 0, "the planted time-outs did not happen"
-        if deferred:        # nobody has written these yet: the critic runs once over the stored rows, slot by slot here
-            assert all(_all_ff(t) for t in c["values"] + c["priv_bf16"])
-            for i in range(T):
-                sh = net.shadow_struct(None, c["priv_bf16"][i])
-                L.check(L.lib.hgym_critic_values(C.byref(net.cfg), C.byref(net.struct), N, L.fptr(c["priv"][i]), L.fptr(c["values"][i]), C.byref(sh),
-                                                 _s()), "hgym_critic_values")
-                side.verify("hgym_critic_values slot %d" % i)
-        else:
-            assert all(_all_ff(t) for t in c["time_outs"])
-            c.pop("time_outs")
-        for k, v in c.items():
-            for i, t in enumerate(v):
-                out["%s[%d]" % (k, i)] = t
-        _env_state(buf, out, "rollout.")
-        # the evaluation launch: mu of slot T's rows, the env step on it, observations into two fresh rows
-        eo, ep, act = A_.carve((N, no), F32), A_.carve((N, npv), F32), A_.carve((N, A), F32)
-        L.check(L.lib.hgym_rollout_begin(C.byref(st), L.i64ptr(step), scratch, 0, _s()), "hgym_rollout_begin")
-        o = buf.out_struct(eo, ep, None, True, alt=False)
-        o.log_cur, o.log_stats = None, None
-        L.check(L.lib.hgym_rollout_eval_step(C.byref(net.cfg), C.byref(net.struct), C.byref(cfg), C.byref(sim), C.byref(st), C.byref(o), None,
-                                             L.fptr(c["obs"][T]), L.fptr(act), scratch, 0, _s()), "hgym_rollout_eval_step")
-        side.verify("hgym_rollout_eval_step")
-        L.check(L.lib.hgym_rollout_end(C.byref(cfg), C.byref(st), C.byref(o), scratch, 0, _s()), "hgym_rollout_end")
-        side.verify("hgym_rollout_end after the evaluation launch")
-        out.update(eval_obs=eo, eval_priv=ep, eval_actions=act)
-        _env_state(buf, out, "eval.")
+        infos.append({})
+        out = _rollout_sequence(side, N, T, False, opts, case, info=infos[-1], warm=WARM)
+        _assert_form(N, infos[-1], c64=N in (128, 320))
+        _ROLLOUT_GUARDED[(N, kb0)] = {k: v.clone() for k, v in out.items()}
         return out
-    _pair(run, "fused rollout N=%d %s" % (N, "deferred" if deferred else "inline"), nbytes=96 << 20, nets=nets)
+    _pair(run, "fused rollout N=%d T=%d inline, HGYM_L0_KB0=%s" % (N, T, kb0), nbytes=rollout_arena_bytes(N, T, opts),
+          nets=_nets(opts, max_batch=max(N, MAX_BATCH)))
+
+
+@pytest.mark.parametrize("N", [128, 320])
+def test_fused_rollout_32_row_layout_between_bands(monkeypatch, N):
+    """HGYM_RO_CRITIC64=0 at the env counts where the 64-row layout is the default: the 32-row layout (rollout_step_kernel<1,1,1> on 4 and
+    10 columns) stays inside the bands too, and every output has the bits of the DEFAULT layout's guarded run -- but for the carried partial
+    sums themselves (12 of the 24 k-steps instead of 20) and the fp32-atomic means, as tests/test_rollout_layout_gpu.py excludes them."""
+    T = 4
+    opts = _opts("bf16-fused")
+    case = _case(opts)
+    nets = _nets(opts, max_batch=max(N, MAX_BATCH))
+    if (N, None) not in _ROLLOUT_GUARDED:      # (run alone: the default layout's guarded run first)
+        _set_rollout_env(monkeypatch, None)
+        arena = G.Arena(DEV, rollout_arena_bytes(N, T, opts))
+        side = Side("default layout N=%d" % N, arena, nets[1], (arena, nets[2]))
+        _ROLLOUT_GUARDED[(N, None)] = {k: v.clone() for k, v in _rollout_sequence(side, N, T, False, opts, case, warm=WARM).items()}
+        side.verify("end of the case")
+    _set_rollout_env(monkeypatch, None, "0")
+    info = {}
+    arena = G.Arena(DEV, rollout_arena_bytes(N, T, opts))
+    side = Side("fused rollout N=%d, 32-row layout" % N, arena, nets[1], (arena, nets[2]))
+    got = _rollout_sequence(side, N, T, False, opts, case, info=info, warm=WARM)
+    side.verify("end of the case")
+    assert sum(p.l0_ready is not None for p in info["plan"]) >= 2 and bool((info["buf"].l0_partial(0) != 0).any())
+    ref = dict(_ROLLOUT_GUARDED[(N, None)])
+    ref.pop("l0_partial"), got.pop("l0_partial")
+    _compare(ref, got, side.what)
+
+
+def test_fused_rollout_any_activation():
+    """A Tanh net (fused_activation): rollout_step_act_kernel (csrc/hgym_rollout_act.hip) in its three modes -- <0> first launch, <1> with the
+    previous finaliser, <1, EVAL> -- at N = 64, T = 3, values deferred, then hgym_critic_values per slot (mlp_fwd_act_kernel).  The any-activation
+    fused step exists without critic tiles only, so there is no inline case."""
+    N, T = 64, 3
+    opts = _opts("bf16-fused", act=U.TANH)
+    case = _case(opts)
+    _pair(lambda side: _rollout_sequence(side, N, T, True, opts, case), "fused rollout N=%d deferred, Tanh" % N,
+          nbytes=rollout_arena_bytes(N, T, opts), nets=_nets(opts))
