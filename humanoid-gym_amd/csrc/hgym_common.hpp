@@ -44,6 +44,10 @@ int device_cus();                           // compute units of the CURRENT devi
 // Returns HGYM_OK or HGYM_E_LAUNCH (message in hgym_last_error).
 int32_t ensure_dynamic_lds(const void* fn, size_t bytes, const char* what);
 
+// n floats at x to +0.0 by ONE LAUNCH on `stream` (hgym_fill.hip): for clears that must replay inside a captured graph, where a memset node is
+// not to be relied on.  HGYM_OK, HGYM_E_BADARG (null x, n < 1) or HGYM_E_LAUNCH.
+int32_t zero_f32_async(float* x, int64_t n, hipStream_t stream);
+
 static inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 static inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
 

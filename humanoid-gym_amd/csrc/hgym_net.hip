@@ -845,9 +845,7 @@ struct NetBase {
     // cloning step does not train (std, critic, auxiliary head) must leave Adam with nothing to apply.  bc_reduce_actor: reduce_range over
     // the actor's segments alone (and, through them, the squared norm: every other entry is zero).
     int32_t bc_zero_grads() {
-        const hipError_t e = hipMemsetAsync(net.grads, 0, (size_t)(w.P + 1) * sizeof(float), s);
-        HG_REQUIRE(e == hipSuccess, HGYM_E_LAUNCH, "hipMemsetAsync(grads): %s", hipGetErrorString(e));
-        return HGYM_OK;
+        return zero_f32_async(net.grads, w.P + 1, s);      // a launch, not a memset node: the step also runs inside captured updates (hgym_fill.hip)
     }
     int32_t bc_reduce_actor(int Mp) { return reduce_range(w.net[0].layer[0].w_off, w.net[1].layer[0].w_off, Mp); }
 

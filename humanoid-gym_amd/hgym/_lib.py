@@ -171,9 +171,19 @@ class ObsShadow(C.Structure):
     _fields_ = [("obs", C.c_void_p), ("ld_obs", C.c_int64), ("priv", C.c_void_p), ("ld_priv", C.c_int64)]
 
 
+RND_MAX_OUTPUTS = 64     # HGYM_RND_MAX_OUTPUTS
+RND_CONSTANT, RND_STEP, RND_LINEAR = 0, 1, 2    # HGYM_RND_*: HgymRndConfig.schedule
+
+
+class RndConfig(C.Structure):
+    """HgymRndConfig: the discount, the weight schedule and the normalisation switch of hgym_rnd_rewards."""
+    _fields_ = [("gamma", C.c_double), ("weight", C.c_double), ("final_value", C.c_double), ("initial_step", C.c_int64),
+                ("final_step", C.c_int64), ("schedule", C.c_int32), ("normalize", C.c_int32)]
+
+
 STRUCTS = dict(HgymEnvConfig=EnvConfig, HgymStrided=Strided, HgymSimTensors=SimTensors, HgymEnvState=EnvState,
                HgymEnvOut=EnvOut, HgymEnvNoise=EnvNoise, HgymNetConfig=NetConfig, HgymPPOConfig=PPOConfig,
-               HgymNet=Net, HgymBatch=Batch, HgymObsShadow=ObsShadow, HgymComm=Comm, HgymBCConfig=BCConfig)
+               HgymNet=Net, HgymBatch=Batch, HgymObsShadow=ObsShadow, HgymComm=Comm, HgymBCConfig=BCConfig, HgymRndConfig=RndConfig)
 
 # every symbol include/hgym.h declares: name -> (restype, argtypes)
 _P = C.POINTER
@@ -211,6 +221,9 @@ SYMBOLS = {
                              c_float_p, c_float_p, c_f64_p, C.c_void_p]),
     "hgym_adv_normalize": (C.c_int32, [C.c_int64, c_float_p, c_f64_p, C.c_void_p]),
     "hgym_adv_normalize_minibatches": (C.c_int32, [C.c_int32, C.c_int64, c_i64_p, c_float_p, c_float_p, C.c_int64, c_f64_p, C.c_void_p]),
+    "hgym_rnd_block_init": (C.c_int32, [C.c_int32, c_f64_p, C.c_void_p]),
+    "hgym_rnd_rewards": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, _P(RndConfig), c_f64_p,
+                                     C.c_void_p]),
     "hgym_gae_bootstrap": (C.c_int32, [C.c_int32, C.c_int32, c_float_p, c_float_p, c_u8_p, c_u8_p, c_float_p, C.c_float, C.c_float,
                                        c_float_p, c_float_p, c_f64_p, C.c_void_p]),
     "hgym_mirror_rows": (C.c_int32, [C.c_int64, C.c_int32, C.POINTER(C.c_int32), c_float_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32,
@@ -389,3 +402,25 @@ def diag_block(total_rows, device):
     """The block of hgym_ppo_diag_reset / hgym_ppo_diag_reduce / hgym_ppo_diagnostics for total_rows rows, zero-filled."""
     import torch
     return torch.zeros(diag_block_doubles(total_rows), dtype=torch.float64, device=device)
+
+
+# the RND reward pass's block (include/hgym.h: HGYM_RND_*)
+RND_HEADER, RND_ROWS_PER_WG, RND_ENVS_PER_PARTIAL, RND_APPLY_WGS = 16, 64, 64, 1024
+(RND_MEAN, RND_VAR, RND_COUNT, RND_COUNTER, RND_SUM_INTRINSIC, RND_SUM_REWARDS, RND_WEIGHT_LAST, RND_STD, RND_ROWS, RND_TICKET_SCAN,
+ RND_TICKET_APPLY) = range(11)
+
+
+def rnd_block_doubles(n):
+    """HGYM_RND_BLOCK_DOUBLES(n) of include/hgym.h."""
+    n = int(n)
+    return RND_HEADER + n + 2 * ((n + RND_ENVS_PER_PARTIAL - 1) // RND_ENVS_PER_PARTIAL) + 2 * RND_APPLY_WGS
+
+
+def rnd_block(n, device):
+    """The state block of hgym_rnd_rewards for n envs on a GPU, written by hgym_rnd_block_init on that device's current stream."""
+    import torch
+    b = torch.empty(rnd_block_doubles(n), dtype=torch.float64, device=device)
+    assert b.is_cuda, "the block lives on the device (hgym_rnd_block_init writes it)"
+    with torch.cuda.device(b.device):
+        check(lib.hgym_rnd_block_init(int(n), f64ptr(b), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "hgym_rnd_block_init")
+    return b

@@ -60,6 +60,9 @@ class Distillation(PPO):
                              % (int(num_transitions_per_env), int(gradient_length)))
 
     def init_storage(self, num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape):
+        if self.rnd is not None:
+            from . import rnd as rnd_module
+            rnd_module.check_setup(distillation=True)
         self.check_setup(self.actor_critic, num_transitions_per_env, self.gradient_length, self._world, self.symmetry,
                          self.mirror_loss_coef, self.advantage_normalization)
         # one "minibatch" is one slice: gradient_length * N rows (PPO.init_storage sizes the net's max_batch from it)

@@ -209,12 +209,14 @@ def _split_algorithm_cfg(alg_cfg):
     off), not a parameter of the reference's PPO: it is taken out here and becomes PPO.symmetry.  The mirror loss's keys (SYMMETRY_KEYS)
     are taken out as well; _split_symmetry_cfg reads them.  So are the advantage normalisation's (ADVANTAGE_KEYS; _split_advantage_cfg)."""
     kwargs = dict(alg_cfg)
-    for k in SYMMETRY_KEYS + ADVANTAGE_KEYS:
+    for k in SYMMETRY_KEYS + ADVANTAGE_KEYS + (RND_KEY,):
         kwargs.pop(k, None)
     return kwargs, bool(kwargs.pop("symmetry", False))
 
 
 ADVANTAGE_KEYS = ("advantage_normalization", "normalize_advantage_per_mini_batch")      # neither is a parameter of PPO.__init__
+RND_KEY = "rnd_cfg"      # rsl_rl's Random Network Distillation block (humanoid.algo.ppo.rnd.parse_config); absent or None: off
+RND_STATE_KEY = "rnd_state_dict"      # what a checkpoint of a run with rnd_cfg carries besides the reference's four keys
 
 
 def _split_advantage_cfg(alg_cfg):
@@ -316,6 +318,12 @@ class OnPolicyRunner:
             self.alg.mirror_loss_coef = mirror_loss_coef
         if any(self.alg_cfg.get(k) is not None for k in ADVANTAGE_KEYS):      # read by init_storage below
             self.alg.advantage_normalization = _split_advantage_cfg(self.alg_cfg)
+        if self.alg_cfg.get(RND_KEY) is not None:      # Random Network Distillation; read by init_storage below
+            from .rnd import RandomNetworkDistillation
+            env_cfg = getattr(getattr(self.env, "cfg", None), "env", None)
+            self.alg.rnd = RandomNetworkDistillation(self.env.num_obs, num_critic_obs, self.alg_cfg[RND_KEY],
+                                                     critic_frame=getattr(env_cfg, "single_num_privileged_obs", None),
+                                                     activation=getattr(actor_critic, "activation", None))
         self.num_steps_per_env = self.cfg["num_steps_per_env"]
         self.save_interval = self.cfg["save_interval"]
         self.alg.init_storage(self.env.num_envs, self.num_steps_per_env, [self.env.num_obs], [self.env.num_privileged_obs],
@@ -395,7 +403,7 @@ class OnPolicyRunner:
                 diag_now = diag_every > 0 and (it + 1) % diag_every == 0
                 if diag_now:
                     alg.diagnostics_prepare()       # slot 0's observation rows, before the update's clear() rotates them away
-                mean_value_loss, mean_surrogate_loss = self._learn_step(plan, gkey, ukey, critic_obs)
+                mean_value_loss, mean_surrogate_loss = self._learn_step(plan, gkey, ukey, critic_obs, obs)
                 diag = alg.diagnostics(sync=False) if diag_now else None       # enqueued; read where this path reads anything
                 if plan.zero_copy:                  # storage.clear() rotated slot T into slot 0
                     obs, critic_obs = obs_all[0], priv_all[0]
@@ -589,11 +597,14 @@ class OnPolicyRunner:
             env.run_finalize(fin)           # the last step has no following policy launch
         return obs, critic_obs
 
-    def _learn_step(self, plan, gkey, ukey, critic_obs):
+    def _learn_step(self, plan, gkey, ukey, critic_obs, obs=None):
         """compute_returns() + update() -> (mean_value_loss, mean_surrogate_loss), None where not read back (PPO.update_capturable)."""
         def launches(sync=False):
             with torch.inference_mode():
-                self.alg.compute_returns(critic_obs)
+                if getattr(self.alg, "_rnd", None) is not None:      # (RND reads the state behind the last transition)
+                    self.alg.compute_returns(critic_obs, last_obs=obs)
+                else:
+                    self.alg.compute_returns(critic_obs)
             return self.alg.update(sync=sync)
 
         return self._update_capture.run(plan.graph_update and self._rollout_capture.valid(gkey), ukey, lambda: launches(not plan.async_mode),
@@ -707,6 +718,8 @@ class OnPolicyRunner:
         o = hgym.opt_summary(pin["opt"][slot], snap["aux"])
         self.alg.last_denoise_loss = o["denoise_loss"]
         self.alg.last_mirror_loss = self.alg.mirror_loss_from(pin["opt"][slot])
+        if hasattr(self.alg, "rnd_log_from"):      # RND: the predictor's loss and the reward pass's sums ride at the block's end
+            self.alg.rnd_log_from(pin["opt"][slot])
         if hasattr(self.alg, "behavior_loss_from"):      # Distillation: the loss rides in the same block
             self.alg.last_behavior_loss = self.alg.behavior_loss_from(pin["opt"][slot])
         ep, returns, lengths = hgym.log_stats_summary(pin["ls"][slot], self.env.reward_names, KERNEL_REWARD_TERMS)
@@ -747,6 +760,10 @@ class OnPolicyRunner:
             scal("Loss/mirror", self.alg.last_mirror_loss, locs["it"])
         if behavior is not None:
             scal("Loss/behavior", behavior, locs["it"])
+        rnd_log = getattr(getattr(self.alg, "_rnd", None), "last_log", None)
+        if rnd_log is not None:      # Loss/rnd, Rnd/intrinsic_reward, Rnd/extrinsic_reward, Rnd/weight, Rnd/std
+            for key, value in rnd_log.items():
+                scal(key, value, locs["it"])
         scal("Policy/mean_noise_std", mean_std, locs["it"])
         scal("Perf/total_fps", fps, locs["it"])
         scal("Perf/collection time", locs["collection_time"], locs["it"])
@@ -765,6 +782,9 @@ class OnPolicyRunner:
                f"""{'Mean action noise std:':>{pad}} {mean_std:.2f}\n""")
         if behavior is not None:
             out += f"""{'Behavior loss:':>{pad}} {behavior:.6f}\n"""
+        if rnd_log is not None:
+            out += (f"""{'RND predictor loss:':>{pad}} {rnd_log['Loss/rnd']:.6f}\n"""
+                    f"""{'Mean intrinsic reward:':>{pad}} {rnd_log['Rnd/intrinsic_reward']:.6f} (weight {rnd_log['Rnd/weight']:.4g})\n""")
         if have_eps:
             out += (f"""{'Mean reward:':>{pad}} {statistics.mean(locs['rewbuffer']):.2f}\n"""
                     f"""{'Mean episode length:':>{pad}} {statistics.mean(locs['lenbuffer']):.2f}\n""")
@@ -830,7 +850,9 @@ class OnPolicyRunner:
         if (net is None or not str(self.device).startswith("cuda") or os.environ.get("HGYM_ASYNC_SAVE", "1") == "0"
                 or not hasattr(self.alg.actor_critic, "_net")
                 # a StudentTeacher's teacher.* entries live in a second flat vector: the blocking form, which cuts nothing by offset
-                or getattr(self.alg.actor_critic, "_teacher_net", None) is not None):
+                or getattr(self.alg.actor_critic, "_teacher_net", None) is not None
+                # RND's two nets, the predictor's optimiser and the reward pass's block live in buffers of their own: the blocking form as well
+                or getattr(self.alg, "_rnd", None) is not None):
             if env_state:
                 side = dict(env={k: (v.cpu() if torch.is_tensor(v) else v) for k, v in self.env.state_dict().items()},
                             **self._env_state_extra(iterations_done))
@@ -838,6 +860,8 @@ class OnPolicyRunner:
                 torch.save(side, side_path + ".tmp%d" % os.getpid())
                 os.replace(side_path + ".tmp%d" % os.getpid(), side_path)
             norm = self.alg.actor_critic.norm_state_dicts() if hasattr(self.alg.actor_critic, "norm_state_dicts") else {}
+            if getattr(self.alg, "_rnd", None) is not None:
+                norm = dict(norm, **{RND_STATE_KEY: self.alg._rnd.rnd_state_dict()})
             torch.save({"model_state_dict": self.alg.actor_critic.state_dict(),
                         "optimizer_state_dict": self.alg.optimizer.state_dict(),
                         "iter": self.current_learning_iteration, "infos": infos, **norm}, path)
@@ -991,6 +1015,12 @@ class OnPolicyRunner:
         # observations under the same parameter names
         has_norm = bool(getattr(self.alg.actor_critic, "empirical_normalization", False))
         _check_norm_keys(loaded, has_norm, os.path.basename(str(path)), getattr(self.alg.actor_critic, "obs_norm_spec", None))
+        # a checkpoint of a run with RND for a run without it, or the reverse, or the per-env average of another number of envs: refused by name
+        rnd = getattr(self.alg, "_rnd", None)
+        from .rnd import check_state_dict as _check_rnd_state
+        _check_rnd_state(loaded.get(RND_STATE_KEY), os.path.basename(str(path)), rnd is not None, getattr(rnd, "num_envs", None))
+        if rnd is not None:
+            rnd.load_rnd_state_dict(loaded[RND_STATE_KEY])
         if has_norm:        # the statistics first, then the parameters (whose load refolds the first layers with them)
             self.alg.net.load_norm_state(dict(obs=loaded[NORM_KEYS[0]], critic_obs=loaded[NORM_KEYS[1]]))
         self.alg.actor_critic.load_state_dict(loaded["model_state_dict"])

@@ -88,6 +88,11 @@ class PPO:
     # augments).  Read once, in init_storage.  DESIGN.md section 24.
     advantage_normalization = "batch"
     ADVANTAGE_NORMALIZATIONS = ("batch", "minibatch", "none")
+    # Random Network Distillation (rsl_rl's rnd_cfg): None, or a humanoid.algo.ppo.rnd.RandomNetworkDistillation -- compute_returns then
+    # adds an intrinsic exploration reward to the stored rewards ahead of GAE (one pass over the stored rows behind the rollout:
+    # hgym_rnd_rewards), and update() follows every minibatch's Adam step with one step of the predictor on the same rows.  One rank, no
+    # symmetry augmentation, not with Distillation (ValueError from init_storage).  Read once, in init_storage.  DESIGN.md section 27.
+    rnd = None
 
     def __init__(self, actor_critic, num_learning_epochs=1, num_mini_batches=1, clip_param=0.2, gamma=0.998, lam=0.95,
                  value_loss_coef=1.0, entropy_coef=0.0, learning_rate=1e-3, max_grad_norm=1.0, use_clipped_value_loss=True,
@@ -147,6 +152,10 @@ class PPO:
         self._mirror_coef = coef
         self._augment = self.symmetry is not None and bool(self.symmetry_augmentation)
         self._symmetry = self.symmetry if (self._augment or coef > 0.0) else None      # neither half asked for: symmetry off
+        self._rnd = None
+        if self.rnd is not None:
+            from . import rnd as rnd_module
+            rnd_module.check_setup(self._world, self.symmetry if self._augment else None, self._augment)
         if self._symmetry is not None:
             self.storage.enable_mirror(self._symmetry)      # (before enable_shadow and before anything binds a slot's address)
         ac = self.actor_critic
@@ -202,6 +211,7 @@ class PPO:
         self._perm_seed = (torch.initial_seed() * 0x9E3779B97F4A7C15 + 0xABCD + 104729 * self._rank) & 0xFFFFFFFFFFFFFFFF
         self._perm_draws = 0
         self._deferred_ready = False        # deferred_values() has run since the last compute_returns()
+        self._slot_T_written = False        # the rollout's producer writes the NEXT observations into the storage's slots (read by PPO.rnd)
         # diagnostics(): slot 0 of the observations as the update saw it (diagnostics_prepare), whether an update has run on the stored rows
         self._diag_rows0 = None
         self._diag_saved = self._diag_updated = False
@@ -210,6 +220,9 @@ class PPO:
         ac._sample_step = self._sample_step
         # exploration-noise key: from the run's seed (as the permutation key above) and the rank
         ac._sample_seed = (torch.initial_seed() * 0xD1342543DE82EF95 + 0x5EED + 7919 * self._rank) & 0xFFFFFFFFFFFFFFFF
+        if self.rnd is not None:      # two more NetBuffers at the PPO precision, the reward pass's block, the storage's rnd_* fields
+            self._rnd = self.rnd.bind(int(self.net.cfg.precision), max(mb, 1), self.device, num_envs)
+            self.storage.enable_rnd(self._rnd.num_states, self._rnd.num_outputs)
 
     def seek(self, iteration, steps_per_iteration):
         """Position the device generators' counters where a run that has done `iteration` learning iterations has them
@@ -260,6 +273,8 @@ class PPO:
         # invalidates it again
         sh = st.shadow_slot(s) if (out is not None and obs.data_ptr() == st._obs_all[s].data_ptr()
                                    and st._priv_all is not None and critic_obs.data_ptr() == st._priv_all[s].data_ptr()) else None
+        # obs IS the slot: a zero-copy rollout, whose env writes step s + 1's observations into slot s + 1 -- at the last step, slot T
+        self._slot_T_written = out is not None and obs.data_ptr() == st._obs_all[s].data_ptr()
         t.actions = self.actor_critic.act(obs, critic_obs, out=out, env_fin=env_fin, shadow=sh)
         last = self.actor_critic._last
         t.values, t.actions_log_prob = last["values"], last["logp"]
@@ -302,6 +317,7 @@ class PPO:
         if st.step != 0 or T > st.num_transitions_per_env:
             raise AssertionError("Rollout buffer overflow")
         self._rows_overwritten()
+        self._slot_T_written = True      # launch i writes slot i + 1
         env.rollout_begin(self.net, self.rollout_columns(deferred), T, rows_ahead, l0_ahead)
         for i in range(T):
             env.rollout_step(i)
@@ -358,9 +374,13 @@ class PPO:
             return stats
         return dist_utils.allreduce_adv_stats(stats)
 
-    def compute_returns(self, last_critic_obs):
+    def compute_returns(self, last_critic_obs, last_obs=None):
+        """last_obs (native extension, read by PPO.rnd only): the env's observations behind the last step, for an RND state taken from
+        "obs" when the rollout did not write the storage's slot T (RandomNetworkDistillation.reward_pass)."""
         st, deferred = self.storage, self._deferred_ready       # deferred_values() has evaluated the bootstrap observation with the rest
         last_values = st.last_values if deferred else self.actor_critic.evaluate(last_critic_obs)
+        if self._rnd is not None:      # rewards += intrinsic, ahead of GAE on both paths (the deferred path's time-out bootstrap is added behind it)
+            self._rnd.reward_pass(st, last_critic_obs, last_obs, self._slot_T_written)
         st.compute_returns(last_values, self.gamma, self.lam, stats_hook=self._adv_stats, time_outs=st.time_outs if deferred else None,
                            normalize=self._adv_mode == "batch")
         self._returns_done()
@@ -393,6 +413,9 @@ class PPO:
                 # the mirror loss (its coefficient is also part of _ppo_cfg's bytes above), whether the batch is doubled, the scratch the launches name
                 self._mirror_coef, self._augment,
                 None if self._mirror_target is None else (self._mirror_target.data_ptr(), self._mirror_sums.data_ptr()),
+                # RND: its nets, block and configuration bytes (ahead of the three entries tests read from the end)
+                None if self._rnd is None else (id(self._rnd), id(self._rnd.nets[0]), id(self._rnd.nets[1]), self._rnd.block.data_ptr(),
+                                                bytes(C.string_at(C.addressof(self._rnd.rnd_cfg), C.sizeof(self._rnd.rnd_cfg)))),
                 # how the advantages are standardised, and the column and scratch the per-minibatch pass names
                 self._adv_mode,
                 None if self.storage.advantages_mb is None else (self.storage.advantages_mb.data_ptr(), self.storage._adv_mb_scratch.data_ptr()),
@@ -466,6 +489,8 @@ class PPO:
         net.opt_state[hgym._lib.OPT_KL_SUM:hgym._lib.OPT_MINIBATCHES + 1] = 0.0     # the four per-update sums and their count (and the informational last norm between them): one fill
         if self._ppo_cfg.aux_coef > 0.0:
             net.opt_state[hgym._lib.OPT_AUX_SUM:hgym._lib.OPT_AUX_SUM + 1] = 0.0     # (a slice: a fill kernel -- an indexed scalar store is a host-to-device copy, which a stream capture refuses)
+        if self._rnd is not None:
+            self._rnd.begin_update()
         for _ in range(self.num_learning_epochs):
             for i in range(self.num_mini_batches):
                 idx = perm[i * mb:(i + 1) * mb]
@@ -494,8 +519,12 @@ class PPO:
                         ev[1].record()
                         self.comm_timing.append(ev + ("p2p" if direct else "collective",))
                 net.ppo_apply(self._ppo_cfg)
+                if self._rnd is not None:      # one predictor step on the SAME rows, against the target's embedding of them
+                    self._rnd.train_step(st, idx)
         if self._obs_norm is not None:
             self.normalizer_step()
+        if self._rnd is not None:
+            self._rnd.end_update(st)
         st.rotate()
         self._update_done()
         if not sync:
@@ -503,14 +532,25 @@ class PPO:
         o = self.log_block().cpu()             # the one host read-back of the update
         self.check_comm()                      # (the stream is idle now: reading the exchange's status costs one small copy)
         self.last_mirror_loss = self.mirror_loss_from(o)
+        self.rnd_log_from(o)
         o = hgym.opt_summary(o, self._ppo_cfg.aux_coef > 0.0)
         self.last_denoise_loss = o["denoise_loss"]
         return o["mean_value_loss"], o["mean_surrogate_loss"]
 
     def log_block(self):
-        """What a log block reads after an update, as ONE device tensor (one copy to the host): opt_state, and behind it the mirror
-        loss's two sums when that loss is on."""
-        return self.net.opt_state if self._mirror_sums is None else torch.cat((self.net.opt_state, self._mirror_sums))
+        """What a log block reads after an update, as ONE device tensor (one copy to the host): opt_state, behind it the mirror
+        loss's two sums when that loss is on, and last RND's tail when that is on."""
+        parts = [self.net.opt_state] + ([] if self._mirror_sums is None else [self._mirror_sums])
+        if getattr(self, "_rnd", None) is not None:      # the predictor loss's two sums and the head of the reward pass's block, last
+            parts.append(self._rnd.log_tail())
+        return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+    def rnd_log_from(self, block):
+        """Loss/rnd and the Rnd/* numbers from a host copy of log_block() (RandomNetworkDistillation.log_from); None when RND is off."""
+        rnd = getattr(self, "_rnd", None)
+        if rnd is None:
+            return None
+        return rnd.log_from(block[block.numel() - rnd.LOG_DOUBLES:])
 
     def mirror_loss_from(self, block):
         """The mean mirror MSE per minibatch from a host copy of log_block(); None when the loss is off."""

@@ -90,6 +90,15 @@ class RolloutStorage:
         hgym.adv_normalize_minibatches(perm, adv, self.advantages_mb, segments, self._adv_mb_scratch)
         return self.advantages_mb
 
+    def enable_rnd(self, num_states, num_outputs):
+        """Native extension (PPO.rnd): rnd_states (T + 1, N, S) -- a contiguous copy of the chosen observation columns of slots 0 .. T (the
+        net kernels gather rows without a leading dimension) --, rnd_target (T + 1, N, K), rnd_pred (T, N, K) -- the predictor over slots
+        1 .. T --, rnd_error and rnd_intrinsic (T, N).  Filled by RandomNetworkDistillation.reward_pass."""
+        T, N = self.num_transitions_per_env, self.num_envs
+        z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=self.device)
+        self.rnd_states, self.rnd_target = z(T + 1, N, int(num_states)), z(T + 1, N, int(num_outputs))
+        self.rnd_pred, self.rnd_error, self.rnd_intrinsic = z(T, N, int(num_outputs)), z(T, N), z(T, N)
+
     def enable_shadow(self, ld_obs, ld_priv):
         """Native extension: allocate (T, N, ld) bfloat16 copies of `observations` / `privileged_observations` (ld = the widths
         padded to 128, zero pad columns).  Slot s counts as valid once a policy launch has written it (shadow_slot)."""

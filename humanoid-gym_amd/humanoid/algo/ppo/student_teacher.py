@@ -20,6 +20,22 @@ PLACEHOLDER_CRITIC_DIMS = [256, 128, 128]      # the smallest trunk the fused bf
 TEACHER_MAX_BATCH = 16384      # rows per launch of the teacher's pass by default: one 64-row tile per CU of a 256-CU device
 
 
+def forward_in_pieces(net, x, y, which=0):
+    """Net `which` of a NetBuffers over all M rows of x ((M, in) fp32 contiguous) into y ((M, out) fp32 contiguous), in pieces of at most
+    max_batch rows (whole 64-row tiles when max_batch allows) -- one hgym_mlp_forward per piece, nothing allocated."""
+    import ctypes as C
+    from hgym import _lib as L
+    assert x.is_contiguous() and y.is_contiguous() and x.dtype == torch.float32 and y.dtype == torch.float32 and x.shape[0] == y.shape[0]
+    M, mb = int(x.shape[0]), int(net.cfg.max_batch)
+    piece = mb if mb < 64 else mb // 64 * 64
+    for m0 in range(0, M, piece):
+        m = min(piece, M - m0)
+        a, b = x[m0:m0 + m], y[m0:m0 + m]
+        L.check(L.lib.hgym_mlp_forward(C.byref(net.cfg), C.byref(net.struct), which, m, L.fptr(a), a.stride(0), L.fptr(b), net.stream()),
+                "hgym_mlp_forward")
+    return y
+
+
 class StudentTeacher(ActorCritic):
     # rows per launch of the teacher's pass over the stored observations (teacher_pass); None: see bind()
     teacher_max_batch = None
@@ -116,16 +132,6 @@ class StudentTeacher(ActorCritic):
     def teacher_pass(self, observations, out):
         """The teacher over all M rows of `observations` ((M, num_obs) fp32 contiguous) into `out` ((M, num_actions) fp32 contiguous), in
         pieces of at most max_batch rows (whole 64-row tiles when max_batch allows) -- one hgym_mlp_forward per piece, nothing allocated."""
-        import ctypes as C
-        from hgym import _lib as L
         net = self._need_teacher_net()
-        assert observations.is_contiguous() and out.is_contiguous() and observations.dtype == torch.float32 and out.dtype == torch.float32
-        M, mb = int(observations.shape[0]), int(net.cfg.max_batch)
-        assert out.shape[0] == M and out.shape[1] == self.num_actions
-        piece = mb if mb < 64 else mb // 64 * 64
-        for m0 in range(0, M, piece):
-            m = min(piece, M - m0)
-            x, y = observations[m0:m0 + m], out[m0:m0 + m]
-            L.check(L.lib.hgym_mlp_forward(C.byref(net.cfg), C.byref(net.struct), 0, m, L.fptr(x), x.stride(0), L.fptr(y), net.stream()),
-                    "hgym_mlp_forward")
-        return out
+        assert out.shape[0] == observations.shape[0] and out.shape[1] == self.num_actions
+        return forward_in_pieces(net, observations, out)

@@ -28,7 +28,11 @@ folded into the first layers (ActorCritic(empirical_normalization=True), DESIGN.
 
 HGYM_ADV_NORM=minibatch|none|batch sets `algorithm.advantage_normalization` the same way: the advantages standardised per minibatch
 (rsl_rl's normalize_advantage_per_mini_batch), not at all, or -- "batch", unset: the reference's way -- once over the whole batch
-(PPO.advantage_normalization)."""
+(PPO.advantage_normalization).
+
+HGYM_RND=<weight> sets `algorithm.rnd_cfg = {"weight": <weight>}` the same way: Random Network Distillation with its defaults and that
+constant weight -- an intrinsic exploration reward added to the stored rewards ahead of GAE (PPO.rnd); checkpoints
+carry rnd_state_dict.  Unset: off."""
 import os
 import sys
 
@@ -56,6 +60,8 @@ def train(args):
         task_registry.get_cfgs(args.task)[1].policy.empirical_normalization = True
     if os.environ.get("HGYM_ADV_NORM"):
         task_registry.get_cfgs(args.task)[1].algorithm.advantage_normalization = os.environ["HGYM_ADV_NORM"]
+    if os.environ.get("HGYM_RND"):
+        task_registry.get_cfgs(args.task)[1].algorithm.rnd_cfg = {"weight": float(os.environ["HGYM_RND"])}
     ppo_runner, train_cfg = task_registry.make_alg_runner(env=env, name=args.task, args=args, **({} if rank == 0 else {"log_root": None}))
     ppo_runner.learn(num_learning_iterations=train_cfg.runner.max_iterations, init_at_random_ep_len=True)
     if os.environ.get("HGYM_TRAIN_SIGNATURE"):      # tests: a signature of this rank's final parameters (replicas must agree bit for bit)

@@ -69,7 +69,9 @@ extern "C" {
                              *    (same version, later: hgym_adv_normalize_minibatches -- advantages standardised per minibatch into a second column;
                              *    no layout changes)
                              *    (same version, later: hgym_bc_grad and HgymBCConfig -- one behaviour-cloning minibatch of the actor, rsl_rl's
-                             *    Distillation; no layout changes) */
+                             *    Distillation; no layout changes)
+                             *    (same version, later: hgym_rnd_block_init, hgym_rnd_rewards and HgymRndConfig -- Random Network Distillation's
+                             *    reward pass; no layout changes) */
 
 enum {
     HGYM_OK = 0,
@@ -457,6 +459,81 @@ int32_t hgym_adv_normalize(int64_t count, float* advantages, const double* stats
 #define HGYM_ADV_MB_SCRATCH_DOUBLES(segments, seg_len) ((int64_t)(segments) * (3 + 2 * (((int64_t)(seg_len) + 1023) / 1024)))
 int32_t hgym_adv_normalize_minibatches(int32_t segments, int64_t seg_len, const int64_t* idx, const float* adv, float* out, int64_t rows,
                                        double* scratch, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Random Network Distillation's reward pass (rsl_rl's rnd_cfg; PPO.rnd; header v9, no layout changes).
+ * Behind a rollout the caller runs a frozen target net and a trained predictor over the NEXT state of every stored transition (storage
+ * slots 1 .. T); this call turns the two embeddings into a normalised, scheduled exploration reward and adds it to the stored rewards,
+ * ahead of GAE.
+ *   pred, target   (T * n, K) fp32, row-major, contiguous; row t * n + i is transition t of env i.  1 <= K <= HGYM_RND_MAX_OUTPUTS.
+ *   rewards        (T, n) fp32, updated in place.        err, intrinsic   (T, n) fp32, written.
+ *   block          HGYM_RND_BLOCK_DOUBLES(n) doubles of the caller, written once by hgym_rnd_block_init; the state carried from call to call.
+ * Arithmetic, every operation rounded once:
+ *   raw error      e[t][i] = sqrtf(sum_j (target_j - pred_j)^2): differences, squares and the sum in fp32, the sum starting from 0 with j
+ *                  ascending, the square root correctly rounded (torch.linalg.norm(target - predictor, dim=1)).
+ *   discounted average, per env, fp64, carried ACROSS calls in block[HGYM_RND_HEADER + i]:
+ *                  G_i = gamma * G_i + (double)e[t][i]   for t = 0 .. T - 1; no reset on episode ends (rsl_rl's DiscountedAverage has none).
+ *   running statistics of G, (mean, var, count) = (0, 1, 0) after hgym_rnd_block_init: the call's T * n values of G are ONE batch of
+ *                  nb = T * n values with mu_b = sum G / nb and var_b = sum G^2 / nb - mu_b^2 clamped at 0, merged FIRST, by the formula stated
+ *                  for hgym_net_norm_merge:
+ *                      count += nb;  rate = nb / count;  d = mu_b - mean;  mean += rate * d;  var += rate * (var_b - var + d * (mu_b - mean_new))
+ *                  The two sums are fp64 partial sums per HGYM_RND_ENVS_PER_PARTIAL envs (per env t ascending; the envs of a partial by a
+ *                  fixed tree), added in a fixed order: no fp64 atomics, the same inputs give the same bits in every run.  std = sqrt(var).
+ *   weight         row t uses the step count c = counter + t + 1, counter = block[HGYM_RND_COUNTER] (an integer in a double slot; the call
+ *                  leaves counter += T), in fp64:
+ *                      HGYM_RND_CONSTANT  w = weight
+ *                      HGYM_RND_STEP      w = weight while c < final_step, then final_value
+ *                      HGYM_RND_LINEAR    w = weight for c <= initial_step, final_value for c >= final_step, between them
+ *                                         weight + (final_value - weight) * (double)(c - initial_step) / (double)(final_step - initial_step),
+ *                                         evaluated left to right
+ *   applying it    scale_t = (float)(normalize && std > 0 ? w / std : w);  intrinsic[t][i] = e[t][i] * scale_t, one fp32 product;
+ *                  rewards[t][i] += intrinsic[t][i], one fp32 addition.  normalize = 0: the statistics are kept, scale_t = (float)w.
+ *   logging        written, not accumulated: block[HGYM_RND_SUM_INTRINSIC] = sum of (double)intrinsic, block[HGYM_RND_SUM_REWARDS] = sum of the
+ *                  (double) incoming rewards (both over all T * n entries, ordered partial sums), block[HGYM_RND_WEIGHT_LAST] = w of row
+ *                  T - 1, block[HGYM_RND_STD] = std, block[HGYM_RND_ROWS] = T * n.
+ * The block: [HGYM_RND_MEAN], [HGYM_RND_VAR], [HGYM_RND_COUNT], [HGYM_RND_COUNTER], the five logging slots, two arrival counters (integers in
+ * the first word of their slots, zero between calls), HGYM_RND_HEADER doubles in all; then G [n]; then scratch of the launches.
+ * Rows-per-workgroup of the launches (informational, for tests that sit on the edges): HGYM_RND_ROWS_PER_WG rows of the embeddings,
+ * HGYM_RND_ENVS_PER_PARTIAL envs of the average, 256 envs of one row when applying.
+ * hgym_rnd_block_init writes every double of the block (mean 0, var 1, everything else 0).  Both calls enqueue on `stream`; nothing
+ * synchronises, nothing allocates; with fixed arguments hgym_rnd_rewards is capturable (three launches).  One call at a time per block.
+ * HGYM_E_BADARG and nothing launched: a null pointer; T, n or K < 1; K > HGYM_RND_MAX_OUTPUTS; gamma outside [0, 1); a schedule other than the
+ * three; weight (and, where the schedule reads it, final_value) negative or not finite; HGYM_RND_LINEAR with final_step <= initial_step;
+ * normalize outside {0, 1}.
+ * ---------------------------------------------------------------------------------------------- */
+#define HGYM_RND_MAX_OUTPUTS 64
+#define HGYM_RND_CONSTANT 0
+#define HGYM_RND_STEP 1
+#define HGYM_RND_LINEAR 2
+#define HGYM_RND_HEADER 16
+#define HGYM_RND_MEAN 0
+#define HGYM_RND_VAR 1
+#define HGYM_RND_COUNT 2
+#define HGYM_RND_COUNTER 3
+#define HGYM_RND_SUM_INTRINSIC 4
+#define HGYM_RND_SUM_REWARDS 5
+#define HGYM_RND_WEIGHT_LAST 6
+#define HGYM_RND_STD 7
+#define HGYM_RND_ROWS 8
+#define HGYM_RND_TICKET_SCAN 9
+#define HGYM_RND_TICKET_APPLY 10
+#define HGYM_RND_ROWS_PER_WG 64
+#define HGYM_RND_ENVS_PER_PARTIAL 64
+#define HGYM_RND_APPLY_WGS 1024
+#define HGYM_RND_BLOCK_DOUBLES(n) ((size_t)HGYM_RND_HEADER + (size_t)(n) + 2 * (((size_t)(n) + HGYM_RND_ENVS_PER_PARTIAL - 1) / HGYM_RND_ENVS_PER_PARTIAL) + 2 * (size_t)HGYM_RND_APPLY_WGS)
+typedef struct {
+    double gamma;          /* discount of the per-env average G, in [0, 1) */
+    double weight;         /* the (initial) weight, finite and >= 0 */
+    double final_value;    /* HGYM_RND_STEP / HGYM_RND_LINEAR: the weight from final_step on */
+    int64_t initial_step;  /* HGYM_RND_LINEAR */
+    int64_t final_step;    /* HGYM_RND_STEP / HGYM_RND_LINEAR */
+    int32_t schedule;      /* HGYM_RND_CONSTANT / HGYM_RND_STEP / HGYM_RND_LINEAR */
+    int32_t normalize;     /* 1: divide by the running deviation of G (rsl_rl's reward_normalization); 0: the statistics are kept but not used */
+} HgymRndConfig;
+int32_t hgym_rnd_block_init(int32_t n, double* block, void* stream);
+int32_t hgym_rnd_rewards(int32_t T, int32_t n, int32_t K, const float* pred, const float* target, float* rewards, float* err, float* intrinsic,
+                         const HgymRndConfig* cfg, double* block, void* stream);
+
 /* hgym_gae for a rollout collected with deferred values (HgymEnvOut.t_time_outs): rewards (T, n) holds the RAW rewards and is
  * overwritten with r_t + gamma * (V_t * time_outs_t) -- PPO.process_env_step's bootstrap (ppo.py:107-108), the three fp32 roundings of
  * hgym_store_step -- before the scan uses it, so that afterwards every storage column is what the per-step path leaves. */
