@@ -22,6 +22,8 @@
 // Weight operand layout: "fragment-major", fragment (nb, kb) = 1 KiB in exact lane order (lane l: row nb*16 + (l&15),
 // k = kb*32 + 8*(l>>4) .. +7), so a wavefront's weight load is one contiguous 1 KiB global_load_dwordx4.
 #pragma once
+#include <type_traits>
+
 #include "hgym_finalize.hpp"
 // This header's arithmetic is compiled with the same contraction setting in every translation unit (hgym_net.hip: the default;
 // hgym_rollout.hip: built with -ffp-contract=off for the env arithmetic it also contains, and defines HGYM_TU_CONTRACT_OFF).
@@ -31,6 +33,11 @@
 namespace hgym {
 
 constexpr int FUSED_CHUNK = 128;      // input columns staged per first-layer chunk (4 k-blocks of 32)
+// HGYM_L0_TRIM: which first-layer loops stop at FusedLayer::KR instead of KB (A/B builds): 0 none, 1 the tiles with a ring of 4
+// (32-row tiles), 2 all
+#ifndef HGYM_L0_TRIM
+#define HGYM_L0_TRIM 2
+#endif
 // Workgroup shapes: the update uses 64-row tiles with 16 wavefronts (4 per SIMD: the weight stream comes from L2 with
 // ~1 us latency under load and only thread-level parallelism hides it); the rollout uses 32-row tiles with 8 wavefronts,
 // two workgroups per CU.
@@ -46,10 +53,26 @@ struct FusedLayer {
     const u32x4* WTf;   // backward fragments [K/16][NBB][64] x 16 B (this layer's W, transposed role)
     const float* bias;  // [N] fp32, 4-byte aligned
     int K, N;           // logical in / out features
-    int KB;             // forward contraction blocks of 32
+    int KB;             // forward contraction blocks of 32 the fragment buffer holds (first layer: padded to whole 128-column chunks)
     int NB;             // forward output blocks of 16
     int NBB;            // backward contraction blocks of 32 (N padded to 32)
+    int KR;             // forward contraction blocks that hold a valid column, ceil(K / 32) <= KB: the k-steps a first-layer loop runs
 };
+
+// First layer of width K: what the buffers hold and what the loops run.  The weight fragments, the bf16 shadow and X0 are padded to
+// whole chunks (KB k-steps, NC chunks of 4); k-steps [KR, KB) hold zero weights against zero input columns and add +0 to
+// accumulators that started from +0, so the loops stop at KR: the last chunk runs nlast = KR - 4 (NC - 1) k-steps (1..4).
+struct L0KSteps {
+    int KB, KR, NC, nlast;
+};
+inline L0KSteps l0_ksteps(int K) {
+    L0KSteps s;
+    s.KB = (K + FUSED_CHUNK - 1) / FUSED_CHUNK * (FUSED_CHUNK / 32);
+    s.KR = (K + 31) / 32;
+    s.NC = s.KB / 4;
+    s.nlast = s.KR - 4 * (s.NC - 1);
+    return s;
+}
 
 struct FusedNet {
     FusedLayer layer[4];
@@ -287,8 +310,8 @@ __device__ __forceinline__ void mma_stream(WRing<GR, D>& R, const u32x4* __restr
 }
 
 // mma_chunk: the 4 k-steps t0 .. t0 + 3 (t0 % 4 == 0, D divides 4) of a stream whose input arrives in 4-k-block LDS chunks
-// (first layer).  LAST: this is the final chunk, nothing beyond k-step t0 + 3 exists.
-template <int G, int MB, int D, bool LAST, int XBP = -1, int GR>
+// (first layer); every slot is refilled, so at least one more chunk follows.  mma_chunk_last is the final chunk.
+template <int G, int MB, int D, int XBP = -1, int GR>
 __device__ __forceinline__ void mma_chunk(WRing<GR, D>& R, const u32x4* __restrict__ wl, int wstride, int t0, const char* xl, int CBx,
                                           int lane, f32x4 (&acc)[MB][G]) {
     static_assert(D == 2 || D == 4, "ring depth must divide the chunk");
@@ -321,11 +344,139 @@ __device__ __forceinline__ void mma_chunk(WRing<GR, D>& R, const u32x4* __restri
 #pragma unroll
             for (int g = 0; g < G; ++g) mma_frag<__bf16>(R.w[d][g], (XB && (s4 & 1)) ? xc[i] : xa[i], acc[i][g]);
         __builtin_amdgcn_sched_barrier(0);
-        if (!LAST || s4 + D < 4) {
+#pragma unroll
+        for (int g = 0; g < G; ++g) R.w[d][g] = wl[(int64_t)g * wstride + (t0 + s4 + D) * 64];
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// mma_chunk_n: a final chunk of exactly NL k-steps (1..4), straight-line: nothing beyond k-step t0 + NL - 1 is loaded.
+template <int G, int MB, int D, int NL, int XBP = -1, int GR>
+__device__ __forceinline__ void mma_chunk_n(WRing<GR, D>& R, const u32x4* __restrict__ wl, int wstride, int t0, const char* xl, int CBx,
+                                            int lane, f32x4 (&acc)[MB][G]) {
+    static_assert(NL >= 1 && NL <= 4 && (D == 2 || D == 4), "a chunk is 4 k-steps, the ring depth divides it");
+    constexpr bool XB = XBP < 0 ? (MB <= 2) : (XBP != 0);
+    const int r = lane & 15, q = lane >> 4;
+    const char* xb = xl + (q >> 1) * 512 + r * 32 + (q & 1) * 16;
+    u32x4 xa[MB], xc[XB ? MB : 1];
+    if (XB) {
+#pragma unroll
+        for (int i = 0; i < MB; ++i) xa[i] = *reinterpret_cast<const u32x4*>(xb + (i * CBx) * 512);
+    }
+#pragma unroll
+    for (int s4 = 0; s4 < NL; ++s4) {
+        const int d = s4 % D;
+        if (XB) {
+            if (s4 + 1 < NL) {
+#pragma unroll
+                for (int i = 0; i < MB; ++i) {
+                    const u32x4 v = *reinterpret_cast<const u32x4*>(xb + (i * CBx + 2 * (s4 + 1)) * 512);
+                    if (s4 & 1) xa[i] = v; else xc[i] = v;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < MB; ++i) xa[i] = *reinterpret_cast<const u32x4*>(xb + (i * CBx + 2 * s4) * 512);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < MB; ++i)
+#pragma unroll
+            for (int g = 0; g < G; ++g) mma_frag<__bf16>(R.w[d][g], (XB && (s4 & 1)) ? xc[i] : xa[i], acc[i][g]);
+        __builtin_amdgcn_sched_barrier(0);
+        if (s4 + D < NL) {
 #pragma unroll
             for (int g = 0; g < G; ++g) R.w[d][g] = wl[(int64_t)g * wstride + (t0 + s4 + D) * 64];
         }
         __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// mma_chunk_last: the final chunk of a first layer -- its first nlast k-steps (1..4, wave-uniform; struct L0KSteps), the ones that
+// hold a valid input column; the ring holds k-steps t0 .. t0 + min(D, nlast) - 1 (mma_chunk's refills, or wring_prime with the
+// true remaining count).  ONE unrolled body, so that a kernel that carries several tile bodies pays for no second copy
+// (mlp_fb_kernel has ~1 KB left of the 128 KiB a kernel may have): the MFMAs of a k-step at or beyond nlast are skipped by a
+// wave-uniform branch around them.  Such a branch holds no load, so the number of loads in flight is the same on both sides of it
+// and the vmcnt in front of every k-step stays as exact as in mma_stream; the x fragments are read regardless (LDS holds the whole
+// staged chunk, zero-filled pad columns included).  Ring of 4: the chunk is resident, nothing is refilled.  Ring of 2: k-steps
+// t0 + 2 / t0 + 3 are refilled behind k-steps t0 / t0 + 1, and a refill inside an `if` would join two paths with different
+// counts -- the wait behind the join is then for the worse of the two.  So
+//   * [t0 + 2] is issued whatever nlast is: for nlast <= 2 a fragment nobody reads (it lies inside the padded buffer);
+//   * [t0 + 3] belongs to nlast = 4 alone, which takes a branch of its own from there on: [t0 + 3] k2 k3 against k2 for nlast = 3,
+//     the one k-step that exists twice.
+// COPY = false leaves that second k2 out where it does not fit (the update tiles on fp32 rows, mlp_fb_kernel<false>: four bodies,
+// 130 000 bytes before this chunk form) and puts [t0 + 3] into an `if`: still exact for nlast = 3, which has nothing in flight
+// behind k-step t0 + 2 either way, while nlast = 4 waits for k-steps t0 + 2 AND t0 + 3 in front of k2.
+template <int G, int MB, int D, int XBP = -1, bool COPY = true, int GR>
+__device__ __forceinline__ void mma_chunk_last(WRing<GR, D>& R, const u32x4* __restrict__ wl, int wstride, int t0, int nlast, const char* xl,
+                                               int CBx, int lane, f32x4 (&acc)[MB][G]) {
+    static_assert(D == 2 || D == 4, "ring depth must divide the chunk");
+    constexpr bool XB = XBP < 0 ? (MB <= 2) : (XBP != 0);
+    const int r = lane & 15, q = lane >> 4;
+    const char* xb = xl + (q >> 1) * 512 + r * 32 + (q & 1) * 16;
+    u32x4 xa[MB], xc[XB ? MB : 1];
+    if (XB) {
+#pragma unroll
+        for (int i = 0; i < MB; ++i) xa[i] = *reinterpret_cast<const u32x4*>(xb + (i * CBx) * 512);
+    }
+    auto xread = [&](auto s4c) __attribute__((always_inline)) {           // the x fragments k-step s4 reads (XB: those of s4 + 1)
+        constexpr int s4 = decltype(s4c)::value;
+        if (XB) {
+            if (s4 + 1 < 4) {
+#pragma unroll
+                for (int i = 0; i < MB; ++i) {
+                    const u32x4 v = *reinterpret_cast<const u32x4*>(xb + (i * CBx + 2 * (s4 + 1)) * 512);
+                    if (s4 & 1) xa[i] = v; else xc[i] = v;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < MB; ++i) xa[i] = *reinterpret_cast<const u32x4*>(xb + (i * CBx + 2 * s4) * 512);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    auto mfmas = [&](auto s4c) __attribute__((always_inline)) {
+        constexpr int s4 = decltype(s4c)::value, d = s4 % D;
+#pragma unroll
+        for (int i = 0; i < MB; ++i)
+#pragma unroll
+            for (int g = 0; g < G; ++g) mma_frag<__bf16>(R.w[d][g], (XB && (s4 & 1)) ? xc[i] : xa[i], acc[i][g]);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    auto refill = [&](auto s4c) __attribute__((always_inline)) {          // slot s4 % D <- k-step t0 + s4 + D (ring of 2 only)
+        if constexpr (D == 2) {
+            constexpr int s4 = decltype(s4c)::value, d = s4 % D;
+#pragma unroll
+            for (int g = 0; g < G; ++g) R.w[d][g] = wl[(int64_t)g * wstride + (t0 + s4 + D) * 64];
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+    using K0 = std::integral_constant<int, 0>;
+    using K1 = std::integral_constant<int, 1>;
+    using K2 = std::integral_constant<int, 2>;
+    using K3 = std::integral_constant<int, 3>;
+    xread(K0());
+    mfmas(K0());
+    refill(K0());
+    xread(K1());
+    if (nlast > 1) mfmas(K1());
+    if constexpr (D == 2 && COPY) {
+        if (nlast > 3) {
+            refill(K1());
+            xread(K2());
+            mfmas(K2());
+            xread(K3());
+            mfmas(K3());
+        } else if (nlast > 2) {
+            xread(K2());
+            mfmas(K2());
+        }
+    } else {
+        if (nlast > 3) refill(K1());
+        xread(K2());
+        if (nlast > 2) mfmas(K2());
+        xread(K3());
+        if (nlast > 3) mfmas(K3());
     }
 }
 
@@ -670,6 +821,10 @@ __device__ __forceinline__ void fwd_body(const FwdArgs& a, const FusedNet& n, bo
     auto prime1 = [&]() { hidden_prime<GH, D>(r1, L1, wave, lane); };
 
     // ---------------------------------------------------------------- layer 0: input streamed in 128-column chunks
+    // k-steps the loop runs (struct L0KSteps).  The 64-row tile on 8 wavefronts (the rollout launch's critic tile: 6 n-blocks a wave,
+    // 254 VGPRs in a kernel that has no scratch) keeps all KB of them in the straight-line form: either short form costs it spills.
+    constexpr bool L0_FULL = NW <= 8 && D == 2;
+    const int KR0 = (!L0_FULL && HGYM_L0_TRIM >= (D == 4 ? 1 : 2)) ? L0.KR : L0.KB;
     if constexpr (XB16) {
         // input rows from the bf16 shadow: a chunk is 64 (32) rows x 256 B = one 16-byte item per lane, loaded as it will lie in
         // LDS.  Lane map: 16 consecutive lanes = 8 rows x the two halves of one block row (a conflict-free 256-byte LDS
@@ -694,20 +849,21 @@ __device__ __forceinline__ void fwd_body(const FwdArgs& a, const FusedNet& n, bo
         WRing<G1, D> r0;
         const u32x4* wl0 = L0.Wf + (int64_t)nb0 * L0.KB * 64 + lane;
         phase_stamp(a.dbg, 0);
-        wring_prime<G1, D>(r0, wl0, L0.KB * 64, L0.KB);
+        wring_prime<G1, D>(r0, wl0, L0.KB * 64, KR0);
         stage_load(0);
         hook_early(extra);
         stage_write(0);
         bias_to_lds();
         __syncthreads();
         phase_stamp(a.dbg, 1);
+        // (the staging keeps whole chunks: the pad columns it copies are the zeros the shadow holds)
         for (int c = 0; c + 1 < NC; ++c) {
             stage_load(c + 1);
-            mma_chunk<G1, MB, D, false, XBF>(r0, wl0, L0.KB * 64, c * 4, Q + (c & 1) * (BM * FUSED_CHUNK * 2), 8, lane, acc);
+            mma_chunk<G1, MB, D, XBF>(r0, wl0, L0.KB * 64, c * 4, Q + (c & 1) * (BM * FUSED_CHUNK * 2), 8, lane, acc);
             stage_write((c + 1) & 1);
             __syncthreads();
         }
-        mma_chunk<G1, MB, D, true, XBF>(r0, wl0, L0.KB * 64, (NC - 1) * 4, Q + ((NC - 1) & 1) * (BM * FUSED_CHUNK * 2), 8, lane, acc);
+        mma_chunk_last<G1, MB, D, XBF>(r0, wl0, L0.KB * 64, (NC - 1) * 4, KR0 - (NC - 1) * 4, Q + ((NC - 1) & 1) * (BM * FUSED_CHUNK * 2), 8, lane, acc);
         phase_stamp(a.dbg, 2);
         if (AHEAD) prime1();
         epilogue_elu<G1, MB, GA>(acc, bl, nb0, P, L0.NB, train_h ? n.H[0] : nullptr, mbg0, lane, a.act);
@@ -788,7 +944,7 @@ __device__ __forceinline__ void fwd_body(const FwdArgs& a, const FusedNet& n, bo
         WRing<G1, D> r0;
         const u32x4* wl0 = L0.Wf + (int64_t)nb0 * L0.KB * 64 + lane + (int64_t)c0 * 4 * 64;
         phase_stamp(a.dbg, 0);
-        wring_prime<G1, D>(r0, wl0, L0.KB * 64, L0.KB - c0 * 4);
+        wring_prime<G1, D>(r0, wl0, L0.KB * 64, KR0 - c0 * 4);
         stage_load(c0);
         hook_early(extra);
         stage_write(c0, 0);
@@ -806,11 +962,13 @@ __device__ __forceinline__ void fwd_body(const FwdArgs& a, const FusedNet& n, bo
         // steady state: no condition inside the body (see mma_stream); the last chunk is peeled
         for (int c = c0; c + 1 < NC; ++c) {
             stage_load(c + 1);
-            mma_chunk<G1, MB, D, false, XBF>(r0, wl0, L0.KB * 64, (c - c0) * 4, Q + ((c - c0) & 1) * (BM * FUSED_CHUNK * 2), 8, lane, acc);
+            mma_chunk<G1, MB, D, XBF>(r0, wl0, L0.KB * 64, (c - c0) * 4, Q + ((c - c0) & 1) * (BM * FUSED_CHUNK * 2), 8, lane, acc);
             stage_write(c + 1, (c + 1 - c0) & 1);
             __syncthreads();
         }
-        mma_chunk<G1, MB, D, true, XBF>(r0, wl0, L0.KB * 64, (NC - 1 - c0) * 4, Q + ((NC - 1 - c0) & 1) * (BM * FUSED_CHUNK * 2), 8, lane, acc);
+        // (the staging keeps whole chunks: the zero-filled pad columns still reach LDS, the shadow and X0)
+        if constexpr (L0_FULL) mma_chunk_n<G1, MB, D, 4, XBF>(r0, wl0, L0.KB * 64, (NC - 1 - c0) * 4, Q + ((NC - 1 - c0) & 1) * (BM * FUSED_CHUNK * 2), 8, lane, acc);
+        else mma_chunk_last<G1, MB, D, XBF, NW <= 8>(r0, wl0, L0.KB * 64, (NC - 1 - c0) * 4, KR0 - (NC - 1) * 4, Q + ((NC - 1 - c0) & 1) * (BM * FUSED_CHUNK * 2), 8, lane, acc);
         phase_stamp(a.dbg, 2);
         if (AHEAD) prime1();
         epilogue_elu<G1, MB, GA>(acc, bl, nb0, P, L0.NB, train_h ? n.H[0] : nullptr, mbg0, lane, a.act);

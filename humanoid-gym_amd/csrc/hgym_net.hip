@@ -46,6 +46,7 @@ struct LayerLayout {
     int64_t X, XT, dY, dYT;  // byte offsets: layer input, its transpose, output grad, its transpose
     // fused bf16 path (hgym_fused.hpp): fragment-major operand copies
     int KBf, NBf, NBBf;      // forward k-blocks of 32, output blocks of 16, backward contraction blocks of 32
+    int KRf;                 // forward k-blocks that hold a valid column, ceil(K / 32): what the first-layer loops run (l0_ksteps); KBf sizes every buffer
     int64_t Wf, WTf;         // byte offsets
 };
 
@@ -205,7 +206,8 @@ static int32_t ws_layout(const HgymNetConfig* c, WsLayout* w) {
             y.b_off = poff;
             poff += y.N;
             if (n.fused) {
-                y.KBf = (int)round_up(y.K, l == 0 ? FUSED_CHUNK : 32) / 32;
+                y.KBf = l == 0 ? l0_ksteps(y.K).KB : (int)round_up(y.K, 32) / 32;      // first layer: whole 128-column chunks
+                y.KRf = l == 0 ? l0_ksteps(y.K).KR : y.KBf;
                 y.NBf = y.N16 / 16;
                 y.NBBf = (int)round_up(y.N, 32) / 32;
                 y.Wf = take((int64_t)y.NBf * y.KBf * 1024);
@@ -1187,6 +1189,7 @@ struct FusedPath : NetBase {
             d.K = y.K;
             d.N = y.N;
             d.KB = y.KBf;
+            d.KR = y.KRf;
             d.NB = y.NBf;
             d.NBB = y.NBBf;
         }
@@ -1707,6 +1710,32 @@ int32_t hgym_critic_values(const HgymNetConfig* cfg, const HgymNet* net, int64_t
         HG_REQUIRE(M > 0 && priv && values, HGYM_E_BADARG, "M=%lld, null priv / values", (long long)M);
         return R.critic_values(M, priv, values, shadow);
     });
+}
+
+// Test hook, not part of include/hgym.h: out[0..3] = KB, KR, NC, nlast of a first layer (struct L0KSteps) -- cfg == NULL: of input
+// width K by l0_ksteps alone; else: as ws_layout lays out net `which` of cfg (K ignored).  Host arithmetic only, no device call.
+int32_t hgym_internal_l0_ksteps(const HgymNetConfig* cfg, int32_t which, int32_t K, int32_t* out) {
+    HG_REQUIRE(out, HGYM_E_BADARG, "null out");
+    L0KSteps s;
+    if (cfg) {
+        WsLayout w;
+        const int32_t rc = ws_layout(cfg, &w);
+        if (rc) return rc;
+        HG_REQUIRE(which >= 0 && which < w.nnets && w.net[which].fused, HGYM_E_BADARG, "which=%d: not a net on the fused layout", which);
+        const LayerLayout& y = w.net[which].layer[0];
+        s.KB = y.KBf;
+        s.KR = y.KRf;
+        s.NC = y.KBf / 4;
+        s.nlast = y.KRf - 4 * (s.NC - 1);
+    } else {
+        HG_REQUIRE(K > 0, HGYM_E_BADARG, "K=%d", K);
+        s = l0_ksteps(K);
+    }
+    out[0] = s.KB;
+    out[1] = s.KR;
+    out[2] = s.NC;
+    out[3] = s.nlast;
+    return HGYM_OK;
 }
 
 int64_t hgym_net_shadow_ld(const HgymNetConfig* cfg, int32_t which) {

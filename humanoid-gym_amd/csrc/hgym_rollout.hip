@@ -155,6 +155,9 @@ int32_t hgym_rollout_step(const HgymNetConfig* cfg, const HgymNet* net, const Hg
         HG_REQUIRE(!part || prev_out, HGYM_E_BADARG, "l0_ready on the first step of a rollout: no launch has left partial sums");
         HG_REQUIRE(!(part || out->l0_ahead) || (f.net[0].layer[0].KB == 24 && f.net[0].layer[0].N == 512 && HGYM_OBS_FRAME * 14 >= 32 * KB0_AHEAD),
                    HGYM_E_UNSUPPORTED, "the carried first layer is built for XBot-L's 15 x 47 -> 512 actor input");
+        // the consuming tile runs k-steps [kb0, KR): at least one of them (its last-chunk form takes 1..4)
+        HG_REQUIRE(!(part || out->l0_ahead) || KB0_AHEAD <= f.net[0].layer[0].KR - 1, HGYM_E_UNSUPPORTED,
+                   "the carried first layer: %d k-steps ahead of the %d the input width needs", KB0_AHEAD, f.net[0].layer[0].KR);
         HG_REQUIRE(!out->l0_ahead || (((uintptr_t)out->l0_ahead & 15) == 0 && out->l0_ahead != out->l0_ready), HGYM_E_BADARG,
                    "l0_ahead must be 16-byte aligned and distinct from l0_ready");
         HG_REQUIRE(!out->obs_bf16_ahead || (out->l0_ahead && out->ld_obs_bf16_ahead >= 768 && out->ld_obs_bf16_ahead % 8 == 0 &&
