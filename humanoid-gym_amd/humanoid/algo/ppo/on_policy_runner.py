@@ -3,13 +3,9 @@ checkpoint save / load (same dict keys), inference-policy getters, console + opt
 
 The env writes its observations straight into the rollout-storage slots, and episode book-keeping stays on the device,
 read back once per iteration (the reference syncs the host every step, :146-152)."""
-import atexit
 import gc
 import os
-import sys
-import queue
 import statistics
-import threading
 import time
 from collections import deque
 from dataclasses import dataclass
@@ -18,6 +14,8 @@ from typing import Optional
 
 import torch
 
+from . import checkpoint as ckpt
+from .checkpoint import NORM_KEYS, RND_STATE_KEY, _check_norm_keys  # noqa: F401  (re-exported: tests and tools read them here)
 from .ppo import PPO
 from .actor_critic import ActorCritic
 from .student_teacher import StudentTeacher  # noqa: F401  (policy_class_name is eval'ed below)
@@ -32,54 +30,6 @@ try:
     import wandb
 except Exception:  # pragma: no cover
     wandb = None
-
-
-class _CheckpointWriter:
-    """One background thread that turns pinned-host snapshots into checkpoint files (OnPolicyRunner.save): the training thread only
-    enqueues device -> pinned-host copies behind the update and goes on; the pickling + file write (6-15 ms for XBot-L's 11 MB of
-    parameters and Adam moments) happens here, under the next iteration.  Files appear atomically (written to a temporary name,
-    then renamed)."""
-
-    def __init__(self):
-        self.q = queue.Queue()
-        self.thread = None
-        self.error = None
-        self.lock = threading.Lock()
-
-    def submit(self, job):
-        with self.lock:
-            if self.thread is None or not self.thread.is_alive():
-                self.thread = threading.Thread(target=self._run, name="hgym-checkpoint-writer", daemon=True)
-                self.thread.start()
-        self.q.put(job)
-
-    def _run(self):
-        # this thread's CPU tensor work stays on this thread: the default intra-op pool is one thread per host core (128+ on the GPU boxes), and a
-        # parallel region opened from here -- a 3.7 MB copy is enough -- wakes all of them next to the thread that launches the kernels
-        # (measured: sporadic 50-350 ms stalls of a checkpoint job and, now and then, of the training thread; profiles/r06_async_checkpoint_default.txt)
-        try:
-            torch.set_num_threads(1)
-        except Exception:      # noqa: BLE001
-            pass
-        while True:
-            job = self.q.get()
-            try:
-                if job is not None:
-                    job()
-            except Exception as e:      # noqa: BLE001 -- re-raised on the training thread by wait()
-                self.error = e
-            finally:
-                self.q.task_done()
-
-    def wait(self):
-        self.q.join()
-        if self.error is not None:
-            e, self.error = self.error, None
-            raise e
-
-
-_WRITER = _CheckpointWriter()
-atexit.register(lambda: _WRITER.q.join())
 
 
 @dataclass(frozen=True)
@@ -216,7 +166,6 @@ def _split_algorithm_cfg(alg_cfg):
 
 ADVANTAGE_KEYS = ("advantage_normalization", "normalize_advantage_per_mini_batch")      # neither is a parameter of PPO.__init__
 RND_KEY = "rnd_cfg"      # rsl_rl's Random Network Distillation block (humanoid.algo.ppo.rnd.parse_config); absent or None: off
-RND_STATE_KEY = "rnd_state_dict"      # what a checkpoint of a run with rnd_cfg carries besides the reference's four keys
 
 
 def _split_advantage_cfg(alg_cfg):
@@ -273,24 +222,6 @@ def _split_policy_cfg(policy_cfg, runner_cfg):
                              % (kwargs["empirical_normalization"], runner_cfg["empirical_normalization"]))
         kwargs["empirical_normalization"] = r
     return kwargs
-
-
-NORM_KEYS = ("obs_norm_state_dict", "critic_obs_norm_state_dict")      # a checkpoint of a run with empirical_normalization carries both
-
-
-def _check_norm_keys(loaded, has_norm, name, spec=None):
-    """A checkpoint with statistics for a policy built without normalisation, or the reverse: refused, naming the key.  spec: this policy's
-    (eps, until) -- statistics saved under another eps or until are another function of the observations, or stop elsewhere: refused too."""
-    for k in NORM_KEYS:
-        if (k in loaded) != has_norm:
-            if has_norm:
-                raise RuntimeError("%s has no `%s`: it was trained without empirical_normalization, this policy was built with it" % (name, k))
-            raise RuntimeError("%s carries `%s`: it was trained with empirical_normalization, this policy was built without it" % (name, k))
-        if has_norm and spec is not None:
-            theirs = (loaded[k].get("eps"), loaded[k].get("until"))
-            if theirs[0] is None or float(theirs[0]) != float(spec[0]) or theirs[1] != spec[1]:
-                raise RuntimeError("%s: `%s` was saved with normalization_eps=%r, normalization_until=%r; this policy was built with %r, %r"
-                                   % (name, k, theirs[0], theirs[1], spec[0], spec[1]))
 
 
 class OnPolicyRunner:
@@ -357,7 +288,7 @@ class OnPolicyRunner:
         if init_at_random_ep_len and self._keep_episode_lengths:
             init_at_random_ep_len = False            # (once: the episode lengths are part of the env state load() has just restored)
         self._keep_episode_lengths = False
-        exact = self._exact_resume_on()
+        exact = ckpt.exact_resume_on(self.cfg, getattr(self.alg, "_world", 1), self)
         if init_at_random_ep_len:
             self.env.episode_length_buf = torch.randint_like(self.env.episode_length_buf, high=int(self.env.max_episode_length))
         env, alg, log_on = self.env, self.alg, self.log_dir is not None
@@ -800,30 +731,7 @@ class OnPolicyRunner:
         """Drop the captured rollout; the next learn() iteration runs eagerly and the one after re-captures."""
         self._rollout_capture, self._update_capture = _CapturedGraph(), _CapturedGraph()
 
-    @staticmethod
-    def env_state_path(path):
-        """The sidecar that goes with checkpoint `path`: envstate_<it>.pt next to model_<it>.pt.  Its name never contains "model":
-        helpers.get_load_path takes the last file of a run directory whose name does."""
-        d, base = os.path.split(path)
-        return os.path.join(d, "envstate" + base[len("model"):] if base.startswith("model") else "envstate_" + base.replace("model", "ckpt"))
-
-    def _exact_resume_on(self):
-        """cfg["exact_resume"] (absent: off), on one rank.  Data-parallel runs: every rank's env is its own and only rank 0 writes
-        checkpoints, so env state is not saved there -- said once, and the run goes on as without the switch."""
-        if not self.cfg.get("exact_resume", False):
-            return False
-        if getattr(self.alg, "_world", 1) > 1:
-            if not self._warned_env_state:
-                self._warned_env_state = True
-                print("exact_resume: env state is not saved in a data-parallel run (world size %d); checkpoints are written as without it"
-                      % self.alg._world)
-            return False
-        return True
-
-    def _env_state_extra(self, iterations_done):
-        return dict(iterations_done=int(self.current_learning_iteration if iterations_done is None else iterations_done),
-                    num_steps_per_env=int(self.num_steps_per_env), world_size=int(getattr(self.alg, "_world", 1)),
-                    rank=int(getattr(self.alg, "_rank", 0)))
+    env_state_path = staticmethod(ckpt.env_state_path)
 
     def save(self, path, infos=None, wait=True, env_state=False, iterations_done=None):
         """on_policy_runner.py:274-281 (same dict, same keys).
@@ -837,126 +745,33 @@ class OnPolicyRunner:
         On the background path the env snapshot follows the parameters': stream-ordered copies into two alternating pinned host sets,
         the file written by the same writer job.
 
-        wait=True (the reference's semantics, and what a direct caller gets): the file is on disk when the call returns.  On the
-        device path the tensors are first copied to pinned host memory stream-side (behind
-        whatever the update has enqueued -- the host does not wait) and pickled + written by a background thread, so a checkpoint costs the
-        training thread ~0.1 ms instead of a device sync + 5-15 ms.  learn() passes wait=False for ALL its checkpoints, the final one
-        included (round 6: default; `test_background_checkpoint_equals_the_synchronous_one`): the file of the last iteration is complete a
-        few milliseconds AFTER learn() returns -- `wait_for_saves()` (called by load(), by the next save(wait=True), and at interpreter
-        exit, which is when scripts/train.py ends) waits for it.  A caller that reads model_<it>.pt from the same process right after
-        learn() calls runner.wait_for_saves() first; HGYM_ASYNC_SAVE=0 restores the reference's blocking torch.save everywhere."""
+        wait=True (the reference's semantics, and what a direct caller gets): the file is on disk when the call returns.  learn() passes
+        wait=False for ALL its checkpoints, the final one included: on the background path (humanoid/algo/ppo/checkpoint.py, which also
+        holds the measurements) the file of the last iteration is complete a few milliseconds AFTER learn() returns -- `wait_for_saves()`
+        (called by load(), by the next save(wait=True), and at interpreter exit, which is when scripts/train.py ends) waits for it.  A
+        caller that reads model_<it>.pt from the same process right after learn() calls runner.wait_for_saves() first."""
         t0 = time.time()
-        net = getattr(self.alg, "net", None)
-        if (net is None or not str(self.device).startswith("cuda") or os.environ.get("HGYM_ASYNC_SAVE", "1") == "0"
-                or not hasattr(self.alg.actor_critic, "_net")
-                # a StudentTeacher's teacher.* entries live in a second flat vector: the blocking form, which cuts nothing by offset
-                or getattr(self.alg.actor_critic, "_teacher_net", None) is not None
-                # RND's two nets, the predictor's optimiser and the reward pass's block live in buffers of their own: the blocking form as well
-                or getattr(self.alg, "_rnd", None) is not None):
-            if env_state:
-                side = dict(env={k: (v.cpu() if torch.is_tensor(v) else v) for k, v in self.env.state_dict().items()},
-                            **self._env_state_extra(iterations_done))
-                side_path = self.env_state_path(path)
-                torch.save(side, side_path + ".tmp%d" % os.getpid())
-                os.replace(side_path + ".tmp%d" % os.getpid(), side_path)
-            norm = self.alg.actor_critic.norm_state_dicts() if hasattr(self.alg.actor_critic, "norm_state_dicts") else {}
-            if getattr(self.alg, "_rnd", None) is not None:
-                norm = dict(norm, **{RND_STATE_KEY: self.alg._rnd.rnd_state_dict()})
-            torch.save({"model_state_dict": self.alg.actor_critic.state_dict(),
-                        "optimizer_state_dict": self.alg.optimizer.state_dict(),
-                        "iter": self.current_learning_iteration, "infos": infos, **norm}, path)
+        alg, it = self.alg, self.current_learning_iteration
+        extra = dict(iterations_done=int(it if iterations_done is None else iterations_done), num_steps_per_env=int(self.num_steps_per_env),
+                     world_size=int(getattr(alg, "_world", 1)), rank=int(getattr(alg, "_rank", 0))) if env_state else None
+        if not ckpt.background_eligible(alg, self.device):
+            side = dict(env={k: (v.cpu() if torch.is_tensor(v) else v) for k, v in self.env.state_dict().items()}, **extra) if env_state else None
+            ckpt.write_checkpoint({"model_state_dict": alg.actor_critic.state_dict(), "optimizer_state_dict": alg.optimizer.state_dict(),
+                                   "iter": it, "infos": infos, **ckpt.extra_entries(alg)}, path, side)
         else:
-            if getattr(self, "_save_pin", None) is None:
-                mk = lambda n, dt: torch.empty(n, dtype=dt).pin_memory()
-                self._save_pin = [dict(params=mk(net.P, torch.float32), m=mk(net.P, torch.float32), v=mk(net.P, torch.float32),
-                                       opt=mk(net.opt_state.numel(), net.opt_state.dtype), busy=threading.Event()) for _ in range(2)]
-                for b in self._save_pin:
-                    b["busy"].set()         # set = free
-                self._save_n = 0
-            buf = self._save_pin[self._save_n & 1]
-            self._save_n += 1
-            buf["busy"].wait()              # (two snapshots in flight at most: the writer is two checkpoints behind only if the disk is)
-            buf["busy"].clear()
-            buf["params"].copy_(net.params, non_blocking=True)
-            buf["m"].copy_(net.adam_m, non_blocking=True)
-            buf["v"].copy_(net.adam_v, non_blocking=True)
-            buf["opt"].copy_(net.opt_state, non_blocking=True)
-            norm_on = getattr(net, "obs_norm", None) is not None
-            if norm_on:       # the normaliser's state rides with the parameters: header (eps, until, counts), then mean / var of both statistics
-                K = (int(net.cfg.num_obs), int(net.cfg.num_priv))
-                if "norm" not in buf:
-                    buf["norm"] = torch.empty(8 + 2 * (K[0] + K[1]), dtype=torch.float64).pin_memory()
-                parts = [net.norm_view("header")] + [net.norm_view(n, k) for k in (0, 1) for n in ("mean", "var")]
-                o = 0
-                for t in parts:
-                    buf["norm"][o:o + t.numel()].copy_(t, non_blocking=True)
-                    o += t.numel()
-                norm_spec = net.obs_norm
-            side = None
-            if env_state:
-                if "env" not in buf:        # (pinned on first use: a run without the switch allocates nothing)
-                    buf["env"] = self.env.state_host_buffers()
-                side = dict(env=self.env.state_dict(out=buf["env"]), **self._env_state_extra(iterations_done))
-                side_path = self.env_state_path(path)
-            done = torch.cuda.Event()
-            done.record()
-            # name -> (offset, shape) of every parameter in the flat vector: state_dict order = nn.Module's named_parameters order
-            base = net.params.data_ptr()
-            layout = [(k, (v.data_ptr() - base) // 4, tuple(v.shape)) for k, v in self.alg.actor_critic.state_dict().items()]
-            opt_layout = [((v.data_ptr() - base) // 4, tuple(v.shape)) for v in net.views.values()]
-            # (alg.optimizer.param_groups reads the learning rate from the device: a host sync; the snapshot carries it instead)
-            it, group = self.current_learning_iteration, dict(lr=None, **type(self.alg.optimizer).HYPER)
-            # every state_dict entry must be an fp32 view INTO the flat vector (the cut below is by offset and shape only)
-            for (k, o, shp), v in zip(layout, self.alg.actor_critic.state_dict().values()):
-                n = int(torch.Size(shp).numel())
-                assert v.dtype == torch.float32 and v.numel() == n and v.is_contiguous(), "%s is not an fp32 view of the flat parameter vector" % k
-                assert 0 <= o and o + n <= net.P and (v.data_ptr() - base) % 4 == 0, "%s lies outside the flat parameter vector" % k
-
-            def job():
-                try:
-                    tj = [time.perf_counter()]
-                    done.synchronize()
-                    tj.append(time.perf_counter())
-                    # views INTO the snapshot, no copies: torch.save writes each flat buffer once (tensors that share a storage are
-                    # pickled as offset + shape into it), torch.load hands back the same named tensors
-                    cut = lambda t, o, shp: t[o:o + int(torch.Size(shp).numel())].view(shp)
-                    lr, step = float(buf["opt"][0]), float(buf["opt"][1])
-                    model = {k: cut(buf["params"], o, shp) for k, o, shp in layout}
-                    state = {i: dict(step=torch.tensor(step), exp_avg=cut(buf["m"], o, shp), exp_avg_sq=cut(buf["v"], o, shp))
-                             for i, (o, shp) in enumerate(opt_layout)}
-                    group["lr"] = lr
-                    ck = {"model_state_dict": model,
-                          "optimizer_state_dict": dict(state=state, param_groups=[dict(group, params=list(range(len(state))))]),
-                          "iter": it, "infos": infos}
-                    if norm_on:
-                        nb, o = buf["norm"], 8
-                        for k, key in enumerate(NORM_KEYS):
-                            ck[key] = dict(mean=nb[o:o + K[k]].clone(), var=nb[o + K[k]:o + 2 * K[k]].clone(), count=float(nb[2 + k]),
-                                           eps=norm_spec[0], until=norm_spec[1])
-                            o += 2 * K[k]
-                    tmp = path + ".tmp%d" % os.getpid()
-                    tj.append(time.perf_counter())
-                    if side is not None:
-                        torch.save(side, side_path + ".tmp%d" % os.getpid())
-                        os.replace(side_path + ".tmp%d" % os.getpid(), side_path)
-                    torch.save(ck, tmp)
-                    tj.append(time.perf_counter())
-                    os.replace(tmp, path)
-                    tj.append(time.perf_counter())
-                    if os.environ.get("HGYM_SAVE_TRACE"):
-                        sys.stderr.write("writer job %s: event %.2f, cut %.2f, torch.save %.2f, rename %.2f ms\n" % (
-                            os.path.basename(path), *[(b - a) * 1e3 for a, b in zip(tj, tj[1:])]))
-                finally:
-                    buf["busy"].set()
-            _WRITER.submit(job)
+            if getattr(self, "_snapshot", None) is None:
+                self._snapshot = ckpt.Snapshot(alg.net)
+            shot = self._snapshot.take(alg.net, alg.actor_critic, self.env if env_state else None)
+            side = dict(env=shot["env"], **extra) if env_state else None
+            ckpt.WRITER.submit(lambda: ckpt.write_snapshot(shot, type(alg.optimizer).HYPER, it, infos, path, side))
             if wait:
-                _WRITER.wait()
+                ckpt.WRITER.wait()
         self.save_time_s = getattr(self, "save_time_s", 0.0) + (time.time() - t0)     # host time the TRAINING thread spent in checkpoints (bench.py reports it)
 
     def wait_for_saves(self):
         """Block until every checkpoint handed to the background writer is on disk (re-raises a writer error)."""
         t0 = time.time()
-        _WRITER.wait()
+        ckpt.WRITER.wait()
         self.save_time_s = getattr(self, "save_time_s", 0.0) + (time.time() - t0)
 
     def load(self, path, load_optimizer=True, env_state=None):
@@ -974,69 +789,38 @@ class OnPolicyRunner:
         torch's global generator, which the sidecar does not carry; a data-parallel run says once that it ignores the sidecar and resumes as without it.
         The log sink's rings and the host's rewbuffer / lenbuffer are logging state, zeroed at every learn(): the first log blocks
         after a resume average over fewer episodes.  An evaluation env (set_eval_env) is not touched.  Without a sidecar: as ever."""
-        _WRITER.wait()                      # a checkpoint this process is still writing
-        loaded = None
-        if isinstance(self.alg.actor_critic, StudentTeacher):
+        ckpt.WRITER.wait()                      # a checkpoint this process is still writing
+        alg, ac, loaded = self.alg, self.alg.actor_critic, None
+        if isinstance(ac, StudentTeacher):
             # a distillation run: a checkpoint without `teacher.*` entries is the TEACHER's PPO checkpoint (StudentTeacher.load_state_dict):
             # its weights become the teacher, and nothing else of it -- no optimiser state, no env sidecar, iteration 0
             loaded = torch.load(path, map_location=self.device)
             if not any(k.startswith("teacher.") for k in loaded["model_state_dict"]):
-                self.alg.actor_critic.load_state_dict(loaded["model_state_dict"])
+                ac.load_state_dict(loaded["model_state_dict"])
                 self.current_learning_iteration = 0
                 return loaded.get("infos")
-        side_path = None
-        if env_state is not False:
-            side_path = env_state if isinstance(env_state, (str, os.PathLike)) else self.env_state_path(path)
-            if not isinstance(env_state, (str, os.PathLike)) and not os.path.exists(side_path):
-                side_path = None
-        if side_path is not None and getattr(self.alg, "_world", 1) > 1:
-            if not self._warned_env_state:
-                self._warned_env_state = True
-                print("exact_resume: %s is not loaded in a data-parallel run (world size %d); resuming as without it"
-                      % (os.path.basename(side_path), self.alg._world))
-            side_path = None
-        side = None
+        side, side_path = None, ckpt.resolve_sidecar(path, env_state, getattr(alg, "_world", 1), self)
         if side_path is not None:
             side = torch.load(side_path, map_location="cpu")
-            if int(side["world_size"]) != 1:
-                raise ValueError("env state: world_size is %d in the sidecar; exact resume covers one rank" % int(side["world_size"]))
-            if int(side["num_steps_per_env"]) != int(self.num_steps_per_env):
-                raise ValueError("env state: num_steps_per_env is %d in the sidecar, %d here" % (int(side["num_steps_per_env"]), self.num_steps_per_env))
-            self.env.check_state_dict(side["env"])      # (a sidecar that does not fit this env: refused before anything is changed)
+            ckpt.check_sidecar(side, self.num_steps_per_env, self.env)      # (refused before anything is changed)
         if loaded is None:
             loaded = torch.load(path, map_location=self.device)
-        # a checkpoint of the other noise parametrisation: its first entry is another quantity under another name
-        msd, mine = loaded["model_state_dict"], getattr(self.alg.actor_critic, "noise_std_type", "scalar")
-        theirs = "log" if "log_std" in msd else ("scalar" if "std" in msd else mine)
-        if theirs != mine:
-            raise RuntimeError("%s was trained with noise_std_type=\"%s\" (its model_state_dict has `%s`); this policy was built with "
-                               "noise_std_type=\"%s\"" % (os.path.basename(str(path)), theirs, "log_std" if theirs == "log" else "std", mine))
-        # a checkpoint with the normaliser's statistics for a policy without normalisation, or the reverse: another function of the
-        # observations under the same parameter names
-        has_norm = bool(getattr(self.alg.actor_critic, "empirical_normalization", False))
-        _check_norm_keys(loaded, has_norm, os.path.basename(str(path)), getattr(self.alg.actor_critic, "obs_norm_spec", None))
-        # a checkpoint of a run with RND for a run without it, or the reverse, or the per-env average of another number of envs: refused by name
-        rnd = getattr(self.alg, "_rnd", None)
-        from .rnd import check_state_dict as _check_rnd_state
-        _check_rnd_state(loaded.get(RND_STATE_KEY), os.path.basename(str(path)), rnd is not None, getattr(rnd, "num_envs", None))
+        rnd = getattr(alg, "_rnd", None)
+        ckpt.check_compatible(loaded, ac, rnd, os.path.basename(str(path)))
         if rnd is not None:
             rnd.load_rnd_state_dict(loaded[RND_STATE_KEY])
-        if has_norm:        # the statistics first, then the parameters (whose load refolds the first layers with them)
-            self.alg.net.load_norm_state(dict(obs=loaded[NORM_KEYS[0]], critic_obs=loaded[NORM_KEYS[1]]))
-        self.alg.actor_critic.load_state_dict(loaded["model_state_dict"])
+        if getattr(ac, "empirical_normalization", False):        # the statistics first, then the parameters (whose load refolds the first layers with them)
+            alg.net.load_norm_state(dict(obs=loaded[NORM_KEYS[0]], critic_obs=loaded[NORM_KEYS[1]]))
+        ac.load_state_dict(loaded["model_state_dict"])
         if load_optimizer or (side is not None and self.cfg.get("exact_resume", False)):
-            self.alg.optimizer.load_state_dict(loaded["optimizer_state_dict"])
+            alg.optimizer.load_state_dict(loaded["optimizer_state_dict"])
+        self.current_learning_iteration = loaded["iter"] if side is None else int(side["iterations_done"])
+        if hasattr(alg, "seek"):
+            alg.seek(self.current_learning_iteration, self.num_steps_per_env)
         if side is not None:
-            self.current_learning_iteration = int(side["iterations_done"])
-            if hasattr(self.alg, "seek"):
-                self.alg.seek(self.current_learning_iteration, self.num_steps_per_env)
             self.env.load_state_dict(side["env"])
             self._keep_episode_lengths = True
-            return loaded["infos"]
-        self.current_learning_iteration = loaded["iter"]
-        if hasattr(self.alg, "seek"):
-            self.alg.seek(self.current_learning_iteration, self.num_steps_per_env)
-        if hasattr(self.env, "seek"):       # the env's draw streams (commands, pushes, noise, resets) continue as well
+        elif hasattr(self.env, "seek"):       # the env's draw streams (commands, pushes, noise, resets) continue as well
             self.env.seek(self.current_learning_iteration, self.num_steps_per_env)
         return loaded["infos"]
 

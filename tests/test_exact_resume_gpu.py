@@ -389,7 +389,7 @@ def test_off_means_off(tmp_path, monkeypatch):
     u.wait_for_saves()
     files = sorted(os.listdir(u.log_dir))
     assert not [f for f in files if f.startswith("envstate")] and {"model_0.pt", "model_2.pt", "model_3.pt"} <= set(files)
-    assert getattr(u, "_save_pin", None) is not None and all("env" not in b for b in u._save_pin)      # nothing pinned for it either
+    assert getattr(u, "_snapshot", None) is not None and all("env" not in b for b in u._snapshot.sets)      # nothing pinned for it either
     # load() without a sidecar: the env keeps its state, except counters[0] (seek)
     r = _runner(None, exact=False, presteps=3)
     before = r.env.state_dict()
@@ -462,11 +462,11 @@ def test_synchronous_and_background_sidecars_agree(tmp_path, monkeypatch):
     for n in ("sync", "async"):
         assert set(torch.load(str(tmp_path / ("model_%s.pt" % n)), map_location="cpu")) == KEYS4
     # the training thread only enqueues: the pinned sets are pinned, and the snapshot copies do not synchronise
-    assert all(t.is_pinned() for bset in u._save_pin for t in bset["env"].values())
+    assert all(t.is_pinned() for bset in u._snapshot.sets for t in bset["env"].values())
     torch.cuda.synchronize()
     torch.cuda.set_sync_debug_mode("error")
     try:
-        u.env.state_dict(out=u._save_pin[0]["env"])
+        u.env.state_dict(out=u._snapshot.sets[0]["env"])
     finally:
         torch.cuda.set_sync_debug_mode(0)
     torch.cuda.synchronize()
