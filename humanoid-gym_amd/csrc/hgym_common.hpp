@@ -128,7 +128,9 @@ enum : uint32_t {
     SLOT_TERRAIN = 10,    // x,y: spawn jitter of custom origins, z: terrain-level redraw
     SLOT_OBS = 16,        // 16..27: 47 observation-noise normals (pairs)
     SLOT_PHYS = 32,       // 32..47: synthetic physics
-    SLOT_POLICY = 64      // 64..66: 12 policy-sampling normals
+    SLOT_POLICY = 64,     // 64..66: 12 policy-sampling normals
+    SLOT_PERTURB = 128    // 128..128 + ceil(width / 4) - 1: the normals of one perturbed row (hgym_perturb_rows; env word = the storage row,
+                          // step word = the Adam step count)
 };
 
 // standard normal number `i` of a block of normals starting at slot `base` (2 normals per uniform pair)

@@ -1215,6 +1215,22 @@ struct FbMirror {
 };
 constexpr int FB_MIRROR_LDS = 64 * 12 * 4 + 2 * 16 * 4;      // 64 rows x 12 floats, then act_src[16] (ints) and act_sign[16]
 
+// The smoothness regulariser (hgym_ppo_grad_smooth): an argument of the SM instantiations only (hgym_update_smooth.hip,
+// hgym_update_act_smooth.hip), so that FbLoss and FbMirror keep their layouts.  Two detached targets and one weight per row of the MINIBATCH
+// (contiguous, no gather): d mu += gT w (mu - tnext) + gS (mu - tnear).  A term whose g is 0 is off and its pointers are not read.
+// An SM tile never carries the mirror loss, so the partial row's regression slot and the pad behind it are free for its two squared errors.
+struct FbSmooth {
+    const float* tnext;        // (M, A) fp32: mu of every row's successor (the temporal pre-pass)
+    const float* tnear;        // (M, A) fp32: mu of every row's perturbed copy (the spatial pre-pass)
+    const float* weight;       // (M,) 0 where the row has no successor, else 1
+    float gT, gS;              // 2 * coef / (M * A)
+    int stage;                 // 1: the launch has FB_SMOOTH_LDS more bytes of dynamic LDS behind fb_lds_bytes(net), and the tile's targets and
+                               // weights are staged there by the wavefronts idle in the third layer
+};
+constexpr int LP_SMOOTH_T = LP_MIRROR, LP_SMOOTH_S = LP_MIRROR + 1;      // sum w |mu - tnext|^2, sum |mu - tnear|^2
+static_assert(LP_SMOOTH_S < LOSS_PARTIALS, "the partial row has 32 floats");
+constexpr int FB_SMOOTH_LDS = 2 * 64 * 12 * 4 + 64 * 4;      // tnext 64 x 12, tnear 64 x 12, weight 64
+
 // Behaviour cloning (hgym_bc_grad): an argument of the BC instantiations only (hgym_update_bc.hip, hgym_update_act_bc.hip).  The head
 // regresses mu on target[row] -- a storage column gathered through FwdArgs::idx like every other loss input -- and nothing else: no
 // surrogate, no entropy, no KL, no d std.  The tile's 64 target rows are staged in the actor's loss-input region of LDS (fb_lds_lin:
@@ -1258,10 +1274,12 @@ inline int fb_lds_bytes(const int32_t* dims) {
 // ML: the actor's head also forms the mirror loss (FbMirror, *Mr); off by default, `if constexpr`: every other instantiation is what it was
 // BC: the actor's head forms the behaviour-cloning regression instead of the PPO loss (FbBC, *Bc); off by default, `if constexpr` and
 // lambdas of its own (l2idle_bc, head_bc) that no other instantiation calls
-template <int G1, bool AUX = false, bool XB16 = false, bool VU = false, bool GA = false, bool ML = false, bool BC = false>
+// SM: the actor's head also forms the smoothness regulariser (FbSmooth, *Sm); off by default, `if constexpr` like ML
+template <int G1, bool AUX = false, bool XB16 = false, bool VU = false, bool GA = false, bool ML = false, bool BC = false, bool SM = false>
 __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const FusedNet& n, bool is_actor, char* smem,
-                                        const FbMirror* Mr = nullptr, const FbBC* Bc = nullptr) {
+                                        const FbMirror* Mr = nullptr, const FbBC* Bc = nullptr, const FbSmooth* Sm = nullptr) {
     static_assert(!BC || (!AUX && !ML && !VU), "the behaviour-cloning head is the actor's alone");
+    static_assert(!SM || (!AUX && !ML && !VU && !BC), "the smoothness head is the actor's alone, and never beside the mirror loss");
     constexpr int BM = 64, NW = 16, D = 2, MB = BM / 16;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 15, q = lane >> 4;
@@ -1336,6 +1354,30 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
                 if (j >= 208 && j < 224) mt[64 * 12 + 16 + tj] = gv;
             }
         }
+        if constexpr (SM) {
+            // the tile's two target blocks and its weights (contiguous rows of the minibatch) -> LDS behind the other loss inputs: lanes
+            // 0 .. 191 the temporal targets, 192 .. 383 the spatial ones, 384 .. 447 the weights.  A term that is off is neither read nor
+            // staged (its pointers may be null): the load goes to the other term's block instead, the store is skipped.  Invariant: at
+            // least one term is on -- with both off the host launches the plain tile, never this kernel -- so `src` below is never null.
+            // Rows of 12 floats: l2idle runs under `pre` only, which for the actor means A == 12 (FB_SMOOTH_LDS is sized for that).
+            // (Lanes 384 .. 511 also issue the 16-byte load, of row 63, and drop it: unconditional loads, conditional stores, as above.)
+            if (Sm->stage) {
+                float* st = lin + FB_LIN_ACTOR * 64;
+                const bool onT = Sm->gT > 0.0f, onS = Sm->gS > 0.0f;
+                const bool second = j >= 192;
+                const int jj = second ? j - 192 : j;
+                const int rw = jj / 3 < 63 ? jj / 3 : 63, k = jj % 3;
+                int mrow = m0 + rw;
+                mrow = mrow < a.M ? mrow : a.M - 1;
+                const float* src = (second ? onS : !onT) ? Sm->tnear : Sm->tnext;
+                const F4 vt = *reinterpret_cast<const F4*>(src + (int64_t)mrow * 12 + 4 * k);
+                int wrow = m0 + (j & 63);
+                wrow = wrow < a.M ? wrow : a.M - 1;
+                const float wv = onT ? Sm->weight[wrow] : 0.0f;
+                if (j < 384 && (second ? onS : onT)) *reinterpret_cast<F4*>(st + (second ? 64 * 12 : 0) + rw * 12 + 4 * k) = vt;
+                if (j >= 384 && j < 448) st[2 * 64 * 12 + (j & 63)] = wv;
+            }
+        }
         if (is_actor) {
             // round 1: (row, quad k): actions 0..2, old mu 3..5, old sigma 6..7; round 2: old sigma quad 2, advantage, old log-prob.
             // Every load is issued before the first LDS write.
@@ -1364,7 +1406,7 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
         const int rl = hw * 16 + r;                 // row of the tile
         const int64_t row = rowidx[rl];
         float g[4] = {0.f, 0.f, 0.f, 0.f};
-        constexpr int NPART = ML ? 12 : 11;         // ML: [11] the mirror loss's squared error
+        constexpr int NPART = ML ? 12 : (SM ? 13 : 11);         // ML: [11] the mirror loss's squared error; SM: [11], [12] the two terms'
         float part[NPART];
 #pragma unroll
         for (int k = 0; k < NPART; ++k) part[k] = 0.0f;
@@ -1452,6 +1494,40 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
                 se += __shfl_xor(se, 16, 64); se += __shfl_xor(se, 32, 64);
                 if (q == 0) part[11] = se;
             }
+            if constexpr (SM) {
+                // the smoothness terms: gT w (mu - tnext) + gS (mu - tnear) joins d mu (and the head-bias sum), the two squared errors the
+                // tile's partial sums; nothing else moves.  A term that is off reads nothing.
+                const bool staged = pre && Sm->stage;
+                const float* st = lin + FB_LIN_ACTOR * 64;
+                const int mrow = valid ? m : a.M - 1;
+                const bool onT = Sm->gT > 0.0f, onS = Sm->gS > 0.0f;
+                const float wgt = onT ? (staged ? st[2 * 64 * 12 + rl] : Sm->weight[mrow]) : 0.0f;
+                float seT = 0.0f, seS = 0.0f;
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (4 * q + e < A) {
+                        if (onT) {
+                            const float t = staged ? st[rl * 12 + 4 * q + e] : Sm->tnext[(int64_t)mrow * A + 4 * q + e];
+                            const float dm = out[e] - t;
+                            if (valid) {
+                                g[e] += Sm->gT * wgt * dm;
+                                seT += wgt * dm * dm;
+                            }
+                        }
+                        if (onS) {
+                            const float t = staged ? st[64 * 12 + rl * 12 + 4 * q + e] : Sm->tnear[(int64_t)mrow * A + 4 * q + e];
+                            const float dm = out[e] - t;
+                            if (valid) {
+                                g[e] += Sm->gS * dm;
+                                seS += dm * dm;
+                            }
+                        }
+                        if (valid) part[7 + e] = g[e];
+                    }
+                seT += __shfl_xor(seT, 16, 64); seT += __shfl_xor(seT, 32, 64);
+                seS += __shfl_xor(seS, 16, 64); seS += __shfl_xor(seS, 32, 64);
+                if (q == 0) { part[11] = seT; part[12] = seS; }
+            }
         } else {
             const float ret = pre ? lin[rl * 2] : L.returns[row], vold = pre ? lin[rl * 2 + 1] : L.values[row];
             const float v = out[0];
@@ -1495,6 +1571,7 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
             if (is_actor) {
                 if (q == 0) { w[LP_SURROGATE] = part[0]; w[LP_ENTROPY] = part[1]; w[LP_KL] = part[2]; }
                 if constexpr (ML) { if (q == 0) w[LP_MIRROR] = part[11]; }
+                if constexpr (SM) { if (q == 0) { w[LP_SMOOTH_T] = part[11]; w[LP_SMOOTH_S] = part[12]; } }
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
                     if (4 * q + e < 12) { w[LP_DSTD + 4 * q + e] = part[3 + e]; w[LP_DBIAS_MU + 4 * q + e] = part[7 + e]; }
@@ -1583,7 +1660,7 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
     }
     __syncthreads();          // dZ3 tile and the per-wave sums are in LDS; H0 sits in P, H1 in Q, H2 in its own buffer
     if (tid < LOSS_PARTIALS) {
-        const bool mine = BC ? ((tid >= LP_DBIAS_MU && tid < LP_DBIAS_V) || tid == LP_MIRROR) : AUX ? tid == LP_AUX : (is_actor ? ((tid != LP_VALUE && tid < LP_DBIAS_V) || (ML && tid == LP_MIRROR)) : (tid == LP_VALUE || tid == LP_DBIAS_V));
+        const bool mine = BC ? ((tid >= LP_DBIAS_MU && tid < LP_DBIAS_V) || tid == LP_MIRROR) : AUX ? tid == LP_AUX : (is_actor ? ((tid != LP_VALUE && tid < LP_DBIAS_V) || (ML && tid == LP_MIRROR) || (SM && (tid == LP_SMOOTH_T || tid == LP_SMOOTH_S))) : (tid == LP_VALUE || tid == LP_DBIAS_V));
         if (mine) L.partials[(int64_t)blockIdx.x * LOSS_PARTIALS + tid] = red[tid] + red[LOSS_PARTIALS + tid] + red[2 * LOSS_PARTIALS + tid] + red[3 * LOSS_PARTIALS + tid];
     }
     // ---- dZ chain on the resident tile
@@ -1700,6 +1777,37 @@ int32_t launch_mlp_fb_mirror_form(const FwdArgs& fb0, const FbLoss& fl, const Fb
     if (g1 == 1) return shadow ? launch_mlp_fb_mirror_one<1, true, GA>(fb, fl, mr, tiles, lds, s) : launch_mlp_fb_mirror_one<1, false, GA>(fb, fl, mr, tiles, lds, s);
     if (g1 == 2) return shadow ? launch_mlp_fb_mirror_one<2, true, GA>(fb, fl, mr, tiles, lds, s) : launch_mlp_fb_mirror_one<2, false, GA>(fb, fl, mr, tiles, lds, s);
     if (g1 == 3) return shadow ? launch_mlp_fb_mirror_one<3, true, GA>(fb, fl, mr, tiles, lds, s) : launch_mlp_fb_mirror_one<3, false, GA>(fb, fl, mr, tiles, lds, s);
+    return HGYM_E_UNSUPPORTED;
+}
+
+// The ACTOR's update tile with the smoothness regulariser in its head (hgym_ppo_grad_smooth): one kernel per first hidden width, input
+// form and activation form, the actor alone -- every other net's tiles run through the kernels they always had, as beside the mirror
+// tiles.  hgym_update_smooth.hip holds the ELU(1) kernels, hgym_update_act_smooth.hip the generic ones.
+template <int G1, bool XB16, bool GA>
+__global__ __launch_bounds__(1024) void mlp_fb_smooth_kernel(const FwdArgs a, const FbLoss L, const FbSmooth sm) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    fb_body<G1, false, XB16, false, GA, false, false, true>(a, L, a.net[0], true, smem, nullptr, nullptr, &sm);
+}
+template <int G1, bool XB16, bool GA>
+int32_t launch_mlp_fb_smooth_one(const FwdArgs& fb, const FbLoss& fl, const FbSmooth& sm, int tiles, size_t lds, hipStream_t s) {
+    const int32_t rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&mlp_fb_smooth_kernel<G1, XB16, GA>), lds, "mlp_fb_smooth_kernel");
+    if (rc) return rc;
+    hipLaunchKernelGGL((mlp_fb_smooth_kernel<G1, XB16, GA>), dim3(tiles), dim3(1024), lds, s, fb, fl, sm);
+    return HGYM_OK;
+}
+template <bool GA>
+int32_t launch_mlp_fb_smooth_form(const FwdArgs& fb0, const FbLoss& fl, const FbSmooth& sm0, bool shadow, int tiles, hipStream_t s) {
+    FwdArgs fb = fb0;
+    fb.net0 = 0;
+    fb.nets = 1;
+    FbSmooth sm = sm0;
+    size_t lds = (size_t)fb_lds_bytes(fb.net[0]);
+    sm.stage = lds + FB_SMOOTH_LDS <= FB_LDS_LIMIT ? 1 : 0;      // no room: the head reads the targets and the weight from memory
+    if (sm.stage) lds += FB_SMOOTH_LDS;
+    const int g1 = fb.net[0].layer[0].NB / 16;         // first hidden width 256 / 512 / 768
+    if (g1 == 1) return shadow ? launch_mlp_fb_smooth_one<1, true, GA>(fb, fl, sm, tiles, lds, s) : launch_mlp_fb_smooth_one<1, false, GA>(fb, fl, sm, tiles, lds, s);
+    if (g1 == 2) return shadow ? launch_mlp_fb_smooth_one<2, true, GA>(fb, fl, sm, tiles, lds, s) : launch_mlp_fb_smooth_one<2, false, GA>(fb, fl, sm, tiles, lds, s);
+    if (g1 == 3) return shadow ? launch_mlp_fb_smooth_one<3, true, GA>(fb, fl, sm, tiles, lds, s) : launch_mlp_fb_smooth_one<3, false, GA>(fb, fl, sm, tiles, lds, s);
     return HGYM_E_UNSUPPORTED;
 }
 

@@ -167,6 +167,91 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(const LossArgs a) {
         red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
 
+// ------------------------------------------------------------------------------------------------ smoothness (hgym_ppo_grad_smooth)
+// ppo_loss_smooth_kernel: the layer-by-layer path's head with the smoothness regulariser.  Like an ML instantiation it runs BEHIND the plain
+// ppo_loss_kernel on the same arguments and overwrites only what the terms change: d mu (row-major and transposed), the LP_DBIAS_MU
+// partials, and the two squared-error partials LP_SMOOTH_T / LP_SMOOTH_S.  A kernel of its own and not one more template parameter of
+// ppo_loss_kernel: a parameter would rename every existing instantiation, and LossArgs -- their kernel argument -- keeps its layout.  The
+// value-loss form does not enter (d V is the plain kernel's).  A term whose g is 0 is off and its pointers are not read.
+struct LossSmooth {
+    const float* tnext;          // [B][A] mu of every row's successor (the temporal pre-pass), rows of the MINIBATCH
+    const float* tnear;          // [B][A] mu of every row's perturbed copy (the spatial pre-pass)
+    const float* weight;         // [B] 0 where the row has no successor, else 1
+    float gT, gS;                // 2 * coef / (B * A)
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void ppo_loss_smooth_kernel(const LossArgs a, const LossSmooth sm) {
+    __shared__ float red[4][16];
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int B = a.b.B, A = a.A;
+    const float invB = 1.0f / (float)B;
+    float acc[14];               // [0 .. 12) d mu, [12] w |mu - tnext|^2, [13] |mu - tnear|^2
+#pragma unroll
+    for (int k = 0; k < 14; ++k) acc[k] = 0.0f;
+    T* dmu = (T*)a.dmu;
+    T* dmuT = (T*)a.dmuT;
+    const bool onT = sm.gT > 0.0f, onS = sm.gS > 0.0f;
+    if (i < B) {
+        const int64_t r = a.b.idx[i];
+        const float adv = a.b.advantages[r], lpold = a.b.logp[r];
+        float lp = 0.0f;
+        float diff[16], sg[16], rowm[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            diff[j] = 0.0f;
+            sg[j] = 1.0f;
+            rowm[j] = 0.0f;
+            if (j >= A) continue;
+            const float m = a.mu[(int64_t)i * A + j];
+            const float s = m * 0.0f + a.std_[j];
+            const float d = a.b.actions[r * A + j] - m;
+            rowm[j] = m;
+            diff[j] = d;
+            sg[j] = s;
+            lp += -(d * d) / (2.0f * s * s) - logf(s) - 0.9189385332046727f;
+        }
+        const float ratio = expf(lp - lpold);
+        const float s1 = -adv * ratio;
+        const float s2 = -adv * clampf(ratio, 1.0f - a.clip, 1.0f + a.clip);
+        const float in_range = (ratio >= 1.0f - a.clip && ratio <= 1.0f + a.clip) ? 1.0f : 0.0f;
+        const float w1 = s1 > s2 ? 1.0f : (s1 == s2 ? 0.5f : 0.0f);
+        const float d_lp = (-adv) * (w1 + (1.0f - w1) * in_range) * invB * ratio;
+        const float wgt = onT ? sm.weight[i] : 0.0f;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            if (j >= A) continue;
+            const float s = sg[j], d = diff[j];
+            float g_mu = d_lp * d / (s * s);
+            if (onT) {
+                const float dm = rowm[j] - sm.tnext[(int64_t)i * A + j];
+                g_mu += sm.gT * wgt * dm;
+                acc[12] += wgt * dm * dm;
+            }
+            if (onS) {
+                const float dm = rowm[j] - sm.tnear[(int64_t)i * A + j];
+                g_mu += sm.gS * dm;
+                acc[13] += dm * dm;
+            }
+            if (j < 12) acc[j] = g_mu;
+            dmu[(int64_t)i * a.ld_dmu + j] = from_f32<T>(g_mu);
+            dmuT[(int64_t)j * a.ld_t + i] = from_f32<T>(g_mu);
+        }
+    } else if (i < a.Bp) {       // the contraction padding of the gradient stays zero
+        for (int j = 0; j < A; ++j) dmuT[(int64_t)j * a.ld_t + i] = from_f32<T>(0.0f);
+    }
+#pragma unroll
+    for (int k = 0; k < 14; ++k) {
+        float s = acc[k];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = s;
+    }
+    __syncthreads();
+    const int k = threadIdx.x;
+    if (k < 14) a.partials[(int64_t)blockIdx.x * LOSS_PARTIALS + (k < 12 ? LP_DBIAS_MU + k : LP_SMOOTH_T + (k - 12))] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
+}
+
 // ------------------------------------------------------------------------------------------------ behaviour cloning (hgym_bc_grad)
 // bc_loss_kernel: the regression head of the layer-by-layer path, one thread per sample: e = mu - target[idx[i]], d mu into the actor's
 // last dY / dYT (the operands of the backward that follows), the sample's loss terms and d mu into the block's partial row (LP_MIRROR --

@@ -36,6 +36,14 @@ int32_t launch_mlp_fb_bc(const FwdArgs& fb, const FbLoss& fl, const FbBC& bc, bo
 int32_t launch_mlp_fb_act_bc(const FwdArgs& fb, const FbLoss& fl, const FbBC& bc, bool shadow, int tiles, hipStream_t s);
 int32_t launch_bc_loss(const BcLossArgs& a, bool bf16, int nblocks, hipStream_t s);
 int32_t launch_bc_scalars(const BcScalArgs& a, hipStream_t s);
+// hgym_update_smooth.hip, hgym_update_act_smooth.hip, hgym_loss_smooth.hip, hgym_smooth.hip: hgym_ppo_grad_smooth's kernels -- the actor's
+// tiles / the layer-by-layer head with the smoothness regulariser, the perturbed rows of the spatial pre-pass, the minibatch's sums
+int32_t launch_mlp_fb_smooth(const FwdArgs& fb, const FbLoss& fl, const FbSmooth& sm, bool shadow, int tiles, hipStream_t s);
+int32_t launch_mlp_fb_act_smooth(const FwdArgs& fb, const FbLoss& fl, const FbSmooth& sm, bool shadow, int tiles, hipStream_t s);
+int32_t launch_ppo_loss_smooth(const LossArgs& a, const LossSmooth& sm, bool bf16, int nblocks, hipStream_t s);
+int32_t launch_perturb_rows(int64_t M, int width, const float* src, int64_t ld_src, const int64_t* idx, const float* noise_std, uint64_t seed,
+                            const double* opt_state, float* dst, int64_t ld_dst, hipStream_t s);
+int32_t launch_smooth_sums(int nblocks, int B, int A, const float* partials, const float* weight, double* sums, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------ layouts
 struct LayerLayout {
@@ -892,6 +900,28 @@ struct NetBase {
     }
 };
 
+// hgym_ppo_grad_smooth's pre-passes on either path, ahead of everything else of the call: the targets of the two terms under the current
+// parameters, forward only (no gradient through a target).  Both read fp32 rows, as the mirror loss's pre-pass does.  The perturbation comes
+// first of all: it reads opt_state[HGYM_OPT_STEP], which the loss-scalar workgroup of this very call may advance.
+inline int smooth_ld(int num_obs) { return (num_obs + 3) / 4 * 4; }
+template <class R>
+static int32_t smooth_prepass(R& r, const HgymBatch& b, const HgymSmooth& sm) {
+    const int B = b.B, A = r.cfg.num_actions;
+    if (sm.spatial_coef > 0.0f) {
+        const int ld = smooth_ld(r.cfg.num_obs);
+        int32_t rc = launch_perturb_rows(B, r.cfg.num_obs, b.obs, r.cfg.num_obs, b.idx, sm.noise_std, sm.seed, r.net.opt_state, sm.rows, ld, r.s);
+        if (rc) return rc;
+        rc = r.forward(0, B, sm.rows, ld, nullptr, sm.target_near, A, false);
+        if (rc) return rc;
+    }
+    if (sm.temporal_coef > 0.0f) {
+        const int32_t rc = r.forward(0, B, b.obs, r.cfg.num_obs, sm.next_idx, sm.target_next, A, false);
+        if (rc) return rc;
+    }
+    return HGYM_OK;
+}
+inline bool smooth_on(const HgymSmooth* sm) { return sm && (sm->temporal_coef > 0.0f || sm->spatial_coef > 0.0f); }
+
 // The layer-by-layer path: every dense product through gemm_nt_kernel in the operand precision T, plus the packs, transposes and
 // row sums around it.
 template <typename T>
@@ -1019,14 +1049,20 @@ struct GemmPath : NetBase {
 
     // part 1 (the second half of hgym_ppo_grad_part) has nothing left to do: part 0 does everything (the caller's first bucket goes out
     // complete, just later)
-    int32_t grad(const HgymPPOConfig& ppo, const HgymBatch& b, int part) {
+    // sm (hgym_ppo_grad_smooth): the smoothness regulariser joins d mu; null or both coefficients 0: off, the launches of hgym_ppo_grad
+    int32_t grad(const HgymPPOConfig& ppo, const HgymBatch& b, int part, const HgymSmooth* sm = nullptr) {
         if (part == 1) return HGYM_OK;
         const int B = b.B, A = cfg.num_actions;
         float* mu = at<float>(w.net[0].out_f32);
         float* val = at<float>(w.net[1].out_f32);
         // (no zeroing of net.grads: ppo_scalars_kernel writes std's gradient, reduce_slabs_kernel every weight and bias segment)
         const bool mirror = ppo.mirror_coef > 0.0f;
+        const bool smooth = smooth_on(sm);
         int32_t rc = HGYM_OK;
+        if (smooth) {
+            rc = smooth_prepass(*this, b, *sm);
+            if (rc) return rc;
+        }
         if (mirror) {     // the pre-pass: the partner rows' raw mu under the current parameters (forward only: no gradient through the target)
             rc = forward(0, B, b.obs, cfg.num_obs, b.pair_idx, b.mirror_target, A, false);
             if (rc) return rc;
@@ -1071,6 +1107,14 @@ struct GemmPath : NetBase {
         if (mirror) {      // behind it: d mu with the term, the LP_DBIAS_MU / LP_MIRROR partials (hgym_loss.hpp)
             const int32_t rc_ml = launch_ppo_loss_mirror(a, sizeof(T) == 2, ppo.value_loss_unclipped != 0, nblocks, s);
             if (rc_ml) return rc_ml;
+        }
+        if (smooth) {      // behind it: d mu with the two terms, the LP_DBIAS_MU / LP_SMOOTH_* partials (hgym_loss.hpp), then the sums
+            const float gs = 2.0f / ((float)B * (float)A);
+            const LossSmooth ls = {sm->target_next, sm->target_near, sm->next_weight, gs * sm->temporal_coef, gs * sm->spatial_coef};
+            int32_t rc_sm = launch_ppo_loss_smooth(a, ls, sizeof(T) == 2, nblocks, s);
+            if (rc_sm) return rc_sm;
+            rc_sm = launch_smooth_sums(nblocks, B, A, at<float>(w.partials), sm->next_weight, sm->sums, s);
+            if (rc_sm) return rc_sm;
         }
         prof_end(HGYM_PROF_LOSS, s, (double)B * (4.0 * (5 * A + 6) + (double)sizeof(T) * (2 * A + 2)));
         HG_CHECK_LAUNCH("ppo_loss_kernel");
@@ -1354,7 +1398,8 @@ struct FusedPath : NetBase {
 
     // part < 0: the whole minibatch gradient.  part 0 / 1: the two halves of hgym_ppo_grad_part -- 0 leaves std's and the actor's
     // gradient final, 1 the critic's, the auxiliary head's and the KL slot.
-    int32_t grad(const HgymPPOConfig& ppo, const HgymBatch& b, int part) {
+    // sm (hgym_ppo_grad_smooth): the smoothness regulariser joins d mu; null or both coefficients 0: off, the launches of hgym_ppo_grad
+    int32_t grad(const HgymPPOConfig& ppo, const HgymBatch& b, int part, const HgymSmooth* sm = nullptr) {
         const int B = b.B, A = cfg.num_actions;
         const int64_t critic_off = w.net[1].layer[0].w_off;
         const int Mp = (int)round_up(B, w.SE);
@@ -1376,6 +1421,11 @@ struct FusedPath : NetBase {
             // the target).  It gathers the fp32 rows, not their bf16 shadow: the forward tiles that gather by index from a shadow exist in
             // the update kernels only, and the shadow is bf16(fp32 row) exactly -- the same bits reach the first layer either way.
             const int32_t rc_pre = forward(0, B, b.obs, cfg.num_obs, b.pair_idx, b.mirror_target, A, false);
+            if (rc_pre) return rc_pre;
+        }
+        const bool smooth = smooth_on(sm);
+        if (smooth) {
+            const int32_t rc_pre = smooth_prepass(*this, b, *sm);
             if (rc_pre) return rc_pre;
         }
         {   // forward + PPO loss + dZ chain of both nets: ONE launch (hgym_fused.hpp: mlp_fb_kernel)
@@ -1417,11 +1467,19 @@ struct FusedPath : NetBase {
             fb.dbg = phase_buffer((int64_t)tiles * nets);
             prof_begin(HGYM_PROF_MLP_FWD, s);
             int32_t rc_fb = HGYM_OK;
-            if (mirror) {
-                // the actor's tiles through the kernels with the mirror loss in their head (their own launch), every other net's through
-                // the kernels they always had, from net 1 on
-                const FbMirror mr = {b.mirror_target, b.mirror_act_src, b.mirror_act_sign, 2.0f * ppo.mirror_coef / ((float)B * (float)A), 0};
-                rc_fb = act_is_elu1(w.act) ? launch_mlp_fb_mirror(fb, fl, mr, shadow, tiles, s) : launch_mlp_fb_act_mirror(fb, fl, mr, shadow, tiles, s);
+            if (mirror || smooth) {
+                // the actor's tiles through the kernels with the mirror loss (or the smoothness regulariser) in their head (their own
+                // launch), every other net's through the kernels they always had, from net 1 on
+                if (mirror) {
+                    const FbMirror mr = {b.mirror_target, b.mirror_act_src, b.mirror_act_sign, 2.0f * ppo.mirror_coef / ((float)B * (float)A), 0};
+                    rc_fb = act_is_elu1(w.act) ? launch_mlp_fb_mirror(fb, fl, mr, shadow, tiles, s) : launch_mlp_fb_act_mirror(fb, fl, mr, shadow, tiles, s);
+                } else {
+                    const float gs = 2.0f / ((float)B * (float)A);
+                    const FbSmooth fs = {sm->target_next, sm->target_near, sm->next_weight, gs * sm->temporal_coef, gs * sm->spatial_coef, 0};
+                    rc_fb = act_is_elu1(w.act) ? launch_mlp_fb_smooth(fb, fl, fs, shadow, tiles, s) : launch_mlp_fb_act_smooth(fb, fl, fs, shadow, tiles, s);
+                    if (rc_fb) return rc_fb;
+                    rc_fb = launch_smooth_sums(tiles, B, A, at<float>(w.partials), sm->next_weight, sm->sums, s);
+                }
                 if (rc_fb) return rc_fb;
                 if (act_is_elu1(w.act)) {
                     FwdArgs rest = fb;
@@ -1775,6 +1833,40 @@ int32_t hgym_ppo_grad(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const 
         HG_REQUIRE(net->grads && net->opt_state, HGYM_E_BADARG, "null grads / opt_state");
         rc = check_batch(R.w, ppo, batch);
         return rc ? rc : R.grad(*ppo, *batch, -1);
+    });
+}
+
+int32_t hgym_ppo_grad_smooth(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const HgymNet* net, const HgymBatch* batch,
+                             const HgymSmooth* smooth, void* stream) {
+    // every refusal below comes before anything is launched
+    HG_REQUIRE(cfg && ppo && net && batch && smooth, HGYM_E_BADARG, "hgym_ppo_grad_smooth: null cfg / ppo / net / batch / smooth");
+    const float lt = smooth->temporal_coef, ls = smooth->spatial_coef;
+    // (written so that a NaN fails it)
+    HG_REQUIRE(lt >= 0.0f && lt < INFINITY && ls >= 0.0f && ls < INFINITY, HGYM_E_BADARG,
+               "HgymSmooth.temporal_coef=%g / spatial_coef=%g must be finite and >= 0 (0: that term is off)", (double)lt, (double)ls);
+    HG_REQUIRE(!(ppo->mirror_coef > 0.0f), HGYM_E_BADARG, "hgym_ppo_grad_smooth with HgymPPOConfig.mirror_coef > 0: the two heads do not combine");
+    HG_REQUIRE(ppo->world_size <= 1, HGYM_E_BADARG, "hgym_ppo_grad_smooth with world_size=%d: one rank only", ppo->world_size);
+    if (lt > 0.0f || ls > 0.0f) {
+        HG_REQUIRE(smooth->sums && ((uintptr_t)smooth->sums & 7) == 0, HGYM_E_BADARG, "HgymSmooth.sums must be non-null and 8-byte aligned");
+        if (lt > 0.0f) {
+            HG_REQUIRE(smooth->next_idx && smooth->next_weight && smooth->target_next, HGYM_E_BADARG,
+                       "HgymSmooth.temporal_coef > 0 needs next_idx, next_weight and target_next");
+            HG_REQUIRE(((uintptr_t)smooth->target_next & 15) == 0 && ((uintptr_t)smooth->next_idx & 7) == 0 && ((uintptr_t)smooth->next_weight & 3) == 0,
+                       HGYM_E_BADARG, "HgymSmooth.target_next must be 16-byte aligned (next_idx 8, next_weight 4)");
+        }
+        if (ls > 0.0f) {
+            HG_REQUIRE(smooth->noise_std && smooth->target_near && smooth->rows, HGYM_E_BADARG,
+                       "HgymSmooth.spatial_coef > 0 needs noise_std, target_near and rows");
+            HG_REQUIRE((((uintptr_t)smooth->target_near | (uintptr_t)smooth->rows) & 15) == 0 && ((uintptr_t)smooth->noise_std & 3) == 0, HGYM_E_BADARG,
+                       "HgymSmooth.target_near and rows must be 16-byte aligned (noise_std 4)");
+        }
+    }
+    return run(cfg, net, stream, [&](auto& R) -> int32_t {
+        int32_t rc = check_ppo(ppo);
+        if (rc) return rc;
+        HG_REQUIRE(net->grads && net->opt_state, HGYM_E_BADARG, "null grads / opt_state");
+        rc = check_batch(R.w, ppo, batch);
+        return rc ? rc : R.grad(*ppo, *batch, -1, smooth);
     });
 }
 

@@ -5,6 +5,40 @@ from .env_buffers import EnvBuffers, default_env_config, log_stats_summary
 from .net import NetBuffers, make_net_config, make_ppo_config, make_batch, activation_spec, diag_from_block, DIAG_KEYS, opt_summary
 from .net import check_obs_norm, norm_layout
 from .net import make_bc_config, make_bc_batch, BC_LOSS_TYPES
+from .net import make_smooth, smooth_ld
+
+
+def smooth_pairs(idx, dones, N, next_idx, next_weight):
+    """hgym_smooth_pairs on the current stream: next_idx[b] = idx[b] + N, next_weight[b] = 0 where dones[idx[b]] else 1.  idx, next_idx int64
+    (B,), next_weight float32 (B,), dones uint8 / bool over the stored rows (flat); contiguous device tensors."""
+    import ctypes as C
+    import torch
+    assert idx.dtype == torch.int64 and next_idx.dtype == torch.int64 and next_weight.dtype == torch.float32
+    assert dones.dtype in (torch.uint8, torch.bool) and dones.is_contiguous()
+    assert idx.is_contiguous() and next_idx.is_contiguous() and next_weight.is_contiguous()
+    assert next_idx.numel() >= idx.numel() and next_weight.numel() >= idx.numel()
+    check(lib.hgym_smooth_pairs(int(idx.numel()), int(N), _lib.i64ptr(idx), _lib.u8ptr(dones), _lib.i64ptr(next_idx), _lib.fptr(next_weight),
+                                C.c_void_p(torch.cuda.current_stream().cuda_stream)), "hgym_smooth_pairs")
+
+
+def perturb_rows(src, noise_std, seed, opt_state, dst, idx=None):
+    """hgym_perturb_rows on the current stream: dst[m, c] = src[row, c] + noise_std[c] * z, row = idx[m] (idx=None: m), z the Philox normal
+    of (seed, step = opt_state[OPT_STEP], row, slot 128 + c // 4).  src (rows, width) float32 with contiguous rows; dst (M, ld) float32,
+    ld = its row stride, a multiple of 4 and >= smooth_ld(width), 16-byte aligned; noise_std float32 (width,); opt_state float64 (16,)."""
+    import ctypes as C
+    import torch
+    assert src.dim() == 2 and dst.dim() == 2 and src.dtype == torch.float32 and dst.dtype == torch.float32
+    assert (src.shape[1] == 1 or src.stride(1) == 1) and (dst.shape[1] == 1 or dst.stride(1) == 1)
+    width = int(src.shape[1])
+    assert noise_std.dtype == torch.float32 and noise_std.is_contiguous() and noise_std.numel() == width
+    assert opt_state.dtype == torch.float64 and opt_state.is_contiguous() and opt_state.numel() >= _lib.OPT_STATE
+    assert idx is None or (idx.dtype == torch.int64 and idx.is_contiguous())
+    M = int(dst.shape[0]) if idx is None else int(idx.numel())
+    assert dst.shape[0] >= M and (idx is not None or src.shape[0] >= M)
+    ld = lambda t: max(int(t.stride(0)), int(t.shape[1]))
+    check(lib.hgym_perturb_rows(M, width, _lib.fptr(src), ld(src), _lib.i64ptr(idx), _lib.fptr(noise_std), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                _lib.f64ptr(opt_state), _lib.fptr(dst), ld(dst), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+          "hgym_perturb_rows")
 
 
 def mirror_rows(src, dst, src_col, sign, zero_to=None):

@@ -181,9 +181,20 @@ class RndConfig(C.Structure):
                 ("final_step", C.c_int64), ("schedule", C.c_int32), ("normalize", C.c_int32)]
 
 
+SLOT_PERTURB = 128       # hgym_common.hpp slot map: 128 .. 128 + ceil(width / 4) - 1 = the normals of one row of hgym_perturb_rows
+
+
+class Smooth(C.Structure):
+    """HgymSmooth: the coefficients, the successor map, the perturbation and the caller-owned scratch of hgym_ppo_grad_smooth."""
+    _fields_ = [("temporal_coef", C.c_float), ("spatial_coef", C.c_float), ("next_idx", c_i64_p), ("next_weight", c_float_p),
+                ("noise_std", c_float_p), ("seed", C.c_uint64), ("target_next", c_float_p), ("target_near", c_float_p),
+                ("rows", c_float_p), ("sums", c_f64_p)]
+
+
 STRUCTS = dict(HgymEnvConfig=EnvConfig, HgymStrided=Strided, HgymSimTensors=SimTensors, HgymEnvState=EnvState,
                HgymEnvOut=EnvOut, HgymEnvNoise=EnvNoise, HgymNetConfig=NetConfig, HgymPPOConfig=PPOConfig,
-               HgymNet=Net, HgymBatch=Batch, HgymObsShadow=ObsShadow, HgymComm=Comm, HgymBCConfig=BCConfig, HgymRndConfig=RndConfig)
+               HgymNet=Net, HgymBatch=Batch, HgymObsShadow=ObsShadow, HgymComm=Comm, HgymBCConfig=BCConfig, HgymRndConfig=RndConfig,
+               HgymSmooth=Smooth)
 
 # every symbol include/hgym.h declares: name -> (restype, argtypes)
 _P = C.POINTER
@@ -260,6 +271,10 @@ SYMBOLS = {
     "hgym_ppo_grad": (C.c_int32, [_P(NetConfig), _P(PPOConfig), _P(Net), _P(Batch), C.c_void_p]),
     "hgym_ppo_grad_part": (C.c_int32, [_P(NetConfig), _P(PPOConfig), _P(Net), _P(Batch), C.c_int32, C.c_void_p]),
     "hgym_bc_grad": (C.c_int32, [_P(NetConfig), _P(BCConfig), _P(Net), _P(Batch), c_float_p, c_f64_p, C.c_void_p]),
+    "hgym_smooth_pairs": (C.c_int32, [C.c_int64, C.c_int64, c_i64_p, c_u8_p, c_i64_p, c_float_p, C.c_void_p]),
+    "hgym_perturb_rows": (C.c_int32, [C.c_int64, C.c_int32, c_float_p, C.c_int64, c_i64_p, c_float_p, C.c_uint64, c_f64_p, c_float_p, C.c_int64,
+                                      C.c_void_p]),
+    "hgym_ppo_grad_smooth": (C.c_int32, [_P(NetConfig), _P(PPOConfig), _P(Net), _P(Batch), _P(Smooth), C.c_void_p]),
     "hgym_net_param_offset": (C.c_int64, [_P(NetConfig), C.c_int32]),
     "hgym_ppo_apply": (C.c_int32, [_P(NetConfig), _P(PPOConfig), _P(Net), C.c_void_p]),
     "hgym_prof_enable": (C.c_int32, [C.c_int32]),

@@ -316,6 +316,11 @@ class NetBuffers:
     def ppo_grad(self, ppo, batch):
         L.check(L.lib.hgym_ppo_grad(C.byref(self.cfg), C.byref(ppo), C.byref(self.struct), C.byref(batch), self.stream()), "hgym_ppo_grad")
 
+    def ppo_grad_smooth(self, ppo, batch, smooth):
+        """hgym_ppo_grad_smooth: hgym_ppo_grad with the smoothness regulariser (make_smooth); both coefficients 0: hgym_ppo_grad itself."""
+        L.check(L.lib.hgym_ppo_grad_smooth(C.byref(self.cfg), C.byref(ppo), C.byref(self.struct), C.byref(batch), C.byref(smooth), self.stream()),
+                "hgym_ppo_grad_smooth")
+
     def ppo_grad_part(self, ppo, batch, part):
         """hgym_ppo_grad in two halves (data-parallel update): after part 0 `grads_ext[:bucket_split]` (std | actor, the larger
         bucket) is final, after part 1 `grads_ext[bucket_split:]` (critic | auxiliary head | KL slot)."""
@@ -387,6 +392,30 @@ def make_batch(obs, priv, actions, values, advantages, returns, logp, mu, sigma,
         b.pair_idx, b.mirror_act_src, b.mirror_act_sign = L.i64ptr(pair_idx), C.cast(src.data_ptr(), C.POINTER(C.c_int32)), L.fptr(sign)
         b.mirror_target, b.mirror_sums = L.fptr(target), L.f64ptr(sums)
     return b
+
+
+def smooth_ld(num_obs):
+    """Leading dimension (floats) of HgymSmooth.rows: the observation width rounded up to 4, so that every row starts on 16 bytes."""
+    return (int(num_obs) + 3) // 4 * 4
+
+
+def make_smooth(temporal_coef=0.0, spatial_coef=0.0, next_idx=None, next_weight=None, noise_std=None, seed=0, target_next=None,
+                target_near=None, rows=None, sums=None):
+    """HgymSmooth of hgym_ppo_grad_smooth.  Coefficients: finite and >= 0 (ValueError otherwise); a term at 0 is off and its tensors may be
+    None.  Device tensors the caller keeps alive: next_idx int64 (B,), next_weight fp32 (B,) (hgym.smooth_pairs writes both); noise_std fp32
+    (num_obs,); target_next / target_near fp32 scratch of at least B * num_actions elements; rows fp32 scratch of at least B *
+    smooth_ld(num_obs) elements; sums float64 (4,), zeroed by the caller.  Scratch must be 16-byte aligned (the library refuses otherwise)."""
+    import math
+    lt, ls = float(temporal_coef), float(spatial_coef)
+    for name, v in (("temporal_coef", lt), ("spatial_coef", ls)):
+        if not (v >= 0.0 and math.isfinite(v)):
+            raise ValueError("%s=%r: must be finite and >= 0" % (name, v))
+    for t, dt in ((next_idx, torch.int64), (next_weight, torch.float32), (noise_std, torch.float32), (target_next, torch.float32),
+                  (target_near, torch.float32), (rows, torch.float32), (sums, torch.float64)):
+        assert t is None or (t.dtype == dt and t.is_contiguous())
+    assert sums is None or sums.numel() >= 4
+    return L.Smooth(lt, ls, L.i64ptr(next_idx), L.fptr(next_weight), L.fptr(noise_std), int(seed) & 0xFFFFFFFFFFFFFFFF, L.fptr(target_next),
+                    L.fptr(target_near), L.fptr(rows), L.f64ptr(sums))
 
 
 BC_LOSS_TYPES = ("mse", "huber")

@@ -63,6 +63,10 @@ class Distillation(PPO):
         if self.rnd is not None:
             from . import rnd as rnd_module
             rnd_module.check_setup(distillation=True)
+        if self.smoothness is not None:
+            from . import smoothness as smooth_module
+            if smooth_module.parse_config(self.smoothness, self.actor_critic.num_actor_obs) is not None:
+                smooth_module.check_setup(distillation=True)
         self.check_setup(self.actor_critic, num_transitions_per_env, self.gradient_length, self._world, self.symmetry,
                          self.mirror_loss_coef, self.advantage_normalization)
         # one "minibatch" is one slice: gradient_length * N rows (PPO.init_storage sizes the net's max_batch from it)

@@ -159,12 +159,13 @@ def _split_algorithm_cfg(alg_cfg):
     off), not a parameter of the reference's PPO: it is taken out here and becomes PPO.symmetry.  The mirror loss's keys (SYMMETRY_KEYS)
     are taken out as well; _split_symmetry_cfg reads them.  So are the advantage normalisation's (ADVANTAGE_KEYS; _split_advantage_cfg)."""
     kwargs = dict(alg_cfg)
-    for k in SYMMETRY_KEYS + ADVANTAGE_KEYS + (RND_KEY,):
+    for k in SYMMETRY_KEYS + ADVANTAGE_KEYS + (RND_KEY, SMOOTH_KEY):
         kwargs.pop(k, None)
     return kwargs, bool(kwargs.pop("symmetry", False))
 
 
 ADVANTAGE_KEYS = ("advantage_normalization", "normalize_advantage_per_mini_batch")      # neither is a parameter of PPO.__init__
+SMOOTH_KEY = "smoothness_cfg"      # the smoothness regulariser's block (humanoid.algo.ppo.smoothness.parse_config); absent or None: off
 RND_KEY = "rnd_cfg"      # rsl_rl's Random Network Distillation block (humanoid.algo.ppo.rnd.parse_config); absent or None: off
 
 
@@ -255,6 +256,13 @@ class OnPolicyRunner:
             self.alg.rnd = RandomNetworkDistillation(self.env.num_obs, num_critic_obs, self.alg_cfg[RND_KEY],
                                                      critic_frame=getattr(env_cfg, "single_num_privileged_obs", None),
                                                      activation=getattr(actor_critic, "activation", None))
+        if self.alg_cfg.get(SMOOTH_KEY) is not None:      # the smoothness regulariser; read by init_storage below
+            from . import smoothness as smooth_module
+            sc = dict(self.alg_cfg[SMOOTH_KEY])
+            if sc.get("noise_std") is None:      # the sensor noise the env itself models, per stacked column
+                sc["noise_std"] = smooth_module.env_noise_std(getattr(self.env, "cfg", None), getattr(self.env, "noise_scale_vec", None),
+                                                              self.env.num_obs)
+            self.alg.smoothness = sc
         self.num_steps_per_env = self.cfg["num_steps_per_env"]
         self.save_interval = self.cfg["save_interval"]
         self.alg.init_storage(self.env.num_envs, self.num_steps_per_env, [self.env.num_obs], [self.env.num_privileged_obs],
@@ -532,7 +540,7 @@ class OnPolicyRunner:
         """compute_returns() + update() -> (mean_value_loss, mean_surrogate_loss), None where not read back (PPO.update_capturable)."""
         def launches(sync=False):
             with torch.inference_mode():
-                if getattr(self.alg, "_rnd", None) is not None:      # (RND reads the state behind the last transition)
+                if getattr(self.alg, "_rnd", None) is not None or getattr(self.alg, "_smooth", None) is not None:      # (RND and the smoothness term read the state behind the last transition)
                     self.alg.compute_returns(critic_obs, last_obs=obs)
                 else:
                     self.alg.compute_returns(critic_obs)
@@ -649,6 +657,8 @@ class OnPolicyRunner:
         o = hgym.opt_summary(pin["opt"][slot], snap["aux"])
         self.alg.last_denoise_loss = o["denoise_loss"]
         self.alg.last_mirror_loss = self.alg.mirror_loss_from(pin["opt"][slot])
+        if hasattr(self.alg, "smoothness_from"):      # the smoothness regulariser's sums ride at the block's very end
+            self.alg.last_smoothness = self.alg.smoothness_from(pin["opt"][slot])
         if hasattr(self.alg, "rnd_log_from"):      # RND: the predictor's loss and the reward pass's sums ride at the block's end
             self.alg.rnd_log_from(pin["opt"][slot])
         if hasattr(self.alg, "behavior_loss_from"):      # Distillation: the loss rides in the same block
@@ -689,6 +699,10 @@ class OnPolicyRunner:
             scal("Loss/denoise_mse", self.alg.last_denoise_loss, locs["it"])
         if getattr(self.alg, "_mirror_coef", 0.0) > 0.0 and getattr(self.alg, "last_mirror_loss", None) is not None:
             scal("Loss/mirror", self.alg.last_mirror_loss, locs["it"])
+        smooth_log = getattr(self.alg, "last_smoothness", None)
+        if smooth_log is not None:
+            scal("Loss/smooth_temporal", smooth_log["temporal"], locs["it"])
+            scal("Loss/smooth_spatial", smooth_log["spatial"], locs["it"])
         if behavior is not None:
             scal("Loss/behavior", behavior, locs["it"])
         rnd_log = getattr(getattr(self.alg, "_rnd", None), "last_log", None)

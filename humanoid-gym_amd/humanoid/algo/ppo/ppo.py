@@ -93,6 +93,12 @@ class PPO:
     # hgym_rnd_rewards), and update() follows every minibatch's Adam step with one step of the predictor on the same rows.  One rank, no
     # symmetry augmentation, not with Distillation (ValueError from init_storage).  Read once, in init_storage.  DESIGN.md section 27.
     rnd = None
+    # the smoothness regulariser on the policy's mean, after CAPS: None, or a dict {temporal_coef, spatial_coef, noise_std, noise_scale, seed}
+    # (humanoid.algo.ppo.smoothness.parse_config) -- update() then calls hgym_ppo_grad_smooth in place of hgym_ppo_grad: lamT pulls mu(s_t)
+    # towards mu(s_t+1) over rows whose episode went on, lamS pulls mu(s) towards mu(s + noise_std z), both targets detached.  One rank, no
+    # PPO.symmetry, not with Distillation (ValueError from init_storage).  Read once, in init_storage.  `last_smoothness`: {temporal, spatial,
+    # valid_fraction} of the last update.  DESIGN.md section 28.
+    smoothness = None
 
     def __init__(self, actor_critic, num_learning_epochs=1, num_mini_batches=1, clip_param=0.2, gamma=0.998, lam=0.95,
                  value_loss_coef=1.0, entropy_coef=0.0, learning_rate=1e-3, max_grad_norm=1.0, use_clipped_value_loss=True,
@@ -156,6 +162,10 @@ class PPO:
         if self.rnd is not None:
             from . import rnd as rnd_module
             rnd_module.check_setup(self._world, self.symmetry if self._augment else None, self._augment)
+        from . import smoothness as smooth_module
+        self._smooth = smooth_module.parse_config(self.smoothness, self.actor_critic.num_actor_obs, torch.initial_seed())
+        if self._smooth is not None:
+            smooth_module.check_setup(self._world, self.symmetry)      # (Distillation.init_storage refuses it ahead of this)
         if self._symmetry is not None:
             self.storage.enable_mirror(self._symmetry)      # (before enable_shadow and before anything binds a slot's address)
         ac = self.actor_critic
@@ -207,6 +217,9 @@ class PPO:
         if coef > 0.0:      # the pre-pass's output (one minibatch of raw partner means) and the two sums behind the per-update loss sums
             self._mirror_target = torch.zeros(max(mb, 1) * ac.num_actions, dtype=torch.float32, device=self.device)
             self._mirror_sums = torch.zeros(2, dtype=torch.float64, device=self.device)
+        self.last_smoothness = None
+        if self._smooth is not None:      # the successor map of a whole permutation, the two pre-passes' outputs, the perturbed rows, the four sums
+            self.storage.enable_smoothness(self.num_mini_batches * mb, mb, ac.num_actor_obs, ac.num_actions, self._smooth["noise_std"])
         self._sample_step = torch.zeros(1, dtype=torch.int64, device=self.device)
         self._perm_seed = (torch.initial_seed() * 0x9E3779B97F4A7C15 + 0xABCD + 104729 * self._rank) & 0xFFFFFFFFFFFFFFFF
         self._perm_draws = 0
@@ -379,6 +392,13 @@ class PPO:
         "obs" when the rollout did not write the storage's slot T (RandomNetworkDistillation.reward_pass)."""
         st, deferred = self.storage, self._deferred_ready       # deferred_values() has evaluated the bootstrap observation with the rest
         last_values = st.last_values if deferred else self.actor_critic.evaluate(last_critic_obs)
+        if self._smooth is not None and self._smooth["temporal_coef"] > 0.0 and not self._slot_T_written:
+            # a rollout that copied its observations in (add_transitions) has not written slot T: the temporal term's successor of the last
+            # step's rows is the bootstrap observation, which only the caller holds
+            if last_obs is None:
+                raise RuntimeError("PPO.smoothness: the rollout did not write the storage's slot T; call compute_returns(last_critic_obs, "
+                                   "last_obs=<the env's last observations>)")
+            st._obs_all[st.num_transitions_per_env].copy_(last_obs)
         if self._rnd is not None:      # rewards += intrinsic, ahead of GAE on both paths (the deferred path's time-out bootstrap is added behind it)
             self._rnd.reward_pass(st, last_critic_obs, last_obs, self._slot_T_written)
         st.compute_returns(last_values, self.gamma, self.lam, stats_hook=self._adv_stats, time_outs=st.time_outs if deferred else None,
@@ -413,6 +433,9 @@ class PPO:
                 # the mirror loss (its coefficient is also part of _ppo_cfg's bytes above), whether the batch is doubled, the scratch the launches name
                 self._mirror_coef, self._augment,
                 None if self._mirror_target is None else (self._mirror_target.data_ptr(), self._mirror_sums.data_ptr()),
+                # the smoothness regulariser: its coefficients and seed, and the scratch the launches name (ahead of RND's entry, which tests read from the end)
+                None if self._smooth is None else (self._smooth["temporal_coef"], self._smooth["spatial_coef"], self._smooth["seed"])
+                + tuple(t.data_ptr() for t in self.storage.smooth_buffers()),
                 # RND: its nets, block and configuration bytes (ahead of the three entries tests read from the end)
                 None if self._rnd is None else (id(self._rnd), id(self._rnd.nets[0]), id(self._rnd.nets[1]), self._rnd.block.data_ptr(),
                                                 bytes(C.string_at(C.addressof(self._rnd.rnd_cfg), C.sizeof(self._rnd.rnd_cfg)))),
@@ -478,7 +501,14 @@ class PPO:
             pair = mirror_pair_rows(perm, T, N)
             mirror = st._mirror["act"] + (self._mirror_target, self._mirror_sums)
             self._mirror_sums[0:2] = 0.0      # (a slice: a fill kernel, as below)
+        smooth = self._smooth
+        if smooth is not None:      # one pass over the whole permutation: every epoch reuses the slices, as the advantage pass's are
+            sb = st._smooth
+            hgym.smooth_pairs(perm, st.dones.view(-1), N, sb["next_idx"], sb["next_weight"])
+            sb["sums"][0:4] = 0.0      # (a slice: a fill kernel)
         cols = st.batch_columns()
+        if smooth is not None:      # the T + 1 observation slots are ONE allocation under the column's base pointer: next_idx reaches into slot T
+            assert cols[0].data_ptr() == st._obs_all.data_ptr() and st._obs_all.is_contiguous()
         if self._adv_mode == "minibatch":
             # the slices below partition perm once for every epoch: all minibatches standardised in one pass, into the column the batches name
             cols = cols[:4] + (st.normalize_minibatch_advantages(perm, self.num_mini_batches),) + cols[5:]
@@ -498,7 +528,14 @@ class PPO:
                     batch = hgym.make_batch(*cols, idx, pair_idx=pair[i * mb:(i + 1) * mb], mirror=mirror, **sh)
                 else:
                     batch = hgym.make_batch(*cols, idx, **sh)
-                net.ppo_grad(self._ppo_cfg, batch)
+                if smooth is not None:
+                    on_t = smooth["temporal_coef"] > 0.0
+                    net.ppo_grad_smooth(self._ppo_cfg, batch, hgym.make_smooth(
+                        smooth["temporal_coef"], smooth["spatial_coef"], next_idx=sb["next_idx"][i * mb:(i + 1) * mb] if on_t else None,
+                        next_weight=sb["next_weight"][i * mb:(i + 1) * mb], noise_std=sb["noise_std"], seed=smooth["seed"],
+                        target_next=sb["target_next"], target_near=sb["target_near"], rows=sb["rows"], sums=sb["sums"]))
+                else:
+                    net.ppo_grad(self._ppo_cfg, batch)
                 if self._obs_norm is not None:
                     net.norm_unfold_grad()      # first-layer gradients: of the folded operands -> of the master parameters, ahead of the exchange and the norm
                 if dist_utils.active():
@@ -532,6 +569,7 @@ class PPO:
         o = self.log_block().cpu()             # the one host read-back of the update
         self.check_comm()                      # (the stream is idle now: reading the exchange's status costs one small copy)
         self.last_mirror_loss = self.mirror_loss_from(o)
+        self.last_smoothness = self.smoothness_from(o)
         self.rnd_log_from(o)
         o = hgym.opt_summary(o, self._ppo_cfg.aux_coef > 0.0)
         self.last_denoise_loss = o["denoise_loss"]
@@ -541,8 +579,10 @@ class PPO:
         """What a log block reads after an update, as ONE device tensor (one copy to the host): opt_state, behind it the mirror
         loss's two sums when that loss is on, and last RND's tail when that is on."""
         parts = [self.net.opt_state] + ([] if self._mirror_sums is None else [self._mirror_sums])
-        if getattr(self, "_rnd", None) is not None:      # the predictor loss's two sums and the head of the reward pass's block, last
+        if getattr(self, "_rnd", None) is not None:      # the predictor loss's two sums and the head of the reward pass's block
             parts.append(self._rnd.log_tail())
+        if getattr(self, "_smooth", None) is not None:      # the regulariser's four sums, behind what was there before
+            parts.append(self.storage._smooth["sums"])
         return parts[0] if len(parts) == 1 else torch.cat(parts)
 
     def rnd_log_from(self, block):
@@ -550,7 +590,18 @@ class PPO:
         rnd = getattr(self, "_rnd", None)
         if rnd is None:
             return None
-        return rnd.log_from(block[block.numel() - rnd.LOG_DOUBLES:])
+        end = block.numel() - (4 if getattr(self, "_smooth", None) is not None else 0)
+        return rnd.log_from(block[end - rnd.LOG_DOUBLES:end])
+
+    def smoothness_from(self, block):
+        """{temporal, spatial, valid_fraction} from a host copy of log_block(): the mean plain MSE per minibatch of either term and the share
+        of drawn rows with a successor; None when the regulariser is off."""
+        if getattr(self, "_smooth", None) is None:
+            return None
+        t, s, w, n = (float(x) for x in block[block.numel() - 4:])
+        mb = self.storage._smooth["target_next"].numel() // self.actor_critic.num_actions
+        n = max(n, 1.0)
+        return dict(temporal=t / n, spatial=s / n, valid_fraction=w / (mb * n))
 
     def mirror_loss_from(self, block):
         """The mean mirror MSE per minibatch from a host copy of log_block(); None when the loss is off."""

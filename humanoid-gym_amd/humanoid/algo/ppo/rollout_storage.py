@@ -90,6 +90,24 @@ class RolloutStorage:
         hgym.adv_normalize_minibatches(perm, adv, self.advantages_mb, segments, self._adv_mb_scratch)
         return self.advantages_mb
 
+    _smooth = None      # the smoothness regulariser's buffers (enable_smoothness), None without it
+
+    def enable_smoothness(self, perm_len, mb, num_obs, num_actions, noise_std):
+        """Native extension (PPO.smoothness): everything hgym_smooth_pairs and hgym_ppo_grad_smooth name, allocated once (torch.zeros: nothing
+        is allocated during an update) -- next_idx / next_weight for a whole permutation of perm_len rows, noise_std (num_obs; zeros when
+        the spatial term is off), and for one minibatch of mb rows target_next, target_near (mb x num_actions) and rows (mb x the width
+        rounded up to 4), then the four sums."""
+        import hgym
+        z = lambda n, dtype=torch.float32: torch.zeros(max(int(n), 1), dtype=dtype, device=self.device)
+        ns = z(num_obs)
+        if noise_std is not None:
+            ns.copy_(torch.tensor(noise_std, dtype=torch.float32))
+        self._smooth = dict(next_idx=z(perm_len, torch.int64), next_weight=z(perm_len), noise_std=ns, target_next=z(mb * num_actions),
+                            target_near=z(mb * num_actions), rows=z(mb * hgym.smooth_ld(num_obs)), sums=z(4, torch.float64))
+
+    def smooth_buffers(self):
+        return () if self._smooth is None else tuple(self._smooth.values())
+
     def enable_rnd(self, num_states, num_outputs):
         """Native extension (PPO.rnd): rnd_states (T + 1, N, S) -- a contiguous copy of the chosen observation columns of slots 0 .. T (the
         net kernels gather rows without a leading dimension) --, rnd_target (T + 1, N, K), rnd_pred (T, N, K) -- the predictor over slots

@@ -32,7 +32,10 @@ HGYM_ADV_NORM=minibatch|none|batch sets `algorithm.advantage_normalization` the 
 
 HGYM_RND=<weight> sets `algorithm.rnd_cfg = {"weight": <weight>}` the same way: Random Network Distillation with its defaults and that
 constant weight -- an intrinsic exploration reward added to the stored rewards ahead of GAE (PPO.rnd); checkpoints
-carry rnd_state_dict.  Unset: off."""
+carry rnd_state_dict.  Unset: off.
+
+HGYM_SMOOTH=<lamT>[,<lamS>] sets `algorithm.smoothness_cfg = {"temporal_coef": lamT, "spatial_coef": lamS}`: the smoothness regulariser on
+the policy's mean (PPO.smoothness), the spatial term's noise the env's own noise_scale_vec * noise_level.  Unset: off."""
 import os
 import sys
 
@@ -62,6 +65,9 @@ def train(args):
         task_registry.get_cfgs(args.task)[1].algorithm.advantage_normalization = os.environ["HGYM_ADV_NORM"]
     if os.environ.get("HGYM_RND"):
         task_registry.get_cfgs(args.task)[1].algorithm.rnd_cfg = {"weight": float(os.environ["HGYM_RND"])}
+    if os.environ.get("HGYM_SMOOTH"):
+        lam = [float(x) for x in os.environ["HGYM_SMOOTH"].split(",")]
+        task_registry.get_cfgs(args.task)[1].algorithm.smoothness_cfg = {"temporal_coef": lam[0], "spatial_coef": lam[1] if len(lam) > 1 else 0.0}
     ppo_runner, train_cfg = task_registry.make_alg_runner(env=env, name=args.task, args=args, **({} if rank == 0 else {"log_root": None}))
     ppo_runner.learn(num_learning_iterations=train_cfg.runner.max_iterations, init_at_random_ep_len=True)
     if os.environ.get("HGYM_TRAIN_SIGNATURE"):      # tests: a signature of this rank's final parameters (replicas must agree bit for bit)

@@ -71,7 +71,9 @@ extern "C" {
                              *    (same version, later: hgym_bc_grad and HgymBCConfig -- one behaviour-cloning minibatch of the actor, rsl_rl's
                              *    Distillation; no layout changes)
                              *    (same version, later: hgym_rnd_block_init, hgym_rnd_rewards and HgymRndConfig -- Random Network Distillation's
-                             *    reward pass; no layout changes) */
+                             *    reward pass; no layout changes)
+                             *    (same version, later: hgym_smooth_pairs, hgym_perturb_rows, hgym_ppo_grad_smooth and HgymSmooth -- the smoothness
+                             *    regulariser on the policy's mean; no layout changes) */
 
 enum {
     HGYM_OK = 0,
@@ -999,6 +1001,52 @@ typedef struct HgymBCConfig {
 } HgymBCConfig;
 int32_t hgym_bc_grad(const HgymNetConfig* cfg, const HgymBCConfig* bc, const HgymNet* net, const HgymBatch* batch, const float* target,
                      double* sums, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The smoothness regulariser (header v9, no layout change): a penalty on the policy's mean itself, after CAPS
+ * (Mysore et al. 2021).  With B rows, A actions, r_b = idx[b] and mu_b = mu(obs[r_b]) as the update computes it:
+ *   temporal   tT_b = mu(obs[next_idx[b]]),                 w_b = next_weight[b]        (hgym_smooth_pairs: r_b + N, 0 where dones[r_b])
+ *   spatial    tS_b = mu(obs[r_b] + noise_std (.) z_b),     z_b[c] = normal c of the Philox block at slot 128 (hgym_perturb_rows)
+ *   L_s = temporal_coef / (B A) sum_b w_b |mu_b - tT_b|^2 + spatial_coef / (B A) sum_b |mu_b - tS_b|^2
+ *   d mu_b += 2 / (B A) (temporal_coef w_b (mu_b - tT_b) + spatial_coef (mu_b - tS_b))
+ * Both targets are formed under the current parameters by forward-only passes over fp32 rows: no gradient flows through them.  Nothing
+ * but d mu, and hence the actor's gradients, differs from hgym_ppo_grad: d std, the critic, the auxiliary head, the KL slot and the loss
+ * sums of opt_state keep their bits.
+ *
+ * hgym_smooth_pairs: next_idx[b] = idx[b] + N, next_weight[b] = dones[idx[b]] ? 0 : 1 for b in [0, B); one launch, capturable.  The
+ *   rollout storage keeps T + 1 observation slots of N rows, so idx[b] + N is always a stored row.
+ * hgym_perturb_rows: dst[m][c] = src[row][c] + noise_std[c] * z for m in [0, M), c in [0, width), row = idx ? idx[m] : m; z is normal
+ *   number c of the Philox block (key = seed, env word = (uint32) row, step word = (int64) opt_state[HGYM_OPT_STEP] read on the device,
+ *   slots 128 .. 128 + ceil(width / 4) - 1), one fused multiply-add.  A column with noise_std[c] == 0 is copied bit for bit.  src rows of
+ *   ld_src >= width floats, 4-byte aligned; dst rows of ld_dst floats, ld_dst a multiple of 4 and >= width rounded up to 4, dst 16-byte
+ *   aligned.  Columns [width, width rounded up to 4) of dst are written as +0.0, columns behind those are not touched.  One launch,
+ *   capturable; HGYM_E_BADARG with nothing launched for a NULL src / noise_std / opt_state / dst, M < 1, width < 1 or a bad leading
+ *   dimension / alignment.
+ * hgym_ppo_grad_smooth: hgym_ppo_grad with the regulariser.  First of all the spatial pre-pass (hgym_perturb_rows over obs[idx] into
+ *   `rows`, the actor's forward over them into target_near; skipped at spatial_coef == 0), then the temporal one (the actor's forward
+ *   gathered through next_idx into target_next; skipped at temporal_coef == 0), then hgym_ppo_grad's launches with the actor's loss head
+ *   replaced.  The perturbation reads opt_state[HGYM_OPT_STEP] before the call's own loss scalars can advance it.  With both coefficients 0
+ *   the launches and the bits are hgym_ppo_grad's.  HGYM_E_BADARG with nothing launched: a negative, NaN or infinite coefficient; a
+ *   pointer needed by a term that is on (or sums) NULL; misaligned scratch; ppo->mirror_coef > 0; ppo->world_size > 1. */
+typedef struct HgymSmooth {
+    float temporal_coef;          /* >= 0, finite; 0: the temporal term is off and next_idx, next_weight, target_next are not read */
+    float spatial_coef;           /* >= 0, finite; 0: the spatial term is off and noise_std, seed, target_near, rows are not read */
+    const int64_t* next_idx;      /* (B,) the successor's storage row of every row of idx */
+    const float* next_weight;     /* (B,) 0 where the row has no successor, else 1 */
+    const float* noise_std;       /* (num_obs,) per-column standard deviation of the perturbation, raw observation units */
+    uint64_t seed;                /* Philox key of the perturbation */
+    float* target_next;           /* caller-owned scratch, (B, num_actions) fp32, 16-byte aligned */
+    float* target_near;           /* caller-owned scratch, (B, num_actions) fp32, 16-byte aligned */
+    float* rows;                  /* caller-owned scratch, (B, ld) fp32 with ld = num_obs rounded up to 4, 16-byte aligned: receives the
+                                     perturbed rows (the padding columns +0.0) */
+    double* sums;                 /* four device doubles the caller zeroes: [0] += sum_b w_b |mu_b - tT_b|^2 / (B A), [1] += sum_b |mu_b -
+                                     tS_b|^2 / (B A), [2] += sum_b w_b (whenever next_weight is not NULL, either term on), [3] += 1 */
+} HgymSmooth;
+int32_t hgym_smooth_pairs(int64_t B, int64_t N, const int64_t* idx, const uint8_t* dones, int64_t* next_idx, float* next_weight, void* stream);
+int32_t hgym_perturb_rows(int64_t M, int32_t width, const float* src, int64_t ld_src, const int64_t* idx, const float* noise_std, uint64_t seed,
+                          const double* opt_state, float* dst, int64_t ld_dst, void* stream);
+int32_t hgym_ppo_grad_smooth(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const HgymNet* net, const HgymBatch* batch,
+                             const HgymSmooth* smooth, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Diagnostics of an update (header v9, no layout change): what the update did to the policy, measured on the rows it trained on.
