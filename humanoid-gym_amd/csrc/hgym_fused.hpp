@@ -6,8 +6,8 @@
 //                        the tile's 32 envs behind it in the same launch) and for inference.
 //   mlp_fb_kernel        the update: the same forward on 64-row tiles, the loss gradient on the head wavefronts (PPO surrogate /
 //                        value loss / the auxiliary head's MSE) and dZ_l = (dZ_{l+1} * W_{l+1}) .* elu'(H_l) for l = 2, 1, 0 on the
-//                        activations still resident in LDS; one grid row per net.  (mlp_fb_mirror_kernel: the actor's tile with the
-//                        mirror loss of left-right symmetry in its head, HgymPPOConfig.mirror_coef > 0.)
+//                        activations still resident in LDS; one grid row per net.  (mlp_fb_head_kernel: the actor's tile with a
+//                        head of its own -- the mirror loss, the smoothness regulariser, behaviour cloning.)
 //   dw_kernel_rs         all weight-gradient products dW_l = dZ_l^T * X_l (+ bias gradients) in ONE launch:
 //                        contraction over the batch, operands staged registers -> LDS and read with the gfx950
 //                        transpose read (ds_read_b64_tr_b16), so no transposed copy of anything exists in HBM.
@@ -1203,7 +1203,7 @@ struct FbLoss {
     float aux_coef;
 };
 
-// The mirror loss (HgymPPOConfig.mirror_coef > 0): an argument of the ML instantiations only (hgym_update_mirror.hip,
+// The mirror loss (HgymPPOConfig.mirror_coef > 0): the argument of the FbMirror head's kernels only (hgym_update_mirror.hip,
 // hgym_update_act_mirror.hip), so that FbLoss -- a kernel argument of every other update kernel -- keeps its layout.
 struct FbMirror {
     const float* target;       // (M, A) fp32, row m of the MINIBATCH (contiguous, no gather): the raw mu of row m's partner (the pre-pass)
@@ -1215,7 +1215,7 @@ struct FbMirror {
 };
 constexpr int FB_MIRROR_LDS = 64 * 12 * 4 + 2 * 16 * 4;      // 64 rows x 12 floats, then act_src[16] (ints) and act_sign[16]
 
-// The smoothness regulariser (hgym_ppo_grad_smooth): an argument of the SM instantiations only (hgym_update_smooth.hip,
+// The smoothness regulariser (hgym_ppo_grad_smooth): the argument of the FbSmooth head's kernels only (hgym_update_smooth.hip,
 // hgym_update_act_smooth.hip), so that FbLoss and FbMirror keep their layouts.  Two detached targets and one weight per row of the MINIBATCH
 // (contiguous, no gather): d mu += gT w (mu - tnext) + gS (mu - tnear).  A term whose g is 0 is off and its pointers are not read.
 // An SM tile never carries the mirror loss, so the partial row's regression slot and the pad behind it are free for its two squared errors.
@@ -1231,7 +1231,7 @@ constexpr int LP_SMOOTH_T = LP_MIRROR, LP_SMOOTH_S = LP_MIRROR + 1;      // sum 
 static_assert(LP_SMOOTH_S < LOSS_PARTIALS, "the partial row has 32 floats");
 constexpr int FB_SMOOTH_LDS = 2 * 64 * 12 * 4 + 64 * 4;      // tnext 64 x 12, tnear 64 x 12, weight 64
 
-// Behaviour cloning (hgym_bc_grad): an argument of the BC instantiations only (hgym_update_bc.hip, hgym_update_act_bc.hip).  The head
+// Behaviour cloning (hgym_bc_grad): the argument of the FbBC head's kernels only (hgym_update_bc.hip, hgym_update_act_bc.hip).  The head
 // regresses mu on target[row] -- a storage column gathered through FwdArgs::idx like every other loss input -- and nothing else: no
 // surrogate, no entropy, no KL, no d std.  The tile's 64 target rows are staged in the actor's loss-input region of LDS (fb_lds_lin:
 // 64 x FB_LIN_ACTOR floats, of which a row's first 12 are used), so a BC tile asks for exactly fb_lds_bytes(net).
@@ -1270,16 +1270,31 @@ inline int fb_lds_bytes(const int32_t* dims) {
     return fb_lds_bytes(n);
 }
 
+// The head of an update tile is a type.  FbPlain: the PPO head alone (actor: surrogate, entropy, KL; critic: value loss; AUX: the
+// auxiliary head's MSE).  FbMirror / FbSmooth: the actor's PPO head with that term joined to d mu.  FbBC: the actor's regression head.
+struct FbPlain {};
+template <class T, class Head>      // H where the tile's head is a T, else null
+__device__ __forceinline__ const T* head_as(const Head* H) { if constexpr (__is_same(T, Head)) return H; else return nullptr; }
+// The slots of the partial row (LP_*) that a tile writes: each net's tiles their own, so that the launches of a minibatch do not meet.
+template <class Head, bool AUX>
+__device__ __forceinline__ constexpr bool fb_partial_mine(bool is_actor, int tid) {
+    constexpr bool ML = __is_same(Head, FbMirror), BC = __is_same(Head, FbBC), SM = __is_same(Head, FbSmooth);
+    return BC    ? ((tid >= LP_DBIAS_MU && tid < LP_DBIAS_V) || tid == LP_MIRROR)      // d mu's sums and the regression slot
+           : AUX ? tid == LP_AUX
+                 : (is_actor ? ((tid != LP_VALUE && tid < LP_DBIAS_V) ||               // all of the PPO head's but the critic's two
+                                (ML && tid == LP_MIRROR) ||
+                                (SM && (tid == LP_SMOOTH_T || tid == LP_SMOOTH_S)))
+                             : (tid == LP_VALUE || tid == LP_DBIAS_V));
+}
+
 // VU: the unclipped value loss (HgymPPOConfig.value_loss_unclipped); a template parameter, so that the clipped kernels stay as they were
-// ML: the actor's head also forms the mirror loss (FbMirror, *Mr); off by default, `if constexpr`: every other instantiation is what it was
-// BC: the actor's head forms the behaviour-cloning regression instead of the PPO loss (FbBC, *Bc); off by default, `if constexpr` and
-// lambdas of its own (l2idle_bc, head_bc) that no other instantiation calls
-// SM: the actor's head also forms the smoothness regulariser (FbSmooth, *Sm); off by default, `if constexpr` like ML
-template <int G1, bool AUX = false, bool XB16 = false, bool VU = false, bool GA = false, bool ML = false, bool BC = false, bool SM = false>
-__device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const FusedNet& n, bool is_actor, char* smem,
-                                        const FbMirror* Mr = nullptr, const FbBC* Bc = nullptr, const FbSmooth* Sm = nullptr) {
-    static_assert(!BC || (!AUX && !ML && !VU), "the behaviour-cloning head is the actor's alone");
-    static_assert(!SM || (!AUX && !ML && !VU && !BC), "the smoothness head is the actor's alone, and never beside the mirror loss");
+// Head, *H: the tile's head and its arguments (null for FbPlain).  Every head-specific line stands under `if constexpr`, so each
+// instantiation is what it would be without the others; the behaviour-cloning head has lambdas of its own (l2idle_bc, head_bc).
+template <int G1, bool AUX = false, bool XB16 = false, bool VU = false, bool GA = false, class Head = FbPlain>
+__device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const FusedNet& n, bool is_actor, char* smem, const Head* H = nullptr) {
+    constexpr bool ML = __is_same(Head, FbMirror), BC = __is_same(Head, FbBC), SM = __is_same(Head, FbSmooth);
+    static_assert(__is_same(Head, FbPlain) || (!AUX && !VU), "a head other than the plain one is the actor's alone");
+    const FbMirror* Mr = head_as<FbMirror>(H); const FbBC* Bc = head_as<FbBC>(H); const FbSmooth* Sm = head_as<FbSmooth>(H);
     constexpr int BM = 64, NW = 16, D = 2, MB = BM / 16;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 15, q = lane >> 4;
@@ -1660,7 +1675,7 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
     }
     __syncthreads();          // dZ3 tile and the per-wave sums are in LDS; H0 sits in P, H1 in Q, H2 in its own buffer
     if (tid < LOSS_PARTIALS) {
-        const bool mine = BC ? ((tid >= LP_DBIAS_MU && tid < LP_DBIAS_V) || tid == LP_MIRROR) : AUX ? tid == LP_AUX : (is_actor ? ((tid != LP_VALUE && tid < LP_DBIAS_V) || (ML && tid == LP_MIRROR) || (SM && (tid == LP_SMOOTH_T || tid == LP_SMOOTH_S))) : (tid == LP_VALUE || tid == LP_DBIAS_V));
+        const bool mine = fb_partial_mine<Head, AUX>(is_actor, tid);
         if (mine) L.partials[(int64_t)blockIdx.x * LOSS_PARTIALS + tid] = red[tid] + red[LOSS_PARTIALS + tid] + red[2 * LOSS_PARTIALS + tid] + red[3 * LOSS_PARTIALS + tid];
     }
     // ---- dZ chain on the resident tile
@@ -1728,7 +1743,7 @@ int32_t launch_mlp_fb_act_one(const FwdArgs& fb, const FbLoss& fl, bool shadow, 
     return HGYM_OK;
 }
 // the launches of mlp_fb_act_kernel for nets [0, nets) of fb0 (hgym_update_act.hip: clipped value loss, hgym_update_act_vu.hip: unclipped)
-// first: the first net launched (1: the actor's tiles have their own launch, launch_mlp_fb_act_mirror)
+// first: the first net launched (1: the actor's tiles have their own launch, launch_mlp_fb_head)
 template <bool VU>
 int32_t launch_mlp_fb_act_form(const FwdArgs& fb0, const FbLoss& fl, bool shadow, int tiles, int nets, hipStream_t s, int first = 0) {
     for (int i = first; i < nets; ++i) {
@@ -1748,96 +1763,75 @@ int32_t launch_mlp_fb_act_form(const FwdArgs& fb0, const FbLoss& fl, bool shadow
     return HGYM_OK;
 }
 
-// The ACTOR's update tile with the mirror loss in its head (HgymPPOConfig.mirror_coef > 0): one kernel per first hidden width, input
-// form and activation form (GA), the actor alone -- the critic's and the auxiliary head's tiles run through the kernels they always had
-// (mlp_fb_kernel from net 1 on, launch_mlp_fb_act_form with first = 1), so those nets' bits cannot move.  hgym_update_mirror.hip holds
-// the ELU(1) kernels, hgym_update_act_mirror.hip the generic ones.
-template <int G1, bool XB16, bool GA>
-__global__ __launch_bounds__(1024) void mlp_fb_mirror_kernel(const FwdArgs a, const FbLoss L, const FbMirror mr) {
+// The ACTOR's update tile with a head of its own (FbMirror: HgymPPOConfig.mirror_coef > 0, FbSmooth: hgym_ppo_grad_smooth, FbBC:
+// hgym_bc_grad): one kernel per head, first hidden width, input form and activation form (GA), the actor alone.  Beside the mirror and
+// the smooth tiles the critic's and the auxiliary head's tiles run through the kernels they always had (mlp_fb_kernel from net 1 on,
+// launch_mlp_fb_act_form with first = 1), so those nets' bits cannot move; a cloning step has no other net.  The head is THIS kernel's
+// third argument, so that FbLoss -- an argument of every other update kernel -- keeps its layout.
+template <class Head, int G1, bool XB16, bool GA>
+__global__ __launch_bounds__(1024) void mlp_fb_head_kernel(const FwdArgs a, const FbLoss L, const Head head) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    fb_body<G1, false, XB16, false, GA, true>(a, L, a.net[0], true, smem, &mr);
+    fb_body<G1, false, XB16, false, GA, Head>(a, L, a.net[0], true, smem, &head);
 }
-template <int G1, bool XB16, bool GA>
-int32_t launch_mlp_fb_mirror_one(const FwdArgs& fb, const FbLoss& fl, const FbMirror& mr, int tiles, size_t lds, hipStream_t s) {
-    const int32_t rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&mlp_fb_mirror_kernel<G1, XB16, GA>), lds, "mlp_fb_mirror_kernel");
-    if (rc) return rc;
-    hipLaunchKernelGGL((mlp_fb_mirror_kernel<G1, XB16, GA>), dim3(tiles), dim3(1024), lds, s, fb, fl, mr);
-    return HGYM_OK;
-}
-template <bool GA>
-int32_t launch_mlp_fb_mirror_form(const FwdArgs& fb0, const FbLoss& fl, const FbMirror& mr0, bool shadow, int tiles, hipStream_t s) {
-    FwdArgs fb = fb0;
-    fb.net0 = 0;
-    fb.nets = 1;
-    FbMirror mr = mr0;
-    size_t lds = (size_t)fb_lds_bytes(fb.net[0]);
-    mr.stage = lds + FB_MIRROR_LDS <= FB_LDS_LIMIT ? 1 : 0;      // no room: the head reads the target from memory
-    if (mr.stage) lds += FB_MIRROR_LDS;
-    const int g1 = fb.net[0].layer[0].NB / 16;         // first hidden width 256 / 512 / 768
-    if (g1 == 1) return shadow ? launch_mlp_fb_mirror_one<1, true, GA>(fb, fl, mr, tiles, lds, s) : launch_mlp_fb_mirror_one<1, false, GA>(fb, fl, mr, tiles, lds, s);
-    if (g1 == 2) return shadow ? launch_mlp_fb_mirror_one<2, true, GA>(fb, fl, mr, tiles, lds, s) : launch_mlp_fb_mirror_one<2, false, GA>(fb, fl, mr, tiles, lds, s);
-    if (g1 == 3) return shadow ? launch_mlp_fb_mirror_one<3, true, GA>(fb, fl, mr, tiles, lds, s) : launch_mlp_fb_mirror_one<3, false, GA>(fb, fl, mr, tiles, lds, s);
-    return HGYM_E_UNSUPPORTED;
-}
-
-// The ACTOR's update tile with the smoothness regulariser in its head (hgym_ppo_grad_smooth): one kernel per first hidden width, input
-// form and activation form, the actor alone -- every other net's tiles run through the kernels they always had, as beside the mirror
-// tiles.  hgym_update_smooth.hip holds the ELU(1) kernels, hgym_update_act_smooth.hip the generic ones.
-template <int G1, bool XB16, bool GA>
-__global__ __launch_bounds__(1024) void mlp_fb_smooth_kernel(const FwdArgs a, const FbLoss L, const FbSmooth sm) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    fb_body<G1, false, XB16, false, GA, false, false, true>(a, L, a.net[0], true, smem, nullptr, nullptr, &sm);
-}
-template <int G1, bool XB16, bool GA>
-int32_t launch_mlp_fb_smooth_one(const FwdArgs& fb, const FbLoss& fl, const FbSmooth& sm, int tiles, size_t lds, hipStream_t s) {
-    const int32_t rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&mlp_fb_smooth_kernel<G1, XB16, GA>), lds, "mlp_fb_smooth_kernel");
-    if (rc) return rc;
-    hipLaunchKernelGGL((mlp_fb_smooth_kernel<G1, XB16, GA>), dim3(tiles), dim3(1024), lds, s, fb, fl, sm);
-    return HGYM_OK;
-}
-template <bool GA>
-int32_t launch_mlp_fb_smooth_form(const FwdArgs& fb0, const FbLoss& fl, const FbSmooth& sm0, bool shadow, int tiles, hipStream_t s) {
-    FwdArgs fb = fb0;
-    fb.net0 = 0;
-    fb.nets = 1;
-    FbSmooth sm = sm0;
-    size_t lds = (size_t)fb_lds_bytes(fb.net[0]);
-    sm.stage = lds + FB_SMOOTH_LDS <= FB_LDS_LIMIT ? 1 : 0;      // no room: the head reads the targets and the weight from memory
-    if (sm.stage) lds += FB_SMOOTH_LDS;
-    const int g1 = fb.net[0].layer[0].NB / 16;         // first hidden width 256 / 512 / 768
-    if (g1 == 1) return shadow ? launch_mlp_fb_smooth_one<1, true, GA>(fb, fl, sm, tiles, lds, s) : launch_mlp_fb_smooth_one<1, false, GA>(fb, fl, sm, tiles, lds, s);
-    if (g1 == 2) return shadow ? launch_mlp_fb_smooth_one<2, true, GA>(fb, fl, sm, tiles, lds, s) : launch_mlp_fb_smooth_one<2, false, GA>(fb, fl, sm, tiles, lds, s);
-    if (g1 == 3) return shadow ? launch_mlp_fb_smooth_one<3, true, GA>(fb, fl, sm, tiles, lds, s) : launch_mlp_fb_smooth_one<3, false, GA>(fb, fl, sm, tiles, lds, s);
-    return HGYM_E_UNSUPPORTED;
-}
-
-// The ACTOR's update tile with the behaviour-cloning head (hgym_bc_grad): one kernel per first hidden width, input form and activation
-// form, the actor alone -- no other net has tiles in a cloning step.  hgym_update_bc.hip holds the ELU(1) kernels, hgym_update_act_bc.hip
-// the generic ones.
+// The cloning head's kernel is mlp_fb_head_kernel<FbBC, ..> under the name it came with.  A kernel's name is part of its code object:
+// its length decides where the kernel descriptors come to lie, and the change that gave the heads one template moved no byte of any
+// code object's .text or .rodata (tools/code_identity.py).  Whatever next moves this code anyway can drop this template.
 template <int G1, bool XB16, bool GA>
 __global__ __launch_bounds__(1024) void mlp_fb_bc_kernel(const FwdArgs a, const FbLoss L, const FbBC bc) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    fb_body<G1, false, XB16, false, GA, false, true>(a, L, a.net[0], true, smem, nullptr, &bc);
+    fb_body<G1, false, XB16, false, GA, FbBC>(a, L, a.net[0], true, smem, &bc);
 }
-template <int G1, bool XB16, bool GA>
-int32_t launch_mlp_fb_bc_one(const FwdArgs& fb, const FbLoss& fl, const FbBC& bc, int tiles, size_t lds, hipStream_t s) {
-    const int32_t rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&mlp_fb_bc_kernel<G1, XB16, GA>), lds, "mlp_fb_bc_kernel");
-    if (rc) return rc;
-    hipLaunchKernelGGL((mlp_fb_bc_kernel<G1, XB16, GA>), dim3(tiles), dim3(1024), lds, s, fb, fl, bc);
-    return HGYM_OK;
+template <class Head, int G1, bool XB16, bool GA>
+auto fb_head_kernel() {
+    if constexpr (__is_same(Head, FbBC)) return &mlp_fb_bc_kernel<G1, XB16, GA>;
+    else return &mlp_fb_head_kernel<Head, G1, XB16, GA>;
 }
-template <bool GA>
-int32_t launch_mlp_fb_bc_form(const FwdArgs& fb0, const FbLoss& fl, const FbBC& bc, bool shadow, int tiles, hipStream_t s) {
+
+// What the launch knows about a head: the dynamic LDS it stages its targets in behind fb_lds_bytes(net), the field that says so
+// (`stage`), and its name in an error message.
+inline int fb_head_lds(const FbMirror&) { return FB_MIRROR_LDS; }
+inline int fb_head_lds(const FbSmooth&) { return FB_SMOOTH_LDS; }
+inline int fb_head_lds(const FbBC&) { return 0; }      // its targets lie in the loss-input region the sum already holds
+inline void fb_head_stage(FbMirror& h, int on) { h.stage = on; }
+inline void fb_head_stage(FbSmooth& h, int on) { h.stage = on; }
+inline void fb_head_stage(FbBC&, int) {}
+inline const char* fb_head_name(const FbMirror&) { return "mlp_fb_head_kernel<mirror>"; }
+inline const char* fb_head_name(const FbSmooth&) { return "mlp_fb_head_kernel<smooth>"; }
+inline const char* fb_head_name(const FbBC&) { return "mlp_fb_bc_kernel"; }
+
+// One launch of the actor's tiles with `head0`.  Each (GA, Head) is explicitly instantiated in a translation unit, i.e. a device code
+// object, of its own (hgym_update_{mirror,smooth,bc}.hip: ELU(1), hgym_update_act_{mirror,smooth,bc}.hip: any resolved activation) and
+// declared `extern` below: no other translation unit carries these kernels.
+template <bool GA, class Head>
+int32_t launch_mlp_fb_head(const FwdArgs& fb0, const FbLoss& fl, const Head& head0, bool shadow, int tiles, hipStream_t s) {
     FwdArgs fb = fb0;
     fb.net0 = 0;
     fb.nets = 1;
-    const size_t lds = (size_t)fb_lds_bytes(fb.net[0]);      // the targets lie in the loss-input region the sum already holds
+    Head head = head0;
+    size_t lds = (size_t)fb_lds_bytes(fb.net[0]);
+    const int stage = lds + fb_head_lds(head) <= FB_LDS_LIMIT ? 1 : 0;      // no room: the head reads its targets from memory
+    fb_head_stage(head, stage);
+    if (stage) lds += fb_head_lds(head);
+    auto one = [&](auto g1, auto xb16) -> int32_t {                // one kernel: first hidden width 256 * g1, input form xb16
+        const auto kernel = fb_head_kernel<Head, decltype(g1)::value, decltype(xb16)::value, GA>();
+        const int32_t rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), lds, fb_head_name(head));
+        if (rc) return rc;
+        hipLaunchKernelGGL(kernel, dim3(tiles), dim3(1024), lds, s, fb, fl, head);
+        return HGYM_OK;
+    };
+    auto both = [&](auto g1) { return shadow ? one(g1, std::true_type()) : one(g1, std::false_type()); };      // runtime `shadow` -> XB16
     const int g1 = fb.net[0].layer[0].NB / 16;         // first hidden width 256 / 512 / 768
-    if (g1 == 1) return shadow ? launch_mlp_fb_bc_one<1, true, GA>(fb, fl, bc, tiles, lds, s) : launch_mlp_fb_bc_one<1, false, GA>(fb, fl, bc, tiles, lds, s);
-    if (g1 == 2) return shadow ? launch_mlp_fb_bc_one<2, true, GA>(fb, fl, bc, tiles, lds, s) : launch_mlp_fb_bc_one<2, false, GA>(fb, fl, bc, tiles, lds, s);
-    if (g1 == 3) return shadow ? launch_mlp_fb_bc_one<3, true, GA>(fb, fl, bc, tiles, lds, s) : launch_mlp_fb_bc_one<3, false, GA>(fb, fl, bc, tiles, lds, s);
+    if (g1 == 1) return both(std::integral_constant<int, 1>());
+    if (g1 == 2) return both(std::integral_constant<int, 2>());
+    if (g1 == 3) return both(std::integral_constant<int, 3>());
     return HGYM_E_UNSUPPORTED;
 }
+extern template int32_t launch_mlp_fb_head<false, FbMirror>(const FwdArgs&, const FbLoss&, const FbMirror&, bool, int, hipStream_t);
+extern template int32_t launch_mlp_fb_head<true, FbMirror>(const FwdArgs&, const FbLoss&, const FbMirror&, bool, int, hipStream_t);
+extern template int32_t launch_mlp_fb_head<false, FbSmooth>(const FwdArgs&, const FbLoss&, const FbSmooth&, bool, int, hipStream_t);
+extern template int32_t launch_mlp_fb_head<true, FbSmooth>(const FwdArgs&, const FbLoss&, const FbSmooth&, bool, int, hipStream_t);
+extern template int32_t launch_mlp_fb_head<false, FbBC>(const FwdArgs&, const FbLoss&, const FbBC&, bool, int, hipStream_t);
+extern template int32_t launch_mlp_fb_head<true, FbBC>(const FwdArgs&, const FbLoss&, const FbBC&, bool, int, hipStream_t);
 
 // ================================================================================================ per-minibatch loss scalars
 // Sums the per-tile loss partials of a minibatch ([nblocks][32], mlp_fb_kernel / ppo_loss_kernel) into opt_state and writes the

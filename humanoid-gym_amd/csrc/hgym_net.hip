@@ -25,21 +25,15 @@ namespace hgym {
 int32_t launch_mlp_fb(const FwdArgs& fb, const FbLoss& fl, bool shadow, bool unclipped, int tiles, int nets, size_t lds, hipStream_t s);
 // hgym_update_act.hip, hgym_fwd_act.hip: the same tiles with any resolved activation, one launch per net
 int32_t launch_mlp_fb_act(const FwdArgs& fb, const FbLoss& fl, bool shadow, bool unclipped, int tiles, int nets, hipStream_t s, int first);
-// hgym_update_mirror.hip, hgym_update_act_mirror.hip: the actor's tiles with the mirror loss in their head (HgymPPOConfig.mirror_coef > 0)
-int32_t launch_mlp_fb_mirror(const FwdArgs& fb, const FbLoss& fl, const FbMirror& mr, bool shadow, int tiles, hipStream_t s);
-int32_t launch_mlp_fb_act_mirror(const FwdArgs& fb, const FbLoss& fl, const FbMirror& mr, bool shadow, int tiles, hipStream_t s);
+// (the actor's tiles with a head of their own -- mirror loss, smoothness regulariser, behaviour cloning: launch_mlp_fb_head, hgym_fused.hpp)
 // hgym_loss_mirror.hip: ppo_loss_kernel<.., ML = true>, the layer-by-layer path's loss with the mirror loss
 int32_t launch_ppo_loss_mirror(const LossArgs& a, bool bf16, bool unclipped, int nblocks, hipStream_t s);
 int32_t launch_mlp_fwd_act(const FwdArgs& a, int nets, bool wide, int64_t dbg_tiles, hipStream_t s);
-// hgym_update_bc.hip, hgym_update_act_bc.hip: the actor's tiles with the behaviour-cloning head, and the small kernels of hgym_bc_grad
-int32_t launch_mlp_fb_bc(const FwdArgs& fb, const FbLoss& fl, const FbBC& bc, bool shadow, int tiles, hipStream_t s);
-int32_t launch_mlp_fb_act_bc(const FwdArgs& fb, const FbLoss& fl, const FbBC& bc, bool shadow, int tiles, hipStream_t s);
+// hgym_update_bc.hip: the small kernels of hgym_bc_grad
 int32_t launch_bc_loss(const BcLossArgs& a, bool bf16, int nblocks, hipStream_t s);
 int32_t launch_bc_scalars(const BcScalArgs& a, hipStream_t s);
-// hgym_update_smooth.hip, hgym_update_act_smooth.hip, hgym_loss_smooth.hip, hgym_smooth.hip: hgym_ppo_grad_smooth's kernels -- the actor's
-// tiles / the layer-by-layer head with the smoothness regulariser, the perturbed rows of the spatial pre-pass, the minibatch's sums
-int32_t launch_mlp_fb_smooth(const FwdArgs& fb, const FbLoss& fl, const FbSmooth& sm, bool shadow, int tiles, hipStream_t s);
-int32_t launch_mlp_fb_act_smooth(const FwdArgs& fb, const FbLoss& fl, const FbSmooth& sm, bool shadow, int tiles, hipStream_t s);
+// hgym_loss_smooth.hip, hgym_smooth.hip: hgym_ppo_grad_smooth's kernels -- the layer-by-layer head with the smoothness regulariser, the
+// perturbed rows of the spatial pre-pass, the minibatch's sums
 int32_t launch_ppo_loss_smooth(const LossArgs& a, const LossSmooth& sm, bool bf16, int nblocks, hipStream_t s);
 int32_t launch_perturb_rows(int64_t M, int width, const float* src, int64_t ld_src, const int64_t* idx, const float* noise_std, uint64_t seed,
                             const double* opt_state, float* dst, int64_t ld_dst, hipStream_t s);
@@ -1396,6 +1390,74 @@ struct FusedPath : NetBase {
         return HGYM_OK;
     }
 
+    // The update tiles of a minibatch over nets [0, nets): what grad and bc_grad decide, check and fill in the same way.  Two steps,
+    // because both launch something in between (the pre-passes; the zero fill) and plan_tiles' refusal comes before any launch.
+    struct UpdateTiles {
+        bool shadow;      // the tiles gather their rows from the bf16 shadows of the storage rows (HgymBatch.obs_bf16 / priv_bf16)
+        int tiles;        // 64-row tiles per net
+        size_t lds;       // dynamic LDS of the net that needs most
+        FwdArgs fb;
+        FbLoss fl;        // zero but for `partials`: the caller's head fills in what it reads
+    };
+    static const void* shadow_rows(const HgymBatch& b, int i) { return i == 1 ? b.priv_bf16 : b.obs_bf16; }
+
+    int32_t plan_tiles(const HgymBatch& b, int nets, UpdateTiles* u) const {
+        const int B = b.B;
+        // bf16 shadows of the storage rows, every net's or none: gather 2 B per element, keep no operand copy
+        u->shadow = b.num_rows > 0;
+        for (int i = 0; i < nets; ++i)
+            u->shadow = u->shadow && shadow_rows(b, i) && b.num_rows * shadow_ld(w, i == 1 ? 1 : 0) * 2 < ((int64_t)1 << 32);
+        // (128-row tiles on eight 256-register wavefronts -- round 4's mlp_fb2_kernel -- measured equal to slightly slower:
+        // profiles/r04_fb2_128row_tiles_negative_result.txt; its source is profiles/r04_fb2_128row_kernel.patch; round 6 rebuilt the idea on role-specialised wavefronts at 64 and 128 rows: profiles/r06_fb3_role_specialised_wavefronts.txt.)
+        const int tiles = (int)round_up(B, 64) / 64;
+        HG_REQUIRE(tiles <= MAX_LOSS_BLOCKS, HGYM_E_UNSUPPORTED, "minibatch %d too large for the loss partial buffer", B);
+        u->tiles = tiles;
+        return HGYM_OK;
+    }
+
+    // kernel: the name that the LDS refusal gives
+    int32_t fill_tiles(const HgymBatch& b, int nets, const NetIO io[3], const char* kernel, UpdateTiles* u) {
+        FwdArgs& fb = u->fb;
+        fb = make_fwd_args(0, nets, b.B, io, b.idx, true, nullptr, nullptr);
+        if (nets > 2) fb.net[2].X0 = nullptr;       // the head's first-layer operand for the weight gradient is the actor's copy (dw)
+        if (u->shadow) {
+            uintptr_t bits = 0;
+            for (int i = 0; i < nets; ++i) bits |= (uintptr_t)shadow_rows(b, i);
+            HG_REQUIRE((bits & 15) == 0, HGYM_E_BADARG, "observation shadows must be 16-byte aligned");
+            for (int i = 0; i < nets; ++i) {
+                fb.net[i].xb = (const __bf16*)shadow_rows(b, i);
+                fb.net[i].ldxb = shadow_ld(w, i == 1 ? 1 : 0);
+                fb.net[i].X0 = nullptr;
+            }
+        }
+        memset(&u->fl, 0, sizeof(u->fl));
+        u->fl.partials = at<float>(w.partials);
+        u->lds = 0;
+        for (int i = 0; i < nets; ++i)
+            u->lds = std::max(u->lds, (size_t)fb_lds_bytes(fb.net[i]));       // the nets the kernel receives (fused_supported: same sum)
+        HG_REQUIRE(u->lds <= FB_LDS_LIMIT, HGYM_E_UNSUPPORTED, "%s needs %zu bytes of LDS", kernel, u->lds);
+        fb.nets = nets;
+        fb.dbg = phase_buffer((int64_t)u->tiles * nets);
+        return HGYM_OK;
+    }
+
+    // algorithmic (unpadded) flops of the update tiles of nets [0, nets): the forward and the dZ chain
+    double tile_flops(int nets, int B) const {
+        double flops = 0.0;
+        for (int i = 0; i < nets; ++i) {
+            for (int l = 0; l < 4; ++l) flops += 2.0 * (double)B * w.net[i].layer[l].N * w.net[i].layer[l].K;
+            for (int l = 1; l < 4; ++l) flops += 2.0 * (double)B * w.net[i].layer[l].K * w.net[i].layer[l].N;
+        }
+        return flops;
+    }
+
+    // the actor's tiles with `head` in them, their own launch (hgym_fused.hpp: mlp_fb_head_kernel)
+    template <class Head>
+    int32_t launch_actor_head(const UpdateTiles& u, const Head& head) {
+        return act_is_elu1(w.act) ? launch_mlp_fb_head<false, Head>(u.fb, u.fl, head, u.shadow, u.tiles, s)
+                                  : launch_mlp_fb_head<true, Head>(u.fb, u.fl, head, u.shadow, u.tiles, s);
+    }
+
     // part < 0: the whole minibatch gradient.  part 0 / 1: the two halves of hgym_ppo_grad_part -- 0 leaves std's and the actor's
     // gradient final, 1 the critic's, the auxiliary head's and the KL slot.
     // sm (hgym_ppo_grad_smooth): the smoothness regulariser joins d mu; null or both coefficients 0: off, the launches of hgym_ppo_grad
@@ -1408,13 +1470,9 @@ struct FusedPath : NetBase {
         // two launches of 144 and 112 workgroups on 256 CUs, each as long as the full one -- 2 x 142 us against 178 us.)
         if (part == 1) return reduce_range(critic_off, w.P, Mp);
         const int nets = w.net[2].fused ? 3 : 2;      // the auxiliary head as a third grid row of the same launches
-        // bf16 shadows of the storage rows (HgymBatch.obs_bf16 / priv_bf16): gather 2 B per element, keep no operand copy
-        const bool shadow = b.obs_bf16 && b.priv_bf16 && b.num_rows > 0 && b.num_rows * shadow_ld(w, 0) * 2 < ((int64_t)1 << 32) &&
-                            b.num_rows * shadow_ld(w, 1) * 2 < ((int64_t)1 << 32);
-        // (128-row tiles on eight 256-register wavefronts -- round 4's mlp_fb2_kernel -- measured equal to slightly slower:
-        // profiles/r04_fb2_128row_tiles_negative_result.txt; its source is profiles/r04_fb2_128row_kernel.patch; round 6 rebuilt the idea on role-specialised wavefronts at 64 and 128 rows: profiles/r06_fb3_role_specialised_wavefronts.txt.)
-        const int tiles = (int)round_up(B, 64) / 64;
-        HG_REQUIRE(tiles <= MAX_LOSS_BLOCKS, HGYM_E_UNSUPPORTED, "minibatch %d too large for the loss partial buffer", B);
+        UpdateTiles u;
+        const int32_t rc_plan = plan_tiles(b, nets, &u);
+        if (rc_plan) return rc_plan;
         const bool mirror = ppo.mirror_coef > 0.0f;
         if (mirror) {
             // the mirror loss's pre-pass: the raw mu of the partner rows under the current parameters, forward only (no gradient through
@@ -1432,18 +1490,9 @@ struct FusedPath : NetBase {
             const NetIO io[3] = {{b.obs, cfg.num_obs, at<float>(w.net[0].out_f32), A},
                                  {b.priv, cfg.num_priv, at<float>(w.net[1].out_f32), 1},
                                  {b.obs, cfg.num_obs, nullptr, 0}};
-            FwdArgs fb = make_fwd_args(0, nets, B, io, b.idx, true, nullptr, nullptr);
-            fb.net[2].X0 = nullptr;       // the head's first-layer operand for the weight gradient is the actor's copy (dw)
-            if (shadow) {
-                HG_REQUIRE((((uintptr_t)b.obs_bf16 | (uintptr_t)b.priv_bf16) & 15) == 0, HGYM_E_BADARG, "observation shadows must be 16-byte aligned");
-                for (int i = 0; i < nets; ++i) {
-                    fb.net[i].xb = (const __bf16*)(i == 1 ? b.priv_bf16 : b.obs_bf16);
-                    fb.net[i].ldxb = shadow_ld(w, i == 1 ? 1 : 0);
-                    fb.net[i].X0 = nullptr;
-                }
-            }
-            FbLoss fl;
-            memset(&fl, 0, sizeof(fl));
+            const int32_t rc_fill = fill_tiles(b, nets, io, "mlp_fb_kernel", &u);
+            if (rc_fill) return rc_fill;
+            FbLoss& fl = u.fl;
             fl.actions = b.actions;
             fl.old_mu = b.mu;
             fl.old_sigma = b.sigma;
@@ -1454,63 +1503,50 @@ struct FusedPath : NetBase {
             fl.clip = ppo.clip_param;
             fl.value_coef = ppo.value_loss_coef;
             fl.entropy_coef = ppo.entropy_coef;
-            fl.partials = at<float>(w.partials);
             fl.aux_target = b.priv;
             fl.aux_ldt = cfg.num_priv;
             fl.aux_off = cfg.aux_target_offset;
             fl.aux_coef = ppo.aux_coef;
-            size_t lds = 0;
-            for (int i = 0; i < nets; ++i)
-                lds = std::max(lds, (size_t)fb_lds_bytes(fb.net[i]));       // the nets the kernel receives (fused_supported: same sum)
-            HG_REQUIRE(lds <= FB_LDS_LIMIT, HGYM_E_UNSUPPORTED, "mlp_fb_kernel needs %zu bytes of LDS", lds);
-            fb.nets = nets;
-            fb.dbg = phase_buffer((int64_t)tiles * nets);
+            const bool unclipped = ppo.value_loss_unclipped != 0;
             prof_begin(HGYM_PROF_MLP_FWD, s);
             int32_t rc_fb = HGYM_OK;
-            if (mirror || smooth) {
-                // the actor's tiles through the kernels with the mirror loss (or the smoothness regulariser) in their head (their own
-                // launch), every other net's through the kernels they always had, from net 1 on
-                if (mirror) {
-                    const FbMirror mr = {b.mirror_target, b.mirror_act_src, b.mirror_act_sign, 2.0f * ppo.mirror_coef / ((float)B * (float)A), 0};
-                    rc_fb = act_is_elu1(w.act) ? launch_mlp_fb_mirror(fb, fl, mr, shadow, tiles, s) : launch_mlp_fb_act_mirror(fb, fl, mr, shadow, tiles, s);
-                } else {
-                    const float gs = 2.0f / ((float)B * (float)A);
-                    const FbSmooth fs = {sm->target_next, sm->target_near, sm->next_weight, gs * sm->temporal_coef, gs * sm->spatial_coef, 0};
-                    rc_fb = act_is_elu1(w.act) ? launch_mlp_fb_smooth(fb, fl, fs, shadow, tiles, s) : launch_mlp_fb_act_smooth(fb, fl, fs, shadow, tiles, s);
-                    if (rc_fb) return rc_fb;
-                    rc_fb = launch_smooth_sums(tiles, B, A, at<float>(w.partials), sm->next_weight, sm->sums, s);
-                }
+            int first = 0;      // the first net of the launches every net always had
+            if (mirror) {
+                // the actor's tiles through the kernels with the mirror loss in their head (their own launch), the rest from net 1 on
+                const FbMirror head = {b.mirror_target, b.mirror_act_src, b.mirror_act_sign, 2.0f * ppo.mirror_coef / ((float)B * (float)A), 0};
+                rc_fb = launch_actor_head(u, head);
+                first = 1;
+            } else if (smooth) {
+                // the same with the smoothness regulariser, and the sums of its two terms
+                const float gs = 2.0f / ((float)B * (float)A);
+                const FbSmooth head = {sm->target_next, sm->target_near, sm->next_weight, gs * sm->temporal_coef, gs * sm->spatial_coef, 0};
+                rc_fb = launch_actor_head(u, head);
                 if (rc_fb) return rc_fb;
-                if (act_is_elu1(w.act)) {
-                    FwdArgs rest = fb;
-                    rest.net0 = 1;
-                    rest.nets = nets - 1;
-                    if (rest.dbg) rest.dbg += (int64_t)tiles * 8;      // phase stamps: behind the actor's slots
-                    rc_fb = launch_mlp_fb(rest, fl, shadow, ppo.value_loss_unclipped != 0, tiles, nets - 1, lds, s);
-                } else {
-                    rc_fb = launch_mlp_fb_act(fb, fl, shadow, ppo.value_loss_unclipped != 0, tiles, nets, s, 1);
-                }
-            } else {
-                rc_fb = act_is_elu1(w.act) ? launch_mlp_fb(fb, fl, shadow, ppo.value_loss_unclipped != 0, tiles, nets, lds, s)      // (hgym_update.hip: the kernel's own code object)
-                                           : launch_mlp_fb_act(fb, fl, shadow, ppo.value_loss_unclipped != 0, tiles, nets, s, 0);
+                rc_fb = launch_smooth_sums(u.tiles, B, A, at<float>(w.partials), sm->next_weight, sm->sums, s);
+                first = 1;
             }
             if (rc_fb) return rc_fb;
-            double flops = 0.0;
-            for (int i = 0; i < nets; ++i) {
-                for (int l = 0; l < 4; ++l) flops += 2.0 * (double)B * w.net[i].layer[l].N * w.net[i].layer[l].K;
-                for (int l = 1; l < 4; ++l) flops += 2.0 * (double)B * w.net[i].layer[l].K * w.net[i].layer[l].N;
+            if (act_is_elu1(w.act)) {      // (hgym_update.hip: the kernel's own code object)
+                FwdArgs rest = u.fb;
+                rest.net0 = first;
+                rest.nets = nets - first;
+                if (rest.dbg) rest.dbg += (int64_t)first * u.tiles * 8;      // phase stamps: behind the actor's slots
+                rc_fb = launch_mlp_fb(rest, fl, u.shadow, unclipped, u.tiles, nets - first, u.lds, s);
+            } else {
+                rc_fb = launch_mlp_fb_act(u.fb, fl, u.shadow, unclipped, u.tiles, nets, s, first);
             }
-            prof_end(HGYM_PROF_MLP_FWD, s, flops);
+            if (rc_fb) return rc_fb;
+            prof_end(HGYM_PROF_MLP_FWD, s, tile_flops(nets, B));
             HG_CHECK_LAUNCH("mlp_fb_kernel");
         }
         // the minibatch's loss scalars (per-tile partials -> opt_state, std / head-bias gradients, KL slot): one extra workgroup of
         // the weight-gradient launch that follows anyway (it needs nothing but the partials mlp_fb_kernel has just written)
-        ScalArgs sc = {tiles, B, A, nets == 3 ? w.net[2].layer[3].N : 0, at<float>(w.partials), net.grads,
+        ScalArgs sc = {u.tiles, B, A, nets == 3 ? w.net[2].layer[3].N : 0, at<float>(w.partials), net.grads,
                              net.grads + w.net[0].layer[3].b_off, net.grads + w.net[1].layer[3].b_off, net.grads + w.P, net.opt_state,
                              (double)ppo.beta1, (double)ppo.beta2, prologue_in_grad(ppo) ? 1 : 0, ppo.adaptive_lr, ppo.desired_kl, ppo.lr_min,
                              ppo.lr_max, 1, grad_sigma()};
         if (mirror) sc.mirror_sums = b.mirror_sums;      // (else null: off)
-        int32_t rc = dw(nets, B, sc, shadow ? &b : nullptr);
+        int32_t rc = dw(nets, B, sc, u.shadow ? &b : nullptr);
         if (rc) return rc;
         if (w.nnets > 2 && nets == 2) {
             rc = aux.aux_grad(ppo, b);
@@ -1524,41 +1560,27 @@ struct FusedPath : NetBase {
     int32_t bc_grad(const HgymBCConfig& bc, const HgymBatch& b, const float* target, double* sums) {
         const int B = b.B, A = cfg.num_actions;
         const int Mp = (int)round_up(B, w.SE);
-        const bool shadow = b.obs_bf16 && b.num_rows > 0 && b.num_rows * shadow_ld(w, 0) * 2 < ((int64_t)1 << 32);
-        const int tiles = (int)round_up(B, 64) / 64;
-        HG_REQUIRE(tiles <= MAX_LOSS_BLOCKS, HGYM_E_UNSUPPORTED, "minibatch %d too large for the loss partial buffer", B);
+        UpdateTiles u;
+        int32_t rc = plan_tiles(b, 1, &u);
+        if (rc) return rc;
         HG_REQUIRE(A != 12 || ((uintptr_t)target & 15) == 0, HGYM_E_BADARG, "hgym_bc_grad: target must be 16-byte aligned");
-        int32_t rc = bc_zero_grads();
+        rc = bc_zero_grads();
         if (rc) return rc;
         const NetIO io[3] = {{b.obs, cfg.num_obs, at<float>(w.net[0].out_f32), A}, {}, {}};
-        FwdArgs fb = make_fwd_args(0, 1, B, io, b.idx, true, nullptr, nullptr);
-        if (shadow) {
-            HG_REQUIRE(((uintptr_t)b.obs_bf16 & 15) == 0, HGYM_E_BADARG, "observation shadows must be 16-byte aligned");
-            fb.net[0].xb = (const __bf16*)b.obs_bf16;
-            fb.net[0].ldxb = shadow_ld(w, 0);
-            fb.net[0].X0 = nullptr;
-        }
-        FbLoss fl;
-        memset(&fl, 0, sizeof(fl));
-        fl.partials = at<float>(w.partials);
-        HG_REQUIRE((size_t)fb_lds_bytes(fb.net[0]) <= FB_LDS_LIMIT, HGYM_E_UNSUPPORTED, "mlp_fb_bc_kernel needs %d bytes of LDS", fb_lds_bytes(fb.net[0]));
-        fb.nets = 1;
-        fb.dbg = phase_buffer((int64_t)tiles);
-        const FbBC hb = {target, 1.0f / ((float)B * (float)A), bc.huber_delta, bc.loss_type == HGYM_BC_HUBER ? 1 : 0};
+        rc = fill_tiles(b, 1, io, "mlp_fb_bc_kernel", &u);
+        if (rc) return rc;
+        const FbBC head = {target, 1.0f / ((float)B * (float)A), bc.huber_delta, bc.loss_type == HGYM_BC_HUBER ? 1 : 0};
         prof_begin(HGYM_PROF_MLP_FWD, s);
-        rc = act_is_elu1(w.act) ? launch_mlp_fb_bc(fb, fl, hb, shadow, tiles, s) : launch_mlp_fb_act_bc(fb, fl, hb, shadow, tiles, s);
-        double flops = 0.0;
-        for (int l = 0; l < 4; ++l) flops += 2.0 * (double)B * w.net[0].layer[l].N * w.net[0].layer[l].K;
-        for (int l = 1; l < 4; ++l) flops += 2.0 * (double)B * w.net[0].layer[l].K * w.net[0].layer[l].N;
-        prof_end(HGYM_PROF_MLP_FWD, s, flops);      // (before the error return: a refused launch must not leave the interval open)
+        rc = launch_actor_head(u, head);
+        prof_end(HGYM_PROF_MLP_FWD, s, tile_flops(1, B));      // (before the error return: a refused launch must not leave the interval open)
         if (rc) return rc;
         HG_CHECK_LAUNCH("mlp_fb_bc_kernel");
-        const BcScalArgs sc = {tiles, B, A, at<float>(w.partials), net.grads + w.net[0].layer[3].b_off, net.opt_state, sums};
+        const BcScalArgs sc = {u.tiles, B, A, at<float>(w.partials), net.grads + w.net[0].layer[3].b_off, net.opt_state, sums};
         rc = launch_bc_scalars(sc, s);
         if (rc) return rc;
         ScalArgs none;
         memset(&none, 0, sizeof(none));
-        rc = dw(1, B, none, shadow ? &b : nullptr, false);
+        rc = dw(1, B, none, u.shadow ? &b : nullptr, false);
         if (rc) return rc;
         return bc_reduce_actor(Mp);
     }
@@ -1826,14 +1848,22 @@ int32_t hgym_policy_act_fin(const HgymNetConfig* cfg, const HgymNet* net, int32_
     });
 }
 
-int32_t hgym_ppo_grad(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const HgymNet* net, const HgymBatch* batch, void* stream) {
+// Behind hgym_ppo_grad, hgym_ppo_grad_part and hgym_ppo_grad_smooth: the checks they share, in one order, then the runner's grad.
+// part: null for the whole gradient, else hgym_ppo_grad_part's half; smooth: null unless hgym_ppo_grad_smooth.
+static int32_t ppo_grad_entry(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const HgymNet* net, const HgymBatch* batch,
+                              const int32_t* part, const HgymSmooth* smooth, void* stream) {
     return run(cfg, net, stream, [&](auto& R) -> int32_t {
         int32_t rc = check_ppo(ppo);
         if (rc) return rc;
+        HG_REQUIRE(!part || *part == 0 || *part == 1, HGYM_E_BADARG, "part=%d (0 or 1)", *part);
         HG_REQUIRE(net->grads && net->opt_state, HGYM_E_BADARG, "null grads / opt_state");
         rc = check_batch(R.w, ppo, batch);
-        return rc ? rc : R.grad(*ppo, *batch, -1);
+        return rc ? rc : R.grad(*ppo, *batch, part ? *part : -1, smooth);
     });
+}
+
+int32_t hgym_ppo_grad(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const HgymNet* net, const HgymBatch* batch, void* stream) {
+    return ppo_grad_entry(cfg, ppo, net, batch, nullptr, nullptr, stream);
 }
 
 int32_t hgym_ppo_grad_smooth(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const HgymNet* net, const HgymBatch* batch,
@@ -1861,25 +1891,12 @@ int32_t hgym_ppo_grad_smooth(const HgymNetConfig* cfg, const HgymPPOConfig* ppo,
                        "HgymSmooth.target_near and rows must be 16-byte aligned (noise_std 4)");
         }
     }
-    return run(cfg, net, stream, [&](auto& R) -> int32_t {
-        int32_t rc = check_ppo(ppo);
-        if (rc) return rc;
-        HG_REQUIRE(net->grads && net->opt_state, HGYM_E_BADARG, "null grads / opt_state");
-        rc = check_batch(R.w, ppo, batch);
-        return rc ? rc : R.grad(*ppo, *batch, -1, smooth);
-    });
+    return ppo_grad_entry(cfg, ppo, net, batch, nullptr, smooth, stream);
 }
 
 int32_t hgym_ppo_grad_part(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const HgymNet* net, const HgymBatch* batch, int32_t part,
                            void* stream) {
-    return run(cfg, net, stream, [&](auto& R) -> int32_t {
-        int32_t rc = check_ppo(ppo);
-        if (rc) return rc;
-        HG_REQUIRE(part == 0 || part == 1, HGYM_E_BADARG, "part=%d (0 or 1)", part);
-        HG_REQUIRE(net->grads && net->opt_state, HGYM_E_BADARG, "null grads / opt_state");
-        rc = check_batch(R.w, ppo, batch);
-        return rc ? rc : R.grad(*ppo, *batch, part);
-    });
+    return ppo_grad_entry(cfg, ppo, net, batch, &part, nullptr, stream);
 }
 
 int32_t hgym_bc_grad(const HgymNetConfig* cfg, const HgymBCConfig* bc, const HgymNet* net, const HgymBatch* batch, const float* target,

@@ -1,12 +1,10 @@
-// hgym_update_act_bc.hip -- mlp_fb_bc_kernel<.., GA = true> (hgym_fused.hpp): the actor's update tile with the behaviour-cloning head
-// (hgym_bc_grad) and any resolved activation (HgymNetConfig.fused_activation), in a device code object of its own beside
-// hgym_update_bc.hip's ELU(1) kernels.  Host code reaches them through launch_mlp_fb_act_bc only.
+// hgym_update_act_bc.hip -- the device code object of mlp_fb_bc_kernel<G1, XB16, GA = true> (hgym_fused.hpp): the actor's update tile
+// with the behaviour-cloning head (hgym_bc_grad), any resolved activation (HgymNetConfig.fused_activation).
+// Six kernels: first hidden width 256 / 512 / 768 x input form (fp32 rows, bf16 shadow).
 #include "hgym_fused.hpp"
 
 namespace hgym {
 
-int32_t launch_mlp_fb_act_bc(const FwdArgs& fb, const FbLoss& fl, const FbBC& bc, bool shadow, int tiles, hipStream_t s) {
-    return launch_mlp_fb_bc_form<true>(fb, fl, bc, shadow, tiles, s);
-}
+template int32_t launch_mlp_fb_head<true, FbBC>(const FwdArgs&, const FbLoss&, const FbBC&, bool, int, hipStream_t);
 
 }  // namespace hgym

@@ -1,12 +1,10 @@
-// hgym_update_act_mirror.hip -- mlp_fb_mirror_kernel<.., GA = true> (hgym_fused.hpp): the actor's update tile with the mirror loss in its
-// head and any resolved activation (HgymNetConfig.fused_activation), in a device code object of its own beside hgym_update_mirror.hip's
-// ELU(1) kernels.  Host code reaches them through launch_mlp_fb_act_mirror only.
+// hgym_update_act_mirror.hip -- the device code object of mlp_fb_head_kernel<FbMirror, G1, XB16, GA = true> (hgym_fused.hpp): the actor's update
+// tile with the mirror loss in its head (HgymPPOConfig.mirror_coef > 0), any resolved activation (HgymNetConfig.fused_activation).
+// Six kernels: first hidden width 256 / 512 / 768 x input form (fp32 rows, bf16 shadow).
 #include "hgym_fused.hpp"
 
 namespace hgym {
 
-int32_t launch_mlp_fb_act_mirror(const FwdArgs& fb, const FbLoss& fl, const FbMirror& mr, bool shadow, int tiles, hipStream_t s) {
-    return launch_mlp_fb_mirror_form<true>(fb, fl, mr, shadow, tiles, s);
-}
+template int32_t launch_mlp_fb_head<true, FbMirror>(const FwdArgs&, const FbLoss&, const FbMirror&, bool, int, hipStream_t);
 
 }  // namespace hgym

@@ -1,12 +1,10 @@
-// hgym_update_act_smooth.hip -- mlp_fb_smooth_kernel<.., GA = true> (hgym_fused.hpp): the actor's update tile with the smoothness
-// regulariser in its head and any resolved activation (HgymNetConfig.fused_activation), in a device code object of its own beside
-// hgym_update_smooth.hip's ELU(1) kernels.  Host code reaches them through launch_mlp_fb_act_smooth only.
+// hgym_update_act_smooth.hip -- the device code object of mlp_fb_head_kernel<FbSmooth, G1, XB16, GA = true> (hgym_fused.hpp): the actor's update
+// tile with the smoothness regulariser in its head (hgym_ppo_grad_smooth), any resolved activation (HgymNetConfig.fused_activation).
+// Six kernels: first hidden width 256 / 512 / 768 x input form (fp32 rows, bf16 shadow).
 #include "hgym_fused.hpp"
 
 namespace hgym {
 
-int32_t launch_mlp_fb_act_smooth(const FwdArgs& fb, const FbLoss& fl, const FbSmooth& sm, bool shadow, int tiles, hipStream_t s) {
-    return launch_mlp_fb_smooth_form<true>(fb, fl, sm, shadow, tiles, s);
-}
+template int32_t launch_mlp_fb_head<true, FbSmooth>(const FwdArgs&, const FbLoss&, const FbSmooth&, bool, int, hipStream_t);
 
 }  // namespace hgym

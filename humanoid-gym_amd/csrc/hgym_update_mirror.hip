@@ -1,14 +1,10 @@
-// hgym_update_mirror.hip -- mlp_fb_mirror_kernel<.., GA = false> (hgym_fused.hpp): the ACTOR's update tile with the mirror loss of left-right
-// symmetry in its head (HgymPPOConfig.mirror_coef > 0), ELU(1), in a device code object of its own: six kernels, one per first hidden
-// width (256 / 512 / 768) and input form (fp32 rows, bf16 shadow).  The value-loss form does not enter -- it is the critic's, whose tiles
-// (and the auxiliary head's) run through hgym_update.hip / hgym_update_vu.hip's kernels as ever.  The generic-activation kernels are
-// hgym_update_act_mirror.hip's.  Host code reaches them through launch_mlp_fb_mirror only.
+// hgym_update_mirror.hip -- the device code object of mlp_fb_head_kernel<FbMirror, G1, XB16, GA = false> (hgym_fused.hpp): the actor's update
+// tile with the mirror loss in its head (HgymPPOConfig.mirror_coef > 0), ELU(1).
+// Six kernels: first hidden width 256 / 512 / 768 x input form (fp32 rows, bf16 shadow).
 #include "hgym_fused.hpp"
 
 namespace hgym {
 
-int32_t launch_mlp_fb_mirror(const FwdArgs& fb, const FbLoss& fl, const FbMirror& mr, bool shadow, int tiles, hipStream_t s) {
-    return launch_mlp_fb_mirror_form<false>(fb, fl, mr, shadow, tiles, s);
-}
+template int32_t launch_mlp_fb_head<false, FbMirror>(const FwdArgs&, const FbLoss&, const FbMirror&, bool, int, hipStream_t);
 
 }  // namespace hgym

@@ -4,7 +4,7 @@
             alternating; per leg the update's time (the runner's HIP events around it), the rollout's, and ms per iteration over
             learn(iters) by a host clock around a device synchronise.  Both HIP graphs are captured in the warm-up.
   --trace   one runner in one mode (default: both terms on), a few iterations and nothing else: the process to put under
-            `rocprofv3 --kernel-trace --stats` for the per-launch figures (mlp_fb_smooth_kernel beside mlp_fb_kernel, perturb_rows_kernel,
+            `rocprofv3 --kernel-trace --stats` for the per-launch figures (mlp_fb_head_kernel<FbSmooth, ..> beside mlp_fb_kernel, perturb_rows_kernel,
             the pre-passes' mlp_fwd_kernel).
 
 python tools/smoothness_cost.py [num_envs] [iters] [legs]      |      python tools/smoothness_cost.py --trace [num_envs] [iters] [off|temporal|spatial|both]"""
