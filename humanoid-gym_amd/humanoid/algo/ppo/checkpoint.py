@@ -92,7 +92,7 @@ def write_checkpoint(ck, path, side=None):
 def extra_entries(alg):
     """What a checkpoint carries beyond the reference's four keys, in file order: the two normaliser dicts (NORM_KEYS) of a policy with
     empirical_normalization, then RND_STATE_KEY of a run with rnd_cfg.  Reads the device (the blocking path)."""
-    ac, rnd = alg.actor_critic, getattr(alg, "_rnd", None)
+    ac, rnd = alg.actor_critic, alg._rnd
     extra = dict(ac.norm_state_dicts()) if hasattr(ac, "norm_state_dicts") else {}
     if rnd is not None:
         extra[RND_STATE_KEY] = rnd.rnd_state_dict()
@@ -141,7 +141,7 @@ def background_eligible(alg, device):
     reward pass's block live in buffers of their own."""
     return (getattr(alg, "net", None) is not None and str(device).startswith("cuda") and os.environ.get("HGYM_ASYNC_SAVE", "1") != "0"
             and hasattr(alg.actor_critic, "_net") and getattr(alg.actor_critic, "_teacher_net", None) is None
-            and getattr(alg, "_rnd", None) is None)
+            and alg._rnd is None)
 
 
 class Snapshot:

@@ -11,6 +11,9 @@ import math
 
 import torch
 
+from . import rnd as rnd_module
+from . import smoothness as smooth_module
+from .log_block import mean_of_sums
 from .ppo import PPO
 from .student_teacher import StudentTeacher
 
@@ -61,16 +64,14 @@ class Distillation(PPO):
 
     def init_storage(self, num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape):
         if self.rnd is not None:
-            from . import rnd as rnd_module
             rnd_module.check_setup(distillation=True)
-        if self.smoothness is not None:
-            from . import smoothness as smooth_module
-            if smooth_module.parse_config(self.smoothness, self.actor_critic.num_actor_obs) is not None:
-                smooth_module.check_setup(distillation=True)
+        if smooth_module.parse_config(self.smoothness, self.actor_critic.num_actor_obs) is not None:
+            smooth_module.check_setup(distillation=True)
         self.check_setup(self.actor_critic, num_transitions_per_env, self.gradient_length, self._world, self.symmetry,
                          self.mirror_loss_coef, self.advantage_normalization)
         # one "minibatch" is one slice: gradient_length * N rows (PPO.init_storage sizes the net's max_batch from it)
         self.num_mini_batches = int(num_transitions_per_env) // self.gradient_length
+        self._bc_sums = torch.zeros(2, dtype=torch.float64, device=self.device)      # (ahead of PPO's part, which ends by building the log block)
         super().init_storage(num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape)
         hgym, st = self._hgym, self.storage
         T, N = st.num_transitions_per_env, st.num_envs
@@ -79,7 +80,6 @@ class Distillation(PPO):
         # the step is hgym_ppo_apply's: no learning-rate rule, its own norm pass, the clip as asked for
         self._ppo_cfg = hgym.make_ppo_config(max_grad_norm=self.max_grad_norm, desired_kl=0.0, adaptive=False, world_size=1,
                                              grad_norm_ready=False)
-        self._bc_sums = torch.zeros(2, dtype=torch.float64, device=self.device)
         self._rows = torch.arange(T * N, dtype=torch.int64, device=self.device)
 
     # ------------------------------------------------------------------
@@ -118,20 +118,23 @@ class Distillation(PPO):
         self._update_done()
         if not sync:
             return None, None
-        self.last_behavior_loss = self.behavior_loss_from(self.log_block().cpu())
+        self.read_log(self.log_block().cpu())
         return 0.0, self.last_behavior_loss
 
-    def log_block(self):
-        """opt_state and, behind it, the behaviour loss's two sums: ONE device tensor, one copy to the host."""
-        return torch.cat((self.net.opt_state, self._bc_sums))
+    def _log_parts(self):
+        """opt | bc(2): opt_state and, behind it, the behaviour loss's two sums (every option of PPO's block is refused here)."""
+        return [("opt", self.net.opt_state), ("bc", self._bc_sums)]
 
-    def mirror_loss_from(self, block):
-        return None
+    def read_log(self, block):      # PPO's, and last_behavior_loss; log_scalars: Loss/behavior behind PPO's pairs
+        self.last_behavior_loss = self.behavior_loss_from(block)
+        return super().read_log(block)
+
+    def log_scalars(self):
+        return super().log_scalars() + ([] if self.last_behavior_loss is None else [("Loss/behavior", self.last_behavior_loss)])
 
     def behavior_loss_from(self, block):
         """The mean behaviour loss per Adam step of the last update from a host copy of log_block()."""
-        n = self.net.opt_state.numel()
-        return float(block[n]) / max(float(block[n + 1]), 1.0)
+        return mean_of_sums(self._log.split(block)["bc"])
 
     # ------------------------------------------------------------------ what a cloning run has no use for
     def diagnostics_prepare(self):

@@ -540,7 +540,7 @@ class OnPolicyRunner:
         """compute_returns() + update() -> (mean_value_loss, mean_surrogate_loss), None where not read back (PPO.update_capturable)."""
         def launches(sync=False):
             with torch.inference_mode():
-                if getattr(self.alg, "_rnd", None) is not None or getattr(self.alg, "_smooth", None) is not None:      # (RND and the smoothness term read the state behind the last transition)
+                if self.alg._rnd is not None or self.alg._smooth is not None:      # (RND and the smoothness term read the state behind the last transition)
                     self.alg.compute_returns(critic_obs, last_obs=obs)
                 else:
                     self.alg.compute_returns(critic_obs)
@@ -612,9 +612,8 @@ class OnPolicyRunner:
         if net is None:
             return None
         expired = 0
-        comm = getattr(alg, "_comm", None)
-        if comm is not None and (getattr(alg, "_comm_p2p", False) or getattr(alg, "_comm_direct_used", False)):
-            expired = int(comm.read_status()[0] != 0)
+        if alg._comm is not None and (alg._comm_p2p or alg._comm_direct_used):
+            expired = int(alg._comm.read_status()[0] != 0)
         self.last_replica_digest = dist_utils.check_replicas(net.params, lr=alg.learning_rate, comm_expired=expired, what=what)
         return self.last_replica_digest
 
@@ -627,14 +626,14 @@ class OnPolicyRunner:
             self._log_pin = dict(opt=mk(alg.log_block().numel(), alg.net.opt_state.dtype), ls=mk(env._buf.log_stats.numel(), torch.float32),
                                  std=mk(1, torch.float32))
         pin = self._log_pin
-        pin["opt"][slot].copy_(alg.log_block(), non_blocking=True)      # opt_state (+ the mirror loss's sums): one copy
+        pin["opt"][slot].copy_(alg.log_block(), non_blocking=True)      # opt_state (+ the sums of the options that are on): one copy
         pin["ls"][slot].copy_(env._buf.log_stats, non_blocking=True)
         pin["std"][slot].copy_(self._noise_std(alg.actor_critic).mean().reshape(1), non_blocking=True)
-        comm_words = alg.comm_status_snapshot(slot) if hasattr(alg, "comm_status_snapshot") else None
+        comm_words = alg.comm_status_snapshot(slot)
         env._buf.clear_log_sums()
         done = torch.cuda.Event()
         done.record()
-        return dict(slot=slot, done=done, aux=alg._ppo_cfg.aux_coef > 0.0, comm=comm_words)
+        return dict(slot=slot, done=done, comm=comm_words)
 
     @staticmethod
     def _noise_std(ac):
@@ -654,15 +653,7 @@ class OnPolicyRunner:
         if snap.get("diag") is not None:
             self._diag_publish(pending["it"], snap["diag"])
         pin, slot = self._log_pin, snap["slot"]
-        o = hgym.opt_summary(pin["opt"][slot], snap["aux"])
-        self.alg.last_denoise_loss = o["denoise_loss"]
-        self.alg.last_mirror_loss = self.alg.mirror_loss_from(pin["opt"][slot])
-        if hasattr(self.alg, "smoothness_from"):      # the smoothness regulariser's sums ride at the block's very end
-            self.alg.last_smoothness = self.alg.smoothness_from(pin["opt"][slot])
-        if hasattr(self.alg, "rnd_log_from"):      # RND: the predictor's loss and the reward pass's sums ride at the block's end
-            self.alg.rnd_log_from(pin["opt"][slot])
-        if hasattr(self.alg, "behavior_loss_from"):      # Distillation: the loss rides in the same block
-            self.alg.last_behavior_loss = self.alg.behavior_loss_from(pin["opt"][slot])
+        o = self.alg.read_log(pin["opt"][slot])      # (also leaves the options' losses where log() finds them: alg.log_scalars())
         ep, returns, lengths = hgym.log_stats_summary(pin["ls"][slot], self.env.reward_names, KERNEL_REWARD_TERMS)
         collection_time, learn_time = ev[0].elapsed_time(ev[1]) * 1e-3, ev[1].elapsed_time(ev[2]) * 1e-3
         self.last_collection_time, self.last_learn_time = collection_time, learn_time
@@ -689,26 +680,16 @@ class OnPolicyRunner:
         mean_std = locs["mean_std"] if "mean_std" in locs else float(self._noise_std(self.alg.actor_critic).mean())
         learning_rate = locs["learning_rate"] if "learning_rate" in locs else self.alg.learning_rate
         fps = int(self.num_steps_per_env * self.env.num_envs / iteration_time)
-        behavior = getattr(self.alg, "last_behavior_loss", None)
+        options = self.alg.log_scalars()      # the losses of the options that are on, in the order they are written
+        opt = dict(options)
+        behavior = opt.get("Loss/behavior")
         if behavior is not None:      # Distillation.update() hands its loss back in the surrogate's place; a cloning run has no surrogate
             locs = dict(locs, mean_surrogate_loss=0.0)
         scal("Loss/value_function", locs["mean_value_loss"], locs["it"])
         scal("Loss/surrogate", locs["mean_surrogate_loss"], locs["it"])
         scal("Loss/learning_rate", learning_rate, locs["it"])
-        if getattr(self.alg, "denoise_coef", 0.0) and getattr(self.alg, "last_denoise_loss", None) is not None:
-            scal("Loss/denoise_mse", self.alg.last_denoise_loss, locs["it"])
-        if getattr(self.alg, "_mirror_coef", 0.0) > 0.0 and getattr(self.alg, "last_mirror_loss", None) is not None:
-            scal("Loss/mirror", self.alg.last_mirror_loss, locs["it"])
-        smooth_log = getattr(self.alg, "last_smoothness", None)
-        if smooth_log is not None:
-            scal("Loss/smooth_temporal", smooth_log["temporal"], locs["it"])
-            scal("Loss/smooth_spatial", smooth_log["spatial"], locs["it"])
-        if behavior is not None:
-            scal("Loss/behavior", behavior, locs["it"])
-        rnd_log = getattr(getattr(self.alg, "_rnd", None), "last_log", None)
-        if rnd_log is not None:      # Loss/rnd, Rnd/intrinsic_reward, Rnd/extrinsic_reward, Rnd/weight, Rnd/std
-            for key, value in rnd_log.items():
-                scal(key, value, locs["it"])
+        for tag, value in options:
+            scal(tag, value, locs["it"])
         scal("Policy/mean_noise_std", mean_std, locs["it"])
         scal("Perf/total_fps", fps, locs["it"])
         scal("Perf/collection time", locs["collection_time"], locs["it"])
@@ -727,9 +708,9 @@ class OnPolicyRunner:
                f"""{'Mean action noise std:':>{pad}} {mean_std:.2f}\n""")
         if behavior is not None:
             out += f"""{'Behavior loss:':>{pad}} {behavior:.6f}\n"""
-        if rnd_log is not None:
-            out += (f"""{'RND predictor loss:':>{pad}} {rnd_log['Loss/rnd']:.6f}\n"""
-                    f"""{'Mean intrinsic reward:':>{pad}} {rnd_log['Rnd/intrinsic_reward']:.6f} (weight {rnd_log['Rnd/weight']:.4g})\n""")
+        if "Loss/rnd" in opt:
+            out += (f"""{'RND predictor loss:':>{pad}} {opt['Loss/rnd']:.6f}\n"""
+                    f"""{'Mean intrinsic reward:':>{pad}} {opt['Rnd/intrinsic_reward']:.6f} (weight {opt['Rnd/weight']:.4g})\n""")
         if have_eps:
             out += (f"""{'Mean reward:':>{pad}} {statistics.mean(locs['rewbuffer']):.2f}\n"""
                     f"""{'Mean episode length:':>{pad}} {statistics.mean(locs['lenbuffer']):.2f}\n""")
@@ -819,10 +800,9 @@ class OnPolicyRunner:
             ckpt.check_sidecar(side, self.num_steps_per_env, self.env)      # (refused before anything is changed)
         if loaded is None:
             loaded = torch.load(path, map_location=self.device)
-        rnd = getattr(alg, "_rnd", None)
-        ckpt.check_compatible(loaded, ac, rnd, os.path.basename(str(path)))
-        if rnd is not None:
-            rnd.load_rnd_state_dict(loaded[RND_STATE_KEY])
+        ckpt.check_compatible(loaded, ac, alg._rnd, os.path.basename(str(path)))
+        if alg._rnd is not None:
+            alg._rnd.load_rnd_state_dict(loaded[RND_STATE_KEY])
         if getattr(ac, "empirical_normalization", False):        # the statistics first, then the parameters (whose load refolds the first layers with them)
             alg.net.load_norm_state(dict(obs=loaded[NORM_KEYS[0]], critic_obs=loaded[NORM_KEYS[1]]))
         ac.load_state_dict(loaded["model_state_dict"])

@@ -6,14 +6,23 @@ hgym_ppo_grad (gather + forward + KL + loss + hand-written backward, all on the 
 [when torch.distributed is initialised: one RCCL all-reduce of [flat gradient | minibatch KL]] -> hgym_ppo_apply (adaptive-KL
 learning rate, grad-norm clip, Adam, operand-shadow refresh).  The host reads the loss sums back once per update.
 """
+import ctypes as C
+import math
 import os
 
 import torch
 import torch.nn as nn  # noqa: F401  (kept importable like the reference module)
 
 from .actor_critic import ActorCritic
+from .log_block import LogBlock, mean_of_sums
 from .rollout_storage import RolloutStorage, mirror_pair_rows
 from . import dist_utils
+from . import rnd as rnd_module
+from . import smoothness as smooth_module
+
+
+def _struct_bytes(s):      # a ctypes structure's contents, hashable
+    return bytes(C.string_at(C.addressof(s), C.sizeof(s)))
 
 
 class _DeviceAdam:
@@ -124,6 +133,13 @@ class PPO:
         # True while a runner has the env store the scalar columns and bump the sampling step itself (transition_sink)
         self.env_stores_transitions = False
         self.comm_timing = None      # a list: update() appends a pair of HIP events around the wait for the gradient exchange
+        # every option's state, "off" until init_storage reads the option: nobody probes for these
+        self._rnd = self._smooth = self._symmetry = self._obs_norm = None
+        self._augment, self._mirror_coef, self._adv_mode = False, 0.0, "batch"
+        self._mirror_target = self._mirror_sums = None
+        self._comm, self._comm_p2p, self._comm_direct_used = None, False, False
+        self._log = None      # the LogBlock behind log_block() / read_log()
+        self.last_denoise_loss = self.last_mirror_loss = self.last_smoothness = None
         self._world = 1
         self._rank = 0
         if torch.distributed.is_available() and torch.distributed.is_initialized():
@@ -142,37 +158,45 @@ class PPO:
         if self.net is not None:
             self.net.opt_state[self._hgym._lib.OPT_LR] = v
 
+    @staticmethod
+    def check_setup(num_envs, num_transitions_per_env, num_mini_batches, num_actor_obs, world=1, symmetry=None, symmetry_augmentation=True,
+                    mirror_loss_coef=0.0, advantage_normalization="batch", rnd=None, smoothness=None):
+        """What init_storage refuses, as a function that needs no device (ValueError each), in the order the refusals win: an unknown
+        advantage mode; a mirror coefficient that is negative or not finite, or one > 0 without `symmetry`; what PPO.rnd and PPO.smoothness
+        refuse (their own check_setup); per-minibatch advantages over minibatches of fewer than 2 rows."""
+        if advantage_normalization not in PPO.ADVANTAGE_NORMALIZATIONS:
+            raise ValueError("PPO.advantage_normalization=%r: one of %s" % (advantage_normalization, ", ".join(PPO.ADVANTAGE_NORMALIZATIONS)))
+        coef = float(mirror_loss_coef)
+        if not (coef >= 0.0 and math.isfinite(coef)):
+            raise ValueError("PPO.mirror_loss_coef=%r: must be finite and >= 0" % (mirror_loss_coef,))
+        if coef > 0.0 and symmetry is None:
+            raise ValueError("PPO.mirror_loss_coef=%r needs the mirror tables: set PPO.symmetry to a MirrorSpec" % (mirror_loss_coef,))
+        augment = symmetry is not None and bool(symmetry_augmentation)
+        if rnd is not None:
+            rnd_module.check_setup(world, symmetry if augment else None, augment)
+        if smooth_module.parse_config(smoothness, num_actor_obs) is not None:
+            smooth_module.check_setup(world, symmetry)
+        mb = ((2 if augment else 1) * num_envs * num_transitions_per_env) // num_mini_batches
+        if advantage_normalization == "minibatch" and mb < 2:      # (rsl_rl would divide by the NaN deviation of one value)
+            raise ValueError("PPO.advantage_normalization='minibatch' needs minibatches of at least 2 rows (they have %d)" % mb)
+
     def init_storage(self, num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape):
         import hgym
         self._hgym = hgym
-        if self.advantage_normalization not in self.ADVANTAGE_NORMALIZATIONS:
-            raise ValueError("PPO.advantage_normalization=%r: one of %s" % (self.advantage_normalization, ", ".join(self.ADVANTAGE_NORMALIZATIONS)))
+        ac = self.actor_critic
+        # (PPO.check_setup by name: a subclass has refusals of its own under that name, and runs them ahead of this call)
+        PPO.check_setup(num_envs, num_transitions_per_env, self.num_mini_batches, ac.num_actor_obs, self._world, self.symmetry,
+                        self.symmetry_augmentation, self.mirror_loss_coef, self.advantage_normalization, self.rnd, self.smoothness)
         self._adv_mode = self.advantage_normalization
         self.storage = RolloutStorage(num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape, self.device)
-        import math
-        coef = float(self.mirror_loss_coef)
-        if not (coef >= 0.0 and math.isfinite(coef)):
-            raise ValueError("PPO.mirror_loss_coef=%r: must be finite and >= 0" % (self.mirror_loss_coef,))
-        if coef > 0.0 and self.symmetry is None:
-            raise ValueError("PPO.mirror_loss_coef=%r needs the mirror tables: set PPO.symmetry to a MirrorSpec" % (self.mirror_loss_coef,))
-        self._mirror_coef = coef
+        self._mirror_coef = coef = float(self.mirror_loss_coef)
         self._augment = self.symmetry is not None and bool(self.symmetry_augmentation)
         self._symmetry = self.symmetry if (self._augment or coef > 0.0) else None      # neither half asked for: symmetry off
-        self._rnd = None
-        if self.rnd is not None:
-            from . import rnd as rnd_module
-            rnd_module.check_setup(self._world, self.symmetry if self._augment else None, self._augment)
-        from . import smoothness as smooth_module
-        self._smooth = smooth_module.parse_config(self.smoothness, self.actor_critic.num_actor_obs, torch.initial_seed())
-        if self._smooth is not None:
-            smooth_module.check_setup(self._world, self.symmetry)      # (Distillation.init_storage refuses it ahead of this)
+        self._smooth = smooth_module.parse_config(self.smoothness, ac.num_actor_obs, torch.initial_seed())
         if self._symmetry is not None:
             self.storage.enable_mirror(self._symmetry)      # (before enable_shadow and before anything binds a slot's address)
-        ac = self.actor_critic
         mb = ((2 if self._augment else 1) * num_envs * num_transitions_per_env) // self.num_mini_batches
         if self._adv_mode == "minibatch":
-            if mb < 2:      # (rsl_rl would divide by the NaN deviation of one value)
-                raise ValueError("PPO.advantage_normalization='minibatch' needs minibatches of at least 2 rows (they have %d)" % mb)
             self.storage.enable_minibatch_advantages(self.num_mini_batches, mb)      # (behind enable_mirror: the enlarged column's layout)
         aux = getattr(ac, "denoiser_hidden_dims", None)
         cfg = hgym.make_net_config(ac.num_actor_obs, ac.num_critic_obs, ac.num_actions, ac.actor_hidden_dims, ac.critic_hidden_dims,
@@ -183,7 +207,6 @@ class PPO:
         # data-parallel update: the exchange is chosen here, once (HGYM_COMM=auto: the direct kernel over peer mappings is set up,
         # checked and timed against the collective, and used when it is faster; any failure falls back on every rank -- dist_utils).
         # With the direct exchange the gradient vector lives in peer-mapped memory.
-        import ctypes as C
         self._comm = dist_utils.make_comm(int(hgym._lib.lib.hgym_net_param_count(C.byref(cfg))) + 1, self.device)
         self._comm_p2p = self._comm is not None and dist_utils.comm_backend() == "p2p"
         self._comm_pin = None
@@ -211,13 +234,9 @@ class PPO:
                                              grad_norm_ready=self._obs_norm is None,
                                              aux_coef=self.denoise_coef if aux else 0.0,
                                              clipped_value_loss=self.use_clipped_value_loss, mirror_coef=coef)
-        self.last_denoise_loss = None
-        self.last_mirror_loss = None
-        self._mirror_target = self._mirror_sums = None
         if coef > 0.0:      # the pre-pass's output (one minibatch of raw partner means) and the two sums behind the per-update loss sums
             self._mirror_target = torch.zeros(max(mb, 1) * ac.num_actions, dtype=torch.float32, device=self.device)
             self._mirror_sums = torch.zeros(2, dtype=torch.float64, device=self.device)
-        self.last_smoothness = None
         if self._smooth is not None:      # the successor map of a whole permutation, the two pre-passes' outputs, the perturbed rows, the four sums
             self.storage.enable_smoothness(self.num_mini_batches * mb, mb, ac.num_actor_obs, ac.num_actions, self._smooth["noise_std"])
         self._sample_step = torch.zeros(1, dtype=torch.int64, device=self.device)
@@ -236,6 +255,18 @@ class PPO:
         if self.rnd is not None:      # two more NetBuffers at the PPO precision, the reward pass's block, the storage's rnd_* fields
             self._rnd = self.rnd.bind(int(self.net.cfg.precision), max(mb, 1), self.device, num_envs)
             self.storage.enable_rnd(self._rnd.num_states, self._rnd.num_outputs)
+        self._log = LogBlock(self._log_parts())
+
+    def _log_parts(self):
+        """opt | mirror(2) | rnd_sums(2) | rnd_block(RND_HEADER) | smooth(4): opt_state, then the sums of every option that is on."""
+        parts = [("opt", self.net.opt_state)]
+        if self._mirror_sums is not None:
+            parts.append(("mirror", self._mirror_sums))
+        if self._rnd is not None:      # the predictor loss's two sums and the head of the reward pass's block
+            parts += self._rnd.log_parts()
+        if self._smooth is not None:
+            parts.append(("smooth", self.storage._smooth["sums"]))
+        return parts
 
     def seek(self, iteration, steps_per_iteration):
         """Position the device generators' counters where a run that has done `iteration` learning iterations has them
@@ -347,7 +378,6 @@ class PPO:
 
     def process_env_step(self, rewards, dones, infos, stored=False):
         """`stored=True`: the env already wrote this step's rewards / dones slot (transition_sink)."""
-        import ctypes as C
         L = self._hgym._lib
         st, s = self.storage, self.storage.step
         if s >= st.num_transitions_per_env:
@@ -423,26 +453,21 @@ class PPO:
         return bool(self._comm is not None and self._comm_p2p and not self.comm_flip and getattr(self._comm, "capturable", False))
 
     def update_graph_key(self):
-        """Everything host-side that compute_returns() / update() bake into their launches: a change re-captures."""
-        import ctypes as C
-        return (bytes(C.string_at(C.addressof(self._ppo_cfg), C.sizeof(self._ppo_cfg))), self.num_learning_epochs, self.num_mini_batches,
-                float(self.gamma), float(self.lam), self.permutation, self._perm_seed, id(self.storage), id(self.net),
-                bool(dist_utils.active()), bool(self._comm_p2p), bytes(C.string_at(C.addressof(self.net.cfg), C.sizeof(self.net.cfg))),
-                self.storage._obs_bf16 is not None, bool(self.comm_flip), self._world,
-                None if self._symmetry is None else self._symmetry.key(),
-                # the mirror loss (its coefficient is also part of _ppo_cfg's bytes above), whether the batch is doubled, the scratch the launches name
-                self._mirror_coef, self._augment,
-                None if self._mirror_target is None else (self._mirror_target.data_ptr(), self._mirror_sums.data_ptr()),
-                # the smoothness regulariser: its coefficients and seed, and the scratch the launches name (ahead of RND's entry, which tests read from the end)
-                None if self._smooth is None else (self._smooth["temporal_coef"], self._smooth["spatial_coef"], self._smooth["seed"])
-                + tuple(t.data_ptr() for t in self.storage.smooth_buffers()),
-                # RND: its nets, block and configuration bytes (ahead of the three entries tests read from the end)
-                None if self._rnd is None else (id(self._rnd), id(self._rnd.nets[0]), id(self._rnd.nets[1]), self._rnd.block.data_ptr(),
-                                                bytes(C.string_at(C.addressof(self._rnd.rnd_cfg), C.sizeof(self._rnd.rnd_cfg)))),
-                # how the advantages are standardised, and the column and scratch the per-minibatch pass names
-                self._adv_mode,
-                None if self.storage.advantages_mb is None else (self.storage.advantages_mb.data_ptr(), self.storage._adv_mb_scratch.data_ptr()),
-                self._obs_norm)      # (stays the last entry: tests/test_obs_norm_runner_gpu.py reads it there)
+        """Everything host-side that compute_returns() / update() bake into their launches, as (name, value) pairs: a change re-captures.
+        dict(key)[name] reads an entry; an option's entry is None while the option is off and comes from where the option lives."""
+        st = self.storage
+        return (("ppo_cfg", _struct_bytes(self._ppo_cfg)), ("num_learning_epochs", self.num_learning_epochs),
+                ("num_mini_batches", self.num_mini_batches), ("gamma", float(self.gamma)), ("lam", float(self.lam)),
+                ("permutation", self.permutation), ("perm_seed", self._perm_seed), ("storage", id(st)), ("net", id(self.net)),
+                ("dist_active", bool(dist_utils.active())), ("comm_p2p", bool(self._comm_p2p)), ("net_cfg", _struct_bytes(self.net.cfg)),
+                ("shadows", st._obs_bf16 is not None), ("comm_flip", bool(self.comm_flip)), ("world", self._world),
+                ("symmetry", None if self._symmetry is None else self._symmetry.key()),
+                # the mirror loss (its coefficient is also part of ppo_cfg's bytes), whether the batch is doubled, the scratch the launches name
+                ("mirror_coef", self._mirror_coef), ("augment", self._augment),
+                ("mirror_scratch", None if self._mirror_target is None else (self._mirror_target.data_ptr(), self._mirror_sums.data_ptr())),
+                ("smoothness", smooth_module.graph_key(self._smooth, st.smooth_buffers())),
+                ("rnd", None if self._rnd is None else self._rnd.graph_key()),
+                ("adv_mode", self._adv_mode), ("adv_scratch", st.minibatch_advantages_key()), ("obs_norm", self._obs_norm))
 
     def rollout_graph_key(self):
         """Everything of this side that a rollout bakes into its launches: the storage's slots, the sink's gamma (BY VALUE), the shadows."""
@@ -566,49 +591,58 @@ class PPO:
         self._update_done()
         if not sync:
             return None, None
-        o = self.log_block().cpu()             # the one host read-back of the update
+        block = self.log_block().cpu()         # the one host read-back of the update
         self.check_comm()                      # (the stream is idle now: reading the exchange's status costs one small copy)
-        self.last_mirror_loss = self.mirror_loss_from(o)
-        self.last_smoothness = self.smoothness_from(o)
-        self.rnd_log_from(o)
-        o = hgym.opt_summary(o, self._ppo_cfg.aux_coef > 0.0)
-        self.last_denoise_loss = o["denoise_loss"]
+        o = self.read_log(block)
         return o["mean_value_loss"], o["mean_surrogate_loss"]
 
     def log_block(self):
-        """What a log block reads after an update, as ONE device tensor (one copy to the host): opt_state, behind it the mirror
-        loss's two sums when that loss is on, and last RND's tail when that is on."""
-        parts = [self.net.opt_state] + ([] if self._mirror_sums is None else [self._mirror_sums])
-        if getattr(self, "_rnd", None) is not None:      # the predictor loss's two sums and the head of the reward pass's block
-            parts.append(self._rnd.log_tail())
-        if getattr(self, "_smooth", None) is not None:      # the regulariser's four sums, behind what was there before
-            parts.append(self.storage._smooth["sums"])
-        return parts[0] if len(parts) == 1 else torch.cat(parts)
+        """What a log line reads after an update, as ONE device tensor (one copy to the host): the parts init_storage listed
+        (_log_parts); opt_state itself when no option adds a part."""
+        return self._log.device()
+
+    def read_log(self, block):
+        """A host copy of log_block() -> hgym.opt_summary's dict; sets last_denoise_loss, last_mirror_loss, last_smoothness and RND's
+        last_log on the way.  The one reader behind update(sync=True) and the runner's asynchronous log."""
+        self.last_mirror_loss = self.mirror_loss_from(block)
+        self.last_smoothness = self.smoothness_from(block)
+        self.rnd_log_from(block)
+        o = self._hgym.opt_summary(self._log.split(block)["opt"], self._ppo_cfg.aux_coef > 0.0)
+        self.last_denoise_loss = o["denoise_loss"]
+        return o
+
+    def log_scalars(self):
+        """The optional loss scalars of the last read_log() as ordered (tag, value) pairs, for the runner's writer."""
+        out = []
+        if self.denoise_coef and self.last_denoise_loss is not None:
+            out.append(("Loss/denoise_mse", self.last_denoise_loss))
+        if self._mirror_coef > 0.0 and self.last_mirror_loss is not None:
+            out.append(("Loss/mirror", self.last_mirror_loss))
+        if self.last_smoothness is not None:
+            out += [("Loss/smooth_temporal", self.last_smoothness["temporal"]), ("Loss/smooth_spatial", self.last_smoothness["spatial"])]
+        if self._rnd is not None and self._rnd.last_log is not None:      # Loss/rnd, Rnd/intrinsic_reward, Rnd/extrinsic_reward, Rnd/weight, Rnd/std
+            out += list(self._rnd.last_log.items())
+        return out
 
     def rnd_log_from(self, block):
         """Loss/rnd and the Rnd/* numbers from a host copy of log_block() (RandomNetworkDistillation.log_from); None when RND is off."""
-        rnd = getattr(self, "_rnd", None)
-        if rnd is None:
-            return None
-        end = block.numel() - (4 if getattr(self, "_smooth", None) is not None else 0)
-        return rnd.log_from(block[end - rnd.LOG_DOUBLES:end])
+        p = self._log.split(block)
+        return None if self._rnd is None else self._rnd.log_from(torch.cat((p["rnd_sums"], p["rnd_block"])))
 
     def smoothness_from(self, block):
         """{temporal, spatial, valid_fraction} from a host copy of log_block(): the mean plain MSE per minibatch of either term and the share
         of drawn rows with a successor; None when the regulariser is off."""
-        if getattr(self, "_smooth", None) is None:
+        sums = self._log.split(block).get("smooth")
+        if sums is None:
             return None
-        t, s, w, n = (float(x) for x in block[block.numel() - 4:])
+        t, s, w, n = (float(x) for x in sums)
         mb = self.storage._smooth["target_next"].numel() // self.actor_critic.num_actions
         n = max(n, 1.0)
         return dict(temporal=t / n, spatial=s / n, valid_fraction=w / (mb * n))
 
     def mirror_loss_from(self, block):
         """The mean mirror MSE per minibatch from a host copy of log_block(); None when the loss is off."""
-        if self._mirror_sums is None:
-            return None
-        n = self.net.opt_state.numel()
-        return float(block[n]) / max(float(block[n + 1]), 1.0)
+        return mean_of_sums(self._log.split(block).get("mirror"))
 
     def normalizer_step(self):
         """The normaliser's one step per iteration, at the end of update(), ahead of storage.clear(): accumulate the T * N stored raw

@@ -10,6 +10,7 @@ the target only ever runs hgym_mlp_forward; the predictor is trained by hgym_bc_
 
 Set `PPO.rnd = RandomNetworkDistillation(...)` before init_storage (OnPolicyRunner does it from train_cfg["algorithm"]["rnd_cfg"]).
 """
+import ctypes as C
 import math
 
 import torch
@@ -261,7 +262,6 @@ class RandomNetworkDistillation(nn.Module):
         plain path (act / process_env_step with the env's own tensors) add_transitions fills slots 0 .. T - 1 only, and the caller's
         bootstrap observation -- compute_returns' last_critic_obs, or last_obs for a state taken from "obs" -- is copied into row T of
         rnd_states here.  slot_T_written False and no such observation: RuntimeError, because the storage's slot T is then stale."""
-        import ctypes as C
         from hgym import _lib as L
         st = storage
         T, N = st.num_transitions_per_env, st.num_envs
@@ -318,12 +318,21 @@ class RandomNetworkDistillation(nn.Module):
             nz["m"].copy_(nz["mean"])
             nz["s"].copy_(1.0 / (nz["var"].sqrt() + STATE_NORM_EPS))
 
+    def graph_key(self):
+        """PPO.update_graph_key's entry: the nets, the block and the configuration bytes the captured launches name."""
+        return (id(self), id(self.nets[0]), id(self.nets[1]), self.block.data_ptr(),
+                bytes(C.string_at(C.addressof(self.rnd_cfg), C.sizeof(self.rnd_cfg))))
+
     # ------------------------------------------------------------------ logging
     LOG_DOUBLES = 2 + 16      # the loss's two sums, then the head of the block
 
-    def log_tail(self):
+    def log_parts(self):
+        """The two adjacent parts of PPO's log block (LogBlock.add), together log_tail()'s layout."""
         from hgym import _lib as L
-        return torch.cat((self.sums, self.block[:L.RND_HEADER]))
+        return ("rnd_sums", self.sums), ("rnd_block", self.block[:L.RND_HEADER])
+
+    def log_tail(self):
+        return torch.cat([t for _, t in self.log_parts()])
 
     def log_from(self, tail):
         """The log numbers from a host copy of log_tail(): Loss/rnd (mean MSE per predictor step) and the block's sums as per-row means."""

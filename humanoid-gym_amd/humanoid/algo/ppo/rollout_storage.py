@@ -90,6 +90,10 @@ class RolloutStorage:
         hgym.adv_normalize_minibatches(perm, adv, self.advantages_mb, segments, self._adv_mb_scratch)
         return self.advantages_mb
 
+    def minibatch_advantages_key(self):
+        """PPO.update_graph_key's entry: the column and the scratch the per-minibatch pass names; None without them."""
+        return None if self.advantages_mb is None else (self.advantages_mb.data_ptr(), self._adv_mb_scratch.data_ptr())
+
     _smooth = None      # the smoothness regulariser's buffers (enable_smoothness), None without it
 
     def enable_smoothness(self, perm_len, mb, num_obs, num_actions, noise_std):

@@ -66,6 +66,14 @@ def check_setup(world=1, symmetry=None, distillation=False):
         raise ValueError("PPO.smoothness does not support Distillation")
 
 
+def graph_key(cfg, buffers):
+    """PPO.update_graph_key's entry: the coefficients and the seed of a parse_config() dict (None: off) and the scratch the launches name
+    (RolloutStorage.smooth_buffers)."""
+    if cfg is None:
+        return None
+    return (cfg["temporal_coef"], cfg["spatial_coef"], cfg["seed"]) + tuple(t.data_ptr() for t in buffers)
+
+
 def env_noise_std(env_cfg, noise_scale_vec, num_obs):
     """The env's own sensor noise per stacked observation column: noise_scale_vec * cfg.noise.noise_level tiled over the frames (a list of
     num_obs floats), or None when the env states none."""

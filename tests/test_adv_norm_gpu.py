@@ -322,7 +322,7 @@ def test_runner_captured_as_eager_with_diagnostics(monkeypatch, keys, mode):
             assert torch.isfinite(t).all(), (graph_update, k)
         if graph_update == "0":
             key = alg.update_graph_key()
-            assert key[-1] is alg._obs_norm and mode in key
+            assert dict(key)["obs_norm"] is alg._obs_norm and dict(key)["adv_mode"] == mode
             keep, alg._adv_mode = alg._adv_mode, "batch"
             assert alg.update_graph_key() != key      # another mode re-captures
             alg._adv_mode = keep
@@ -342,7 +342,7 @@ def test_batch_mode_is_the_default_and_touches_nothing_new(monkeypatch):
         monkeypatch.setattr(hgym, "adv_normalize_minibatches", lambda *a, **k: (calls.append(1), real(*a, **k)))
         assert alg._adv_mode == "batch" and alg.storage.advantages_mb is None and alg.storage._adv_mb_scratch is None
         key = alg.update_graph_key()
-        assert key[-3:-1] == ("batch", None)
+        assert (dict(key)["adv_mode"], dict(key)["adv_scratch"]) == ("batch", None)
         idx_log, grad_log = _record_batches(monkeypatch, alg)
         alg.update()
         torch.cuda.synchronize()

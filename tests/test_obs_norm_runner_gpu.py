@@ -138,7 +138,7 @@ def test_captured_update_equals_eager_update(monkeypatch):
     assert float(a.alg.net.norm_view("header")[2]) == 3 * T * N
     assert _same(sa, sb)
     key_on, key_off = a.alg.update_graph_key(), _runner(norm=False).alg.update_graph_key()
-    assert key_on[-1] == (1e-2, None) and key_off[-1] is None
+    assert dict(key_on)["obs_norm"] == (1e-2, None) and dict(key_off)["obs_norm"] is None
 
 
 def test_checkpoints_carry_the_statistics_and_an_exact_resume_is_the_run(tmp_path, monkeypatch):

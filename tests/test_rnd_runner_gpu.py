@@ -7,6 +7,7 @@ rollouts of 4 steps, 2 minibatches; the predictor and the target on the fused bf
   * ten predictor steps on fixed stored rows lower the MSE;
   * the captured update replays what the eager update does, the three nets and the block included;
   * checkpoints carry rnd_state_dict, load() refuses both mismatches by name, and an exact resume (2 + 2 iterations) is the run of 4;
+  * with the mirror loss on beside it, the log block holds both tails and each reader finds its own by name;
   * with PPO.rnd = None nothing of the feature exists."""
 import copy
 import os
@@ -24,7 +25,7 @@ NETS = dict(fused=dict(predictor_hidden_dims=[256, 128, 128], target_hidden_dims
             layer=dict(predictor_hidden_dims=[64, 32], target_hidden_dims=[48, 32], num_outputs=5))
 
 
-def _runner(tmp=None, rnd=None, seed=31, exact=False, save_interval=50):
+def _runner(tmp=None, rnd=None, seed=31, exact=False, save_interval=50, mirror_loss_coef=None):
     from humanoid.algo import PPO
     from humanoid.envs import task_registry
     from humanoid.utils import get_args
@@ -40,6 +41,8 @@ def _runner(tmp=None, rnd=None, seed=31, exact=False, save_interval=50):
         train_cfg.runner.exact_resume = True
     if rnd is not None:
         train_cfg.algorithm.rnd_cfg = rnd
+    if mirror_loss_coef is not None:      # the mirror loss WITHOUT the augmentation: the one form of symmetry RND accepts
+        train_cfg.algorithm.symmetry, train_cfg.algorithm.mirror_loss_coef = False, mirror_loss_coef
     env, _ = task_registry.make_env(name=TASK, args=args, env_cfg=env_cfg)
     runner, _ = task_registry.make_alg_runner(env=env, args=args, train_cfg=train_cfg, log_root=None if tmp is None else str(tmp))
     assert (runner.alg._rnd is not None) == (rnd is not None) and PPO.rnd is None
@@ -170,9 +173,10 @@ def test_captured_update_equals_eager_update(monkeypatch, state_norm):
         assert float(a.alg._rnd.norm["count"]) == 3 * T * N
     key = a.alg.update_graph_key()
     off = _runner().alg.update_graph_key()
-    # the RND entry sits before the three entries existing tests read from the end (the advantage mode, its scratch, _obs_norm)
-    assert len(key) == len(off) and key[-1] is None and key[-3:-1] == ("batch", None) and key[-4] is not None and off[-4] is None
-    assert [i for i, (x, y) in enumerate(zip(key, off)) if type(x) is not type(y)] == [len(key) - 4]
+    on, no = dict(key), dict(off)      # entries are read by name
+    assert [n for n, _ in key] == [n for n, _ in off] and len(on) == len(key)
+    assert on["obs_norm"] is None and (on["adv_mode"], on["adv_scratch"]) == ("batch", None) and on["rnd"] is not None and no["rnd"] is None
+    assert [n for n in on if type(on[n]) is not type(no[n])] == ["rnd"]
 
 
 def test_checkpoints_and_exact_resume(tmp_path):
@@ -245,6 +249,25 @@ def test_separate_learn_calls_replay_the_cloning_step_correctly():
     b = _runner(rnd=cfg)
     b.learn(num_learning_iterations=4, init_at_random_ep_len=True)
     assert _same(_policy_state(a) + _rnd_state(a), _policy_state(b) + _rnd_state(b))
+
+
+def test_mirror_loss_and_rnd_share_the_log_block():
+    """The mirror loss (no augmentation) together with RND: both tails lie behind opt_state and each reader finds its own by name."""
+    r = _runner(rnd=dict(weight=0.5, **NETS["fused"]), mirror_loss_coef=0.5)
+    alg = r.alg
+    assert alg._mirror_coef == 0.5 and alg._augment is False and alg._rnd is not None and alg._smooth is None
+    r.learn(num_learning_iterations=1, init_at_random_ep_len=True)
+    block = alg.log_block().cpu()
+    assert block.numel() == alg._log.numel() == L.OPT_STATE + 2 + alg._rnd.LOG_DOUBLES
+    parts = alg._log.split(block)
+    assert list(parts) == ["opt", "mirror", "rnd_sums", "rnd_block"]
+    assert torch.equal(parts["opt"], alg.net.opt_state.cpu()) and torch.equal(parts["mirror"], alg._mirror_sums.cpu())
+    mirror, rnd = alg.mirror_loss_from(block), alg.rnd_log_from(block)
+    print("Loss/mirror %.4e" % mirror, rnd)
+    assert np.isfinite(mirror) and mirror > 0
+    assert set(rnd) == {"Loss/rnd", "Rnd/intrinsic_reward", "Rnd/extrinsic_reward", "Rnd/weight", "Rnd/std"}
+    assert all(np.isfinite(v) for v in rnd.values()) and rnd["Loss/rnd"] > 0 and rnd["Rnd/intrinsic_reward"] > 0 and rnd["Rnd/weight"] == 0.5
+    assert alg.smoothness_from(block) is None
 
 
 def test_off_means_absent():
