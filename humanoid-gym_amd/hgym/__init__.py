@@ -80,3 +80,49 @@ def adv_normalize_minibatches(idx, adv, out, segments, scratch):
     check(lib.hgym_adv_normalize_minibatches(segments, seg_len, _lib.i64ptr(idx), _lib.fptr(adv), _lib.fptr(out), int(adv.numel()),
                                              _lib.f64ptr(scratch), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
           "hgym_adv_normalize_minibatches")
+
+
+def _value_norm_args(x, block, eps=None):
+    import torch
+    assert x.dtype == torch.float32 and x.is_cuda and x.is_contiguous()
+    assert block.dtype == torch.float64 and block.is_cuda and block.is_contiguous() and block.numel() >= _lib.VALUE_NORM_BLOCK_DOUBLES
+    return None if eps is None else float(eps)
+
+
+def value_denormalize(src, block, eps, out=None):
+    """hgym_value_denormalize on the current stream: out[i] = src[i] * scale_f + mean_f, mean_f = (float)block[1], scale_f =
+    (float)sqrt(block[2]) + eps.  src, out float32 contiguous device tensors of one size (out=None: in place); block: _lib.value_norm_block.
+    -> out."""
+    import ctypes as C
+    import torch
+    out = src if out is None else out
+    eps = _value_norm_args(src, block, eps)
+    _value_norm_args(out, block)
+    assert out.numel() == src.numel()
+    check(lib.hgym_value_denormalize(int(src.numel()), _lib.fptr(src), _lib.fptr(out), _lib.f64ptr(block), eps,
+                                     C.c_void_p(torch.cuda.current_stream().cuda_stream)), "hgym_value_denormalize")
+    return out
+
+
+def value_norm_merge(returns, block, scratch):
+    """hgym_value_norm_merge on the current stream: the fp64 statistics of the float32 values `returns` (fixed order: the same bits in every
+    run) -> scratch[0:3] = n, mean, population variance, merged into block = (count, mean, var).  scratch:
+    _lib.value_norm_scratch(returns.numel(), device), zero-filled once, reusable from call to call."""
+    import ctypes as C
+    import torch
+    _value_norm_args(returns, block)
+    assert scratch.dtype == torch.float64 and scratch.is_cuda and scratch.is_contiguous()
+    assert scratch.numel() >= _lib.value_norm_scratch_doubles(returns.numel())
+    check(lib.hgym_value_norm_merge(int(returns.numel()), _lib.fptr(returns), _lib.f64ptr(block), _lib.f64ptr(scratch),
+                                    C.c_void_p(torch.cuda.current_stream().cuda_stream)), "hgym_value_norm_merge")
+
+
+def value_normalize(x, block, eps):
+    """hgym_value_normalize on the current stream: x[i] = (x[i] - mean_f) / scale_f in place (the floats as value_denormalize forms them).
+    -> x."""
+    import ctypes as C
+    import torch
+    eps = _value_norm_args(x, block, eps)
+    check(lib.hgym_value_normalize(int(x.numel()), _lib.fptr(x), _lib.f64ptr(block), eps, C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+          "hgym_value_normalize")
+    return x

@@ -232,6 +232,9 @@ SYMBOLS = {
                              c_float_p, c_float_p, c_f64_p, C.c_void_p]),
     "hgym_adv_normalize": (C.c_int32, [C.c_int64, c_float_p, c_f64_p, C.c_void_p]),
     "hgym_adv_normalize_minibatches": (C.c_int32, [C.c_int32, C.c_int64, c_i64_p, c_float_p, c_float_p, C.c_int64, c_f64_p, C.c_void_p]),
+    "hgym_value_denormalize": (C.c_int32, [C.c_int64, c_float_p, c_float_p, c_f64_p, C.c_float, C.c_void_p]),
+    "hgym_value_norm_merge": (C.c_int32, [C.c_int64, c_float_p, c_f64_p, c_f64_p, C.c_void_p]),
+    "hgym_value_normalize": (C.c_int32, [C.c_int64, c_float_p, c_f64_p, C.c_float, C.c_void_p]),
     "hgym_rnd_block_init": (C.c_int32, [C.c_int32, c_f64_p, C.c_void_p]),
     "hgym_rnd_rewards": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, _P(RndConfig), c_f64_p,
                                      C.c_void_p]),
@@ -400,6 +403,29 @@ def adv_mb_scratch(segments, seg_len, device):
     """The `scratch` buffer of hgym_adv_normalize_minibatches, zero-filled."""
     import torch
     return torch.zeros(adv_mb_scratch_doubles(segments, seg_len), dtype=torch.float64, device=device)
+
+
+# value-target normalisation (include/hgym.h: HGYM_VALUE_NORM_*)
+VALUE_NORM_BLOCK_DOUBLES, VALUE_NORM_CHUNK, VALUE_NORM_MAX_BLOCKS = 3, 1024, 1024
+VALUE_NORM_COUNT, VALUE_NORM_MEAN, VALUE_NORM_VAR = range(3)      # the block's slots
+VALUE_NORM_BATCH, VALUE_NORM_TICKET, VALUE_NORM_PARTIALS = 0, 3, 4      # the scratch's
+
+
+def value_norm_scratch_doubles(n):
+    """HGYM_VALUE_NORM_SCRATCH_DOUBLES(n) of include/hgym.h."""
+    return VALUE_NORM_PARTIALS + 2 * ((int(n) + VALUE_NORM_CHUNK - 1) // VALUE_NORM_CHUNK)
+
+
+def value_norm_scratch(n, device):
+    """The `scratch` buffer of hgym_value_norm_merge for n values, zero-filled."""
+    import torch
+    return torch.zeros(value_norm_scratch_doubles(n), dtype=torch.float64, device=device)
+
+
+def value_norm_block(device):
+    """The `block` of the hgym_value_* calls in its initial state: count 0, mean 0, var 1."""
+    import torch
+    return torch.tensor([0.0, 0.0, 1.0], dtype=torch.float64, device=device)
 
 
 # the diagnostics pass's block (include/hgym.h: HGYM_DIAG_*)

@@ -16,6 +16,7 @@ import torch
 
 NORM_KEYS = ("obs_norm_state_dict", "critic_obs_norm_state_dict")      # a checkpoint of a run with empirical_normalization carries both
 RND_STATE_KEY = "rnd_state_dict"      # what a checkpoint of a run with rnd_cfg carries besides the reference's four keys
+VALUE_NORM_KEY = "value_norm_state_dict"      # what a checkpoint of a run with PPO.value_normalization carries: count, mean, var, eps
 NORM_COUNT = 2      # NetBuffers.norm_view("header"): eps, until, then count of statistics k at NORM_COUNT + k, of L.NORM_HEADER_DOUBLES doubles
 
 
@@ -91,11 +92,14 @@ def write_checkpoint(ck, path, side=None):
 # ------------------------------------------------------------------ what a checkpoint contains
 def extra_entries(alg):
     """What a checkpoint carries beyond the reference's four keys, in file order: the two normaliser dicts (NORM_KEYS) of a policy with
-    empirical_normalization, then RND_STATE_KEY of a run with rnd_cfg.  Reads the device (the blocking path)."""
+    empirical_normalization, then RND_STATE_KEY of a run with rnd_cfg, then VALUE_NORM_KEY of a run with PPO.value_normalization.  Reads the
+    device (the blocking path)."""
     ac, rnd = alg.actor_critic, alg._rnd
     extra = dict(ac.norm_state_dicts()) if hasattr(ac, "norm_state_dicts") else {}
     if rnd is not None:
         extra[RND_STATE_KEY] = rnd.rnd_state_dict()
+    if getattr(alg, "value_normalizer", None) is not None:
+        extra[VALUE_NORM_KEY] = alg.value_normalizer.state_dict()
     return extra
 
 
@@ -111,9 +115,10 @@ def param_layout(state_dict, params):
     return layout
 
 
-def assemble(buf, layout, opt_layout, group, it, infos, norm=None):
+def assemble(buf, layout, opt_layout, group, it, infos, norm=None, value_norm=None):
     """The checkpoint dict from a host snapshot, key for key what the blocking path saves.  buf: flat `params`, `m`, `v` (fp32) and `opt`
     (opt_state), and with norm = ((num_obs, num_priv), (eps, until)) also `norm`: the header, then mean / var of both statistics (fp64).
+    value_norm = eps: `value_norm` holds the three doubles (count, mean, var) -> VALUE_NORM_KEY, python floats as the blocking path's.
     layout: param_layout(); opt_layout: [(offset, shape)] of the optimiser's views; group: the hyper-parameters without lr and params.
     The tensors are views INTO the snapshot, no copies: torch.save writes each flat buffer once (tensors that share a storage are
     pickled as offset + shape into it), torch.load hands back the same named tensors."""
@@ -131,6 +136,9 @@ def assemble(buf, layout, opt_layout, group, it, infos, norm=None):
         for k, key in enumerate(NORM_KEYS):
             ck[key] = dict(mean=nb[o:o + K[k]].clone(), var=nb[o + K[k]:o + 2 * K[k]].clone(), count=float(nb[NORM_COUNT + k]), eps=eps, until=until)
             o += 2 * K[k]
+    if value_norm is not None:
+        count, mean, var = (float(x) for x in buf["value_norm"])
+        ck[VALUE_NORM_KEY] = dict(count=count, mean=mean, var=var, eps=float(value_norm))
     return ck
 
 
@@ -157,7 +165,7 @@ class Snapshot:
             b["busy"].set()
         self.n = 0
 
-    def take(self, net, actor_critic, env=None):
+    def take(self, net, actor_critic, env=None, value_norm=None):
         """Enqueue the device -> pinned copies of one checkpoint (env: its state too) -> what write_snapshot needs: the buffer set, the event
         behind the copies, the layouts (recomputed per save), the normaliser's shape (None: off) and the env's snapshot (None: not asked)."""
         buf = self.sets[self.n & 1]
@@ -176,6 +184,10 @@ class Snapshot:
                 buf["norm"][o:o + t.numel()].copy_(t, non_blocking=True)
                 o += t.numel()
             norm = ((int(net.cfg.num_obs), int(net.cfg.num_priv)), net.obs_norm)
+        if value_norm is not None:      # (block, eps) of PPO.value_normalization: three doubles ride with the parameters
+            if "value_norm" not in buf:
+                buf["value_norm"] = torch.empty(3, dtype=torch.float64).pin_memory()
+            buf["value_norm"].copy_(value_norm[0], non_blocking=True)
         env_state = None
         if env is not None:
             if "env" not in buf:
@@ -184,6 +196,7 @@ class Snapshot:
         done = torch.cuda.Event()
         done.record()
         return dict(buf=buf, done=done, layout=param_layout(actor_critic.state_dict(), net.params), norm=norm, env=env_state,
+                    value_norm=None if value_norm is None else float(value_norm[1]),
                     opt_layout=[(o, shape) for _, o, shape in param_layout(net.views, net.params)])
 
 
@@ -193,7 +206,7 @@ def write_snapshot(shot, group, it, infos, path, side):
         tj = [time.perf_counter()]
         shot["done"].synchronize()
         tj.append(time.perf_counter())
-        ck = assemble(shot["buf"], shot["layout"], shot["opt_layout"], group, it, infos, shot["norm"])
+        ck = assemble(shot["buf"], shot["layout"], shot["opt_layout"], group, it, infos, shot["norm"], shot.get("value_norm"))
         tj.append(time.perf_counter())
         write_checkpoint(ck, path, side)
         tj.append(time.perf_counter())
@@ -260,8 +273,29 @@ def _check_norm_keys(loaded, has_norm, name, spec=None):
                                    % (name, k, theirs[0], theirs[1], spec[0], spec[1]))
 
 
-def check_compatible(loaded, actor_critic, rnd, name):
-    """Checkpoint `loaded` (file `name`) against this run's policy and RND module (None: off); raises before anything is changed."""
+def value_norm_spec(alg):
+    """check_compatible's value_norm argument for `alg`: the option's eps, or None when PPO.value_normalization is off."""
+    vn = getattr(alg, "value_normalizer", None)
+    return None if vn is None else vn.eps
+
+
+def _check_value_norm_key(loaded, eps, name):
+    """A checkpoint of a run with PPO.value_normalization for a run without it, or the reverse, or one saved under another eps: the critic's
+    parameters mean another function of the state under the same names.  Refused by key name."""
+    sd = loaded.get(VALUE_NORM_KEY)
+    if sd is not None and eps is None:
+        raise RuntimeError("%s carries `%s`: it was trained with PPO.value_normalization (its critic outputs normalised values), this run "
+                           "was built without it" % (name, VALUE_NORM_KEY))
+    if sd is None and eps is not None:
+        raise RuntimeError("%s has no `%s`: it was trained without PPO.value_normalization (its critic outputs raw values), this run was "
+                           "built with it" % (name, VALUE_NORM_KEY))
+    if sd is not None and (sd.get("eps") is None or float(sd["eps"]) != float(eps)):
+        raise RuntimeError("%s: `%s` was saved with value_normalization_eps=%r; this run was built with %r" % (name, VALUE_NORM_KEY, sd.get("eps"), eps))
+
+
+def check_compatible(loaded, actor_critic, rnd, name, value_norm=None):
+    """Checkpoint `loaded` (file `name`) against this run's policy, RND module (None: off) and value normalisation (value_norm: its eps,
+    None: off); raises before anything is changed."""
     # a checkpoint of the other noise parametrisation: its first entry is another quantity under another name
     msd, mine = loaded["model_state_dict"], getattr(actor_critic, "noise_std_type", "scalar")
     theirs = "log" if "log_std" in msd else ("scalar" if "std" in msd else mine)
@@ -274,3 +308,4 @@ def check_compatible(loaded, actor_critic, rnd, name):
     # a checkpoint of a run with RND for a run without it, or the reverse, or the per-env average of another number of envs: refused by name
     from .rnd import check_state_dict as check_rnd_state
     check_rnd_state(loaded.get(RND_STATE_KEY), name, rnd is not None, getattr(rnd, "num_envs", None))
+    _check_value_norm_key(loaded, value_norm, name)

@@ -4,6 +4,8 @@ The statistics live on the device, in the block a hgym.NetBuffers owns (HgymNet.
 normaliser is folded into the first layer of every net.  `mean`, `var`, `std`, `count` read that state; `forward`
 is the plain torch expression for host-side users (plots, a policy evaluated outside the kernels).  Before the ActorCritic is bound to a
 net the module holds the initial state itself: mean 0, var 1, count 0."""
+import math
+
 import torch
 import torch.nn as nn
 
@@ -50,3 +52,70 @@ class EmpiricalNormalization(nn.Module):
         """mean, var (fp64, cpu), count, eps, until: the checkpoint entry of this normaliser."""
         return dict(mean=self._part("mean").detach().cpu().clone(), var=self._part("var").detach().cpu().clone(), count=float(self.count),
                     eps=self.eps, until=self.until)
+
+
+class ValueNormalizer:
+    """What `PPO.value_normalizer` exposes with PPO.value_normalization on: the running statistics of the raw
+    returns, seen from the host.  The state lives on the device, in the three doubles (count, mean, var) the hgym_value_* calls name, and
+    the kernels never call this object: every property reads a host copy of the block (a synchronising read-back), `forward` / `inverse`
+    are the plain torch expressions for host-side users -- a critic evaluated outside the kernels returns normalised values
+    (ActorCritic.evaluate), inverse() turns them into raw ones.  Not for the training loop: each property, and each forward / inverse call,
+    waits for the device; a caller that wants several numbers takes them from ONE read, stats().  `block` is the device tensor itself
+    (what a checkpoint snapshot copies stream-side, without a wait)."""
+
+    def __init__(self, block, eps):
+        self._block, self.eps = block, float(eps)
+
+    @property
+    def block(self):
+        """The three doubles (count, mean, var) on the device, as the hgym_value_* calls name them."""
+        return self._block
+
+    def _host(self):
+        return self._block.detach().cpu()
+
+    def stats(self):
+        """{count, mean, var, std} as python numbers from one read-back."""
+        count, mean, var = (float(x) for x in self._host())
+        return dict(count=int(count), mean=mean, var=var, std=math.sqrt(max(var, 0.0)))
+
+    @property
+    def count(self):
+        return int(self._host()[0])
+
+    @property
+    def mean(self):
+        return self._host()[1].clone()
+
+    @property
+    def var(self):
+        return self._host()[2].clone()
+
+    @property
+    def std(self):
+        return torch.sqrt(self._host()[2])
+
+    def _floats(self, x):
+        b = self._host()
+        return b[1].to(device=x.device, dtype=x.dtype), torch.sqrt(b[2]).to(device=x.device, dtype=x.dtype) + self.eps
+
+    def forward(self, x):
+        """(x - mean) / (std + eps): raw returns or values -> the critic's units, in x's dtype and on x's device."""
+        m, s = self._floats(x)
+        return (x - m) / s
+
+    __call__ = forward
+
+    def inverse(self, y):
+        """y * (std + eps) + mean: the critic's outputs -> raw values."""
+        m, s = self._floats(y)
+        return y * s + m
+
+    def state_dict(self):
+        """count, mean, var, eps as python floats: the checkpoint entry (value_norm_state_dict)."""
+        b = self._host()
+        return dict(count=float(b[0]), mean=float(b[1]), var=float(b[2]), eps=self.eps)
+
+    def load_state_dict(self, sd):
+        """The three doubles back onto the device (python floats are doubles: the same bits)."""
+        self._block.copy_(torch.tensor([float(sd["count"]), float(sd["mean"]), float(sd["var"])], dtype=torch.float64))

@@ -61,6 +61,9 @@ def _plan_loop(env, alg, device, log_on):
     fuse = (env.rollout_fused_mode(alg.net) if (defer_fin and hasattr(env, "rollout_fused_mode") and hasattr(alg, "fused_rollout_step")
                                                 and knob("HGYM_FUSE_ROLLOUT")) else None)
     fuse = "inline" if (fuse == "deferred" and not hasattr(alg, "deferred_values")) else fuse
+    # PPO.value_normalization: the inline form computes V and consumes it (the time-out bootstrap) in the same launch, with no place for the
+    # denormalisation between the two -- the critic runs behind the rollout instead, followed by the denormalise launches
+    fuse = "deferred" if (fuse == "inline" and getattr(alg, "value_normalizer", None) is not None) else fuse
     async_ok = cuda and isinstance(alg, PPO) and knob("HGYM_ASYNC")
     async_mode = "events" if (not log_on and async_ok) else "log" if (log_sink and async_ok) else None
     graph_update = bool(graph and async_mode is not None and hasattr(alg, "update_capturable") and alg.update_capturable()
@@ -159,13 +162,14 @@ def _split_algorithm_cfg(alg_cfg):
     off), not a parameter of the reference's PPO: it is taken out here and becomes PPO.symmetry.  The mirror loss's keys (SYMMETRY_KEYS)
     are taken out as well; _split_symmetry_cfg reads them.  So are the advantage normalisation's (ADVANTAGE_KEYS; _split_advantage_cfg)."""
     kwargs = dict(alg_cfg)
-    for k in SYMMETRY_KEYS + ADVANTAGE_KEYS + (RND_KEY, SMOOTH_KEY):
+    for k in SYMMETRY_KEYS + ADVANTAGE_KEYS + VALUE_NORM_KEYS + (RND_KEY, SMOOTH_KEY):
         kwargs.pop(k, None)
     return kwargs, bool(kwargs.pop("symmetry", False))
 
 
 ADVANTAGE_KEYS = ("advantage_normalization", "normalize_advantage_per_mini_batch")      # neither is a parameter of PPO.__init__
 SMOOTH_KEY = "smoothness_cfg"      # the smoothness regulariser's block (humanoid.algo.ppo.smoothness.parse_config); absent or None: off
+VALUE_NORM_KEYS = ("value_normalization", "value_normalization_eps")      # PPO.value_normalization / _eps; neither is a parameter of PPO.__init__
 RND_KEY = "rnd_cfg"      # rsl_rl's Random Network Distillation block (humanoid.algo.ppo.rnd.parse_config); absent or None: off
 
 
@@ -263,6 +267,10 @@ class OnPolicyRunner:
                 sc["noise_std"] = smooth_module.env_noise_std(getattr(self.env, "cfg", None), getattr(self.env, "noise_scale_vec", None),
                                                               self.env.num_obs)
             self.alg.smoothness = sc
+        if self.alg_cfg.get("value_normalization") is not None:      # value targets standardised by running statistics; read by init_storage below
+            self.alg.value_normalization = bool(self.alg_cfg["value_normalization"])
+        if self.alg_cfg.get("value_normalization_eps") is not None:
+            self.alg.value_normalization_eps = float(self.alg_cfg["value_normalization_eps"])
         self.num_steps_per_env = self.cfg["num_steps_per_env"]
         self.save_interval = self.cfg["save_interval"]
         self.alg.init_storage(self.env.num_envs, self.num_steps_per_env, [self.env.num_obs], [self.env.num_privileged_obs],
@@ -756,7 +764,9 @@ class OnPolicyRunner:
         else:
             if getattr(self, "_snapshot", None) is None:
                 self._snapshot = ckpt.Snapshot(alg.net)
-            shot = self._snapshot.take(alg.net, alg.actor_critic, self.env if env_state else None)
+            vn = getattr(alg, "value_normalizer", None)      # PPO.value_normalization: its three doubles ride in the snapshot
+            shot = self._snapshot.take(alg.net, alg.actor_critic, self.env if env_state else None,
+                                       value_norm=None if vn is None else (vn.block, vn.eps))
             side = dict(env=shot["env"], **extra) if env_state else None
             ckpt.WRITER.submit(lambda: ckpt.write_snapshot(shot, type(alg.optimizer).HYPER, it, infos, path, side))
             if wait:
@@ -800,7 +810,9 @@ class OnPolicyRunner:
             ckpt.check_sidecar(side, self.num_steps_per_env, self.env)      # (refused before anything is changed)
         if loaded is None:
             loaded = torch.load(path, map_location=self.device)
-        ckpt.check_compatible(loaded, ac, alg._rnd, os.path.basename(str(path)))
+        ckpt.check_compatible(loaded, ac, alg._rnd, os.path.basename(str(path)), value_norm=ckpt.value_norm_spec(alg))
+        if getattr(alg, "value_normalizer", None) is not None:
+            alg.value_normalizer.load_state_dict(loaded[ckpt.VALUE_NORM_KEY])
         if alg._rnd is not None:
             alg._rnd.load_rnd_state_dict(loaded[RND_STATE_KEY])
         if getattr(ac, "empirical_normalization", False):        # the statistics first, then the parameters (whose load refolds the first layers with them)

@@ -108,6 +108,16 @@ class PPO:
     # PPO.symmetry, not with Distillation (ValueError from init_storage).  Read once, in init_storage.  `last_smoothness`: {temporal, spatial,
     # valid_fraction} of the last update.  DESIGN.md section 28.
     smoothness = None
+    # value targets standardised by running statistics (rl_games' normalize_value, the return half of SB3's VecNormalize): the critic lives
+    # in normalised units.  Per iteration: the critic's outputs are denormalised as they are stored (one launch behind the policy launch,
+    # or behind deferred_values()), GAE and the advantages run on raw values, then compute_returns merges the T N raw returns into the
+    # running (count, mean, var) -- ahead of the update, so the targets are normalised by statistics that already include them, as in
+    # rl_games -- and puts `returns` and the old `values` into the critic's units.  No update kernel changes: the value clip range is
+    # clip_param in normalised units.  ActorCritic.evaluate() keeps returning what the critic outputs (normalised); `value_normalizer`
+    # (mean, var, std, count, forward, inverse) is the host's view.  A one-launch rollout takes the deferred critic.  One rank, not with
+    # Distillation (ValueError from init_storage).  Both read once, in init_storage.  DESIGN.md section 31.
+    value_normalization = False
+    value_normalization_eps = 1e-2
 
     def __init__(self, actor_critic, num_learning_epochs=1, num_mini_batches=1, clip_param=0.2, gamma=0.998, lam=0.95,
                  value_loss_coef=1.0, entropy_coef=0.0, learning_rate=1e-3, max_grad_norm=1.0, use_clipped_value_loss=True,
@@ -137,6 +147,7 @@ class PPO:
         self._rnd = self._smooth = self._symmetry = self._obs_norm = None
         self._augment, self._mirror_coef, self._adv_mode = False, 0.0, "batch"
         self._mirror_target = self._mirror_sums = None
+        self._value_norm = self.value_normalizer = self.last_value_norm = None      # the storage's buffers, the host's view, the last log's numbers
         self._comm, self._comm_p2p, self._comm_direct_used = None, False, False
         self._log = None      # the LogBlock behind log_block() / read_log()
         self.last_denoise_loss = self.last_mirror_loss = self.last_smoothness = None
@@ -160,10 +171,12 @@ class PPO:
 
     @staticmethod
     def check_setup(num_envs, num_transitions_per_env, num_mini_batches, num_actor_obs, world=1, symmetry=None, symmetry_augmentation=True,
-                    mirror_loss_coef=0.0, advantage_normalization="batch", rnd=None, smoothness=None):
+                    mirror_loss_coef=0.0, advantage_normalization="batch", rnd=None, smoothness=None, value_normalization=False,
+                    value_normalization_eps=1e-2):
         """What init_storage refuses, as a function that needs no device (ValueError each), in the order the refusals win: an unknown
         advantage mode; a mirror coefficient that is negative or not finite, or one > 0 without `symmetry`; what PPO.rnd and PPO.smoothness
-        refuse (their own check_setup); per-minibatch advantages over minibatches of fewer than 2 rows."""
+        refuse (their own check_setup); per-minibatch advantages over minibatches of fewer than 2 rows; value normalisation on more than one
+        rank or with an eps that is negative or not finite."""
         if advantage_normalization not in PPO.ADVANTAGE_NORMALIZATIONS:
             raise ValueError("PPO.advantage_normalization=%r: one of %s" % (advantage_normalization, ", ".join(PPO.ADVANTAGE_NORMALIZATIONS)))
         coef = float(mirror_loss_coef)
@@ -179,6 +192,12 @@ class PPO:
         mb = ((2 if augment else 1) * num_envs * num_transitions_per_env) // num_mini_batches
         if advantage_normalization == "minibatch" and mb < 2:      # (rsl_rl would divide by the NaN deviation of one value)
             raise ValueError("PPO.advantage_normalization='minibatch' needs minibatches of at least 2 rows (they have %d)" % mb)
+        if value_normalization:
+            if int(world) > 1:      # (a follow-up: the batch statistics would go through the exchange the advantage statistics use)
+                raise ValueError("PPO.value_normalization runs on one rank (world size %d): the returns' statistics have no exchange" % int(world))
+            eps = float(value_normalization_eps)
+            if not (eps >= 0.0 and math.isfinite(eps)):
+                raise ValueError("PPO.value_normalization_eps=%r: must be finite and >= 0" % (value_normalization_eps,))
 
     def init_storage(self, num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape):
         import hgym
@@ -186,7 +205,8 @@ class PPO:
         ac = self.actor_critic
         # (PPO.check_setup by name: a subclass has refusals of its own under that name, and runs them ahead of this call)
         PPO.check_setup(num_envs, num_transitions_per_env, self.num_mini_batches, ac.num_actor_obs, self._world, self.symmetry,
-                        self.symmetry_augmentation, self.mirror_loss_coef, self.advantage_normalization, self.rnd, self.smoothness)
+                        self.symmetry_augmentation, self.mirror_loss_coef, self.advantage_normalization, self.rnd, self.smoothness,
+                        bool(self.value_normalization), self.value_normalization_eps)
         self._adv_mode = self.advantage_normalization
         self.storage = RolloutStorage(num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape, self.device)
         self._mirror_coef = coef = float(self.mirror_loss_coef)
@@ -255,10 +275,16 @@ class PPO:
         if self.rnd is not None:      # two more NetBuffers at the PPO precision, the reward pass's block, the storage's rnd_* fields
             self._rnd = self.rnd.bind(int(self.net.cfg.precision), max(mb, 1), self.device, num_envs)
             self.storage.enable_rnd(self._rnd.num_states, self._rnd.num_outputs)
+        if self.value_normalization:      # the block of three doubles, the merge's scratch, the bootstrap value's buffer
+            from .normalizer import ValueNormalizer
+            self.storage.enable_value_normalization(float(self.value_normalization_eps))
+            self._value_norm = self.storage._value_norm
+            self.value_normalizer = ValueNormalizer(self._value_norm["block"], self._value_norm["eps"])
         self._log = LogBlock(self._log_parts())
 
     def _log_parts(self):
-        """opt | mirror(2) | rnd_sums(2) | rnd_block(RND_HEADER) | smooth(4): opt_state, then the sums of every option that is on."""
+        """opt | mirror(2) | rnd_sums(2) | rnd_block(RND_HEADER) | smooth(4) | value_norm(3): opt_state, then the sums of every option that is
+        on; value_norm is the statistics' block itself (count, mean, var)."""
         parts = [("opt", self.net.opt_state)]
         if self._mirror_sums is not None:
             parts.append(("mirror", self._mirror_sums))
@@ -266,6 +292,10 @@ class PPO:
             parts += self._rnd.log_parts()
         if self._smooth is not None:
             parts.append(("smooth", self.storage._smooth["sums"]))
+        # a defaulted read, the one place: stand-ins with a fixed field set call this method (tests/test_log_block.py) and know nothing of the option
+        vn = getattr(self, "_value_norm", None)
+        if vn is not None:
+            parts.append(("value_norm", vn["block"]))
         return parts
 
     def seek(self, iteration, steps_per_iteration):
@@ -322,6 +352,10 @@ class PPO:
         t.actions = self.actor_critic.act(obs, critic_obs, out=out, env_fin=env_fin, shadow=sh)
         last = self.actor_critic._last
         t.values, t.actions_log_prob = last["values"], last["logp"]
+        if self._value_norm is not None:
+            # the critic's output -> a raw value, in place, before anything reads the slot: hgym_store_step, the env's transition sink, the
+            # finaliser riding in the next policy launch (time-out bootstrap r += gamma V), GAE
+            st.denormalize_values(t.values)
         t.action_mean, t.action_sigma = last["mu"], last["sigma"]
         t.observations, t.critic_observations = obs, critic_obs
         if not self.env_stores_transitions:
@@ -406,6 +440,9 @@ class PPO:
         shadow = st._priv_bf16.flatten(0, 1) if st._priv_bf16 is not None else None
         self.net.critic_values(st._priv_all[:T].flatten(0, 1), st.values.view(-1), shadow)
         self.net.critic_values(st._priv_all[T], st.last_values.view(-1))
+        if self._value_norm is not None:      # the statistics the critic was last trained under: those of the previous update
+            st.denormalize_values(st.values)
+            st.denormalize_values(st.last_values)
         self._rollout_done(T, [True] * T if shadow is not None else st.shadow_valid, True)
 
     def _adv_stats(self, stats):
@@ -422,6 +459,8 @@ class PPO:
         "obs" when the rollout did not write the storage's slot T (RandomNetworkDistillation.reward_pass)."""
         st, deferred = self.storage, self._deferred_ready       # deferred_values() has evaluated the bootstrap observation with the rest
         last_values = st.last_values if deferred else self.actor_critic.evaluate(last_critic_obs)
+        if self._value_norm is not None and not deferred:      # (deferred_values() has denormalised its own)
+            last_values = st.denormalize_values(last_values.reshape(-1, 1).contiguous(), out=self._value_norm["last_values"]).view(-1, 1)
         if self._smooth is not None and self._smooth["temporal_coef"] > 0.0 and not self._slot_T_written:
             # a rollout that copied its observations in (add_transitions) has not written slot T: the temporal term's successor of the last
             # step's rows is the bootstrap observation, which only the caller holds
@@ -433,6 +472,8 @@ class PPO:
             self._rnd.reward_pass(st, last_critic_obs, last_obs, self._slot_T_written)
         st.compute_returns(last_values, self.gamma, self.lam, stats_hook=self._adv_stats, time_outs=st.time_outs if deferred else None,
                            normalize=self._adv_mode == "batch")
+        if self._value_norm is not None:      # merge the raw returns FIRST, then returns and old values into the critic's units under the new statistics
+            st.normalize_value_targets()
         self._returns_done()
 
     def _returns_done(self):      # what compute_returns() changes on the host, issued or replayed: the deferred values are used up
@@ -467,11 +508,14 @@ class PPO:
                 ("mirror_scratch", None if self._mirror_target is None else (self._mirror_target.data_ptr(), self._mirror_sums.data_ptr())),
                 ("smoothness", smooth_module.graph_key(self._smooth, st.smooth_buffers())),
                 ("rnd", None if self._rnd is None else self._rnd.graph_key()),
-                ("adv_mode", self._adv_mode), ("adv_scratch", st.minibatch_advantages_key()), ("obs_norm", self._obs_norm))
+                ("adv_mode", self._adv_mode), ("adv_scratch", st.minibatch_advantages_key()), ("obs_norm", self._obs_norm),
+                ("value_norm", st.value_norm_key()))
 
     def rollout_graph_key(self):
         """Everything of this side that a rollout bakes into its launches: the storage's slots, the sink's gamma (BY VALUE), the shadows."""
-        return id(self.storage), self.gamma, self.storage._obs_bf16 is not None
+        key = id(self.storage), self.gamma, self.storage._obs_bf16 is not None
+        # with value normalisation the stepwise rollout contains the denormalise launches (eps by value, the block by address); off: the key as ever
+        return key if self._value_norm is None else key + (self.storage.value_norm_key(),)
 
     def after_rollout_replay(self, end_state):
         """Host-side book-keeping of one replayed rollout.  end_state: rollout_end_state() behind the captured pass."""
@@ -602,11 +646,12 @@ class PPO:
         return self._log.device()
 
     def read_log(self, block):
-        """A host copy of log_block() -> hgym.opt_summary's dict; sets last_denoise_loss, last_mirror_loss, last_smoothness and RND's
-        last_log on the way.  The one reader behind update(sync=True) and the runner's asynchronous log."""
+        """A host copy of log_block() -> hgym.opt_summary's dict; sets last_denoise_loss, last_mirror_loss, last_smoothness,
+        last_value_norm and RND's last_log on the way.  The one reader behind update(sync=True) and the runner's asynchronous log."""
         self.last_mirror_loss = self.mirror_loss_from(block)
         self.last_smoothness = self.smoothness_from(block)
         self.rnd_log_from(block)
+        self.last_value_norm = self.value_norm_from(block)
         o = self._hgym.opt_summary(self._log.split(block)["opt"], self._ppo_cfg.aux_coef > 0.0)
         self.last_denoise_loss = o["denoise_loss"]
         return o
@@ -622,7 +667,18 @@ class PPO:
             out += [("Loss/smooth_temporal", self.last_smoothness["temporal"]), ("Loss/smooth_spatial", self.last_smoothness["spatial"])]
         if self._rnd is not None and self._rnd.last_log is not None:      # Loss/rnd, Rnd/intrinsic_reward, Rnd/extrinsic_reward, Rnd/weight, Rnd/std
             out += list(self._rnd.last_log.items())
+        vn = getattr(self, "last_value_norm", None)      # (defaulted as in _log_parts: the same stand-ins call this method)
+        if vn is not None:
+            out += [("Policy/value_norm_mean", vn["mean"]), ("Policy/value_norm_std", vn["std"])]
         return out
+
+    def value_norm_from(self, block):
+        """{count, mean, var, std} of the returns' running statistics from a host copy of log_block(); None when the option is off."""
+        b = self._log.split(block).get("value_norm")
+        if b is None:
+            return None
+        count, mean, var = (float(x) for x in b)
+        return dict(count=count, mean=mean, var=var, std=math.sqrt(max(var, 0.0)))
 
     def rnd_log_from(self, block):
         """Loss/rnd and the Rnd/* numbers from a host copy of log_block() (RandomNetworkDistillation.log_from); None when RND is off."""

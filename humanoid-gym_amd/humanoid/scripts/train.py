@@ -35,7 +35,10 @@ constant weight -- an intrinsic exploration reward added to the stored rewards a
 carry rnd_state_dict.  Unset: off.
 
 HGYM_SMOOTH=<lamT>[,<lamS>] sets `algorithm.smoothness_cfg = {"temporal_coef": lamT, "spatial_coef": lamS}`: the smoothness regulariser on
-the policy's mean (PPO.smoothness), the spatial term's noise the env's own noise_scale_vec * noise_level.  Unset: off."""
+the policy's mean (PPO.smoothness), the spatial term's noise the env's own noise_scale_vec * noise_level.  Unset: off.
+
+HGYM_VALUE_NORM=1 sets `algorithm.value_normalization` the same way: the value targets standardised by running statistics of the returns, the
+critic in normalised units (PPO.value_normalization); checkpoints carry value_norm_state_dict.  Unset: off."""
 import os
 import sys
 
@@ -68,6 +71,8 @@ def train(args):
     if os.environ.get("HGYM_SMOOTH"):
         lam = [float(x) for x in os.environ["HGYM_SMOOTH"].split(",")]
         task_registry.get_cfgs(args.task)[1].algorithm.smoothness_cfg = {"temporal_coef": lam[0], "spatial_coef": lam[1] if len(lam) > 1 else 0.0}
+    if os.environ.get("HGYM_VALUE_NORM", "0") == "1":
+        task_registry.get_cfgs(args.task)[1].algorithm.value_normalization = True
     ppo_runner, train_cfg = task_registry.make_alg_runner(env=env, name=args.task, args=args, **({} if rank == 0 else {"log_root": None}))
     ppo_runner.learn(num_learning_iterations=train_cfg.runner.max_iterations, init_at_random_ep_len=True)
     if os.environ.get("HGYM_TRAIN_SIGNATURE"):      # tests: a signature of this rank's final parameters (replicas must agree bit for bit)

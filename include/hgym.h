@@ -73,7 +73,9 @@ extern "C" {
                              *    (same version, later: hgym_rnd_block_init, hgym_rnd_rewards and HgymRndConfig -- Random Network Distillation's
                              *    reward pass; no layout changes)
                              *    (same version, later: hgym_smooth_pairs, hgym_perturb_rows, hgym_ppo_grad_smooth and HgymSmooth -- the smoothness
-                             *    regulariser on the policy's mean; no layout changes) */
+                             *    regulariser on the policy's mean; no layout changes)
+                             *    (same version, later: hgym_value_denormalize, hgym_value_norm_merge, hgym_value_normalize -- value targets
+                             *    standardised by running statistics; no layout changes) */
 
 enum {
     HGYM_OK = 0,
@@ -461,6 +463,50 @@ int32_t hgym_adv_normalize(int64_t count, float* advantages, const double* stats
 #define HGYM_ADV_MB_SCRATCH_DOUBLES(segments, seg_len) ((int64_t)(segments) * (3 + 2 * (((int64_t)(seg_len) + 1023) / 1024)))
 int32_t hgym_adv_normalize_minibatches(int32_t segments, int64_t seg_len, const int64_t* idx, const float* adv, float* out, int64_t rows,
                                        double* scratch, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Value targets standardised by running statistics (PPO.value_normalization; rl_games' normalize_value, the return half of SB3's
+ * VecNormalize; header v9, no layout changes).  The critic lives in normalised units; around GAE three scalar
+ * columns change units.
+ *   block     HGYM_VALUE_NORM_BLOCK_DOUBLES doubles of the caller on the device, 8-byte aligned: [0] count, [1] mean, [2] var (population
+ *             variance).  The caller writes the initial state 0, 0, 1; hgym_value_norm_merge is the only writer afterwards.
+ *   floats    mean_f = (float)mean, scale_f = (float)sqrt(var) + eps, formed by every call from the block; eps >= 0 and finite.
+ *   denormalise   V = v * scale_f + mean_f        fp32, two roundings (no fma)
+ *   normalise     y = (x - mean_f) / scale_f      fp32, two roundings, the division correctly rounded
+ *   merge     of a batch of n fp32 values with mean_b and population variance var_b, in fp64, rsl_rl's EmpiricalNormalization merge as
+ *             hgym_net_norm_merge does it:
+ *                 count' = count + n;  rate = n / count';  d = mean_b - mean;  mean' = mean + rate * d;
+ *                 var' = var + rate * (var_b - var + d * (mean_b - mean')), clamped at 0
+ *             From count = 0 the formula's value IS the batch's statistics: the call then stores mean' = mean_b, var' = var_b themselves (in
+ *             floating point 1 + (var_b - 1) would round).
+ *   batch statistics   chunk-wise (n, mean, M2) combined by Chan's rule; no sum of raw squares is formed, so the variance survives
+ *             |mean| >> std.  Per chunk of HGYM_VALUE_NORM_CHUNK consecutive values, two passes in fp64: mean_c = (sum x) / n_c, then
+ *             M2_c = sum (x - mean_c)^2, each sum by a fixed tree.  The chunks' (n_c, mean_c, M2_c) are combined pairwise in a fixed order,
+ *                 n = n_a + n_b;  d = mean_b - mean_a;  mean = mean_a + d * (n_b / n);  M2 = M2_a + M2_b + d * d * (n_a * n_b / n),
+ *             by the last workgroup to arrive (a counter in the scratch, left zero again): no fp64 atomics, the same inputs give the same
+ *             bits in every run.  var_b = M2 / n.
+ *   scratch   HGYM_VALUE_NORM_SCRATCH_DOUBLES(n) doubles on the device, 8-byte aligned, ZERO-FILLED ONCE by the caller:
+ *             [HGYM_VALUE_NORM_BATCH + 0 .. 2] the batch's raw n, mean_b, var_b as the last call left them (what a multi-rank exchange would
+ *             carry between "batch statistics" and "merge"), [HGYM_VALUE_NORM_TICKET] the arrival counter, [HGYM_VALUE_NORM_PARTIALS ..)
+ *             mean_c, M2_c per chunk.  One call at a time per scratch buffer.
+ * Every call: ONE launch on `stream`, ceil(n / HGYM_VALUE_NORM_CHUNK) workgroups up to HGYM_VALUE_NORM_MAX_BLOCKS (which then walk the
+ * chunks with that stride), no allocation, no host synchronisation, the same arguments in every iteration (capturable).  16-byte loads and
+ * stores where the columns are 16-byte aligned, 4-byte ones otherwise.
+ *   hgym_value_denormalize   dst[i] = src[i] * scale_f + mean_f, i < n.  dst == src is allowed; any other overlap is HGYM_E_BADARG.
+ *   hgym_value_norm_merge    the statistics of returns[0 .. n) -> scratch, merged into block.
+ *   hgym_value_normalize     x[i] = (x[i] - mean_f) / scale_f in place, i < n.
+ * Nothing launched and HGYM_E_SHAPE: n < 1.  HGYM_E_UNSUPPORTED: n > 2^40.  HGYM_E_BADARG: a null pointer, block or scratch not 8-byte
+ * aligned, a column not 4-byte aligned, eps negative or not finite. */
+#define HGYM_VALUE_NORM_BLOCK_DOUBLES 3
+#define HGYM_VALUE_NORM_CHUNK 1024
+#define HGYM_VALUE_NORM_MAX_BLOCKS 1024
+#define HGYM_VALUE_NORM_BATCH 0
+#define HGYM_VALUE_NORM_TICKET 3
+#define HGYM_VALUE_NORM_PARTIALS 4
+#define HGYM_VALUE_NORM_SCRATCH_DOUBLES(n) (HGYM_VALUE_NORM_PARTIALS + 2 * (((int64_t)(n) + HGYM_VALUE_NORM_CHUNK - 1) / HGYM_VALUE_NORM_CHUNK))
+int32_t hgym_value_denormalize(int64_t n, const float* src, float* dst, const double* block, float eps, void* stream);
+int32_t hgym_value_norm_merge(int64_t n, const float* returns, double* block, double* scratch, void* stream);
+int32_t hgym_value_normalize(int64_t n, float* x, const double* block, float eps, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Random Network Distillation's reward pass (rsl_rl's rnd_cfg; PPO.rnd; header v9, no layout changes).
