@@ -1,8 +1,8 @@
 """The log block of an update: the device tensors a log line reads, copied to the host as ONE tensor and taken apart again by name.
 
-PPO.init_storage lists `opt` (opt_state) and, behind it, one part per option that is on (PPO._log_parts); the order of the list is the
-byte layout (checkpoints, tools and tests hold such blocks):  PPO  opt | mirror(2) | rnd_sums(2) | rnd_block(RND_HEADER) | smooth(4);
-Distillation  opt | bc(2).  Plain torch, no device needed."""
+PPO.init_storage lists `opt` (opt_state) and, behind it, the log_parts() of every option that is on (PPO._log_parts); the order of the
+list is the byte layout (checkpoints, tools and tests hold such blocks):  PPO  opt | mirror(2) | rnd_sums(2) | rnd_block(RND_HEADER) |
+smooth(4) | value_norm(3);  Distillation  opt | bc(2).  Plain torch, no device needed."""
 import torch
 
 

@@ -55,24 +55,62 @@ class EmpiricalNormalization(nn.Module):
 
 
 class ValueNormalizer:
-    """What `PPO.value_normalizer` exposes with PPO.value_normalization on: the running statistics of the raw
-    returns, seen from the host.  The state lives on the device, in the three doubles (count, mean, var) the hgym_value_* calls name, and
-    the kernels never call this object: every property reads a host copy of the block (a synchronising read-back), `forward` / `inverse`
-    are the plain torch expressions for host-side users -- a critic evaluated outside the kernels returns normalised values
-    (ActorCritic.evaluate), inverse() turns them into raw ones.  Not for the training loop: each property, and each forward / inverse call,
-    waits for the device; a caller that wants several numbers takes them from ONE read, stats().  `block` is the device tensor itself
-    (what a checkpoint snapshot copies stream-side, without a wait)."""
+    """PPO.value_normalization as PPO holds it (`PPO.value_normalizer`; None: off): the running statistics of the raw
+    returns -- `block`, three doubles (count, mean, var) on the device --, the launches that use them, and the host's view of them.
 
-    def __init__(self, block, eps):
-        self._block, self.eps = block, float(eps)
+    The launches (on_device() allocates what they name): whoever fills the storage's `values` follows with denormalize(), compute_returns()
+    runs GAE on raw values, and normalize_targets() behind it puts `returns` and `values` into the critic's units for the update.
 
-    @property
-    def block(self):
-        """The three doubles (count, mean, var) on the device, as the hgym_value_* calls name them."""
-        return self._block
+    The host's view: every property reads a host copy of the block (a synchronising read-back), `forward` / `inverse` are the plain torch
+    expressions for host-side users -- a critic evaluated outside the kernels returns normalised values (ActorCritic.evaluate), inverse()
+    turns them into raw ones.  Not for the training loop: each property, and each forward / inverse call, waits for the device; a caller
+    that wants several numbers takes them from ONE read, stats().  `block` is the device tensor itself (what a checkpoint snapshot copies
+    stream-side, without a wait)."""
+
+    def __init__(self, block, eps, scratch=None, last_values=None):
+        """scratch, last_values: hgym_value_norm_merge's scratch and the (N, 1) buffer of the denormalised bootstrap value; the host's view
+        needs neither."""
+        self.block, self.eps, self.scratch, self.last_values, self.last = block, float(eps), scratch, last_values, None
+
+    @classmethod
+    def on_device(cls, eps, num_values, num_envs, device):
+        """The statistics at (0, 0, 1) and the scratch for merging num_values (T N) returns at a time, all allocated once."""
+        from hgym import _lib as L
+        return cls(L.value_norm_block(device), eps, L.value_norm_scratch(num_values, device),
+                   torch.zeros(num_envs, 1, dtype=torch.float32, device=device))
+
+    def denormalize(self, v, out=None):
+        """out (default: v itself) = v * scale_f + mean_f under the statistics as they are (hgym_value_denormalize: one launch, fixed
+        arguments -- capturable): the critic's outputs -> raw values.  v: any contiguous fp32 column."""
+        import hgym
+        return hgym.value_denormalize(v.view(-1), self.block, self.eps, None if out is None else out.view(-1))
+
+    def normalize_targets(self, returns, values):
+        """Behind compute_returns(): merge the raw returns into the statistics FIRST (hgym_value_norm_merge), then returns <- normalise(returns)
+        and values <- normalise(values) in place under the NEW statistics (hgym_value_normalize twice): three launches, fixed arguments."""
+        import hgym
+        hgym.value_norm_merge(returns.view(-1), self.block, self.scratch)
+        hgym.value_normalize(returns.view(-1), self.block, self.eps)
+        hgym.value_normalize(values.view(-1), self.block, self.eps)
+
+    def graph_key(self):
+        """PPO.update_graph_key's entry (and the tail of rollout_graph_key): eps and the two buffers the launches name."""
+        return dict(value_norm=(self.eps, self.block.data_ptr(), self.scratch.data_ptr()))
+
+    def log_parts(self):
+        return [("value_norm", self.block)]
+
+    def read_log(self, parts):
+        """`last` = {count, mean, var, std} from the parts of a host copy of PPO.log_block()."""
+        count, mean, var = (float(x) for x in parts["value_norm"])
+        self.last = dict(count=count, mean=mean, var=var, std=math.sqrt(max(var, 0.0)))
+        return self.last
+
+    def log_scalars(self):
+        return [] if self.last is None else [("Policy/value_norm_mean", self.last["mean"]), ("Policy/value_norm_std", self.last["std"])]
 
     def _host(self):
-        return self._block.detach().cpu()
+        return self.block.detach().cpu()
 
     def stats(self):
         """{count, mean, var, std} as python numbers from one read-back."""
@@ -118,4 +156,4 @@ class ValueNormalizer:
 
     def load_state_dict(self, sd):
         """The three doubles back onto the device (python floats are doubles: the same bits)."""
-        self._block.copy_(torch.tensor([float(sd["count"]), float(sd["mean"]), float(sd["var"])], dtype=torch.float64))
+        self.block.copy_(torch.tensor([float(sd["count"]), float(sd["mean"]), float(sd["var"])], dtype=torch.float64))

@@ -63,7 +63,7 @@ def _plan_loop(env, alg, device, log_on):
     fuse = "inline" if (fuse == "deferred" and not hasattr(alg, "deferred_values")) else fuse
     # PPO.value_normalization: the inline form computes V and consumes it (the time-out bootstrap) in the same launch, with no place for the
     # denormalisation between the two -- the critic runs behind the rollout instead, followed by the denormalise launches
-    fuse = "deferred" if (fuse == "inline" and getattr(alg, "value_normalizer", None) is not None) else fuse
+    fuse = "deferred" if (fuse == "inline" and alg.value_normalizer is not None) else fuse
     async_ok = cuda and isinstance(alg, PPO) and knob("HGYM_ASYNC")
     async_mode = "events" if (not log_on and async_ok) else "log" if (log_sink and async_ok) else None
     graph_update = bool(graph and async_mode is not None and hasattr(alg, "update_capturable") and alg.update_capturable()

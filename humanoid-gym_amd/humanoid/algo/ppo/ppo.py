@@ -14,8 +14,10 @@ import torch
 import torch.nn as nn  # noqa: F401  (kept importable like the reference module)
 
 from .actor_critic import ActorCritic
-from .log_block import LogBlock, mean_of_sums
-from .rollout_storage import RolloutStorage, mirror_pair_rows
+from .log_block import LogBlock
+from .mirror_loss import MirrorLoss
+from .normalizer import ValueNormalizer
+from .rollout_storage import RolloutStorage
 from . import dist_utils
 from . import rnd as rnd_module
 from . import smoothness as smooth_module
@@ -118,6 +120,7 @@ class PPO:
     # Distillation (ValueError from init_storage).  Both read once, in init_storage.  DESIGN.md section 31.
     value_normalization = False
     value_normalization_eps = 1e-2
+    value_normalizer = None      # the option's object once init_storage has built it; here, so that a PPO made without __init__ has the handle too
 
     def __init__(self, actor_critic, num_learning_epochs=1, num_mini_batches=1, clip_param=0.2, gamma=0.998, lam=0.95,
                  value_loss_coef=1.0, entropy_coef=0.0, learning_rate=1e-3, max_grad_norm=1.0, use_clipped_value_loss=True,
@@ -143,14 +146,15 @@ class PPO:
         # True while a runner has the env store the scalar columns and bump the sampling step itself (transition_sink)
         self.env_stores_transitions = False
         self.comm_timing = None      # a list: update() appends a pair of HIP events around the wait for the gradient exchange
-        # every option's state, "off" until init_storage reads the option: nobody probes for these
-        self._rnd = self._smooth = self._symmetry = self._obs_norm = None
-        self._augment, self._mirror_coef, self._adv_mode = False, 0.0, "batch"
-        self._mirror_target = self._mirror_sums = None
-        self._value_norm = self.value_normalizer = self.last_value_norm = None      # the storage's buffers, the host's view, the last log's numbers
+        # every option's state, "off" until init_storage reads the option: nobody probes for these.  The four option
+        # objects (MirrorLoss, RandomNetworkDistillation, Smoothness, ValueNormalizer; None: off) and those that are on (init_storage)
+        self._mirror_loss = self._rnd = self._smooth = None      # (value_normalizer: the class attribute)
+        self._options = self._scalar_order = ()
+        self._symmetry = self._obs_norm = None
+        self._augment, self._adv_mode = False, "batch"
         self._comm, self._comm_p2p, self._comm_direct_used = None, False, False
         self._log = None      # the LogBlock behind log_block() / read_log()
-        self.last_denoise_loss = self.last_mirror_loss = self.last_smoothness = None
+        self.last_denoise_loss = None
         self._world = 1
         self._rank = 0
         if torch.distributed.is_available() and torch.distributed.is_initialized():
@@ -168,6 +172,11 @@ class PPO:
         self._lr0 = v
         if self.net is not None:
             self.net.opt_state[self._hgym._lib.OPT_LR] = v
+
+    # what the last read_log() left on an option, under the names users read; None while the option is off or nothing has been read
+    last_mirror_loss = property(lambda self: self._mirror_loss and self._mirror_loss.last)
+    last_smoothness = property(lambda self: self._smooth and self._smooth.last)
+    last_value_norm = property(lambda self: self.value_normalizer and self.value_normalizer.last)
 
     @staticmethod
     def check_setup(num_envs, num_transitions_per_env, num_mini_batches, num_actor_obs, world=1, symmetry=None, symmetry_augmentation=True,
@@ -209,10 +218,9 @@ class PPO:
                         bool(self.value_normalization), self.value_normalization_eps)
         self._adv_mode = self.advantage_normalization
         self.storage = RolloutStorage(num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape, self.device)
-        self._mirror_coef = coef = float(self.mirror_loss_coef)
+        coef = float(self.mirror_loss_coef)
         self._augment = self.symmetry is not None and bool(self.symmetry_augmentation)
         self._symmetry = self.symmetry if (self._augment or coef > 0.0) else None      # neither half asked for: symmetry off
-        self._smooth = smooth_module.parse_config(self.smoothness, ac.num_actor_obs, torch.initial_seed())
         if self._symmetry is not None:
             self.storage.enable_mirror(self._symmetry)      # (before enable_shadow and before anything binds a slot's address)
         mb = ((2 if self._augment else 1) * num_envs * num_transitions_per_env) // self.num_mini_batches
@@ -255,10 +263,10 @@ class PPO:
                                              aux_coef=self.denoise_coef if aux else 0.0,
                                              clipped_value_loss=self.use_clipped_value_loss, mirror_coef=coef)
         if coef > 0.0:      # the pre-pass's output (one minibatch of raw partner means) and the two sums behind the per-update loss sums
-            self._mirror_target = torch.zeros(max(mb, 1) * ac.num_actions, dtype=torch.float32, device=self.device)
-            self._mirror_sums = torch.zeros(2, dtype=torch.float64, device=self.device)
-        if self._smooth is not None:      # the successor map of a whole permutation, the two pre-passes' outputs, the perturbed rows, the four sums
-            self.storage.enable_smoothness(self.num_mini_batches * mb, mb, ac.num_actor_obs, ac.num_actions, self._smooth["noise_std"])
+            self._mirror_loss = MirrorLoss(coef, mb, ac.num_actions, self.device)
+        smooth = smooth_module.parse_config(self.smoothness, ac.num_actor_obs, torch.initial_seed())
+        if smooth is not None:      # the successor map of a whole permutation, the two pre-passes' outputs, the perturbed rows, the four sums
+            self._smooth = smooth_module.Smoothness(smooth, self.num_mini_batches * mb, mb, ac.num_actor_obs, ac.num_actions, self.device)
         self._sample_step = torch.zeros(1, dtype=torch.int64, device=self.device)
         self._perm_seed = (torch.initial_seed() * 0x9E3779B97F4A7C15 + 0xABCD + 104729 * self._rank) & 0xFFFFFFFFFFFFFFFF
         self._perm_draws = 0
@@ -276,27 +284,18 @@ class PPO:
             self._rnd = self.rnd.bind(int(self.net.cfg.precision), max(mb, 1), self.device, num_envs)
             self.storage.enable_rnd(self._rnd.num_states, self._rnd.num_outputs)
         if self.value_normalization:      # the block of three doubles, the merge's scratch, the bootstrap value's buffer
-            from .normalizer import ValueNormalizer
-            self.storage.enable_value_normalization(float(self.value_normalization_eps))
-            self._value_norm = self.storage._value_norm
-            self.value_normalizer = ValueNormalizer(self._value_norm["block"], self._value_norm["eps"])
+            self.value_normalizer = ValueNormalizer.on_device(self.value_normalization_eps, num_envs * num_transitions_per_env, num_envs, self.device)
+        # the options that are on, in the two orders that are fixed: the log block's byte layout (checkpoints, tools and tests hold such
+        # blocks) and the order in which the writer gets their scalars.  A new option goes at the end of both.
+        on = lambda *options: tuple(o for o in options if o is not None)
+        self._options = on(self._mirror_loss, self._rnd, self._smooth, self.value_normalizer)
+        self._scalar_order = on(self._mirror_loss, self._smooth, self._rnd, self.value_normalizer)
         self._log = LogBlock(self._log_parts())
 
     def _log_parts(self):
-        """opt | mirror(2) | rnd_sums(2) | rnd_block(RND_HEADER) | smooth(4) | value_norm(3): opt_state, then the sums of every option that is
-        on; value_norm is the statistics' block itself (count, mean, var)."""
-        parts = [("opt", self.net.opt_state)]
-        if self._mirror_sums is not None:
-            parts.append(("mirror", self._mirror_sums))
-        if self._rnd is not None:      # the predictor loss's two sums and the head of the reward pass's block
-            parts += self._rnd.log_parts()
-        if self._smooth is not None:
-            parts.append(("smooth", self.storage._smooth["sums"]))
-        # a defaulted read, the one place: stand-ins with a fixed field set call this method (tests/test_log_block.py) and know nothing of the option
-        vn = getattr(self, "_value_norm", None)
-        if vn is not None:
-            parts.append(("value_norm", vn["block"]))
-        return parts
+        """opt | mirror(2) | rnd_sums(2) | rnd_block(RND_HEADER) | smooth(4) | value_norm(3): opt_state, then the part(s) of every option that
+        is on; value_norm is the statistics' block itself (count, mean, var)."""
+        return [("opt", self.net.opt_state)] + [part for o in self._options for part in o.log_parts()]
 
     def seek(self, iteration, steps_per_iteration):
         """Position the device generators' counters where a run that has done `iteration` learning iterations has them
@@ -352,10 +351,10 @@ class PPO:
         t.actions = self.actor_critic.act(obs, critic_obs, out=out, env_fin=env_fin, shadow=sh)
         last = self.actor_critic._last
         t.values, t.actions_log_prob = last["values"], last["logp"]
-        if self._value_norm is not None:
+        if self.value_normalizer is not None:
             # the critic's output -> a raw value, in place, before anything reads the slot: hgym_store_step, the env's transition sink, the
             # finaliser riding in the next policy launch (time-out bootstrap r += gamma V), GAE
-            st.denormalize_values(t.values)
+            self.value_normalizer.denormalize(t.values)
         t.action_mean, t.action_sigma = last["mu"], last["sigma"]
         t.observations, t.critic_observations = obs, critic_obs
         if not self.env_stores_transitions:
@@ -440,9 +439,9 @@ class PPO:
         shadow = st._priv_bf16.flatten(0, 1) if st._priv_bf16 is not None else None
         self.net.critic_values(st._priv_all[:T].flatten(0, 1), st.values.view(-1), shadow)
         self.net.critic_values(st._priv_all[T], st.last_values.view(-1))
-        if self._value_norm is not None:      # the statistics the critic was last trained under: those of the previous update
-            st.denormalize_values(st.values)
-            st.denormalize_values(st.last_values)
+        if self.value_normalizer is not None:      # the statistics the critic was last trained under: those of the previous update
+            self.value_normalizer.denormalize(st.values)
+            self.value_normalizer.denormalize(st.last_values)
         self._rollout_done(T, [True] * T if shadow is not None else st.shadow_valid, True)
 
     def _adv_stats(self, stats):
@@ -459,9 +458,10 @@ class PPO:
         "obs" when the rollout did not write the storage's slot T (RandomNetworkDistillation.reward_pass)."""
         st, deferred = self.storage, self._deferred_ready       # deferred_values() has evaluated the bootstrap observation with the rest
         last_values = st.last_values if deferred else self.actor_critic.evaluate(last_critic_obs)
-        if self._value_norm is not None and not deferred:      # (deferred_values() has denormalised its own)
-            last_values = st.denormalize_values(last_values.reshape(-1, 1).contiguous(), out=self._value_norm["last_values"]).view(-1, 1)
-        if self._smooth is not None and self._smooth["temporal_coef"] > 0.0 and not self._slot_T_written:
+        vn = self.value_normalizer
+        if vn is not None and not deferred:      # (deferred_values() has denormalised its own)
+            last_values = vn.denormalize(last_values.reshape(-1, 1).contiguous(), out=vn.last_values).view(-1, 1)
+        if self._smooth is not None and self._smooth.cfg["temporal_coef"] > 0.0 and not self._slot_T_written:
             # a rollout that copied its observations in (add_transitions) has not written slot T: the temporal term's successor of the last
             # step's rows is the bootstrap observation, which only the caller holds
             if last_obs is None:
@@ -472,8 +472,8 @@ class PPO:
             self._rnd.reward_pass(st, last_critic_obs, last_obs, self._slot_T_written)
         st.compute_returns(last_values, self.gamma, self.lam, stats_hook=self._adv_stats, time_outs=st.time_outs if deferred else None,
                            normalize=self._adv_mode == "batch")
-        if self._value_norm is not None:      # merge the raw returns FIRST, then returns and old values into the critic's units under the new statistics
-            st.normalize_value_targets()
+        if vn is not None:      # merge the raw returns FIRST, then returns and old values into the critic's units under the new statistics
+            vn.normalize_targets(st.returns, st.values)
         self._returns_done()
 
     def _returns_done(self):      # what compute_returns() changes on the host, issued or replayed: the deferred values are used up
@@ -495,27 +495,26 @@ class PPO:
 
     def update_graph_key(self):
         """Everything host-side that compute_returns() / update() bake into their launches, as (name, value) pairs: a change re-captures.
-        dict(key)[name] reads an entry; an option's entry is None while the option is off and comes from where the option lives."""
+        dict(key)[name] reads an entry; an option's entries are listed here as they read while it is off, and an option that is on
+        fills in its own (its graph_key())."""
         st = self.storage
-        return (("ppo_cfg", _struct_bytes(self._ppo_cfg)), ("num_learning_epochs", self.num_learning_epochs),
-                ("num_mini_batches", self.num_mini_batches), ("gamma", float(self.gamma)), ("lam", float(self.lam)),
-                ("permutation", self.permutation), ("perm_seed", self._perm_seed), ("storage", id(st)), ("net", id(self.net)),
-                ("dist_active", bool(dist_utils.active())), ("comm_p2p", bool(self._comm_p2p)), ("net_cfg", _struct_bytes(self.net.cfg)),
-                ("shadows", st._obs_bf16 is not None), ("comm_flip", bool(self.comm_flip)), ("world", self._world),
-                ("symmetry", None if self._symmetry is None else self._symmetry.key()),
-                # the mirror loss (its coefficient is also part of ppo_cfg's bytes), whether the batch is doubled, the scratch the launches name
-                ("mirror_coef", self._mirror_coef), ("augment", self._augment),
-                ("mirror_scratch", None if self._mirror_target is None else (self._mirror_target.data_ptr(), self._mirror_sums.data_ptr())),
-                ("smoothness", smooth_module.graph_key(self._smooth, st.smooth_buffers())),
-                ("rnd", None if self._rnd is None else self._rnd.graph_key()),
-                ("adv_mode", self._adv_mode), ("adv_scratch", st.minibatch_advantages_key()), ("obs_norm", self._obs_norm),
-                ("value_norm", st.value_norm_key()))
+        key = dict(ppo_cfg=_struct_bytes(self._ppo_cfg), num_learning_epochs=self.num_learning_epochs, num_mini_batches=self.num_mini_batches,
+                   gamma=float(self.gamma), lam=float(self.lam), permutation=self.permutation, perm_seed=self._perm_seed, storage=id(st),
+                   net=id(self.net), dist_active=bool(dist_utils.active()), comm_p2p=bool(self._comm_p2p), net_cfg=_struct_bytes(self.net.cfg),
+                   shadows=st._obs_bf16 is not None, comm_flip=bool(self.comm_flip), world=self._world,
+                   symmetry=None if self._symmetry is None else self._symmetry.key(),
+                   # (the mirror loss's coefficient is also part of ppo_cfg's bytes; augment: whether the batch is doubled)
+                   mirror_coef=0.0, augment=self._augment, mirror_scratch=None, smoothness=None, rnd=None,
+                   adv_mode=self._adv_mode, adv_scratch=st.minibatch_advantages_key(), obs_norm=self._obs_norm, value_norm=None)
+        for o in self._options:
+            key.update(o.graph_key())
+        return tuple(key.items())
 
     def rollout_graph_key(self):
         """Everything of this side that a rollout bakes into its launches: the storage's slots, the sink's gamma (BY VALUE), the shadows."""
         key = id(self.storage), self.gamma, self.storage._obs_bf16 is not None
         # with value normalisation the stepwise rollout contains the denormalise launches (eps by value, the block by address); off: the key as ever
-        return key if self._value_norm is None else key + (self.storage.value_norm_key(),)
+        return key if self.value_normalizer is None else key + (self.value_normalizer.graph_key()["value_norm"],)
 
     def after_rollout_replay(self, end_state):
         """Host-side book-keeping of one replayed rollout.  end_state: rollout_end_state() behind the captured pass."""
@@ -543,7 +542,7 @@ class PPO:
         (None, None), so the host can already enqueue the next rollout while this update runs."""
         hgym, net, st, direct = self._hgym, self.net, self.storage, self._direct_exchange()
         T, N = st.num_transitions_per_env, st.num_envs
-        sym, aug, mirror_loss = self._symmetry is not None, self._augment, self._mirror_coef > 0.0
+        sym, aug, mirror_loss, smooth = self._symmetry is not None, self._augment, self._mirror_loss, self._smooth
         if sym:
             # the mirrored half of every column, from the finished rollout (returns, advantages, values, shadows: all there); the mirror
             # loss alone reads only the mirrored observations
@@ -565,16 +564,10 @@ class PPO:
             perm = torch.randperm(self.num_mini_batches * mb, device=self.device)
         if aug:
             perm = st.mirror_index(perm)      # drawn over 2 T N rows; the mirrored half lies behind the bootstrap slot
-        pair = mirror = None
-        if mirror_loss:      # every drawn row's partner, original or mirrored (without augmentation only rows < T N are drawn)
-            pair = mirror_pair_rows(perm, T, N)
-            mirror = st._mirror["act"] + (self._mirror_target, self._mirror_sums)
-            self._mirror_sums[0:2] = 0.0      # (a slice: a fill kernel, as below)
-        smooth = self._smooth
-        if smooth is not None:      # one pass over the whole permutation: every epoch reuses the slices, as the advantage pass's are
-            sb = st._smooth
-            hgym.smooth_pairs(perm, st.dones.view(-1), N, sb["next_idx"], sb["next_weight"])
-            sb["sums"][0:4] = 0.0      # (a slice: a fill kernel)
+        if mirror_loss is not None:      # every drawn row's partner, for every epoch
+            pair = mirror_loss.begin_update(perm, st)
+        if smooth is not None:      # one pass over the whole permutation
+            smooth.begin_update(perm, st)
         cols = st.batch_columns()
         if smooth is not None:      # the T + 1 observation slots are ONE allocation under the column's base pointer: next_idx reaches into slot T
             assert cols[0].data_ptr() == st._obs_all.data_ptr() and st._obs_all.is_contiguous()
@@ -593,16 +586,10 @@ class PPO:
         for _ in range(self.num_learning_epochs):
             for i in range(self.num_mini_batches):
                 idx = perm[i * mb:(i + 1) * mb]
-                if mirror_loss:
-                    batch = hgym.make_batch(*cols, idx, pair_idx=pair[i * mb:(i + 1) * mb], mirror=mirror, **sh)
-                else:
-                    batch = hgym.make_batch(*cols, idx, **sh)
+                mirror = {} if mirror_loss is None else mirror_loss.minibatch(pair[i * mb:(i + 1) * mb], st)
+                batch = hgym.make_batch(*cols, idx, **mirror, **sh)
                 if smooth is not None:
-                    on_t = smooth["temporal_coef"] > 0.0
-                    net.ppo_grad_smooth(self._ppo_cfg, batch, hgym.make_smooth(
-                        smooth["temporal_coef"], smooth["spatial_coef"], next_idx=sb["next_idx"][i * mb:(i + 1) * mb] if on_t else None,
-                        next_weight=sb["next_weight"][i * mb:(i + 1) * mb], noise_std=sb["noise_std"], seed=smooth["seed"],
-                        target_next=sb["target_next"], target_near=sb["target_near"], rows=sb["rows"], sums=sb["sums"]))
+                    net.ppo_grad_smooth(self._ppo_cfg, batch, smooth.minibatch(i))
                 else:
                     net.ppo_grad(self._ppo_cfg, batch)
                 if self._obs_norm is not None:
@@ -648,11 +635,10 @@ class PPO:
     def read_log(self, block):
         """A host copy of log_block() -> hgym.opt_summary's dict; sets last_denoise_loss, last_mirror_loss, last_smoothness,
         last_value_norm and RND's last_log on the way.  The one reader behind update(sync=True) and the runner's asynchronous log."""
-        self.last_mirror_loss = self.mirror_loss_from(block)
-        self.last_smoothness = self.smoothness_from(block)
-        self.rnd_log_from(block)
-        self.last_value_norm = self.value_norm_from(block)
-        o = self._hgym.opt_summary(self._log.split(block)["opt"], self._ppo_cfg.aux_coef > 0.0)
+        parts = self._log.split(block)
+        for option in self._options:      # each leaves its numbers on itself: last_mirror_loss, last_smoothness, last_value_norm read them there
+            option.read_log(parts)
+        o = self._hgym.opt_summary(parts["opt"], self._ppo_cfg.aux_coef > 0.0)
         self.last_denoise_loss = o["denoise_loss"]
         return o
 
@@ -661,44 +647,9 @@ class PPO:
         out = []
         if self.denoise_coef and self.last_denoise_loss is not None:
             out.append(("Loss/denoise_mse", self.last_denoise_loss))
-        if self._mirror_coef > 0.0 and self.last_mirror_loss is not None:
-            out.append(("Loss/mirror", self.last_mirror_loss))
-        if self.last_smoothness is not None:
-            out += [("Loss/smooth_temporal", self.last_smoothness["temporal"]), ("Loss/smooth_spatial", self.last_smoothness["spatial"])]
-        if self._rnd is not None and self._rnd.last_log is not None:      # Loss/rnd, Rnd/intrinsic_reward, Rnd/extrinsic_reward, Rnd/weight, Rnd/std
-            out += list(self._rnd.last_log.items())
-        vn = getattr(self, "last_value_norm", None)      # (defaulted as in _log_parts: the same stand-ins call this method)
-        if vn is not None:
-            out += [("Policy/value_norm_mean", vn["mean"]), ("Policy/value_norm_std", vn["std"])]
+        for option in self._scalar_order:      # Loss/mirror; Loss/smooth_temporal, Loss/smooth_spatial; Loss/rnd, Rnd/*; Policy/value_norm_mean, Policy/value_norm_std
+            out += option.log_scalars()
         return out
-
-    def value_norm_from(self, block):
-        """{count, mean, var, std} of the returns' running statistics from a host copy of log_block(); None when the option is off."""
-        b = self._log.split(block).get("value_norm")
-        if b is None:
-            return None
-        count, mean, var = (float(x) for x in b)
-        return dict(count=count, mean=mean, var=var, std=math.sqrt(max(var, 0.0)))
-
-    def rnd_log_from(self, block):
-        """Loss/rnd and the Rnd/* numbers from a host copy of log_block() (RandomNetworkDistillation.log_from); None when RND is off."""
-        p = self._log.split(block)
-        return None if self._rnd is None else self._rnd.log_from(torch.cat((p["rnd_sums"], p["rnd_block"])))
-
-    def smoothness_from(self, block):
-        """{temporal, spatial, valid_fraction} from a host copy of log_block(): the mean plain MSE per minibatch of either term and the share
-        of drawn rows with a successor; None when the regulariser is off."""
-        sums = self._log.split(block).get("smooth")
-        if sums is None:
-            return None
-        t, s, w, n = (float(x) for x in sums)
-        mb = self.storage._smooth["target_next"].numel() // self.actor_critic.num_actions
-        n = max(n, 1.0)
-        return dict(temporal=t / n, spatial=s / n, valid_fraction=w / (mb * n))
-
-    def mirror_loss_from(self, block):
-        """The mean mirror MSE per minibatch from a host copy of log_block(); None when the loss is off."""
-        return mean_of_sums(self._log.split(block).get("mirror"))
 
     def normalizer_step(self):
         """The normaliser's one step per iteration, at the end of update(), ahead of storage.clear(): accumulate the T * N stored raw

@@ -320,8 +320,8 @@ class RandomNetworkDistillation(nn.Module):
 
     def graph_key(self):
         """PPO.update_graph_key's entry: the nets, the block and the configuration bytes the captured launches name."""
-        return (id(self), id(self.nets[0]), id(self.nets[1]), self.block.data_ptr(),
-                bytes(C.string_at(C.addressof(self.rnd_cfg), C.sizeof(self.rnd_cfg))))
+        return dict(rnd=(id(self), id(self.nets[0]), id(self.nets[1]), self.block.data_ptr(),
+                         bytes(C.string_at(C.addressof(self.rnd_cfg), C.sizeof(self.rnd_cfg)))))
 
     # ------------------------------------------------------------------ logging
     LOG_DOUBLES = 2 + 16      # the loss's two sums, then the head of the block
@@ -343,6 +343,13 @@ class RandomNetworkDistillation(nn.Module):
         self.last_log = {"Loss/rnd": self.last_loss, "Rnd/intrinsic_reward": t[2 + L.RND_SUM_INTRINSIC] / rows,
                          "Rnd/extrinsic_reward": t[2 + L.RND_SUM_REWARDS] / rows, "Rnd/weight": t[2 + L.RND_WEIGHT_LAST], "Rnd/std": t[2 + L.RND_STD]}
         return self.last_log
+
+    def read_log(self, parts):
+        """log_from() on the two parts of a host copy of PPO.log_block()."""
+        return self.log_from(torch.cat((parts["rnd_sums"], parts["rnd_block"])))
+
+    def log_scalars(self):      # Loss/rnd, Rnd/intrinsic_reward, Rnd/extrinsic_reward, Rnd/weight, Rnd/std
+        return [] if self.last_log is None else list(self.last_log.items())
 
     # ------------------------------------------------------------------ checkpoints
     def rnd_state_dict(self):

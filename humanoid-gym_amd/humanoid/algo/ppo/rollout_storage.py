@@ -94,58 +94,6 @@ class RolloutStorage:
         """PPO.update_graph_key's entry: the column and the scratch the per-minibatch pass names; None without them."""
         return None if self.advantages_mb is None else (self.advantages_mb.data_ptr(), self._adv_mb_scratch.data_ptr())
 
-    _value_norm = None      # value-target normalisation's state and buffers (enable_value_normalization), None without it
-
-    def enable_value_normalization(self, eps):
-        """Native extension (PPO.value_normalization): the running statistics of the raw returns -- `block`, three
-        doubles (count, mean, var) = (0, 0, 1) --, the scratch of hgym_value_norm_merge for the T N returns, and an (N, 1) buffer for the
-        denormalised bootstrap value, all allocated once.  The critic then lives in normalised units: whoever fills `values` follows with
-        denormalize_values(), compute_returns() runs GAE on raw values, and normalize_value_targets() behind it puts `returns` and
-        `values` into the critic's units for the update."""
-        from hgym import _lib as L
-        T, N = self.num_transitions_per_env, self.num_envs
-        self._value_norm = dict(eps=float(eps), block=L.value_norm_block(self.device), scratch=L.value_norm_scratch(T * N, self.device),
-                                last_values=torch.zeros(N, 1, dtype=torch.float32, device=self.device))
-
-    def denormalize_values(self, v, out=None):
-        """out (default: v itself) = v * scale_f + mean_f under the statistics as they are (hgym_value_denormalize: one launch, fixed
-        arguments -- capturable): the critic's outputs -> raw values.  v: any contiguous fp32 column."""
-        import hgym
-        vn = self._value_norm
-        return hgym.value_denormalize(v.view(-1), vn["block"], vn["eps"], None if out is None else out.view(-1))
-
-    def normalize_value_targets(self):
-        """Behind compute_returns(): merge the T N raw returns into the statistics (hgym_value_norm_merge), then returns <- normalise(returns)
-        and values <- normalise(values) in place under the NEW statistics (hgym_value_normalize twice): three launches, fixed arguments."""
-        import hgym
-        vn = self._value_norm
-        hgym.value_norm_merge(self.returns.view(-1), vn["block"], vn["scratch"])
-        hgym.value_normalize(self.returns.view(-1), vn["block"], vn["eps"])
-        hgym.value_normalize(self.values.view(-1), vn["block"], vn["eps"])
-
-    def value_norm_key(self):
-        """PPO.update_graph_key's entry: eps and the two buffers the launches name; None without them."""
-        vn = self._value_norm
-        return None if vn is None else (vn["eps"], vn["block"].data_ptr(), vn["scratch"].data_ptr())
-
-    _smooth = None      # the smoothness regulariser's buffers (enable_smoothness), None without it
-
-    def enable_smoothness(self, perm_len, mb, num_obs, num_actions, noise_std):
-        """Native extension (PPO.smoothness): everything hgym_smooth_pairs and hgym_ppo_grad_smooth name, allocated once (torch.zeros: nothing
-        is allocated during an update) -- next_idx / next_weight for a whole permutation of perm_len rows, noise_std (num_obs; zeros when
-        the spatial term is off), and for one minibatch of mb rows target_next, target_near (mb x num_actions) and rows (mb x the width
-        rounded up to 4), then the four sums."""
-        import hgym
-        z = lambda n, dtype=torch.float32: torch.zeros(max(int(n), 1), dtype=dtype, device=self.device)
-        ns = z(num_obs)
-        if noise_std is not None:
-            ns.copy_(torch.tensor(noise_std, dtype=torch.float32))
-        self._smooth = dict(next_idx=z(perm_len, torch.int64), next_weight=z(perm_len), noise_std=ns, target_next=z(mb * num_actions),
-                            target_near=z(mb * num_actions), rows=z(mb * hgym.smooth_ld(num_obs)), sums=z(4, torch.float64))
-
-    def smooth_buffers(self):
-        return () if self._smooth is None else tuple(self._smooth.values())
-
     def enable_rnd(self, num_states, num_outputs):
         """Native extension (PPO.rnd): rnd_states (T + 1, N, S) -- a contiguous copy of the chosen observation columns of slots 0 .. T (the
         net kernels gather rows without a leading dimension) --, rnd_target (T + 1, N, K), rnd_pred (T, N, K) -- the predictor over slots

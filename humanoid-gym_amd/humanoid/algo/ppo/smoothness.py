@@ -1,5 +1,5 @@
 """The smoothness regulariser on the policy's mean (PPO.smoothness): the configuration and what init_storage refuses,
-as functions that need no device.
+as functions that need no device, and the option's device side, Smoothness.
 
 PPO.smoothness = None | dict with the keys of DEFAULTS:
   temporal_coef  lamT >= 0: pulls mu(s_t) towards mu(s_t+1) (rows whose episode ended weigh 0)
@@ -10,6 +10,8 @@ PPO.smoothness = None | dict with the keys of DEFAULTS:
   seed           the Philox key of the perturbation (default: the run's seed)
 None, or both coefficients 0: off."""
 import math
+
+import torch
 
 DEFAULTS = dict(temporal_coef=0.0, spatial_coef=0.0, noise_std=None, noise_scale=1.0, seed=None)
 
@@ -66,12 +68,56 @@ def check_setup(world=1, symmetry=None, distillation=False):
         raise ValueError("PPO.smoothness does not support Distillation")
 
 
-def graph_key(cfg, buffers):
-    """PPO.update_graph_key's entry: the coefficients and the seed of a parse_config() dict (None: off) and the scratch the launches name
-    (RolloutStorage.smooth_buffers)."""
-    if cfg is None:
-        return None
-    return (cfg["temporal_coef"], cfg["spatial_coef"], cfg["seed"]) + tuple(t.data_ptr() for t in buffers)
+class Smoothness:
+    """The option as PPO holds it (PPO._smooth; None: off): the parse_config() dict `cfg`, everything hgym_smooth_pairs and
+    hgym_ppo_grad_smooth name, and its part of the log."""
+    BUFFERS = ("next_idx", "next_weight", "noise_std", "target_next", "target_near", "rows", "sums")
+
+    def __init__(self, cfg, perm_len, mb, num_obs, num_actions, device):
+        """Allocated once (torch.zeros: nothing is allocated during an update) -- next_idx / next_weight for a whole permutation of
+        perm_len rows, noise_std (num_obs; zeros when the spatial term is off), and for one minibatch of mb rows target_next, target_near
+        (mb x num_actions) and rows (mb x the width rounded up to 4), then the four sums."""
+        import hgym
+        z = lambda n, dtype=torch.float32: torch.zeros(max(int(n), 1), dtype=dtype, device=device)
+        self.cfg, self.mb, self.last = cfg, int(mb), None
+        self.next_idx, self.next_weight, self.noise_std = z(perm_len, torch.int64), z(perm_len), z(num_obs)
+        if cfg["noise_std"] is not None:
+            self.noise_std.copy_(torch.tensor(cfg["noise_std"], dtype=torch.float32))
+        self.target_next, self.target_near = z(mb * num_actions), z(mb * num_actions)
+        self.rows, self.sums = z(mb * hgym.smooth_ld(num_obs)), z(4, torch.float64)
+
+    def begin_update(self, perm, storage):
+        """One pass over the whole permutation: every epoch reuses the slices, as the advantage pass's are."""
+        import hgym
+        hgym.smooth_pairs(perm, storage.dones.view(-1), storage.num_envs, self.next_idx, self.next_weight)
+        self.sums[0:4] = 0.0      # (a slice: a fill kernel)
+
+    def minibatch(self, i):
+        """hgym_ppo_grad_smooth's descriptor of minibatch i: its slices of the successor map, and no next_idx with the temporal term off."""
+        import hgym
+        c, rows = self.cfg, slice(i * self.mb, (i + 1) * self.mb)
+        return hgym.make_smooth(c["temporal_coef"], c["spatial_coef"], next_idx=self.next_idx[rows] if c["temporal_coef"] > 0.0 else None,
+                                next_weight=self.next_weight[rows], noise_std=self.noise_std, seed=c["seed"], target_next=self.target_next,
+                                target_near=self.target_near, rows=self.rows, sums=self.sums)
+
+    def graph_key(self):
+        """PPO.update_graph_key's entry: the coefficients and the seed, and the scratch the launches name."""
+        c = self.cfg
+        return dict(smoothness=(c["temporal_coef"], c["spatial_coef"], c["seed"]) + tuple(getattr(self, n).data_ptr() for n in self.BUFFERS))
+
+    def log_parts(self):
+        return [("smooth", self.sums)]
+
+    def read_log(self, parts):
+        """`last` = {temporal, spatial, valid_fraction} from the parts of a host copy of PPO.log_block(): the mean plain MSE per minibatch
+        of either term and the share of drawn rows with a successor."""
+        t, s, w, n = (float(x) for x in parts["smooth"])
+        n = max(n, 1.0)
+        self.last = dict(temporal=t / n, spatial=s / n, valid_fraction=w / (self.mb * n))
+        return self.last
+
+    def log_scalars(self):
+        return [] if self.last is None else [("Loss/smooth_temporal", self.last["temporal"]), ("Loss/smooth_spatial", self.last["spatial"])]
 
 
 def env_noise_std(env_cfg, noise_scale_vec, num_obs):

@@ -3,7 +3,7 @@
 1. Layout: every on/off combination of PPO's three tails and Distillation's block -- device() is the hand-written concatenation
    opt | mirror(2) | rnd sums(2) | rnd block head(RND_HEADER) | smooth(4)  /  opt | bc(2), split() names exactly the parts that are on, and
    an option-free block IS opt_state.
-2. The public readers (mirror_loss_from, smoothness_from, rnd_log_from, behavior_loss_from) against the offset arithmetic they replace.
+2. The options' readers (read_log of MirrorLoss, Smoothness and RND; Distillation.behavior_loss_from) against the offset arithmetic they replace.
 3. PPO.check_setup: every refusal with its message, the order in which they win, Distillation's refusals ahead of them -- no device."""
 import itertools
 import re
@@ -15,23 +15,49 @@ import torch
 from hgym import _lib as L
 from humanoid.algo import PPO, Distillation, RandomNetworkDistillation as RND
 from humanoid.algo.ppo.log_block import LogBlock
+from humanoid.algo.ppo.mirror_loss import MirrorLoss
+from humanoid.algo.ppo.smoothness import Smoothness
 
-MB, ACTIONS = 4, 3
+MB = 4
 f64 = lambda *v: torch.tensor(v, dtype=torch.float64)
+
+
+def _option(cls, **fields):
+    """An option object made without __init__ (which allocates on a device): the fields its log side uses."""
+    o = object.__new__(cls)
+    o.__dict__.update(dict(last=None), **fields)
+    return o
+
+
+def _rnd(**fields):
+    """The same for RND (an nn.Module): a stand-in that borrows its log methods."""
+    r = SimpleNamespace(**fields)
+    r.log_parts, r.log_from, r.read_log, r.log_scalars = (lambda: RND.log_parts(r)), (lambda tail: RND.log_from(r, tail)), \
+        (lambda parts: RND.read_log(r, parts)), (lambda: RND.log_scalars(r))
+    return r
 
 
 def _alg(mirror=None, rnd=None, smooth=None, bc=None):
     """A stand-in for a PPO (or, with bc, a Distillation) behind init_storage: the fields _log_parts and the readers use.  mirror,
     smooth, bc: the part's tensor or None (off); rnd: (sums, block) or None."""
     opt = torch.arange(1.0, L.OPT_STATE + 1.0, dtype=torch.float64)
-    a = SimpleNamespace(net=SimpleNamespace(opt_state=opt), _mirror_sums=mirror, _rnd=None, _smooth=None if smooth is None else {},
-                        storage=SimpleNamespace(_smooth=None if smooth is None else dict(sums=smooth, target_next=torch.zeros(MB * ACTIONS))),
-                        actor_critic=SimpleNamespace(num_actions=ACTIONS), _bc_sums=bc)
-    if rnd is not None:
-        r = a._rnd = SimpleNamespace(sums=rnd[0], block=rnd[1])
-        r.log_parts, r.log_from = (lambda: RND.log_parts(r)), (lambda tail: RND.log_from(r, tail))
+    a = SimpleNamespace(net=SimpleNamespace(opt_state=opt), _mirror_loss=None if mirror is None else _option(MirrorLoss, sums=mirror),
+                        _rnd=None if rnd is None else _rnd(sums=rnd[0], block=rnd[1]),
+                        _smooth=None if smooth is None else _option(Smoothness, sums=smooth, mb=MB), value_normalizer=None, _bc_sums=bc)
+    a._options = tuple(o for o in (a._mirror_loss, a._rnd, a._smooth, a.value_normalizer) if o is not None)
     a._log = LogBlock((PPO if bc is None else Distillation)._log_parts(a))
     return a
+
+
+def _read(a, option, block):
+    """Option `option` of stand-in `a` reads its numbers from a host copy of the log block; None when it is off."""
+    o = getattr(a, option)
+    return None if o is None else o.read_log(a._log.split(block))
+
+
+mirror_loss_from = lambda a, block: _read(a, "_mirror_loss", block)
+smoothness_from = lambda a, block: _read(a, "_smooth", block)
+rnd_log_from = lambda a, block: _read(a, "_rnd", block)
 
 
 def _tails():
@@ -88,18 +114,18 @@ def test_readers_against_the_offsets_they_replace():
     # the mirror loss: sum / steps, behind opt_state
     a = _alg(mirror=f64(7.0, 2.0))
     block = a._log.device()
-    assert PPO.mirror_loss_from(a, block) == 7.0 / 2.0 == float(block[n]) / max(float(block[n + 1]), 1.0)
-    assert PPO.mirror_loss_from(_alg(mirror=f64(7.0, 0.0)), _alg(mirror=f64(7.0, 0.0))._log.device()) == 7.0      # no step: divides by 1
-    assert PPO.smoothness_from(a, block) is None and PPO.rnd_log_from(a, block) is None
+    assert mirror_loss_from(a, block) == 7.0 / 2.0 == float(block[n]) / max(float(block[n + 1]), 1.0)
+    assert mirror_loss_from(_alg(mirror=f64(7.0, 0.0)), _alg(mirror=f64(7.0, 0.0))._log.device()) == 7.0      # no step: divides by 1
+    assert smoothness_from(a, block) is None and rnd_log_from(a, block) is None
     # smoothness: the last four numbers; n = 0 divides by 1
     for sums, want in (((3.0, 5.0, 6.0, 0.0), dict(temporal=3.0, spatial=5.0, valid_fraction=6.0 / MB)),
                        ((3.0, 5.0, 6.0, 2.0), dict(temporal=1.5, spatial=2.5, valid_fraction=6.0 / (MB * 2.0)))):
         a = _alg(mirror=f64(7.0, 2.0), smooth=f64(*sums))
         block = a._log.device()
-        assert PPO.smoothness_from(a, block) == want
+        assert smoothness_from(a, block) == want
         t, s, w, cnt = (float(x) for x in block[block.numel() - 4:])
         assert want == dict(temporal=t / max(cnt, 1.0), spatial=s / max(cnt, 1.0), valid_fraction=w / (MB * max(cnt, 1.0)))
-        assert PPO.mirror_loss_from(a, block) == 3.5
+        assert mirror_loss_from(a, block) == 3.5
     # RND: LOG_DOUBLES numbers ahead of the smoothness sums (or at the end without them)
     head = torch.zeros(L.RND_HEADER + 5, dtype=torch.float64)
     head[L.RND_ROWS], head[L.RND_SUM_INTRINSIC], head[L.RND_SUM_REWARDS], head[L.RND_WEIGHT_LAST], head[L.RND_STD] = 8.0, 2.0, 4.0, 0.75, 1.25
@@ -107,31 +133,31 @@ def test_readers_against_the_offsets_they_replace():
     for smooth in (None, f64(3.0, 5.0, 6.0, 2.0)):
         a = _alg(mirror=f64(7.0, 2.0), rnd=(f64(6.0, 4.0), head), smooth=smooth)
         block = a._log.device()
-        got = PPO.rnd_log_from(a, block)
+        got = rnd_log_from(a, block)
         assert got == want and list(got) == list(want) and a._rnd.last_log == want and a._rnd.last_loss == 1.5
         end = block.numel() - (4 if smooth is not None else 0)
         assert RND.log_from(SimpleNamespace(), block[end - RND.LOG_DOUBLES:end]) == want
-        assert PPO.mirror_loss_from(a, block) == 3.5 and (PPO.smoothness_from(a, block) is None) == (smooth is None)
+        assert mirror_loss_from(a, block) == 3.5 and (smoothness_from(a, block) is None) == (smooth is None)
     # everything off
     a = _alg()
     block = a._log.device()
-    assert PPO.mirror_loss_from(a, block) is None and PPO.smoothness_from(a, block) is None and PPO.rnd_log_from(a, block) is None
+    assert mirror_loss_from(a, block) is None and smoothness_from(a, block) is None and rnd_log_from(a, block) is None
     # Distillation: sum / steps behind opt_state, and no mirror loss
     a = _alg(bc=f64(9.0, 4.0))
     block = a._log.device()
     assert Distillation.behavior_loss_from(a, block) == 9.0 / 4.0 == float(block[n]) / max(float(block[n + 1]), 1.0)
-    assert PPO.mirror_loss_from(a, block) is None and "mirror_loss_from" not in vars(Distillation)
+    assert mirror_loss_from(a, block) is None and a._options == ()
 
 
 def test_log_scalars_order_and_conditions():
-    a = SimpleNamespace(denoise_coef=0.5, last_denoise_loss=1.0, _mirror_coef=0.25, last_mirror_loss=2.0,
-                        last_smoothness=dict(temporal=3.0, spatial=4.0, valid_fraction=1.0),
-                        _rnd=SimpleNamespace(last_log={"Loss/rnd": 5.0, "Rnd/intrinsic_reward": 6.0, "Rnd/extrinsic_reward": 7.0, "Rnd/weight": 8.0, "Rnd/std": 9.0}))
+    rnd = _rnd(last_log={"Loss/rnd": 5.0, "Rnd/intrinsic_reward": 6.0, "Rnd/extrinsic_reward": 7.0, "Rnd/weight": 8.0, "Rnd/std": 9.0})
+    a = SimpleNamespace(denoise_coef=0.5, last_denoise_loss=1.0,
+                        _scalar_order=(_option(MirrorLoss, last=2.0), _option(Smoothness, last=dict(temporal=3.0, spatial=4.0, valid_fraction=1.0)), rnd))
     assert PPO.log_scalars(a) == [("Loss/denoise_mse", 1.0), ("Loss/mirror", 2.0), ("Loss/smooth_temporal", 3.0), ("Loss/smooth_spatial", 4.0),
                                   ("Loss/rnd", 5.0), ("Rnd/intrinsic_reward", 6.0), ("Rnd/extrinsic_reward", 7.0), ("Rnd/weight", 8.0), ("Rnd/std", 9.0)]
-    a.denoise_coef, a._mirror_coef, a.last_smoothness, a._rnd.last_log = 0.0, 0.0, None, None      # values left behind, options off
+    a.denoise_coef, a._scalar_order, rnd.last_log = 0.0, (rnd,), None      # a value left behind, the other options off, RND on with nothing read yet
     assert PPO.log_scalars(a) == []
-    a._rnd = None
+    a._scalar_order = ()
     assert PPO.log_scalars(a) == []
 
 

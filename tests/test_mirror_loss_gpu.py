@@ -261,7 +261,7 @@ def test_update_with_the_mirror_loss(monkeypatch, augmentation):
     alg, spec, obs, idx_log, pair_log, params_log = _update_run(monkeypatch, M.COEF, augmentation)
     T, N = T_UP, N_UP
     st = alg.storage
-    assert st.mirrored and alg._mirror_coef == M.COEF and alg._augment is augmentation and alg._ppo_cfg.mirror_coef == M.COEF
+    assert st.mirrored and alg._mirror_loss.coef == M.COEF and alg._augment is augmentation and alg._ppo_cfg.mirror_coef == M.COEF
     assert len(idx_log) == 2 == len(pair_log) == len(params_log)
     rows = (2 if augmentation else 1) * T * N
     full = torch.zeros((2 * T + 1) * N, obs.shape[1])
@@ -300,7 +300,7 @@ def test_augmentation_alone_is_the_parents_update(monkeypatch):
     runs = []
     for coef, aug in ((0.0, True), (None, None)):
         alg, _, _, idx_log, pair_log, _ = _update_run(monkeypatch, coef, aug)
-        assert alg._mirror_target is None and alg._mirror_sums is None and alg.last_mirror_loss is None and pair_log == [None, None]
+        assert alg._mirror_loss is None and alg._options == () and alg.last_mirror_loss is None and pair_log == [None, None]
         assert alg._augment and idx_log[0].numel() == T_UP * N_UP
         runs.append((alg.net.params.clone(), alg.net.adam_m.clone(), alg.net.adam_v.clone(), idx_log))
         monkeypatch.undo()
@@ -369,7 +369,7 @@ def _runner(monkeypatch, log_root, augmentation, seed=57):
     env, _ = task_registry.make_env(name="humanoid_ppo", args=args, env_cfg=env_cfg)
     runner, _ = task_registry.make_alg_runner(env=env, name="humanoid_ppo", args=args, train_cfg=train_cfg, log_root=str(log_root))
     alg = runner.alg
-    assert alg.storage.mirrored and alg._mirror_coef == M.COEF and alg._augment is augmentation and alg._ppo_cfg.mirror_coef == M.COEF
+    assert alg.storage.mirrored and alg._mirror_loss.coef == M.COEF and alg._augment is augmentation and alg._ppo_cfg.mirror_coef == M.COEF
     return runner
 
 
@@ -391,7 +391,7 @@ def test_runner_captured_as_eager(monkeypatch, tmp_path, augmentation):
             opt[L.OPT_GRAD_SQNORM] = 0.0
         assert alg.last_mirror_loss is not None and alg.last_mirror_loss > 0.0
         runs[mode] = dict(params=net.params.clone(), adam_m=net.adam_m.clone(), adam_v=net.adam_v.clone(), opt_state=opt,
-                          mirror_sums=alg._mirror_sums.clone(), last=torch.tensor([alg.last_mirror_loss], dtype=torch.float64))
+                          mirror_sums=alg._mirror_loss.sums.clone(), last=torch.tensor([alg.last_mirror_loss], dtype=torch.float64))
         for k, t in runs[mode].items():
             assert torch.isfinite(t).all(), (mode, k)
         if mode == "0":

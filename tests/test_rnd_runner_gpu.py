@@ -100,7 +100,7 @@ def test_weight_zero_leaves_the_policy_alone(path):
     K = a.alg._rnd.num_outputs
     assert not torch.equal(p0[K:], p1[K:]) and torch.equal(t0, a.alg._rnd.nets[1].params)      # the predictor moved, the target did not
     assert torch.equal(p0[:K], p1[:K])                                                          # (its unused sigma slots did not either)
-    log = a.alg.rnd_log_from(a.alg.log_block().cpu())
+    log = a.alg._rnd.read_log(a.alg._log.split(a.alg.log_block().cpu()))
     print(log)
     assert np.isfinite(log["Loss/rnd"]) and log["Loss/rnd"] > 0 and log["Rnd/weight"] == 0.0 and log["Rnd/intrinsic_reward"] == 0.0
     assert float(a.alg._rnd.block[R.COUNTER]) == 3 * T and float(a.alg._rnd.nets[0].opt_state[L.OPT_STEP]) == 3 * 4
@@ -255,25 +255,25 @@ def test_mirror_loss_and_rnd_share_the_log_block():
     """The mirror loss (no augmentation) together with RND: both tails lie behind opt_state and each reader finds its own by name."""
     r = _runner(rnd=dict(weight=0.5, **NETS["fused"]), mirror_loss_coef=0.5)
     alg = r.alg
-    assert alg._mirror_coef == 0.5 and alg._augment is False and alg._rnd is not None and alg._smooth is None
+    assert alg._mirror_loss.coef == 0.5 and alg._augment is False and alg._rnd is not None and alg._smooth is None
     r.learn(num_learning_iterations=1, init_at_random_ep_len=True)
     block = alg.log_block().cpu()
     assert block.numel() == alg._log.numel() == L.OPT_STATE + 2 + alg._rnd.LOG_DOUBLES
     parts = alg._log.split(block)
     assert list(parts) == ["opt", "mirror", "rnd_sums", "rnd_block"]
-    assert torch.equal(parts["opt"], alg.net.opt_state.cpu()) and torch.equal(parts["mirror"], alg._mirror_sums.cpu())
-    mirror, rnd = alg.mirror_loss_from(block), alg.rnd_log_from(block)
+    assert torch.equal(parts["opt"], alg.net.opt_state.cpu()) and torch.equal(parts["mirror"], alg._mirror_loss.sums.cpu())
+    mirror, rnd = alg._mirror_loss.read_log(parts), alg._rnd.read_log(parts)
     print("Loss/mirror %.4e" % mirror, rnd)
     assert np.isfinite(mirror) and mirror > 0
     assert set(rnd) == {"Loss/rnd", "Rnd/intrinsic_reward", "Rnd/extrinsic_reward", "Rnd/weight", "Rnd/std"}
     assert all(np.isfinite(v) for v in rnd.values()) and rnd["Loss/rnd"] > 0 and rnd["Rnd/intrinsic_reward"] > 0 and rnd["Rnd/weight"] == 0.5
-    assert alg.smoothness_from(block) is None
+    assert alg._smooth is None and "smooth" not in parts
 
 
 def test_off_means_absent():
     r = _runner()
     alg, st = r.alg, r.alg.storage
-    assert alg._rnd is None and alg.rnd is None and alg.rnd_log_from(alg.log_block().cpu()) is None
+    assert alg._rnd is None and alg.rnd is None and alg._options == () and list(alg._log.split(alg.log_block().cpu())) == ["opt"]
     assert not any(hasattr(st, k) for k in ("rnd_states", "rnd_target", "rnd_pred", "rnd_error", "rnd_intrinsic"))
     assert alg.log_block().numel() == alg.net.opt_state.numel() == L.OPT_STATE
     import hgym

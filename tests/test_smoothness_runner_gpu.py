@@ -59,10 +59,10 @@ def _runner(tmp=None, smooth=None, seed=31, exact=False, save_interval=50, combi
 
 def _state(runner):
     torch.cuda.synchronize()
-    net, st = runner.alg.net, runner.alg.storage
+    net, st, sm = runner.alg.net, runner.alg.storage, runner.alg._smooth
     out = [net.params.clone(), net.adam_m.clone(), net.adam_v.clone(), net.opt_state[L.OPT_LR:L.OPT_STEP + 1].clone(), st._obs_all[0].clone()]
-    if st._smooth is not None:
-        out += [st._smooth["sums"].clone(), st._smooth["next_weight"].clone()]
+    if sm is not None:
+        out += [sm.sums.clone(), sm.next_weight.clone()]
     return out
 
 
@@ -77,8 +77,8 @@ def test_captured_update_equals_eager_update(monkeypatch, tmp_path, plan):
     for k, v in PLANS[plan].items():
         monkeypatch.setenv(k, v)
     a = _runner(tmp_path / "a", smooth=BOTH)
-    assert a.alg._smooth["noise_std"] is not None and len(a.alg._smooth["noise_std"]) == a.env.num_obs      # the env's own sensor noise
-    assert max(a.alg._smooth["noise_std"]) > 0.0
+    assert a.alg._smooth.cfg["noise_std"] is not None and len(a.alg._smooth.cfg["noise_std"]) == a.env.num_obs      # the env's own sensor noise
+    assert max(a.alg._smooth.cfg["noise_std"]) > 0.0
     a.learn(num_learning_iterations=3, init_at_random_ep_len=True)
     a.wait_for_saves()
     sa = _state(a)
@@ -91,12 +91,12 @@ def test_captured_update_equals_eager_update(monkeypatch, tmp_path, plan):
     print("plan %s: update graph %s, rollout graph %s" % (plan, a._update_graph is not None, a._graph is not None))
     if plan == "default":
         assert a._update_graph is not None and a.alg.update_capturable()
-    log = b.alg.smoothness_from(b.alg.log_block().cpu())
+    log = b.alg._smooth.read_log(b.alg._log.split(b.alg.log_block().cpu()))
     print("Loss/smooth_temporal %.4e Loss/smooth_spatial %.4e valid_fraction %.3f" % (log["temporal"], log["spatial"], log["valid_fraction"]))
     assert np.isfinite(log["temporal"]) and log["temporal"] > 0 and np.isfinite(log["spatial"]) and log["spatial"] > 0
     assert 0.5 < log["valid_fraction"] <= 1.0
     key = a.alg.update_graph_key()
-    a.alg._smooth["temporal_coef"] = 3.0
+    a.alg._smooth.cfg["temporal_coef"] = 3.0
     assert a.alg.update_graph_key() != key      # another coefficient re-captures
     off = _runner().alg.update_graph_key()
     assert dict(off)["smoothness"] is None and dict(key)["smoothness"] is not None and [n for n, _ in off] == [n for n, _ in key]
@@ -131,8 +131,9 @@ def test_everything_else_on(monkeypatch):
     assert _same(sa, _state(b))
     assert all(torch.isfinite(t.double()).all() for t in sa)
     block = b.alg.log_block().cpu()
-    log = b.alg.smoothness_from(block)
-    assert log["temporal"] > 0 and log["spatial"] > 0 and b.alg.rnd_log_from(block)["Loss/rnd"] > 0      # both tails are read where they lie
+    parts = b.alg._log.split(block)
+    log = b.alg._smooth.read_log(parts)
+    assert log["temporal"] > 0 and log["spatial"] > 0 and b.alg._rnd.read_log(parts)["Loss/rnd"] > 0      # both tails are read where they lie
     assert block.numel() == L.OPT_STATE + b.alg._rnd.LOG_DOUBLES + 4
 
 
@@ -179,8 +180,8 @@ def test_slot_T_holds_the_bootstrap_observation():
 def test_off_means_absent_and_the_parents_launches(monkeypatch):
     r = _runner()
     alg, st = r.alg, r.alg.storage
-    assert alg._smooth is None and alg.smoothness is None and st._smooth is None and st.smooth_buffers() == ()
-    assert alg.log_block().numel() == alg.net.opt_state.numel() == L.OPT_STATE and alg.smoothness_from(alg.log_block().cpu()) is None
+    assert alg._smooth is None and alg.smoothness is None and alg._options == () and dict(alg.update_graph_key())["smoothness"] is None
+    assert alg.log_block().numel() == alg.net.opt_state.numel() == L.OPT_STATE and list(alg._log.split(alg.log_block().cpu())) == ["opt"]
     calls = []
     monkeypatch.setattr(alg.net, "ppo_grad_smooth", lambda *a: calls.append("smooth"))
     grad = alg.net.ppo_grad

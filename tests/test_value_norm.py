@@ -20,6 +20,7 @@ from humanoid.algo import PPO, Distillation
 from humanoid.algo.ppo import checkpoint as ckpt
 from humanoid.algo.ppo.log_block import LogBlock
 from humanoid.algo.ppo.normalizer import ValueNormalizer
+from humanoid.algo.ppo.smoothness import Smoothness
 
 
 # ------------------------------------------------------------------------------------------------ 1. the restatement
@@ -151,20 +152,22 @@ def test_log_block_part_and_its_readers_on_stand_ins():
     opt = torch.arange(1.0, L.OPT_STATE + 1.0, dtype=torch.float64)
     smooth = torch.tensor([41.0, 42.0, 43.0, 44.0], dtype=torch.float64)
     block3 = torch.tensor([512.0, 1.5, 4.0], dtype=torch.float64)
-    # a stand-in with tests/test_log_block.py's fixed field set: no _value_norm attribute at all
-    old = SimpleNamespace(net=SimpleNamespace(opt_state=opt), _mirror_sums=None, _rnd=None, _smooth={}, storage=SimpleNamespace(_smooth=dict(sums=smooth)))
+    # stand-ins in tests/test_log_block.py's way: the options that are on, made without a device
+    sm, vn = object.__new__(Smoothness), ValueNormalizer(block3, 1e-2)
+    sm.sums = smooth
+    old = SimpleNamespace(net=SimpleNamespace(opt_state=opt), _options=(sm,))
     assert [n for n, _ in PPO._log_parts(old)] == ["opt", "smooth"]
-    on = SimpleNamespace(**vars(old), _value_norm=dict(block=block3))
+    on = SimpleNamespace(net=SimpleNamespace(opt_state=opt), _options=(sm, vn))
     assert [n for n, _ in PPO._log_parts(on)] == ["opt", "smooth", "value_norm"]      # behind smooth
     on._log = LogBlock(PPO._log_parts(on))
     block = on._log.device()
     assert block.numel() == L.OPT_STATE + 4 + 3 and torch.equal(block[-3:], block3)
-    assert PPO.value_norm_from(on, block) == dict(count=512.0, mean=1.5, var=4.0, std=2.0)
+    assert vn.last is None and vn.read_log(on._log.split(block)) == dict(count=512.0, mean=1.5, var=4.0, std=2.0) == vn.last
     old._log = LogBlock(PPO._log_parts(old))
-    assert PPO.value_norm_from(old, old._log.device()) is None
-    scal = SimpleNamespace(denoise_coef=0.0, last_denoise_loss=None, _mirror_coef=0.0, last_mirror_loss=None, last_smoothness=None, _rnd=None)
-    assert PPO.log_scalars(scal) == []      # (no last_value_norm attribute: the same stand-ins)
-    scal.last_value_norm = dict(count=512.0, mean=1.5, var=4.0, std=2.0)
+    assert "value_norm" not in old._log.split(old._log.device())
+    scal = SimpleNamespace(denoise_coef=0.0, last_denoise_loss=None, _scalar_order=())
+    assert PPO.log_scalars(scal) == []      # (the option off)
+    scal._scalar_order = (vn,)
     assert PPO.log_scalars(scal) == [("Policy/value_norm_mean", 1.5), ("Policy/value_norm_std", 2.0)]
 
 

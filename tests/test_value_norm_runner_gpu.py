@@ -67,16 +67,16 @@ def _runner(tmp=None, on=True, eps=None, seed=31, exact=False, save_interval=50,
         setattr(train_cfg.policy, k, v)
     env, _ = task_registry.make_env(name=task, args=args, env_cfg=env_cfg)
     runner, _ = task_registry.make_alg_runner(env=env, name=task, args=args, train_cfg=train_cfg, log_root=None if tmp is None else str(tmp))
-    assert (getattr(runner.alg, "_value_norm", None) is not None) == on and getattr(PPO, "value_normalization", False) is False
+    assert (runner.alg.value_normalizer is not None) == on and getattr(PPO, "value_normalization", False) is False
     return runner
 
 
 def _state(runner):
     torch.cuda.synchronize()
-    net, st = runner.alg.net, runner.alg.storage
+    net, st, vn = runner.alg.net, runner.alg.storage, runner.alg.value_normalizer
     out = [net.params.clone(), net.adam_m.clone(), net.adam_v.clone(), net.opt_state[L.OPT_LR:L.OPT_STEP + 1].clone(), st._obs_all[0].clone()]
-    if getattr(st, "_value_norm", None) is not None:
-        out.append(st._value_norm["block"].clone())
+    if vn is not None:
+        out.append(vn.block.clone())
     return out
 
 
@@ -97,7 +97,7 @@ def test_off_means_absent(monkeypatch, tmp_path):
     _clean(monkeypatch)
     r = _runner(tmp_path / "off", on=False)
     alg, st = r.alg, r.alg.storage
-    assert getattr(alg, "_value_norm", None) is None and getattr(st, "_value_norm", None) is None and getattr(alg, "value_normalizer", None) is None
+    assert alg.value_normalizer is None and alg._options == () and alg.last_value_norm is None
     assert dict(alg.update_graph_key()).get("value_norm") is None
     assert alg.rollout_graph_key() == (id(st), alg.gamma, st._obs_bf16 is not None)
     assert alg.log_block().numel() == alg.net.opt_state.numel() == L.OPT_STATE
@@ -119,21 +119,21 @@ def test_one_iteration_against_the_restatement(monkeypatch):
     _clean(monkeypatch)
     r = _runner(eps=0.05)
     env, alg, st = r.env, r.alg, r.alg.storage
-    vn = st._value_norm
-    assert vn["eps"] == 0.05 and [float(x) for x in vn["block"].cpu()] == list(V.INITIAL) and vn["last_values"].shape == (N, 1)
-    assert alg.value_normalizer.count == 0 and vn["scratch"].numel() == V.scratch_doubles(T * N)
+    vn = alg.value_normalizer
+    assert vn.eps == 0.05 and [float(x) for x in vn.block.cpu()] == list(V.INITIAL) and vn.last_values.shape == (N, 1)
+    assert alg.value_normalizer.count == 0 and vn.scratch.numel() == V.scratch_doubles(T * N)
     before = (300.0, 0.7, 2.3)      # a state that already holds data: the maps are not the identity
-    vn["block"].copy_(torch.tensor(before, dtype=torch.float64))
-    mean_f, scale_f = _host_floats(vn["block"], 0.05)
+    vn.block.copy_(torch.tensor(before, dtype=torch.float64))
+    mean_f, scale_f = _host_floats(vn.block, 0.05)
     seen = []
-    real = st.denormalize_values
+    real = vn.denormalize
 
     def recorded(v, out=None):
         v_in = v.clone()
         res = real(v, out)
         seen.append((v_in.cpu().view(-1), res.clone().cpu().view(-1)))
         return res
-    monkeypatch.setattr(st, "denormalize_values", recorded)
+    monkeypatch.setattr(vn, "denormalize", recorded)
     with torch.inference_mode():
         obs, priv = env.get_observations(), env.get_privileged_observations()
         for s in range(T):
@@ -157,17 +157,17 @@ def test_one_iteration_against_the_restatement(monkeypatch):
         alg.compute_returns(priv)
         torch.cuda.synchronize()
     assert len(seen) == T + 1 and torch.equal(seen[-1][0], v_last) and torch.equal(seen[-1][1].view(torch.int32), V_last.cpu().view(torch.int32))
-    assert torch.equal(vn["last_values"].cpu().view(-1), V_last.cpu())
+    assert torch.equal(vn.last_values.cpu().view(-1), V_last.cpu())
     # the block: the restatement's merge of the raw returns' statistics
     batch = V.batch_stats(raw_returns.numpy())
     want = V.merge(before, batch)
-    got = [float(x) for x in vn["block"].cpu()]
+    got = [float(x) for x in vn.block.cpu()]
     errs = [V.rel(g, w) for g, w in zip(got, want)]
     print("block after compute_returns %r, restatement %r, relative errors %r" % (got, want, errs))
     assert got[0] == want[0] == 300.0 + T * N and max(errs) <= 1e-10
-    assert max(V.rel(float(g), w) for g, w in zip(vn["scratch"][:3].cpu(), batch)) <= 1e-10
+    assert max(V.rel(float(g), w) for g, w in zip(vn.scratch[:3].cpu(), batch)) <= 1e-10
     # returns and values: the fp32 map of the raw columns under the NEW statistics, bitwise; the advantages are untouched by the option
-    m2, s2 = _host_floats(vn["block"], 0.05)
+    m2, s2 = _host_floats(vn.block, 0.05)
     assert float(m2) != float(mean_f)
     for name, raw in (("returns", raw_returns), ("values", raw_values)):
         assert torch.equal(getattr(st, name).cpu().view(torch.int32), ((raw - m2) / s2).view(torch.int32)), name
@@ -207,7 +207,7 @@ def test_captured_equals_eager_on_every_plan(monkeypatch, tmp_path, plan):
         c.learn(num_learning_iterations=3, init_at_random_ep_len=True)
         c.wait_for_saves()
         assert c._graph is None and _same(sa, _state(c)), "the captured stepwise rollout and the eager one differ"
-    block = [float(x) for x in a.alg.storage._value_norm["block"].cpu()]
+    block = [float(x) for x in a.alg.value_normalizer.block.cpu()]
     assert block[0] == 3.0 * T * N and np.isfinite(block[1]) and block[2] > 0.0
     assert all(bool(torch.isfinite(t.double()).all()) for t in sa)
     # the host state a replay must leave, as tests/test_runner_graph_gpu.py compares it
@@ -219,11 +219,11 @@ def test_keys_change_with_the_option(monkeypatch):
     _clean(monkeypatch)
     on, off = _runner().alg, _runner(on=False).alg
     key, key_off = on.update_graph_key(), off.update_graph_key()
-    vn = on.storage._value_norm
-    assert dict(key)["value_norm"] == (1e-2, vn["block"].data_ptr(), vn["scratch"].data_ptr()) and dict(key_off)["value_norm"] is None
+    vn = on.value_normalizer
+    assert dict(key)["value_norm"] == (1e-2, vn.block.data_ptr(), vn.scratch.data_ptr()) and dict(key_off)["value_norm"] is None
     assert [n for n, _ in key] == [n for n, _ in key_off]
     assert on.rollout_graph_key()[:3] == (id(on.storage), on.gamma, True) and len(on.rollout_graph_key()) == 4 and len(off.rollout_graph_key()) == 3
-    vn["eps"] = 0.5
+    vn.eps = 0.5
     assert on.update_graph_key() != key and on.rollout_graph_key()[3][0] == 0.5      # another eps re-captures both graphs
 
 
@@ -247,7 +247,7 @@ def test_both_save_paths_carry_the_entry_and_a_round_trip(monkeypatch, tmp_path)
     a = _runner(tmp_path / "a")
     a.learn(num_learning_iterations=2, init_at_random_ep_len=True)
     a.wait_for_saves()
-    block = a.alg.storage._value_norm["block"].cpu()
+    block = a.alg.value_normalizer.block.cpu()
     entry = dict(count=float(block[0]), mean=float(block[1]), var=float(block[2]), eps=1e-2)
     background = torch.load(os.path.join(a.log_dir, "model_2.pt"), map_location="cpu")
     assert list(background)[-1] == KEY and background[KEY] == entry and entry["count"] == 2.0 * T * N
@@ -259,7 +259,7 @@ def test_both_save_paths_carry_the_entry_and_a_round_trip(monkeypatch, tmp_path)
     b = _runner(tmp_path / "b", seed=32)
     assert b.alg.value_normalizer.count == 0
     b.load(os.path.join(a.log_dir, "model_2.pt"))
-    assert torch.equal(b.alg.storage._value_norm["block"].cpu().view(torch.int64), block.view(torch.int64))
+    assert torch.equal(b.alg.value_normalizer.block.cpu().view(torch.int64), block.view(torch.int64))
     assert b.alg.value_normalizer.state_dict() == entry and torch.equal(b.alg.net.params, a.alg.net.params)
 
 
@@ -301,9 +301,9 @@ def test_everything_else_on(monkeypatch, combined):
     alg = a.alg
     assert alg._obs_norm is not None and alg._adv_mode == COMBINED[combined]["alg"]["advantage_normalization"]
     if combined == "mirror-loss+rnd":
-        assert alg._rnd is not None and alg._mirror_coef == 0.5 and not alg._augment and alg._symmetry is not None
+        assert alg._rnd is not None and alg._mirror_loss.coef == 0.5 and not alg._augment and alg._symmetry is not None
     elif combined == "augmentation+mirror-loss":
-        assert alg._augment and alg._mirror_coef == 0.5 and not alg.use_clipped_value_loss and alg.storage.mirrored
+        assert alg._augment and alg._mirror_loss.coef == 0.5 and not alg.use_clipped_value_loss and alg.storage.mirrored
     else:
         assert alg._rnd is not None and alg._smooth is not None and alg._ppo_cfg.aux_coef > 0.0
     a.learn(num_learning_iterations=2, init_at_random_ep_len=True)

@@ -39,7 +39,7 @@ def _runner(num_envs, augmentation, coef):
     env, _ = task_registry.make_env(name=args.task, args=args, env_cfg=env_cfg)
     runner, _ = task_registry.make_alg_runner(env=env, args=args, train_cfg=train_cfg, log_root=None)
     alg = runner.alg
-    assert alg._augment is augmentation and alg._mirror_coef == coef and alg.storage.mirrored == (augmentation or coef > 0.0)
+    assert alg._augment is augmentation and (alg._mirror_loss.coef if alg._mirror_loss is not None else 0.0) == coef and alg.storage.mirrored == (augmentation or coef > 0.0)
     return runner
 
 

@@ -115,5 +115,5 @@ if __name__ == "__main__":
     torch.cuda.synchronize()
     res = dict(num_envs=n, loops=loops_cost(runners, n, iters, legs))
     res["calls"] = calls_cost(runners["rnd"], reps)
-    res["rnd_log"] = runners["rnd"].alg.rnd_log_from(runners["rnd"].alg.log_block().cpu())
+    res["rnd_log"] = runners["rnd"].alg._rnd.read_log(runners["rnd"].alg._log.split(runners["rnd"].alg.log_block().cpu()))
     print(json.dumps(res, indent=1), flush=True)

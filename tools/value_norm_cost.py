@@ -35,7 +35,7 @@ def _runner(num_envs, on):
         train_cfg.algorithm.value_normalization = True
     env, _ = task_registry.make_env(name=args.task, args=args, env_cfg=env_cfg)
     runner, _ = task_registry.make_alg_runner(env=env, args=args, train_cfg=train_cfg, log_root=None)
-    assert (runner.alg._value_norm is not None) == on
+    assert (runner.alg.value_normalizer is not None) == on
     return runner
 
 
@@ -68,7 +68,7 @@ def runs_cost(num_envs, iters, legs):
     out["fuse"] = {name: _plan_loop(r.env, r.alg, r.device, False).fuse for name, r in runners.items()}
     out["fuse"]["off-deferred"] = "deferred (HGYM_ROLLOUT_CRITIC)"
     st = runners["on"].alg.storage
-    out["shape"] = dict(values=int(st.returns.numel()), block=[float(x) for x in st._value_norm["block"].cpu()])
+    out["shape"] = dict(values=int(st.returns.numel()), block=[float(x) for x in runners["on"].alg.value_normalizer.block.cpu()])
     return out
 
 
