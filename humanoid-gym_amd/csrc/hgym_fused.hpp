@@ -1231,6 +1231,22 @@ constexpr int LP_SMOOTH_T = LP_MIRROR, LP_SMOOTH_S = LP_MIRROR + 1;      // sum 
 static_assert(LP_SMOOTH_S < LOSS_PARTIALS, "the partial row has 32 floats");
 constexpr int FB_SMOOTH_LDS = 2 * 64 * 12 * 4 + 64 * 4;      // tnext 64 x 12, tnear 64 x 12, weight 64
 
+// Both at once (hgym_ppo_grad_smooth_mirror): the argument of the FbMirrorSmooth head's kernels only
+// (hgym_update_mirror_smooth.hip, hgym_update_act_mirror_smooth.hip).  It holds the two heads' records as they are, so that every line of
+// the tile that reads one of them is the line the single head runs: d mu = ((d mu_ppo + g (mu - M_a tm)) + gT w (mu - tT)) + gS (mu - tS).
+// The partial row has two free slots for the actor and the combination has three sums: the mirror loss's squared error stays in LP_MIRROR
+// (ppo_scalars_block turns it into HgymBatch.mirror_sums), the two smoothness errors of tile t go to head_partials[4 t], [4 t + 1].
+struct FbMirrorSmooth {
+    FbMirror m;                // (m.stage and s.stage repeat `stage`)
+    FbSmooth s;
+    float* head_partials;      // [tiles][4] fp32, caller-owned: sum w |mu - tnext|^2, sum |mu - tnear|^2, two floats never written
+    int stage;                 // 1: the launch has FB_MIRROR_LDS + FB_SMOOTH_LDS more bytes of dynamic LDS behind fb_lds_bytes(net): the mirror
+                               // head's block first, the smooth head's behind it
+};
+// where an MS tile's head waves leave the two smoothness sums in `red` for the cross-wave sum: slots of the row that an actor tile's waves
+// never write (LP_AUX is the auxiliary tile's, the last float is pad); they leave LDS for head_partials, not for the partial row
+constexpr int MS_RED_T = LP_AUX, MS_RED_S = LP_MIRROR + 1;
+
 // Behaviour cloning (hgym_bc_grad): the argument of the FbBC head's kernels only (hgym_update_bc.hip, hgym_update_act_bc.hip).  The head
 // regresses mu on target[row] -- a storage column gathered through FwdArgs::idx like every other loss input -- and nothing else: no
 // surrogate, no entropy, no KL, no d std.  The tile's 64 target rows are staged in the actor's loss-input region of LDS (fb_lds_lin:
@@ -1271,18 +1287,24 @@ inline int fb_lds_bytes(const int32_t* dims) {
 }
 
 // The head of an update tile is a type.  FbPlain: the PPO head alone (actor: surrogate, entropy, KL; critic: value loss; AUX: the
-// auxiliary head's MSE).  FbMirror / FbSmooth: the actor's PPO head with that term joined to d mu.  FbBC: the actor's regression head.
+// auxiliary head's MSE).  FbMirror / FbSmooth: the actor's PPO head with that term joined to d mu.  FbMirrorSmooth: with both.  FbBC: the
+// actor's regression head.
 struct FbPlain {};
-template <class T, class Head>      // H where the tile's head is a T, else null
-__device__ __forceinline__ const T* head_as(const Head* H) { if constexpr (__is_same(T, Head)) return H; else return nullptr; }
+template <class T, class Head>      // H where the tile's head is a T (or, for FbMirrorSmooth, its record of that type), else null
+__device__ __forceinline__ const T* head_as(const Head* H) {
+    if constexpr (__is_same(T, Head)) return H;
+    else if constexpr (__is_same(Head, FbMirrorSmooth) && __is_same(T, FbMirror)) return &H->m;
+    else if constexpr (__is_same(Head, FbMirrorSmooth) && __is_same(T, FbSmooth)) return &H->s;
+    else return nullptr;
+}
 // The slots of the partial row (LP_*) that a tile writes: each net's tiles their own, so that the launches of a minibatch do not meet.
 template <class Head, bool AUX>
 __device__ __forceinline__ constexpr bool fb_partial_mine(bool is_actor, int tid) {
-    constexpr bool ML = __is_same(Head, FbMirror), BC = __is_same(Head, FbBC), SM = __is_same(Head, FbSmooth);
+    constexpr bool ML = __is_same(Head, FbMirror), BC = __is_same(Head, FbBC), SM = __is_same(Head, FbSmooth), MS = __is_same(Head, FbMirrorSmooth);
     return BC    ? ((tid >= LP_DBIAS_MU && tid < LP_DBIAS_V) || tid == LP_MIRROR)      // d mu's sums and the regression slot
            : AUX ? tid == LP_AUX
                  : (is_actor ? ((tid != LP_VALUE && tid < LP_DBIAS_V) ||               // all of the PPO head's but the critic's two
-                                (ML && tid == LP_MIRROR) ||
+                                ((ML || MS) && tid == LP_MIRROR) ||
                                 (SM && (tid == LP_SMOOTH_T || tid == LP_SMOOTH_S)))
                              : (tid == LP_VALUE || tid == LP_DBIAS_V));
 }
@@ -1293,6 +1315,8 @@ __device__ __forceinline__ constexpr bool fb_partial_mine(bool is_actor, int tid
 template <int G1, bool AUX = false, bool XB16 = false, bool VU = false, bool GA = false, class Head = FbPlain>
 __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const FusedNet& n, bool is_actor, char* smem, const Head* H = nullptr) {
     constexpr bool ML = __is_same(Head, FbMirror), BC = __is_same(Head, FbBC), SM = __is_same(Head, FbSmooth);
+    constexpr bool MS = __is_same(Head, FbMirrorSmooth);      // both heads: every ML line and every SM line, the SM block of LDS behind the ML one
+    constexpr int SM_LDS0 = MS ? FB_MIRROR_LDS / 4 : 0;       // floats ahead of the smooth head's staged block
     static_assert(__is_same(Head, FbPlain) || (!AUX && !VU), "a head other than the plain one is the actor's alone");
     const FbMirror* Mr = head_as<FbMirror>(H); const FbBC* Bc = head_as<FbBC>(H); const FbSmooth* Sm = head_as<FbSmooth>(H);
     constexpr int BM = 64, NW = 16, D = 2, MB = BM / 16;
@@ -1352,7 +1376,7 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
         if (!pre) return;
         const int j = tid - 8 * 64;                 // 0 .. 511 (wavefronts 8 .. 15)
         if (j < 0) return;
-        if constexpr (ML) {
+        if constexpr (ML || MS) {
             // the tile's target rows (contiguous rows of the minibatch: no index to wait for) and M_a's table -> LDS, beside the other
             // loss inputs: the head reads them there, one LDS access behind another instead of two dependent trips to memory
             if (Mr->stage) {
@@ -1369,7 +1393,7 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
                 if (j >= 208 && j < 224) mt[64 * 12 + 16 + tj] = gv;
             }
         }
-        if constexpr (SM) {
+        if constexpr (SM || MS) {
             // the tile's two target blocks and its weights (contiguous rows of the minibatch) -> LDS behind the other loss inputs: lanes
             // 0 .. 191 the temporal targets, 192 .. 383 the spatial ones, 384 .. 447 the weights.  A term that is off is neither read nor
             // staged (its pointers may be null): the load goes to the other term's block instead, the store is skipped.  Invariant: at
@@ -1377,7 +1401,7 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
             // Rows of 12 floats: l2idle runs under `pre` only, which for the actor means A == 12 (FB_SMOOTH_LDS is sized for that).
             // (Lanes 384 .. 511 also issue the 16-byte load, of row 63, and drop it: unconditional loads, conditional stores, as above.)
             if (Sm->stage) {
-                float* st = lin + FB_LIN_ACTOR * 64;
+                float* st = lin + FB_LIN_ACTOR * 64 + SM_LDS0;
                 const bool onT = Sm->gT > 0.0f, onS = Sm->gS > 0.0f;
                 const bool second = j >= 192;
                 const int jj = second ? j - 192 : j;
@@ -1421,7 +1445,8 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
         const int rl = hw * 16 + r;                 // row of the tile
         const int64_t row = rowidx[rl];
         float g[4] = {0.f, 0.f, 0.f, 0.f};
-        constexpr int NPART = ML ? 12 : (SM ? 13 : 11);         // ML: [11] the mirror loss's squared error; SM: [11], [12] the two terms'
+        constexpr int NPART = MS ? 14 : (ML ? 12 : (SM ? 13 : 11));      // ML: [11] the mirror loss's squared error; SM: [11], [12] the two terms'; MS: [11], then [12], [13]
+        constexpr int PT = MS ? 12 : 11;                        // the temporal term's sum, the spatial term's behind it
         float part[NPART];
 #pragma unroll
         for (int k = 0; k < NPART; ++k) part[k] = 0.0f;
@@ -1459,7 +1484,14 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
                     sg[e] = s;
                     lp += -(d * d) / (2.0f * s * s) - logf(s) - 0.9189385332046727f;
                     ent += 0.5f + 0.9189385332046727f + logf(s);
-                    kl += logf(s / so[e] + 1.e-5f) + (so[e] * so[e] + (mo[e] - mm) * (mo[e] - mm)) / (2.0f * (s * s)) - 0.5f;
+                    if constexpr (MS) {
+                        // The one sum of two products in the head: which of them the compiler fuses into the add is its choice per
+                        // instantiation.  Every other tile forms fma(so, so, (mo - mm)^2); left to itself this one fuses the other
+                        // product, and the KL partial -- which must keep hgym_ppo_grad's bits -- moves in its last place.  So it is spelt out.
+                        kl += logf(s / so[e] + 1.e-5f) + __builtin_fmaf(so[e], so[e], (mo[e] - mm) * (mo[e] - mm)) / (2.0f * (s * s)) - 0.5f;
+                    } else {
+                        kl += logf(s / so[e] + 1.e-5f) + (so[e] * so[e] + (mo[e] - mm) * (mo[e] - mm)) / (2.0f * (s * s)) - 0.5f;
+                    }
                 }
             }
             lp += __shfl_xor(lp, 16, 64);  lp += __shfl_xor(lp, 32, 64);
@@ -1482,7 +1514,7 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
                         part[7 + e] = g[e];
                     }
             }
-            if constexpr (ML) {
+            if constexpr (ML || MS) {
                 // the mirror loss: g (mu - t) joins d mu (and the head-bias sum), (mu - t)^2 the tile's partial sum; nothing else moves
                 const bool staged = pre && Mr->stage;
                 const float* mt = lin + FB_LIN_ACTOR * 64;
@@ -1509,11 +1541,11 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
                 se += __shfl_xor(se, 16, 64); se += __shfl_xor(se, 32, 64);
                 if (q == 0) part[11] = se;
             }
-            if constexpr (SM) {
+            if constexpr (SM || MS) {
                 // the smoothness terms: gT w (mu - tnext) + gS (mu - tnear) joins d mu (and the head-bias sum), the two squared errors the
                 // tile's partial sums; nothing else moves.  A term that is off reads nothing.
                 const bool staged = pre && Sm->stage;
-                const float* st = lin + FB_LIN_ACTOR * 64;
+                const float* st = lin + FB_LIN_ACTOR * 64 + SM_LDS0;
                 const int mrow = valid ? m : a.M - 1;
                 const bool onT = Sm->gT > 0.0f, onS = Sm->gS > 0.0f;
                 const float wgt = onT ? (staged ? st[2 * 64 * 12 + rl] : Sm->weight[mrow]) : 0.0f;
@@ -1541,7 +1573,7 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
                     }
                 seT += __shfl_xor(seT, 16, 64); seT += __shfl_xor(seT, 32, 64);
                 seS += __shfl_xor(seS, 16, 64); seS += __shfl_xor(seS, 32, 64);
-                if (q == 0) { part[11] = seT; part[12] = seS; }
+                if (q == 0) { part[PT] = seT; part[PT + 1] = seS; }
             }
         } else {
             const float ret = pre ? lin[rl * 2] : L.returns[row], vold = pre ? lin[rl * 2 + 1] : L.values[row];
@@ -1585,8 +1617,9 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
             float* w = red + hw * LOSS_PARTIALS;
             if (is_actor) {
                 if (q == 0) { w[LP_SURROGATE] = part[0]; w[LP_ENTROPY] = part[1]; w[LP_KL] = part[2]; }
-                if constexpr (ML) { if (q == 0) w[LP_MIRROR] = part[11]; }
+                if constexpr (ML || MS) { if (q == 0) w[LP_MIRROR] = part[11]; }
                 if constexpr (SM) { if (q == 0) { w[LP_SMOOTH_T] = part[11]; w[LP_SMOOTH_S] = part[12]; } }
+                if constexpr (MS) { if (q == 0) { w[MS_RED_T] = part[PT]; w[MS_RED_S] = part[PT + 1]; } }
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
                     if (4 * q + e < 12) { w[LP_DSTD + 4 * q + e] = part[3 + e]; w[LP_DBIAS_MU + 4 * q + e] = part[7 + e]; }
@@ -1677,6 +1710,10 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
     if (tid < LOSS_PARTIALS) {
         const bool mine = fb_partial_mine<Head, AUX>(is_actor, tid);
         if (mine) L.partials[(int64_t)blockIdx.x * LOSS_PARTIALS + tid] = red[tid] + red[LOSS_PARTIALS + tid] + red[2 * LOSS_PARTIALS + tid] + red[3 * LOSS_PARTIALS + tid];
+        if constexpr (MS) {      // the tile's two smoothness sums, added across the head waves as the partial row's slots are
+            if (tid == MS_RED_T || tid == MS_RED_S)
+                H->head_partials[(int64_t)blockIdx.x * 4 + (tid == MS_RED_S ? 1 : 0)] = red[tid] + red[LOSS_PARTIALS + tid] + red[2 * LOSS_PARTIALS + tid] + red[3 * LOSS_PARTIALS + tid];
+        }
     }
     // ---- dZ chain on the resident tile
     const int N0 = n.layer[0].N, N1 = n.layer[1].N, N2 = n.layer[2].N;
@@ -1763,8 +1800,8 @@ int32_t launch_mlp_fb_act_form(const FwdArgs& fb0, const FbLoss& fl, bool shadow
     return HGYM_OK;
 }
 
-// The ACTOR's update tile with a head of its own (FbMirror: HgymPPOConfig.mirror_coef > 0, FbSmooth: hgym_ppo_grad_smooth, FbBC:
-// hgym_bc_grad): one kernel per head, first hidden width, input form and activation form (GA), the actor alone.  Beside the mirror and
+// The ACTOR's update tile with a head of its own (FbMirror: HgymPPOConfig.mirror_coef > 0, FbSmooth: hgym_ppo_grad_smooth, FbMirrorSmooth:
+// hgym_ppo_grad_smooth_mirror, FbBC: hgym_bc_grad): one kernel per head, first hidden width, input form and activation form (GA), the actor alone.  Beside the mirror and
 // the smooth tiles the critic's and the auxiliary head's tiles run through the kernels they always had (mlp_fb_kernel from net 1 on,
 // launch_mlp_fb_act_form with first = 1), so those nets' bits cannot move; a cloning step has no other net.  The head is THIS kernel's
 // third argument, so that FbLoss -- an argument of every other update kernel -- keeps its layout.
@@ -1791,16 +1828,19 @@ auto fb_head_kernel() {
 // (`stage`), and its name in an error message.
 inline int fb_head_lds(const FbMirror&) { return FB_MIRROR_LDS; }
 inline int fb_head_lds(const FbSmooth&) { return FB_SMOOTH_LDS; }
+inline int fb_head_lds(const FbMirrorSmooth&) { return FB_MIRROR_LDS + FB_SMOOTH_LDS; }
 inline int fb_head_lds(const FbBC&) { return 0; }      // its targets lie in the loss-input region the sum already holds
 inline void fb_head_stage(FbMirror& h, int on) { h.stage = on; }
 inline void fb_head_stage(FbSmooth& h, int on) { h.stage = on; }
+inline void fb_head_stage(FbMirrorSmooth& h, int on) { h.stage = h.m.stage = h.s.stage = on; }
 inline void fb_head_stage(FbBC&, int) {}
 inline const char* fb_head_name(const FbMirror&) { return "mlp_fb_head_kernel<mirror>"; }
 inline const char* fb_head_name(const FbSmooth&) { return "mlp_fb_head_kernel<smooth>"; }
+inline const char* fb_head_name(const FbMirrorSmooth&) { return "mlp_fb_head_kernel<mirror_smooth>"; }
 inline const char* fb_head_name(const FbBC&) { return "mlp_fb_bc_kernel"; }
 
 // One launch of the actor's tiles with `head0`.  Each (GA, Head) is explicitly instantiated in a translation unit, i.e. a device code
-// object, of its own (hgym_update_{mirror,smooth,bc}.hip: ELU(1), hgym_update_act_{mirror,smooth,bc}.hip: any resolved activation) and
+// object, of its own (hgym_update_{mirror,smooth,mirror_smooth,bc}.hip: ELU(1), hgym_update_act_{..}.hip: any resolved activation) and
 // declared `extern` below: no other translation unit carries these kernels.
 template <bool GA, class Head>
 int32_t launch_mlp_fb_head(const FwdArgs& fb0, const FbLoss& fl, const Head& head0, bool shadow, int tiles, hipStream_t s) {
@@ -1830,6 +1870,8 @@ extern template int32_t launch_mlp_fb_head<false, FbMirror>(const FwdArgs&, cons
 extern template int32_t launch_mlp_fb_head<true, FbMirror>(const FwdArgs&, const FbLoss&, const FbMirror&, bool, int, hipStream_t);
 extern template int32_t launch_mlp_fb_head<false, FbSmooth>(const FwdArgs&, const FbLoss&, const FbSmooth&, bool, int, hipStream_t);
 extern template int32_t launch_mlp_fb_head<true, FbSmooth>(const FwdArgs&, const FbLoss&, const FbSmooth&, bool, int, hipStream_t);
+extern template int32_t launch_mlp_fb_head<false, FbMirrorSmooth>(const FwdArgs&, const FbLoss&, const FbMirrorSmooth&, bool, int, hipStream_t);
+extern template int32_t launch_mlp_fb_head<true, FbMirrorSmooth>(const FwdArgs&, const FbLoss&, const FbMirrorSmooth&, bool, int, hipStream_t);
 extern template int32_t launch_mlp_fb_head<false, FbBC>(const FwdArgs&, const FbLoss&, const FbBC&, bool, int, hipStream_t);
 extern template int32_t launch_mlp_fb_head<true, FbBC>(const FwdArgs&, const FbLoss&, const FbBC&, bool, int, hipStream_t);
 

@@ -38,6 +38,10 @@ int32_t launch_ppo_loss_smooth(const LossArgs& a, const LossSmooth& sm, bool bf1
 int32_t launch_perturb_rows(int64_t M, int width, const float* src, int64_t ld_src, const int64_t* idx, const float* noise_std, uint64_t seed,
                             const double* opt_state, float* dst, int64_t ld_dst, hipStream_t s);
 int32_t launch_smooth_sums(int nblocks, int B, int A, const float* partials, const float* weight, double* sums, hipStream_t s);
+// hgym_loss_mirror_smooth.hip: hgym_ppo_grad_smooth_mirror's small kernels -- the layer-by-layer head with the mirror loss and the smoothness
+// regulariser at once, and the sums of the two smoothness terms from head_partials
+int32_t launch_ppo_loss_mirror_smooth(const LossArgs& a, const LossSmooth& sm, float* head_partials, bool bf16, int nblocks, hipStream_t s);
+int32_t launch_head_sums(int nblocks, int B, int A, const float* head_partials, const float* weight, double* sums, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------ layouts
 struct LayerLayout {
@@ -1044,7 +1048,8 @@ struct GemmPath : NetBase {
     // part 1 (the second half of hgym_ppo_grad_part) has nothing left to do: part 0 does everything (the caller's first bucket goes out
     // complete, just later)
     // sm (hgym_ppo_grad_smooth): the smoothness regulariser joins d mu; null or both coefficients 0: off, the launches of hgym_ppo_grad
-    int32_t grad(const HgymPPOConfig& ppo, const HgymBatch& b, int part, const HgymSmooth* sm = nullptr) {
+    // hp (hgym_ppo_grad_smooth_mirror): head_partials, named only when the mirror loss and the regulariser are both on
+    int32_t grad(const HgymPPOConfig& ppo, const HgymBatch& b, int part, const HgymSmooth* sm = nullptr, float* hp = nullptr) {
         if (part == 1) return HGYM_OK;
         const int B = b.B, A = cfg.num_actions;
         float* mu = at<float>(w.net[0].out_f32);
@@ -1068,6 +1073,8 @@ struct GemmPath : NetBase {
         const int Bp = (int)round_up(B, w.SE);
         const int nblocks = ceil_div(Bp, 256);
         HG_REQUIRE(nblocks <= MAX_LOSS_BLOCKS, HGYM_E_UNSUPPORTED, "minibatch %d too large for the loss partial buffer", B);
+        // (head_partials holds 4 floats per 64 rows, a loss block covers 256 of the padded rows)
+        HG_REQUIRE(!hp || nblocks <= (B + 63) / 64, HGYM_E_UNSUPPORTED, "%d loss blocks for B=%d: more than head_partials holds", nblocks, B);
         const LayerLayout& la = w.net[0].layer[w.net[0].L - 1];
         const LayerLayout& lc = w.net[1].layer[w.net[1].L - 1];
         LossArgs a;
@@ -1098,11 +1105,21 @@ struct GemmPath : NetBase {
         prof_begin(HGYM_PROF_LOSS, s);
         if (ppo.value_loss_unclipped) hipLaunchKernelGGL((ppo_loss_kernel<T, true>), dim3(nblocks), dim3(256), 0, s, a);
         else hipLaunchKernelGGL((ppo_loss_kernel<T>), dim3(nblocks), dim3(256), 0, s, a);
-        if (mirror) {      // behind it: d mu with the term, the LP_DBIAS_MU / LP_MIRROR partials (hgym_loss.hpp)
+        if (mirror && smooth) {      // behind it: d mu with all three terms, the LP_DBIAS_MU / LP_MIRROR partials, head_partials, then the sums
+            const float gs = 2.0f / ((float)B * (float)A);
+            const LossSmooth ls = {sm->target_next, sm->target_near, sm->next_weight, gs * sm->temporal_coef, gs * sm->spatial_coef};
+            if (sizeof(T) == 4) {      // fp32: the first two terms of d mu and LP_MIRROR are the mirror kernel's own, to the bit (hgym_loss_mirror_smooth.hip)
+                const int32_t rc_ml = launch_ppo_loss_mirror(a, false, ppo.value_loss_unclipped != 0, nblocks, s);
+                if (rc_ml) return rc_ml;
+            }
+            int32_t rc_ms = launch_ppo_loss_mirror_smooth(a, ls, hp, sizeof(T) == 2, nblocks, s);
+            if (rc_ms) return rc_ms;
+            rc_ms = launch_head_sums(nblocks, B, A, hp, sm->next_weight, sm->sums, s);
+            if (rc_ms) return rc_ms;
+        } else if (mirror) {      // behind it: d mu with the term, the LP_DBIAS_MU / LP_MIRROR partials (hgym_loss.hpp)
             const int32_t rc_ml = launch_ppo_loss_mirror(a, sizeof(T) == 2, ppo.value_loss_unclipped != 0, nblocks, s);
             if (rc_ml) return rc_ml;
-        }
-        if (smooth) {      // behind it: d mu with the two terms, the LP_DBIAS_MU / LP_SMOOTH_* partials (hgym_loss.hpp), then the sums
+        } else if (smooth) {      // behind it: d mu with the two terms, the LP_DBIAS_MU / LP_SMOOTH_* partials (hgym_loss.hpp), then the sums
             const float gs = 2.0f / ((float)B * (float)A);
             const LossSmooth ls = {sm->target_next, sm->target_near, sm->next_weight, gs * sm->temporal_coef, gs * sm->spatial_coef};
             int32_t rc_sm = launch_ppo_loss_smooth(a, ls, sizeof(T) == 2, nblocks, s);
@@ -1461,7 +1478,8 @@ struct FusedPath : NetBase {
     // part < 0: the whole minibatch gradient.  part 0 / 1: the two halves of hgym_ppo_grad_part -- 0 leaves std's and the actor's
     // gradient final, 1 the critic's, the auxiliary head's and the KL slot.
     // sm (hgym_ppo_grad_smooth): the smoothness regulariser joins d mu; null or both coefficients 0: off, the launches of hgym_ppo_grad
-    int32_t grad(const HgymPPOConfig& ppo, const HgymBatch& b, int part, const HgymSmooth* sm = nullptr) {
+    // hp (hgym_ppo_grad_smooth_mirror): head_partials, named only when the mirror loss and the regulariser are both on
+    int32_t grad(const HgymPPOConfig& ppo, const HgymBatch& b, int part, const HgymSmooth* sm = nullptr, float* hp = nullptr) {
         const int B = b.B, A = cfg.num_actions;
         const int64_t critic_off = w.net[1].layer[0].w_off;
         const int Mp = (int)round_up(B, w.SE);
@@ -1474,16 +1492,16 @@ struct FusedPath : NetBase {
         const int32_t rc_plan = plan_tiles(b, nets, &u);
         if (rc_plan) return rc_plan;
         const bool mirror = ppo.mirror_coef > 0.0f;
+        const bool smooth = smooth_on(sm);
+        if (smooth) {      // (ahead of the mirror loss's pre-pass: hgym_ppo_grad_smooth_mirror's order; alone, either is the only one)
+            const int32_t rc_pre = smooth_prepass(*this, b, *sm);
+            if (rc_pre) return rc_pre;
+        }
         if (mirror) {
             // the mirror loss's pre-pass: the raw mu of the partner rows under the current parameters, forward only (no gradient through
             // the target).  It gathers the fp32 rows, not their bf16 shadow: the forward tiles that gather by index from a shadow exist in
             // the update kernels only, and the shadow is bf16(fp32 row) exactly -- the same bits reach the first layer either way.
             const int32_t rc_pre = forward(0, B, b.obs, cfg.num_obs, b.pair_idx, b.mirror_target, A, false);
-            if (rc_pre) return rc_pre;
-        }
-        const bool smooth = smooth_on(sm);
-        if (smooth) {
-            const int32_t rc_pre = smooth_prepass(*this, b, *sm);
             if (rc_pre) return rc_pre;
         }
         {   // forward + PPO loss + dZ chain of both nets: ONE launch (hgym_fused.hpp: mlp_fb_kernel)
@@ -1511,7 +1529,16 @@ struct FusedPath : NetBase {
             prof_begin(HGYM_PROF_MLP_FWD, s);
             int32_t rc_fb = HGYM_OK;
             int first = 0;      // the first net of the launches every net always had
-            if (mirror) {
+            if (mirror && smooth) {
+                // the actor's tiles through the kernels with both terms in their head, the sums of the two smoothness terms from head_partials
+                const float gs = 2.0f / ((float)B * (float)A);
+                const FbMirrorSmooth head = {{b.mirror_target, b.mirror_act_src, b.mirror_act_sign, 2.0f * ppo.mirror_coef / ((float)B * (float)A), 0},
+                                             {sm->target_next, sm->target_near, sm->next_weight, gs * sm->temporal_coef, gs * sm->spatial_coef, 0}, hp, 0};
+                rc_fb = launch_actor_head(u, head);
+                if (rc_fb) return rc_fb;
+                rc_fb = launch_head_sums(u.tiles, B, A, hp, sm->next_weight, sm->sums, s);
+                first = 1;
+            } else if (mirror) {
                 // the actor's tiles through the kernels with the mirror loss in their head (their own launch), the rest from net 1 on
                 const FbMirror head = {b.mirror_target, b.mirror_act_src, b.mirror_act_sign, 2.0f * ppo.mirror_coef / ((float)B * (float)A), 0};
                 rc_fb = launch_actor_head(u, head);
@@ -1848,17 +1875,18 @@ int32_t hgym_policy_act_fin(const HgymNetConfig* cfg, const HgymNet* net, int32_
     });
 }
 
-// Behind hgym_ppo_grad, hgym_ppo_grad_part and hgym_ppo_grad_smooth: the checks they share, in one order, then the runner's grad.
-// part: null for the whole gradient, else hgym_ppo_grad_part's half; smooth: null unless hgym_ppo_grad_smooth.
+// Behind hgym_ppo_grad, hgym_ppo_grad_part, hgym_ppo_grad_smooth and hgym_ppo_grad_smooth_mirror: the checks they share, in one order, then
+// the runner's grad.  part: null for the whole gradient, else hgym_ppo_grad_part's half; smooth: null unless hgym_ppo_grad_smooth(_mirror);
+// head_partials: null unless hgym_ppo_grad_smooth_mirror with all of its terms on.
 static int32_t ppo_grad_entry(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const HgymNet* net, const HgymBatch* batch,
-                              const int32_t* part, const HgymSmooth* smooth, void* stream) {
+                              const int32_t* part, const HgymSmooth* smooth, void* stream, float* head_partials = nullptr) {
     return run(cfg, net, stream, [&](auto& R) -> int32_t {
         int32_t rc = check_ppo(ppo);
         if (rc) return rc;
         HG_REQUIRE(!part || *part == 0 || *part == 1, HGYM_E_BADARG, "part=%d (0 or 1)", *part);
         HG_REQUIRE(net->grads && net->opt_state, HGYM_E_BADARG, "null grads / opt_state");
         rc = check_batch(R.w, ppo, batch);
-        return rc ? rc : R.grad(*ppo, *batch, part ? *part : -1, smooth);
+        return rc ? rc : R.grad(*ppo, *batch, part ? *part : -1, smooth, head_partials);
     });
 }
 
@@ -1866,16 +1894,15 @@ int32_t hgym_ppo_grad(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const 
     return ppo_grad_entry(cfg, ppo, net, batch, nullptr, nullptr, stream);
 }
 
-int32_t hgym_ppo_grad_smooth(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const HgymNet* net, const HgymBatch* batch,
-                             const HgymSmooth* smooth, void* stream) {
-    // every refusal below comes before anything is launched
-    HG_REQUIRE(cfg && ppo && net && batch && smooth, HGYM_E_BADARG, "hgym_ppo_grad_smooth: null cfg / ppo / net / batch / smooth");
+// What hgym_ppo_grad_smooth and hgym_ppo_grad_smooth_mirror refuse of an HgymSmooth, the same for both (fn: the caller's name)
+// alone: hgym_ppo_grad_smooth, which also refuses the mirror loss (at the place in the order it always had)
+static int32_t check_smooth(const HgymPPOConfig* ppo, const HgymSmooth* smooth, const char* fn, bool alone) {
     const float lt = smooth->temporal_coef, ls = smooth->spatial_coef;
     // (written so that a NaN fails it)
     HG_REQUIRE(lt >= 0.0f && lt < INFINITY && ls >= 0.0f && ls < INFINITY, HGYM_E_BADARG,
                "HgymSmooth.temporal_coef=%g / spatial_coef=%g must be finite and >= 0 (0: that term is off)", (double)lt, (double)ls);
-    HG_REQUIRE(!(ppo->mirror_coef > 0.0f), HGYM_E_BADARG, "hgym_ppo_grad_smooth with HgymPPOConfig.mirror_coef > 0: the two heads do not combine");
-    HG_REQUIRE(ppo->world_size <= 1, HGYM_E_BADARG, "hgym_ppo_grad_smooth with world_size=%d: one rank only", ppo->world_size);
+    HG_REQUIRE(!alone || !(ppo->mirror_coef > 0.0f), HGYM_E_BADARG, "hgym_ppo_grad_smooth with HgymPPOConfig.mirror_coef > 0: the two heads do not combine");
+    HG_REQUIRE(ppo->world_size <= 1, HGYM_E_BADARG, "%s with world_size=%d: one rank only", fn, ppo->world_size);
     if (lt > 0.0f || ls > 0.0f) {
         HG_REQUIRE(smooth->sums && ((uintptr_t)smooth->sums & 7) == 0, HGYM_E_BADARG, "HgymSmooth.sums must be non-null and 8-byte aligned");
         if (lt > 0.0f) {
@@ -1891,7 +1918,34 @@ int32_t hgym_ppo_grad_smooth(const HgymNetConfig* cfg, const HgymPPOConfig* ppo,
                        "HgymSmooth.target_near and rows must be 16-byte aligned (noise_std 4)");
         }
     }
+    return HGYM_OK;
+}
+
+int32_t hgym_ppo_grad_smooth(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const HgymNet* net, const HgymBatch* batch,
+                             const HgymSmooth* smooth, void* stream) {
+    // every refusal below comes before anything is launched
+    HG_REQUIRE(cfg && ppo && net && batch && smooth, HGYM_E_BADARG, "hgym_ppo_grad_smooth: null cfg / ppo / net / batch / smooth");
+    const int32_t rc = check_smooth(ppo, smooth, "hgym_ppo_grad_smooth", true);
+    if (rc) return rc;
     return ppo_grad_entry(cfg, ppo, net, batch, nullptr, smooth, stream);
+}
+
+int32_t hgym_ppo_grad_smooth_mirror(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const HgymNet* net, const HgymBatch* batch,
+                                    const HgymSmooth* smooth, float* head_partials, int64_t head_partials_len, void* stream) {
+    // every refusal below comes before anything is launched
+    HG_REQUIRE(cfg && ppo && net && batch && smooth, HGYM_E_BADARG, "hgym_ppo_grad_smooth_mirror: null cfg / ppo / net / batch / smooth");
+    const int32_t rc = check_smooth(ppo, smooth, "hgym_ppo_grad_smooth_mirror", false);
+    if (rc) return rc;
+    const bool all = ppo->mirror_coef > 0.0f && smooth_on(smooth);
+    if (all) {      // (else hgym_ppo_grad_smooth or hgym_ppo_grad: head_partials is not looked at)
+        HG_REQUIRE(batch->B >= 1, HGYM_E_BADARG, "hgym_ppo_grad_smooth_mirror: B=%d", batch->B);
+        const int64_t need = 4 * (((int64_t)batch->B + 63) / 64);
+        HG_REQUIRE(head_partials && ((uintptr_t)head_partials & 15) == 0, HGYM_E_BADARG,
+                   "hgym_ppo_grad_smooth_mirror: head_partials must be non-null and 16-byte aligned");
+        HG_REQUIRE(head_partials_len >= need, HGYM_E_BADARG, "hgym_ppo_grad_smooth_mirror: head_partials_len=%lld, B=%d needs %lld floats",
+                   (long long)head_partials_len, batch->B, (long long)need);
+    }
+    return ppo_grad_entry(cfg, ppo, net, batch, nullptr, smooth, stream, all ? head_partials : nullptr);
 }
 
 int32_t hgym_ppo_grad_part(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const HgymNet* net, const HgymBatch* batch, int32_t part,

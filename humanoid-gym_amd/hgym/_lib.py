@@ -278,6 +278,7 @@ SYMBOLS = {
     "hgym_perturb_rows": (C.c_int32, [C.c_int64, C.c_int32, c_float_p, C.c_int64, c_i64_p, c_float_p, C.c_uint64, c_f64_p, c_float_p, C.c_int64,
                                       C.c_void_p]),
     "hgym_ppo_grad_smooth": (C.c_int32, [_P(NetConfig), _P(PPOConfig), _P(Net), _P(Batch), _P(Smooth), C.c_void_p]),
+    "hgym_ppo_grad_smooth_mirror": (C.c_int32, [_P(NetConfig), _P(PPOConfig), _P(Net), _P(Batch), _P(Smooth), c_float_p, C.c_int64, C.c_void_p]),
     "hgym_net_param_offset": (C.c_int64, [_P(NetConfig), C.c_int32]),
     "hgym_ppo_apply": (C.c_int32, [_P(NetConfig), _P(PPOConfig), _P(Net), C.c_void_p]),
     "hgym_prof_enable": (C.c_int32, [C.c_int32]),

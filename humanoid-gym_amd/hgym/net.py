@@ -321,6 +321,15 @@ class NetBuffers:
         L.check(L.lib.hgym_ppo_grad_smooth(C.byref(self.cfg), C.byref(ppo), C.byref(self.struct), C.byref(batch), C.byref(smooth), self.stream()),
                 "hgym_ppo_grad_smooth")
 
+    def ppo_grad_smooth_mirror(self, ppo, batch, smooth, head_partials):
+        """hgym_ppo_grad_smooth_mirror: hgym_ppo_grad with the mirror loss (ppo.mirror_coef, make_batch's mirror fields) and the smoothness
+        regulariser (make_smooth) in one actor head.  head_partials: float32 device scratch of at least smooth_mirror_partials(batch.B)
+        elements, 16-byte aligned, that the caller keeps alive.  mirror_coef 0: hgym_ppo_grad_smooth; both coefficients 0: hgym_ppo_grad."""
+        assert head_partials is None or (head_partials.dtype == torch.float32 and head_partials.is_contiguous())
+        L.check(L.lib.hgym_ppo_grad_smooth_mirror(C.byref(self.cfg), C.byref(ppo), C.byref(self.struct), C.byref(batch), C.byref(smooth),
+                                                  L.fptr(head_partials), 0 if head_partials is None else int(head_partials.numel()),
+                                                  self.stream()), "hgym_ppo_grad_smooth_mirror")
+
     def ppo_grad_part(self, ppo, batch, part):
         """hgym_ppo_grad in two halves (data-parallel update): after part 0 `grads_ext[:bucket_split]` (std | actor, the larger
         bucket) is final, after part 1 `grads_ext[bucket_split:]` (critic | auxiliary head | KL slot)."""
@@ -397,6 +406,11 @@ def make_batch(obs, priv, actions, values, advantages, returns, logp, mu, sigma,
 def smooth_ld(num_obs):
     """Leading dimension (floats) of HgymSmooth.rows: the observation width rounded up to 4, so that every row starts on 16 bytes."""
     return (int(num_obs) + 3) // 4 * 4
+
+
+def smooth_mirror_partials(mb):
+    """Length (floats) of hgym_ppo_grad_smooth_mirror's head_partials for minibatches of mb rows: 4 per tile of 64 rows."""
+    return 4 * ((int(mb) + 63) // 64)
 
 
 def make_smooth(temporal_coef=0.0, spatial_coef=0.0, next_idx=None, next_weight=None, noise_std=None, seed=0, target_next=None,

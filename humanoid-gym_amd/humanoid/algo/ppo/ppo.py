@@ -87,8 +87,8 @@ class PPO:
     # the mirror loss, the other half of rsl_rl's symmetry_cfg (use_mirror_loss / mirror_loss_coeff): mirror_loss_coef * mse(mu(s), M_a mu(M s))
     # added to the PPO loss, the target under the current parameters and detached (HgymPPOConfig.mirror_coef).  Needs `symmetry` (its
     # tables; ValueError otherwise).  symmetry_augmentation = False keeps the mirrored observations (the loss's partner rows) but trains on
-    # the T N original rows only: minibatches of today's size, one more actor forward per minibatch.  With the coefficient 0 it is the
-    # same as symmetry off.  Both read once, in init_storage.  `last_mirror_loss`: the mean MSE per minibatch of the last update.
+    # the T N original rows only: minibatches of today's size, one more actor forward per minibatch; in that form it combines with
+    # PPO.smoothness.  With the coefficient 0 it is the same as symmetry off.  Both read once, in init_storage.  `last_mirror_loss`: the mean MSE per minibatch of the last update.
     mirror_loss_coef = 0.0
     symmetry_augmentation = True
     # how the advantages are standardised: "batch" -- the reference's way, once over the whole T N batch at the end of compute_returns (the
@@ -107,8 +107,10 @@ class PPO:
     # the smoothness regulariser on the policy's mean, after CAPS: None, or a dict {temporal_coef, spatial_coef, noise_std, noise_scale, seed}
     # (humanoid.algo.ppo.smoothness.parse_config) -- update() then calls hgym_ppo_grad_smooth in place of hgym_ppo_grad: lamT pulls mu(s_t)
     # towards mu(s_t+1) over rows whose episode went on, lamS pulls mu(s) towards mu(s + noise_std z), both targets detached.  One rank, no
-    # PPO.symmetry, not with Distillation (ValueError from init_storage).  Read once, in init_storage.  `last_smoothness`: {temporal, spatial,
-    # valid_fraction} of the last update.  DESIGN.md section 28.
+    # symmetry augmentation, not with Distillation (ValueError from init_storage).  Beside the mirror loss without augmentation
+    # (mirror_loss_coef > 0, symmetry_augmentation = False) update() calls hgym_ppo_grad_smooth_mirror, one actor head for all three terms; the
+    # spatial term's noise_std must then be invariant under the observation mirror table (ValueError naming the column).  Read once, in
+    # init_storage.  `last_smoothness`: {temporal, spatial, valid_fraction} of the last update.  DESIGN.md sections 28 and 32.
     smoothness = None
     # value targets standardised by running statistics (rl_games' normalize_value, the return half of SB3's VecNormalize): the critic lives
     # in normalised units.  Per iteration: the critic's outputs are denormalised as they are stored (one launch behind the policy launch,
@@ -197,7 +199,9 @@ class PPO:
         if rnd is not None:
             rnd_module.check_setup(world, symmetry if augment else None, augment)
         if smooth_module.parse_config(smoothness, num_actor_obs) is not None:
-            smooth_module.check_setup(world, symmetry)
+            # (its refusal is of the mirrored half of the storage: the mirror loss without augmentation trains on the original rows only.
+            # Exactly that form is let through -- a MirrorSpec with neither half asked for is refused as it always was)
+            smooth_module.check_setup(world, None if (coef > 0.0 and not augment) else symmetry)
         mb = ((2 if augment else 1) * num_envs * num_transitions_per_env) // num_mini_batches
         if advantage_normalization == "minibatch" and mb < 2:      # (rsl_rl would divide by the NaN deviation of one value)
             raise ValueError("PPO.advantage_normalization='minibatch' needs minibatches of at least 2 rows (they have %d)" % mb)
@@ -266,7 +270,10 @@ class PPO:
             self._mirror_loss = MirrorLoss(coef, mb, ac.num_actions, self.device)
         smooth = smooth_module.parse_config(self.smoothness, ac.num_actor_obs, torch.initial_seed())
         if smooth is not None:      # the successor map of a whole permutation, the two pre-passes' outputs, the perturbed rows, the four sums
-            self._smooth = smooth_module.Smoothness(smooth, self.num_mini_batches * mb, mb, ac.num_actor_obs, ac.num_actions, self.device)
+            if coef > 0.0 and smooth["spatial_coef"] > 0.0:      # a perturbation that told left from right would fight the mirror term
+                smooth_module.check_noise_mirror(smooth["noise_std"], self._symmetry.obs_src)
+            self._smooth = smooth_module.Smoothness(smooth, self.num_mini_batches * mb, mb, ac.num_actor_obs, ac.num_actions, self.device,
+                                                    mirror_loss=coef > 0.0)
         self._sample_step = torch.zeros(1, dtype=torch.int64, device=self.device)
         self._perm_seed = (torch.initial_seed() * 0x9E3779B97F4A7C15 + 0xABCD + 104729 * self._rank) & 0xFFFFFFFFFFFFFFFF
         self._perm_draws = 0
@@ -588,7 +595,9 @@ class PPO:
                 idx = perm[i * mb:(i + 1) * mb]
                 mirror = {} if mirror_loss is None else mirror_loss.minibatch(pair[i * mb:(i + 1) * mb], st)
                 batch = hgym.make_batch(*cols, idx, **mirror, **sh)
-                if smooth is not None:
+                if smooth is not None and mirror_loss is not None:      # one actor head for the three detached-target terms
+                    net.ppo_grad_smooth_mirror(self._ppo_cfg, batch, smooth.minibatch(i), smooth.head_partials)
+                elif smooth is not None:
                     net.ppo_grad_smooth(self._ppo_cfg, batch, smooth.minibatch(i))
                 else:
                     net.ppo_grad(self._ppo_cfg, batch)

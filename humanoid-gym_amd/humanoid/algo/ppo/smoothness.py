@@ -58,8 +58,8 @@ def parse_config(cfg, num_obs, default_seed=0):
 
 def check_setup(world=1, symmetry=None, distillation=False):
     """What init_storage refuses with the regulariser on (ValueError each; DESIGN.md section 28 names each as a follow-up): more than one
-    rank; PPO.symmetry in any form (the mirrored half stores no mirrored bootstrap slot, and the mirror head and this head are separate
-    kernels); Distillation."""
+    rank; a `symmetry` that is not None (the mirrored half stores no mirrored bootstrap slot); Distillation.  PPO.check_setup withholds its
+    MirrorSpec exactly when the mirror loss is on without augmentation: that form combines."""
     if int(world) > 1:
         raise ValueError("PPO.smoothness runs on one rank (world size %d)" % int(world))
     if symmetry is not None:
@@ -70,13 +70,14 @@ def check_setup(world=1, symmetry=None, distillation=False):
 
 class Smoothness:
     """The option as PPO holds it (PPO._smooth; None: off): the parse_config() dict `cfg`, everything hgym_smooth_pairs and
-    hgym_ppo_grad_smooth name, and its part of the log."""
+    hgym_ppo_grad_smooth name, and its part of the log.  `head_partials`: hgym_ppo_grad_smooth_mirror's scratch, None unless the mirror loss
+    is on beside the regulariser."""
     BUFFERS = ("next_idx", "next_weight", "noise_std", "target_next", "target_near", "rows", "sums")
 
-    def __init__(self, cfg, perm_len, mb, num_obs, num_actions, device):
+    def __init__(self, cfg, perm_len, mb, num_obs, num_actions, device, mirror_loss=False):
         """Allocated once (torch.zeros: nothing is allocated during an update) -- next_idx / next_weight for a whole permutation of
         perm_len rows, noise_std (num_obs; zeros when the spatial term is off), and for one minibatch of mb rows target_next, target_near
-        (mb x num_actions) and rows (mb x the width rounded up to 4), then the four sums."""
+        (mb x num_actions) and rows (mb x the width rounded up to 4), then the four sums; mirror_loss: head_partials as well."""
         import hgym
         z = lambda n, dtype=torch.float32: torch.zeros(max(int(n), 1), dtype=dtype, device=device)
         self.cfg, self.mb, self.last = cfg, int(mb), None
@@ -85,6 +86,7 @@ class Smoothness:
             self.noise_std.copy_(torch.tensor(cfg["noise_std"], dtype=torch.float32))
         self.target_next, self.target_near = z(mb * num_actions), z(mb * num_actions)
         self.rows, self.sums = z(mb * hgym.smooth_ld(num_obs)), z(4, torch.float64)
+        self.head_partials = z(hgym.smooth_mirror_partials(mb)) if mirror_loss else None
 
     def begin_update(self, perm, storage):
         """One pass over the whole permutation: every epoch reuses the slices, as the advantage pass's are."""
@@ -101,9 +103,10 @@ class Smoothness:
                                 target_near=self.target_near, rows=self.rows, sums=self.sums)
 
     def graph_key(self):
-        """PPO.update_graph_key's entry: the coefficients and the seed, and the scratch the launches name."""
+        """PPO.update_graph_key's entry: the coefficients and the seed, and the scratch the launches name (head_partials last, when there)."""
         c = self.cfg
-        return dict(smoothness=(c["temporal_coef"], c["spatial_coef"], c["seed"]) + tuple(getattr(self, n).data_ptr() for n in self.BUFFERS))
+        hp = () if self.head_partials is None else (self.head_partials.data_ptr(),)
+        return dict(smoothness=(c["temporal_coef"], c["spatial_coef"], c["seed"]) + tuple(getattr(self, n).data_ptr() for n in self.BUFFERS) + hp)
 
     def log_parts(self):
         return [("smooth", self.sums)]
@@ -130,3 +133,18 @@ def env_noise_std(env_cfg, noise_scale_vec, num_obs):
     if not frame or int(num_obs) % len(frame) != 0:
         return None
     return frame * (int(num_obs) // len(frame))
+
+
+def check_noise_mirror(noise_std, obs_src):
+    """With the mirror loss beside the spatial term the perturbation must treat left and right alike, or it fights the mirror term:
+    noise_std[obs_src[c]] == noise_std[c] for every observation column c (obs_src: the MirrorSpec's observation table, the column each
+    mirrored column is read from).  ValueError naming the first column that breaks it.  The env's own noise_scale_vec passes."""
+    ns = noise_std.tolist() if hasattr(noise_std, "tolist") else list(noise_std)
+    src = obs_src.tolist() if hasattr(obs_src, "tolist") else list(obs_src)
+    if len(ns) != len(src):
+        raise ValueError("PPO.smoothness.noise_std has %d values, the observation mirror table %d" % (len(ns), len(src)))
+    for c, (v, j) in enumerate(zip(ns, src)):
+        if float(ns[int(j)]) != float(v):
+            raise ValueError("PPO.smoothness.noise_std is not invariant under the observation mirror table: column %d has %r, its mirror "
+                             "column %d has %r (PPO.mirror_loss_coef > 0 with spatial_coef > 0 needs a left-right symmetric perturbation)"
+                             % (c, float(v), int(j), float(ns[int(j)])))

@@ -35,7 +35,8 @@ constant weight -- an intrinsic exploration reward added to the stored rewards a
 carry rnd_state_dict.  Unset: off.
 
 HGYM_SMOOTH=<lamT>[,<lamS>] sets `algorithm.smoothness_cfg = {"temporal_coef": lamT, "spatial_coef": lamS}`: the smoothness regulariser on
-the policy's mean (PPO.smoothness), the spatial term's noise the env's own noise_scale_vec * noise_level.  Unset: off.
+the policy's mean (PPO.smoothness), the spatial term's noise the env's own noise_scale_vec * noise_level.  Unset: off.  With HGYM_MIRROR_LOSS=<coef> and no HGYM_SYMMETRY both regularisers train at once, in one
+actor head; with HGYM_SYMMETRY=1 the pair is refused.
 
 HGYM_VALUE_NORM=1 sets `algorithm.value_normalization` the same way: the value targets standardised by running statistics of the returns, the
 critic in normalised units (PPO.value_normalization); checkpoints carry value_norm_state_dict.  Unset: off."""

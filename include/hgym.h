@@ -75,7 +75,9 @@ extern "C" {
                              *    (same version, later: hgym_smooth_pairs, hgym_perturb_rows, hgym_ppo_grad_smooth and HgymSmooth -- the smoothness
                              *    regulariser on the policy's mean; no layout changes)
                              *    (same version, later: hgym_value_denormalize, hgym_value_norm_merge, hgym_value_normalize -- value targets
-                             *    standardised by running statistics; no layout changes) */
+                             *    standardised by running statistics; no layout changes)
+                             *    (same version, later: hgym_ppo_grad_smooth_mirror -- the mirror loss and the smoothness regulariser in one
+                             *    actor head; no layout changes) */
 
 enum {
     HGYM_OK = 0,
@@ -1093,6 +1095,32 @@ int32_t hgym_perturb_rows(int64_t M, int32_t width, const float* src, int64_t ld
                           const double* opt_state, float* dst, int64_t ld_dst, void* stream);
 int32_t hgym_ppo_grad_smooth(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const HgymNet* net, const HgymBatch* batch,
                              const HgymSmooth* smooth, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The mirror loss and the smoothness regulariser in one call (header v9, no layout change).  In the notation of the
+ * two terms above, with tm_b the raw mean of the partner row pair_idx[b] and M_a the action table (mirror_act_src, mirror_act_sign),
+ * c_m = ppo->mirror_coef, lamT = temporal_coef, lamS = spatial_coef:
+ *   L      = L_ppo + c_m / (B A) sum_b |mu_b - M_a tm_b|^2 + lamT / (B A) sum_b w_b |mu_b - tT_b|^2 + lamS / (B A) sum_b |mu_b - tS_b|^2
+ *   d mu_b = ((d mu_ppo + g_m (mu_b - M_a tm_b)) + gT w_b (mu_b - tT_b)) + gS (mu_b - tS_b),   g_m = 2 c_m / (B A), gT = 2 lamT / (B A), gS = 2 lamS / (B A)
+ * formed in that association, each term by the expression of its own head.  All three targets are formed under the current parameters
+ * and detached.  Only d mu, and hence the actor's gradient, differs from hgym_ppo_grad: d std, the critic, the auxiliary head, the KL slot
+ * and the loss sums of opt_state keep the bits hgym_ppo_grad gives them on the same inputs.
+ *
+ * hgym_ppo_grad_smooth_mirror: the launches, in order: the spatial pre-pass (hgym_perturb_rows, then the actor's forward into target_near),
+ *   the temporal pre-pass (forward through next_idx into target_next), the mirror pre-pass (forward through batch->pair_idx into
+ *   batch->mirror_target), then hgym_ppo_grad's launches with the actor's head replaced.  The perturbation reads opt_state[HGYM_OPT_STEP]
+ *   before the call's loss scalars can advance it.  The mirror loss's sums arrive in batch->mirror_sums as from hgym_ppo_grad, the
+ *   regulariser's in smooth->sums as from hgym_ppo_grad_smooth: the same bits as the single-option calls give on the same inputs.
+ *   head_partials: caller-owned fp32 scratch, 16-byte aligned, head_partials_len >= 4 * ceil(B / 64) floats.  The loss partial row has no
+ *   room for the combination's third sum, so the two smoothness errors of every 64-row tile (or 256-row loss block) pass through it; the
+ *   caller never reads it.
+ *   With ppo->mirror_coef == 0 the call is hgym_ppo_grad_smooth; with both smoothness coefficients 0 it is hgym_ppo_grad, mirror loss
+ *   included: the same launches, the same bits, and head_partials is not looked at.
+ *   HGYM_E_BADARG with nothing launched: everything hgym_ppo_grad_smooth refuses other than mirror_coef > 0; everything the mirror loss
+ *   refuses (a NULL pair_idx, table, mirror_target or mirror_sums, or a misaligned one); with all terms on a NULL, misaligned or too short
+ *   head_partials; ppo->world_size > 1.  HgymNet.norm is served as by the two single-option calls. */
+int32_t hgym_ppo_grad_smooth_mirror(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const HgymNet* net, const HgymBatch* batch,
+                                    const HgymSmooth* smooth, float* head_partials, int64_t head_partials_len, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Diagnostics of an update (header v9, no layout change): what the update did to the policy, measured on the rows it trained on.
