@@ -1258,6 +1258,20 @@ struct FbBC {
     int huber;                 // 0: MSE, d mu = 2 e inv; 1: Huber, d mu = clamp(e, -delta, delta) inv
 };
 
+// Guidance by a frozen teacher (hgym_ppo_grad_guide): the argument of the FbGuide head's kernels only
+// (hgym_update_guide.hip, hgym_update_act_guide.hip).  The PPO actor head plus c * inv2 * (mu - target[row]), the target a storage column
+// gathered through FwdArgs::idx like every other loss input.  The coefficient c changes with every update of a captured graph, so it is
+// read from the device -- one scalar load per tile -- and is no by-value argument.  A guided tile never carries the mirror loss: the squared
+// error goes to the partial row's LP_MIRROR slot.
+struct FbGuide {
+    const float* target;       // (num_rows, A) fp32: the teacher's mean of every stored row; 16-byte aligned rows when A == 12
+    const float* coef;         // one device float: this update's coefficient (hgym_guide_schedule)
+    float inv2;                // 2 / (M * A): d L_g / d mu = coef * inv2 * (mu - t)
+    int stage;                 // 1: the launch has FB_GUIDE_LDS more bytes of dynamic LDS behind fb_lds_bytes(net) and the tile's target rows are
+                               // staged there by the wavefronts idle in the third layer (with the other loss inputs)
+};
+constexpr int FB_GUIDE_LDS = 64 * 12 * 4;      // 64 rows x 12 floats
+
 // LDS of the fused kernel behind the forward's P / Q / bias regions: the dZ3 tile (64 rows x 32 * layer[3].NBB bf16 columns), the
 // head waves' partial sums, and H2 (64 x layer[2].N bf16) -- the forward writes it there instead of over H0, so that all three
 // activations are resident for the dZ chain
@@ -1288,7 +1302,7 @@ inline int fb_lds_bytes(const int32_t* dims) {
 
 // The head of an update tile is a type.  FbPlain: the PPO head alone (actor: surrogate, entropy, KL; critic: value loss; AUX: the
 // auxiliary head's MSE).  FbMirror / FbSmooth: the actor's PPO head with that term joined to d mu.  FbMirrorSmooth: with both.  FbBC: the
-// actor's regression head.
+// actor's regression head.  FbGuide: the actor's PPO head with the teacher's term joined to d mu.
 struct FbPlain {};
 template <class T, class Head>      // H where the tile's head is a T (or, for FbMirrorSmooth, its record of that type), else null
 __device__ __forceinline__ const T* head_as(const Head* H) {
@@ -1301,10 +1315,11 @@ __device__ __forceinline__ const T* head_as(const Head* H) {
 template <class Head, bool AUX>
 __device__ __forceinline__ constexpr bool fb_partial_mine(bool is_actor, int tid) {
     constexpr bool ML = __is_same(Head, FbMirror), BC = __is_same(Head, FbBC), SM = __is_same(Head, FbSmooth), MS = __is_same(Head, FbMirrorSmooth);
+    constexpr bool GD = __is_same(Head, FbGuide);
     return BC    ? ((tid >= LP_DBIAS_MU && tid < LP_DBIAS_V) || tid == LP_MIRROR)      // d mu's sums and the regression slot
            : AUX ? tid == LP_AUX
                  : (is_actor ? ((tid != LP_VALUE && tid < LP_DBIAS_V) ||               // all of the PPO head's but the critic's two
-                                ((ML || MS) && tid == LP_MIRROR) ||
+                                ((ML || MS || GD) && tid == LP_MIRROR) ||
                                 (SM && (tid == LP_SMOOTH_T || tid == LP_SMOOTH_S)))
                              : (tid == LP_VALUE || tid == LP_DBIAS_V));
 }
@@ -1317,8 +1332,10 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
     constexpr bool ML = __is_same(Head, FbMirror), BC = __is_same(Head, FbBC), SM = __is_same(Head, FbSmooth);
     constexpr bool MS = __is_same(Head, FbMirrorSmooth);      // both heads: every ML line and every SM line, the SM block of LDS behind the ML one
     constexpr int SM_LDS0 = MS ? FB_MIRROR_LDS / 4 : 0;       // floats ahead of the smooth head's staged block
+    constexpr bool GD = __is_same(Head, FbGuide);             // the teacher's term: gathered target rows, the coefficient from the device
     static_assert(__is_same(Head, FbPlain) || (!AUX && !VU), "a head other than the plain one is the actor's alone");
     const FbMirror* Mr = head_as<FbMirror>(H); const FbBC* Bc = head_as<FbBC>(H); const FbSmooth* Sm = head_as<FbSmooth>(H);
+    const FbGuide* Gd = head_as<FbGuide>(H);
     constexpr int BM = 64, NW = 16, D = 2, MB = BM / 16;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 15, q = lane >> 4;
@@ -1339,6 +1356,8 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
     const bool pre = !AUX && n.layer[2].NB <= 8 && (is_actor ? A == 12 : true);
     const float invB = 1.0f / (float)a.M;
     float aux_se = 0.0f;
+    float guide_g = 0.0f;      // GD: coef * 2 / (M A), the coefficient read once per tile (a uniform address: one scalar load)
+    if constexpr (GD) guide_g = Gd->coef[0] * Gd->inv2;
     // auxiliary head: lane (r, q) of head wave hw, row m, outputs nb * 16 + 4q .. + 3 (called once per column block).
     // loss = coef * mean_b sum_j (y - t)^2 / No, dL/dy = 2 coef (y - t) / (B No)    (aux_mse_kernel's arithmetic)
     auto head_aux = [&](int hw, int m, int nb, const float (&out)[4]) {
@@ -1417,6 +1436,17 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
                 if (j >= 384 && j < 448) st[2 * 64 * 12 + (j & 63)] = wv;
             }
         }
+        if constexpr (GD) {
+            // the tile's 64 target rows, gathered through rowidx like the actions (three 16-byte loads per row), -> LDS behind the other
+            // loss inputs.  Rows of 12 floats: l2idle runs under `pre` only, which for the actor means A == 12.
+            if (Gd->stage) {
+                float* gt = lin + FB_LIN_ACTOR * 64;
+                const int rw = j / 3 < 63 ? j / 3 : 63, k = j % 3;
+                const int64_t ri = rowidx[rw];
+                const F4 vt = *reinterpret_cast<const F4*>(Gd->target + ri * 12 + 4 * k);
+                if (j < 192) *reinterpret_cast<F4*>(gt + rw * 12 + 4 * k) = vt;
+            }
+        }
         if (is_actor) {
             // round 1: (row, quad k): actions 0..2, old mu 3..5, old sigma 6..7; round 2: old sigma quad 2, advantage, old log-prob.
             // Every load is issued before the first LDS write.
@@ -1445,7 +1475,7 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
         const int rl = hw * 16 + r;                 // row of the tile
         const int64_t row = rowidx[rl];
         float g[4] = {0.f, 0.f, 0.f, 0.f};
-        constexpr int NPART = MS ? 14 : (ML ? 12 : (SM ? 13 : 11));      // ML: [11] the mirror loss's squared error; SM: [11], [12] the two terms'; MS: [11], then [12], [13]
+        constexpr int NPART = MS ? 14 : ((ML || GD) ? 12 : (SM ? 13 : 11));      // ML: [11] the mirror loss's squared error; SM: [11], [12] the two terms'; MS: [11], then [12], [13]; GD: [11] the teacher's
         constexpr int PT = MS ? 12 : 11;                        // the temporal term's sum, the spatial term's behind it
         float part[NPART];
 #pragma unroll
@@ -1575,6 +1605,25 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
                 seS += __shfl_xor(seS, 16, 64); seS += __shfl_xor(seS, 32, 64);
                 if (q == 0) { part[PT] = seT; part[PT + 1] = seS; }
             }
+            if constexpr (GD) {
+                // the teacher's term: c inv2 (mu - t) joins d mu (and the head-bias sum), (mu - t)^2 the tile's partial sum; nothing else moves
+                const bool staged = pre && Gd->stage;
+                const float* gt = lin + FB_LIN_ACTOR * 64;
+                float se = 0.0f;
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (4 * q + e < A) {
+                        const float t = staged ? gt[rl * 12 + 4 * q + e] : Gd->target[row * A + 4 * q + e];
+                        const float dm = out[e] - t;
+                        if (valid) {
+                            g[e] += guide_g * dm;
+                            part[7 + e] = g[e];
+                            se += dm * dm;
+                        }
+                    }
+                se += __shfl_xor(se, 16, 64); se += __shfl_xor(se, 32, 64);
+                if (q == 0) part[11] = se;
+            }
         } else {
             const float ret = pre ? lin[rl * 2] : L.returns[row], vold = pre ? lin[rl * 2 + 1] : L.values[row];
             const float v = out[0];
@@ -1617,7 +1666,7 @@ __device__ __forceinline__ void fb_body(const FwdArgs& a, const FbLoss& L, const
             float* w = red + hw * LOSS_PARTIALS;
             if (is_actor) {
                 if (q == 0) { w[LP_SURROGATE] = part[0]; w[LP_ENTROPY] = part[1]; w[LP_KL] = part[2]; }
-                if constexpr (ML || MS) { if (q == 0) w[LP_MIRROR] = part[11]; }
+                if constexpr (ML || MS || GD) { if (q == 0) w[LP_MIRROR] = part[11]; }
                 if constexpr (SM) { if (q == 0) { w[LP_SMOOTH_T] = part[11]; w[LP_SMOOTH_S] = part[12]; } }
                 if constexpr (MS) { if (q == 0) { w[MS_RED_T] = part[PT]; w[MS_RED_S] = part[PT + 1]; } }
 #pragma unroll
@@ -1829,18 +1878,21 @@ auto fb_head_kernel() {
 inline int fb_head_lds(const FbMirror&) { return FB_MIRROR_LDS; }
 inline int fb_head_lds(const FbSmooth&) { return FB_SMOOTH_LDS; }
 inline int fb_head_lds(const FbMirrorSmooth&) { return FB_MIRROR_LDS + FB_SMOOTH_LDS; }
+inline int fb_head_lds(const FbGuide&) { return FB_GUIDE_LDS; }
 inline int fb_head_lds(const FbBC&) { return 0; }      // its targets lie in the loss-input region the sum already holds
 inline void fb_head_stage(FbMirror& h, int on) { h.stage = on; }
 inline void fb_head_stage(FbSmooth& h, int on) { h.stage = on; }
 inline void fb_head_stage(FbMirrorSmooth& h, int on) { h.stage = h.m.stage = h.s.stage = on; }
+inline void fb_head_stage(FbGuide& h, int on) { h.stage = on; }
 inline void fb_head_stage(FbBC&, int) {}
 inline const char* fb_head_name(const FbMirror&) { return "mlp_fb_head_kernel<mirror>"; }
 inline const char* fb_head_name(const FbSmooth&) { return "mlp_fb_head_kernel<smooth>"; }
 inline const char* fb_head_name(const FbMirrorSmooth&) { return "mlp_fb_head_kernel<mirror_smooth>"; }
+inline const char* fb_head_name(const FbGuide&) { return "mlp_fb_head_kernel<guide>"; }
 inline const char* fb_head_name(const FbBC&) { return "mlp_fb_bc_kernel"; }
 
 // One launch of the actor's tiles with `head0`.  Each (GA, Head) is explicitly instantiated in a translation unit, i.e. a device code
-// object, of its own (hgym_update_{mirror,smooth,mirror_smooth,bc}.hip: ELU(1), hgym_update_act_{..}.hip: any resolved activation) and
+// object, of its own (hgym_update_{mirror,smooth,mirror_smooth,guide,bc}.hip: ELU(1), hgym_update_act_{..}.hip: any resolved activation) and
 // declared `extern` below: no other translation unit carries these kernels.
 template <bool GA, class Head>
 int32_t launch_mlp_fb_head(const FwdArgs& fb0, const FbLoss& fl, const Head& head0, bool shadow, int tiles, hipStream_t s) {
@@ -1872,6 +1924,8 @@ extern template int32_t launch_mlp_fb_head<false, FbSmooth>(const FwdArgs&, cons
 extern template int32_t launch_mlp_fb_head<true, FbSmooth>(const FwdArgs&, const FbLoss&, const FbSmooth&, bool, int, hipStream_t);
 extern template int32_t launch_mlp_fb_head<false, FbMirrorSmooth>(const FwdArgs&, const FbLoss&, const FbMirrorSmooth&, bool, int, hipStream_t);
 extern template int32_t launch_mlp_fb_head<true, FbMirrorSmooth>(const FwdArgs&, const FbLoss&, const FbMirrorSmooth&, bool, int, hipStream_t);
+extern template int32_t launch_mlp_fb_head<false, FbGuide>(const FwdArgs&, const FbLoss&, const FbGuide&, bool, int, hipStream_t);
+extern template int32_t launch_mlp_fb_head<true, FbGuide>(const FwdArgs&, const FbLoss&, const FbGuide&, bool, int, hipStream_t);
 extern template int32_t launch_mlp_fb_head<false, FbBC>(const FwdArgs&, const FbLoss&, const FbBC&, bool, int, hipStream_t);
 extern template int32_t launch_mlp_fb_head<true, FbBC>(const FwdArgs&, const FbLoss&, const FbBC&, bool, int, hipStream_t);
 

@@ -252,6 +252,14 @@ __global__ __launch_bounds__(256) void ppo_loss_smooth_kernel(const LossArgs a, 
     if (k < 14) a.partials[(int64_t)blockIdx.x * LOSS_PARTIALS + (k < 12 ? LP_DBIAS_MU + k : LP_SMOOTH_T + (k - 12))] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
 }
 
+// ------------------------------------------------------------------------------------------------ guidance (hgym_ppo_grad_guide)
+// The argument of ppo_loss_guide_kernel (hgym_guide.hip), the layer-by-layer path's head with the frozen teacher's cloning term.
+struct LossGuide {
+    const float* target;         // (num_rows, A) the teacher's mean of every stored row, gathered through idx
+    const float* coef;           // one device float: this update's coefficient
+    float inv2;                  // 2 / (B * A)
+};
+
 // ------------------------------------------------------------------------------------------------ behaviour cloning (hgym_bc_grad)
 // bc_loss_kernel: the regression head of the layer-by-layer path, one thread per sample: e = mu - target[idx[i]], d mu into the actor's
 // last dY / dYT (the operands of the backward that follows), the sample's loss terms and d mu into the block's partial row (LP_MIRROR --

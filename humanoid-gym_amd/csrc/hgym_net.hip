@@ -42,6 +42,9 @@ int32_t launch_smooth_sums(int nblocks, int B, int A, const float* partials, con
 // regulariser at once, and the sums of the two smoothness terms from head_partials
 int32_t launch_ppo_loss_mirror_smooth(const LossArgs& a, const LossSmooth& sm, float* head_partials, bool bf16, int nblocks, hipStream_t s);
 int32_t launch_head_sums(int nblocks, int B, int A, const float* head_partials, const float* weight, double* sums, hipStream_t s);
+// hgym_guide.hip: hgym_ppo_grad_guide's small kernels -- the layer-by-layer head with the teacher's term, and the sums of its squared error
+int32_t launch_ppo_loss_guide(const LossArgs& a, const LossGuide& gd, bool bf16, int nblocks, hipStream_t s);
+int32_t launch_guide_sums(int nblocks, int B, int A, const float* partials, double* sums, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------ layouts
 struct LayerLayout {
@@ -1049,7 +1052,9 @@ struct GemmPath : NetBase {
     // complete, just later)
     // sm (hgym_ppo_grad_smooth): the smoothness regulariser joins d mu; null or both coefficients 0: off, the launches of hgym_ppo_grad
     // hp (hgym_ppo_grad_smooth_mirror): head_partials, named only when the mirror loss and the regulariser are both on
-    int32_t grad(const HgymPPOConfig& ppo, const HgymBatch& b, int part, const HgymSmooth* sm = nullptr, float* hp = nullptr) {
+    // gd (hgym_ppo_grad_guide): the teacher's term joins d mu; never together with the mirror loss or sm
+    int32_t grad(const HgymPPOConfig& ppo, const HgymBatch& b, int part, const HgymSmooth* sm = nullptr, float* hp = nullptr,
+                 const HgymGuide* gd = nullptr) {
         if (part == 1) return HGYM_OK;
         const int B = b.B, A = cfg.num_actions;
         float* mu = at<float>(w.net[0].out_f32);
@@ -1126,6 +1131,12 @@ struct GemmPath : NetBase {
             if (rc_sm) return rc_sm;
             rc_sm = launch_smooth_sums(nblocks, B, A, at<float>(w.partials), sm->next_weight, sm->sums, s);
             if (rc_sm) return rc_sm;
+        } else if (gd) {          // behind it: d mu with the teacher's term, the LP_DBIAS_MU / LP_MIRROR partials (hgym_guide.hip), then the sums
+            const LossGuide lg = {gd->teacher_mu, gd->coef, 2.0f / ((float)B * (float)A)};
+            int32_t rc_gd = launch_ppo_loss_guide(a, lg, sizeof(T) == 2, nblocks, s);
+            if (rc_gd) return rc_gd;
+            rc_gd = launch_guide_sums(nblocks, B, A, at<float>(w.partials), gd->sums, s);
+            if (rc_gd) return rc_gd;
         }
         prof_end(HGYM_PROF_LOSS, s, (double)B * (4.0 * (5 * A + 6) + (double)sizeof(T) * (2 * A + 2)));
         HG_CHECK_LAUNCH("ppo_loss_kernel");
@@ -1479,7 +1490,9 @@ struct FusedPath : NetBase {
     // gradient final, 1 the critic's, the auxiliary head's and the KL slot.
     // sm (hgym_ppo_grad_smooth): the smoothness regulariser joins d mu; null or both coefficients 0: off, the launches of hgym_ppo_grad
     // hp (hgym_ppo_grad_smooth_mirror): head_partials, named only when the mirror loss and the regulariser are both on
-    int32_t grad(const HgymPPOConfig& ppo, const HgymBatch& b, int part, const HgymSmooth* sm = nullptr, float* hp = nullptr) {
+    // gd (hgym_ppo_grad_guide): the teacher's term joins d mu; never together with the mirror loss or sm
+    int32_t grad(const HgymPPOConfig& ppo, const HgymBatch& b, int part, const HgymSmooth* sm = nullptr, float* hp = nullptr,
+                 const HgymGuide* gd = nullptr) {
         const int B = b.B, A = cfg.num_actions;
         const int64_t critic_off = w.net[1].layer[0].w_off;
         const int Mp = (int)round_up(B, w.SE);
@@ -1550,6 +1563,13 @@ struct FusedPath : NetBase {
                 rc_fb = launch_actor_head(u, head);
                 if (rc_fb) return rc_fb;
                 rc_fb = launch_smooth_sums(u.tiles, B, A, at<float>(w.partials), sm->next_weight, sm->sums, s);
+                first = 1;
+            } else if (gd) {
+                // the same with the teacher's term (the coefficient is read on the device), and the sums of its squared error
+                const FbGuide head = {gd->teacher_mu, gd->coef, 2.0f / ((float)B * (float)A), 0};
+                rc_fb = launch_actor_head(u, head);
+                if (rc_fb) return rc_fb;
+                rc_fb = launch_guide_sums(u.tiles, B, A, at<float>(w.partials), gd->sums, s);
                 first = 1;
             }
             if (rc_fb) return rc_fb;
@@ -1875,18 +1895,20 @@ int32_t hgym_policy_act_fin(const HgymNetConfig* cfg, const HgymNet* net, int32_
     });
 }
 
-// Behind hgym_ppo_grad, hgym_ppo_grad_part, hgym_ppo_grad_smooth and hgym_ppo_grad_smooth_mirror: the checks they share, in one order, then
-// the runner's grad.  part: null for the whole gradient, else hgym_ppo_grad_part's half; smooth: null unless hgym_ppo_grad_smooth(_mirror);
-// head_partials: null unless hgym_ppo_grad_smooth_mirror with all of its terms on.
+// Behind hgym_ppo_grad, hgym_ppo_grad_part, hgym_ppo_grad_smooth, hgym_ppo_grad_smooth_mirror and hgym_ppo_grad_guide: the checks they
+// share, in one order, then the runner's grad.  part: null for the whole gradient, else hgym_ppo_grad_part's half; smooth: null unless
+// hgym_ppo_grad_smooth(_mirror); head_partials: null unless hgym_ppo_grad_smooth_mirror with all of its terms on; guide: null unless
+// hgym_ppo_grad_guide.
 static int32_t ppo_grad_entry(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const HgymNet* net, const HgymBatch* batch,
-                              const int32_t* part, const HgymSmooth* smooth, void* stream, float* head_partials = nullptr) {
+                              const int32_t* part, const HgymSmooth* smooth, void* stream, float* head_partials = nullptr,
+                              const HgymGuide* guide = nullptr) {
     return run(cfg, net, stream, [&](auto& R) -> int32_t {
         int32_t rc = check_ppo(ppo);
         if (rc) return rc;
         HG_REQUIRE(!part || *part == 0 || *part == 1, HGYM_E_BADARG, "part=%d (0 or 1)", *part);
         HG_REQUIRE(net->grads && net->opt_state, HGYM_E_BADARG, "null grads / opt_state");
         rc = check_batch(R.w, ppo, batch);
-        return rc ? rc : R.grad(*ppo, *batch, part ? *part : -1, smooth, head_partials);
+        return rc ? rc : R.grad(*ppo, *batch, part ? *part : -1, smooth, head_partials, guide);
     });
 }
 
@@ -1946,6 +1968,18 @@ int32_t hgym_ppo_grad_smooth_mirror(const HgymNetConfig* cfg, const HgymPPOConfi
                    (long long)head_partials_len, batch->B, (long long)need);
     }
     return ppo_grad_entry(cfg, ppo, net, batch, nullptr, smooth, stream, all ? head_partials : nullptr);
+}
+
+int32_t hgym_ppo_grad_guide(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const HgymNet* net, const HgymBatch* batch,
+                            const HgymGuide* guide, void* stream) {
+    // every refusal below comes before anything is launched
+    HG_REQUIRE(cfg && ppo && net && batch && guide, HGYM_E_BADARG, "hgym_ppo_grad_guide: null cfg / ppo / net / batch / guide");
+    HG_REQUIRE(guide->teacher_mu && guide->coef && guide->sums, HGYM_E_BADARG, "hgym_ppo_grad_guide: null HgymGuide.teacher_mu / coef / sums");
+    HG_REQUIRE(((uintptr_t)guide->teacher_mu & 15) == 0 && ((uintptr_t)guide->coef & 3) == 0 && ((uintptr_t)guide->sums & 7) == 0, HGYM_E_BADARG,
+               "hgym_ppo_grad_guide: HgymGuide.teacher_mu must be 16-byte aligned (coef 4, sums 8)");
+    HG_REQUIRE(!(ppo->mirror_coef > 0.0f), HGYM_E_BADARG, "hgym_ppo_grad_guide with HgymPPOConfig.mirror_coef > 0: the two heads do not combine");
+    HG_REQUIRE(ppo->world_size <= 1, HGYM_E_BADARG, "hgym_ppo_grad_guide with world_size=%d: one rank only", ppo->world_size);
+    return ppo_grad_entry(cfg, ppo, net, batch, nullptr, nullptr, stream, nullptr, guide);
 }
 
 int32_t hgym_ppo_grad_part(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const HgymNet* net, const HgymBatch* batch, int32_t part,

@@ -6,6 +6,7 @@ from .net import NetBuffers, make_net_config, make_ppo_config, make_batch, activ
 from .net import check_obs_norm, norm_layout
 from .net import make_bc_config, make_bc_batch, BC_LOSS_TYPES
 from .net import make_smooth, smooth_ld, smooth_mirror_partials
+from .net import make_guide, make_guide_schedule, guide_schedule, guide_schedule_coef, GUIDE_MODES
 
 
 def smooth_pairs(idx, dones, N, next_idx, next_weight):

@@ -191,10 +191,24 @@ class Smooth(C.Structure):
                 ("rows", c_float_p), ("sums", c_f64_p)]
 
 
+GUIDE_CONSTANT, GUIDE_STEP, GUIDE_LINEAR = 0, 1, 2    # HGYM_GUIDE_*: HgymGuideSchedule.mode
+
+
+class GuideSchedule(C.Structure):
+    """HgymGuideSchedule: the coefficient of the guidance term as a function of the update count (hgym_guide_schedule)."""
+    _fields_ = [("coef", C.c_double), ("final_value", C.c_double), ("initial_step", C.c_int64), ("final_step", C.c_int64),
+                ("mode", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Guide(C.Structure):
+    """HgymGuide: the teacher's mean column, the device-resident coefficient and the two sums of hgym_ppo_grad_guide."""
+    _fields_ = [("teacher_mu", c_float_p), ("coef", c_float_p), ("sums", c_f64_p)]
+
+
 STRUCTS = dict(HgymEnvConfig=EnvConfig, HgymStrided=Strided, HgymSimTensors=SimTensors, HgymEnvState=EnvState,
                HgymEnvOut=EnvOut, HgymEnvNoise=EnvNoise, HgymNetConfig=NetConfig, HgymPPOConfig=PPOConfig,
                HgymNet=Net, HgymBatch=Batch, HgymObsShadow=ObsShadow, HgymComm=Comm, HgymBCConfig=BCConfig, HgymRndConfig=RndConfig,
-               HgymSmooth=Smooth)
+               HgymSmooth=Smooth, HgymGuideSchedule=GuideSchedule, HgymGuide=Guide)
 
 # every symbol include/hgym.h declares: name -> (restype, argtypes)
 _P = C.POINTER
@@ -279,6 +293,8 @@ SYMBOLS = {
                                       C.c_void_p]),
     "hgym_ppo_grad_smooth": (C.c_int32, [_P(NetConfig), _P(PPOConfig), _P(Net), _P(Batch), _P(Smooth), C.c_void_p]),
     "hgym_ppo_grad_smooth_mirror": (C.c_int32, [_P(NetConfig), _P(PPOConfig), _P(Net), _P(Batch), _P(Smooth), c_float_p, C.c_int64, C.c_void_p]),
+    "hgym_guide_schedule": (C.c_int32, [_P(GuideSchedule), c_i64_p, c_float_p, C.c_void_p]),
+    "hgym_ppo_grad_guide": (C.c_int32, [_P(NetConfig), _P(PPOConfig), _P(Net), _P(Batch), _P(Guide), C.c_void_p]),
     "hgym_net_param_offset": (C.c_int64, [_P(NetConfig), C.c_int32]),
     "hgym_ppo_apply": (C.c_int32, [_P(NetConfig), _P(PPOConfig), _P(Net), C.c_void_p]),
     "hgym_prof_enable": (C.c_int32, [C.c_int32]),

@@ -330,6 +330,12 @@ class NetBuffers:
                                                   L.fptr(head_partials), 0 if head_partials is None else int(head_partials.numel()),
                                                   self.stream()), "hgym_ppo_grad_smooth_mirror")
 
+    def ppo_grad_guide(self, ppo, batch, guide):
+        """hgym_ppo_grad_guide: hgym_ppo_grad with a frozen teacher's cloning term (make_guide) in the actor's head.  The coefficient is read
+        from the device on every call, so a captured call follows hgym.guide_schedule.  Refused: ppo.mirror_coef > 0, several ranks."""
+        L.check(L.lib.hgym_ppo_grad_guide(C.byref(self.cfg), C.byref(ppo), C.byref(self.struct), C.byref(batch), C.byref(guide), self.stream()),
+                "hgym_ppo_grad_guide")
+
     def ppo_grad_part(self, ppo, batch, part):
         """hgym_ppo_grad in two halves (data-parallel update): after part 0 `grads_ext[:bucket_split]` (std | actor, the larger
         bucket) is final, after part 1 `grads_ext[bucket_split:]` (critic | auxiliary head | KL slot)."""
@@ -430,6 +436,67 @@ def make_smooth(temporal_coef=0.0, spatial_coef=0.0, next_idx=None, next_weight=
     assert sums is None or sums.numel() >= 4
     return L.Smooth(lt, ls, L.i64ptr(next_idx), L.fptr(next_weight), L.fptr(noise_std), int(seed) & 0xFFFFFFFFFFFFFFFF, L.fptr(target_next),
                     L.fptr(target_near), L.fptr(rows), L.f64ptr(sums))
+
+
+GUIDE_MODES = ("constant", "step", "linear")
+
+
+def make_guide_schedule(mode="constant", coef=0.0, final_value=None, initial_step=0, final_step=0):
+    """HgymGuideSchedule of hgym_guide_schedule.  mode: "constant", "step" (coef while k < final_step, then final_value) or "linear" (coef
+    up to initial_step, a straight line to final_value at final_step, final_value beyond).  ValueError for an unknown mode, a coefficient
+    that is not finite and >= 0, a negative step, or linear with final_step <= initial_step."""
+    import math
+    if mode not in GUIDE_MODES:
+        raise ValueError("mode=%r: one of %s" % (mode, ", ".join(GUIDE_MODES)))
+    c = float(coef)
+    f = c if final_value is None or mode == "constant" else float(final_value)
+    for name, v in (("coef", c), ("final_value", f)):
+        if not (v >= 0.0 and math.isfinite(v)):
+            raise ValueError("%s=%r: must be finite and >= 0" % (name, v))
+    i0, i1 = (0, 0) if mode == "constant" else (int(initial_step) if mode == "linear" else 0, int(final_step))
+    if i0 < 0 or i1 < 0:
+        raise ValueError("initial_step=%r / final_step=%r: must be >= 0" % (initial_step, final_step))
+    if mode == "linear" and i1 <= i0:
+        raise ValueError("final_step=%d must be greater than initial_step=%d" % (i1, i0))
+    return L.GuideSchedule(c, f, i0, i1, GUIDE_MODES.index(mode), 0)
+
+
+def guide_schedule_coef(sched, k):
+    """The coefficient hgym_guide_schedule writes at update count k, bit for bit: python doubles, left to right, rounded to fp32 once.
+    sched: an HgymGuideSchedule (make_guide_schedule).  Returns the fp32 value as a python float."""
+    import struct
+    k = int(k)
+    c, f, i0, i1 = float(sched.coef), float(sched.final_value), int(sched.initial_step), int(sched.final_step)
+    if sched.mode == L.GUIDE_STEP:
+        v = c if k < i1 else f
+    elif sched.mode == L.GUIDE_LINEAR:
+        if k <= i0:
+            v = c
+        elif k >= i1:
+            v = f
+        else:
+            v = c + (f - c) * float(k - i0) / float(i1 - i0)
+    else:
+        v = c
+    return struct.unpack("f", struct.pack("f", v))[0]
+
+
+def guide_schedule(sched, count, coef, stream=None):
+    """hgym_guide_schedule on the current stream: coef[0] = schedule(count[0]) as fp32, then count[0] += 1.  count: int64 (1,) device tensor,
+    coef: float32 (1,) device tensor; one launch with fixed arguments, capturable."""
+    assert count.dtype == torch.int64 and count.numel() >= 1 and coef.dtype == torch.float32 and coef.numel() >= 1
+    assert count.is_cuda and coef.is_cuda
+    s = C.c_void_p(torch.cuda.current_stream(count.device).cuda_stream) if stream is None else stream
+    L.check(L.lib.hgym_guide_schedule(C.byref(sched), L.i64ptr(count), L.fptr(coef), s), "hgym_guide_schedule")
+
+
+def make_guide(teacher_mu, coef, sums):
+    """HgymGuide of hgym_ppo_grad_guide.  Device tensors the caller keeps alive: teacher_mu fp32 (num_rows, num_actions) contiguous, 16-byte
+    aligned -- the frozen teacher's mean of every stored row, gathered through the batch's idx; coef fp32 (1,), this update's coefficient
+    (hgym.guide_schedule writes it); sums float64 (2,), zeroed by the caller: [0] += the minibatch's unweighted MSE, [1] += 1."""
+    assert teacher_mu.dtype == torch.float32 and teacher_mu.is_contiguous() and teacher_mu.dim() == 2
+    assert coef.dtype == torch.float32 and coef.numel() >= 1 and sums.dtype == torch.float64 and sums.is_contiguous() and sums.numel() >= 2
+    return L.Guide(L.fptr(teacher_mu), L.fptr(coef), L.f64ptr(sums))
 
 
 BC_LOSS_TYPES = ("mse", "huber")

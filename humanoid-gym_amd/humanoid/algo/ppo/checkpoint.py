@@ -17,6 +17,7 @@ import torch
 NORM_KEYS = ("obs_norm_state_dict", "critic_obs_norm_state_dict")      # a checkpoint of a run with empirical_normalization carries both
 RND_STATE_KEY = "rnd_state_dict"      # what a checkpoint of a run with rnd_cfg carries besides the reference's four keys
 VALUE_NORM_KEY = "value_norm_state_dict"      # what a checkpoint of a run with PPO.value_normalization carries: count, mean, var, eps
+GUIDE_KEY = "guidance_state_dict"      # what a checkpoint of a run with PPO.guidance carries: count, schedule, the teacher's actor tensors
 NORM_COUNT = 2      # NetBuffers.norm_view("header"): eps, until, then count of statistics k at NORM_COUNT + k, of L.NORM_HEADER_DOUBLES doubles
 
 
@@ -92,14 +93,16 @@ def write_checkpoint(ck, path, side=None):
 # ------------------------------------------------------------------ what a checkpoint contains
 def extra_entries(alg):
     """What a checkpoint carries beyond the reference's four keys, in file order: the two normaliser dicts (NORM_KEYS) of a policy with
-    empirical_normalization, then RND_STATE_KEY of a run with rnd_cfg, then VALUE_NORM_KEY of a run with PPO.value_normalization.  Reads the
-    device (the blocking path)."""
+    empirical_normalization, then RND_STATE_KEY of a run with rnd_cfg, then VALUE_NORM_KEY of a run with PPO.value_normalization, then
+    GUIDE_KEY of a run with PPO.guidance (host data: the background path adds the same dict).  Reads the device (the blocking path)."""
     ac, rnd = alg.actor_critic, alg._rnd
     extra = dict(ac.norm_state_dicts()) if hasattr(ac, "norm_state_dicts") else {}
     if rnd is not None:
         extra[RND_STATE_KEY] = rnd.rnd_state_dict()
     if getattr(alg, "value_normalizer", None) is not None:
         extra[VALUE_NORM_KEY] = alg.value_normalizer.state_dict()
+    if getattr(alg, "_guide", None) is not None:
+        extra[GUIDE_KEY] = alg._guide.state_dict()
     return extra
 
 
@@ -207,6 +210,8 @@ def write_snapshot(shot, group, it, infos, path, side):
         shot["done"].synchronize()
         tj.append(time.perf_counter())
         ck = assemble(shot["buf"], shot["layout"], shot["opt_layout"], group, it, infos, shot["norm"], shot.get("value_norm"))
+        if shot.get("guidance") is not None:      # PPO.guidance: Guidance.state_dict() as the training thread formed it at save() (host data)
+            ck[GUIDE_KEY] = shot["guidance"]
         tj.append(time.perf_counter())
         write_checkpoint(ck, path, side)
         tj.append(time.perf_counter())
@@ -293,9 +298,9 @@ def _check_value_norm_key(loaded, eps, name):
         raise RuntimeError("%s: `%s` was saved with value_normalization_eps=%r; this run was built with %r" % (name, VALUE_NORM_KEY, sd.get("eps"), eps))
 
 
-def check_compatible(loaded, actor_critic, rnd, name, value_norm=None):
-    """Checkpoint `loaded` (file `name`) against this run's policy, RND module (None: off) and value normalisation (value_norm: its eps,
-    None: off); raises before anything is changed."""
+def check_compatible(loaded, actor_critic, rnd, name, value_norm=None, guidance=None):
+    """Checkpoint `loaded` (file `name`) against this run's policy, RND module (None: off), value normalisation (value_norm: its eps,
+    None: off) and guidance (the run's Guidance, None: off); raises before anything is changed."""
     # a checkpoint of the other noise parametrisation: its first entry is another quantity under another name
     msd, mine = loaded["model_state_dict"], getattr(actor_critic, "noise_std_type", "scalar")
     theirs = "log" if "log_std" in msd else ("scalar" if "std" in msd else mine)
@@ -309,3 +314,6 @@ def check_compatible(loaded, actor_critic, rnd, name, value_norm=None):
     from .rnd import check_state_dict as check_rnd_state
     check_rnd_state(loaded.get(RND_STATE_KEY), name, rnd is not None, getattr(rnd, "num_envs", None))
     _check_value_norm_key(loaded, value_norm, name)
+    # a checkpoint of a guided run for a run without the option, the reverse, or another schedule: refused by key name
+    from .guidance import check_state_dict as check_guide_state
+    check_guide_state(loaded.get(GUIDE_KEY), name, guidance is not None, getattr(guidance, "schedule", None))

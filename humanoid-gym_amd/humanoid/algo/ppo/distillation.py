@@ -67,6 +67,9 @@ class Distillation(PPO):
             rnd_module.check_setup(distillation=True)
         if smooth_module.parse_config(self.smoothness, self.actor_critic.num_actor_obs) is not None:
             smooth_module.check_setup(distillation=True)
+        from . import guidance as guide_module
+        if guide_module.parse_config(self.guidance) is not None:
+            guide_module.check_setup(distillation=True)
         if self.value_normalization:      # (a follow-up at most: a cloning run computes no returns, the critic is not trained)
             raise ValueError("PPO.value_normalization does not support Distillation: a cloning run has no returns to standardise")
         self.check_setup(self.actor_critic, num_transitions_per_env, self.gradient_length, self._world, self.symmetry,

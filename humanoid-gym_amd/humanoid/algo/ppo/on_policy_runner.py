@@ -162,7 +162,7 @@ def _split_algorithm_cfg(alg_cfg):
     off), not a parameter of the reference's PPO: it is taken out here and becomes PPO.symmetry.  The mirror loss's keys (SYMMETRY_KEYS)
     are taken out as well; _split_symmetry_cfg reads them.  So are the advantage normalisation's (ADVANTAGE_KEYS; _split_advantage_cfg)."""
     kwargs = dict(alg_cfg)
-    for k in SYMMETRY_KEYS + ADVANTAGE_KEYS + VALUE_NORM_KEYS + (RND_KEY, SMOOTH_KEY):
+    for k in SYMMETRY_KEYS + ADVANTAGE_KEYS + VALUE_NORM_KEYS + (RND_KEY, SMOOTH_KEY, GUIDE_KEY):
         kwargs.pop(k, None)
     return kwargs, bool(kwargs.pop("symmetry", False))
 
@@ -170,6 +170,7 @@ def _split_algorithm_cfg(alg_cfg):
 ADVANTAGE_KEYS = ("advantage_normalization", "normalize_advantage_per_mini_batch")      # neither is a parameter of PPO.__init__
 SMOOTH_KEY = "smoothness_cfg"      # the smoothness regulariser's block (humanoid.algo.ppo.smoothness.parse_config); absent or None: off
 VALUE_NORM_KEYS = ("value_normalization", "value_normalization_eps")      # PPO.value_normalization / _eps; neither is a parameter of PPO.__init__
+GUIDE_KEY = "guidance_cfg"      # guidance by a frozen teacher (humanoid.algo.ppo.guidance.parse_config); absent or None: off
 RND_KEY = "rnd_cfg"      # rsl_rl's Random Network Distillation block (humanoid.algo.ppo.rnd.parse_config); absent or None: off
 
 
@@ -267,6 +268,8 @@ class OnPolicyRunner:
                 sc["noise_std"] = smooth_module.env_noise_std(getattr(self.env, "cfg", None), getattr(self.env, "noise_scale_vec", None),
                                                               self.env.num_obs)
             self.alg.smoothness = sc
+        if self.alg_cfg.get(GUIDE_KEY) is not None:      # guidance by a frozen teacher; read by init_storage below
+            self.alg.guidance = dict(self.alg_cfg[GUIDE_KEY])
         if self.alg_cfg.get("value_normalization") is not None:      # value targets standardised by running statistics; read by init_storage below
             self.alg.value_normalization = bool(self.alg_cfg["value_normalization"])
         if self.alg_cfg.get("value_normalization_eps") is not None:
@@ -350,6 +353,10 @@ class OnPolicyRunner:
                 diag_now = diag_every > 0 and (it + 1) % diag_every == 0
                 if diag_now:
                     alg.diagnostics_prepare()       # slot 0's observation rows, before the update's clear() rotates them away
+                if plan.graph_update and getattr(alg, "_guide", None) is not None:
+                    # the one option whose graph key changes inside a run: when its schedule runs out the update is the plain one again
+                    alg._guide.retire_if_run_out()
+                    ukey = (gkey, alg.update_graph_key(), plan.fuse == "deferred")
                 mean_value_loss, mean_surrogate_loss = self._learn_step(plan, gkey, ukey, critic_obs, obs)
                 diag = alg.diagnostics(sync=False) if diag_now else None       # enqueued; read where this path reads anything
                 if plan.zero_copy:                  # storage.clear() rotated slot T into slot 0
@@ -767,6 +774,8 @@ class OnPolicyRunner:
             vn = getattr(alg, "value_normalizer", None)      # PPO.value_normalization: its three doubles ride in the snapshot
             shot = self._snapshot.take(alg.net, alg.actor_critic, self.env if env_state else None,
                                        value_norm=None if vn is None else (vn.block, vn.eps))
+            if getattr(alg, "_guide", None) is not None:      # PPO.guidance: host data, formed here where the count is this checkpoint's
+                shot["guidance"] = alg._guide.state_dict()
             side = dict(env=shot["env"], **extra) if env_state else None
             ckpt.WRITER.submit(lambda: ckpt.write_snapshot(shot, type(alg.optimizer).HYPER, it, infos, path, side))
             if wait:
@@ -810,7 +819,10 @@ class OnPolicyRunner:
             ckpt.check_sidecar(side, self.num_steps_per_env, self.env)      # (refused before anything is changed)
         if loaded is None:
             loaded = torch.load(path, map_location=self.device)
-        ckpt.check_compatible(loaded, ac, alg._rnd, os.path.basename(str(path)), value_norm=ckpt.value_norm_spec(alg))
+        ckpt.check_compatible(loaded, ac, alg._rnd, os.path.basename(str(path)), value_norm=ckpt.value_norm_spec(alg),
+                              guidance=getattr(alg, "_guide", None))
+        if getattr(alg, "_guide", None) is not None:
+            alg._guide.load_state_dict(loaded[ckpt.GUIDE_KEY])
         if getattr(alg, "value_normalizer", None) is not None:
             alg.value_normalizer.load_state_dict(loaded[ckpt.VALUE_NORM_KEY])
         if alg._rnd is not None:

@@ -19,6 +19,7 @@ from .mirror_loss import MirrorLoss
 from .normalizer import ValueNormalizer
 from .rollout_storage import RolloutStorage
 from . import dist_utils
+from . import guidance as guide_module
 from . import rnd as rnd_module
 from . import smoothness as smooth_module
 
@@ -123,6 +124,14 @@ class PPO:
     value_normalization = False
     value_normalization_eps = 1e-2
     value_normalizer = None      # the option's object once init_storage has built it; here, so that a PPO made without __init__ has the handle too
+    # guidance by a frozen teacher (kickstarting): None, or a dict {teacher, coef, coef_schedule, teacher_hidden_dims, teacher_activation,
+    # teacher_max_batch} (humanoid.algo.ppo.guidance.parse_config) -- compute_returns then ends with the teacher's pass over the T N stored
+    # observation rows (storage.teacher_mu), update() starts with hgym_guide_schedule (the coefficient of this update, formed and kept on
+    # the device) and calls hgym_ppo_grad_guide in place of hgym_ppo_grad: coef / (B A) sum (mu - t)^2 joins the loss, t detached.  When a
+    # schedule that ends at 0 has run out the update is the plain one again (one re-capture).  One rank, no symmetry in either form, not
+    # with PPO.smoothness, not with Distillation (ValueError from init_storage).  Read once, in init_storage.  `last_guidance`: {loss, coef}
+    # of the last update.  DESIGN.md section 33.
+    guidance = None
 
     def __init__(self, actor_critic, num_learning_epochs=1, num_mini_batches=1, clip_param=0.2, gamma=0.998, lam=0.95,
                  value_loss_coef=1.0, entropy_coef=0.0, learning_rate=1e-3, max_grad_norm=1.0, use_clipped_value_loss=True,
@@ -150,7 +159,7 @@ class PPO:
         self.comm_timing = None      # a list: update() appends a pair of HIP events around the wait for the gradient exchange
         # every option's state, "off" until init_storage reads the option: nobody probes for these.  The four option
         # objects (MirrorLoss, RandomNetworkDistillation, Smoothness, ValueNormalizer; None: off) and those that are on (init_storage)
-        self._mirror_loss = self._rnd = self._smooth = None      # (value_normalizer: the class attribute)
+        self._mirror_loss = self._rnd = self._smooth = self._guide = None      # (value_normalizer: the class attribute)
         self._options = self._scalar_order = ()
         self._symmetry = self._obs_norm = None
         self._augment, self._adv_mode = False, "batch"
@@ -179,15 +188,16 @@ class PPO:
     last_mirror_loss = property(lambda self: self._mirror_loss and self._mirror_loss.last)
     last_smoothness = property(lambda self: self._smooth and self._smooth.last)
     last_value_norm = property(lambda self: self.value_normalizer and self.value_normalizer.last)
+    last_guidance = property(lambda self: self._guide and self._guide.last)
 
     @staticmethod
     def check_setup(num_envs, num_transitions_per_env, num_mini_batches, num_actor_obs, world=1, symmetry=None, symmetry_augmentation=True,
                     mirror_loss_coef=0.0, advantage_normalization="batch", rnd=None, smoothness=None, value_normalization=False,
-                    value_normalization_eps=1e-2):
+                    value_normalization_eps=1e-2, guidance=None):
         """What init_storage refuses, as a function that needs no device (ValueError each), in the order the refusals win: an unknown
         advantage mode; a mirror coefficient that is negative or not finite, or one > 0 without `symmetry`; what PPO.rnd and PPO.smoothness
         refuse (their own check_setup); per-minibatch advantages over minibatches of fewer than 2 rows; value normalisation on more than one
-        rank or with an eps that is negative or not finite."""
+        rank or with an eps that is negative or not finite; what PPO.guidance refuses (its own check_setup)."""
         if advantage_normalization not in PPO.ADVANTAGE_NORMALIZATIONS:
             raise ValueError("PPO.advantage_normalization=%r: one of %s" % (advantage_normalization, ", ".join(PPO.ADVANTAGE_NORMALIZATIONS)))
         coef = float(mirror_loss_coef)
@@ -211,6 +221,9 @@ class PPO:
             eps = float(value_normalization_eps)
             if not (eps >= 0.0 and math.isfinite(eps)):
                 raise ValueError("PPO.value_normalization_eps=%r: must be finite and >= 0" % (value_normalization_eps,))
+        if guide_module.parse_config(guidance) is not None:
+            guide_module.check_setup(world, symmetry if (augment or coef > 0.0) else None, coef,
+                                     smooth_module.parse_config(smoothness, num_actor_obs) is not None)
 
     def init_storage(self, num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape):
         import hgym
@@ -219,7 +232,7 @@ class PPO:
         # (PPO.check_setup by name: a subclass has refusals of its own under that name, and runs them ahead of this call)
         PPO.check_setup(num_envs, num_transitions_per_env, self.num_mini_batches, ac.num_actor_obs, self._world, self.symmetry,
                         self.symmetry_augmentation, self.mirror_loss_coef, self.advantage_normalization, self.rnd, self.smoothness,
-                        bool(self.value_normalization), self.value_normalization_eps)
+                        bool(self.value_normalization), self.value_normalization_eps, self.guidance)
         self._adv_mode = self.advantage_normalization
         self.storage = RolloutStorage(num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape, self.device)
         coef = float(self.mirror_loss_coef)
@@ -292,15 +305,20 @@ class PPO:
             self.storage.enable_rnd(self._rnd.num_states, self._rnd.num_outputs)
         if self.value_normalization:      # the block of three doubles, the merge's scratch, the bootstrap value's buffer
             self.value_normalizer = ValueNormalizer.on_device(self.value_normalization_eps, num_envs * num_transitions_per_env, num_envs, self.device)
+        guide = guide_module.parse_config(self.guidance)
+        if guide is not None:      # the teacher's NetBuffers, the device count and coefficient, the log's three doubles, storage.teacher_mu
+            self._guide = guide_module.Guidance(guide, ac, self.net, num_envs * num_transitions_per_env, self.device)
+            self.storage.enable_guidance(ac.num_actions)
+            self._guide.bind_storage(self.storage)
         # the options that are on, in the two orders that are fixed: the log block's byte layout (checkpoints, tools and tests hold such
         # blocks) and the order in which the writer gets their scalars.  A new option goes at the end of both.
         on = lambda *options: tuple(o for o in options if o is not None)
-        self._options = on(self._mirror_loss, self._rnd, self._smooth, self.value_normalizer)
-        self._scalar_order = on(self._mirror_loss, self._smooth, self._rnd, self.value_normalizer)
+        self._options = on(self._mirror_loss, self._rnd, self._smooth, self.value_normalizer, self._guide)
+        self._scalar_order = on(self._mirror_loss, self._smooth, self._rnd, self.value_normalizer, self._guide)
         self._log = LogBlock(self._log_parts())
 
     def _log_parts(self):
-        """opt | mirror(2) | rnd_sums(2) | rnd_block(RND_HEADER) | smooth(4) | value_norm(3): opt_state, then the part(s) of every option that
+        """opt | mirror(2) | rnd_sums(2) | rnd_block(RND_HEADER) | smooth(4) | value_norm(3) | guide(2) | guide_coef(1): opt_state, then the part(s) of every option that
         is on; value_norm is the statistics' block itself (count, mean, var)."""
         return [("opt", self.net.opt_state)] + [part for o in self._options for part in o.log_parts()]
 
@@ -481,6 +499,10 @@ class PPO:
                            normalize=self._adv_mode == "batch")
         if vn is not None:      # merge the raw returns FIRST, then returns and old values into the critic's units under the new statistics
             vn.normalize_targets(st.returns, st.values)
+        if self._guide is not None:
+            self._guide.retire_if_run_out()      # (once, and never inside a capture)
+            if self._guide.active:               # the teacher's mean of the T N stored rows, for every minibatch of every epoch
+                self._guide.teacher_pass(st)
         self._returns_done()
 
     def _returns_done(self):      # what compute_returns() changes on the host, issued or replayed: the deferred values are used up
@@ -512,7 +534,8 @@ class PPO:
                    symmetry=None if self._symmetry is None else self._symmetry.key(),
                    # (the mirror loss's coefficient is also part of ppo_cfg's bytes; augment: whether the batch is doubled)
                    mirror_coef=0.0, augment=self._augment, mirror_scratch=None, smoothness=None, rnd=None,
-                   adv_mode=self._adv_mode, adv_scratch=st.minibatch_advantages_key(), obs_norm=self._obs_norm, value_norm=None)
+                   adv_mode=self._adv_mode, adv_scratch=st.minibatch_advantages_key(), obs_norm=self._obs_norm, value_norm=None,
+                   guidance=None)
         for o in self._options:
             key.update(o.graph_key())
         return tuple(key.items())
@@ -542,6 +565,8 @@ class PPO:
         self._diag_updated = True
         if self._direct_exchange():
             self._comm_direct_used = True
+        if self._guide is not None:
+            self._guide.update_done()
 
     def update(self, sync=True):
         """ppo.py:119-184.  Returns (mean_value_loss, mean_surrogate_loss) as floats -- the one host read-back of the
@@ -550,6 +575,7 @@ class PPO:
         hgym, net, st, direct = self._hgym, self.net, self.storage, self._direct_exchange()
         T, N = st.num_transitions_per_env, st.num_envs
         sym, aug, mirror_loss, smooth = self._symmetry is not None, self._augment, self._mirror_loss, self._smooth
+        guide = self._guide if (self._guide is not None and self._guide.active) else None      # (run out: the plain update)
         if sym:
             # the mirrored half of every column, from the finished rollout (returns, advantages, values, shadows: all there); the mirror
             # loss alone reads only the mirrored observations
@@ -590,6 +616,9 @@ class PPO:
             net.opt_state[hgym._lib.OPT_AUX_SUM:hgym._lib.OPT_AUX_SUM + 1] = 0.0     # (a slice: a fill kernel -- an indexed scalar store is a host-to-device copy, which a stream capture refuses)
         if self._rnd is not None:
             self._rnd.begin_update()
+        if guide is not None:      # this update's coefficient, formed on the device; the two sums zeroed
+            guide.begin_update()
+            guided = guide.minibatch()      # (the same descriptor for every minibatch: the column is gathered through the batch's idx)
         for _ in range(self.num_learning_epochs):
             for i in range(self.num_mini_batches):
                 idx = perm[i * mb:(i + 1) * mb]
@@ -599,6 +628,8 @@ class PPO:
                     net.ppo_grad_smooth_mirror(self._ppo_cfg, batch, smooth.minibatch(i), smooth.head_partials)
                 elif smooth is not None:
                     net.ppo_grad_smooth(self._ppo_cfg, batch, smooth.minibatch(i))
+                elif guide is not None:
+                    net.ppo_grad_guide(self._ppo_cfg, batch, guided)
                 else:
                     net.ppo_grad(self._ppo_cfg, batch)
                 if self._obs_norm is not None:
@@ -643,7 +674,7 @@ class PPO:
 
     def read_log(self, block):
         """A host copy of log_block() -> hgym.opt_summary's dict; sets last_denoise_loss, last_mirror_loss, last_smoothness,
-        last_value_norm and RND's last_log on the way.  The one reader behind update(sync=True) and the runner's asynchronous log."""
+        last_value_norm, last_guidance and RND's last_log on the way.  The one reader behind update(sync=True) and the runner's asynchronous log."""
         parts = self._log.split(block)
         for option in self._options:      # each leaves its numbers on itself: last_mirror_loss, last_smoothness, last_value_norm read them there
             option.read_log(parts)
@@ -656,7 +687,7 @@ class PPO:
         out = []
         if self.denoise_coef and self.last_denoise_loss is not None:
             out.append(("Loss/denoise_mse", self.last_denoise_loss))
-        for option in self._scalar_order:      # Loss/mirror; Loss/smooth_temporal, Loss/smooth_spatial; Loss/rnd, Rnd/*; Policy/value_norm_mean, Policy/value_norm_std
+        for option in self._scalar_order:      # Loss/mirror; Loss/smooth_temporal, Loss/smooth_spatial; Loss/rnd, Rnd/*; Policy/value_norm_mean, Policy/value_norm_std; Loss/guidance, Guidance/coef
             out += option.log_scalars()
         return out
 

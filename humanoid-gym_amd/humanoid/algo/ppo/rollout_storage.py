@@ -103,6 +103,12 @@ class RolloutStorage:
         self.rnd_states, self.rnd_target = z(T + 1, N, int(num_states)), z(T + 1, N, int(num_outputs))
         self.rnd_pred, self.rnd_error, self.rnd_intrinsic = z(T, N, int(num_outputs)), z(T, N), z(T, N)
 
+    def enable_guidance(self, num_actions):
+        """Native extension (PPO.guidance): teacher_mu (T + 1, N, A) -- the frozen teacher's mean of every stored observation row, one row
+        per row of the observation column (slot T's are never read); filled by Guidance.teacher_pass at the end of compute_returns."""
+        T, N = self.num_transitions_per_env, self.num_envs
+        self.teacher_mu = torch.zeros(T + 1, N, int(num_actions), dtype=torch.float32, device=self.device)
+
     def enable_shadow(self, ld_obs, ld_priv):
         """Native extension: allocate (T, N, ld) bfloat16 copies of `observations` / `privileged_observations` (ld = the widths
         padded to 128, zero pad columns).  Slot s counts as valid once a policy launch has written it (shadow_slot)."""

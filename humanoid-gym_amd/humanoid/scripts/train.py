@@ -39,7 +39,13 @@ the policy's mean (PPO.smoothness), the spatial term's noi
 actor head; with HGYM_SYMMETRY=1 the pair is refused.
 
 HGYM_VALUE_NORM=1 sets `algorithm.value_normalization` the same way: the value targets standardised by running statistics of the returns, the
-critic in normalised units (PPO.value_normalization); checkpoints carry value_norm_state_dict.  Unset: off."""
+critic in normalised units (PPO.value_normalization); checkpoints carry value_norm_state_dict.  Unset: off.
+
+HGYM_GUIDE_TEACHER=<model_*.pt> with HGYM_GUIDE=<coef>[,<final_step>] sets `algorithm.guidance_cfg = {"teacher": <path>, "coef": <coef>}` the
+same way, with a final step also `"coef_schedule": {"mode": "linear", "initial_step": 0, "final_step": <final_step>, "final_value": 0}`: a
+frozen teacher's cloning term inside the PPO loss, coef / (B A) sum (mu - mu_teacher)^2, its coefficient formed on the device and, with a
+final step, decaying linearly to 0 over that many learning iterations, after which the update is the plain one again (PPO.guidance, DESIGN.md
+section 33); checkpoints carry guidance_state_dict, so --resume needs no teacher file.  Both unset: off; exactly one set: ValueError."""
 import os
 import sys
 
@@ -50,7 +56,23 @@ from humanoid.utils import get_args, task_registry  # noqa: E402
 from humanoid.utils.helpers import init_distributed  # noqa: E402
 
 
+def guidance_cfg_from_env(environ):
+    """HGYM_GUIDE_TEACHER / HGYM_GUIDE -> `algorithm.guidance_cfg`, or None when both are unset.  Exactly one set: guidance was asked for
+    and cannot run -- ValueError, not a silently unguided run."""
+    teacher, spec = environ.get("HGYM_GUIDE_TEACHER"), environ.get("HGYM_GUIDE")
+    if bool(teacher) != bool(spec):
+        raise ValueError("HGYM_GUIDE_TEACHER=%r and HGYM_GUIDE=%r: guidance needs both (a teacher checkpoint and <coef>[,<final_step>])" % (teacher, spec))
+    if not teacher:
+        return None
+    g = spec.split(",")
+    gc = {"teacher": teacher, "coef": float(g[0])}
+    if len(g) > 1:
+        gc["coef_schedule"] = {"mode": "linear", "initial_step": 0, "final_step": int(g[1]), "final_value": 0.0}
+    return gc
+
+
 def train(args):
+    guidance_cfg_from_env(os.environ)      # (a half-set pair is refused before anything is built)
     rank, world = init_distributed(args)
     env, env_cfg = task_registry.make_env(name=args.task, args=args)
     if os.environ.get("HGYM_EXACT_RESUME", "0") == "1":
@@ -74,6 +96,9 @@ def train(args):
         task_registry.get_cfgs(args.task)[1].algorithm.smoothness_cfg = {"temporal_coef": lam[0], "spatial_coef": lam[1] if len(lam) > 1 else 0.0}
     if os.environ.get("HGYM_VALUE_NORM", "0") == "1":
         task_registry.get_cfgs(args.task)[1].algorithm.value_normalization = True
+    gc = guidance_cfg_from_env(os.environ)
+    if gc is not None:
+        task_registry.get_cfgs(args.task)[1].algorithm.guidance_cfg = gc
     ppo_runner, train_cfg = task_registry.make_alg_runner(env=env, name=args.task, args=args, **({} if rank == 0 else {"log_root": None}))
     ppo_runner.learn(num_learning_iterations=train_cfg.runner.max_iterations, init_at_random_ep_len=True)
     if os.environ.get("HGYM_TRAIN_SIGNATURE"):      # tests: a signature of this rank's final parameters (replicas must agree bit for bit)

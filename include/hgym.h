@@ -77,7 +77,9 @@ extern "C" {
                              *    (same version, later: hgym_value_denormalize, hgym_value_norm_merge, hgym_value_normalize -- value targets
                              *    standardised by running statistics; no layout changes)
                              *    (same version, later: hgym_ppo_grad_smooth_mirror -- the mirror loss and the smoothness regulariser in one
-                             *    actor head; no layout changes) */
+                             *    actor head; no layout changes)
+                             *    (same version, later: hgym_guide_schedule, hgym_ppo_grad_guide, HgymGuideSchedule and HgymGuide -- a frozen
+                             *    teacher's cloning term with a device-resident coefficient; no layout changes) */
 
 enum {
     HGYM_OK = 0,
@@ -1121,6 +1123,52 @@ int32_t hgym_ppo_grad_smooth(const HgymNetConfig* cfg, const HgymPPOConfig* ppo,
  *   head_partials; ppo->world_size > 1.  HgymNet.norm is served as by the two single-option calls. */
 int32_t hgym_ppo_grad_smooth_mirror(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const HgymNet* net, const HgymBatch* batch,
                                     const HgymSmooth* smooth, float* head_partials, int64_t head_partials_len, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Guidance by a frozen teacher (header v9, no layout change): a cloning term inside the PPO loss whose coefficient
+ * decays (kickstarting, Schmitt et al. 2018, with the squared error of the means in place of a KL).  With B rows, A actions, r_b = idx[b]
+ * and mu_b = mu(obs[r_b]) as the update computes it:
+ *   t_b   = teacher_mu[r_b]                                  the frozen teacher's mean, formed by the caller for every stored row
+ *   c     = *coef                                            one device float, this update's coefficient (hgym_guide_schedule)
+ *   L_g   = c / (B A) sum_b sum_j (mu_bj - t_bj)^2
+ *   d mu_b += 2 c / (B A) (mu_b - t_b)
+ * Nothing but d mu, and hence the actor's gradients, differs from hgym_ppo_grad: d std, the critic, the auxiliary head, the KL slot and the
+ * loss sums of opt_state keep their bits.
+ *
+ * hgym_guide_schedule: one launch of one thread with fixed arguments, capturable.  It reads k = *count, writes
+ *   *coef = (float) schedule(k) and then *count = k + 1.  schedule(k), in fp64, left to right, rounded to fp32 once:
+ *     HGYM_GUIDE_CONSTANT  coef
+ *     HGYM_GUIDE_STEP      k < final_step ? coef : final_value
+ *     HGYM_GUIDE_LINEAR    k <= initial_step ? coef : k >= final_step ? final_value
+ *                          : coef + (final_value - coef) * (double)(k - initial_step) / (double)(final_step - initial_step)
+ *   HGYM_E_BADARG with nothing launched: a NULL or misaligned pointer (count 8 bytes, coef 4), an unknown mode, a negative, NaN or
+ *   infinite coef / final_value, a negative step, LINEAR with final_step <= initial_step.
+ * hgym_ppo_grad_guide: hgym_ppo_grad's launches with the actor's loss head replaced (fused path: the actor's tiles through kernels of
+ *   their own, which stage the tile's 64 target rows in LDS where there is room; layer-by-layer path: one kernel behind the loss head),
+ *   then one workgroup that adds the per-tile squared errors in a fixed order.  The coefficient is read from the device by the head, so
+ *   a captured call follows a coefficient that changes.  With *coef == 0.0 every gradient has hgym_ppo_grad's value.
+ *   HGYM_E_BADARG with nothing launched: a NULL guide, teacher_mu, coef or sums; teacher_mu not 16-byte aligned (coef 4, sums 8);
+ *   ppo->mirror_coef > 0 (separate heads); ppo->world_size > 1.  HgymNet.norm is served as by hgym_ppo_grad. */
+#define HGYM_GUIDE_CONSTANT 0
+#define HGYM_GUIDE_STEP 1
+#define HGYM_GUIDE_LINEAR 2
+typedef struct HgymGuideSchedule {
+    double coef;              /* >= 0, finite: the coefficient up to initial_step (LINEAR), below final_step (STEP), always (CONSTANT) */
+    double final_value;       /* >= 0, finite: the coefficient from final_step on (STEP, LINEAR) */
+    int64_t initial_step;     /* LINEAR: the last update count at `coef` */
+    int64_t final_step;       /* STEP, LINEAR: the first update count at final_value */
+    int32_t mode;             /* HGYM_GUIDE_CONSTANT / HGYM_GUIDE_STEP / HGYM_GUIDE_LINEAR */
+    int32_t reserved;         /* 0 */
+} HgymGuideSchedule;
+typedef struct HgymGuide {
+    const float* teacher_mu;  /* (batch->num_rows, num_actions) fp32, 16-byte aligned: the teacher's mean of every stored row, gathered
+                                 through batch->idx like every other loss input */
+    const float* coef;        /* one device float: this update's coefficient, >= 0 */
+    double* sums;             /* two device doubles the caller zeroes: [0] += sum_b |mu_b - t_b|^2 / (B A), [1] += 1 */
+} HgymGuide;
+int32_t hgym_guide_schedule(const HgymGuideSchedule* sched, int64_t* count, float* coef, void* stream);
+int32_t hgym_ppo_grad_guide(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const HgymNet* net, const HgymBatch* batch,
+                            const HgymGuide* guide, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Diagnostics of an update (header v9, no layout change): what the update did to the policy, measured on the rows it trained on.
