@@ -3,6 +3,7 @@
 // 64 rows x 16) and tile body (first hidden width 256 / 512 / 768, the auxiliary head's wide head).  Host code reaches them through
 // launch_mlp_fwd_act only.
 #include "hgym_fused.hpp"
+#include "hgym_loss.hpp"      // (the declaration of what this file defines for hgym_net.hip)
 
 namespace hgym {
 

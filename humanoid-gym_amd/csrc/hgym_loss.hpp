@@ -356,4 +356,28 @@ __global__ __launch_bounds__(THREADS) void bc_scalars_kernel(const BcScalArgs a)
     }
 }
 
+// ------------------------------------------------------------------------------------------------ launchers of other translation units
+// What hgym_net.hip calls of the files that hold kernels of their own; each of them includes this header, so a drifting signature fails to compile there.
+// hgym_update.hip, hgym_update_act.hip: the update's tiles from net `first` on (ELU(1); any resolved activation)
+int32_t launch_mlp_fb(const FwdArgs& fb, const FbLoss& fl, bool shadow, bool unclipped, int tiles, int nets, size_t lds, hipStream_t s);
+int32_t launch_mlp_fb_act(const FwdArgs& fb, const FbLoss& fl, bool shadow, bool unclipped, int tiles, int nets, hipStream_t s, int first);
+// hgym_fwd_act.hip: the fused forward with any resolved activation
+int32_t launch_mlp_fwd_act(const FwdArgs& a, int nets, bool wide, int64_t dbg_tiles, hipStream_t s);
+// hgym_loss_mirror.hip: ppo_loss_kernel<.., ML = true>
+int32_t launch_ppo_loss_mirror(const LossArgs& a, bool bf16, bool unclipped, int nblocks, hipStream_t s);
+// hgym_update_bc.hip: the small kernels of hgym_bc_grad
+int32_t launch_bc_loss(const BcLossArgs& a, bool bf16, int nblocks, hipStream_t s);
+int32_t launch_bc_scalars(const BcScalArgs& a, hipStream_t s);
+// hgym_loss_smooth.hip, hgym_smooth.hip: the layer-by-layer head with the smoothness regulariser, the spatial pre-pass's perturbed rows, the sums
+int32_t launch_ppo_loss_smooth(const LossArgs& a, const LossSmooth& sm, bool bf16, int nblocks, hipStream_t s);
+int32_t launch_perturb_rows(int64_t M, int width, const float* src, int64_t ld_src, const int64_t* idx, const float* noise_std, uint64_t seed,
+                            const double* opt_state, float* dst, int64_t ld_dst, hipStream_t s);
+int32_t launch_smooth_sums(int nblocks, int B, int A, const float* partials, const float* weight, double* sums, hipStream_t s);
+// hgym_loss_mirror_smooth.hip: the layer-by-layer head with both at once, and the sums of the two smoothness terms from head_partials
+int32_t launch_ppo_loss_mirror_smooth(const LossArgs& a, const LossSmooth& sm, float* head_partials, bool bf16, int nblocks, hipStream_t s);
+int32_t launch_head_sums(int nblocks, int B, int A, const float* head_partials, const float* weight, double* sums, hipStream_t s);
+// hgym_guide.hip: the layer-by-layer head with the teacher's term, and the sums of its squared error
+int32_t launch_ppo_loss_guide(const LossArgs& a, const LossGuide& gd, bool bf16, int nblocks, hipStream_t s);
+int32_t launch_guide_sums(int nblocks, int B, int A, const float* partials, double* sums, hipStream_t s);
+
 }  // namespace hgym

@@ -21,31 +21,6 @@
 
 namespace hgym {
 
-// hgym_update.hip
-int32_t launch_mlp_fb(const FwdArgs& fb, const FbLoss& fl, bool shadow, bool unclipped, int tiles, int nets, size_t lds, hipStream_t s);
-// hgym_update_act.hip, hgym_fwd_act.hip: the same tiles with any resolved activation, one launch per net
-int32_t launch_mlp_fb_act(const FwdArgs& fb, const FbLoss& fl, bool shadow, bool unclipped, int tiles, int nets, hipStream_t s, int first);
-// (the actor's tiles with a head of their own -- mirror loss, smoothness regulariser, behaviour cloning: launch_mlp_fb_head, hgym_fused.hpp)
-// hgym_loss_mirror.hip: ppo_loss_kernel<.., ML = true>, the layer-by-layer path's loss with the mirror loss
-int32_t launch_ppo_loss_mirror(const LossArgs& a, bool bf16, bool unclipped, int nblocks, hipStream_t s);
-int32_t launch_mlp_fwd_act(const FwdArgs& a, int nets, bool wide, int64_t dbg_tiles, hipStream_t s);
-// hgym_update_bc.hip: the small kernels of hgym_bc_grad
-int32_t launch_bc_loss(const BcLossArgs& a, bool bf16, int nblocks, hipStream_t s);
-int32_t launch_bc_scalars(const BcScalArgs& a, hipStream_t s);
-// hgym_loss_smooth.hip, hgym_smooth.hip: hgym_ppo_grad_smooth's kernels -- the layer-by-layer head with the smoothness regulariser, the
-// perturbed rows of the spatial pre-pass, the minibatch's sums
-int32_t launch_ppo_loss_smooth(const LossArgs& a, const LossSmooth& sm, bool bf16, int nblocks, hipStream_t s);
-int32_t launch_perturb_rows(int64_t M, int width, const float* src, int64_t ld_src, const int64_t* idx, const float* noise_std, uint64_t seed,
-                            const double* opt_state, float* dst, int64_t ld_dst, hipStream_t s);
-int32_t launch_smooth_sums(int nblocks, int B, int A, const float* partials, const float* weight, double* sums, hipStream_t s);
-// hgym_loss_mirror_smooth.hip: hgym_ppo_grad_smooth_mirror's small kernels -- the layer-by-layer head with the mirror loss and the smoothness
-// regulariser at once, and the sums of the two smoothness terms from head_partials
-int32_t launch_ppo_loss_mirror_smooth(const LossArgs& a, const LossSmooth& sm, float* head_partials, bool bf16, int nblocks, hipStream_t s);
-int32_t launch_head_sums(int nblocks, int B, int A, const float* head_partials, const float* weight, double* sums, hipStream_t s);
-// hgym_guide.hip: hgym_ppo_grad_guide's small kernels -- the layer-by-layer head with the teacher's term, and the sums of its squared error
-int32_t launch_ppo_loss_guide(const LossArgs& a, const LossGuide& gd, bool bf16, int nblocks, hipStream_t s);
-int32_t launch_guide_sums(int nblocks, int B, int A, const float* partials, double* sums, hipStream_t s);
-
 // ------------------------------------------------------------------------------------------------ layouts
 struct LayerLayout {
     int K, N;                // in, out features
@@ -923,6 +898,64 @@ static int32_t smooth_prepass(R& r, const HgymBatch& b, const HgymSmooth& sm) {
 }
 inline bool smooth_on(const HgymSmooth* sm) { return sm && (sm->temporal_coef > 0.0f || sm->spatial_coef > 0.0f); }
 
+// The actor's head of one hgym_ppo_grad* call: what joins d mu beside the PPO term, resolved once (actor_head) for both runners.
+//   sm (hgym_ppo_grad_smooth): the smoothness regulariser joins d mu; null or both coefficients 0: off, the launches of hgym_ppo_grad
+//   hp (hgym_ppo_grad_smooth_mirror): head_partials, carried only when the mirror loss and the regulariser are both on
+//   gd (hgym_ppo_grad_guide): the teacher's term joins d mu; never together with the mirror loss or sm
+struct ActorHead {
+    enum Kind { PLAIN, MIRROR, SMOOTH, MIRROR_SMOOTH, GUIDE } kind;      // (a pointer or a scale that the kind does not use stays null / 0)
+    const HgymSmooth* sm;
+    float* hp;
+    const HgymGuide* gd;
+    float m_g;               // 2 * mirror_coef / (B * A)
+    float gT, gS;            // 2 * temporal_coef / (B * A), 2 * spatial_coef / (B * A)
+    float inv2;              // the guide's 2 / (B * A)
+    bool mirror() const { return kind == MIRROR || kind == MIRROR_SMOOTH; }
+    bool smooth() const { return kind == SMOOTH || kind == MIRROR_SMOOTH; }
+};
+
+// The scales are fp32 kernel arguments: each is formed by the one expression, in the one operation order, it always had.
+static ActorHead actor_head(const HgymPPOConfig& ppo, int B, int A, const HgymSmooth* sm, float* hp, const HgymGuide* gd) {
+    const bool mirror = ppo.mirror_coef > 0.0f, smooth = smooth_on(sm);
+    // (gd arrives only with both off: hgym_ppo_grad_guide refuses the mirror loss and hands over no HgymSmooth)
+    const bool guide = gd && !mirror && !smooth;
+    const ActorHead::Kind kind = mirror ? (smooth ? ActorHead::MIRROR_SMOOTH : ActorHead::MIRROR) : (smooth ? ActorHead::SMOOTH : (guide ? ActorHead::GUIDE : ActorHead::PLAIN));
+    ActorHead h = {kind, smooth ? sm : nullptr, mirror && smooth ? hp : nullptr, guide ? gd : nullptr, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (mirror) h.m_g = 2.0f * ppo.mirror_coef / ((float)B * (float)A);
+    if (smooth) {
+        const float gs = 2.0f / ((float)B * (float)A);
+        h.gT = gs * sm->temporal_coef;
+        h.gS = gs * sm->spatial_coef;
+    }
+    if (guide) h.inv2 = 2.0f / ((float)B * (float)A);
+    return h;
+}
+
+// The head's pre-passes on either path, ahead of everything else of the call: the smoothness regulariser's first (hgym_ppo_grad_smooth_mirror's order;
+// alone, either is the only one), then the mirror loss's -- the raw mu of the partner rows under the current parameters, forward only (no gradient
+// through the target).  On the fused path it gathers the fp32 rows, not their bf16 shadow: the forward tiles that gather by index from a shadow
+// exist in the update kernels only, and the shadow is bf16(fp32 row) exactly -- the same bits reach the first layer either way.
+template <class R>
+static int32_t head_prepass(R& r, const HgymBatch& b, const ActorHead& h) {
+    if (h.smooth()) {
+        const int32_t rc = smooth_prepass(r, b, *h.sm);
+        if (rc) return rc;
+    }
+    if (h.mirror()) return r.forward(0, b.B, b.obs, r.cfg.num_obs, b.pair_idx, b.mirror_target, r.cfg.num_actions, false);
+    return HGYM_OK;
+}
+
+// Behind the head's launch on either path: the sums of the head's own squared errors from the n partial rows it left (n: the fused path's tiles,
+// the layer-by-layer path's loss blocks).  The mirror loss alone has none: its sum rides with the loss scalars (ScalArgs::mirror_sums).
+static int32_t head_sums(const ActorHead& h, int n, int B, int A, const float* partials, hipStream_t s) {
+    switch (h.kind) {
+    case ActorHead::MIRROR_SMOOTH: return launch_head_sums(n, B, A, h.hp, h.sm->next_weight, h.sm->sums, s);
+    case ActorHead::SMOOTH: return launch_smooth_sums(n, B, A, partials, h.sm->next_weight, h.sm->sums, s);
+    case ActorHead::GUIDE: return launch_guide_sums(n, B, A, partials, h.gd->sums, s);
+    default: return HGYM_OK;
+    }
+}
+
 // The layer-by-layer path: every dense product through gemm_nt_kernel in the operand precision T, plus the packs, transposes and
 // row sums around it.
 template <typename T>
@@ -1048,29 +1081,18 @@ struct GemmPath : NetBase {
         return backward(2, B);
     }
 
+    static LossSmooth loss_smooth(const ActorHead& h) { return {h.sm->target_next, h.sm->target_near, h.sm->next_weight, h.gT, h.gS}; }
+
     // part 1 (the second half of hgym_ppo_grad_part) has nothing left to do: part 0 does everything (the caller's first bucket goes out
     // complete, just later)
-    // sm (hgym_ppo_grad_smooth): the smoothness regulariser joins d mu; null or both coefficients 0: off, the launches of hgym_ppo_grad
-    // hp (hgym_ppo_grad_smooth_mirror): head_partials, named only when the mirror loss and the regulariser are both on
-    // gd (hgym_ppo_grad_guide): the teacher's term joins d mu; never together with the mirror loss or sm
-    int32_t grad(const HgymPPOConfig& ppo, const HgymBatch& b, int part, const HgymSmooth* sm = nullptr, float* hp = nullptr,
-                 const HgymGuide* gd = nullptr) {
+    int32_t grad(const HgymPPOConfig& ppo, const HgymBatch& b, int part, const ActorHead& h) {
         if (part == 1) return HGYM_OK;
         const int B = b.B, A = cfg.num_actions;
         float* mu = at<float>(w.net[0].out_f32);
         float* val = at<float>(w.net[1].out_f32);
         // (no zeroing of net.grads: ppo_scalars_kernel writes std's gradient, reduce_slabs_kernel every weight and bias segment)
-        const bool mirror = ppo.mirror_coef > 0.0f;
-        const bool smooth = smooth_on(sm);
-        int32_t rc = HGYM_OK;
-        if (smooth) {
-            rc = smooth_prepass(*this, b, *sm);
-            if (rc) return rc;
-        }
-        if (mirror) {     // the pre-pass: the partner rows' raw mu under the current parameters (forward only: no gradient through the target)
-            rc = forward(0, B, b.obs, cfg.num_obs, b.pair_idx, b.mirror_target, A, false);
-            if (rc) return rc;
-        }
+        int32_t rc = head_prepass(*this, b, h);
+        if (rc) return rc;
         rc = forward(0, B, b.obs, cfg.num_obs, b.idx, mu, A, true);
         if (rc) return rc;
         rc = forward(1, B, b.priv, cfg.num_priv, b.idx, val, 1, true);
@@ -1079,7 +1101,7 @@ struct GemmPath : NetBase {
         const int nblocks = ceil_div(Bp, 256);
         HG_REQUIRE(nblocks <= MAX_LOSS_BLOCKS, HGYM_E_UNSUPPORTED, "minibatch %d too large for the loss partial buffer", B);
         // (head_partials holds 4 floats per 64 rows, a loss block covers 256 of the padded rows)
-        HG_REQUIRE(!hp || nblocks <= (B + 63) / 64, HGYM_E_UNSUPPORTED, "%d loss blocks for B=%d: more than head_partials holds", nblocks, B);
+        HG_REQUIRE(!h.hp || nblocks <= (B + 63) / 64, HGYM_E_UNSUPPORTED, "%d loss blocks for B=%d: more than head_partials holds", nblocks, B);
         const LayerLayout& la = w.net[0].layer[w.net[0].L - 1];
         const LayerLayout& lc = w.net[1].layer[w.net[1].L - 1];
         LossArgs a;
@@ -1101,48 +1123,34 @@ struct GemmPath : NetBase {
         a.dvalT = at<T>(lc.dYT);
         a.Bp = Bp;
         a.partials = at<float>(w.partials);
-        if (mirror) {
+        if (h.mirror()) {
             a.mt = b.mirror_target;
             a.m_src = b.mirror_act_src;
             a.m_sign = b.mirror_act_sign;
-            a.m_g = 2.0f * ppo.mirror_coef / ((float)B * (float)A);
+            a.m_g = h.m_g;
         }
+        const bool bf16 = sizeof(T) == 2, unclipped = ppo.value_loss_unclipped != 0;
         prof_begin(HGYM_PROF_LOSS, s);
-        if (ppo.value_loss_unclipped) hipLaunchKernelGGL((ppo_loss_kernel<T, true>), dim3(nblocks), dim3(256), 0, s, a);
+        if (unclipped) hipLaunchKernelGGL((ppo_loss_kernel<T, true>), dim3(nblocks), dim3(256), 0, s, a);
         else hipLaunchKernelGGL((ppo_loss_kernel<T>), dim3(nblocks), dim3(256), 0, s, a);
-        if (mirror && smooth) {      // behind it: d mu with all three terms, the LP_DBIAS_MU / LP_MIRROR partials, head_partials, then the sums
-            const float gs = 2.0f / ((float)B * (float)A);
-            const LossSmooth ls = {sm->target_next, sm->target_near, sm->next_weight, gs * sm->temporal_coef, gs * sm->spatial_coef};
-            if (sizeof(T) == 4) {      // fp32: the first two terms of d mu and LP_MIRROR are the mirror kernel's own, to the bit (hgym_loss_mirror_smooth.hip)
-                const int32_t rc_ml = launch_ppo_loss_mirror(a, false, ppo.value_loss_unclipped != 0, nblocks, s);
-                if (rc_ml) return rc_ml;
-            }
-            int32_t rc_ms = launch_ppo_loss_mirror_smooth(a, ls, hp, sizeof(T) == 2, nblocks, s);
-            if (rc_ms) return rc_ms;
-            rc_ms = launch_head_sums(nblocks, B, A, hp, sm->next_weight, sm->sums, s);
-            if (rc_ms) return rc_ms;
-        } else if (mirror) {      // behind it: d mu with the term, the LP_DBIAS_MU / LP_MIRROR partials (hgym_loss.hpp)
-            const int32_t rc_ml = launch_ppo_loss_mirror(a, sizeof(T) == 2, ppo.value_loss_unclipped != 0, nblocks, s);
-            if (rc_ml) return rc_ml;
-        } else if (smooth) {      // behind it: d mu with the two terms, the LP_DBIAS_MU / LP_SMOOTH_* partials (hgym_loss.hpp), then the sums
-            const float gs = 2.0f / ((float)B * (float)A);
-            const LossSmooth ls = {sm->target_next, sm->target_near, sm->next_weight, gs * sm->temporal_coef, gs * sm->spatial_coef};
-            int32_t rc_sm = launch_ppo_loss_smooth(a, ls, sizeof(T) == 2, nblocks, s);
-            if (rc_sm) return rc_sm;
-            rc_sm = launch_smooth_sums(nblocks, B, A, at<float>(w.partials), sm->next_weight, sm->sums, s);
-            if (rc_sm) return rc_sm;
-        } else if (gd) {          // behind it: d mu with the teacher's term, the LP_DBIAS_MU / LP_MIRROR partials (hgym_guide.hip), then the sums
-            const LossGuide lg = {gd->teacher_mu, gd->coef, 2.0f / ((float)B * (float)A)};
-            int32_t rc_gd = launch_ppo_loss_guide(a, lg, sizeof(T) == 2, nblocks, s);
-            if (rc_gd) return rc_gd;
-            rc_gd = launch_guide_sums(nblocks, B, A, at<float>(w.partials), gd->sums, s);
-            if (rc_gd) return rc_gd;
+        // behind it, the head's own kernel -- d mu with the head's terms, the LP_DBIAS_MU partials and the head's squared-error partials --, then its sums
+        switch (h.kind) {
+        case ActorHead::MIRROR_SMOOTH:      // fp32: the first two terms of d mu and LP_MIRROR are the mirror kernel's own, to the bit (hgym_loss_mirror_smooth.hip)
+            if (!bf16) rc = launch_ppo_loss_mirror(a, false, unclipped, nblocks, s);
+            if (!rc) rc = launch_ppo_loss_mirror_smooth(a, loss_smooth(h), h.hp, bf16, nblocks, s);
+            break;
+        case ActorHead::MIRROR: rc = launch_ppo_loss_mirror(a, bf16, unclipped, nblocks, s); break;
+        case ActorHead::SMOOTH: rc = launch_ppo_loss_smooth(a, loss_smooth(h), bf16, nblocks, s); break;
+        case ActorHead::GUIDE: rc = launch_ppo_loss_guide(a, LossGuide{h.gd->teacher_mu, h.gd->coef, h.inv2}, bf16, nblocks, s); break;
+        case ActorHead::PLAIN: break;
         }
-        prof_end(HGYM_PROF_LOSS, s, (double)B * (4.0 * (5 * A + 6) + (double)sizeof(T) * (2 * A + 2)));
+        if (!rc) rc = head_sums(h, nblocks, B, A, at<float>(w.partials), s);
+        prof_end(HGYM_PROF_LOSS, s, (double)B * (4.0 * (5 * A + 6) + (double)sizeof(T) * (2 * A + 2)));      // (before the error return, as in bc_grad)
+        if (rc) return rc;
         HG_CHECK_LAUNCH("ppo_loss_kernel");
         ScalArgs sc = {nblocks, B, A, 0, at<float>(w.partials), net.grads, nullptr, nullptr, net.grads + w.P, net.opt_state,
                        (double)ppo.beta1, (double)ppo.beta2, 0, 0, 0.0f, 0.0, 0.0, 1, grad_sigma()};
-        if (mirror) sc.mirror_sums = b.mirror_sums;      // (else null: off)
+        if (h.mirror()) sc.mirror_sums = b.mirror_sums;      // (else null: off)
         hipLaunchKernelGGL(ppo_scalars_kernel, dim3(1), dim3(512), 0, s, sc);
         HG_CHECK_LAUNCH("ppo_scalars_kernel");
         rc = backward(0, B);
@@ -1486,13 +1494,23 @@ struct FusedPath : NetBase {
                                   : launch_mlp_fb_head<true, Head>(u.fb, u.fl, head, u.shadow, u.tiles, s);
     }
 
+    // the head records of the mirror loss and of the smoothness regulariser (`stage` is the launch's to set)
+    static FbMirror fb_mirror(const HgymBatch& b, const ActorHead& h) { return {b.mirror_target, b.mirror_act_src, b.mirror_act_sign, h.m_g, 0}; }
+    static FbSmooth fb_smooth(const ActorHead& h) { return {h.sm->target_next, h.sm->target_near, h.sm->next_weight, h.gT, h.gS, 0}; }
+
+    // the tiles of nets [first, nets) through the kernels every net always had
+    int32_t launch_rest(const UpdateTiles& u, bool unclipped, int nets, int first) {
+        if (!act_is_elu1(w.act)) return launch_mlp_fb_act(u.fb, u.fl, u.shadow, unclipped, u.tiles, nets, s, first);
+        FwdArgs rest = u.fb;      // (hgym_update.hip: the kernel's own code object)
+        rest.net0 = first;
+        rest.nets = nets - first;
+        if (rest.dbg) rest.dbg += (int64_t)first * u.tiles * 8;      // phase stamps: behind the actor's slots
+        return launch_mlp_fb(rest, u.fl, u.shadow, unclipped, u.tiles, nets - first, u.lds, s);
+    }
+
     // part < 0: the whole minibatch gradient.  part 0 / 1: the two halves of hgym_ppo_grad_part -- 0 leaves std's and the actor's
     // gradient final, 1 the critic's, the auxiliary head's and the KL slot.
-    // sm (hgym_ppo_grad_smooth): the smoothness regulariser joins d mu; null or both coefficients 0: off, the launches of hgym_ppo_grad
-    // hp (hgym_ppo_grad_smooth_mirror): head_partials, named only when the mirror loss and the regulariser are both on
-    // gd (hgym_ppo_grad_guide): the teacher's term joins d mu; never together with the mirror loss or sm
-    int32_t grad(const HgymPPOConfig& ppo, const HgymBatch& b, int part, const HgymSmooth* sm = nullptr, float* hp = nullptr,
-                 const HgymGuide* gd = nullptr) {
+    int32_t grad(const HgymPPOConfig& ppo, const HgymBatch& b, int part, const ActorHead& h) {
         const int B = b.B, A = cfg.num_actions;
         const int64_t critic_off = w.net[1].layer[0].w_off;
         const int Mp = (int)round_up(B, w.SE);
@@ -1504,19 +1522,8 @@ struct FusedPath : NetBase {
         UpdateTiles u;
         const int32_t rc_plan = plan_tiles(b, nets, &u);
         if (rc_plan) return rc_plan;
-        const bool mirror = ppo.mirror_coef > 0.0f;
-        const bool smooth = smooth_on(sm);
-        if (smooth) {      // (ahead of the mirror loss's pre-pass: hgym_ppo_grad_smooth_mirror's order; alone, either is the only one)
-            const int32_t rc_pre = smooth_prepass(*this, b, *sm);
-            if (rc_pre) return rc_pre;
-        }
-        if (mirror) {
-            // the mirror loss's pre-pass: the raw mu of the partner rows under the current parameters, forward only (no gradient through
-            // the target).  It gathers the fp32 rows, not their bf16 shadow: the forward tiles that gather by index from a shadow exist in
-            // the update kernels only, and the shadow is bf16(fp32 row) exactly -- the same bits reach the first layer either way.
-            const int32_t rc_pre = forward(0, B, b.obs, cfg.num_obs, b.pair_idx, b.mirror_target, A, false);
-            if (rc_pre) return rc_pre;
-        }
+        const int32_t rc_pre = head_prepass(*this, b, h);
+        if (rc_pre) return rc_pre;
         {   // forward + PPO loss + dZ chain of both nets: ONE launch (hgym_fused.hpp: mlp_fb_kernel)
             const NetIO io[3] = {{b.obs, cfg.num_obs, at<float>(w.net[0].out_f32), A},
                                  {b.priv, cfg.num_priv, at<float>(w.net[1].out_f32), 1},
@@ -1538,52 +1545,21 @@ struct FusedPath : NetBase {
             fl.aux_ldt = cfg.num_priv;
             fl.aux_off = cfg.aux_target_offset;
             fl.aux_coef = ppo.aux_coef;
-            const bool unclipped = ppo.value_loss_unclipped != 0;
             prof_begin(HGYM_PROF_MLP_FWD, s);
             int32_t rc_fb = HGYM_OK;
-            int first = 0;      // the first net of the launches every net always had
-            if (mirror && smooth) {
-                // the actor's tiles through the kernels with both terms in their head, the sums of the two smoothness terms from head_partials
-                const float gs = 2.0f / ((float)B * (float)A);
-                const FbMirrorSmooth head = {{b.mirror_target, b.mirror_act_src, b.mirror_act_sign, 2.0f * ppo.mirror_coef / ((float)B * (float)A), 0},
-                                             {sm->target_next, sm->target_near, sm->next_weight, gs * sm->temporal_coef, gs * sm->spatial_coef, 0}, hp, 0};
-                rc_fb = launch_actor_head(u, head);
-                if (rc_fb) return rc_fb;
-                rc_fb = launch_head_sums(u.tiles, B, A, hp, sm->next_weight, sm->sums, s);
-                first = 1;
-            } else if (mirror) {
-                // the actor's tiles through the kernels with the mirror loss in their head (their own launch), the rest from net 1 on
-                const FbMirror head = {b.mirror_target, b.mirror_act_src, b.mirror_act_sign, 2.0f * ppo.mirror_coef / ((float)B * (float)A), 0};
-                rc_fb = launch_actor_head(u, head);
-                first = 1;
-            } else if (smooth) {
-                // the same with the smoothness regulariser, and the sums of its two terms
-                const float gs = 2.0f / ((float)B * (float)A);
-                const FbSmooth head = {sm->target_next, sm->target_near, sm->next_weight, gs * sm->temporal_coef, gs * sm->spatial_coef, 0};
-                rc_fb = launch_actor_head(u, head);
-                if (rc_fb) return rc_fb;
-                rc_fb = launch_smooth_sums(u.tiles, B, A, at<float>(w.partials), sm->next_weight, sm->sums, s);
-                first = 1;
-            } else if (gd) {
-                // the same with the teacher's term (the coefficient is read on the device), and the sums of its squared error
-                const FbGuide head = {gd->teacher_mu, gd->coef, 2.0f / ((float)B * (float)A), 0};
-                rc_fb = launch_actor_head(u, head);
-                if (rc_fb) return rc_fb;
-                rc_fb = launch_guide_sums(u.tiles, B, A, at<float>(w.partials), gd->sums, s);
-                first = 1;
+            // a head of the actor's own: the actor's tiles through the kernels with it in their head (their own launch), then its sums, the rest from net 1 on
+            switch (h.kind) {
+            case ActorHead::MIRROR_SMOOTH: rc_fb = launch_actor_head(u, FbMirrorSmooth{fb_mirror(b, h), fb_smooth(h), h.hp, 0}); break;
+            case ActorHead::MIRROR: rc_fb = launch_actor_head(u, fb_mirror(b, h)); break;
+            case ActorHead::SMOOTH: rc_fb = launch_actor_head(u, fb_smooth(h)); break;
+            case ActorHead::GUIDE: rc_fb = launch_actor_head(u, FbGuide{h.gd->teacher_mu, h.gd->coef, h.inv2, 0}); break;      // (the coefficient is read on the device)
+            case ActorHead::PLAIN: break;
             }
+            if (!rc_fb) rc_fb = head_sums(h, u.tiles, B, A, at<float>(w.partials), s);
+            const int first = h.kind != ActorHead::PLAIN;      // the first net of the launches every net always had
+            if (!rc_fb) rc_fb = launch_rest(u, ppo.value_loss_unclipped != 0, nets, first);
+            prof_end(HGYM_PROF_MLP_FWD, s, tile_flops(nets, B));      // (before the error return, as in bc_grad)
             if (rc_fb) return rc_fb;
-            if (act_is_elu1(w.act)) {      // (hgym_update.hip: the kernel's own code object)
-                FwdArgs rest = u.fb;
-                rest.net0 = first;
-                rest.nets = nets - first;
-                if (rest.dbg) rest.dbg += (int64_t)first * u.tiles * 8;      // phase stamps: behind the actor's slots
-                rc_fb = launch_mlp_fb(rest, fl, u.shadow, unclipped, u.tiles, nets - first, u.lds, s);
-            } else {
-                rc_fb = launch_mlp_fb_act(u.fb, fl, u.shadow, unclipped, u.tiles, nets, s, first);
-            }
-            if (rc_fb) return rc_fb;
-            prof_end(HGYM_PROF_MLP_FWD, s, tile_flops(nets, B));
             HG_CHECK_LAUNCH("mlp_fb_kernel");
         }
         // the minibatch's loss scalars (per-tile partials -> opt_state, std / head-bias gradients, KL slot): one extra workgroup of
@@ -1592,7 +1568,7 @@ struct FusedPath : NetBase {
                              net.grads + w.net[0].layer[3].b_off, net.grads + w.net[1].layer[3].b_off, net.grads + w.P, net.opt_state,
                              (double)ppo.beta1, (double)ppo.beta2, prologue_in_grad(ppo) ? 1 : 0, ppo.adaptive_lr, ppo.desired_kl, ppo.lr_min,
                              ppo.lr_max, 1, grad_sigma()};
-        if (mirror) sc.mirror_sums = b.mirror_sums;      // (else null: off)
+        if (h.mirror()) sc.mirror_sums = b.mirror_sums;      // (else null: off)
         int32_t rc = dw(nets, B, sc, u.shadow ? &b : nullptr);
         if (rc) return rc;
         if (w.nnets > 2 && nets == 2) {
@@ -1896,24 +1872,22 @@ int32_t hgym_policy_act_fin(const HgymNetConfig* cfg, const HgymNet* net, int32_
 }
 
 // Behind hgym_ppo_grad, hgym_ppo_grad_part, hgym_ppo_grad_smooth, hgym_ppo_grad_smooth_mirror and hgym_ppo_grad_guide: the checks they
-// share, in one order, then the runner's grad.  part: null for the whole gradient, else hgym_ppo_grad_part's half; smooth: null unless
-// hgym_ppo_grad_smooth(_mirror); head_partials: null unless hgym_ppo_grad_smooth_mirror with all of its terms on; guide: null unless
-// hgym_ppo_grad_guide.
+// share, in one order, then the actor's head (struct ActorHead) and the runner's grad.  part: null for the whole gradient, else
+// hgym_ppo_grad_part's half; smooth, head_partials, guide: what the entry point has of them, else null.
 static int32_t ppo_grad_entry(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const HgymNet* net, const HgymBatch* batch,
-                              const int32_t* part, const HgymSmooth* smooth, void* stream, float* head_partials = nullptr,
-                              const HgymGuide* guide = nullptr) {
+                              const int32_t* part, const HgymSmooth* smooth, float* head_partials, const HgymGuide* guide, void* stream) {
     return run(cfg, net, stream, [&](auto& R) -> int32_t {
         int32_t rc = check_ppo(ppo);
         if (rc) return rc;
         HG_REQUIRE(!part || *part == 0 || *part == 1, HGYM_E_BADARG, "part=%d (0 or 1)", *part);
         HG_REQUIRE(net->grads && net->opt_state, HGYM_E_BADARG, "null grads / opt_state");
         rc = check_batch(R.w, ppo, batch);
-        return rc ? rc : R.grad(*ppo, *batch, part ? *part : -1, smooth, head_partials, guide);
+        return rc ? rc : R.grad(*ppo, *batch, part ? *part : -1, actor_head(*ppo, batch->B, cfg->num_actions, smooth, head_partials, guide));
     });
 }
 
 int32_t hgym_ppo_grad(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const HgymNet* net, const HgymBatch* batch, void* stream) {
-    return ppo_grad_entry(cfg, ppo, net, batch, nullptr, nullptr, stream);
+    return ppo_grad_entry(cfg, ppo, net, batch, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 // What hgym_ppo_grad_smooth and hgym_ppo_grad_smooth_mirror refuse of an HgymSmooth, the same for both (fn: the caller's name)
@@ -1949,7 +1923,7 @@ int32_t hgym_ppo_grad_smooth(const HgymNetConfig* cfg, const HgymPPOConfig* ppo,
     HG_REQUIRE(cfg && ppo && net && batch && smooth, HGYM_E_BADARG, "hgym_ppo_grad_smooth: null cfg / ppo / net / batch / smooth");
     const int32_t rc = check_smooth(ppo, smooth, "hgym_ppo_grad_smooth", true);
     if (rc) return rc;
-    return ppo_grad_entry(cfg, ppo, net, batch, nullptr, smooth, stream);
+    return ppo_grad_entry(cfg, ppo, net, batch, nullptr, smooth, nullptr, nullptr, stream);
 }
 
 int32_t hgym_ppo_grad_smooth_mirror(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const HgymNet* net, const HgymBatch* batch,
@@ -1967,7 +1941,7 @@ int32_t hgym_ppo_grad_smooth_mirror(const HgymNetConfig* cfg, const HgymPPOConfi
         HG_REQUIRE(head_partials_len >= need, HGYM_E_BADARG, "hgym_ppo_grad_smooth_mirror: head_partials_len=%lld, B=%d needs %lld floats",
                    (long long)head_partials_len, batch->B, (long long)need);
     }
-    return ppo_grad_entry(cfg, ppo, net, batch, nullptr, smooth, stream, all ? head_partials : nullptr);
+    return ppo_grad_entry(cfg, ppo, net, batch, nullptr, smooth, head_partials, nullptr, stream);
 }
 
 int32_t hgym_ppo_grad_guide(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const HgymNet* net, const HgymBatch* batch,
@@ -1979,12 +1953,12 @@ int32_t hgym_ppo_grad_guide(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, 
                "hgym_ppo_grad_guide: HgymGuide.teacher_mu must be 16-byte aligned (coef 4, sums 8)");
     HG_REQUIRE(!(ppo->mirror_coef > 0.0f), HGYM_E_BADARG, "hgym_ppo_grad_guide with HgymPPOConfig.mirror_coef > 0: the two heads do not combine");
     HG_REQUIRE(ppo->world_size <= 1, HGYM_E_BADARG, "hgym_ppo_grad_guide with world_size=%d: one rank only", ppo->world_size);
-    return ppo_grad_entry(cfg, ppo, net, batch, nullptr, nullptr, stream, nullptr, guide);
+    return ppo_grad_entry(cfg, ppo, net, batch, nullptr, nullptr, nullptr, guide, stream);
 }
 
 int32_t hgym_ppo_grad_part(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const HgymNet* net, const HgymBatch* batch, int32_t part,
                            void* stream) {
-    return ppo_grad_entry(cfg, ppo, net, batch, &part, nullptr, stream);
+    return ppo_grad_entry(cfg, ppo, net, batch, &part, nullptr, nullptr, nullptr, stream);
 }
 
 int32_t hgym_bc_grad(const HgymNetConfig* cfg, const HgymBCConfig* bc, const HgymNet* net, const HgymBatch* batch, const float* target,

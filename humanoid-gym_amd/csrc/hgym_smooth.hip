@@ -4,6 +4,7 @@
 //   smooth_sums_kernel    the minibatch's two squared-error partials and its weights -> HgymSmooth.sums, in a fixed order
 // A translation unit of its own, so that no existing device code object changes.
 #include "hgym_fused.hpp"
+#include "hgym_loss.hpp"      // (the declaration of what this file defines for hgym_net.hip)
 
 namespace hgym {
 

@@ -4,6 +4,7 @@
 // round 4: DESIGN.md section 7).  Host code reaches the kernel through launch_mlp_fb only.  This file holds the clipped value loss
 // (the default); the two kernels of the unclipped form are hgym_update_vu.hip's.
 #include "hgym_fused.hpp"
+#include "hgym_loss.hpp"      // (the declaration of what this file defines for hgym_net.hip)
 
 namespace hgym {
 

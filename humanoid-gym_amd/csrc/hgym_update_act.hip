@@ -3,6 +3,7 @@
 // (first hidden width 256 / 512 / 768, the auxiliary head) and input form (fp32 rows, bf16 shadow).  The unclipped form is
 // hgym_update_act_vu.hip's.  Host code reaches them through launch_mlp_fb_act only.
 #include "hgym_fused.hpp"
+#include "hgym_loss.hpp"      // (the declaration of what this file defines for hgym_net.hip)
 
 namespace hgym {
 
