@@ -356,6 +356,126 @@ __global__ __launch_bounds__(THREADS) void bc_scalars_kernel(const BcScalArgs a)
     }
 }
 
+// ------------------------------------------------------------------------------------------------ critic only (hgym_vf_grad, hgym_bc_vf_grad)
+// vf_loss_kernel: the value part of ppo_loss_kernel alone, the layer-by-layer path's head of a critic-only step, one thread per sample:
+// d V into the critic's last dY / dYT (the operands of the backward that follows), zero in the contraction padding, and the block's two
+// partials LP_VALUE / LP_DBIAS_V -- no other slot of the partial row is written, so a cloning head's row (LP_DBIAS_MU, LP_MIRROR) may share it.
+// vf_scalars_kernel: one workgroup that adds the partial rows of either path -- LP_VALUE and LP_DBIAS_V in ppo_scalars_block's order (16
+// interleaved fp64 sums per quantity, each of four chains combined as (s0 + s1) + (s2 + s3)), so that the critic's head bias gradient has
+// the bits hgym_ppo_grad gives it -> sums[0] += the mean value loss, sums[1] += 1, the head bias gradient (fused path), and
+// opt[HGYM_OPT_GRAD_SQNORM] = 0 unless the caller keeps what is there.  With bc_sums set it is also bc_scalars_kernel, quantity by
+// quantity in that kernel's own order: the one scalars workgroup of hgym_bc_vf_grad.  It touches no other slot of opt_state.
+struct VfLossArgs {
+    const float* val;            // [B] the critic's fp32 output
+    const float* values;         // (num_rows,) the stored old values, gathered through idx; not read by the unclipped form
+    const float* returns;        // (num_rows,)
+    const int64_t* idx;
+    int B, Bp;
+    void* dval; int64_t ld_dval; // [B][Ncp] operand type
+    void* dvalT;                 // [16][Mp]
+    float clip, value_coef;
+    float* partials;             // [gridDim.x][LOSS_PARTIALS]
+};
+struct VfScalArgs {
+    int nblocks, B, A;
+    const float* partials;
+    float* grads_bv;             // the critic's head bias gradient (fused path), null: it comes from the slabs
+    double* opt;
+    double* sums;                // the value loss's two sums
+    int keep_sqnorm;             // 1: opt[HGYM_OPT_GRAD_SQNORM] is left as found (the slab sum behind adds to it)
+    float* grads_bmu;            // with bc_sums: the actor's head bias gradient (fused path), null: it comes from the slabs
+    double* bc_sums;             // non-null: the cloning loss's two sums, as bc_scalars_kernel leaves them
+};
+
+template <typename T, bool VU>
+__global__ __launch_bounds__(256) void vf_loss_kernel(const VfLossArgs a) {
+    __shared__ float red[4][2];
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const float invB = 1.0f / (float)a.B;
+    float vl = 0.0f, d_v = 0.0f;
+    T* dval = (T*)a.dval;
+    T* dvalT = (T*)a.dvalT;
+    if (i < a.B) {
+        const int64_t r = a.idx[i];
+        const float ret = a.returns[r];
+        const float v = a.val[i];
+        if constexpr (VU) {         // (R - V)^2: the stored old value plays no part
+            vl = (v - ret) * (v - ret);
+            d_v = a.value_coef * invB * (2.0f * (v - ret));
+        } else {
+            const float vold = a.values[r];
+            const float vc = vold + clampf(v - vold, -a.clip, a.clip);
+            const float l1 = (v - ret) * (v - ret), l2 = (vc - ret) * (vc - ret);
+            vl = fmaxf(l1, l2);
+            // backward (torch.max splits ties evenly between its operands; clamp passes gradient on the closed range)
+            const float v_in = ((v - vold) >= -a.clip && (v - vold) <= a.clip) ? 1.0f : 0.0f;
+            const float u1 = l1 > l2 ? 1.0f : (l1 == l2 ? 0.5f : 0.0f);
+            d_v = a.value_coef * invB * (u1 * 2.0f * (v - ret) + (1.0f - u1) * 2.0f * (vc - ret) * v_in);
+        }
+        dval[(int64_t)i * a.ld_dval] = from_f32<T>(d_v);
+        dvalT[i] = from_f32<T>(d_v);
+    } else if (i < a.Bp) {       // zero the contraction padding of the gradient
+        dvalT[i] = from_f32<T>(0.0f);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        vl += __shfl_down(vl, off, 64);
+        d_v += __shfl_down(d_v, off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        red[threadIdx.x >> 6][0] = vl;
+        red[threadIdx.x >> 6][1] = d_v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2)
+        a.partials[(int64_t)blockIdx.x * LOSS_PARTIALS + (threadIdx.x == 0 ? LP_VALUE : LP_DBIAS_V)] =
+            red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+}
+
+template <int THREADS = 512>      // (a template: emitted only where it is launched, hgym_update_vf.hip)
+__global__ __launch_bounds__(THREADS) void vf_scalars_kernel(const VfScalArgs a) {
+    static_assert(THREADS == 16 * LOSS_PARTIALS, "16 partial sums per quantity");
+    __shared__ double red[16][LOSS_PARTIALS + 1];
+    const int tid = threadIdx.x;
+    const int k = tid & (LOSS_PARTIALS - 1), part = tid / LOSS_PARTIALS;      // 512 threads: 16 parts
+    const bool vf_k = k == LP_VALUE || k == LP_DBIAS_V;
+    const bool bc_k = a.bc_sums && ((k >= LP_DBIAS_MU && k < LP_DBIAS_V) || k == LP_MIRROR);
+    const float* __restrict__ partials = a.partials;
+    const int nblocks = a.nblocks;
+    double s = 0.0;
+    if (vf_k) {                  // ppo_scalars_block's order
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+        int b = part;
+        for (; b + 48 < nblocks; b += 64) {
+            const float v0 = partials[(int64_t)b * LOSS_PARTIALS + k], v1 = partials[(int64_t)(b + 16) * LOSS_PARTIALS + k];
+            const float v2 = partials[(int64_t)(b + 32) * LOSS_PARTIALS + k], v3 = partials[(int64_t)(b + 48) * LOSS_PARTIALS + k];
+            s0 += (double)v0; s1 += (double)v1; s2 += (double)v2; s3 += (double)v3;
+        }
+        for (; b < nblocks; b += 16) s0 += (double)partials[(int64_t)b * LOSS_PARTIALS + k];
+        s = (s0 + s1) + (s2 + s3);
+    } else if (bc_k) {           // bc_scalars_kernel's order
+        for (int b = part; b < nblocks; b += 16) s += (double)partials[(int64_t)b * LOSS_PARTIALS + k];
+    }
+    red[part][k] = s;
+    __syncthreads();
+    if (tid < LOSS_PARTIALS && (vf_k || bc_k)) {
+        double t = 0.0;
+        for (int p = 0; p < 16; ++p) t += red[p][tid];
+        if (tid == LP_VALUE) {
+            a.sums[0] += t / a.B;
+            a.sums[1] += 1.0;
+            if (!a.keep_sqnorm) a.opt[HGYM_OPT_GRAD_SQNORM] = 0.0;      // accumulated by reduce_slabs_kernel later in this call
+        } else if (tid == LP_DBIAS_V) {
+            if (a.grads_bv) a.grads_bv[0] = (float)t;
+        } else if (tid == LP_MIRROR) {
+            a.bc_sums[0] += t / ((double)a.B * (double)a.A);
+            a.bc_sums[1] += 1.0;
+        } else if (a.grads_bmu && tid - LP_DBIAS_MU < a.A) {
+            a.grads_bmu[tid - LP_DBIAS_MU] = (float)t;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ launchers of other translation units
 // What hgym_net.hip calls of the files that hold kernels of their own; each of them includes this header, so a drifting signature fails to compile there.
 // hgym_update.hip, hgym_update_act.hip: the update's tiles from net `first` on (ELU(1); any resolved activation)
@@ -379,5 +499,8 @@ int32_t launch_head_sums(int nblocks, int B, int A, const float* head_partials, 
 // hgym_guide.hip: the layer-by-layer head with the teacher's term, and the sums of its squared error
 int32_t launch_ppo_loss_guide(const LossArgs& a, const LossGuide& gd, bool bf16, int nblocks, hipStream_t s);
 int32_t launch_guide_sums(int nblocks, int B, int A, const float* partials, double* sums, hipStream_t s);
+// hgym_update_vf.hip: the small kernels of a critic-only step
+int32_t launch_vf_loss(const VfLossArgs& a, bool bf16, bool unclipped, int nblocks, hipStream_t s);
+int32_t launch_vf_scalars(const VfScalArgs& a, hipStream_t s);
 
 }  // namespace hgym

@@ -834,6 +834,9 @@ struct NetBase {
         return zero_f32_async(net.grads, w.P + 1, s);      // a launch, not a memset node: the step also runs inside captured updates (hgym_fill.hip)
     }
     int32_t bc_reduce_actor(int Mp) { return reduce_range(w.net[0].layer[0].w_off, w.net[1].layer[0].w_off, Mp); }
+    // hgym_vf_grad / hgym_bc_vf_grad: the critic's segments alone; the actor's and the critic's in one pass
+    int32_t vf_reduce_critic(int Mp) { return reduce_range(w.net[1].layer[0].w_off, w.aux_p0, Mp); }
+    int32_t bc_vf_reduce(int Mp) { return reduce_range(w.net[0].layer[0].w_off, w.aux_p0, Mp); }
 
     // slab reduction of the segments whose parameters lie in [lo, hi) of the flat vector (Mp: an auxiliary head on the layer-by-layer
     // path took its slab counts from the minibatch's contraction padding)
@@ -1205,6 +1208,90 @@ struct GemmPath : NetBase {
         return bc_reduce_actor(Bp);
     }
 
+    // the critic's forward and vf_loss_kernel: d V and its two partials are in place afterwards
+    int32_t vf_head(const HgymVFConfig& vf, const HgymBatch& b, int Bp, int nblocks) {
+        const int B = b.B;
+        float* val = at<float>(w.net[1].out_f32);
+        const int32_t rc = forward(1, B, b.priv, cfg.num_priv, b.idx, val, 1, true);
+        if (rc) return rc;
+        const LayerLayout& lc = w.net[1].layer[w.net[1].L - 1];
+        VfLossArgs a;
+        memset(&a, 0, sizeof(a));
+        a.val = val;
+        a.values = b.values;
+        a.returns = b.returns;
+        a.idx = b.idx;
+        a.B = B;
+        a.Bp = Bp;
+        a.dval = at<T>(lc.dY);
+        a.ld_dval = lc.Ncp;
+        a.dvalT = at<T>(lc.dYT);
+        a.clip = vf.clip_param;
+        a.value_coef = vf.value_coef;
+        a.partials = at<float>(w.partials);
+        return launch_vf_loss(a, sizeof(T) == 2, vf.unclipped != 0, nblocks, s);
+    }
+
+    // hgym_vf_grad: the critic's forward, vf_loss_kernel, the scalars, the critic's backward, the critic's slab sums
+    int32_t vf_grad(const HgymVFConfig& vf, const HgymBatch& b, double* sums) {
+        const int B = b.B;
+        const int Bp = (int)round_up(B, w.SE);
+        const int nblocks = ceil_div(Bp, 256);
+        HG_REQUIRE(nblocks <= MAX_LOSS_BLOCKS, HGYM_E_UNSUPPORTED, "minibatch %d too large for the loss partial buffer", B);
+        int32_t rc = vf.keep_others ? HGYM_OK : bc_zero_grads();
+        if (rc) return rc;
+        rc = vf_head(vf, b, Bp, nblocks);
+        if (rc) return rc;
+        const VfScalArgs sc = {nblocks, B, cfg.num_actions, at<float>(w.partials), nullptr, net.opt_state, sums, vf.keep_others, nullptr, nullptr};
+        rc = launch_vf_scalars(sc, s);
+        if (rc) return rc;
+        rc = backward(1, B);
+        if (rc) return rc;
+        return vf_reduce_critic(Bp);
+    }
+
+    // hgym_bc_vf_grad: both forwards, both heads, ONE scalars workgroup, both backwards, ONE slab pass over the actor and the critic
+    int32_t bc_vf_grad(const HgymBCConfig& bc, const HgymVFConfig& vf, const HgymBatch& b, const float* target, double* bc_sums, double* vf_sums) {
+        const int B = b.B, A = cfg.num_actions;
+        float* mu = at<float>(w.net[0].out_f32);
+        const int Bp = (int)round_up(B, w.SE);
+        const int nblocks = ceil_div(Bp, 256);
+        HG_REQUIRE(nblocks <= MAX_LOSS_BLOCKS, HGYM_E_UNSUPPORTED, "minibatch %d too large for the loss partial buffer", B);
+        int32_t rc = bc_zero_grads();
+        if (rc) return rc;
+        rc = forward(0, B, b.obs, cfg.num_obs, b.idx, mu, A, true);
+        if (rc) return rc;
+        const LayerLayout& la = w.net[0].layer[w.net[0].L - 1];
+        BcLossArgs a;
+        memset(&a, 0, sizeof(a));
+        a.mu = mu;
+        a.target = target;
+        a.idx = b.idx;
+        a.B = B;
+        a.Bp = Bp;
+        a.A = A;
+        a.dmu = at<T>(la.dY);
+        a.ld_dmu = la.Ncp;
+        a.dmuT = at<T>(la.dYT);
+        a.ld_t = w.Mp;
+        a.inv = 1.0f / ((float)B * (float)A);
+        a.delta = bc.huber_delta;
+        a.huber = bc.loss_type == HGYM_BC_HUBER;
+        a.partials = at<float>(w.partials);
+        rc = launch_bc_loss(a, sizeof(T) == 2, nblocks, s);
+        if (rc) return rc;
+        rc = vf_head(vf, b, Bp, nblocks);
+        if (rc) return rc;
+        const VfScalArgs sc = {nblocks, B, A, at<float>(w.partials), nullptr, net.opt_state, vf_sums, 0, nullptr, bc_sums};
+        rc = launch_vf_scalars(sc, s);
+        if (rc) return rc;
+        rc = backward(0, B);
+        if (rc) return rc;
+        rc = backward(1, B);
+        if (rc) return rc;
+        return bc_vf_reduce(Bp);
+    }
+
     int32_t act(int M, const float* obs, const float* priv, const float* z, uint64_t seed, const int64_t* step, float* actions, float* mu,
                 float* sigma, float* logp, float* values, const FinArgs* fin, const HgymObsShadow* sh) {
         HG_REQUIRE(!sh || (!sh->obs && !sh->priv), HGYM_E_UNSUPPORTED, "the observation shadow exists on the fused bf16 path only (hgym_net_shadow_ld = 0 here)");
@@ -1374,14 +1461,16 @@ struct FusedPath : NetBase {
     // gb (mlp_fb_kernel<XB16> ran): the first-layer operands were never copied -- those products gather their rows by gb->idx from the
     // bf16 shadows
     // ride: the loss-scalar workgroup `sc` rides in the launch (false: hgym_bc_grad, whose scalars have a launch of their own)
-    int32_t dw(int nets, int B, const ScalArgs& sc, const HgymBatch* gb, bool ride = true) {
+    // first: the first net whose products are launched (1: a critic-only step); gmask: bit i set -- net i gathers from gb's shadow
+    // (a cloning step with the critic decides it per net, as its two halves do)
+    int32_t dw(int nets, int B, const ScalArgs& sc, const HgymBatch* gb, bool ride = true, int first = 0, unsigned gmask = ~0u) {
         const int Bp = (int)round_up(B, 64);
         DwArgs d;
         memset(&d, 0, sizeof(d));
         d.B = B;
         int tile = 0;
         double fl = 0.0;
-        for (int i = 0; i < nets; ++i)
+        for (int i = first; i < nets; ++i)
             for (int l = 0; l < 4; ++l) {
                 const NetLayout& n = w.net[i];
                 const LayerLayout& y = n.layer[l];
@@ -1391,7 +1480,7 @@ struct FusedPath : NetBase {
                 p.CBz = l < 3 ? y.N / 16 : 2 * y.NBBf;
                 p.X = l == 0 ? at<__bf16>(w.net[i == 2 ? 0 : i].X0b) : at<__bf16>(n.Hb[l - 1]);
                 p.CBx = l == 0 ? 2 * y.KBf : y.K / 16;
-                if (l == 0 && gb) {
+                if (l == 0 && gb && ((gmask >> i) & 1u)) {
                     p.X = (const __bf16*)(i == 1 ? gb->priv_bf16 : gb->obs_bf16);
                     p.gidx = gb->idx;
                     p.ldg = shadow_ld(w, i == 1 ? 1 : 0);
@@ -1437,11 +1526,12 @@ struct FusedPath : NetBase {
     };
     static const void* shadow_rows(const HgymBatch& b, int i) { return i == 1 ? b.priv_bf16 : b.obs_bf16; }
 
-    int32_t plan_tiles(const HgymBatch& b, int nets, UpdateTiles* u) const {
+    // first: the first net of the tiles (1: the critic alone)
+    int32_t plan_tiles(const HgymBatch& b, int nets, UpdateTiles* u, int first = 0) const {
         const int B = b.B;
         // bf16 shadows of the storage rows, every net's or none: gather 2 B per element, keep no operand copy
         u->shadow = b.num_rows > 0;
-        for (int i = 0; i < nets; ++i)
+        for (int i = first; i < nets; ++i)
             u->shadow = u->shadow && shadow_rows(b, i) && b.num_rows * shadow_ld(w, i == 1 ? 1 : 0) * 2 < ((int64_t)1 << 32);
         // (128-row tiles on eight 256-register wavefronts -- round 4's mlp_fb2_kernel -- measured equal to slightly slower:
         // profiles/r04_fb2_128row_tiles_negative_result.txt; its source is profiles/r04_fb2_128row_kernel.patch; round 6 rebuilt the idea on role-specialised wavefronts at 64 and 128 rows: profiles/r06_fb3_role_specialised_wavefronts.txt.)
@@ -1452,15 +1542,15 @@ struct FusedPath : NetBase {
     }
 
     // kernel: the name that the LDS refusal gives
-    int32_t fill_tiles(const HgymBatch& b, int nets, const NetIO io[3], const char* kernel, UpdateTiles* u) {
+    int32_t fill_tiles(const HgymBatch& b, int nets, const NetIO io[3], const char* kernel, UpdateTiles* u, int first = 0) {
         FwdArgs& fb = u->fb;
-        fb = make_fwd_args(0, nets, b.B, io, b.idx, true, nullptr, nullptr);
+        fb = make_fwd_args(first, nets - first, b.B, io, b.idx, true, nullptr, nullptr);
         if (nets > 2) fb.net[2].X0 = nullptr;       // the head's first-layer operand for the weight gradient is the actor's copy (dw)
         if (u->shadow) {
             uintptr_t bits = 0;
-            for (int i = 0; i < nets; ++i) bits |= (uintptr_t)shadow_rows(b, i);
+            for (int i = first; i < nets; ++i) bits |= (uintptr_t)shadow_rows(b, i);
             HG_REQUIRE((bits & 15) == 0, HGYM_E_BADARG, "observation shadows must be 16-byte aligned");
-            for (int i = 0; i < nets; ++i) {
+            for (int i = first; i < nets; ++i) {
                 fb.net[i].xb = (const __bf16*)shadow_rows(b, i);
                 fb.net[i].ldxb = shadow_ld(w, i == 1 ? 1 : 0);
                 fb.net[i].X0 = nullptr;
@@ -1469,7 +1559,7 @@ struct FusedPath : NetBase {
         memset(&u->fl, 0, sizeof(u->fl));
         u->fl.partials = at<float>(w.partials);
         u->lds = 0;
-        for (int i = 0; i < nets; ++i)
+        for (int i = first; i < nets; ++i)
             u->lds = std::max(u->lds, (size_t)fb_lds_bytes(fb.net[i]));       // the nets the kernel receives (fused_supported: same sum)
         HG_REQUIRE(u->lds <= FB_LDS_LIMIT, HGYM_E_UNSUPPORTED, "%s needs %zu bytes of LDS", kernel, u->lds);
         fb.nets = nets;
@@ -1606,6 +1696,90 @@ struct FusedPath : NetBase {
         rc = dw(1, B, none, u.shadow ? &b : nullptr, false);
         if (rc) return rc;
         return bc_reduce_actor(Mp);
+    }
+
+    // The critic's tiles of a critic-only step, through the kernels the critic always had (launch_rest from net 1 on): planned and
+    // filled (vf_tiles, before anything is launched), then launched (vf_launch).
+    int32_t vf_tiles(const HgymVFConfig& vf, const HgymBatch& b, UpdateTiles* u) {
+        int32_t rc = plan_tiles(b, 2, u, 1);
+        if (rc) return rc;
+        const NetIO io[3] = {{}, {b.priv, cfg.num_priv, at<float>(w.net[1].out_f32), 1}, {}};
+        rc = fill_tiles(b, 2, io, "mlp_fb_kernel", u, 1);
+        if (rc) return rc;
+        FbLoss& fl = u->fl;
+        fl.values = (vf.unclipped && !b.values) ? b.returns : b.values;      // (the unclipped tile still loads the old value and drops it)
+        fl.returns = b.returns;
+        fl.clip = vf.clip_param;
+        fl.value_coef = vf.value_coef;
+        return HGYM_OK;
+    }
+    int32_t vf_launch(const HgymVFConfig& vf, const UpdateTiles& u, int B) {
+        double flops = 0.0;
+        for (int l = 0; l < 4; ++l) flops += (l > 0 ? 4.0 : 2.0) * (double)B * w.net[1].layer[l].N * w.net[1].layer[l].K;
+        prof_begin(HGYM_PROF_MLP_FWD, s);
+        const int32_t rc = launch_rest(u, vf.unclipped != 0, 2, 1);
+        prof_end(HGYM_PROF_MLP_FWD, s, flops);      // (before the error return, as in bc_grad)
+        if (rc) return rc;
+        HG_CHECK_LAUNCH("mlp_fb_kernel");
+        return HGYM_OK;
+    }
+
+    // hgym_vf_grad: the critic's tiles, the scalars, the critic's four weight-gradient products, the critic's slab sums
+    int32_t vf_grad(const HgymVFConfig& vf, const HgymBatch& b, double* sums) {
+        const int B = b.B;
+        const int Mp = (int)round_up(B, w.SE);
+        UpdateTiles u;
+        int32_t rc = vf_tiles(vf, b, &u);
+        if (rc) return rc;
+        rc = vf.keep_others ? HGYM_OK : bc_zero_grads();
+        if (rc) return rc;
+        rc = vf_launch(vf, u, B);
+        if (rc) return rc;
+        const VfScalArgs sc = {u.tiles, B, cfg.num_actions, at<float>(w.partials), net.grads + w.net[1].layer[3].b_off, net.opt_state, sums,
+                               vf.keep_others, nullptr, nullptr};
+        rc = launch_vf_scalars(sc, s);
+        if (rc) return rc;
+        ScalArgs none;
+        memset(&none, 0, sizeof(none));
+        rc = dw(2, B, none, u.shadow ? &b : nullptr, false, 1);
+        if (rc) return rc;
+        return vf_reduce_critic(Mp);
+    }
+
+    // hgym_bc_vf_grad: the actor's tiles with the regression head, the critic's plain tiles, ONE scalars workgroup, ONE weight-gradient launch
+    // with the eight products, ONE slab pass.  Each net decides on its shadow as its own call would.
+    int32_t bc_vf_grad(const HgymBCConfig& bc, const HgymVFConfig& vf, const HgymBatch& b, const float* target, double* bc_sums, double* vf_sums) {
+        const int B = b.B, A = cfg.num_actions;
+        const int Mp = (int)round_up(B, w.SE);
+        UpdateTiles ua, uc;
+        int32_t rc = plan_tiles(b, 1, &ua);
+        if (rc) return rc;
+        HG_REQUIRE(A != 12 || ((uintptr_t)target & 15) == 0, HGYM_E_BADARG, "hgym_bc_vf_grad: target must be 16-byte aligned");
+        rc = vf_tiles(vf, b, &uc);
+        if (rc) return rc;
+        const NetIO io[3] = {{b.obs, cfg.num_obs, at<float>(w.net[0].out_f32), A}, {}, {}};
+        rc = fill_tiles(b, 1, io, "mlp_fb_bc_kernel", &ua);
+        if (rc) return rc;
+        rc = bc_zero_grads();
+        if (rc) return rc;
+        const FbBC head = {target, 1.0f / ((float)B * (float)A), bc.huber_delta, bc.loss_type == HGYM_BC_HUBER ? 1 : 0};
+        prof_begin(HGYM_PROF_MLP_FWD, s);
+        rc = launch_actor_head(ua, head);
+        prof_end(HGYM_PROF_MLP_FWD, s, tile_flops(1, B));
+        if (rc) return rc;
+        HG_CHECK_LAUNCH("mlp_fb_bc_kernel");
+        rc = vf_launch(vf, uc, B);
+        if (rc) return rc;
+        const VfScalArgs sc = {ua.tiles, B, A, at<float>(w.partials), net.grads + w.net[1].layer[3].b_off, net.opt_state, vf_sums, 0,
+                               net.grads + w.net[0].layer[3].b_off, bc_sums};
+        rc = launch_vf_scalars(sc, s);
+        if (rc) return rc;
+        ScalArgs none;
+        memset(&none, 0, sizeof(none));
+        const unsigned gmask = (ua.shadow ? 1u : 0u) | (uc.shadow ? 2u : 0u);
+        rc = dw(2, B, none, gmask ? &b : nullptr, false, 0, gmask);
+        if (rc) return rc;
+        return bc_vf_reduce(Mp);
     }
 
     int32_t act(int M, const float* obs, const float* priv, const float* z, uint64_t seed, const int64_t* step, float* actions, float* mu,
@@ -1979,6 +2153,57 @@ int32_t hgym_bc_grad(const HgymNetConfig* cfg, const HgymBCConfig* bc, const Hgy
         HG_REQUIRE(net->grads && net->opt_state, HGYM_E_BADARG, "null grads / opt_state");
         HG_REQUIRE(!net->norm, HGYM_E_UNSUPPORTED, "hgym_bc_grad with HgymNet.norm set: observation normalisation is not part of a cloning step");
         return R.bc_grad(*bc, *batch, target, sums);
+    });
+}
+
+// What hgym_vf_grad and hgym_bc_vf_grad refuse of the value half, the same for both (fn: the caller's name); before anything is launched
+static int32_t check_vf(const HgymNetConfig* cfg, const HgymVFConfig* vf, const HgymBatch* batch, const double* sums, const char* fn) {
+    HG_REQUIRE(sums && ((uintptr_t)sums & 7) == 0, HGYM_E_BADARG, "%s: the value loss's sums must be non-null and 8-byte aligned", fn);
+    HG_REQUIRE((vf->unclipped == 0 || vf->unclipped == 1) && (vf->keep_others == 0 || vf->keep_others == 1), HGYM_E_BADARG,
+               "%s: HgymVFConfig.unclipped=%d, keep_others=%d (0 or 1 each)", fn, vf->unclipped, vf->keep_others);
+    // (written so that a NaN fails it)
+    HG_REQUIRE(vf->value_coef >= 0.0f && vf->value_coef < INFINITY, HGYM_E_BADARG, "%s: HgymVFConfig.value_coef=%g must be finite and >= 0", fn,
+               (double)vf->value_coef);
+    HG_REQUIRE(vf->unclipped || (vf->clip_param >= 0.0f && vf->clip_param < INFINITY), HGYM_E_BADARG,
+               "%s: HgymVFConfig.clip_param=%g must be finite and >= 0", fn, (double)vf->clip_param);
+    HG_REQUIRE(batch->B >= 1 && batch->B <= cfg->max_batch, HGYM_E_BADARG, "%s: B=%d outside [1, max_batch = %d]", fn, batch->B, cfg->max_batch);
+    HG_REQUIRE(batch->priv && batch->returns && batch->idx, HGYM_E_BADARG, "%s: null HgymBatch.priv / returns / idx", fn);
+    HG_REQUIRE(vf->unclipped || batch->values, HGYM_E_BADARG, "%s: the clipped value loss needs HgymBatch.values", fn);
+    HG_REQUIRE((((uintptr_t)batch->priv | (uintptr_t)batch->returns | (uintptr_t)batch->values) & 3) == 0 && ((uintptr_t)batch->idx & 7) == 0 &&
+                   ((uintptr_t)batch->priv_bf16 & 15) == 0, HGYM_E_BADARG, "%s: misaligned HgymBatch.priv / returns / values / idx / priv_bf16", fn);
+    return HGYM_OK;
+}
+
+int32_t hgym_vf_grad(const HgymNetConfig* cfg, const HgymVFConfig* vf, const HgymNet* net, const HgymBatch* batch, double* sums, void* stream) {
+    // every refusal below comes before anything is launched (and before any pointer of `net` is looked at)
+    HG_REQUIRE(cfg && vf && net && batch, HGYM_E_BADARG, "hgym_vf_grad: null cfg / vf / net / batch");
+    const int32_t rc = check_vf(cfg, vf, batch, sums, "hgym_vf_grad");
+    if (rc) return rc;
+    return run(cfg, net, stream, [&](auto& R) -> int32_t {
+        HG_REQUIRE(net->grads && net->opt_state, HGYM_E_BADARG, "null grads / opt_state");
+        return R.vf_grad(*vf, *batch, sums);
+    });
+}
+
+int32_t hgym_bc_vf_grad(const HgymNetConfig* cfg, const HgymBCConfig* bc, const HgymVFConfig* vf, const HgymNet* net, const HgymBatch* batch,
+                        const float* target, double* bc_sums, double* vf_sums, void* stream) {
+    // every refusal below comes before anything is launched: hgym_bc_grad's, then hgym_vf_grad's
+    HG_REQUIRE(cfg && bc && vf && net && batch, HGYM_E_BADARG, "hgym_bc_vf_grad: null cfg / bc / vf / net / batch");
+    HG_REQUIRE(target && bc_sums, HGYM_E_BADARG, "hgym_bc_vf_grad: null target / bc_sums");
+    HG_REQUIRE(((uintptr_t)bc_sums & 7) == 0 && ((uintptr_t)target & 3) == 0, HGYM_E_BADARG, "hgym_bc_vf_grad: misaligned target / bc_sums");
+    HG_REQUIRE(bc->loss_type == HGYM_BC_MSE || bc->loss_type == HGYM_BC_HUBER, HGYM_E_BADARG,
+               "HgymBCConfig.loss_type=%d (HGYM_BC_MSE = 0, HGYM_BC_HUBER = 1)", bc->loss_type);
+    // (written so that a NaN fails it)
+    HG_REQUIRE(bc->loss_type != HGYM_BC_HUBER || (bc->huber_delta > 0.0f && bc->huber_delta < INFINITY), HGYM_E_BADARG,
+               "HgymBCConfig.huber_delta=%g must be finite and > 0", (double)bc->huber_delta);
+    const int32_t rc = check_vf(cfg, vf, batch, vf_sums, "hgym_bc_vf_grad");
+    if (rc) return rc;
+    HG_REQUIRE(bc_sums != vf_sums, HGYM_E_BADARG, "hgym_bc_vf_grad: bc_sums and vf_sums must be two blocks");
+    HG_REQUIRE(batch->obs && ((uintptr_t)batch->obs_bf16 & 15) == 0, HGYM_E_BADARG, "hgym_bc_vf_grad: null HgymBatch.obs, or a misaligned obs_bf16");
+    return run(cfg, net, stream, [&](auto& R) -> int32_t {
+        HG_REQUIRE(net->grads && net->opt_state, HGYM_E_BADARG, "null grads / opt_state");
+        HG_REQUIRE(!net->norm, HGYM_E_UNSUPPORTED, "hgym_bc_vf_grad with HgymNet.norm set: observation normalisation is not part of a cloning step");
+        return R.bc_vf_grad(*bc, *vf, *batch, target, bc_sums, vf_sums);
     });
 }
 

@@ -5,6 +5,7 @@ from .env_buffers import EnvBuffers, default_env_config, log_stats_summary
 from .net import NetBuffers, make_net_config, make_ppo_config, make_batch, activation_spec, diag_from_block, DIAG_KEYS, opt_summary
 from .net import check_obs_norm, norm_layout
 from .net import make_bc_config, make_bc_batch, BC_LOSS_TYPES
+from .net import make_vf_config, make_vf_batch
 from .net import make_smooth, smooth_ld, smooth_mirror_partials
 from .net import make_guide, make_guide_schedule, guide_schedule, guide_schedule_coef, GUIDE_MODES
 

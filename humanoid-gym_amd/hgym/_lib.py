@@ -166,6 +166,11 @@ class BCConfig(C.Structure):
     _fields_ = [("loss_type", C.c_int32), ("huber_delta", C.c_float)]
 
 
+class VFConfig(C.Structure):
+    """HgymVFConfig: the value loss of a critic-only minibatch (hgym_vf_grad, hgym_bc_vf_grad)."""
+    _fields_ = [("clip_param", C.c_float), ("value_coef", C.c_float), ("unclipped", C.c_int32), ("keep_others", C.c_int32)]
+
+
 class ObsShadow(C.Structure):
     """HgymObsShadow: where a policy launch leaves the bf16 of the observation rows it reads (row-major, ld in elements)."""
     _fields_ = [("obs", C.c_void_p), ("ld_obs", C.c_int64), ("priv", C.c_void_p), ("ld_priv", C.c_int64)]
@@ -208,7 +213,7 @@ class Guide(C.Structure):
 STRUCTS = dict(HgymEnvConfig=EnvConfig, HgymStrided=Strided, HgymSimTensors=SimTensors, HgymEnvState=EnvState,
                HgymEnvOut=EnvOut, HgymEnvNoise=EnvNoise, HgymNetConfig=NetConfig, HgymPPOConfig=PPOConfig,
                HgymNet=Net, HgymBatch=Batch, HgymObsShadow=ObsShadow, HgymComm=Comm, HgymBCConfig=BCConfig, HgymRndConfig=RndConfig,
-               HgymSmooth=Smooth, HgymGuideSchedule=GuideSchedule, HgymGuide=Guide)
+               HgymSmooth=Smooth, HgymGuideSchedule=GuideSchedule, HgymGuide=Guide, HgymVFConfig=VFConfig)
 
 # every symbol include/hgym.h declares: name -> (restype, argtypes)
 _P = C.POINTER
@@ -288,6 +293,8 @@ SYMBOLS = {
     "hgym_ppo_grad": (C.c_int32, [_P(NetConfig), _P(PPOConfig), _P(Net), _P(Batch), C.c_void_p]),
     "hgym_ppo_grad_part": (C.c_int32, [_P(NetConfig), _P(PPOConfig), _P(Net), _P(Batch), C.c_int32, C.c_void_p]),
     "hgym_bc_grad": (C.c_int32, [_P(NetConfig), _P(BCConfig), _P(Net), _P(Batch), c_float_p, c_f64_p, C.c_void_p]),
+    "hgym_vf_grad": (C.c_int32, [_P(NetConfig), _P(VFConfig), _P(Net), _P(Batch), c_f64_p, C.c_void_p]),
+    "hgym_bc_vf_grad": (C.c_int32, [_P(NetConfig), _P(BCConfig), _P(VFConfig), _P(Net), _P(Batch), c_float_p, c_f64_p, c_f64_p, C.c_void_p]),
     "hgym_smooth_pairs": (C.c_int32, [C.c_int64, C.c_int64, c_i64_p, c_u8_p, c_i64_p, c_float_p, C.c_void_p]),
     "hgym_perturb_rows": (C.c_int32, [C.c_int64, C.c_int32, c_float_p, C.c_int64, c_i64_p, c_float_p, C.c_uint64, c_f64_p, c_float_p, C.c_int64,
                                       C.c_void_p]),

@@ -349,6 +349,22 @@ class NetBuffers:
         L.check(L.lib.hgym_bc_grad(C.byref(self.cfg), C.byref(bc), C.byref(self.struct), C.byref(batch), L.fptr(target), L.f64ptr(sums),
                                    self.stream()), "hgym_bc_grad")
 
+    def vf_grad(self, vf, batch, sums):
+        """hgym_vf_grad: one critic-only minibatch (make_vf_config, make_vf_batch).  sums: float64 (2,), [0] += the minibatch's mean value
+        loss (unweighted), [1] += 1.  The step is ppo_apply's with adaptive_lr = 0 and grad_norm_ready = 0."""
+        assert sums.dtype == torch.float64 and sums.is_contiguous() and sums.numel() >= 2
+        L.check(L.lib.hgym_vf_grad(C.byref(self.cfg), C.byref(vf), C.byref(self.struct), C.byref(batch), L.f64ptr(sums), self.stream()),
+                "hgym_vf_grad")
+
+    def bc_vf_grad(self, bc, vf, batch, target, bc_sums, vf_sums):
+        """hgym_bc_vf_grad: one cloning minibatch that also trains the critic -- bit for bit bc_grad followed by vf_grad with
+        keep_others = 1, in fewer launches.  batch: make_vf_batch with obs; target, bc_sums as for bc_grad; vf_sums as for vf_grad."""
+        assert target.dtype == torch.float32 and target.is_contiguous()
+        for t in (bc_sums, vf_sums):
+            assert t.dtype == torch.float64 and t.is_contiguous() and t.numel() >= 2
+        L.check(L.lib.hgym_bc_vf_grad(C.byref(self.cfg), C.byref(bc), C.byref(vf), C.byref(self.struct), C.byref(batch), L.fptr(target),
+                                      L.f64ptr(bc_sums), L.f64ptr(vf_sums), self.stream()), "hgym_bc_vf_grad")
+
     @property
     def bucket_split(self):
         """Offset of the critic's first parameter in the flat vector: the boundary of the two gradient buckets."""
@@ -523,6 +539,41 @@ def make_bc_batch(obs, idx, obs_bf16=None):
     if obs_bf16 is not None:
         assert obs_bf16.dtype == torch.bfloat16 and obs_bf16.is_contiguous() and obs_bf16.shape[0] == obs.shape[0]
         b.obs_bf16 = C.c_void_p(obs_bf16.data_ptr())
+    return b
+
+
+def make_vf_config(clip_param=0.2, value_coef=1.0, clipped_value_loss=True, keep_others=False):
+    """HgymVFConfig of hgym_vf_grad / hgym_bc_vf_grad.  clip_param: the value clip range (finite and >= 0; not read by the unclipped
+    form); value_coef: multiplies the gradient, not the reported loss (finite and >= 0); clipped_value_loss: the reference's
+    use_clipped_value_loss; keep_others: leave the gradient outside the critic's region as found and ADD the critic's squared norm
+    (False: that region becomes +0.0 and the norm is the critic's alone).  ValueError for anything else."""
+    import math
+    c, k = float(clip_param), float(value_coef)
+    if clipped_value_loss and not (c >= 0.0 and math.isfinite(c)):
+        raise ValueError("clip_param=%r: must be finite and >= 0" % (clip_param,))
+    if not (k >= 0.0 and math.isfinite(k)):
+        raise ValueError("value_coef=%r: must be finite and >= 0" % (value_coef,))
+    return L.VFConfig(c if clipped_value_loss else 0.0, k, 0 if clipped_value_loss else 1, 1 if keep_others else 0)
+
+
+def make_vf_batch(priv, values, returns, idx, priv_bf16=None, obs=None, obs_bf16=None):
+    """The HgymBatch hgym_vf_grad reads: priv (rows, num_priv), values (rows,) -- None with the unclipped loss -- and returns (rows,),
+    fp32 contiguous; idx int64 (B,); optionally the (rows, ld) bfloat16 shadow of priv.  obs / obs_bf16: what hgym_bc_vf_grad reads beside
+    them (make_bc_batch's).  Every other member stays NULL."""
+    for t in (priv, values, returns, obs):
+        assert t is None or (t.is_contiguous() and t.dtype == torch.float32)
+    assert idx.dtype == torch.int64 and idx.is_contiguous()
+    rows = int(priv.shape[0])
+    assert returns.numel() == rows and (values is None or values.numel() == rows) and (obs is None or obs.shape[0] == rows)
+    b = L.Batch()
+    b.priv, b.values, b.returns = L.fptr(priv), L.fptr(values), L.fptr(returns)
+    b.idx, b.B, b.num_rows = L.i64ptr(idx), int(idx.numel()), rows
+    if obs is not None:
+        b.obs = L.fptr(obs)
+    for name, t in (("priv_bf16", priv_bf16), ("obs_bf16", obs_bf16)):
+        if t is not None:
+            assert t.dtype == torch.bfloat16 and t.is_contiguous() and t.shape[0] == rows
+            setattr(b, name, C.c_void_p(t.data_ptr()))
     return b
 
 

@@ -18,6 +18,7 @@ NORM_KEYS = ("obs_norm_state_dict", "critic_obs_norm_state_dict")      # a check
 RND_STATE_KEY = "rnd_state_dict"      # what a checkpoint of a run with rnd_cfg carries besides the reference's four keys
 VALUE_NORM_KEY = "value_norm_state_dict"      # what a checkpoint of a run with PPO.value_normalization carries: count, mean, var, eps
 GUIDE_KEY = "guidance_state_dict"      # what a checkpoint of a run with PPO.guidance carries: count, schedule, the teacher's actor tensors
+WARMUP_KEY = "critic_warmup_state_dict"      # what a checkpoint of a run with PPO.critic_warmup_updates > 0 carries: done, updates
 NORM_COUNT = 2      # NetBuffers.norm_view("header"): eps, until, then count of statistics k at NORM_COUNT + k, of L.NORM_HEADER_DOUBLES doubles
 
 
@@ -94,7 +95,8 @@ def write_checkpoint(ck, path, side=None):
 def extra_entries(alg):
     """What a checkpoint carries beyond the reference's four keys, in file order: the two normaliser dicts (NORM_KEYS) of a policy with
     empirical_normalization, then RND_STATE_KEY of a run with rnd_cfg, then VALUE_NORM_KEY of a run with PPO.value_normalization, then
-    GUIDE_KEY of a run with PPO.guidance (host data: the background path adds the same dict).  Reads the device (the blocking path)."""
+    GUIDE_KEY of a run with PPO.guidance, then WARMUP_KEY of a run with PPO.critic_warmup_updates (both host data: the background path adds
+    the same dicts).  Reads the device (the blocking path)."""
     ac, rnd = alg.actor_critic, alg._rnd
     extra = dict(ac.norm_state_dicts()) if hasattr(ac, "norm_state_dicts") else {}
     if rnd is not None:
@@ -103,6 +105,8 @@ def extra_entries(alg):
         extra[VALUE_NORM_KEY] = alg.value_normalizer.state_dict()
     if getattr(alg, "_guide", None) is not None:
         extra[GUIDE_KEY] = alg._guide.state_dict()
+    if getattr(alg, "_warmup", None) is not None:
+        extra[WARMUP_KEY] = alg._warmup.state_dict()
     return extra
 
 
@@ -212,6 +216,8 @@ def write_snapshot(shot, group, it, infos, path, side):
         ck = assemble(shot["buf"], shot["layout"], shot["opt_layout"], group, it, infos, shot["norm"], shot.get("value_norm"))
         if shot.get("guidance") is not None:      # PPO.guidance: Guidance.state_dict() as the training thread formed it at save() (host data)
             ck[GUIDE_KEY] = shot["guidance"]
+        if shot.get("critic_warmup") is not None:      # PPO.critic_warmup_updates: the count as it stood at save() (host data)
+            ck[WARMUP_KEY] = shot["critic_warmup"]
         tj.append(time.perf_counter())
         write_checkpoint(ck, path, side)
         tj.append(time.perf_counter())
@@ -298,9 +304,9 @@ def _check_value_norm_key(loaded, eps, name):
         raise RuntimeError("%s: `%s` was saved with value_normalization_eps=%r; this run was built with %r" % (name, VALUE_NORM_KEY, sd.get("eps"), eps))
 
 
-def check_compatible(loaded, actor_critic, rnd, name, value_norm=None, guidance=None):
+def check_compatible(loaded, actor_critic, rnd, name, value_norm=None, guidance=None, critic_warmup=False):
     """Checkpoint `loaded` (file `name`) against this run's policy, RND module (None: off), value normalisation (value_norm: its eps,
-    None: off) and guidance (the run's Guidance, None: off); raises before anything is changed."""
+    None: off), guidance (the run's Guidance, None: off) and critic warm-up (on?); raises before anything is changed."""
     # a checkpoint of the other noise parametrisation: its first entry is another quantity under another name
     msd, mine = loaded["model_state_dict"], getattr(actor_critic, "noise_std_type", "scalar")
     theirs = "log" if "log_std" in msd else ("scalar" if "std" in msd else mine)
@@ -317,3 +323,6 @@ def check_compatible(loaded, actor_critic, rnd, name, value_norm=None, guidance=
     # a checkpoint of a guided run for a run without the option, the reverse, or another schedule: refused by key name
     from .guidance import check_state_dict as check_guide_state
     check_guide_state(loaded.get(GUIDE_KEY), name, guidance is not None, getattr(guidance, "schedule", None))
+    # a checkpoint of a run with critic warm-up for a run without it, or the reverse: refused by key name
+    from .critic_warmup import check_state_dict as check_warmup_state
+    check_warmup_state(loaded.get(WARMUP_KEY), name, bool(critic_warmup))

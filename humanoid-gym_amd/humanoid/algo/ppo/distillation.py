@@ -6,6 +6,11 @@ the student acts with its noise; the critic's values are computed as ever and th
 pass of the teacher over the T N stored observation rows into storage.teacher_actions.  update() walks the storage in slices of
 `gradient_length` steps, in storage order (rsl_rl's order: no permutation), one hgym_bc_grad + hgym_ppo_apply -- one Adam step -- per
 slice and epoch.  Nothing but the student is trained: the critic and sigma keep their bits through a whole run.
+
+Distillation.train_critic (off by default): the rollout already pays for the critic's tiles and stores rewards, dones
+and values, so compute_returns() runs PPO's own returns machinery ahead of the teacher's pass and update() calls hgym_bc_vf_grad in place
+of hgym_bc_grad -- the student's gradient path is the same, so the student keeps the bits of a run with the option off, and the checkpoint
+leaves with a critic trained on the student's own returns.
 """
 import math
 
@@ -23,6 +28,9 @@ NO_CLIP = 3.0e38      # max_grad_norm=None: a clip that never binds (coef = min(
 class Distillation(PPO):
     policy: StudentTeacher
     LOSS_TYPES = ("mse", "huber")
+    # the critic is trained beside the student, on PPO's returns of the student's own rollouts: value_loss_coef, use_clipped_value_loss,
+    # clip_param, gamma and lam are PPO's attributes of those names (PPO's defaults unless set).  Read once, in init_storage.
+    train_critic = False
 
     def __init__(self, policy, num_learning_epochs=1, gradient_length=15, learning_rate=1e-3, max_grad_norm=None, loss_type="mse",
                  huber_delta=1.0, device="cpu"):
@@ -41,7 +49,8 @@ class Distillation(PPO):
         self.gradient_length = int(gradient_length)
         self.loss_type, self.huber_delta = loss_type, float(huber_delta)
         self.last_behavior_loss = None
-        self._bc_sums = None
+        self.last_value_loss = None      # train_critic: the mean value loss per Adam step of the last update read
+        self._bc_sums = self._vf_sums = None
 
     @staticmethod
     def check_setup(policy, num_transitions_per_env, gradient_length, world=1, symmetry=None, mirror_loss_coef=0.0,
@@ -70,6 +79,9 @@ class Distillation(PPO):
         from . import guidance as guide_module
         if guide_module.parse_config(self.guidance) is not None:
             guide_module.check_setup(distillation=True)
+        from . import critic_warmup as warmup_module
+        if warmup_module.parse_config(self.critic_warmup_updates) > 0:
+            raise ValueError("PPO.critic_warmup_updates does not support Distillation: Distillation.train_critic trains the critic beside the student")
         if self.value_normalization:      # (a follow-up at most: a cloning run computes no returns, the critic is not trained)
             raise ValueError("PPO.value_normalization does not support Distillation: a cloning run has no returns to standardise")
         self.check_setup(self.actor_critic, num_transitions_per_env, self.gradient_length, self._world, self.symmetry,
@@ -77,6 +89,8 @@ class Distillation(PPO):
         # one "minibatch" is one slice: gradient_length * N rows (PPO.init_storage sizes the net's max_batch from it)
         self.num_mini_batches = int(num_transitions_per_env) // self.gradient_length
         self._bc_sums = torch.zeros(2, dtype=torch.float64, device=self.device)      # (ahead of PPO's part, which ends by building the log block)
+        self._train_critic = bool(self.train_critic)
+        self._vf_sums = torch.zeros(2, dtype=torch.float64, device=self.device) if self._train_critic else None
         super().init_storage(num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape)
         hgym, st = self._hgym, self.storage
         T, N = st.num_transitions_per_env, st.num_envs
@@ -86,6 +100,8 @@ class Distillation(PPO):
         self._ppo_cfg = hgym.make_ppo_config(max_grad_norm=self.max_grad_norm, desired_kl=0.0, adaptive=False, world_size=1,
                                              grad_norm_ready=False)
         self._rows = torch.arange(T * N, dtype=torch.int64, device=self.device)
+        if self._train_critic:      # (make_vf_config refuses a clip range or a coefficient that is negative or not finite: ValueError)
+            self._vf_cfg = hgym.make_vf_config(self.clip_param, self.value_loss_coef, clipped_value_loss=bool(self.use_clipped_value_loss))
 
     # ------------------------------------------------------------------
     def compute_returns(self, last_critic_obs):
@@ -94,6 +110,10 @@ class Distillation(PPO):
         on the deferred-values path."""
         st = self.storage
         T = st.num_transitions_per_env
+        if self._train_critic:
+            # PPO's own returns first: the deferred critic where the rollout left it, the time-out bootstrap, GAE (the advantages are a
+            # by-product nobody reads)
+            PPO.compute_returns(self, last_critic_obs)
         self.actor_critic.teacher_pass(st._obs_all[:T].flatten(0, 1), st.teacher_actions.flatten(0, 1))
         self._returns_done()
 
@@ -114,25 +134,43 @@ class Distillation(PPO):
         obs, target = st._obs_all[:T].flatten(0, 1), st.teacher_actions.flatten(0, 1)
         sh = st.shadows()
         self._bc_sums[0:2] = 0.0
+        critic = self._train_critic
+        if critic:
+            self._vf_sums[0:2] = 0.0
+            cols = st.batch_columns()      # (obs, priv, ., values, ., returns, ...): the T N stored rows
+            assert cols[0].data_ptr() == obs.data_ptr()
         for _ in range(self.num_learning_epochs):
             for k in range(T // self.gradient_length):
-                batch = hgym.make_bc_batch(obs, self._rows[k * mb:(k + 1) * mb], None if sh is None else sh[0])
-                net.bc_grad(self._bc_cfg, batch, target, self._bc_sums)
+                rows = self._rows[k * mb:(k + 1) * mb]
+                if critic:      # the student's regression and the critic's value loss in one call: bc_grad, then vf_grad beside it, bit for bit
+                    batch = hgym.make_vf_batch(cols[1], cols[3], cols[5], rows, priv_bf16=None if sh is None else sh[1], obs=obs,
+                                               obs_bf16=None if sh is None else sh[0])
+                    net.bc_vf_grad(self._bc_cfg, self._vf_cfg, batch, target, self._bc_sums, self._vf_sums)
+                else:
+                    batch = hgym.make_bc_batch(obs, rows, None if sh is None else sh[0])
+                    net.bc_grad(self._bc_cfg, batch, target, self._bc_sums)
                 net.ppo_apply(self._ppo_cfg)
         st.rotate()
         self._update_done()
         if not sync:
             return None, None
         self.read_log(self.log_block().cpu())
-        return 0.0, self.last_behavior_loss
+        return (self.last_value_loss if critic else 0.0), self.last_behavior_loss
 
     def _log_parts(self):
-        """opt | bc(2): opt_state and, behind it, the behaviour loss's two sums (every option of PPO's block is refused here)."""
-        return [("opt", self.net.opt_state), ("bc", self._bc_sums)]
+        """opt | bc(2) | vf(2): opt_state and, behind it, the behaviour loss's two sums, then -- train_critic -- the value loss's two (every
+        option of PPO's block is refused here)."""
+        vf = getattr(self, "_vf_sums", None)
+        return [("opt", self.net.opt_state), ("bc", self._bc_sums)] + ([] if vf is None else [("vf", vf)])
 
-    def read_log(self, block):      # PPO's, and last_behavior_loss; log_scalars: Loss/behavior behind PPO's pairs
+    def read_log(self, block):      # PPO's, and last_behavior_loss, last_value_loss; log_scalars: Loss/behavior behind PPO's pairs
         self.last_behavior_loss = self.behavior_loss_from(block)
-        return super().read_log(block)
+        o = super().read_log(block)
+        parts = self._log.split(block)
+        if "vf" in parts:      # train_critic: Loss/value_function is the critic's mean value loss per Adam step
+            self.last_value_loss = mean_of_sums(parts["vf"])
+            o = dict(o, mean_value_loss=self.last_value_loss)
+        return o
 
     def log_scalars(self):
         return super().log_scalars() + ([] if self.last_behavior_loss is None else [("Loss/behavior", self.last_behavior_loss)])

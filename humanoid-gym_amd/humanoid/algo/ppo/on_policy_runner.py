@@ -162,7 +162,7 @@ def _split_algorithm_cfg(alg_cfg):
     off), not a parameter of the reference's PPO: it is taken out here and becomes PPO.symmetry.  The mirror loss's keys (SYMMETRY_KEYS)
     are taken out as well; _split_symmetry_cfg reads them.  So are the advantage normalisation's (ADVANTAGE_KEYS; _split_advantage_cfg)."""
     kwargs = dict(alg_cfg)
-    for k in SYMMETRY_KEYS + ADVANTAGE_KEYS + VALUE_NORM_KEYS + (RND_KEY, SMOOTH_KEY, GUIDE_KEY):
+    for k in SYMMETRY_KEYS + ADVANTAGE_KEYS + VALUE_NORM_KEYS + (RND_KEY, SMOOTH_KEY, GUIDE_KEY, WARMUP_KEY, TRAIN_CRITIC_KEY):
         kwargs.pop(k, None)
     return kwargs, bool(kwargs.pop("symmetry", False))
 
@@ -171,6 +171,10 @@ ADVANTAGE_KEYS = ("advantage_normalization", "normalize_advantage_per_mini_batch
 SMOOTH_KEY = "smoothness_cfg"      # the smoothness regulariser's block (humanoid.algo.ppo.smoothness.parse_config); absent or None: off
 VALUE_NORM_KEYS = ("value_normalization", "value_normalization_eps")      # PPO.value_normalization / _eps; neither is a parameter of PPO.__init__
 GUIDE_KEY = "guidance_cfg"      # guidance by a frozen teacher (humanoid.algo.ppo.guidance.parse_config); absent or None: off
+WARMUP_KEY = "critic_warmup_updates"      # PPO.critic_warmup_updates: the first n updates move the critic alone; absent or 0: off
+TRAIN_CRITIC_KEY = "train_critic"      # Distillation.train_critic: a cloning run also trains the critic; absent: off
+# with it, PPO's own value-loss and returns settings from the same block: not parameters of Distillation.__init__, set as attributes
+DISTILL_CRITIC_KEYS = ("value_loss_coef", "use_clipped_value_loss", "clip_param", "gamma", "lam")
 RND_KEY = "rnd_cfg"      # rsl_rl's Random Network Distillation block (humanoid.algo.ppo.rnd.parse_config); absent or None: off
 
 
@@ -247,7 +251,16 @@ class OnPolicyRunner:
         alg_class = eval(self.cfg["algorithm_class_name"])  # PPO
         alg_kwargs, symmetry = _split_algorithm_cfg(self.alg_cfg)
         augmentation, mirror_loss_coef = _split_symmetry_cfg(self.alg_cfg)
+        distill_critic = {k: alg_kwargs.pop(k) for k in DISTILL_CRITIC_KEYS if k in alg_kwargs} if issubclass(alg_class, Distillation) else {}
         self.alg = alg_class(actor_critic, device=self.device, **alg_kwargs)
+        for k, v in distill_critic.items():      # Distillation.train_critic's value loss and returns; read by init_storage / compute_returns
+            setattr(self.alg, k, v)
+        if self.alg_cfg.get(TRAIN_CRITIC_KEY) is not None:      # read by init_storage below
+            if not issubclass(alg_class, Distillation):
+                raise ValueError("algorithm.train_critic is Distillation's option; %s trains its critic anyway" % alg_class.__name__)
+            self.alg.train_critic = bool(self.alg_cfg[TRAIN_CRITIC_KEY])
+        if self.alg_cfg.get(WARMUP_KEY) is not None:      # critic-only warm-up; read by init_storage below
+            self.alg.critic_warmup_updates = self.alg_cfg[WARMUP_KEY]
         if symmetry or augmentation or mirror_loss_coef > 0.0:        # left-right symmetry with XBot-L's tables; read by init_storage below
             from humanoid.utils.symmetry import xbot_l_mirror
             self.alg.symmetry = xbot_l_mirror(self.env.cfg)
@@ -353,9 +366,13 @@ class OnPolicyRunner:
                 diag_now = diag_every > 0 and (it + 1) % diag_every == 0
                 if diag_now:
                     alg.diagnostics_prepare()       # slot 0's observation rows, before the update's clear() rotates them away
-                if plan.graph_update and getattr(alg, "_guide", None) is not None:
-                    # the one option whose graph key changes inside a run: when its schedule runs out the update is the plain one again
-                    alg._guide.retire_if_run_out()
+                if plan.graph_update and (getattr(alg, "_guide", None) is not None or getattr(alg, "_warmup", None) is not None):
+                    # the options whose graph key changes inside a run: when guidance's schedule runs out, or the last critic-only update
+                    # is done, the update is the plain one again
+                    if alg._guide is not None:
+                        alg._guide.retire_if_run_out()
+                    if alg._warmup is not None:
+                        alg._warmup.retire_if_done()
                     ukey = (gkey, alg.update_graph_key(), plan.fuse == "deferred")
                 mean_value_loss, mean_surrogate_loss = self._learn_step(plan, gkey, ukey, critic_obs, obs)
                 diag = alg.diagnostics(sync=False) if diag_now else None       # enqueued; read where this path reads anything
@@ -776,6 +793,8 @@ class OnPolicyRunner:
                                        value_norm=None if vn is None else (vn.block, vn.eps))
             if getattr(alg, "_guide", None) is not None:      # PPO.guidance: host data, formed here where the count is this checkpoint's
                 shot["guidance"] = alg._guide.state_dict()
+            if getattr(alg, "_warmup", None) is not None:      # PPO.critic_warmup_updates: host data, likewise
+                shot["critic_warmup"] = alg._warmup.state_dict()
             side = dict(env=shot["env"], **extra) if env_state else None
             ckpt.WRITER.submit(lambda: ckpt.write_snapshot(shot, type(alg.optimizer).HYPER, it, infos, path, side))
             if wait:
@@ -820,7 +839,9 @@ class OnPolicyRunner:
         if loaded is None:
             loaded = torch.load(path, map_location=self.device)
         ckpt.check_compatible(loaded, ac, alg._rnd, os.path.basename(str(path)), value_norm=ckpt.value_norm_spec(alg),
-                              guidance=getattr(alg, "_guide", None))
+                              guidance=getattr(alg, "_guide", None), critic_warmup=getattr(alg, "_warmup", None) is not None)
+        if getattr(alg, "_warmup", None) is not None:
+            alg._warmup.load_state_dict(loaded[ckpt.WARMUP_KEY])
         if getattr(alg, "_guide", None) is not None:
             alg._guide.load_state_dict(loaded[ckpt.GUIDE_KEY])
         if getattr(alg, "value_normalizer", None) is not None:

@@ -18,6 +18,7 @@ from .log_block import LogBlock
 from .mirror_loss import MirrorLoss
 from .normalizer import ValueNormalizer
 from .rollout_storage import RolloutStorage
+from . import critic_warmup as warmup_module
 from . import dist_utils
 from . import guidance as guide_module
 from . import rnd as rnd_module
@@ -59,6 +60,10 @@ class _DeviceAdam:
     def load_state_dict(self, sd):
         net = self._ppo.net
         base = net.params.data_ptr()
+        warm = getattr(self._ppo, "_warmup", None)
+        if warm is not None:      # critic-only updates remain: the actor's moments must be zero (refused before anything is changed)
+            warmup_module.check_moments(warm.remaining, [(name, sd["state"][i]["exp_avg"], sd["state"][i]["exp_avg_sq"])
+                                                         for i, name in enumerate(net.views) if i in sd["state"]])
         for i, (name, v) in enumerate(net.views.items()):
             if i in sd["state"]:
                 o = (v.data_ptr() - base) // 4
@@ -132,6 +137,14 @@ class PPO:
     # with PPO.smoothness, not with Distillation (ValueError from init_storage).  Read once, in init_storage.  `last_guidance`: {loss, coef}
     # of the last update.  DESIGN.md section 33.
     guidance = None
+    # critic-only warm-up: the first n updates of a run move the value function alone -- every minibatch step is hgym_vf_grad followed by
+    # hgym_ppo_apply with the learning-rate rule off; the actor, sigma and the learning rate keep their bits (zero gradient on zero Adam
+    # moments), and the actor-side options (mirror loss, smoothness, guidance and its schedule count) are not invoked.  For a checkpoint
+    # without a usable critic: a plain distillation run, an older policy, a changed reward.  compute_returns, value normalisation, both
+    # advantage modes and symmetry augmentation go on unchanged.  The count of updates done is host state: part of update_graph_key() (one
+    # re-capture at the switch) and of a checkpoint.  One rank; an optimiser state with non-zero actor moments is refused while updates
+    # remain (ValueError).  0: off.  Read once, in init_storage.  DESIGN.md section 34.
+    critic_warmup_updates = 0
 
     def __init__(self, actor_critic, num_learning_epochs=1, num_mini_batches=1, clip_param=0.2, gamma=0.998, lam=0.95,
                  value_loss_coef=1.0, entropy_coef=0.0, learning_rate=1e-3, max_grad_norm=1.0, use_clipped_value_loss=True,
@@ -159,7 +172,7 @@ class PPO:
         self.comm_timing = None      # a list: update() appends a pair of HIP events around the wait for the gradient exchange
         # every option's state, "off" until init_storage reads the option: nobody probes for these.  The four option
         # objects (MirrorLoss, RandomNetworkDistillation, Smoothness, ValueNormalizer; None: off) and those that are on (init_storage)
-        self._mirror_loss = self._rnd = self._smooth = self._guide = None      # (value_normalizer: the class attribute)
+        self._mirror_loss = self._rnd = self._smooth = self._guide = self._warmup = None      # (value_normalizer: the class attribute)
         self._options = self._scalar_order = ()
         self._symmetry = self._obs_norm = None
         self._augment, self._adv_mode = False, "batch"
@@ -233,6 +246,9 @@ class PPO:
         PPO.check_setup(num_envs, num_transitions_per_env, self.num_mini_batches, ac.num_actor_obs, self._world, self.symmetry,
                         self.symmetry_augmentation, self.mirror_loss_coef, self.advantage_normalization, self.rnd, self.smoothness,
                         bool(self.value_normalization), self.value_normalization_eps, self.guidance)
+        warmup = warmup_module.parse_config(self.critic_warmup_updates)
+        if warmup > 0:
+            warmup_module.check_setup(self._world)
         self._adv_mode = self.advantage_normalization
         self.storage = RolloutStorage(num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape, self.device)
         coef = float(self.mirror_loss_coef)
@@ -310,15 +326,18 @@ class PPO:
             self._guide = guide_module.Guidance(guide, ac, self.net, num_envs * num_transitions_per_env, self.device)
             self.storage.enable_guidance(ac.num_actions)
             self._guide.bind_storage(self.storage)
+        if warmup > 0:      # the value-loss and apply configurations of the critic-only updates, the log's three doubles
+            self._warmup = warmup_module.CriticWarmup(warmup, self._ppo_cfg, self.clip_param, self.value_loss_coef,
+                                                      bool(self.use_clipped_value_loss), self.device)
         # the options that are on, in the two orders that are fixed: the log block's byte layout (checkpoints, tools and tests hold such
         # blocks) and the order in which the writer gets their scalars.  A new option goes at the end of both.
         on = lambda *options: tuple(o for o in options if o is not None)
-        self._options = on(self._mirror_loss, self._rnd, self._smooth, self.value_normalizer, self._guide)
-        self._scalar_order = on(self._mirror_loss, self._smooth, self._rnd, self.value_normalizer, self._guide)
+        self._options = on(self._mirror_loss, self._rnd, self._smooth, self.value_normalizer, self._guide, self._warmup)
+        self._scalar_order = on(self._mirror_loss, self._smooth, self._rnd, self.value_normalizer, self._guide, self._warmup)
         self._log = LogBlock(self._log_parts())
 
     def _log_parts(self):
-        """opt | mirror(2) | rnd_sums(2) | rnd_block(RND_HEADER) | smooth(4) | value_norm(3) | guide(2) | guide_coef(1): opt_state, then the part(s) of every option that
+        """opt | mirror(2) | rnd_sums(2) | rnd_block(RND_HEADER) | smooth(4) | value_norm(3) | guide(2) | guide_coef(1) | critic_warmup(3): opt_state, then the part(s) of every option that
         is on; value_norm is the statistics' block itself (count, mean, var)."""
         return [("opt", self.net.opt_state)] + [part for o in self._options for part in o.log_parts()]
 
@@ -499,9 +518,12 @@ class PPO:
                            normalize=self._adv_mode == "batch")
         if vn is not None:      # merge the raw returns FIRST, then returns and old values into the critic's units under the new statistics
             vn.normalize_targets(st.returns, st.values)
+        warming = self._warmup is not None and self._warmup.active      # critic-only: no actor-side option is invoked
+        if self._warmup is not None:
+            self._warmup.retire_if_done()        # (once, and never inside a capture)
         if self._guide is not None:
             self._guide.retire_if_run_out()      # (once, and never inside a capture)
-            if self._guide.active:               # the teacher's mean of the T N stored rows, for every minibatch of every epoch
+            if self._guide.active and not warming:      # the teacher's mean of the T N stored rows, for every minibatch of every epoch
                 self._guide.teacher_pass(st)
         self._returns_done()
 
@@ -535,7 +557,7 @@ class PPO:
                    # (the mirror loss's coefficient is also part of ppo_cfg's bytes; augment: whether the batch is doubled)
                    mirror_coef=0.0, augment=self._augment, mirror_scratch=None, smoothness=None, rnd=None,
                    adv_mode=self._adv_mode, adv_scratch=st.minibatch_advantages_key(), obs_norm=self._obs_norm, value_norm=None,
-                   guidance=None)
+                   critic_warmup=False, guidance=None)
         for o in self._options:
             key.update(o.graph_key())
         return tuple(key.items())
@@ -565,7 +587,9 @@ class PPO:
         self._diag_updated = True
         if self._direct_exchange():
             self._comm_direct_used = True
-        if self._guide is not None:
+        if self._warmup is not None and self._warmup.active:
+            self._warmup.update_done()           # (a critic-only update: guidance's schedule count stays where it is)
+        elif self._guide is not None:
             self._guide.update_done()
 
     def update(self, sync=True):
@@ -576,6 +600,9 @@ class PPO:
         T, N = st.num_transitions_per_env, st.num_envs
         sym, aug, mirror_loss, smooth = self._symmetry is not None, self._augment, self._mirror_loss, self._smooth
         guide = self._guide if (self._guide is not None and self._guide.active) else None      # (run out: the plain update)
+        warm = self._warmup if (self._warmup is not None and self._warmup.active) else None     # critic-only: hgym_vf_grad in place of hgym_ppo_grad*
+        if warm is not None:
+            mirror_loss = smooth = guide = None      # the actor-side options are not invoked
         if sym:
             # the mirrored half of every column, from the finished rollout (returns, advantages, values, shadows: all there); the mirror
             # loss alone reads only the mirrored observations
@@ -619,9 +646,19 @@ class PPO:
         if guide is not None:      # this update's coefficient, formed on the device; the two sums zeroed
             guide.begin_update()
             guided = guide.minibatch()      # (the same descriptor for every minibatch: the column is gathered through the batch's idx)
+        if warm is not None:       # the two sums zeroed, the log's count moved on
+            warm.begin_update()
         for _ in range(self.num_learning_epochs):
             for i in range(self.num_mini_batches):
                 idx = perm[i * mb:(i + 1) * mb]
+                if warm is not None:      # the critic alone: its gradient, +0.0 everywhere else, then the step with the learning-rate rule off
+                    net.vf_grad(warm.vf_cfg, hgym.make_vf_batch(cols[1], cols[3], cols[5], idx, priv_bf16=sh.get("priv_bf16")), warm.sums)
+                    if self._obs_norm is not None:
+                        net.norm_unfold_grad()
+                    net.ppo_apply(warm.apply_cfg)
+                    if self._rnd is not None:
+                        self._rnd.train_step(st, idx)
+                    continue
                 mirror = {} if mirror_loss is None else mirror_loss.minibatch(pair[i * mb:(i + 1) * mb], st)
                 batch = hgym.make_batch(*cols, idx, **mirror, **sh)
                 if smooth is not None and mirror_loss is not None:      # one actor head for the three detached-target terms
@@ -680,6 +717,8 @@ class PPO:
             option.read_log(parts)
         o = self._hgym.opt_summary(parts["opt"], self._ppo_cfg.aux_coef > 0.0)
         self.last_denoise_loss = o["denoise_loss"]
+        if self._warmup is not None and self._warmup.last["trained"]:      # a critic-only update: its value loss, no surrogate
+            o = dict(o, mean_value_loss=self._warmup.last["value_loss"], mean_surrogate_loss=0.0)
         return o
 
     def log_scalars(self):

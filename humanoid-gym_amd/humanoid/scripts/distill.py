@@ -3,7 +3,8 @@
 Distils a trained actor into the student of the task's StudentTeacher policy (Distillation).  The teacher is a PPO
 checkpoint, located with the existing --load_run / --checkpoint through get_load_path on the PPO experiment's log directory
 (the train config's `teacher_experiment_name`, XBot_ppo for humanoid_distill), as rsl_rl does; the run itself trains into the
-distillation experiment's own directory.  --resume continues a distillation run from its own checkpoint instead (make_alg_runner)."""
+distillation experiment's own directory.  --resume continues a distillation run from its own checkpoint instead (make_alg_runner).
+HGYM_DISTILL_CRITIC=1 sets the train config's `algorithm.train_critic` (Distillation.train_critic)."""
 import os
 import sys
 
@@ -26,6 +27,8 @@ def distill(args, teacher_log_root=None):
     train_cfg = task_registry.get_cfgs(args.task)[1]
     if train_cfg.runner.algorithm_class_name != "Distillation":
         raise ValueError("task %r does not train with Distillation (algorithm_class_name=%r)" % (args.task, train_cfg.runner.algorithm_class_name))
+    if os.environ.get("HGYM_DISTILL_CRITIC", "0") == "1":      # Distillation.train_critic: the run also trains the critic on its own returns
+        train_cfg.algorithm.train_critic = True
     resume = bool(args.resume)
     path = None if resume else teacher_path(train_cfg, args, teacher_log_root)      # (before the runner is built: a missing teacher costs nothing)
     runner, train_cfg = task_registry.make_alg_runner(env=env, name=args.task, args=args)

@@ -45,7 +45,11 @@ HGYM_GUIDE_TEACHER=<model_*.pt> with HGYM_GUIDE=<coef>[,<final_step>] sets `algo
 same way, with a final step also `"coef_schedule": {"mode": "linear", "initial_step": 0, "final_step": <final_step>, "final_value": 0}`: a
 frozen teacher's cloning term inside the PPO loss, coef / (B A) sum (mu - mu_teacher)^2, its coefficient formed on the device and, with a
 final step, decaying linearly to 0 over that many learning iterations, after which the update is the plain one again (PPO.guidance, DESIGN.md
-section 33); checkpoints carry guidance_state_dict, so --resume needs no teacher file.  Both unset: off; exactly one set: ValueError."""
+section 33); checkpoints carry guidance_state_dict, so --resume needs no teacher file.  Both unset: off; exactly one set: ValueError.
+
+HGYM_CRITIC_WARMUP=<n> sets `algorithm.critic_warmup_updates` the same way: the first n updates of the run move the value function alone
+(PPO.critic_warmup_updates), for a checkpoint whose critic was never trained; 0 or unset: off.
+"""
 import os
 import sys
 
@@ -96,6 +100,8 @@ def train(args):
         task_registry.get_cfgs(args.task)[1].algorithm.smoothness_cfg = {"temporal_coef": lam[0], "spatial_coef": lam[1] if len(lam) > 1 else 0.0}
     if os.environ.get("HGYM_VALUE_NORM", "0") == "1":
         task_registry.get_cfgs(args.task)[1].algorithm.value_normalization = True
+    if int(os.environ.get("HGYM_CRITIC_WARMUP", "0") or 0) > 0:      # PPO.critic_warmup_updates: the first n updates move the critic alone
+        task_registry.get_cfgs(args.task)[1].algorithm.critic_warmup_updates = int(os.environ["HGYM_CRITIC_WARMUP"])
     gc = guidance_cfg_from_env(os.environ)
     if gc is not None:
         task_registry.get_cfgs(args.task)[1].algorithm.guidance_cfg = gc

@@ -79,7 +79,9 @@ extern "C" {
                              *    (same version, later: hgym_ppo_grad_smooth_mirror -- the mirror loss and the smoothness regulariser in one
                              *    actor head; no layout changes)
                              *    (same version, later: hgym_guide_schedule, hgym_ppo_grad_guide, HgymGuideSchedule and HgymGuide -- a frozen
-                             *    teacher's cloning term with a device-resident coefficient; no layout changes) */
+                             *    teacher's cloning term with a device-resident coefficient; no layout changes)
+                             *    (same version, later: hgym_vf_grad, hgym_bc_vf_grad and HgymVFConfig -- one minibatch of the critic alone, and
+                             *    a cloning minibatch that also trains the critic; no layout changes) */
 
 enum {
     HGYM_OK = 0,
@@ -1239,6 +1241,47 @@ int32_t hgym_ppo_diagnostics(const HgymNetConfig* cfg, const HgymPPOConfig* ppo,
  * world_size here, as is the KL in grads[P] before the learning-rate decision), refreshes the
  * compute-precision shadows, bumps opt_state. */
 int32_t hgym_ppo_apply(const HgymNetConfig* cfg, const HgymPPOConfig* ppo, const HgymNet* net, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Critic only (header v9, no layout change): one minibatch of the value part of PPO.update up to and including
+ * backward -- the critic regresses on the stored returns, nothing else is trained.  With B rows, r_b = idx[b], v_b = V(priv[r_b]),
+ * R_b = returns[r_b], vold_b = values[r_b], c = clip_param:
+ *   clipped:    vc_b = vold_b + clamp(v_b - vold_b, -c, c),  L = sum_b max((v_b - R_b)^2, (vc_b - R_b)^2) / B   (ties of the max split evenly,
+ *               the clamp passes gradient on the closed range: torch's backward, as in hgym_ppo_grad)
+ *   unclipped:  L = sum_b (v_b - R_b)^2 / B                                              (HgymPPOConfig.value_loss_unclipped's form)
+ *   d v_b = value_coef / B * dL_b/dv_b: value_coef multiplies the gradient, not the reported loss.
+ * hgym_vf_grad reads batch->priv, priv_bf16 (optional: the bf16 shadow of priv, as in hgym_ppo_grad; 16-byte aligned), values (clipped
+ * form only), returns, idx, B and num_rows; every other member of HgymBatch may be NULL.  sums: two device doubles the caller zeroes,
+ * [0] += this minibatch's L, [1] += 1.
+ * After the call (stream order) net->grads holds the gradient of value_coef * L in the critic's weights and biases.  On the fused bf16
+ * path the critic's tiles, the weight-gradient products and the slab sums are the kernels hgym_ppo_grad runs for the critic: the critic
+ * region has that call's bits on the same inputs.  keep_others = 0: every other slot -- std / log_std, the actor, the auxiliary head, the
+ * KL slot -- is exactly +0.0 and opt_state[HGYM_OPT_GRAD_SQNORM] is SET to the critic's squared norm.  keep_others = 1: those slots are not
+ * touched and the critic's squared norm is ADDED to opt_state[HGYM_OPT_GRAD_SQNORM].  No other slot of opt_state is touched: no
+ * learning-rate decision, no loss sums, no step count.  The step is hgym_ppo_apply's, with adaptive_lr = 0 and grad_norm_ready = 0: zero
+ * gradient on zero moments moves nothing, so the actor and sigma keep their bits while their Adam moments are zero.
+ * HgymNet.norm is served as by hgym_ppo_grad (hgym_net_norm_unfold_grad follows, as there).  One rank.
+ * HGYM_E_BADARG before anything is launched: a NULL cfg, vf, net, batch or sums (sums 8-byte aligned); unclipped or keep_others outside
+ * {0, 1}; value_coef, or clip_param with the clipped form, negative, NaN or infinite; B < 1 or B > max_batch; NULL priv, returns or idx, or
+ * NULL values with the clipped form; a misaligned shadow.
+ *
+ * hgym_bc_vf_grad: a cloning step that also trains the critic.  net->grads, opt_state[HGYM_OPT_GRAD_SQNORM], bc_sums and vf_sums equal, bit
+ * for bit, hgym_bc_grad followed by hgym_vf_grad with keep_others = 1 (which vf->keep_others is ignored for) on the same inputs; the
+ * launches are fewer: the actor's tiles with the regression head, the critic's plain tiles, ONE weight-gradient launch with all
+ * products (every product is summed by workgroups of its own, whatever shares the launch), one slab pass, one scalars workgroup.
+ * Refuses what either of the two refuses. */
+typedef struct HgymVFConfig {
+    float clip_param;     /* value clip range (read unless unclipped) */
+    float value_coef;     /* multiplies the gradient, not the reported loss */
+    int32_t unclipped;    /* 1: (R - V)^2, as HgymPPOConfig.value_loss_unclipped */
+    int32_t keep_others;  /* 0: every gradient slot outside the critic's region becomes +0.0 and
+                             opt_state[HGYM_OPT_GRAD_SQNORM] is SET to the critic's squared norm;
+                             1: those slots are left as found and the critic's squared norm is ADDED */
+} HgymVFConfig;
+int32_t hgym_vf_grad(const HgymNetConfig* cfg, const HgymVFConfig* vf, const HgymNet* net, const HgymBatch* batch, double* sums,
+                     void* stream);
+int32_t hgym_bc_vf_grad(const HgymNetConfig* cfg, const HgymBCConfig* bc, const HgymVFConfig* vf, const HgymNet* net,
+                        const HgymBatch* batch, const float* target, double* bc_sums, double* vf_sums, void* stream);
 
 /* ---- direct gradient exchange over peer mappings (header v6 / v7; the alternative to the RCCL all-reduce of the data-parallel update
  * that HGYM_COMM=auto probes and picks at start-up:
