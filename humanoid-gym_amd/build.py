@@ -27,6 +27,7 @@ EXTRA = {
     "hgym_rollout_act.hip": ["-ffp-contract=off"],  # the same kernel with any resolved activation (hgym_rollout.hpp)
     "hgym_norm.hip": ["-ffp-contract=off"],         # the merge, the fold and the unfold as a test restates them, one rounding per operation
     "hgym_rnd.hip": ["-ffp-contract=off"],          # the reward pass as include/hgym.h states it and a test restates it, one rounding per operation
+    "hgym_noise.hip": ["-ffp-contract=off"],        # the noise table's filter sum as include/hgym.h states it and a test restates it, one rounding per multiply and per add
     "hgym_valnorm.hip": ["-ffp-contract=off"],      # the two fp32 maps as include/hgym.h states them (two roundings) and a test restates them in torch
 }
 

@@ -1883,7 +1883,7 @@ static int32_t run(const HgymNetConfig* cfg, const HgymNet* net, void* stream, F
 // XBot-L's first hidden widths (actor 512, critic 768: the instantiations the rollout kernel carries).
 int32_t rollout_fwd_args(const HgymNetConfig* cfg, const HgymNet* net, int M, const float* obs, const float* priv, uint64_t seed,
                          const int64_t* step, float* actions, float* mu, float* sigma, float* logp, float* values, FwdArgs* out,
-                         size_t* lds_bytes, const HgymObsShadow* sh) {
+                         size_t* lds_bytes, const HgymObsShadow* sh, const float* z) {
     WsLayout w;
     int32_t rc = check_net(cfg, net, &w);
     if (rc) return rc;
@@ -1895,7 +1895,7 @@ int32_t rollout_fwd_args(const HgymNetConfig* cfg, const HgymNet* net, int M, co
     if (rc) return rc;
     const FusedPath R(net_base(cfg, net, w, nullptr));
     const NetIO io[3] = {{obs, cfg->num_obs, mu, cfg->num_actions}, {priv, cfg->num_priv, values, 1}, {}};
-    const FusedPath::SampleOut smp = {nullptr, seed, step, actions, sigma, logp};
+    const FusedPath::SampleOut smp = {z, seed, step, actions, sigma, logp};
     *out = R.make_fwd_args(0, 2, M, io, nullptr, false, &smp, nullptr, sh);
     out->nets = 2;
     *lds_bytes = fwd_lds(*out, 2, 32);

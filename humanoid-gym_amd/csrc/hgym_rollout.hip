@@ -77,7 +77,18 @@ int32_t hgym_rollout_step(const HgymNetConfig* cfg, const HgymNet* net, const Hg
                           const HgymEnvState* st, const HgymEnvOut* out, const HgymEnvOut* prev_out, const float* obs, const float* priv,
                           uint64_t seed, float* actions, float* mu, float* sigma, float* logp, float* values, void* scratch,
                           int32_t parity, const HgymObsShadow* shadow, void* stream) {
+    return hgym_rollout_step_z(cfg, net, env_cfg, sim, st, out, prev_out, obs, priv, seed, actions, mu, sigma, logp, values, scratch, parity,
+                               shadow, stream, nullptr);
+}
+
+// hgym_rollout_step with this step's (num_envs, 12) normals in place of the actor epilogue's own draw (a row of hgym_policy_noise_table's
+// table): the same kernels, launched with FwdArgs.z set -- a host-side difference only.  z = NULL: hgym_rollout_step itself.
+int32_t hgym_rollout_step_z(const HgymNetConfig* cfg, const HgymNet* net, const HgymEnvConfig* env_cfg, const HgymSimTensors* sim,
+                            const HgymEnvState* st, const HgymEnvOut* out, const HgymEnvOut* prev_out, const float* obs, const float* priv,
+                            uint64_t seed, float* actions, float* mu, float* sigma, float* logp, float* values, void* scratch,
+                            int32_t parity, const HgymObsShadow* shadow, void* stream, const float* z) {
     HG_REQUIRE(cfg && net && env_cfg && sim && st && out && scratch, HGYM_E_BADARG, "null argument");
+    HG_REQUIRE(((uintptr_t)z & 3) == 0, HGYM_E_BADARG, "z must be 4-byte aligned");
     const bool nocritic = values == nullptr;      // deferred values (header v7): hgym_critic_values runs after the rollout
     HG_REQUIRE(obs && actions && mu && sigma && logp && (nocritic || priv), HGYM_E_BADARG, "null policy buffer");
     HG_REQUIRE(parity == 0 || parity == 1, HGYM_E_BADARG, "parity=%d", parity);
@@ -95,7 +106,7 @@ int32_t hgym_rollout_step(const HgymNetConfig* cfg, const HgymNet* net, const Hg
     memset(&fin, 0, sizeof(fin));
     pp.prev_reset = nullptr;
     size_t lds_pol = 0;
-    int32_t rc = rollout_fwd_args(cfg, net, M, obs, priv, seed, &scr->pp[parity][2], actions, mu, sigma, logp, values, &f, &lds_pol, shadow);
+    int32_t rc = rollout_fwd_args(cfg, net, M, obs, priv, seed, &scr->pp[parity][2], actions, mu, sigma, logp, values, &f, &lds_pol, shadow, z);
     if (rc) return rc;
     rc = rollout_env_args(env_cfg, sim, st, out, actions, &e);
     if (rc) return rc;

@@ -14,7 +14,7 @@ namespace hgym {
 
 int32_t rollout_fwd_args(const HgymNetConfig* cfg, const HgymNet* net, int M, const float* obs, const float* priv, uint64_t seed,
                          const int64_t* step, float* actions, float* mu, float* sigma, float* logp, float* values, FwdArgs* out,
-                         size_t* lds_bytes, const HgymObsShadow* sh);
+                         size_t* lds_bytes, const HgymObsShadow* sh, const float* z = nullptr);      // z: this step's (M, A) normals in place of the launch's own draw (FwdArgs.z)
 int32_t rollout_eval_fwd_args(const HgymNetConfig* cfg, const HgymNet* net, int M, const float* obs, float* actions, FwdArgs* out,
                               size_t* lds_bytes);
 int32_t rollout_env_args(const HgymEnvConfig* cfg, const HgymSimTensors* sim, const HgymEnvState* st, const HgymEnvOut* out,

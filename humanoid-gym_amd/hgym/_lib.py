@@ -282,6 +282,11 @@ SYMBOLS = {
     "hgym_rollout_step": (C.c_int32, [_P(NetConfig), _P(Net), _P(EnvConfig), _P(SimTensors), _P(EnvState), _P(EnvOut), _P(EnvOut), c_float_p,
                                       c_float_p, C.c_uint64, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, C.c_void_p, C.c_int32,
                                       _P(ObsShadow), C.c_void_p]),
+    "hgym_rollout_step_z": (C.c_int32, [_P(NetConfig), _P(Net), _P(EnvConfig), _P(SimTensors), _P(EnvState), _P(EnvOut), _P(EnvOut), c_float_p,
+                                        c_float_p, C.c_uint64, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, C.c_void_p, C.c_int32,
+                                        _P(ObsShadow), C.c_void_p, c_float_p]),
+    "hgym_policy_noise_table": (C.c_int32, [C.c_int32, C.c_int64, C.c_int32, c_float_p, C.c_int64, c_float_p, c_float_p, C.c_uint64, c_i64_p,
+                                            c_float_p, C.c_void_p]),
     "hgym_rollout_end": (C.c_int32, [_P(EnvConfig), _P(EnvState), _P(EnvOut), C.c_void_p, C.c_int32, C.c_void_p]),
     "hgym_rollout_eval_step": (C.c_int32, [_P(NetConfig), _P(Net), _P(EnvConfig), _P(SimTensors), _P(EnvState), _P(EnvOut), _P(EnvOut), c_float_p,
                                            c_float_p, C.c_void_p, C.c_int32, C.c_void_p]),
@@ -309,6 +314,8 @@ SYMBOLS = {
     "hgym_prof_summary": (C.c_int32, [C.c_int32, _P(C.c_int64), _P(C.c_double), _P(C.c_double)]),
 }
 PROF_GEMM, PROF_ENV_STEP, PROF_GAE, PROF_LOSS, PROF_MLP_FWD, PROF_MLP_BWD, PROF_DW, PROF_REDUCE, PROF_APPLY, PROF_POLICY, PROF_ROLLOUT, PROF_COMM = range(12)
+NOISE_MAX_STEPS = 128     # HGYM_NOISE_MAX_STEPS: the longest table hgym_policy_noise_table fills
+SLOT_POLICY = 64          # hgym_common.hpp slot map: 64 .. 66 = the 12 policy-sampling normals of one env and step
 ROLLOUT_SCRATCH_HEADER_BYTES = 512
 ROLLOUT_DRAW_BYTES_PER_ENV = 1000
 

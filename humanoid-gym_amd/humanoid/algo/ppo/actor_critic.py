@@ -176,17 +176,18 @@ class ActorCritic(nn.Module):
         mu = net.forward(0, observations.contiguous())
         self._last = dict(mu=mu, sigma=mu * 0.0 + self.noise_std)
 
-    def act(self, observations, critic_observations=None, out=None, env_fin=None, shadow=None, **kwargs):
-        """Sample actions.  With critic_observations the critic runs in the same call (what PPO.act needs)."""
+    def act(self, observations, critic_observations=None, out=None, env_fin=None, shadow=None, z=None, **kwargs):
+        """Sample actions.  With critic_observations the critic runs in the same call (what PPO.act needs).  z (native extension):
+        (M, num_actions) standard normals in place of the launch's own draw (PPO.exploration_noise)."""
         net = self._need_net()
         if critic_observations is None:
             self.update_distribution(observations)
-            z = torch.randn_like(self._last["mu"])
+            z = torch.randn_like(self._last["mu"]) if z is None else z
             a = self._last["mu"] + self._last["sigma"] * z
             self._last["actions"] = a
             return a
         self._last = net.act(observations.contiguous(), critic_observations.contiguous(), seed=self._sample_seed,
-                             step_counter=self._sample_step, out=out, env_fin=env_fin, shadow=shadow)
+                             step_counter=self._sample_step, out=out, env_fin=env_fin, shadow=shadow, z=z)
         return self._last["actions"]
 
     def get_actions_log_prob(self, actions):

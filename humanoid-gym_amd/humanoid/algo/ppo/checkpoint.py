@@ -110,6 +110,31 @@ def extra_entries(alg):
     return extra
 
 
+def sidecar_entries(alg, buf=None):
+    """What the exact-resume sidecar carries beside the env's state and the run's counters: the AR(1) state of PPO.exploration_noise under
+    exploration_noise.SIDECAR_KEY (a filter without a carried state, or the option off: nothing).  model_<it>.pt never changes with the
+    option, so any checkpoint loads under any noise setting.  buf: the background path's snapshot buffer set (Snapshot.next_set) -- the
+    state is copied stream-ordered into a pinned member of it, made on first use like the set's "norm" and "env" members."""
+    from .exploration_noise import SIDECAR_KEY
+    noise = getattr(alg, "_noise", None)
+    if noise is None or noise.state is None:
+        return {}
+    out = None
+    if buf is not None:
+        if "noise" not in buf:
+            buf["noise"] = torch.empty(noise.state.shape, dtype=torch.float32).pin_memory()
+        out = buf["noise"]
+    sd = noise.state_dict(out=out)
+    return {} if sd is None else {SIDECAR_KEY: sd}
+
+
+def load_sidecar_entries(side, alg):
+    """sidecar_entries() of a loaded sidecar back into `alg`; an entry this run has no use for is ignored, a missing one leaves the state as built."""
+    from .exploration_noise import SIDECAR_KEY
+    if getattr(alg, "_noise", None) is not None:
+        alg._noise.load_state_dict(side.get(SIDECAR_KEY))
+
+
 def param_layout(state_dict, params):
     """[(name, offset, shape)] of every state_dict entry in the flat vector `params`: state_dict order = nn.Module's named_parameters
     order.  Every entry must be an fp32 view INTO the flat vector (assemble cuts by offset and shape only)."""
@@ -171,6 +196,13 @@ class Snapshot:
         for b in self.sets:
             b["busy"].set()
         self.n = 0
+
+    def next_set(self):
+        """The buffer set the next take() fills, once it is free: for a caller that enqueues a copy of its own into a member of the set
+        ahead of take()'s event (checkpoint.sidecar_entries)."""
+        buf = self.sets[self.n & 1]
+        buf["busy"].wait()
+        return buf
 
     def take(self, net, actor_critic, env=None, value_norm=None):
         """Enqueue the device -> pinned copies of one checkpoint (env: its state too) -> what write_snapshot needs: the buffer set, the event
@@ -259,13 +291,16 @@ def resolve_sidecar(path, env_state, world_size, holder):
     return side_path
 
 
-def check_sidecar(side, num_steps_per_env, env):
-    """A sidecar that does not fit this run or this env: refused before anything is changed."""
+def check_sidecar(side, num_steps_per_env, env, alg=None):
+    """A sidecar that does not fit this run, this env or (alg) this run's exploration-noise state: refused before anything is changed."""
     if int(side["world_size"]) != 1:
         raise ValueError("env state: world_size is %d in the sidecar; exact resume covers one rank" % int(side["world_size"]))
     if int(side["num_steps_per_env"]) != int(num_steps_per_env):
         raise ValueError("env state: num_steps_per_env is %d in the sidecar, %d here" % (int(side["num_steps_per_env"]), num_steps_per_env))
     env.check_state_dict(side["env"])
+    if getattr(alg, "_noise", None) is not None:
+        from .exploration_noise import SIDECAR_KEY
+        alg._noise.check_state_dict(side.get(SIDECAR_KEY))
 
 
 # ------------------------------------------------------------------ what load() refuses

@@ -162,7 +162,7 @@ def _split_algorithm_cfg(alg_cfg):
     off), not a parameter of the reference's PPO: it is taken out here and becomes PPO.symmetry.  The mirror loss's keys (SYMMETRY_KEYS)
     are taken out as well; _split_symmetry_cfg reads them.  So are the advantage normalisation's (ADVANTAGE_KEYS; _split_advantage_cfg)."""
     kwargs = dict(alg_cfg)
-    for k in SYMMETRY_KEYS + ADVANTAGE_KEYS + VALUE_NORM_KEYS + (RND_KEY, SMOOTH_KEY, GUIDE_KEY, WARMUP_KEY, TRAIN_CRITIC_KEY):
+    for k in SYMMETRY_KEYS + ADVANTAGE_KEYS + VALUE_NORM_KEYS + (RND_KEY, SMOOTH_KEY, GUIDE_KEY, WARMUP_KEY, TRAIN_CRITIC_KEY, NOISE_KEY):
         kwargs.pop(k, None)
     return kwargs, bool(kwargs.pop("symmetry", False))
 
@@ -175,6 +175,7 @@ WARMUP_KEY = "critic_warmup_updates"      # PPO.critic_warmup_updates: the first
 TRAIN_CRITIC_KEY = "train_critic"      # Distillation.train_critic: a cloning run also trains the critic; absent: off
 # with it, PPO's own value-loss and returns settings from the same block: not parameters of Distillation.__init__, set as attributes
 DISTILL_CRITIC_KEYS = ("value_loss_coef", "use_clipped_value_loss", "clip_param", "gamma", "lam")
+NOISE_KEY = "exploration_noise_cfg"      # temporally correlated exploration noise (humanoid.algo.ppo.exploration_noise.parse_config); absent or None: off
 RND_KEY = "rnd_cfg"      # rsl_rl's Random Network Distillation block (humanoid.algo.ppo.rnd.parse_config); absent or None: off
 
 
@@ -283,6 +284,8 @@ class OnPolicyRunner:
             self.alg.smoothness = sc
         if self.alg_cfg.get(GUIDE_KEY) is not None:      # guidance by a frozen teacher; read by init_storage below
             self.alg.guidance = dict(self.alg_cfg[GUIDE_KEY])
+        if self.alg_cfg.get(NOISE_KEY) is not None:      # temporally correlated exploration noise; read by init_storage below
+            self.alg.exploration_noise = dict(self.alg_cfg[NOISE_KEY])
         if self.alg_cfg.get("value_normalization") is not None:      # value targets standardised by running statistics; read by init_storage below
             self.alg.value_normalization = bool(self.alg_cfg["value_normalization"])
         if self.alg_cfg.get("value_normalization_eps") is not None:
@@ -782,12 +785,15 @@ class OnPolicyRunner:
         extra = dict(iterations_done=int(it if iterations_done is None else iterations_done), num_steps_per_env=int(self.num_steps_per_env),
                      world_size=int(getattr(alg, "_world", 1)), rank=int(getattr(alg, "_rank", 0))) if env_state else None
         if not ckpt.background_eligible(alg, self.device):
-            side = dict(env={k: (v.cpu() if torch.is_tensor(v) else v) for k, v in self.env.state_dict().items()}, **extra) if env_state else None
+            side = dict(env={k: (v.cpu() if torch.is_tensor(v) else v) for k, v in self.env.state_dict().items()}, **extra,
+                        **ckpt.sidecar_entries(alg)) if env_state else None
             ckpt.write_checkpoint({"model_state_dict": alg.actor_critic.state_dict(), "optimizer_state_dict": alg.optimizer.state_dict(),
                                    "iter": it, "infos": infos, **ckpt.extra_entries(alg)}, path, side)
         else:
             if getattr(self, "_snapshot", None) is None:
                 self._snapshot = ckpt.Snapshot(alg.net)
+            # PPO.exploration_noise: the AR(1) state rides in the sidecar; its copy is enqueued ahead of the snapshot's event
+            side_extra = ckpt.sidecar_entries(alg, buf=self._snapshot.next_set()) if env_state else {}
             vn = getattr(alg, "value_normalizer", None)      # PPO.value_normalization: its three doubles ride in the snapshot
             shot = self._snapshot.take(alg.net, alg.actor_critic, self.env if env_state else None,
                                        value_norm=None if vn is None else (vn.block, vn.eps))
@@ -795,7 +801,7 @@ class OnPolicyRunner:
                 shot["guidance"] = alg._guide.state_dict()
             if getattr(alg, "_warmup", None) is not None:      # PPO.critic_warmup_updates: host data, likewise
                 shot["critic_warmup"] = alg._warmup.state_dict()
-            side = dict(env=shot["env"], **extra) if env_state else None
+            side = dict(env=shot["env"], **extra, **side_extra) if env_state else None
             ckpt.WRITER.submit(lambda: ckpt.write_snapshot(shot, type(alg.optimizer).HYPER, it, infos, path, side))
             if wait:
                 ckpt.WRITER.wait()
@@ -835,7 +841,7 @@ class OnPolicyRunner:
         side, side_path = None, ckpt.resolve_sidecar(path, env_state, getattr(alg, "_world", 1), self)
         if side_path is not None:
             side = torch.load(side_path, map_location="cpu")
-            ckpt.check_sidecar(side, self.num_steps_per_env, self.env)      # (refused before anything is changed)
+            ckpt.check_sidecar(side, self.num_steps_per_env, self.env, alg)      # (refused before anything is changed)
         if loaded is None:
             loaded = torch.load(path, map_location=self.device)
         ckpt.check_compatible(loaded, ac, alg._rnd, os.path.basename(str(path)), value_norm=ckpt.value_norm_spec(alg),
@@ -858,6 +864,7 @@ class OnPolicyRunner:
             alg.seek(self.current_learning_iteration, self.num_steps_per_env)
         if side is not None:
             self.env.load_state_dict(side["env"])
+            ckpt.load_sidecar_entries(side, alg)      # PPO.exploration_noise: the AR(1) state the next rollout's table starts from
             self._keep_episode_lengths = True
         elif hasattr(self.env, "seek"):       # the env's draw streams (commands, pushes, noise, resets) continue as well
             self.env.seek(self.current_learning_iteration, self.num_steps_per_env)

@@ -20,6 +20,7 @@ from .normalizer import ValueNormalizer
 from .rollout_storage import RolloutStorage
 from . import critic_warmup as warmup_module
 from . import dist_utils
+from . import exploration_noise as noise_module
 from . import guidance as guide_module
 from . import rnd as rnd_module
 from . import smoothness as smooth_module
@@ -145,6 +146,15 @@ class PPO:
     # re-capture at the switch) and of a checkpoint.  One rank; an optimiser state with non-zero actor moments is refused while updates
     # remain (ValueError).  0: off.  Read once, in init_storage.  DESIGN.md section 34.
     critic_warmup_updates = 0
+    # temporally correlated exploration noise: None, or a dict {"kind": "ar1", "rho": r} / {"kind": "colored", "beta": b}
+    # (humanoid.algo.ppo.exploration_noise.parse_config) -- the normals of a rollout are a filtered sequence per (env, action) instead of
+    # fresh white draws at every step: one launch at the head of every rollout fills a (T, N, A) table from the very draws the policy
+    # launches would have made (hgym_policy_noise_table), and every policy launch reads its row in place of its own draw (act(): `z`; the
+    # one-launch rollout: hgym_rollout_step_z).  Each x_t stays N(0, 1), so logp, sigma, the ratio and the update are what they were: PPO
+    # treats the steps as independent.  The sequence does not restart at episode resets.  rho = 0 / beta = 0: the reference's noise, bit
+    # for bit.  Combines with every other option, with Distillation and with several ranks (no test runs it on more than one rank); at most 128 steps per rollout (ValueError from
+    # init_storage).  Read once, in init_storage.  DESIGN.md section 35.
+    exploration_noise = None
 
     def __init__(self, actor_critic, num_learning_epochs=1, num_mini_batches=1, clip_param=0.2, gamma=0.998, lam=0.95,
                  value_loss_coef=1.0, entropy_coef=0.0, learning_rate=1e-3, max_grad_norm=1.0, use_clipped_value_loss=True,
@@ -172,7 +182,7 @@ class PPO:
         self.comm_timing = None      # a list: update() appends a pair of HIP events around the wait for the gradient exchange
         # every option's state, "off" until init_storage reads the option: nobody probes for these.  The four option
         # objects (MirrorLoss, RandomNetworkDistillation, Smoothness, ValueNormalizer; None: off) and those that are on (init_storage)
-        self._mirror_loss = self._rnd = self._smooth = self._guide = self._warmup = None      # (value_normalizer: the class attribute)
+        self._mirror_loss = self._rnd = self._smooth = self._guide = self._warmup = self._noise = None      # (value_normalizer: the class attribute)
         self._options = self._scalar_order = ()
         self._symmetry = self._obs_norm = None
         self._augment, self._adv_mode = False, "batch"
@@ -249,6 +259,9 @@ class PPO:
         warmup = warmup_module.parse_config(self.critic_warmup_updates)
         if warmup > 0:
             warmup_module.check_setup(self._world)
+        noise = noise_module.parse_config(self.exploration_noise)
+        if noise is not None:
+            noise_module.check_setup(num_transitions_per_env, ac.num_actions)
         self._adv_mode = self.advantage_normalization
         self.storage = RolloutStorage(num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape, self.device)
         coef = float(self.mirror_loss_coef)
@@ -316,6 +329,9 @@ class PPO:
         ac._sample_step = self._sample_step
         # exploration-noise key: from the run's seed (as the permutation key above) and the rank
         ac._sample_seed = (torch.initial_seed() * 0xD1342543DE82EF95 + 0x5EED + 7919 * self._rank) & 0xFFFFFFFFFFFFFFFF
+        if noise is not None:      # the filter, the AR(1) state (seeded like the key above), the table of one rollout
+            self._noise = noise_module.ExplorationNoise(noise, num_transitions_per_env, num_envs, ac.num_actions, self.device,
+                                                        seed=ac._sample_seed ^ 0xA5A5A5A5A5A5A5A5)
         if self.rnd is not None:      # two more NetBuffers at the PPO precision, the reward pass's block, the storage's rnd_* fields
             self._rnd = self.rnd.bind(int(self.net.cfg.precision), max(mb, 1), self.device, num_envs)
             self.storage.enable_rnd(self._rnd.num_states, self._rnd.num_outputs)
@@ -334,6 +350,8 @@ class PPO:
         on = lambda *options: tuple(o for o in options if o is not None)
         self._options = on(self._mirror_loss, self._rnd, self._smooth, self.value_normalizer, self._guide, self._warmup)
         self._scalar_order = on(self._mirror_loss, self._smooth, self._rnd, self.value_normalizer, self._guide, self._warmup)
+        if self._noise is not None:      # (nothing in the update sees it: no log part, no entry in update_graph_key -- rollout_graph_key has it)
+            self._scalar_order += (self._noise,)
         self._log = LogBlock(self._log_parts())
 
     def _log_parts(self):
@@ -392,7 +410,14 @@ class PPO:
                                    and st._priv_all is not None and critic_obs.data_ptr() == st._priv_all[s].data_ptr()) else None
         # obs IS the slot: a zero-copy rollout, whose env writes step s + 1's observations into slot s + 1 -- at the last step, slot T
         self._slot_T_written = out is not None and obs.data_ptr() == st._obs_all[s].data_ptr()
-        t.actions = self.actor_critic.act(obs, critic_obs, out=out, env_fin=env_fin, shadow=sh)
+        z = None
+        if self._noise is not None:      # the rollout's table at its first step (the sampling step is read on the device), then this step's row
+            # (every act() at storage.step == 0 fills all T rows and moves the AR(1) state on by T steps: a second call there, or a
+            # stepwise rollout that stops early, leaves the state ahead of the steps taken -- still a draw of the stationary process)
+            if s == 0:
+                self._noise.fill(self._sample_step, self.actor_critic._sample_seed)
+            z = self._noise.row(s) if s < st.num_transitions_per_env else None
+        t.actions = self.actor_critic.act(obs, critic_obs, out=out, env_fin=env_fin, shadow=sh, z=z)
         last = self.actor_critic._last
         t.values, t.actions_log_prob = last["values"], last["logp"]
         if self.value_normalizer is not None:
@@ -416,7 +441,7 @@ class PPO:
         return dict(obs=st._obs_all, priv=st._priv_all, actions=st.actions, mu=st.mu, sigma=st.sigma, logp=st.actions_log_prob,
                     values=None if deferred else st.values, rewards=st.rewards, dones=st.dones, time_outs=st.time_outs if deferred else None,
                     obs_bf16=st._obs_bf16, priv_bf16=st._priv_bf16, step=self._sample_step, gamma=self.gamma,
-                    seed=self.actor_critic._sample_seed)
+                    seed=self.actor_critic._sample_seed, z=None if self._noise is None else self._noise.table)
 
     def _rows_overwritten(self):      # a rollout is writing the rows diagnostics() would read
         self._diag_saved = self._diag_updated = False
@@ -439,6 +464,8 @@ class PPO:
             raise AssertionError("Rollout buffer overflow")
         self._rows_overwritten()
         self._slot_T_written = True      # launch i writes slot i + 1
+        if self._noise is not None:      # the T rows the launches read, ahead of the first (the same sampling step hgym_rollout_begin reads)
+            self._noise.fill(self._sample_step, self.actor_critic._sample_seed, T)
         env.rollout_begin(self.net, self.rollout_columns(deferred), T, rows_ahead, l0_ahead)
         for i in range(T):
             env.rollout_step(i)
@@ -566,7 +593,9 @@ class PPO:
         """Everything of this side that a rollout bakes into its launches: the storage's slots, the sink's gamma (BY VALUE), the shadows."""
         key = id(self.storage), self.gamma, self.storage._obs_bf16 is not None
         # with value normalisation the stepwise rollout contains the denormalise launches (eps by value, the block by address); off: the key as ever
-        return key if self.value_normalizer is None else key + (self.value_normalizer.graph_key()["value_norm"],)
+        key = key if self.value_normalizer is None else key + (self.value_normalizer.graph_key()["value_norm"],)
+        # with exploration noise the rollout contains the table launch and its launches read the table's rows; off: the key as ever
+        return key if self._noise is None else key + (self._noise.graph_key(),)
 
     def after_rollout_replay(self, end_state):
         """Host-side book-keeping of one replayed rollout.  end_state: rollout_end_state() behind the captured pass."""

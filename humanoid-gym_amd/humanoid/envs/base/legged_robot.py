@@ -647,11 +647,13 @@ class LeggedRobot(BaseTask):
         if p.bf16_ahead:
             o.obs_bf16_ahead, o.ld_obs_bf16_ahead = C.c_void_p(at("obs_bf16", i + 1).data_ptr()), c["obs_bf16"].shape[-1]
         sh = net.shadow_struct(at("obs_bf16"), at("priv_bf16") if p.shadow_priv else None) if p.shadow_obs else None
-        rc = L.lib.hgym_rollout_step(C.byref(net.cfg), C.byref(net.struct), C.byref(self._ncfg), C.byref(self._sim_s), C.byref(self._st_s),
-                                     C.byref(o), C.byref(self._ro_prev[0]) if p.prev else None, L.fptr(at("obs")), L.fptr(at("priv")),
-                                     int(c["seed"]) & 0xFFFFFFFFFFFFFFFF, L.fptr(at("actions")), L.fptr(at("mu")), L.fptr(at("sigma")),
-                                     L.fptr(at("logp")), L.fptr(at("values")), C.c_void_p(self._buf.rollout_scratch.data_ptr()), p.parity,
-                                     None if sh is None else C.byref(sh), self._stream())
+        args = (C.byref(net.cfg), C.byref(net.struct), C.byref(self._ncfg), C.byref(self._sim_s), C.byref(self._st_s),
+                C.byref(o), C.byref(self._ro_prev[0]) if p.prev else None, L.fptr(at("obs")), L.fptr(at("priv")),
+                int(c["seed"]) & 0xFFFFFFFFFFFFFFFF, L.fptr(at("actions")), L.fptr(at("mu")), L.fptr(at("sigma")),
+                L.fptr(at("logp")), L.fptr(at("values")), C.c_void_p(self._buf.rollout_scratch.data_ptr()), p.parity,
+                None if sh is None else C.byref(sh), self._stream())
+        # cols["z"] (PPO.exploration_noise; absent or None: off): slot i's (N, 12) rows of the rollout's noise table replace the launch's own draw
+        rc = L.lib.hgym_rollout_step(*args) if c.get("z") is None else L.lib.hgym_rollout_step_z(*args, L.fptr(at("z")))
         if rc != 0:
             self._in_rollout = False      # the rollout cannot go on: nothing carried across its launches is left to protect
         L.check(rc, "hgym_rollout_step")

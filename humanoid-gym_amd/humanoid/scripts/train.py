@@ -49,6 +49,10 @@ section 33); checkpoints carry guidance_state_dict, so --resume needs no teacher
 
 HGYM_CRITIC_WARMUP=<n> sets `algorithm.critic_warmup_updates` the same way: the first n updates of the run move the value function alone
 (PPO.critic_warmup_updates), for a checkpoint whose critic was never trained; 0 or unset: off.
+
+HGYM_NOISE_COLOR=<beta> sets `algorithm.exploration_noise_cfg = {"kind": "colored", "beta": <beta>}` the same way, HGYM_NOISE_AR1=<rho> sets
+`{"kind": "ar1", "rho": <rho>}`: the action noise of a rollout is temporally correlated instead of white (PPO.exploration_noise, DESIGN.md
+section 35); 0.5 is the exponent "Colored Noise in PPO" recommends.  Both unset: off; both set: ValueError.
 """
 import os
 import sys
@@ -77,6 +81,8 @@ def guidance_cfg_from_env(environ):
 
 def train(args):
     guidance_cfg_from_env(os.environ)      # (a half-set pair is refused before anything is built)
+    from humanoid.algo.ppo.exploration_noise import config_from_env as noise_cfg_from_env
+    noise_cfg = noise_cfg_from_env(os.environ)      # (both filters at once likewise)
     rank, world = init_distributed(args)
     env, env_cfg = task_registry.make_env(name=args.task, args=args)
     if os.environ.get("HGYM_EXACT_RESUME", "0") == "1":
@@ -102,6 +108,8 @@ def train(args):
         task_registry.get_cfgs(args.task)[1].algorithm.value_normalization = True
     if int(os.environ.get("HGYM_CRITIC_WARMUP", "0") or 0) > 0:      # PPO.critic_warmup_updates: the first n updates move the critic alone
         task_registry.get_cfgs(args.task)[1].algorithm.critic_warmup_updates = int(os.environ["HGYM_CRITIC_WARMUP"])
+    if noise_cfg is not None:
+        task_registry.get_cfgs(args.task)[1].algorithm.exploration_noise_cfg = noise_cfg
     gc = guidance_cfg_from_env(os.environ)
     if gc is not None:
         task_registry.get_cfgs(args.task)[1].algorithm.guidance_cfg = gc

@@ -875,6 +875,23 @@ int32_t hgym_policy_act_fin(const HgymNetConfig* cfg, const HgymNet* net, int32_
                             const HgymEnvConfig* env_cfg, const HgymEnvState* env_st, const HgymEnvOut* env_out,
                             const HgymObsShadow* shadow, void* stream);
 
+/* Temporally correlated exploration noise (added within header v9, no layout change): the `z` tables of all T policy launches of a
+ * rollout in ONE launch ahead of it.  For env m, action j and t = 0 .. T-1
+ *     z[t][m][j] = carry[t] * state[m][j] + sum_{s = 0 .. t} filt[t * ld_filt + s] * w_s[m][j]
+ * where w_s[m][j] is, bit for bit, the standard normal hgym_policy_act (z = NULL, this seed) draws for (m, j) when *step_counter holds
+ * *step + s: the same key, the same counter words, slot 64 + j / 4, the same Box-Muller pairing.  fp32: the carry term first (+0 without
+ * one), then s ascending, every multiply and every add rounded on its own.  Only the lower triangle of filt is read.
+ * z (T, n, A) row-major: row t is the `z` argument of the policy launch of step *step + t (hgym_policy_act, hgym_policy_act_fin,
+ * hgym_rollout_step_z).  carry: T floats or NULL.  state (n, A): read, then overwritten with z[T-1] (the process continues across calls:
+ * AR(1) with filt[t][s] = sqrt(1 - r^2) r^(t-s), carry[t] = r^(t+1)); NULL allowed only with carry NULL, and then not written.
+ * step: a device int64, read by the launch (fixed arguments: capturable).  With filt the identity and no carry the table is the draws
+ * themselves.  Stores are 16 bytes wide where A % 4 == 0 and z is 16-byte aligned.
+ * Nothing launched and HGYM_E_SHAPE: T outside [1, HGYM_NOISE_MAX_STEPS], A outside [1, 12], n < 1, ld_filt < T.  HGYM_E_BADARG: a NULL
+ * filt, step or z; a carry with state NULL; a float pointer not 4-byte aligned, step not 8-byte.  HGYM_E_UNSUPPORTED: n >= 2^31. */
+#define HGYM_NOISE_MAX_STEPS 128
+int32_t hgym_policy_noise_table(int32_t T, int64_t n, int32_t A, const float* filt, int64_t ld_filt, const float* carry, float* state,
+                                uint64_t seed, const int64_t* step, float* z, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Fused rollout step: PPO.act + XBotLFreeEnv.step (synthetic-physics backend) + the previous step's finaliser in ONE launch
  * (algo/ppo/on_policy_runner.py:129-141 is the loop body this stands for: act -> env.step -> process_env_step).
@@ -911,6 +928,13 @@ int32_t hgym_rollout_step(const HgymNetConfig* cfg, const HgymNet* net, const Hg
                           const HgymEnvState* st, const HgymEnvOut* out, const HgymEnvOut* prev_out, const float* obs,
                           const float* priv, uint64_t seed, float* actions, float* mu, float* sigma, float* logp, float* values,
                           void* scratch, int32_t parity, const HgymObsShadow* shadow, void* stream);
+/* hgym_rollout_step with this step's normals handed in (added within header v9): z (num_envs, 12) fp32, 4-byte aligned -- a row of
+ * hgym_policy_noise_table's table -- replaces the actor epilogue's own Philox draw, as the `z` of hgym_policy_act does; `seed` and the
+ * scratch block's sampling step are then not used by the sampling.  The same kernels, the same launches.  z = NULL: hgym_rollout_step. */
+int32_t hgym_rollout_step_z(const HgymNetConfig* cfg, const HgymNet* net, const HgymEnvConfig* env_cfg, const HgymSimTensors* sim,
+                            const HgymEnvState* st, const HgymEnvOut* out, const HgymEnvOut* prev_out, const float* obs,
+                            const float* priv, uint64_t seed, float* actions, float* mu, float* sigma, float* logp, float* values,
+                            void* scratch, int32_t parity, const HgymObsShadow* shadow, void* stream, const float* z);
 int32_t hgym_rollout_end(const HgymEnvConfig* env_cfg, const HgymEnvState* st, const HgymEnvOut* last_out, void* scratch,
                          int32_t parity, void* stream);
 
